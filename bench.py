@@ -18,6 +18,9 @@ Prints ONE JSON line on rank 0 (contract in the task description) with `roofline
 HBM bound as BASELINE.json asks, plus the fp64-VALU figure that actually bounds it), `cpu_baseline`
 (the C/OpenMP oracle timed on this box's host cores on a bounded row sample) and, for sharded runs,
 `sharded` (per-rank partial-solve / velocity milliseconds, all-gather and reduce-scatter microseconds).
+
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy: K, grad_k, v and X_new on one GPU,
+the all-gathered X_new when sharded.  The inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -178,7 +181,32 @@ def parse_args(argv=None):
     ap.add_argument("--headline-only", action="store_true",
                     help="skip the other configurations and the eager-copy figure (clean per-kernel profiles)")
     ap.add_argument("--force-dist", action="store_true", help="use the sharded path even with one rank")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(the inputs are seeded, so two builds can be compared output for output)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outputs: dict, out_dir: str) -> None:
+    """Host copies of the last timed step's outputs as <name>.npy (float32 / float64, as computed)."""
+    import numpy as np
+
+    arrays = {}
+    for name, t in outputs.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: outputs of {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte dump limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -233,8 +261,10 @@ def main(argv=None, backend_cls=HipBackend, script=None) -> int:
         X = X0[r0:r1].to(dev).contiguous()
         score = score0[r0:r1].to(dev).contiguous()
 
+        # each step returns (new X, what a caller of the step receives): here this rank's rows of X
         def step(Xc):
-            return sharded.step(Xc, score)
+            Xn = sharded.step(Xc, score)
+            return Xn, {"X_new": Xn}
 
         def barrier():
             dist.barrier()
@@ -245,20 +275,20 @@ def main(argv=None, backend_cls=HipBackend, script=None) -> int:
 
         def step(Xc):
             K, gk = compute.gram_fwd_bwd(Xc, Xc, 1.0 / H, 0, y_is_x=True)
-            _, Xn = compute.svgd_phi(K, score, gk, X=Xc, lr=LR)
-            return Xn
+            v, Xn = compute.svgd_phi(K, score, gk, X=Xc, lr=LR)
+            return Xn, {"K": K, "grad_k": gk, "v": v, "X_new": Xn}
 
         def barrier():
             sync()
 
     for _ in range(args.warmup):
-        X = step(X)
+        X, _ = step(X)
     barrier()
 
     # ---- timed region: exactly `steps` iterations, inputs resident in HBM ------------------------
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        X = step(X)
+        X, last = step(X)
     barrier()
     elapsed = time.perf_counter() - t0
     if use_dist:
@@ -266,6 +296,15 @@ def main(argv=None, backend_cls=HipBackend, script=None) -> int:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert torch.isfinite(X).all()
+
+    # ---- the last timed step's outputs, before anything else runs (outside the timed region) ---------
+    if args.dump_outputs:
+        if use_dist:
+            from sigsvgd_amd.distributed import all_gather_rows
+
+            last = {"X_new": all_gather_rows(last["X_new"])}
+        if rank == 0:
+            dump_outputs(last, args.dump_outputs)
 
     # ---- sharded runs: where the step's time goes on every rank (outside the timed region) -------------
     shard_report = None

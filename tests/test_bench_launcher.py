@@ -60,6 +60,33 @@ def test_bench_reports_a_failing_rank():
     assert not [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs writes the all-gathered X after exactly warmup + steps iterations: the same number of unsharded
+    oracle iterations from the same seeded inputs gives the same particles"""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bench
+    import helpers
+    from bench_rehearsal import RehearsalBackend
+    from sigsvgd_amd.utils.synthetic import synthetic_inputs
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert _json_line(p.stdout)["steps"] == 3
+    assert sorted(os.listdir(tmp_path)) == ["X_new.npy"]
+    got = np.load(tmp_path / "X_new.npy")
+    X, score = synthetic_inputs(*RehearsalBackend.shape)
+    assert got.dtype == np.float32 and got.shape == tuple(X.shape)
+    for _ in range(1 + 3):
+        K, gk = helpers.gram_fwd_bwd(X, X, 1.0 / bench.H, 0)
+        X = helpers.svgd_phi(K, score, gk, X=X, lr=bench.LR)[1]
+    assert np.abs(got - X.numpy()).max() <= 1e-5 * np.abs(X.numpy()).max()
+
+
 def test_committed_counters_parse():
     """bench.py takes `roofline.traffic` / `valu_issue` from the committed rocprofv3 summaries, not from literals"""
     sys.path.insert(0, ROOT)
