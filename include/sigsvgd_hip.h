@@ -54,9 +54,13 @@
  *     reference's (plain |K - K_ref| / |K_ref|, no floor) over the committed rough-path cases and 18,000
  *     random soak cases; unflagged pairs of the calibration study are within 2.5e-6.  (The 8- / 16-channel
  *     kernels for T <= 64 have no exact pass: their cancelled pairs repeat the sweep in fp64 on fp32
- *     increments, enough in every case seen with d >= 5.)  Only K is repaired: the gradient of a flagged pair keeps
- *     the fp32 solution (its error is relative to the largest gradient entry of the launch and stayed
- *     below 5e-6 of it in every regime measured).  SIGSVGD_FLAG_FORCE_GENERIC returns 6e-8 anywhere.
+ *     increments; tests/test_gpu_precision.py::test_rough_wide_paths_default_dispatch holds d = 5 .. 16,
+ *     T = 32 .. 128, steps 0.2 / 0.5, h = 0.1 .. 1 to 1e-5 in every launch form.)  Only K is repaired: the
+ *     gradient of a flagged pair keeps the fp32 solution (its error is relative to the largest gradient entry
+ *     of the launch and stayed below 5e-6 of it in every regime measured).  Gram + gradient launches of paths
+ *     in ONE channel at dyadic order 0 run on the coverage kernel (fp64 sweeps): very smooth one-channel paths
+ *     (K = 1 + O(1e-4)) left the fp32 sweeps' gradient at up to 2.0e-5; now <= 4.2e-6
+ *     (test_smooth_one_channel_order0).  SIGSVGD_FLAG_FORCE_GENERIC returns 6e-8 anywhere.
  *   - results are bit-reproducible: every reduction over pairs runs in an order fixed by the launch
  *     geometry (no floating-point atomics), so two calls on the same inputs return the same bits.
  *     sigsvgd_vec_kernel_fused is reproducible when it is given its workspace (sigsvgd_vec_fused_workspace_bytes);

@@ -114,10 +114,25 @@ struct Range {
 };
 } // namespace
 
+// Gram + gradient of paths in ONE channel at dyadic order 0 runs on the coverage kernel with fp64 increments and sweeps (what
+// SIGSVGD_FLAG_FORCE_GENERIC does).  Very smooth one-channel paths (|step|^2 / h ~ 1e-5: K = 1 + O(1e-4)) left the gradient of
+// the fp32-sweep kernels at 1.2 .. 2.0e-5 of its largest entry (T = 20, 33: register-resident kernel; T = 128: quadrant
+// kernel), the coverage kernel at <= 4.2e-6 (tests/test_gpu_precision.py::test_smooth_one_channel_order0).  Forward-only
+// launches keep the fp32 route: K is within 1e-6 there.  With Y_IS_X every unordered pair is solved once at any pair count,
+// so K is mirrored bit for bit as on the fp32 route.  No reference caller is one-channel; the cost is DESIGN.md section 3.
+static bool one_channel_grad_to_generic(int T, int d, int n, int kind, unsigned flags, int want_grad)
+{
+    return want_grad && d == 1 && n == 0 && T >= 3 && T <= 128 && kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
+}
+
 static int dispatch(const GramProblem &p)
 {
     const int want_grad = p.gradX_out != nullptr;
-    (void)want_grad;
+    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && one_channel_grad_to_generic(p.T, p.d, p.n, p.kind, p.flags, want_grad)) {
+        GramProblem q = p;
+        q.flags |= SIGSVGD_FLAG_FORCE_GENERIC;
+        return generic_launch(q, true);
+    }
     if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && fast_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags))
         return fast_launch(p);
     // long paths (65 <= T <= 128): the quadrant kernel (stored forward solution, any roughness)
@@ -154,6 +169,17 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
     }
     // size for the kernel dispatch() picks: the same predicates on the same arguments
     const bool forced = (flags & SIGSVGD_FLAG_FORCE_GENERIC) != 0;
+    if (!forced && one_channel_grad_to_generic(T, d, dyadic_order, static_kind, flags, want_grad)) {
+        // (the same query sizes sigsvgd_gram_sym_partial, which stays on the fp32 kernels: enough for either)
+        size_t gb = 0, fb = 0;
+        int rc = generic_workspace_bytes(A, B, T, d, dyadic_order, want_grad, true, &gb, true);
+        if (rc) return rc;
+        rc = fast_supported(A, B, T, d, dyadic_order, static_kind, flags) ? fast_workspace_bytes(A, B, T, d, want_grad, flags, &fb)
+                                                                           : quad_workspace_bytes(A, B, T, d, want_grad, &fb);
+        if (rc) return rc;
+        *bytes = gb > fb ? gb : fb;
+        return SIGSVGD_OK;
+    }
     if (!forced && fast_supported(A, B, T, d, dyadic_order, static_kind, flags))
         return fast_workspace_bytes(A, B, T, d, want_grad, flags, bytes);
     if (!forced && quad_supported(A, B, T, d, dyadic_order, static_kind, flags))

@@ -500,10 +500,11 @@ __global__ void reduce_partials_kernel(const double *partials, const double *col
 namespace {
 // Y is X: each unordered pair once -- when there are enough pairs to fill the chip (below that the launch is latency-bound
 // and the second contraction pass of the symmetric solve only lengthens the critical path) and the per-pair slab of the
-// column-side gradients stays below 1 GiB (beyond that: ordered pairs, twice the solves, no slab)
-bool generic_solves_unordered(int A, int B, int T, int d, int want_grad, unsigned flags)
+// column-side gradients stays below 1 GiB (beyond that: ordered pairs, twice the solves, no slab).  `any_size`: at every pair
+// count -- the one-channel gradient launches the dispatch routes here must mirror K as the fp32-sweep kernels do
+bool generic_solves_unordered(int A, int B, int T, int d, int want_grad, unsigned flags, bool any_size = false)
 {
-    if (!(flags & SIGSVGD_FLAG_Y_IS_X) || A != B || (long long)A * B < 4096) return false;
+    if (!(flags & SIGSVGD_FLAG_Y_IS_X) || A != B || (!any_size && (long long)A * B < 4096)) return false;
     if (want_grad && (size_t)A * B * T * d * sizeof(double) > ((size_t)1 << 30)) return false;
     return true;
 }
@@ -574,7 +575,7 @@ namespace {
 inline size_t plan_bytes(const GenericPlan &pl) { return 512 + pl.partial_bytes + pl.col_bytes + pl.wsk_bytes; }
 }
 
-int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes)
+int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes, bool any_size)
 {
     // the query carries no Y_IS_X promise: size for whichever of the ordered / symmetric plans needs more (the symmetric
     // one uses shorter column chunks, i.e. more partial slabs)
@@ -582,7 +583,7 @@ int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bo
     int rc = make_plan(A, B, T, d, n, want_grad, pl, false, precise);
     if (rc) return rc;
     *bytes = plan_bytes(pl);
-    if (generic_solves_unordered(A, B, T, d, want_grad, SIGSVGD_FLAG_Y_IS_X)) {
+    if (generic_solves_unordered(A, B, T, d, want_grad, SIGSVGD_FLAG_Y_IS_X, any_size)) {
         rc = make_plan(A, B, T, d, n, want_grad, pl, true, precise);
         if (rc) return rc;
         if (plan_bytes(pl) > *bytes) *bytes = plan_bytes(pl);
@@ -631,10 +632,10 @@ hipError_t generic_dispatch(bool f64, bool naive, bool grad, bool big, const Gen
 }
 } // namespace
 
-int generic_launch(const GramProblem &p)
+int generic_launch(const GramProblem &p, bool any_size)
 {
     const int want_grad = p.gradX_out != nullptr;
-    const bool yx = generic_solves_unordered(p.A, p.B, p.T, p.d, want_grad, p.flags);
+    const bool yx = generic_solves_unordered(p.A, p.B, p.T, p.d, want_grad, p.flags, any_size);
     GenericPlan pl;
     int rc = make_plan(p.A, p.B, p.T, p.d, p.n, want_grad, pl, yx, (p.flags & SIGSVGD_FLAG_FORCE_GENERIC) != 0);
     if (rc) return rc;

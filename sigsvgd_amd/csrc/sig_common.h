@@ -197,8 +197,9 @@ struct GramProblem {
 };
 
 // generic (any T, n, d that fits LDS) -- gram_generic.hip
-int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes); // precise: FORCE_GENERIC
-int generic_launch(const GramProblem &p);
+// precise: FORCE_GENERIC; any_size: Y_IS_X launches solve each unordered pair once (mirrored K) whatever their pair count
+int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes, bool any_size = false);
+int generic_launch(const GramProblem &p, bool any_size = false);
 
 // fixed-order reduction of the gradient partial sums shared by the register-resident and the quadrant kernel -- gram_fast.hip
 // Which row tiles a launch owns and the order it enumerates them in (kq = 0 .. owned-1).  A full launch owns all of

@@ -168,3 +168,129 @@ def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
         assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
         K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0, n, static_kind=_lib.STATIC_LINEAR)
         assert torch.equal(K, K2) and torch.equal(g, g2)
+
+
+def _probe_paths(A, T, d, scale, h):
+    """the inputs of one row of profiles/r04_smooth_one_channel.txt: scripts/dev/smooth_one_channel.py drew every row from ONE
+    generator (seed 3) in the order of its loops, so a row's paths are replayed by drawing (and dropping) the rows before it"""
+    rng = np.random.default_rng(3)
+    for (a, t, dd, _n) in [(20, 64, 1, 0), (20, 33, 1, 0), (12, 128, 1, 0), (12, 100, 2, 0), (20, 33, 1, 1), (20, 17, 1, 2),
+                           (20, 64, 2, 0), (20, 5, 1, 4), (16, 9, 1, 3), (20, 20, 1, 0)]:
+        for (s, hh) in [(0.02, 10.0), (0.01, 10.0), (0.02, 4.0)]:
+            X = np.cumsum(s * rng.standard_normal((a, t, dd)), axis=1).astype(np.float32)
+            if (a, t, dd, _n, s, hh) == (A, T, d, 0, scale, h):
+                return X
+    raise ValueError("not a row of the probe")
+
+
+def _parity_all_forms(gpu, X, Y, h, seed, partial=False, ones=True):
+    """the launch forms of test_soak_regimes_default_dispatch on one input: Gram + gradient with a random grad_out (symmetric
+    on X, ordered on X against Y) and, with `ones`, with grad_out = None; forward only (both); with `partial` the sharded
+    symmetric solve over 2 ranks, folded.
+    Returns the errors by form; K per entry (_relK), the gradient over its largest entry (_rel)."""
+    from sigsvgd_amd import ops
+
+    A, B = X.shape[0], Y.shape[0]
+    rng = np.random.default_rng(seed)
+    go_s = rng.uniform(0.5, 1.5, (A, A)).astype(np.float32)
+    go_o = rng.uniform(0.5, 1.5, (A, B)).astype(np.float32)
+    Ks_ref, gs_ref = C.gram_fwd_bwd(X, X, h, 0, grad_out=go_s.astype(np.float64))
+    Ko_ref, go_ref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go_o.astype(np.float64))
+    Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
+    gsg, gog = torch.as_tensor(go_s, device=gpu), torch.as_tensor(go_o, device=gpu)
+    K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, grad_out=gsg, y_is_x=True)
+    Ko, go = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog)
+    Kf = ops.gram_fwd(Xg, Xg, 1.0 / h, y_is_x=True)
+    Kfo = ops.gram_fwd(Xg, Yg, 1.0 / h)
+    torch.cuda.synchronize()
+    err = {"sym K": _relK(K.cpu().numpy(), Ks_ref), "sym grad": _rel(g.cpu().numpy(), gs_ref),
+           "ordered K": _relK(Ko.cpu().numpy(), Ko_ref), "ordered grad": _rel(go.cpu().numpy(), go_ref),
+           "fwd sym K": _relK(Kf.cpu().numpy(), Ks_ref), "fwd ordered K": _relK(Kfo.cpu().numpy(), Ko_ref)}
+    if ones:  # grad_out = None: the gradient sums the partners with equal weights and can cancel far below the weighted one's
+        for name, Z, Zg, yx in (("ones sym", X, Xg, True), ("ones ordered", Y, Yg, False)):
+            K1_ref, g1_ref = C.gram_fwd_bwd(X, Z, h, 0)
+            K1, g1 = ops.gram_fwd_bwd(Xg, Zg, 1.0 / h, y_is_x=yx)
+            torch.cuda.synchronize()
+            err[name + " K"] = _relK(K1.cpu().numpy(), K1_ref)
+            err[name + " grad"] = _rel(g1.cpu().numpy(), g1_ref)
+    if partial:
+        Kp = torch.zeros(A, A, device=gpu)
+        gp = torch.zeros(X.shape, device=gpu, dtype=torch.float64)
+        for r in range(2):
+            k_r, g_r = ops.gram_sym_partial(Xg, 1.0 / h, r, 2, grad_out=gsg, fold=True)
+            Kp += k_r
+            gp += g_r
+        torch.cuda.synchronize()
+        err["partial K"] = _relK(Kp.cpu().numpy(), Ks_ref)
+        err["partial grad"] = _rel(gp.cpu().numpy(), gs_ref)
+    return err
+
+
+# (A, T, d, step, h): very smooth paths in one channel at dyadic order 0 -- |step|^2 / h ~ 1e-5 .. 4e-5, K = 1 + O(1e-4), the
+# gradient O(1e-4) of K.  The first three are the rows of profiles/r04_smooth_one_channel.txt beyond 1e-5 (33 and 20 points:
+# two pairs per wavefront on the register-resident kernel; 128 points: quadrant kernel), the others their neighbours that
+# were inside it (64 and 100 points in one channel, 33 points in two).
+SMOOTH_ONE_CHANNEL = [
+    (20, 33, 1, 0.01, 10.0),
+    (20, 20, 1, 0.02, 10.0),
+    (12, 128, 1, 0.01, 10.0),
+    (20, 64, 1, 0.01, 10.0),
+    (12, 100, 1, 0.01, 10.0),
+    (20, 33, 2, 0.01, 10.0),
+]
+
+
+@pytest.mark.parametrize("A,T,d,step,h,src", [c + ("probe",) for c in SMOOTH_ONE_CHANNEL[:4]]
+                         + [c + (seed,) for c in SMOOTH_ONE_CHANNEL for seed in (0, 1)])
+def test_smooth_one_channel_order0(gpu, A, T, d, step, h, src):
+    """K and the gradient of very smooth few-channel paths, every launch form, within 1e-5 ("very smooth
+    paths in one channel").  src "probe": the exact inputs of the r04 probe row (before the one-channel gradient launches went
+    to the coverage kernel: 1.97e-5, 1.20e-5, 1.24e-5 for the first three, all with grad_out = None); an int: a fixed seed."""
+    if src == "probe":
+        X = _probe_paths(A, T, d, step, h)
+    else:
+        X = _paths(A, T, d, 1000 * T + 10 * d + src, step)
+    Y = X.copy()  # the ordered launch: Y a separate tensor with X's values (the probe's form)
+    err = _parity_all_forms(gpu, X, Y, h, 7 + (0 if src == "probe" else src))
+    assert max(err.values()) < TOL, err
+
+
+@pytest.mark.parametrize("h", [0.1, 0.3, 1.0])
+@pytest.mark.parametrize("step", [0.2, 0.5])
+@pytest.mark.parametrize("T", [32, 64, 100, 128])
+@pytest.mark.parametrize("d", [5, 8, 9, 14, 16])
+def test_rough_wide_paths_default_dispatch(gpu, d, T, step, h):
+    """rough paths in 5 .. 16 channels on the default dispatch, every launch form: the ends of the 8-channel instantiations
+    (5, 8), the first 16-channel one (9), both sides of the quadrant kernel's ROWG split (14, 16); T = 32 / 64 on the
+    register-resident kernel (two pairs per wavefront at 32), T = 100 / 128 on the quadrant kernel.  These kernels flag no pair
+    for conditioning (the 8- and 16-channel register-resident instantiations have no exact pass at all, only the fp64 re-sweep
+    of a cancelled pair), so this is what holds them to 1e-5 where the discrete solution oscillates and K is large."""
+    A, B = 12, 9
+    X = _paths(A, T, d, 10000 + 100 * d + T, step)
+    Y = _paths(B, T, d, 20000 + 100 * d + T, step)
+    Kref = np.concatenate([C.gram_fwd_bwd(X, X, h, 0, want_grad=False)[0], C.gram_fwd_bwd(X, Y, h, 0, want_grad=False)[0]], 1)
+    if not np.isfinite(Kref).all() or np.abs(Kref).max() > 1e30:
+        pytest.skip("K beyond the fp32 range: no fp32 answer exists")
+    err = _parity_all_forms(gpu, X, Y, h, 11, partial=True, ones=False)
+    assert max(err.values()) < TOL, err
+
+
+@pytest.mark.parametrize("yx", [True, False])
+def test_third_caller_order3_coverage(gpu, yx):
+    """the reference's third caller (examples/test_optimise_arm_spline-with-path-signature.py upstream): [6, 100, 3] paths at
+    dyadic order 3, Gram + gradient -- a refined grid of 792 cells per side, beyond the band kernel: the coverage kernel"""
+    from sigsvgd_amd import ops
+
+    h = 1.0
+    X = _paths(6, 100, 3, 31, 0.05)
+    Y = X if yx else _paths(6, 100, 3, 32, 0.05)
+    go = np.random.default_rng(33).uniform(0.5, 1.5, (6, 6)).astype(np.float32)
+    Kref, gref = C.gram_fwd_bwd(X, Y, h, 3, grad_out=go.astype(np.float64))
+    Xg, gog = torch.as_tensor(X, device=gpu), torch.as_tensor(go, device=gpu)
+    Yg = Xg if yx else torch.as_tensor(Y, device=gpu)
+    K, g = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, 3, grad_out=gog, y_is_x=yx)
+    Kf = ops.gram_fwd(Xg, Yg, 1.0 / h, 3, y_is_x=yx)
+    torch.cuda.synchronize()
+    assert _relK(K.cpu().numpy(), Kref) < TOL
+    assert _relK(Kf.cpu().numpy(), Kref) < TOL
+    assert _rel(g.cpu().numpy(), gref) < TOL
