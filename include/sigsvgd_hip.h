@@ -121,8 +121,10 @@ int sigsvgd_abi_version(void);
 const char *sigsvgd_last_error(void);
 
 /* Bytes of scratch the two Gram entry points need for this problem.  Forward-only launches need some too
- * (accumulation buffers, scratch of the persistent grids), so always query; the size covers every value of
- * SIGSVGD_FLAG_Y_IS_X / SIGSVGD_FLAG_SYM for the given shape.  `static_kind` and `flags` are the ones of the launch
+ * (accumulation buffers, scratch of the persistent grids), so always query.  The size is the largest of the launches the
+ * arguments can reach: with SIGSVGD_FLAG_Y_IS_X and A == B the symmetric launch and (want_grad = 1) the symmetric partial
+ * solve of the shape; otherwise the ordered launch and, when A == B, the symmetric one -- either value of
+ * SIGSVGD_FLAG_SYM.  `static_kind` and `flags` are the ones of the launch
  * (ABI 9: the static kernel decides which solver runs -- the linear kernel always takes the coverage kernel --, so the
  * query needs it; ABI <= 8 sized for RBF whatever the launch asked for).
  * want_grad = 0 for sigsvgd_gram_fwd, 1 for sigsvgd_gram_fwd_bwd.  Returns 0 and sets *bytes. */
@@ -152,7 +154,7 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
  *                                column-side; rows the owned pairs do not touch get 0)
  * Summing the buffers over tile_offset = 0..tile_stride-1 gives sigsvgd_gram_fwd_bwd's outputs (K exactly, the
  * gradient up to the fp64 rounding of the sum).  Shapes of the register-resident and quadrant kernels
- * (dyadic_order 0, 3 <= T <= 128, d <= 16, RBF).
+ * (dyadic_order 0, 3 <= T <= 128, d <= 16, RBF, no SIGSVGD_FLAG_NAIVE_SOLVER / SIGSVGD_FLAG_FORCE_GENERIC).
  * `workspace` as sized by sigsvgd_gram_workspace_bytes(N, N, T, d, 0, static_kind, 1, SIGSVGD_FLAG_Y_IS_X). */
 int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h,
                              int static_kind, unsigned flags, int tile_offset, int tile_stride,

@@ -47,7 +47,7 @@ int signature_bwd_launch(const void *X, const void *gsig, int N, int L, int C, i
                          long long sigdim, hipStream_t stream);
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
-                        int n, int kind, const void *K_out)
+                        int n, int kind, unsigned flags, const void *K_out)
 {
     if (!X || !Y || !K_out) {
         set_error("null pointer argument");
@@ -71,6 +71,10 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
     }
     if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) {
         set_error("RBF static kernel needs inv_h > 0 (got %g)", inv_h);
+        return SIGSVGD_E_BADARG;
+    }
+    if ((flags & SIGSVGD_FLAG_SYM) && A != B) {
+        set_error("sym backward needs A == B");
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
@@ -114,36 +118,92 @@ struct Range {
 };
 } // namespace
 
+// ---- which kernel runs a Gram launch (the one place that combines the families' *_supported) ----------
+enum class GramRoute { Fast, Quad, Dyad, BandParallel, BandSerial, Generic, GenericPrecise, GenericOneChannel };
+
+// Band kernel schedule.  Band-parallel wins while its workgroups (one pair each) pass through the chip in a few rounds -- its
+// wavefronts idle BLAG (nb - 1) phases of every sweep, which other workgroups on the CU fill, but the sum of a pair's wavefront
+// time is nb / (1 + BLAG (nb - 1) BGS / (P + 63)) times the serial schedule's.  Measured (Gram + gradient, symmetric, ms,
+// parallel / serial): 10 points order 4 (3 bands, 1,280 resident workgroups) -- N = 50 / 70 / 100 / 150: 0.105 / 0.189 /
+// 0.364 / 0.78 against 0.125 / 0.205 / 0.424 / 0.737; 30 points order 3 (4 bands, 1,024) -- N = 35 / 60 / 100: 0.138 / 0.317 /
+// 0.832 against 0.239 / 0.300 / 0.835.  Rule: at most five rounds with three bands, one and a half with four.  With two bands
+// (65 .. 128 cells) it beats the refined-grid kernel of gram_dyad.hip at every size measured (N = 64 .. 400: 20 points order 2
+// 0.156 / 0.423 / 1.52 against 0.170 / 0.477 / 1.78; 5 points order 5 0.80 / 3.13 against 0.92 / 3.52): always.
+// SIGSVGD_BAND_MODE=serial|parallel (read per launch) overrides it: the tests drive both schedules over the same shapes (serial
+// sends grids of up to 128 cells back to gram_dyad.hip).
+static bool band_parallel(int A, int B, int T, int d, int n, bool sym)
+{
+    const char *e = getenv("SIGSVGD_BAND_MODE");
+    if (e && e[0] == 's') return false;
+    if (e && e[0] == 'p') return true;
+    const long long pairs = sym ? (long long)A * (A + 1) / 2 : (long long)A * B;
+    const int nb = (((T - 1) << n) + 63) >> 6;
+    if (nb <= 2) return true;
+    return 2 * pairs <= (nb >= 4 ? 3ll : 10ll) * device_cu_count() * band_wg_per_cu(T, d, n, false);
+}
+
+// The kernel of a launch: FORCE_GENERIC first, then the first family in the order below whose shapes hold it.  The fp32-sweep
+// families (everything but the coverage kernel) take the RBF static kernel with the second-order solver only.
 // Gram + gradient of paths in ONE channel at dyadic order 0 runs on the coverage kernel with fp64 increments and sweeps (what
 // SIGSVGD_FLAG_FORCE_GENERIC does).  Very smooth one-channel paths (|step|^2 / h ~ 1e-5: K = 1 + O(1e-4)) left the gradient of
 // the fp32-sweep kernels at 1.2 .. 2.0e-5 of its largest entry (T = 20, 33: register-resident kernel; T = 128: quadrant
 // kernel), the coverage kernel at <= 4.2e-6 (tests/test_gpu_precision.py::test_smooth_one_channel_order0).  Forward-only
 // launches keep the fp32 route: K is within 1e-6 there.  With Y_IS_X every unordered pair is solved once at any pair count,
 // so K is mirrored bit for bit as on the fp32 route.  No reference caller is one-channel; the cost is DESIGN.md section 3.
-static bool one_channel_grad_to_generic(int T, int d, int n, int kind, unsigned flags, int want_grad)
+// Refined grids of 64 .. 128 cells (gram_dyad.hip's shapes) go to the band-parallel schedule from two bands on (65 cells and
+// more, r >= 4) and, for one-channel paths, at 64 cells too: their very smooth regime wants the two-float add in both sweeps.
+// `partial`: the symmetric partial solve, which has the register-resident and quadrant kernels only (any other route: it does
+// not take the launch) and keeps them for one-channel paths.
+static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigned flags, int want_grad, bool partial = false)
 {
-    return want_grad && d == 1 && n == 0 && T >= 3 && T <= 128 && kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
+    const bool fp32 = kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
+    if (flags & SIGSVGD_FLAG_FORCE_GENERIC) return GramRoute::GenericPrecise;
+    if (!partial && fp32 && want_grad && d == 1 && n == 0 && T >= 3 && T <= 128) return GramRoute::GenericOneChannel;
+    if (fp32 && fast_supported(T, d, n)) return GramRoute::Fast;
+    if (fp32 && quad_supported(T, d, n)) return GramRoute::Quad;
+    if (!fp32 || partial) return GramRoute::Generic;
+    const bool sym = (flags & SIGSVGD_FLAG_Y_IS_X) && A == B;
+    if (dyad_supported(T, d, n)) {
+        const bool band = band_supported(T, d, n) && (((T - 1) << n) > 64 || d == 1) && band_parallel(A, B, T, d, n, sym);
+        return band ? GramRoute::BandParallel : GramRoute::Dyad;
+    }
+    if (band_supported(T, d, n)) return band_parallel(A, B, T, d, n, sym) ? GramRoute::BandParallel : GramRoute::BandSerial;
+    return GramRoute::Generic;
+}
+static GramRoute gram_route(const GramProblem &p, bool partial = false)
+{
+    return gram_route(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags, p.gradX_out != nullptr, partial);
+}
+
+// the workspace plan of a launch on route r; sym: the Y_IS_X orientation
+static int route_plan(GramRoute r, int A, int B, int T, int d, int n, int want_grad, bool sym, WsPlan &w)
+{
+    switch (r) {
+    case GramRoute::Fast: w = fast_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
+    case GramRoute::Quad: w = quad_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
+    case GramRoute::Dyad: w = dyad_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
+    case GramRoute::BandParallel: w = band_plan(A, B, T, d, n, want_grad, sym, false); return SIGSVGD_OK;
+    case GramRoute::BandSerial: w = band_plan(A, B, T, d, n, want_grad, sym, true); return SIGSVGD_OK;
+    case GramRoute::Generic: return generic_plan(A, B, T, d, n, want_grad, sym, false, false, w);
+    case GramRoute::GenericPrecise: return generic_plan(A, B, T, d, n, want_grad, sym, true, false, w);
+    case GramRoute::GenericOneChannel: return generic_plan(A, B, T, d, n, want_grad, sym, true, true, w);
+    }
+    return SIGSVGD_E_BADARG;
 }
 
 static int dispatch(const GramProblem &p)
 {
-    const int want_grad = p.gradX_out != nullptr;
-    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && one_channel_grad_to_generic(p.T, p.d, p.n, p.kind, p.flags, want_grad)) {
-        GramProblem q = p;
-        q.flags |= SIGSVGD_FLAG_FORCE_GENERIC;
-        return generic_launch(q, true);
+    switch (gram_route(p)) {
+    case GramRoute::Fast: return fast_launch(p);
+    case GramRoute::Quad: return quad_launch(p);
+    case GramRoute::Dyad: return dyad_launch(p);
+    case GramRoute::BandParallel: return band_launch(p, false);
+    case GramRoute::BandSerial: return band_launch(p, true);
+    case GramRoute::Generic: return generic_launch(p, false, false);
+    case GramRoute::GenericPrecise: return generic_launch(p, true, false);
+    case GramRoute::GenericOneChannel: return generic_launch(p, true, true);
     }
-    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && fast_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags))
-        return fast_launch(p);
-    // long paths (65 <= T <= 128): the quadrant kernel (stored forward solution, any roughness)
-    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && quad_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags))
-        return quad_launch(p);
-    // short paths with dyadic refinement whose refined grid has 64 .. 128 cells per side (the reference's own call shapes)
-    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && dyad_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags))
-        return band_takes_refined(p) ? band_launch(p) : dyad_launch(p); // (small launches of 65 .. 128 cells: one wavefront per band)
-    if (!(p.flags & SIGSVGD_FLAG_FORCE_GENERIC) && band_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags))
-        return band_launch(p);
-    return generic_launch(p);
+    return SIGSVGD_E_BADARG;
 }
 
 } // namespace sigsvgd
@@ -167,41 +227,33 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
         set_error("bad static kernel kind %d", static_kind);
         return SIGSVGD_E_BADARG;
     }
-    // size for the kernel dispatch() picks: the same predicates on the same arguments
-    const bool forced = (flags & SIGSVGD_FLAG_FORCE_GENERIC) != 0;
-    if (!forced && one_channel_grad_to_generic(T, d, dyadic_order, static_kind, flags, want_grad)) {
-        // (the same query sizes sigsvgd_gram_sym_partial, which stays on the fp32 kernels: enough for either)
-        size_t gb = 0, fb = 0;
-        int rc = generic_workspace_bytes(A, B, T, d, dyadic_order, want_grad, true, &gb, true);
-        if (rc) return rc;
-        rc = fast_supported(A, B, T, d, dyadic_order, static_kind, flags) ? fast_workspace_bytes(A, B, T, d, want_grad, flags, &fb)
-                                                                           : quad_workspace_bytes(A, B, T, d, want_grad, &fb);
-        if (rc) return rc;
-        *bytes = gb > fb ? gb : fb;
-        return SIGSVGD_OK;
-    }
-    if (!forced && fast_supported(A, B, T, d, dyadic_order, static_kind, flags))
-        return fast_workspace_bytes(A, B, T, d, want_grad, flags, bytes);
-    if (!forced && quad_supported(A, B, T, d, dyadic_order, static_kind, flags))
-        return quad_workspace_bytes(A, B, T, d, want_grad, bytes);
-    if (!forced && dyad_supported(A, B, T, d, dyadic_order, static_kind, flags)) {
-        const int rc = dyad_workspace_bytes(A, B, T, d, want_grad, bytes);
-        if (rc == SIGSVGD_OK && ((T - 1) << dyadic_order) >= 64 && dyadic_order >= 2) { // either kernel may take the launch
-            const size_t pb = band_refined_workspace_bytes(A, B, T, d, dyadic_order, want_grad, flags);
-            if (pb > *bytes) *bytes = pb;
-        }
+    // The largest plan of the launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B
+    // the symmetric launch and -- gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch
+    // and, when A == B, the symmetric one.
+    size_t most = 0;
+    auto cover = [&](bool sym, bool partial) {
+        const unsigned f = sym ? flags | SIGSVGD_FLAG_Y_IS_X : flags & ~SIGSVGD_FLAG_Y_IS_X;
+        const GramRoute r = gram_route(A, B, T, d, dyadic_order, static_kind, f, want_grad, partial);
+        if (partial && r != GramRoute::Fast && r != GramRoute::Quad) return (int)SIGSVGD_OK; // (not a partial-solve shape)
+        WsPlan w;
+        const int rc = route_plan(r, A, B, T, d, dyadic_order, want_grad, sym, w);
+        if (w.total() > most) most = w.total();
         return rc;
-    }
-    if (!forced && band_supported(A, B, T, d, dyadic_order, static_kind, flags))
-        return band_workspace_bytes(A, B, T, d, dyadic_order, want_grad, flags, bytes);
-    return generic_workspace_bytes(A, B, T, d, dyadic_order, want_grad, forced, bytes);
+    };
+    const bool yx = (flags & SIGSVGD_FLAG_Y_IS_X) && A == B;
+    int rc = cover(yx, false);
+    if (!rc && !yx && A == B) rc = cover(true, false);
+    if (!rc && yx && want_grad) rc = cover(true, true);
+    if (rc) return rc;
+    *bytes = most;
+    return SIGSVGD_OK;
 }
 
 int sigsvgd_gram_fwd(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                      int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
                      size_t workspace_bytes, void *stream)
 {
-    int rc = check_common(X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, K_out);
+    int rc = check_common(X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
     if (rc) return rc;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr,
                   K_out, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
@@ -213,7 +265,7 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
                          int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                          void *gradX_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_common(X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, K_out);
+    int rc = check_common(X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
     if (rc) return rc;
     if (!gradX_out) {
         set_error("gradX_out == NULL (use sigsvgd_gram_fwd for forward only)");
@@ -234,7 +286,7 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
                              void *K_partial, double *grad_partial, void *workspace, size_t workspace_bytes,
                              void *stream)
 {
-    int rc = check_common(X, X, N, N, T, d, dtype, inv_h, 0, static_kind, K_partial);
+    int rc = check_common(X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags, K_partial);
     if (rc) return rc;
     if (!grad_partial) {
         set_error("grad_partial == NULL");
@@ -242,17 +294,28 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
     }
     GramProblem p{X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags | SIGSVGD_FLAG_Y_IS_X, grad_out,
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const GramRoute r = gram_route(p, true);
+    if (r != GramRoute::Fast && r != GramRoute::Quad) {
+        set_error("sym_partial: shape/kernel outside the register-resident and quadrant kernels (need 3<=T<=128, d<=16, RBF)");
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
+        set_error("sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
+        return SIGSVGD_E_BADARG;
+    }
     Range range("sigsvgd_gram_sym_partial");
-    if (!fast_supported(N, N, T, d, 0, static_kind, flags) && quad_supported(N, N, T, d, 0, static_kind, flags))
-        return quad_sym_partial(p, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0, grad_partial);
-    return fast_sym_partial(p, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0, grad_partial);
+    const bool fold = (flags & SIGSVGD_FLAG_FOLD_TILES) != 0;
+    return r == GramRoute::Fast ? fast_sym_partial(p, tile_offset, tile_stride, fold, grad_partial)
+                                : quad_sym_partial(p, tile_offset, tile_stride, fold, grad_partial);
 }
 
 int sigsvgd_gram_sym_tile_rows(int T, int d)
 {
-    if (fast_supported(1, 1, T, d, 0, SIGSVGD_STATIC_RBF, 0)) return sym_tile_rows_fast(T, d);
-    if (quad_supported(1, 1, T, d, 0, SIGSVGD_STATIC_RBF, 0)) return 8;
-    return 0;
+    switch (gram_route(1, 1, T, d, 0, SIGSVGD_STATIC_RBF, SIGSVGD_FLAG_Y_IS_X, 1, true)) {
+    case GramRoute::Fast: return sym_tile_rows_fast(T, d);
+    case GramRoute::Quad: return 8;
+    default: return 0;
+    }
 }
 
 int sigsvgd_svgd_phi(const float *K, const float *score, const float *grad_k, const float *mask, int N, int D,

@@ -681,20 +681,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
 
 } // namespace
 
-bool band_supported(int A, int B, int T, int d, int n, int kind, unsigned flags)
+bool band_supported(int T, int d, int n)
 {
-    (void)A; (void)B;
-    if (n < 1 || n > 7 || T < 3 || T > BTMAX || d > 16) return false;
+    if (n < 2 || n > 7 || T < 3 || T > BTMAX || d > 16) return false;
     const int P = (T - 1) << n;
-    if (P <= 128 || P > BPMAX) return false; // (so r = P / (T - 1) >= 8: the kernels' unrolled groups rely on it)
-    if (kind != SIGSVGD_STATIC_RBF) return false;
-    if (flags & SIGSVGD_FLAG_NAIVE_SOLVER) return false;
-    return true;
+    return P >= 64 && P <= BPMAX; // (so r = P / (T - 1) >= 4: the kernels' unrolled groups rely on it)
 }
 
 namespace {
-inline size_t band_flag_bytes(int A, int B) { return (((size_t)A * B + 255) & ~(size_t)255) + generic_repair_bytes(); }
-
 // pairs per workgroup of the serial schedule: eight (two wavefronts per SIMD) where LDS holds them
 inline int band_serial_slots(int T, int d, int n)
 {
@@ -703,8 +697,10 @@ inline int band_serial_slots(int T, int d, int n)
     const int fit = (158 * 1024 - one.pair0) / one.per_pair;
     return fit >= 8 ? 8 : (fit < 1 ? 1 : fit);
 }
+} // namespace
+
 // workgroups a CU holds: by LDS (160 KB a CU) and by wavefronts (every instantiation fits four per SIMD: <= 128 registers)
-inline int band_wg_per_cu(int T, int d, int n, bool serial)
+int band_wg_per_cu(int T, int d, int n, bool serial)
 {
     const int P = (T - 1) << n, nb = (P + 63) >> 6, dpad = d <= 8 ? 8 : 16;
     const int slots = serial ? band_serial_slots(T, d, n) : 0;
@@ -714,6 +710,8 @@ inline int band_wg_per_cu(int T, int d, int n, bool serial)
     const int k = by_lds < by_waves ? by_lds : by_waves;
     return k < 1 ? 1 : k;
 }
+
+namespace {
 inline GradGeom band_geometry(int A, int B, int T, int d, int n, bool sym, bool serial)
 {
     return grad_geometry(A, B, T * d, sym, 0, 1, false, serial ? band_serial_slots(T, d, n) : BPP,
@@ -725,59 +723,27 @@ inline size_t band_wsk_per_pair(int T, int n)
     const size_t rows = (size_t)((P + 63 + BGS - 1) / BGS) * BGS; // whole phases per band
     return (size_t)((P + 63) >> 6) * rows * 64 + 32 * 64; // floats (+ 32 rows in front: the ring's loads need no clamp)
 }
-// Which schedule a launch takes.  Band-parallel wins while its workgroups (one pair each) pass through the chip in a few
-// rounds -- its wavefronts idle BLAG (nb - 1) phases of every sweep, which other workgroups on the CU fill, but the sum of a
-// pair's wavefront time is nb / (1 + BLAG (nb - 1) BGS / (P + 63)) times the serial schedule's.  Measured (Gram + gradient,
-// symmetric, ms, parallel / serial): 10 points order 4 (3 bands, 1,280 resident workgroups) -- N = 50 / 70 / 100 / 150: 0.105 /
-// 0.189 / 0.364 / 0.78 against 0.125 / 0.205 / 0.424 / 0.737; 30 points order 3 (4 bands, 1,024) -- N = 35 / 60 / 100: 0.138 /
-// 0.317 / 0.832 against 0.239 / 0.300 / 0.835.  Rule: at most five rounds with three bands, one and a half with four.  With
-// two bands (65 .. 128 cells) it beats the refined-grid kernel of gram_dyad.hip at every size measured (N = 64 .. 400: 20 points
-// order 2 0.156 / 0.423 / 1.52 against 0.170 / 0.477 / 1.78; 5 points order 5 0.80 / 3.13 against 0.92 / 3.52): always.
-// SIGSVGD_BAND_MODE=serial|parallel (read per launch) overrides it: the tests drive both schedules over the same shapes.
-inline bool band_rule_parallel(int A, int B, int T, int d, int n, bool sym)
-{
-    const char *e = getenv("SIGSVGD_BAND_MODE");
-    if (e && e[0] == 's') return false;
-    if (e && e[0] == 'p') return true;
-    const long long pairs = sym ? (long long)A * (A + 1) / 2 : (long long)A * B;
-    const int nb = (((T - 1) << n) + 63) >> 6;
-    if (nb <= 2) return true;
-    return 2 * pairs <= (nb >= 4 ? 3ll : 10ll) * device_cu_count() * band_wg_per_cu(T, d, n, false);
-}
-inline bool band_use_parallel(const GramProblem &p, bool sym) { return band_rule_parallel(p.A, p.B, p.T, p.d, p.n, sym); }
-// (the serial schedule takes grids of 129 .. 256 cells only: smaller ones that are not band-parallel stay on gram_dyad.hip)
-inline bool band_is_serial(int A, int B, int T, int d, int n, bool sym)
-{
-    return ((T - 1) << n) > 128 && !band_rule_parallel(A, B, T, d, n, sym);
-}
 // forward-solution scratch: one block per pair a launch of `grid` workgroups has in flight
 inline size_t band_wsk_bytes(int grid, int T, int d, int n, bool serial)
 {
     const size_t pairs = (size_t)(grid > 0 ? grid : 1) * (serial ? band_serial_slots(T, d, n) : BPP);
     return ((pairs * band_wsk_per_pair(T, n) * sizeof(float)) + 255) & ~(size_t)255;
 }
-// bytes a launch of this shape and orientation needs, on the schedule the launcher will pick for it
-inline size_t band_need_bytes(int A, int B, int T, int d, int n, int want_grad, bool sym)
-{
-    if (!want_grad) return band_flag_bytes(A, B) + 512;
-    const bool serial = band_is_serial(A, B, T, d, n, sym);
-    const GradGeom g = band_geometry(A, B, T, d, n, sym, serial);
-    return g.rseg_bytes + g.cslab_bytes + band_wsk_bytes(g.grid, T, d, n, serial) + band_flag_bytes(A, B) + 1024;
-}
 } // namespace
 
-int band_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, unsigned flags, size_t *bytes)
+// every launch: [A][B] bytes of cancellation flags for the fp64 pass; gradient launches behind them: [row segments][column
+// slab][forward-solution scratch of the pairs in flight]
+WsPlan band_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, bool serial)
 {
-    // a query with SIGSVGD_FLAG_Y_IS_X is the symmetric launch (half the pairs: often the band-parallel schedule, whose
-    // scratch is a third of the serial one's); without the flag it covers both orientations
-    const size_t yb = A == B ? band_need_bytes(A, B, T, d, n, want_grad, true) : 0;
-    if ((flags & SIGSVGD_FLAG_Y_IS_X) && A == B) {
-        *bytes = yb;
-        return SIGSVGD_OK;
+    WsPlan w;
+    w.g = band_geometry(A, B, T, d, n, sym, serial);
+    w.kflag = w.take(flag_area_bytes(A, B));
+    if (want_grad) {
+        w.rseg = w.take(w.g.rseg_bytes);
+        w.cslab = w.take(w.g.cslab_bytes);
+        w.wsk = w.take(band_wsk_bytes(w.g.grid, T, d, n, serial));
     }
-    const size_t ob = band_need_bytes(A, B, T, d, n, want_grad, false);
-    *bytes = ob > yb ? ob : yb;
-    return SIGSVGD_OK;
+    return w;
 }
 
 namespace {
@@ -842,33 +808,18 @@ int band_launch_variant(const GramProblem &p, BandArgs &a, const GradGeom &g, bo
 }
 } // namespace
 
-// Refined grids of 65 .. 128 cells per side (two bands) with r >= 4 -- BASELINE C1, the planning script's shape: the
-// band-parallel schedule takes them from the refined-grid kernel of gram_dyad.hip (which keeps grids of exactly 64 cells and
-// dyadic order 1; SIGSVGD_BAND_MODE=serial sends them back to it: the tests compare the two).
-bool band_takes_refined(const GramProblem &p)
-{
-    if (p.n < 2 || p.n > 7 || p.T < 3 || p.T > BTMAX || p.d > 16) return false;
-    const int P = (p.T - 1) << p.n;
-    if (P < 64 || P > 128 || (P == 64 && p.d != 1)) return false; // (64 cells, one band: only for the one-channel launches, whose
-                                                                      //  very smooth regime wants the two-float add in both sweeps)
-    if (p.kind != SIGSVGD_STATIC_RBF || (p.flags & (SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_FORCE_GENERIC))) return false;
-    return band_use_parallel(p, (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B);
-}
-size_t band_refined_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, unsigned flags)
-{
-    size_t bytes = 0;
-    (void)band_workspace_bytes(A, B, T, d, n, want_grad, flags, &bytes);
-    return bytes;
-}
-
-int band_launch(const GramProblem &p)
+int band_launch(const GramProblem &p, bool serial)
 {
     const bool grad = p.gradX_out != nullptr;
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B;
-    // (grids of up to 128 cells come here for the band-parallel schedule only: band_takes_refined)
-    const bool serial = band_is_serial(p.A, p.B, p.T, p.d, p.n, sym);
+    const WsPlan w = band_plan(p.A, p.B, p.T, p.d, p.n, grad, sym, serial);
+    unsigned char *base = nullptr;
+    int rc = ws_base(p, w, "band", base);
+    if (rc) return rc;
     BandArgs a;
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out; a.rseg = nullptr; a.cslab = nullptr; a.wsk = nullptr;
+    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
+    a.kflag = ws_at<unsigned char>(base, w.kflag); a.rseg = ws_at<double>(base, w.rseg); a.cslab = ws_at<float>(base, w.cslab);
+    a.wsk = ws_at<float>(base, w.wsk);
     a.wsk_per_wave = band_wsk_per_pair(p.T, p.n);
     a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.n = p.n;
     a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
@@ -878,25 +829,7 @@ int band_launch(const GramProblem &p)
         a.comprev = rev ? 1 : 0;
     }
     a.nitems = 0;
-    if (a.symw && p.A != p.B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
-    const GradGeom g = band_geometry(p.A, p.B, p.T, p.d, p.n, sym, serial);
-    const size_t slabs = grad ? (g.rseg_bytes + g.cslab_bytes + 255) & ~(size_t)255 : 0;
-    const size_t need = band_flag_bytes(p.A, p.B) + slabs + (grad ? band_wsk_bytes(g.grid, p.T, p.d, p.n, serial) : 0) + 256;
-    if (!p.ws || p.ws_bytes < need) {
-        set_error("band: workspace %zu B < required %zu B", p.ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-    a.kflag = base;
-    base += band_flag_bytes(p.A, p.B);
-    if (grad) {
-        a.rseg = reinterpret_cast<double *>(base);
-        a.cslab = sym ? reinterpret_cast<float *>(base + g.rseg_bytes) : nullptr;
-        a.wsk = reinterpret_cast<float *>(base + slabs);
-    }
+    const GradGeom &g = w.g;
 #ifdef SIGSVGD_PHASE_STAMPS
     {
         static unsigned long long *dbg = nullptr;
@@ -905,7 +838,6 @@ int band_launch(const GramProblem &p)
         a.stamps = dbg;
     }
 #endif
-    int rc;
     if (serial)
         rc = p.d <= 8 ? band_launch_variant<8, true>(p, a, g, grad, sym) : band_launch_variant<16, true>(p, a, g, grad, sym);
     else
@@ -926,10 +858,7 @@ int band_launch(const GramProblem &p)
         fprintf(stderr, "total %.3e wave-cycles\n", tot);
     }
 #endif
-    // fp64 pass of the coverage kernel over the flagged pairs (a few microseconds when there are none)
-    rc = generic_repair_launch(p, a.kflag, nullptr, sym, g.tm, g.NW);
-    if (rc || !grad) return rc;
-    return grad_reduce_launch(g, a.rseg, a.cslab, p.gradX_out, p.dtype == SIGSVGD_F64, p.A, p.B, p.T * p.d, sym, p.stream);
+    return finish_launch(p, w, base, sym, g.tm, g.NW, p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 } // namespace sigsvgd

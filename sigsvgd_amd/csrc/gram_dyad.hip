@@ -487,48 +487,29 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
     } // row tiles of the range
 }
 
-bool dyad_supported(int A, int B, int T, int d, int n, int kind, unsigned flags)
+bool dyad_supported(int T, int d, int n)
 {
-    (void)A; (void)B;
     if (n < 1 || n > 6 || T < 3 || T > DTMAX || d > 16) return false;
     const int P = (T - 1) << n;
-    if (P < 64 || P > 128) return false;
-    if (kind != SIGSVGD_STATIC_RBF) return false;
-    if (flags & SIGSVGD_FLAG_NAIVE_SOLVER) return false;
-    return true;
+    return P >= 64 && P <= 128;
 }
 
-namespace {
-// small launches: every 4-row workgroup gets a CU of its own (measured, Gram + gradient, symmetric: N=16 T=20 order 2
+// every launch: [A][B] bytes of cancellation flags for the fp64 pass; gradient launches behind them: [row segments][column slab].
+// Small launches: every 4-row workgroup gets a CU of its own (measured, Gram + gradient, symmetric: N=16 T=20 order 2
 // 0.086 -> 0.071 ms, N=30 T=5 order 5 0.091 -> 0.076; with two such workgroups per CU the 8-row form is faster again:
 // N=64 T=20 0.165 against 0.257 ms -- half the rows per staged column trajectory)
-inline int dyad_nw(int A, int B, bool sym)
+WsPlan dyad_plan(int A, int B, int T, int d, int want_grad, bool sym)
 {
+    WsPlan w;
     const long long pairs = sym ? (long long)A * (A + 1) / 2 : (long long)A * B;
-    return pairs <= 4ll * device_cu_count() ? 4 : 8;
-}
-inline GradGeom dyad_geometry(int A, int B, int T, int d, bool sym, int nw)
-{
-    return grad_geometry(A, B, T * d, sym, 0, 1, false, nw, (long long)device_cu_count());
-}
-} // namespace
-
-namespace {
-inline size_t dyad_flag_bytes(int A, int B) { return (((size_t)A * B + 255) & ~(size_t)255) + generic_repair_bytes(); }
-} // namespace
-
-int dyad_workspace_bytes(int A, int B, int T, int d, int want_grad, size_t *bytes)
-{
-    *bytes = dyad_flag_bytes(A, B) + 512;
-    if (!want_grad) return SIGSVGD_OK;
-    const GradGeom o = dyad_geometry(A, B, T, d, false, dyad_nw(A, B, false));
-    size_t need = o.rseg_bytes;
-    if (A == B) {
-        const GradGeom y = dyad_geometry(A, B, T, d, true, dyad_nw(A, B, true));
-        if (y.rseg_bytes + y.cslab_bytes > need) need = y.rseg_bytes + y.cslab_bytes;
+    const int nw = pairs <= 4ll * device_cu_count() ? 4 : 8;
+    w.g = grad_geometry(A, B, T * d, sym, 0, 1, false, nw, (long long)device_cu_count());
+    w.kflag = w.take(flag_area_bytes(A, B));
+    if (want_grad) {
+        w.rseg = w.take(w.g.rseg_bytes);
+        w.cslab = w.take(w.g.cslab_bytes);
     }
-    *bytes = need + dyad_flag_bytes(A, B) + 512;
-    return SIGSVGD_OK;
+    return w;
 }
 
 namespace {
@@ -561,39 +542,23 @@ int dyad_launch(const GramProblem &p)
 {
     const bool grad = p.gradX_out != nullptr;
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B;
+    const WsPlan w = dyad_plan(p.A, p.B, p.T, p.d, grad, sym);
+    unsigned char *base = nullptr;
+    int rc = ws_base(p, w, "dyad", base);
+    if (rc) return rc;
     DyadArgs a;
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out; a.rseg = nullptr; a.cslab = nullptr;
+    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
+    a.kflag = ws_at<unsigned char>(base, w.kflag); a.rseg = ws_at<double>(base, w.rseg); a.cslab = ws_at<float>(base, w.cslab);
     a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.n = p.n;
     a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
     a.nitems = 0;
-    if (a.symw && p.A != p.B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
-    const int nw = dyad_nw(p.A, p.B, sym);
-    const GradGeom g = dyad_geometry(p.A, p.B, p.T, p.d, sym, nw);
-    const size_t need = dyad_flag_bytes(p.A, p.B) + (grad ? g.rseg_bytes + g.cslab_bytes : 0) + 256;
-    if (!p.ws || p.ws_bytes < need) {
-        set_error("dyad: workspace %zu B < required %zu B", p.ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-    a.kflag = base;
-    base += dyad_flag_bytes(p.A, p.B);
-    if (grad) {
-        a.rseg = reinterpret_cast<double *>(base);
-        a.cslab = sym ? reinterpret_cast<float *>(base + g.rseg_bytes) : nullptr;
-    }
-    int rc;
-    if (nw == 4)
+    const GradGeom &g = w.g;
+    if (g.NW == 4)
         rc = p.d <= 8 ? dyad_launch_variant<8, 4>(p, a, g, grad, sym) : dyad_launch_variant<16, 4>(p, a, g, grad, sym);
     else
         rc = p.d <= 8 ? dyad_launch_variant<8, 8>(p, a, g, grad, sym) : dyad_launch_variant<16, 8>(p, a, g, grad, sym);
     if (rc) return rc;
-    // fp64 pass of the coverage kernel over the flagged pairs (a few microseconds when there are none)
-    rc = generic_repair_launch(p, a.kflag, nullptr, sym, g.tm, nw);
-    if (rc || !grad) return rc;
-    return grad_reduce_launch(g, a.rseg, a.cslab, p.gradX_out, p.dtype == SIGSVGD_F64, p.A, p.B, p.T * p.d, sym, p.stream);
+    return finish_launch(p, w, base, sym, g.tm, g.NW, p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 } // namespace sigsvgd

@@ -1031,14 +1031,7 @@ __global__ __launch_bounds__(RED_W * 64) void grad_reduce_kernel(GradReduceArgs 
 }
 
 // ---- host side ---------------------------------------------------------------------------------
-bool fast_supported(int A, int B, int T, int d, int n, int kind, unsigned flags)
-{
-    (void)A; (void)B;
-    if (n != 0 || T < 3 || T > 64 || d > 16) return false;
-    if (kind != SIGSVGD_STATIC_RBF) return false;
-    if (flags & SIGSVGD_FLAG_NAIVE_SOLVER) return false;
-    return true;
-}
+bool fast_supported(int T, int d, int n) { return n == 0 && T >= 3 && T <= 64 && d <= 16; }
 
 // compute units of the current device (256 on MI355X); the persistent grids are sized from it
 int device_cu_count()
@@ -1101,60 +1094,65 @@ int grad_reduce_launch(const GradGeom &g, const double *rseg, const float *cslab
     return SIGSVGD_OK;
 }
 
+int ws_base(const GramProblem &p, const WsPlan &w, const char *family, unsigned char *&base)
+{
+    if (w.end && (!p.ws || p.ws_bytes < w.total())) {
+        set_error("%s: workspace %zu B < required %zu B", family, p.ws_bytes, w.total());
+        return SIGSVGD_E_WORKSPACE;
+    }
+    base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
+    return SIGSVGD_OK;
+}
+
+int finish_launch(const GramProblem &p, const WsPlan &w, unsigned char *base, bool sym, const TileMap &tm, int tile_rows,
+                  void *out, int out64)
+{
+    if (w.kflag.bytes) { // exact fp64 pass of the coverage kernel over the flagged pairs (a few microseconds when there are none)
+        const int rc = generic_repair_launch(p, base + w.kflag.off, sym, tm, tile_rows);
+        if (rc) return rc;
+    }
+    if (!out) return SIGSVGD_OK;
+    return grad_reduce_launch(w.g, ws_at<double>(base, w.rseg), ws_at<float>(base, w.cslab), out, out64, p.A, p.B, p.T * p.d,
+                              sym, p.stream);
+}
+
 namespace {
-inline int cu_count() { return device_cu_count(); }
 // geometry of a GRADIENT launch (the forward-only launches keep no partial sums): rows per tile, workgroups a CU holds
 inline int grad_nw(int T, int d) { return (d <= 8) ? 8 : 4; } // (T <= 32: 4 wavefronts of two rows each)
 inline int grad_wg_per_cu(int T, int d) { return (d <= 8 && T <= 32) ? 3 : 1; }
-using FastGeom = GradGeom;
-FastGeom fast_geometry(int A, int B, int T, int d, bool sym, const TileMap &tm)
+GradGeom fast_geometry(int A, int B, int T, int d, bool sym, int off, int stride, bool fold)
 {
-    return grad_geometry(A, B, T * d, sym, tm.off, tm.stride, tm.fold != 0, grad_nw(T, d),
-                         (long long)cu_count() * grad_wg_per_cu(T, d));
-}
-FastGeom fast_geometry(int A, int B, int T, int d, bool sym)
-{
-    return grad_geometry(A, B, T * d, sym, 0, 1, false, grad_nw(T, d), (long long)cu_count() * grad_wg_per_cu(T, d));
+    return grad_geometry(A, B, T * d, sym, off, stride, fold, grad_nw(T, d), (long long)device_cu_count() * grad_wg_per_cu(T, d));
 }
 } // namespace
 
 int sym_tile_rows_fast(int T, int d) { return grad_nw(T, d); }
 
-namespace {
-// (the flag array of the exact fp64 pass: the 4-channel instantiations, i.e. paths in one to four channels; see the kernel)
-inline size_t fast_flag_bytes(int A, int B, int d)
+// [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
+WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold)
 {
-    return d <= 4 ? (((size_t)A * B + 255) & ~(size_t)255) + generic_repair_bytes() : 0;
-}
-} // namespace
-
-int fast_workspace_bytes(int A, int B, int T, int d, int want_grad, unsigned flags, size_t *bytes)
-{
-    (void)flags;
-    *bytes = 512 + fast_flag_bytes(A, B, d);
-    if (want_grad) { // the larger of the ordered and the symmetric launch (the query carries no Y_IS_X promise)
-        const FastGeom o = fast_geometry(A, B, T, d, false);
-        size_t need = o.rseg_bytes;
-        if (A == B) {
-            const FastGeom y = fast_geometry(A, B, T, d, true);
-            if (y.rseg_bytes + y.cslab_bytes > need) need = y.rseg_bytes + y.cslab_bytes;
-        }
-        *bytes += need + 256;
+    WsPlan w;
+    if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
+    if (want_grad) {
+        w.g = fast_geometry(A, B, T, d, sym, off, stride, fold);
+        w.rseg = w.take(w.g.rseg_bytes);
+        w.cslab = w.take(w.g.cslab_bytes);
     }
-    return SIGSVGD_OK;
+    return w;
 }
 
 namespace {
 template <int DPAD, int NW, int RING = 64>
-int launch_variant(const GramProblem &p, FastArgs &a, bool grad, bool sym)
+int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
 {
     // items of this launch: (owned row tile, column); symmetric launches only the columns from the tile's first row on
     constexpr int NWR = NW * (RING == 32 ? 2 : 1); // rows per tile: the 32-slot ring solves two rows per wavefront
+    tile_rows = NWR;
     const TileMap tm = make_tilemap((p.A + NWR - 1) / NWR, a.tm.off, a.tm.stride, a.tm.fold != 0);
     if (tm.owned <= 0) return SIGSVGD_OK;
     const long long total = tm.start(tm.owned, p.B, NWR, sym ? 1 : 0);
     if (total <= 0) return SIGSVGD_OK;
-    const int ncu = cu_count();
+    const int ncu = device_cu_count();
     a.tm = tm;
     a.nitems = total;
 #ifdef SIGSVGD_PHASE_STAMPS
@@ -1169,7 +1167,7 @@ int launch_variant(const GramProblem &p, FastArgs &a, bool grad, bool sym)
     dim3 grid((unsigned)(total < resident ? total : resident), 1);
     dim3 block(NW * 64);
     if (grad) { // the reduction kernel re-derives the segments from this geometry: it must be the one the workspace was cut for
-        const FastGeom g = fast_geometry(p.A, p.B, p.T, p.d, sym, a.tm);
+        const GradGeom &g = w.g;
         if (g.NW != NWR || g.grid != (int)grid.x || g.nitems != total) {
             set_error("fast: launch geometry mismatch (rows per tile %d/%d grid %d/%u items %lld/%lld)", g.NW, NWR, g.grid, grid.x,
                       g.nitems, total);
@@ -1192,10 +1190,6 @@ int launch_variant(const GramProblem &p, FastArgs &a, bool grad, bool sym)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, false, false, RING>), grid, block, 0, p.stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
-    if (a.kflag) { // exact fp64 pass of the coverage kernel over the flagged pairs (a few microseconds when there are none)
-        const int rc = generic_repair_launch(p, a.kflag, nullptr, sym, a.tm, NWR);
-        if (rc) return rc;
-    }
 #ifdef SIGSVGD_PHASE_STAMPS
     {
         unsigned long long h[8];
@@ -1214,36 +1208,32 @@ int launch_variant(const GramProblem &p, FastArgs &a, bool grad, bool sym)
     return SIGSVGD_OK;
 }
 
-int dispatch_variant(const GramProblem &p, FastArgs &a, bool grad, bool sym)
+int dispatch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
 {
     if (!grad && p.d <= 4) // forward only: no G image, <=168 VGPRs -> 4-wave workgroups pack 3 waves per SIMD
-        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, false, sym) : launch_variant<4, 4>(p, a, false, sym);
+        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<4, 4>(p, a, w, false, sym, tile_rows);
     if (!grad && p.d <= 8)
-        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, false, sym) : launch_variant<8, 4>(p, a, false, sym);
+        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<8, 4>(p, a, w, false, sym, tile_rows);
     if (p.d <= 4) // (paths of <= 32 points: the 32-slot ring on 4-wave workgroups, three per CU = 3 waves per SIMD)
-        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, grad, sym) : launch_variant<4, 8>(p, a, grad, sym);
+        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<4, 8>(p, a, w, grad, sym, tile_rows);
     if (p.d <= 8)
-        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, grad, sym) : launch_variant<8, 8>(p, a, grad, sym);
-    return launch_variant<16, 4>(p, a, grad, sym); // 1 wave per SIMD: 512-VGPR budget, no spills
+        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<8, 8>(p, a, w, grad, sym, tile_rows);
+    return launch_variant<16, 4>(p, a, w, grad, sym, tile_rows); // 1 wave per SIMD: 512-VGPR budget, no spills
 }
 
-// cut the two slabs out of the caller's workspace and enqueue kernel + reduction
-int run_grad(const GramProblem &p, FastArgs &a, bool sym, void *out, int out64)
+// cut the workspace from the plan, enqueue the kernel, the fp64 pass and (gradient) the reduction into `out`
+int run(const GramProblem &p, FastArgs &a, const WsPlan &w, bool sym, void *out, int out64)
 {
-    const FastGeom g = fast_geometry(p.A, p.B, p.T, p.d, sym, a.tm);
-    const size_t need = fast_flag_bytes(p.A, p.B, p.d) + g.rseg_bytes + g.cslab_bytes + 256;
-    if (!p.ws || p.ws_bytes < need) {
-        set_error("fast: workspace %zu B < required %zu B", p.ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-    a.kflag = p.d <= 4 ? base : nullptr;
-    base += fast_flag_bytes(p.A, p.B, p.d);
-    a.rseg = reinterpret_cast<double *>(base);
-    a.cslab = sym ? reinterpret_cast<float *>(base + g.rseg_bytes) : nullptr;
-    int rc = dispatch_variant(p, a, true, sym);
+    unsigned char *base = nullptr;
+    int rc = ws_base(p, w, "fast", base);
     if (rc) return rc;
-    return grad_reduce_launch(g, a.rseg, a.cslab, out, out64, p.A, p.B, p.T * p.d, sym, p.stream);
+    a.kflag = ws_at<unsigned char>(base, w.kflag);
+    a.rseg = ws_at<double>(base, w.rseg);
+    a.cslab = ws_at<float>(base, w.cslab);
+    int tile_rows = 0;
+    rc = dispatch_variant(p, a, w, out != nullptr, sym, tile_rows);
+    if (rc) return rc;
+    return finish_launch(p, w, base, sym, a.tm, tile_rows, out, out64);
 }
 
 void fill_args(const GramProblem &p, FastArgs &a)
@@ -1260,25 +1250,11 @@ void fill_args(const GramProblem &p, FastArgs &a)
 
 int fast_launch(const GramProblem &p)
 {
-    const bool grad = p.gradX_out != nullptr;
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B; // Y is X: each unordered pair once, K mirrored
     FastArgs a;
     fill_args(p, a);
-    if (a.symw && p.A != p.B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
-    if (!grad) {
-        if (p.d <= 4) {
-            if (!p.ws || p.ws_bytes < fast_flag_bytes(p.A, p.B, p.d) + 256) {
-                set_error("fast: workspace %zu B < required %zu B", p.ws_bytes, fast_flag_bytes(p.A, p.B, p.d) + 256);
-                return SIGSVGD_E_WORKSPACE;
-            }
-            a.kflag = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-        }
-        return dispatch_variant(p, a, false, sym);
-    }
-    return run_grad(p, a, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
+    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym);
+    return run(p, a, w, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 // Symmetric partial solve for particle sharding: this launch owns the row tiles tile_offset + k*tile_stride of the upper
@@ -1286,19 +1262,12 @@ int fast_launch(const GramProblem &p)
 // grad_partial[N,T,d] (fp64) is OVERWRITTEN with this launch's share of the gradient (rows it does not touch get 0).
 int fast_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial)
 {
-    if (!fast_supported(p.A, p.B, p.T, p.d, p.n, p.kind, p.flags) || p.A != p.B) {
-        set_error("sym_partial: shape/kernel outside the register-resident path (need n=0, 3<=T<=64, d<=16, RBF)");
-        return SIGSVGD_E_UNSUPPORTED;
-    }
-    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
-        set_error("sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
-        return SIGSVGD_E_BADARG;
-    }
     FastArgs a;
     fill_args(p, a);
     a.Y = p.X;
     a.tm = make_tilemap((p.A + grad_nw(p.T, p.d) - 1) / grad_nw(p.T, p.d), tile_offset, tile_stride, fold);
-    return run_grad(p, a, true, grad_partial, 1);
+    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold);
+    return run(p, a, w, true, grad_partial, 1);
 }
 
 } // namespace sigsvgd

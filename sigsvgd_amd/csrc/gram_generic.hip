@@ -501,14 +501,15 @@ namespace {
 // Y is X: each unordered pair once -- when there are enough pairs to fill the chip (below that the launch is latency-bound
 // and the second contraction pass of the symmetric solve only lengthens the critical path) and the per-pair slab of the
 // column-side gradients stays below 1 GiB (beyond that: ordered pairs, twice the solves, no slab).  `any_size`: at every pair
-// count -- the one-channel gradient launches the dispatch routes here must mirror K as the fp32-sweep kernels do
-bool generic_solves_unordered(int A, int B, int T, int d, int want_grad, unsigned flags, bool any_size = false)
+// count -- the one-channel gradient launches gram_route sends here must mirror K as the fp32-sweep kernels do
+bool generic_solves_unordered(int A, int B, int T, int d, int want_grad, bool sym, bool any_size)
 {
-    if (!(flags & SIGSVGD_FLAG_Y_IS_X) || A != B || (!any_size && (long long)A * B < 4096)) return false;
+    if (!sym || (!any_size && (long long)A * B < 4096)) return false;
     if (want_grad && (size_t)A * B * T * d * sizeof(double) > ((size_t)1 << 30)) return false;
     return true;
 }
 struct GenericPlan {
+    bool yx = false; // each unordered pair once (generic_solves_unordered)
     int dp, Tm, TmS, r, P, nbands, nsteps, JC, nchunks, grid, big, dd;
     long long items;
     size_t lds, partial_bytes, col_bytes, wsk_per_block, wsk_bytes;
@@ -572,23 +573,28 @@ int make_plan(int A, int B, int T, int d, int n, int want_grad, GenericPlan &pl,
 } // namespace
 
 namespace {
-inline size_t plan_bytes(const GenericPlan &pl) { return 512 + pl.partial_bytes + pl.col_bytes + pl.wsk_bytes; }
-}
-
-int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes, bool any_size)
+// the launch's plan and its workspace: [work counter (used by the symmetric solve)][gradient partials][column-side slab (symmetric
+// solve)][forward-solution scratch]
+int generic_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, bool precise, bool any_size, GenericPlan &pl,
+                 WsPlan &w)
 {
-    // the query carries no Y_IS_X promise: size for whichever of the ordered / symmetric plans needs more (the symmetric
-    // one uses shorter column chunks, i.e. more partial slabs)
-    GenericPlan pl;
-    int rc = make_plan(A, B, T, d, n, want_grad, pl, false, precise);
+    const bool yx = generic_solves_unordered(A, B, T, d, want_grad, sym, any_size);
+    const int rc = make_plan(A, B, T, d, n, want_grad, pl, yx, precise);
     if (rc) return rc;
-    *bytes = plan_bytes(pl);
-    if (generic_solves_unordered(A, B, T, d, want_grad, SIGSVGD_FLAG_Y_IS_X, any_size)) {
-        rc = make_plan(A, B, T, d, n, want_grad, pl, true, precise);
-        if (rc) return rc;
-        if (plan_bytes(pl) > *bytes) *bytes = plan_bytes(pl);
-    }
+    pl.yx = yx;
+    w = WsPlan{};
+    w.counter = w.take(256);
+    w.partials = w.take(pl.partial_bytes);
+    w.colslab = w.take(pl.col_bytes);
+    w.wsk = w.take(pl.wsk_bytes);
     return SIGSVGD_OK;
+}
+} // namespace
+
+int generic_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, bool precise, bool any_size, WsPlan &w)
+{
+    GenericPlan pl;
+    return generic_plan(A, B, T, d, n, want_grad, sym, precise, any_size, pl, w);
 }
 
 namespace {
@@ -632,42 +638,33 @@ hipError_t generic_dispatch(bool f64, bool naive, bool grad, bool big, const Gen
 }
 } // namespace
 
-int generic_launch(const GramProblem &p, bool any_size)
+int generic_launch(const GramProblem &p, bool precise, bool any_size)
 {
     const int want_grad = p.gradX_out != nullptr;
-    const bool yx = generic_solves_unordered(p.A, p.B, p.T, p.d, want_grad, p.flags, any_size);
     GenericPlan pl;
-    int rc = make_plan(p.A, p.B, p.T, p.d, p.n, want_grad, pl, yx, (p.flags & SIGSVGD_FLAG_FORCE_GENERIC) != 0);
+    WsPlan w;
+    int rc = generic_plan(p.A, p.B, p.T, p.d, p.n, want_grad, (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B, precise, any_size,
+                          pl, w);
     if (rc) return rc;
-    const size_t need = plan_bytes(pl);
-    if (p.ws == nullptr || p.ws_bytes < need) {
-        set_error("generic: workspace %zu B < required %zu B", p.ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    const bool sym = (p.flags & SIGSVGD_FLAG_SYM) != 0;
-    if (sym && p.A != p.B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
+    unsigned char *base = nullptr;
+    rc = ws_base(p, w, "generic", base);
+    if (rc) return rc;
+    const bool yx = pl.yx;
     GenericArgs a;
     a.X = p.X; a.Y = p.Y; a.grad_out = p.grad_out; a.K_out = p.K_out;
-    unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-    a.next_item = nullptr;
+    a.next_item = yx ? ws_at<unsigned long long>(base, w.counter) : nullptr;
     if (yx) {
-        a.next_item = reinterpret_cast<unsigned long long *>(base);
         hipError_t ce = hipMemsetAsync(a.next_item, 0, sizeof(unsigned long long), p.stream);
         if (ce != hipSuccess) return hip_fail(ce, "hipMemsetAsync(work counter)");
     }
-    a.partials = want_grad ? reinterpret_cast<double *>(base + 256) : nullptr;
+    a.partials = ws_at<double>(base, w.partials);
     a.yx = yx ? 1 : 0;
-    a.colslab = nullptr;
-    unsigned char *after = want_grad ? reinterpret_cast<unsigned char *>(a.partials) + pl.partial_bytes : nullptr;
-    if (want_grad && yx) a.colslab = reinterpret_cast<double *>(after);
-    a.wsk = want_grad ? reinterpret_cast<float *>(after + pl.col_bytes) : nullptr;
+    a.colslab = ws_at<double>(base, w.colslab);
+    a.wsk = ws_at<float>(base, w.wsk);
     a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.dp = pl.dp; a.n = p.n; a.r = pl.r; a.P = pl.P;
     a.Tm = pl.Tm; a.TmS = pl.TmS; a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.JC = pl.JC;
     a.nchunks = pl.nchunks; a.kind = p.kind; a.naive = (p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) ? 1 : 0;
-    a.sym = sym ? 1 : 0; a.want_grad = want_grad; a.inv_h = p.inv_h;
+    a.sym = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.want_grad = want_grad; a.inv_h = p.inv_h;
     a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
     a.total_items = pl.items; a.wsk_per_block = pl.wsk_per_block; a.big = pl.big;
     a.flags = nullptr; a.tm = make_tilemap(1, 0, 1, false); a.tile_rows = 1;
@@ -722,11 +719,8 @@ int generic_launch(const GramProblem &p, bool any_size)
 // coverage kernel takes one row of K per work item, skips every row without a flag before staging anything (a few
 // microseconds when nothing is flagged) and stores K of the flagged pairs again, from fp64 sweeps.  Items are assigned
 // statically; no counter, no memset.
-size_t generic_repair_bytes() { return 1024; }
-
-int generic_repair_launch(const GramProblem &p, const unsigned char *flags, void *ws, bool sym, const TileMap &tm, int tile_rows)
+int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool sym, const TileMap &tm, int tile_rows)
 {
-    (void)ws;
     GenericPlan pl;
     int rc = make_plan(p.A, p.B, p.T, p.d, p.n, 0, pl, false, true);
     if (rc) return rc;

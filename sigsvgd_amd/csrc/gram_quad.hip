@@ -952,71 +952,36 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 #endif
 }
 
-bool quad_supported(int A, int B, int T, int d, int n, int kind, unsigned flags)
-{
-    (void)A; (void)B;
-    if (n != 0 || T < 65 || T > 128 || d > 16) return false;
-    if (kind != SIGSVGD_STATIC_RBF) return false;
-    if (flags & SIGSVGD_FLAG_NAIVE_SOLVER) return false;
-    return true;
-}
+bool quad_supported(int T, int d, int n) { return n == 0 && T >= 65 && T <= 128 && d <= 16; }
 
 namespace {
-inline int quad_cu_count() { return device_cu_count(); } // the grid is at most one workgroup per CU
 constexpr size_t QUAD_DCACHE_PER_WG = (size_t)QNW * 6 * 64 * 64 * sizeof(float); // 768 KB: increments (+ forward solution, 8-channel layout) of 3 quadrants
 constexpr size_t QUAD_CREC_PER_WG = (size_t)QNW * QREC * sizeof(float);          // 208 KB
 constexpr size_t QUAD_ROWG_PER_WG = (size_t)QNW * 128 * 16 * sizeof(float);      // 64 KB (d = 15, 16 only)
-
-inline GradGeom quad_geometry(int A, int B, int T, int d, bool sym, int off = 0, int stride = 1, bool fold = false)
-{
-    return grad_geometry(A, B, T * d, sym, off, stride, fold, QNW, (long long)quad_cu_count());
-}
-inline GradGeom quad_geometry(int A, int B, int T, int d, bool sym, const TileMap &tm)
-{
-    return quad_geometry(A, B, T, d, sym, tm.off, tm.stride, tm.fold != 0);
-}
-// workspace of a gradient launch: [row segments][column slab][column records][row accumulators (d >= 15)][increment scratch]
-struct QuadCut {
-    size_t rseg, cslab, crec, rowg, dcache, total;
-};
-inline QuadCut quad_cut(const GradGeom &g, int d, bool sym)
-{
-    QuadCut c;
-    const size_t ncu = (size_t)quad_cu_count();
-    c.rseg = 0;
-    c.cslab = c.rseg + g.rseg_bytes;
-    c.crec = c.cslab + g.cslab_bytes;
-    c.rowg = c.crec + (sym ? ncu * QUAD_CREC_PER_WG : 0);
-    c.dcache = c.rowg + (d > 14 ? ncu * QUAD_ROWG_PER_WG : 0);
-    c.total = c.dcache + ncu * QUAD_DCACHE_PER_WG;
-    return c;
-}
 } // namespace
 
-// every launch: [A][B] bytes of cancellation flags + the (small) workspace of the fp64 pass over the flagged pairs, in
-// front of the gradient launch's own areas
-inline size_t quad_flag_bytes(int A, int B) { return (((size_t)A * B + 255) & ~(size_t)255) + generic_repair_bytes(); }
-
-int quad_workspace_bytes(int A, int B, int T, int d, int want_grad, size_t *bytes)
+// every launch: [A][B] bytes of cancellation flags for the fp64 pass; gradient launches behind them: [row segments][column
+// slab][column records][row accumulators (d >= 15)][increment scratch] -- the grid is at most one workgroup per CU, and the
+// increment scratch of a full grid is 100 MB on 256 CUs (it lives in L2 / MALL)
+WsPlan quad_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold)
 {
-    *bytes = quad_flag_bytes(A, B) + 512;
-    if (!want_grad) return SIGSVGD_OK;
-    // the larger of the ordered and the symmetric launch (the query carries no Y_IS_X promise); the increment scratch of a
-    // full grid is 100 MB on 256 CUs and lives in L2 / MALL
-    size_t need = quad_cut(quad_geometry(A, B, T, d, false), d, false).total;
-    if (A == B) {
-        const size_t y = quad_cut(quad_geometry(A, B, T, d, true), d, true).total;
-        if (y > need) need = y;
-    }
-    *bytes = need + quad_flag_bytes(A, B) + 512;
-    return SIGSVGD_OK;
+    WsPlan w;
+    const size_t ncu = (size_t)device_cu_count();
+    w.g = grad_geometry(A, B, T * d, sym, off, stride, fold, QNW, (long long)ncu);
+    w.kflag = w.take(flag_area_bytes(A, B));
+    if (!want_grad) return w;
+    w.rseg = w.take(w.g.rseg_bytes);
+    w.cslab = w.take(w.g.cslab_bytes);
+    w.crec = w.take(sym ? ncu * QUAD_CREC_PER_WG : 0);
+    w.rowg = w.take(d > 14 ? ncu * QUAD_ROWG_PER_WG : 0);
+    w.dcache = w.take(ncu * QUAD_DCACHE_PER_WG);
+    return w;
 }
 
 namespace {
 template <int DPAD>
-int quad_launch_variant(const GramProblem &p, QuadArgs &a, bool grad, bool sym)
+int quad_launch_variant(const GramProblem &p, QuadArgs &a, const GradGeom &g, bool grad, bool sym)
 {
-    const GradGeom g = quad_geometry(p.A, p.B, p.T, p.d, sym, a.tm);
     if (g.tm.owned <= 0 || g.nitems <= 0) return SIGSVGD_OK;
     a.tm = g.tm;
     a.nitems = g.nitems;
@@ -1073,79 +1038,43 @@ int quad_launch_variant(const GramProblem &p, QuadArgs &a, bool grad, bool sym)
     return SIGSVGD_OK;
 }
 
-int quad_dispatch(const GramProblem &p, QuadArgs &a, bool grad, bool sym)
-{
-    if (p.d <= 8) return quad_launch_variant<8>(p, a, grad, sym);
-    return quad_launch_variant<16>(p, a, grad, sym);
-}
-
 void quad_fill_args(const GramProblem &p, QuadArgs &a)
 {
     a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
     a.rseg = nullptr; a.cslab = nullptr; a.crec = nullptr; a.rowg = nullptr;
     a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d;
     a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
-    a.tm = make_tilemap(1, 0, 1, false); // (a full launch; quad_launch_variant derives the tile count)
+    a.tm = make_tilemap(1, 0, 1, false); // (quad_launch_variant takes the plan's tile map)
     a.nitems = 0; a.dcache = nullptr; a.kflag = nullptr;
 }
 
-// the flag area at the head of the workspace (every launch has one), and the fp64 pass that follows the kernel
-unsigned char *quad_ws_base(const GramProblem &p, size_t need)
+// cut the workspace from the plan, enqueue the kernel, the fp64 pass and (gradient) the fixed-order reduction into `out` (the
+// I/O type, or fp64 for the partial solve)
+int quad_run(const GramProblem &p, QuadArgs &a, const WsPlan &w, bool sym, void *out, int out64)
 {
-    if (!p.ws || p.ws_bytes < need + quad_flag_bytes(p.A, p.B) + 256) {
-        set_error("quad: workspace %zu B < required %zu B", p.ws_bytes, need + quad_flag_bytes(p.A, p.B) + 256);
-        return nullptr;
-    }
-    return reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
-}
-int quad_repair(const GramProblem &p, const QuadArgs &a, bool sym)
-{
-    return generic_repair_launch(p, a.kflag, a.kflag + (((size_t)p.A * p.B + 255) & ~(size_t)255), sym, a.tm, QNW);
-}
-
-// cut the workspace, enqueue kernel + fixed-order reduction into `out` (the I/O type, or fp64 for the partial solve)
-int quad_run_grad(const GramProblem &p, QuadArgs &a, bool sym, void *out, int out64)
-{
-    const GradGeom g = quad_geometry(p.A, p.B, p.T, p.d, sym, a.tm);
-    const QuadCut c = quad_cut(g, p.d, sym);
-    unsigned char *base = quad_ws_base(p, c.total);
-    if (!base) return SIGSVGD_E_WORKSPACE;
-    a.kflag = base;
-    base += quad_flag_bytes(p.A, p.B);
-    a.rseg = reinterpret_cast<double *>(base + c.rseg);
-    a.cslab = sym ? reinterpret_cast<float *>(base + c.cslab) : nullptr;
-    a.crec = sym ? reinterpret_cast<float *>(base + c.crec) : nullptr;
-    a.rowg = p.d > 14 ? reinterpret_cast<float *>(base + c.rowg) : nullptr;
-    a.dcache = reinterpret_cast<float *>(base + c.dcache);
-    int rc = quad_dispatch(p, a, true, sym);
+    unsigned char *base = nullptr;
+    int rc = ws_base(p, w, "quad", base);
     if (rc) return rc;
-    a.tm = g.tm;
-    rc = quad_repair(p, a, sym);
+    a.kflag = ws_at<unsigned char>(base, w.kflag);
+    a.rseg = ws_at<double>(base, w.rseg);
+    a.cslab = ws_at<float>(base, w.cslab);
+    a.crec = ws_at<float>(base, w.crec);
+    a.rowg = ws_at<float>(base, w.rowg);
+    a.dcache = ws_at<float>(base, w.dcache);
+    const bool grad = out != nullptr;
+    rc = p.d <= 8 ? quad_launch_variant<8>(p, a, w.g, grad, sym) : quad_launch_variant<16>(p, a, w.g, grad, sym);
     if (rc) return rc;
-    return grad_reduce_launch(g, a.rseg, a.cslab, out, out64, p.A, p.B, p.T * p.d, sym, p.stream);
+    return finish_launch(p, w, base, sym, w.g.tm, QNW, out, out64);
 }
 } // namespace
 
 int quad_launch(const GramProblem &p)
 {
-    const bool grad = p.gradX_out != nullptr;
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B; // Y is X: each unordered pair once
     QuadArgs a;
     quad_fill_args(p, a);
-    if (a.symw && p.A != p.B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
-    if (!grad) {
-        unsigned char *base = quad_ws_base(p, 0);
-        if (!base) return SIGSVGD_E_WORKSPACE;
-        a.kflag = base;
-        int rc = quad_dispatch(p, a, false, sym);
-        if (rc) return rc;
-        a.tm = quad_geometry(p.A, p.B, p.T, p.d, sym, a.tm).tm;
-        return quad_repair(p, a, sym);
-    }
-    return quad_run_grad(p, a, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
+    const WsPlan w = quad_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym);
+    return quad_run(p, a, w, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 // Sharded partial solve (sigsvgd_gram_sym_partial) for the long-path shapes: row tiles of 8 rows, tiles
@@ -1153,14 +1082,10 @@ int quad_launch(const GramProblem &p)
 // OVERWRITTEN with this launch's share of the gradient.
 int quad_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial)
 {
-    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
-        set_error("bad tile_offset/tile_stride %d/%d", tile_offset, tile_stride);
-        return SIGSVGD_E_BADARG;
-    }
     QuadArgs a;
     quad_fill_args(p, a);
-    a.tm = make_tilemap((p.A + QNW - 1) / QNW, tile_offset, tile_stride, fold);
-    return quad_run_grad(p, a, true, grad_partial, 1);
+    const WsPlan w = quad_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold);
+    return quad_run(p, a, w, true, grad_partial, 1);
 }
 
 } // namespace sigsvgd

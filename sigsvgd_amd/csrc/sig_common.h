@@ -196,11 +196,6 @@ struct GramProblem {
     hipStream_t stream;
 };
 
-// generic (any T, n, d that fits LDS) -- gram_generic.hip
-// precise: FORCE_GENERIC; any_size: Y_IS_X launches solve each unordered pair once (mirrored K) whatever their pair count
-int generic_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, bool precise, size_t *bytes, bool any_size = false);
-int generic_launch(const GramProblem &p, bool any_size = false);
-
 // fixed-order reduction of the gradient partial sums shared by the register-resident and the quadrant kernel -- gram_fast.hip
 // Which row tiles a launch owns and the order it enumerates them in (kq = 0 .. owned-1).  A full launch owns all of
 // them (off 0, stride 1).  The sharded partial solve of rank `off` of `stride` owns the tiles off + k*stride (cyclic), or
@@ -244,34 +239,80 @@ GradGeom grad_geometry(int A, int B, int TD, bool sym, int off, int stride, bool
 int grad_reduce_launch(const GradGeom &g, const double *rseg, const float *cslab, void *out, int out64, int A, int B, int TD,
                        bool sym, hipStream_t stream);
 
-// fp64 pass of the coverage kernel over the pairs a fp32-sweep kernel flagged (flags [A][B] bytes; `sym`: the pairs j >= i,
-// K mirrored; rows of the tiles `tm` owns, `tile_rows` rows each; ws: generic_repair_bytes() of scratch) -- gram_generic.hip
-size_t generic_repair_bytes();
-int generic_repair_launch(const GramProblem &p, const unsigned char *flags, void *ws, bool sym, const TileMap &tm, int tile_rows);
+// ---- workspace plans ------------------------------------------------------------------------------------------------------
+// One launch's workspace: areas at byte offsets from the 256-B aligned base of the caller's buffer (an area of 0 bytes is not
+// used) and `total()`, the bytes the caller gives (alignment slack included).  Every family has one plan function; its launcher
+// checks the caller's size against that plan and cuts the buffer from it, and sigsvgd_gram_workspace_bytes returns the
+// largest total of the launches a call can reach.  `sym` below is the Y_IS_X orientation (each unordered pair once).
+struct WsArea {
+    size_t off = 0, bytes = 0;
+};
+struct WsPlan {
+    GradGeom g{}; // geometry of the fp32-sweep kernels' launch (grad_reduce_launch re-derives its segments from it)
+    WsArea kflag;        // [A][B] cancellation flags the fp64 pass reads
+    WsArea rseg, cslab;  // row segments, column slab of the gradient
+    WsArea crec, rowg, dcache; // gram_quad.hip: column records, row accumulators, increment scratch
+    WsArea wsk;          // forward-solution scratch (gram_band.hip, gram_generic.hip)
+    WsArea counter, partials, colslab; // gram_generic.hip: work counter, gradient partials, column-side slab
+    size_t end = 0; // bytes of the areas
+    WsArea take(size_t bytes) // the next area, behind the ones taken so far
+    {
+        const WsArea a{end, bytes};
+        end += bytes;
+        return a;
+    }
+    size_t total() const { return end + 256; } // (+ the slack of aligning the caller's pointer)
+};
+inline size_t flag_area_bytes(int A, int B) { return ((size_t)A * B + 255) & ~(size_t)255; }
+template <typename T>
+inline T *ws_at(unsigned char *base, const WsArea &a)
+{
+    return a.bytes ? reinterpret_cast<T *>(base + a.off) : nullptr;
+}
+// `base` = p.ws aligned to 256 B; SIGSVGD_E_WORKSPACE (message "<family>: workspace ... required N B") when the caller's
+// buffer is smaller than w.total() -- a plan without areas takes any buffer, NULL included
+int ws_base(const GramProblem &p, const WsPlan &w, const char *family, unsigned char *&base);
+// the tail of the fp32-sweep launches: the fp64 pass over the flagged pairs of the rows of the tiles `tm` owns (tile_rows rows
+// each), then the fixed-order gradient reduction into `out` (fp64 when out64; NULL: a forward-only launch)
+int finish_launch(const GramProblem &p, const WsPlan &w, unsigned char *base, bool sym, const TileMap &tm, int tile_rows,
+                  void *out, int out64);
 
-// register-resident fast path (n == 0, T <= 64, RBF/linear) -- gram_fast.hip
-bool fast_supported(int A, int B, int T, int d, int n, int kind, unsigned flags);
-int fast_workspace_bytes(int A, int B, int T, int d, int want_grad, unsigned flags, size_t *bytes);
+// ---- kernel families --------------------------------------------------------------------------------------------------
+// *_supported: the shapes a family's kernels take (dyadic order n; RBF static kernel, second-order solver).  Only gram_route
+// (capi.hip) combines them into the choice of kernel.
+
+// generic (any T, n, d that fits LDS) -- gram_generic.hip
+// precise: fp64 increments wherever they fit (FORCE_GENERIC); any_size: symmetric launches solve each unordered pair once
+// (mirrored K) whatever their pair count
+int generic_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, bool precise, bool any_size, WsPlan &w);
+int generic_launch(const GramProblem &p, bool precise, bool any_size);
+// fp64 pass of the coverage kernel over the pairs a fp32-sweep kernel flagged (flags [A][B] bytes; `sym`: the pairs j >= i,
+// K mirrored; rows of the tiles `tm` owns, `tile_rows` rows each) -- gram_generic.hip
+int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool sym, const TileMap &tm, int tile_rows);
+
+// register-resident fast path (n == 0, T <= 64) -- gram_fast.hip; off / stride / fold: the row tiles a partial solve owns
+bool fast_supported(int T, int d, int n);
+WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false);
 int fast_launch(const GramProblem &p);
 int fast_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial);
 int sym_tile_rows_fast(int T, int d); // rows per tile of the gradient launches (ownership unit of the partial solve)
 
 // long paths, stored forward solution, 2 x 2 quadrants of 64 x 64 cells at two waves per SIMD -- gram_quad.hip
-bool quad_supported(int A, int B, int T, int d, int n, int kind, unsigned flags);
-int quad_workspace_bytes(int A, int B, int T, int d, int want_grad, size_t *bytes);
+bool quad_supported(int T, int d, int n);
+WsPlan quad_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false);
 int quad_launch(const GramProblem &p);
 int quad_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial);
 
 // short paths with dyadic refinement, refined grid of 64 .. 128 cells per side, on the quadrant sweep engine -- gram_dyad.hip
-bool dyad_supported(int A, int B, int T, int d, int n, int kind, unsigned flags);
-int dyad_workspace_bytes(int A, int B, int T, int d, int want_grad, size_t *bytes);
+bool dyad_supported(int T, int d, int n);
+WsPlan dyad_plan(int A, int B, int T, int d, int want_grad, bool sym);
 int dyad_launch(const GramProblem &p);
 
-// the same with 129 .. 256 refined cells per side, swept in bands of 64 rows (fp32 difference form) -- gram_band.hip
-bool band_supported(int A, int B, int T, int d, int n, int kind, unsigned flags);
-int band_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, unsigned flags, size_t *bytes);
-int band_launch(const GramProblem &p);
-bool band_takes_refined(const GramProblem &p); // 65 .. 128 cells, small launches: the band-parallel kernel instead of gram_dyad.hip
-size_t band_refined_workspace_bytes(int A, int B, int T, int d, int n, int want_grad, unsigned flags);
+// refined grids of 64 .. 256 cells per side, one wavefront per band of 64 rows of a pair (band-parallel) or per pair
+// (serial) -- gram_band.hip
+bool band_supported(int T, int d, int n);
+int band_wg_per_cu(int T, int d, int n, bool serial); // workgroups of a schedule a CU holds
+WsPlan band_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, bool serial);
+int band_launch(const GramProblem &p, bool serial);
 
 } // namespace sigsvgd

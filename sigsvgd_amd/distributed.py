@@ -206,8 +206,8 @@ class ShardedSigSVGD:
 
     @staticmethod
     def _partial_supported(X_full) -> bool:
-        """shapes the register-resident and quadrant symmetric kernels cover (include/sigsvgd_hip.h)"""
-        return 3 <= X_full.shape[1] <= 128 and X_full.shape[2] <= 16
+        """shapes the symmetric partial solve takes (the library's routing rule)"""
+        return ops.sym_tile_rows(X_full.shape[1], X_full.shape[2]) > 0
 
     def _step_rowwise(self, X_shard, X_full, s_full):
         """Fallback for shapes outside the symmetric partial solve (e.g. T > 128): each rank solves

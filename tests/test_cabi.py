@@ -104,6 +104,50 @@ def test_workspace_query_covers_every_pair_kernel(lib):
         assert lib.sigsvgd_gram_workspace_bytes(9, 9, T, d, order, 0, 1, 8, ctypes.byref(n)) == 0 and n.value > 0, name
 
 
+def test_workspace_query_covers_every_launch(lib, monkeypatch):
+    """the launchers check their workspace against the same plan the query takes its maximum over: a launch given no workspace
+    reports `required N B` with N <= the query, for shapes that reach every kernel family, both band schedules and every
+    orientation (the dummy pointers never reach a kernel: the workspace check fails first, or -- forward-only launches of the
+    register-resident kernel with d > 4, which need none -- the launch fails for want of a device)"""
+    import torch
+
+    if torch.cuda.is_available():
+        pytest.skip("the dummy pointers must not reach a kernel launch on a HIP device")
+    one = ctypes.c_void_p(16)
+    shapes = [(64, 7, 0), (32, 7, 0), (33, 1, 0), (128, 14, 0), (128, 1, 0), (20, 2, 2), (17, 3, 2), (40, 3, 1), (5, 2, 5),
+              (10, 2, 4), (30, 2, 3), (100, 3, 3)]
+    families, cases = set(), 0
+    for mode in (None, "serial", "parallel"):
+        if mode is None:
+            monkeypatch.delenv("SIGSVGD_BAND_MODE", raising=False)
+        else:
+            monkeypatch.setenv("SIGSVGD_BAND_MODE", mode)
+        for (T, d, order) in shapes:
+            for A, B in ((37, 37), (5, 9), (300, 300)):
+                for flags in ((0, 2, 4, 6, 8) if A == B else (0, 8)):
+                    for kind in (0, 1):
+                        for want_grad in (0, 1):
+                            n = ctypes.c_size_t(0)
+                            assert lib.sigsvgd_gram_workspace_bytes(A, B, T, d, order, kind, want_grad, flags,
+                                                                    ctypes.byref(n)) == 0
+                            if want_grad:
+                                rc = lib.sigsvgd_gram_fwd_bwd(one, one, A, B, T, d, 0, 1.0, order, kind, flags, None, one, one,
+                                                              None, 0, None)
+                            else:
+                                rc = lib.sigsvgd_gram_fwd(one, one, A, B, T, d, 0, 1.0, order, kind, flags, one, None, 0, None)
+                            case = (mode, T, d, order, A, B, flags, kind, want_grad)
+                            cases += 1
+                            if rc == -4:  # (a launch that needs no workspace)
+                                assert not want_grad and order == 0 and T <= 64 and d > 4 and kind == 0 and flags != 8, case
+                                continue
+                            m = re.match(rb"(\w+): workspace 0 B < required (\d+) B", lib.sigsvgd_last_error())
+                            assert rc == -3 and m, (case, rc, lib.sigsvgd_last_error())
+                            assert int(m.group(2)) <= n.value, (case, int(m.group(2)), n.value)
+                            families.add(m.group(1).decode())
+    assert cases > 1000
+    assert families == {"fast", "quad", "dyad", "band", "generic"}
+
+
 def test_argument_errors_are_status_codes(lib):
     """bad arguments are rejected on the host before anything is launched"""
     one = ctypes.c_void_p(16)  # never dereferenced: the checks below fail first
