@@ -20,8 +20,6 @@
 // src/kernels/_traj_kernels.py:176-195; callers src/inference/score.py:68-69.
 #include "sig_common.h"
 
-#include <atomic>
-
 namespace sigsvgd {
 
 struct BandArgs {
@@ -43,36 +41,11 @@ struct BandArgs {
 #endif
 };
 
-// Diagnostic build (-DSIGSVGD_PHASE_STAMPS, scripts/dev/phase_stamps.py): s_memtime around the phases of the band-parallel kernel
-#ifdef SIGSVGD_PHASE_STAMPS
-#define SIGB_STAMP(i)                                                        \
-    {                                                                        \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
-        ph_[i] += now_ - tlast_;                                             \
-        tlast_ = now_;                                                       \
-    }
-#else
-#define SIGB_STAMP(i)
-#endif
-
 namespace {
 constexpr int BTMAX = 33;  // coarse points per path
 constexpr int BPMAX = 256; // refined cells per side
 constexpr int BPAD = 64;   // boundary rows: entry e lives at [BPAD + e]; lanes outside the grid write into the padding
-__device__ __forceinline__ double b_ldany(const void *b, size_t i, int io64)
-{
-    return io64 ? static_cast<const double *>(b)[i] : (double)static_cast<const float *>(b)[i];
-}
-__device__ __forceinline__ void b_stany(void *b, size_t i, double v, int io64)
-{
-    if (io64)
-        static_cast<double *>(b)[i] = v;
-    else
-        static_cast<float *>(b)[i] = (float)v;
-}
-} // namespace
 
-namespace {
 // ---- the band kernel ---------------------------------------------------------------------------------------------------
 // Band-parallel schedule.  The reference's refined call shapes come with few pairs (notebook 5,050, maze 630): one wavefront
 // per pair leaves most of the chip's 1,024 SIMDs with one wavefront or none, each walking nb (P + 63) dependent steps per
@@ -325,8 +298,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
         __syncthreads();
         for (int e = tid; e < T * DPAD; e += NT) {
             const int t = e / DPAD, c = e % DPAD;
-            const double r0 = c < d ? b_ldany(a.Y, (size_t)j * T * d + c, io64) : 0.0;
-            const double v = c < d ? b_ldany(a.Y, ((size_t)j * T + t) * d + c, io64) - r0 : 0.0;
+            const double r0 = c < d ? load_any(a.Y, (size_t)j * T * d + c, io64) : 0.0;
+            const double v = c < d ? load_any(a.Y, ((size_t)j * T + t) * d + c, io64) - r0 : 0.0;
             yd[t * (DPAD + 1) + c] = v;
             yf[t * DPAD + c] = (float)v;
             if (t == 0) yref[c] = r0;
@@ -337,7 +310,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
         }
         __syncthreads();
 
-        SIGB_STAMP(0)
+        SIG_STAMP(0)
         const bool valid = row_ok && (!SYM || j >= i); // (uniform per wavefront)
         if (valid && lead) {
             for (int e = lanep; e < (Tm + 1) * DS; e += 64) Dc[e] = 0.f; // the zeros around the rows (the table is reused per pair)
@@ -348,7 +321,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             double xs[DPAD], xn = 0.0;
 #pragma unroll
             for (int c = 0; c < DPAD; ++c) {
-                const double xc = c < d ? b_ldany(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c] : 0.0;
+                const double xc = c < d ? load_any(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c] : 0.0;
                 xn = __builtin_fma(xc, xc, xn);
                 xs[c] = xc * (2.0 * inv_h);
             }
@@ -368,9 +341,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             if (GRAD)
                 for (int e = lanep; e < Tm * Tm; e += 64) Sc[e] = 0.0;
         }
-        SIGB_STAMP(1)
+        SIG_STAMP(1)
         __syncthreads(); // the pair's increment table is complete
-        SIGB_STAMP(3)
+        SIG_STAMP(3)
 
         // ---- forward sweep: this wavefront's band, BGS steps per phase ---------------------------------------------
         float kmax = 1.f; // largest |K| this lane has seen on the pair's grid
@@ -421,10 +394,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
                             bandp_fwd_phase<false, COMP, GRAD>(st, hv, dcrow, n, qlim, ho, wrow, lanep * 4);
                         ho += hinc;
                     }
-                    SIGB_STAMP(2)
+                    SIG_STAMP(2)
                 }
                 if (!SER) __syncthreads();
-                SIGB_STAMP(3)
+                SIG_STAMP(3)
             }
             kmax = st.kmax;
             if (valid && band == nb - 1 && p == P - 1) *reinterpret_cast<double *>(misc) = (double)st.cur + (double)st.clo;
@@ -445,8 +418,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             const float kfv = (float)kfin;
             const bool cancelled = kfv == kfv && km > (d == 1 ? 2.f : (d == 2 || !COMP) ? 4.f : 8.f) * fmaxf(fabsf(kfv), 0.1f);
             if (lanep == 0) {
-                b_stany(a.K, (size_t)i * a.B + j, kfin, io64);
-                if (SYM && j != i) b_stany(a.K, (size_t)j * a.B + i, kfin, io64);
+                store_any(a.K, (size_t)i * a.B + j, kfin, io64);
+                if (SYM && j != i) store_any(a.K, (size_t)j * a.B + i, kfin, io64);
                 if (!GRAD) a.kflag[(size_t)i * a.B + j] = cancelled ? 1 : 0;
             }
             kfin_keep = kfv;
@@ -530,10 +503,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
                             if (r == 4 && cell2 >= 0) unsafeAtomicAdd(scrow + cell2, (double)out2); // (L = 0 mod 4: steps 2 and 6 of every group)
                             if (((L - 2 - sp0 - h - BFU) & (r - 1)) == 0 && cell6 >= 0) unsafeAtomicAdd(scrow + cell6, (double)out6); // ds_add_f64
                         }
-                        SIGB_STAMP(4)
+                        SIG_STAMP(4)
                     }
                     if (!SER) __syncthreads();
-                    SIGB_STAMP(5)
+                    SIG_STAMP(5)
                 }
                 // (the ring's last loads are never used: consumed here, or hipcc carries them as pending into the next pair's
                 //  forward step loop and waits for vmcnt(0) in every step -- behind the step's own store, a memory round trip)
@@ -559,7 +532,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
                 }
                 for (int e = wtid; e < T * DPAD; e += wnt) {
                     const int m = e / DPAD, c = e - m * DPAD;
-                    xl[e] = c < d ? (float)(b_ldany(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c]) : 0.f;
+                    xl[e] = c < d ? (float)(load_any(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c]) : 0.f;
                 }
             }
             if (valid && lead) {
@@ -582,8 +555,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             if (valid && (SER || band0 == 0 || (SYM && band0 == colwave))) {
                 float w_ij = 1.f, w_ji = 1.f;
                 if (a.go) {
-                    w_ij = (float)b_ldany(a.go, (size_t)i * a.B + j, io64);
-                    if (SYM || a.symw) w_ji = (float)b_ldany(a.go, (size_t)j * a.B + i, io64);
+                    w_ij = (float)load_any(a.go, (size_t)i * a.B + j, io64);
+                    if (SYM || a.symw) w_ji = (float)load_any(a.go, (size_t)j * a.B + i, io64);
                     if (a.symw) { w_ij += w_ji; w_ji = w_ij; }
                 } else if (a.symw) {
                     w_ij = 2.f; w_ji = 2.f;
@@ -644,7 +617,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             }
         }
 
-        SIGB_STAMP(6)
+        SIG_STAMP(6)
         if (GRAD && SYM) {
             __syncthreads(); // every pair has parked its column-side sums
             float *dstc = a.cslab + (size_t)item * (T * d);
@@ -673,7 +646,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
     cstart = 0;
     } // row tiles of the range
 #ifdef SIGSVGD_PHASE_STAMPS
-    SIGB_STAMP(0)
+    SIG_STAMP(0)
     if (lane == 0 && a.stamps)
         for (int k = 0; k < 8; ++k) atomicAdd(&a.stamps[k], ph_[k]);
 #endif
@@ -747,21 +720,6 @@ WsPlan band_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, boo
 }
 
 namespace {
-// (the dynamic-LDS limit of an instantiation, raised once per device: see gram_generic.hip)
-template <int DPAD, bool GRAD, bool SYM, bool COMP, bool SER>
-hipError_t band_raise_lds()
-{
-    static std::atomic<unsigned long long> raised{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !((raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gram_bandp_kernel<DPAD, GRAD, SYM, COMP, SER>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised.fetch_or(1ull << dev, std::memory_order_release);
-    }
-    return hipSuccess;
-}
 // Where the full-magnitude add of a step runs in two floats (template parameter COMP; `rev`: in the reverse sweep too).  The
 // add's rounding has the same sign row after row when neighbouring cells have nearly identical increments, so K drifts by
 // up to 6e-8 per ROW on smooth paths: dyadic order >= 5 (forward sweep: K 1.2e-5 at order 6 without it); one channel at any
@@ -788,7 +746,7 @@ int band_launch_variant(const GramProblem &p, BandArgs &a, const GradGeom &g, bo
     const unsigned lds = (unsigned)bandp_lds(p.T, P, DPAD, slots).total;
 #define SIGB_LAUNCH(G, S)                                                                                          \
     {                                                                                                              \
-        hipError_t ae = comp ? band_raise_lds<DPAD, G, S, true, SER>() : band_raise_lds<DPAD, G, S, false, SER>(); \
+        hipError_t ae = comp ? raise_lds_limit<&gram_bandp_kernel<DPAD, G, S, true, SER>>() : raise_lds_limit<&gram_bandp_kernel<DPAD, G, S, false, SER>>(); \
         if (ae != hipSuccess) return hip_fail(ae, "hipFuncSetAttribute(gram_bandp_kernel)");                       \
         if (comp) hipLaunchKernelGGL((gram_bandp_kernel<DPAD, G, S, true, SER>), grid, block, lds, p.stream, a);   \
         else hipLaunchKernelGGL((gram_bandp_kernel<DPAD, G, S, false, SER>), grid, block, lds, p.stream, a);       \
@@ -816,27 +774,19 @@ int band_launch(const GramProblem &p, bool serial)
     unsigned char *base = nullptr;
     int rc = ws_base(p, w, "band", base);
     if (rc) return rc;
-    BandArgs a;
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
-    a.kflag = ws_at<unsigned char>(base, w.kflag); a.rseg = ws_at<double>(base, w.rseg); a.cslab = ws_at<float>(base, w.cslab);
+    BandArgs a{}; // (band_launch_variant takes the plan's tile map)
+    fill_sweep_args(a, p, w, base);
     a.wsk = ws_at<float>(base, w.wsk);
     a.wsk_per_wave = band_wsk_per_pair(p.T, p.n);
-    a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.n = p.n;
-    a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
+    a.n = p.n;
     {
         bool rev = false;
         (void)band_comp(p.T, p.d, p.n, &rev);
         a.comprev = rev ? 1 : 0;
     }
-    a.nitems = 0;
     const GradGeom &g = w.g;
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg, 0, 8 * sizeof(unsigned long long), p.stream);
-        a.stamps = dbg;
-    }
+    a.stamps = phase_stamps_begin(p.stream);
 #endif
     if (serial)
         rc = p.d <= 8 ? band_launch_variant<8, true>(p, a, g, grad, sym) : band_launch_variant<16, true>(p, a, g, grad, sym);
@@ -844,19 +794,10 @@ int band_launch(const GramProblem &p, bool serial)
         rc = p.d <= 8 ? band_launch_variant<8, false>(p, a, g, grad, sym) : band_launch_variant<16, false>(p, a, g, grad, sym);
     if (rc) return rc;
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        unsigned long long hs[8];
-        (void)hipStreamSynchronize(p.stream);
-        (void)hipMemcpy(hs, a.stamps, sizeof(hs), hipMemcpyDeviceToHost);
-        double tot = 0;
-        for (int k = 0; k < 8; ++k) tot += (double)hs[k];
-        static const char *nm[8] = {"staging/other", "static kernel", "forward steps", "forward barriers + idle phases",
-                                    "reverse steps", "reverse barriers + idle phases", "verdict + coarse gradient / wait", "-"};
-        fprintf(stderr, "[phase stamps band %s] A=%d T=%d d=%d n=%d grad=%d sym=%d: ", serial ? "serial" : "parallel", p.A, p.T, p.d,
-                p.n, grad ? 1 : 0, sym ? 1 : 0);
-        for (int k = 0; k < 7; ++k) fprintf(stderr, "%s %.1f%% | ", nm[k], 100.0 * (double)hs[k] / tot);
-        fprintf(stderr, "total %.3e wave-cycles\n", tot);
-    }
+    static const char *const nm[] = {"staging/other", "static kernel", "forward steps", "forward barriers + idle phases",
+                                      "reverse steps", "reverse barriers + idle phases", "verdict + coarse gradient / wait"};
+    phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps band %s] A=%d T=%d d=%d n=%d grad=%d sym=%d: ",
+                        serial ? "serial" : "parallel", p.A, p.T, p.d, p.n, grad ? 1 : 0, sym ? 1 : 0);
 #endif
     return finish_launch(p, w, base, sym, g.tm, g.NW, p.gradX_out, p.dtype == SIGSVGD_F64);
 }

@@ -44,34 +44,6 @@ constexpr int DTMAX = 33; // coarse points per path
 constexpr int DHN = 136;  // hand-over rows: entries 0 .. 129 are read
 
 #include "quad_sweeps.h"
-
-__device__ __forceinline__ double d_ldany(const void *b, size_t i, int io64)
-{
-    return io64 ? static_cast<const double *>(b)[i] : (double)static_cast<const float *>(b)[i];
-}
-__device__ __forceinline__ float d_max3_abs(float m, float a, float b)
-{
-    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b));
-    return m;
-}
-__device__ __forceinline__ void d_stany(void *b, size_t i, double v, int io64)
-{
-    if (io64)
-        static_cast<double *>(b)[i] = v;
-    else
-        static_cast<float *>(b)[i] = (float)v;
-}
-// sum over the 64 lanes in six DPP adds; the total ends up in lane 63
-__device__ __forceinline__ float d_wave_sum63(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); // row_shr:1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, true)); // row_shr:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, true)); // row_shr:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, true)); // row_shr:8
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, true)); // row_bcast:15 into rows 1, 3
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, true)); // row_bcast:31 into rows 2, 3
-    return v;
-}
 } // namespace
 
 // FEW (forward-only launches of paths in <= 3 channels, 8-channel layout): the forward steps also accumulate sum |K_fwd * D|,
@@ -140,8 +112,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
         __syncthreads();
         for (int e = tid; e < T * DPAD; e += NT) {
             const int t = e / DPAD, c = e % DPAD;
-            const double r0 = c < d ? d_ldany(a.Y, (size_t)j * T * d + c, io64) : 0.0;
-            const double v = c < d ? d_ldany(a.Y, ((size_t)j * T + t) * d + c, io64) - r0 : 0.0;
+            const double r0 = c < d ? load_any(a.Y, (size_t)j * T * d + c, io64) : 0.0;
+            const double v = c < d ? load_any(a.Y, ((size_t)j * T + t) * d + c, io64) - r0 : 0.0;
             yd[t * (DPAD + 1) + c] = v;
             yf[t * DPAD + c] = (float)v;
             if (t == 0) yref[c] = r0;
@@ -156,8 +128,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
             float w_ij = 1.f, w_ji = 1.f;
             if (GRAD) {
                 if (a.go) {
-                    w_ij = (float)d_ldany(a.go, (size_t)i * a.B + j, io64);
-                    if (SYM || a.symw) w_ji = (float)d_ldany(a.go, (size_t)j * a.B + i, io64);
+                    w_ij = (float)load_any(a.go, (size_t)i * a.B + j, io64);
+                    if (SYM || a.symw) w_ji = (float)load_any(a.go, (size_t)j * a.B + i, io64);
                     if (a.symw) { w_ij += w_ji; w_ji = w_ij; }
                 } else if (a.symw) {
                     w_ij = 2.f; w_ji = 2.f;
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                 double xs[DPAD], xn = 0.0;
 #pragma unroll
                 for (int c = 0; c < DPAD; ++c) {
-                    const double xc = c < d ? d_ldany(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c] : 0.0;
+                    const double xc = c < d ? load_any(a.X, ((size_t)i * T + m) * d + c, io64) - yref[c] : 0.0;
                     xn = __builtin_fma(xc, xc, xn);
                     xs[c] = xc * (2.0 * inv_h);
                     xf[c] = (float)xc;
@@ -276,9 +248,9 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                     quad_fwd_all<0, true, FEW ? 1 : 0>(fc, fuA, fuB, fV, Dsl, Ssl, wr, rows, hbf, haddr, hinc, r3, nrows + ncols, cnd);
                     asm volatile("" ::: "memory");
                     if (!kdone) { // (the slots: K at the cells' upper left corners; fc: the row's last value so far)
-                        kmax = d_max3_abs(kmax, fc, fc);
+                        kmax = max3_abs(kmax, fc, fc);
 #pragma unroll
-                        for (int k = 0; k < 64; k += 2) kmax = d_max3_abs(kmax, Ssl[k], Ssl[k + 1]);
+                        for (int k = 0; k < 64; k += 2) kmax = max3_abs(kmax, Ssl[k], Ssl[k + 1]);
                     }
                 }
                 if (b == 0 && h == 0) {
@@ -301,13 +273,13 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                     const float kden = fmaxf(fabsf(kfin), 0.1f);
                     bool fl = kmax > (n >= 5 ? 1.5f : (d == 1 ? 2.f : d == 2 ? 4.f : 8.f)) * kden;
                     if constexpr (FEW) { // conditioning bound of a forward-only launch (gram_fast.hip); sqrt(12) gamma = the fine increment
-                        const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d_wave_sum63(cnd)), 63));
+                        const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
                         fl = fl || sds * 3.46410161513775459f * fmaxf(kmax, 1.f) > 300.f * kden;
                     }
                     const bool cancelled = __builtin_amdgcn_ballot_w64(kfin == kfin && fl) != 0;
                     if (lanep == nrows - 1) {
-                        d_stany(a.K, (size_t)i * a.B + j, (double)fc, io64);
-                        if (SYM && j != i) d_stany(a.K, (size_t)j * a.B + i, (double)fc, io64);
+                        store_any(a.K, (size_t)i * a.B + j, (double)fc, io64);
+                        if (SYM && j != i) store_any(a.K, (size_t)j * a.B + i, (double)fc, io64);
                         if (!GRAD) a.kflag[(size_t)i * a.B + j] = cancelled ? 1 : 0; // (gradient launches: with the condition number, below)
                     }
                     kfin_keep = kfin;
@@ -382,7 +354,7 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                     if (d <= 3) {
                         float cs = 0.f;
                         for (int e = lanep; e < Tm * Tm; e += 64) cs = __builtin_fmaf(fabsf((float)wl.Sc[e]), fabsf(wl.Dc[e]), cs);
-                        const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(d_wave_sum63(cs)), 63));
+                        const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cs)), 63));
                         ill = kfin_keep == kfin_keep && c1 * 3.46410161513775459f > 150.f * fmaxf(fabsf(kfin_keep), 0.1f);
                     }
                     // (`lane`, not the per-pair opaque copy `lanep`: with `lanep == 0` hipcc reuses the mask it formed for the sweeps'
@@ -546,12 +518,9 @@ int dyad_launch(const GramProblem &p)
     unsigned char *base = nullptr;
     int rc = ws_base(p, w, "dyad", base);
     if (rc) return rc;
-    DyadArgs a;
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
-    a.kflag = ws_at<unsigned char>(base, w.kflag); a.rseg = ws_at<double>(base, w.rseg); a.cslab = ws_at<float>(base, w.cslab);
-    a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.n = p.n;
-    a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
-    a.nitems = 0;
+    DyadArgs a{}; // (dyad_launch_variant takes the plan's tile map)
+    fill_sweep_args(a, p, w, base);
+    a.n = p.n;
     const GradGeom &g = w.g;
     if (g.NW == 4)
         rc = p.d <= 8 ? dyad_launch_variant<8, 4>(p, a, g, grad, sym) : dyad_launch_variant<16, 4>(p, a, g, grad, sym);

@@ -37,9 +37,6 @@
 #include <atomic>
 
 #include "sig_common.h"
-#ifdef SIGSVGD_PHASE_STAMPS
-#include <cstdio>
-#endif
 
 namespace sigsvgd {
 
@@ -69,19 +66,6 @@ struct FastArgs {
     unsigned long long *stamps; // diagnostic build only: [8] shader-clock totals per phase, summed over waves
 #endif
 };
-
-// Diagnostic build (-DSIGSVGD_PHASE_STAMPS, scripts/dev/phase_stamps.py): s_memtime around the phases of a pair,
-// summed per wave in scalar registers and added to a buffer no output depends on.  Compiled out of the product.
-#ifdef SIGSVGD_PHASE_STAMPS
-#define SIG_STAMP(i)                                                         \
-    {                                                                        \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
-        ph_[i] += now_ - tlast_;                                             \
-        tlast_ = now_;                                                       \
-    }
-#else
-#define SIG_STAMP(i)
-#endif
 
 // ---- wave-wide shifts on the DPP path ----------------------------------------------------------
 // wave_shr:1 (0x138): lane l reads lane l-1; wave_shl:1 (0x130): lane l reads lane l+1.
@@ -160,7 +144,6 @@ __device__ __forceinline__ float add_rol1(float acc, float v)
     asm("v_add_f32_dpp %0, %1, %2 wave_rol:1 row_mask:0xf bank_mask:0xf" : "=v"(out) : "v"(acc), "v"(v));
     return out;
 }
-__device__ __forceinline__ float dpp_shr1_zero(float v) { return __int_as_float(dpp_shr1_z(__float_as_int(v))); }
 
 // ---- one step of a PDE sweep, hand-scheduled (fp32 difference form, see phase 2 in the kernel) ------------------
 // Every instruction of a step is listed here because the properties that make it fast are scheduling properties.
@@ -349,24 +332,6 @@ __device__ __forceinline__ double resweep_fwd_fp64(const float (&Dsl)[RING], int
     }
     return cur;
 }
-// Sum over the lanes in DPP adds (no LDS round trip).  Lane 31 ends with the total of lanes 0 .. 31; lane 63 with the
-// total of ALL 64 lanes if `whole`, else of lanes 32 .. 63 (two pairs per wavefront).
-template <bool WHOLE>
-__device__ __forceinline__ float wave_sum_dpp(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); // row_shr:1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, true)); // row_shr:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, true)); // row_shr:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, true)); // row_shr:8 (lane 15 of a row: its total)
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, true)); // row_bcast:15 into rows 1, 3
-    if (WHOLE) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, true)); // row_bcast:31 into rows 2, 3
-    return v;
-}
-__device__ __forceinline__ float max3_abs(float m, float a, float b)
-{
-    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b));
-    return m;
-}
 
 // [slot][lane] image of G (then R*G) with row stride 65 floats: every in-sweep access is
 // lane*4 + constant (one ds instruction with an immediate offset, nothing to keep in registers),
@@ -376,23 +341,6 @@ constexpr int GS_WAVE = 64 * GS_STRIDE;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_STRIDE + lane; }
-
-template <typename IO>
-__device__ __forceinline__ double load_io(const void *base, size_t idx)
-{
-    return (double)static_cast<const IO *>(base)[idx];
-}
-__device__ __forceinline__ double load_any(const void *base, size_t idx, int io64)
-{
-    return io64 ? load_io<double>(base, idx) : load_io<float>(base, idx);
-}
-__device__ __forceinline__ void store_any(void *base, size_t idx, double v, int io64)
-{
-    if (io64)
-        static_cast<double *>(base)[idx] = v;
-    else
-        static_cast<float *>(base)[idx] = (float)v;
-}
 
 // LP: the last of the DPAD channels is padding (d == DPAD - 1, e.g. the 7-DoF arm at DPAD = 8): its FMA in the
 // static kernel and its travelling column sum are dropped.
@@ -774,7 +722,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     // shifted S and formed the neighbour's difference a second time: one instruction more per iteration,
                     // 5.38 -> 5.25 ms per C4 launch in a same-box A/B; the result is the same bit for bit)
                     const float e = Sb - Snew;
-                    const float up = dpp_shr1_zero(e); // lane l-1: S[l-1][q+2] - S[l-1][q+1]; lane 0: no row above
+                    const float up = shfl_up_zero(e); // lane l-1: S[l-1][q+2] - S[l-1][q+1]; lane 0: no row above
                     const float R = eprev - up;
                     eprev = e;
                     Sb = Snew;
@@ -1156,12 +1104,7 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     a.tm = tm;
     a.nitems = total;
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, 8 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg, 0, 8 * sizeof(unsigned long long), p.stream);
-        a.stamps = dbg;
-    }
+    a.stamps = phase_stamps_begin(p.stream);
 #endif
     const long long resident = (long long)ncu * (grad ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : (NW == 4 ? ((DPAD <= 8) ? 3 : 2) : 1)); // workgroups the chip holds at once (LDS / VGPR bound)
     dim3 grid((unsigned)(total < resident ? total : resident), 1);
@@ -1191,19 +1134,9 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(p.stream);
-        (void)hipMemcpy(h, a.stamps, sizeof(h), hipMemcpyDeviceToHost);
-        double tot = 0;
-        for (int k = 0; k < 8; ++k) tot += (double)h[k];
-        static const char *nm[8] = {"staging/other", "phase 0+1 static kernel", "phase 2 forward sweep",
-                                    "phase 3 reverse sweep", "phase 4 gradient pass", "pair epilogue",
-                                    "barrier after the pair", "-"};
-        fprintf(stderr, "[phase stamps] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
-        for (int k = 0; k < 7; ++k) fprintf(stderr, "%s %.1f%% | ", nm[k], 100.0 * (double)h[k] / tot);
-        fprintf(stderr, "total %.3e wave-cycles\n", tot);
-    }
+    static const char *const nm[] = {"staging/other", "phase 0+1 static kernel", "phase 2 forward sweep", "phase 3 reverse sweep",
+                                      "phase 4 gradient pass", "pair epilogue", "barrier after the pair"};
+    phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
 #endif
     return SIGSVGD_OK;
 }
@@ -1221,40 +1154,28 @@ int dispatch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool gr
     return launch_variant<16, 4>(p, a, w, grad, sym, tile_rows); // 1 wave per SIMD: 512-VGPR budget, no spills
 }
 
-// cut the workspace from the plan, enqueue the kernel, the fp64 pass and (gradient) the reduction into `out`
-int run(const GramProblem &p, FastArgs &a, const WsPlan &w, bool sym, void *out, int out64)
+// cut the workspace from the plan, enqueue the kernel over the row tiles `own` says (off / stride / fold: the tile count is the
+// kernel's), the fp64 pass and (gradient) the reduction into `out`
+int run(const GramProblem &p, const WsPlan &w, bool sym, const TileMap &own, void *out, int out64)
 {
     unsigned char *base = nullptr;
     int rc = ws_base(p, w, "fast", base);
     if (rc) return rc;
-    a.kflag = ws_at<unsigned char>(base, w.kflag);
-    a.rseg = ws_at<double>(base, w.rseg);
-    a.cslab = ws_at<float>(base, w.cslab);
+    FastArgs a{};
+    fill_sweep_args(a, p, w, base);
+    a.tm = own;
     int tile_rows = 0;
     rc = dispatch_variant(p, a, w, out != nullptr, sym, tile_rows);
     if (rc) return rc;
     return finish_launch(p, w, base, sym, a.tm, tile_rows, out, out64);
-}
-
-void fill_args(const GramProblem &p, FastArgs &a)
-{
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
-    a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d;
-    a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
-    a.tm = make_tilemap(1, 0, 1, false); a.nitems = 0; // (off / stride / fold are what launch_variant reads: a full launch)
-    a.rseg = nullptr;
-    a.cslab = nullptr;
-    a.kflag = nullptr;
 }
 } // namespace
 
 int fast_launch(const GramProblem &p)
 {
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B; // Y is X: each unordered pair once, K mirrored
-    FastArgs a;
-    fill_args(p, a);
     const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym);
-    return run(p, a, w, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
+    return run(p, w, sym, make_tilemap(1, 0, 1, false), p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 // Symmetric partial solve for particle sharding: this launch owns the row tiles tile_offset + k*tile_stride of the upper
@@ -1262,12 +1183,9 @@ int fast_launch(const GramProblem &p)
 // grad_partial[N,T,d] (fp64) is OVERWRITTEN with this launch's share of the gradient (rows it does not touch get 0).
 int fast_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial)
 {
-    FastArgs a;
-    fill_args(p, a);
-    a.Y = p.X;
-    a.tm = make_tilemap((p.A + grad_nw(p.T, p.d) - 1) / grad_nw(p.T, p.d), tile_offset, tile_stride, fold);
     const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold);
-    return run(p, a, w, true, grad_partial, 1);
+    return run(p, w, true, make_tilemap((p.A + grad_nw(p.T, p.d) - 1) / grad_nw(p.T, p.d), tile_offset, tile_stride, fold),
+               grad_partial, 1);
 }
 
 } // namespace sigsvgd

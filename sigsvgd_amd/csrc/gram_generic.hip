@@ -15,27 +15,9 @@
 //
 // Reference semantics: sigkernel _SigKernelGram.forward/backward [RECALLED, SURVEY.md App. A];
 // static kernel src/kernels/_traj_kernels.py:176-195.
-#include <atomic>
-
 #include "sig_common.h"
-#ifdef SIGSVGD_PHASE_STAMPS
-#include <cstdio>
-#endif
 
 namespace sigsvgd {
-
-// Diagnostic build (-DSIGSVGD_PHASE_STAMPS, scripts/dev/phase_stamps.py N T d dyadic<n>): s_memtime per phase, summed
-// over waves and printed after the launch.  Compiled out of the product.
-#ifdef SIGSVGD_PHASE_STAMPS
-#define SIG_GSTAMP(i)                                                        \
-    {                                                                        \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
-        gph_[i] += now_ - gtl_;                                              \
-        gtl_ = now_;                                                         \
-    }
-#else
-#define SIG_GSTAMP(i)
-#endif
 
 struct GenericArgs {
     const void *X, *Y, *grad_out;
@@ -152,7 +134,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
     };
 
 #ifdef SIGSVGD_PHASE_STAMPS
-    unsigned long long gph_[6] = {0, 0, 0, 0, 0, 0}, gtl_ = __builtin_amdgcn_s_memtime();
+    unsigned long long ph_[6] = {0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
     for (long long round = 0;; ++round) {
         long long item;
@@ -229,7 +211,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             }
             __syncthreads();
 
-            SIG_GSTAMP(0)
+            SIG_STAMP(0)
             // ---- phase 1: static kernel rows -> increments D (fp64 arithmetic, stored as DT) ----
             for (int rb = 0; rb < (big ? 0 : Tm); rb += kWave - 1) { // (big: per band, below)
                 const int p = rb + lane;
@@ -250,7 +232,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             }
             __syncthreads();
 
-            SIG_GSTAMP(1)
+            SIG_STAMP(1)
             // ---- phase 2: forward Goursat sweep ------------------------------------------------
             // One wave, one dependent chain: a step costs what its instruction count costs (~5 cycles each), plus every
             // load it has to wait for.  So the step is branch-free (results of lanes outside the grid are computed and
@@ -295,7 +277,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                 if (a.yx && j != i) Kout[(size_t)j * a.B + i] = (IO)Kval;
             }
 
-            SIG_GSTAMP(2)
+            SIG_STAMP(2)
             if (!GRAD) continue;
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
             __syncthreads();
@@ -364,7 +346,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             if (big) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before the assembly reads it
             __syncthreads();
 
-            SIG_GSTAMP(3)
+            SIG_STAMP(3)
             // ---- phase 4: chain S -> R -> static-kernel derivative -> per-point gradient --------
             double w = 1.0;
             if (GO) {
@@ -424,7 +406,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                     }
                 }
             }
-            SIG_GSTAMP(4)
+            SIG_STAMP(4)
             // ---- phase 4b (Y is X, j != i): the same pair seen from x_j, d k(x_j, x_i) / d x_j ---------
             if (a.yx && j != i) {
                 double wc = 1.0;
@@ -467,7 +449,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                     }
                 }
             }
-            SIG_GSTAMP(5)
+            SIG_STAMP(5)
         } // j
 
         if (GRAD && !big) {
@@ -476,9 +458,9 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
         }
     }
 #ifdef SIGSVGD_PHASE_STAMPS
-    SIG_GSTAMP(0)
+    SIG_STAMP(0)
     if (lane == 0 && a.stamps)
-        for (int k = 0; k < 6; ++k) atomicAdd(&a.stamps[k], gph_[k]);
+        for (int k = 0; k < 6; ++k) atomicAdd(&a.stamps[k], ph_[k]);
 #endif
 }
 
@@ -601,18 +583,9 @@ namespace {
 template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT>
 hipError_t generic_launch_one(const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
-    // (once per instantiation, for the largest size any plan can ask for: the call costs ~10 us of host time, which a small
-    //  launch -- the fp64 pass behind a 50-us kernel -- would pay every time
-    //  -- per DEVICE: the attribute belongs to the current device's copy of the function, and a process may drive several)
-    static std::atomic<unsigned long long> raised{0}; // bit = device ordinal (devices >= 64: raised every time)
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64 || !((raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) raised.fetch_or(1ull << dev, std::memory_order_release);
-    }
+    // (the largest size any plan can ask for)
+    const hipError_t e = raise_lds_limit<&gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT>>();
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL((gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
     return hipSuccess;
 }
@@ -670,30 +643,17 @@ int generic_launch(const GramProblem &p, bool precise, bool any_size)
     a.flags = nullptr; a.tm = make_tilemap(1, 0, 1, false); a.tile_rows = 1;
 
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, 6 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg, 0, 6 * sizeof(unsigned long long), p.stream);
-        a.stamps = dbg;
-    }
+    a.stamps = phase_stamps_begin(p.stream);
 #endif
     hipError_t e = generic_dispatch(p.dtype == SIGSVGD_F64, a.naive != 0, want_grad != 0, pl.big != 0, pl, p.stream, a);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(generic)");
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_generic_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        unsigned long long hs[6];
-        (void)hipStreamSynchronize(p.stream);
-        (void)hipMemcpy(hs, a.stamps, sizeof(hs), hipMemcpyDeviceToHost);
-        double tot = 0;
-        for (int k = 0; k < 6; ++k) tot += (double)hs[k];
-        static const char *nm[6] = {"staging/other", "phase 1 static kernel", "forward sweep", "reverse sweep",
-                                    "phase 4 gradient", "phase 4b column side"};
-        fprintf(stderr, "[phase stamps generic] A=%d T=%d d=%d n=%d grad=%d: ", p.A, p.T, p.d, p.n, want_grad);
-        for (int k = 0; k < 6; ++k) fprintf(stderr, "%s %.1f%% | ", nm[k], 100.0 * (double)hs[k] / tot);
-        fprintf(stderr, "total %.3e wave-cycles\n", tot);
-    }
+    static const char *const nm[] = {"staging/other", "phase 1 static kernel", "forward sweep", "reverse sweep", "phase 4 gradient",
+                                      "phase 4b column side"};
+    phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps generic] A=%d T=%d d=%d n=%d grad=%d: ", p.A, p.T, p.d, p.n,
+                        want_grad);
 #endif
     if (want_grad) {
         const int TD = p.T * p.d;

@@ -62,17 +62,6 @@ struct QuadArgs {
 #endif
 };
 
-#ifdef SIGSVGD_PHASE_STAMPS
-#define SIG_QSTAMP(i)                                                        \
-    {                                                                        \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
-        ph_[i] += now_ - tlast_;                                             \
-        tlast_ = now_;                                                       \
-    }
-#else
-#define SIG_QSTAMP(i)
-#endif
-
 namespace {
 #ifndef SIGQ_NW // (-DSIGQ_NW=4: one wavefront per SIMD, a timing experiment of scripts/dev/ab_quad.py)
 #define SIGQ_NW 8
@@ -92,10 +81,6 @@ constexpr float QUAD_CANCEL_RATIO = SIGQ_CANCEL_RATIO;
 constexpr int QREC = 6656;
 using qf32x2 = __attribute__((ext_vector_type(2))) float;
 
-__device__ __forceinline__ double q_ldany(const void *b, size_t i, int io64)
-{
-    return io64 ? static_cast<const double *>(b)[i] : (double)static_cast<const float *>(b)[i];
-}
 // n consecutive elements (stride 1) as doubles, ONE uniform branch on the I/O type and independent loads (a branch
 // per element serialises the loads behind one s_waitcnt each)
 template <int N>
@@ -118,40 +103,6 @@ __device__ __forceinline__ void q_ldrow(const void *b, size_t i0, int nvalid, in
 #pragma unroll
         for (int c = 0; c < N; ++c) out[c] = (c < nvalid) ? (double)tmp[c] : 0.0;
     }
-}
-__device__ __forceinline__ float q_max3_abs(float m, float a, float b)
-{
-    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b));
-    return m;
-}
-__device__ __forceinline__ void q_stany(void *b, size_t i, double v, int io64)
-{
-    if (io64)
-        static_cast<double *>(b)[i] = v;
-    else
-        static_cast<float *>(b)[i] = (float)v;
-}
-// lane l <- lane l+1; lane 63 keeps `old` (compiler-visible DPP: hipcc pads its hazards)
-__device__ __forceinline__ double q_shl_keep(double v, double old)
-{
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), 0x130, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), 0x130, 0xF, 0xF, false);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float q_shr_zero(float v) // lane l <- lane l-1, lane 0 gets 0
-{
-    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xF, 0xF, true));
-}
-// sum over the 64 lanes in six DPP adds (no LDS round trips); the total ends up in lane 63
-__device__ __forceinline__ float q_wave_sum63(float v)
-{
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); // row_shr:1
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, true)); // row_shr:2
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, true)); // row_shr:4
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, true)); // row_shr:8 (inclusive scan of each row of 16)
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, true)); // row_bcast:15 into rows 1, 3
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, true)); // row_bcast:31 into rows 2, 3
-    return v;
 }
 // G[m][n] = 2^(-log2(e)/h * |x~_m - y~_n|^2) in fp32, from the DIFFERENCES (the expanded form loses 6e-8 of its largest
 // term, 1e-5 of G for rough paths).  ONE expression for the gradient pass and both seam passes: the row-side sums
@@ -179,34 +130,6 @@ __device__ __forceinline__ float q_add_ror1(float acc, float v)
     float out;
     asm("v_add_f32_dpp %0, %1, %2 wave_ror:1 row_mask:0xf bank_mask:0xf" : "=v"(out) : "v"(acc), "v"(v));
     return out;
-}
-
-// 2^t as in sig_common.h (exp2_p7), with the coefficients in scalar registers: under this kernel's register pressure
-// hipcc otherwise materialises them as VGPR pairs and spills those (16 scratch round trips per use site)
-struct QExp7 {
-    double c7, c6, c5, c4, c3, c2, c1, c0;
-};
-__device__ __forceinline__ QExp7 qexp7_coef()
-{
-    return QExp7{1.5303701161442145e-05, 1.5469729221575116e-04, 1.3333478471058548e-03, 9.618025613268967e-03,
-                 5.5504109063307244e-02, 2.4022651213498578e-01, 6.931471805568296e-01,  0.9999999999595621};
-}
-__device__ __forceinline__ void qexp7_pin(QExp7 &k)
-{
-    asm volatile("" : "+s"(k.c7), "+s"(k.c6), "+s"(k.c5), "+s"(k.c4), "+s"(k.c3), "+s"(k.c2), "+s"(k.c1), "+s"(k.c0));
-}
-__device__ __forceinline__ double qexp2_p7(double t, const QExp7 &k)
-{
-    const double kf = __builtin_rint(t);
-    const double f = t - kf;
-    double p = __builtin_fma(k.c7, f, k.c6);
-    p = __builtin_fma(p, f, k.c5);
-    p = __builtin_fma(p, f, k.c4);
-    p = __builtin_fma(p, f, k.c3);
-    p = __builtin_fma(p, f, k.c2);
-    p = __builtin_fma(p, f, k.c1);
-    p = __builtin_fma(p, f, k.c0);
-    return ldexp(p, (int)kf);
 }
 
 #include "quad_sweeps.h"
@@ -323,7 +246,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
         asm volatile("" : "+v"(tidp), "+v"(lanep));
         // ---- stage y_j (centred on its first point): fp64 rows + scaled norms, fp32 copy, both twice ----------
         __syncthreads();
-        SIG_QSTAMP(10)
+        SIG_STAMP(10)
         constexpr int EPT = (128 * DPAD) / NT; // elements per thread: all loads of a thread are issued together
         double sv[EPT], sr[EPT];
         if (io64) {
@@ -375,13 +298,13 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
         }
         __syncthreads();
 
-        SIG_QSTAMP(7)
+        SIG_STAMP(7)
         if (row_ok && (!SYM || j >= i)) {
             float w_ij = 1.f, w_ji = 1.f; // row-side / column-side weights
             if (GRAD) {
                 if (a.go) {
-                    w_ij = (float)q_ldany(a.go, (size_t)i * a.B + j, io64);
-                    if (SYM || a.symw) w_ji = (float)q_ldany(a.go, (size_t)j * a.B + i, io64);
+                    w_ij = (float)load_any(a.go, (size_t)i * a.B + j, io64);
+                    if (SYM || a.symw) w_ji = (float)load_any(a.go, (size_t)j * a.B + i, io64);
                     if (a.symw) { w_ij += w_ji; w_ji = w_ij; }
                 } else if (a.symw) {
                     w_ij = 2.f; w_ji = 2.f;
@@ -391,7 +314,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 
             // ---- G row 64 (the row beyond band 0): differences along the row for lane 63 of band 0 ------------
             {
-                QExp7 ek = qexp7_coef();
+                Exp2Coef7 ek = exp2_coef7();
                 double xs2[DPAD], xn2 = 0.0, xr2[DPAD];
                 q_ldrow<DPAD>(a.X, ((size_t)i * T + 64) * d, d, io64, xr2);
 #pragma unroll
@@ -408,7 +331,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     double e2 = xn2 + yr[DPAD];
 #pragma unroll
                     for (int c = 0; c < DPAD; ++c) e2 = __builtin_fma(xs2[c], yr[c], e2);
-                    g64[lanep + 64 * hh] = qexp2_p7(e2, ek);
+                    g64[lanep + 64 * hh] = exp2_p7(e2, ek);
                 }
                 if (GRAD) {
 #pragma unroll
@@ -488,7 +411,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                 const bool rev = (code & 4) != 0, leave_k = (code & 8) != 0;
                 const int dmode = (code >> 4) & 3, dslot = code >> 6;
                 const int nrows = b ? nrows1 : 64, ncols = h ? nrows1 : 64;
-                QExp7 ek = qexp7_coef();
+                Exp2Coef7 ek = exp2_coef7();
                 int lv = lanep; // per-visit copy the optimiser cannot see through: address vectors built from it stay inside
                 asm volatile("" : "+v"(lv)); // the visit instead of becoming spilled loop invariants
                 const int m = 64 * b + lv; // point row of this lane
@@ -508,7 +431,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                 }
                 xn = __builtin_fma(xn, nscale, -1.79248125036057809); // - log2(sqrt(12)): D slots hold D / sqrt(12)
 
-                SIG_QSTAMP(0)
+                SIG_STAMP(0)
                 // ---- phase 1: G row (skewed: local column (t - lane) & 63 on iteration t) -> D slots --------------
                 if (dmode == 2) { // second visit of the quadrant: the increments come back from the launch's scratch (L2)
                     const float *dp = dcw + dslot * 4096 + lv;
@@ -528,7 +451,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                         double e2 = xn + yr[DPAD];
 #pragma unroll
                         for (int c = 0; c < DPAD; ++c) e2 = __builtin_fma(xs[c], yr[c], e2);
-                        g64v = qexp2_p7(e2, ek);
+                        g64v = exp2_p7(e2, ek);
                     }
                     const double *rdhh = rdh + 64 * h;
                     double g0 = 0.0, g1 = 0.0, gprev = 0.0, rdprev = 0.0;
@@ -551,8 +474,8 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                                 for (int c = 0; c <= DPAD; ++c)
                                     if (c < DC || c == DPAD) yrow[c] = yr[c];
                             }
-                            qexp7_pin(ek);
-                            g = qexp2_p7(e2, ek);
+                            exp2_coef7_pin(ek);
+                            g = exp2_p7(e2, ek);
                             if (t == 0) g0 = g;
                             if (t == 1) g1 = g;
                         } else {
@@ -567,7 +490,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                             // row beyond the band (G row 64) from LDS: a virtual lane 64 is at local column t & 63
                             const int cc = (t & 63) ? (t & 63) : 64;
                             const double beyond = (64 * h + cc < 128) ? rdhh[cc] : 0.0;
-                            const double nb = q_shl_keep(rd, beyond);
+                            const double nb = shfl_down_f64(rd, beyond);
                             Dsl[(t - 2) & 63] = (float)(nb - rdprev);
                             asm volatile("" : "+v"(Dsl[(t - 2) & 63])); // formed here (hipcc otherwise sinks it to the sweep)
                         }
@@ -581,7 +504,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     }
                 }
 
-                SIG_QSTAMP(1)
+                SIG_STAMP(1)
                 // ---- phase 2: forward sweep of the quadrant -----------------------------------------------------
                 if (!KSTORE || dmode != 2) {
                     const float *topb = (b ? hK : ones) + 64 * h; // K[64 b][64 h + q + 1] for lane 0 on step sigma = q
@@ -612,9 +535,9 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     quad_fwd_all<0, EARLY, FEW ? 1 : 0>(fc, fuA, fuB, fV, Dsl, Ssl, wr, rows, hbf, haddr, hinc, r3, nrows + ncols, cnd);
                     asm volatile("" ::: "memory");
                     if (!kdone) { // (the slots: K at the cells' upper left corners; fc: the row's last value so far)
-                        kmax = q_max3_abs(kmax, fc, fc);
+                        kmax = max3_abs(kmax, fc, fc);
 #pragma unroll
-                        for (int k = 0; k < 64; k += 2) kmax = q_max3_abs(kmax, Ssl[k], Ssl[k + 1]);
+                        for (int k = 0; k < 64; k += 2) kmax = max3_abs(kmax, Ssl[k], Ssl[k + 1]);
                     }
                     if (KSTORE && dmode == 1) { // reverse sweep and gradient pass follow on a later visit
                         float *kp = dcw + (3 + dslot) * 4096 + lv;
@@ -628,7 +551,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     svA = fuA;
                     svB = fuB;
                 }
-                SIG_QSTAMP(2)
+                SIG_STAMP(2)
                 if (!kdone && b == b_last && h == h_last) { // K[P][P]: last value of the last row with cells
                     kdone = true;
                     // a pair whose solution cancelled (see gram_fast.hip, resweep_fwd_fp64) is marked for the fp64 pass
@@ -638,13 +561,13 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     //  loses the same ~2e-6 of the LARGEST value on its grid as one that oscillates)
                     bool fl = kmax > (d == 1 ? 2.f : d == 2 ? 4.f : QUAD_CANCEL_RATIO) * kden;
                     if constexpr (FEW) { // conditioning bound of a forward-only launch: sum |K_fwd D| max(grid maximum, 1) > 300 max(|K|, 0.1)
-                        const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q_wave_sum63(cnd)), 63));
+                        const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
                         fl = fl || sds * 3.46410161513775459f * fmaxf(kmax, 1.f) > 300.f * kden;
                     }
                     const bool cancelled = __builtin_amdgcn_ballot_w64(kfin == kfin && fl) != 0;
                     if (lanep == nrows - 1) {
-                        q_stany(a.K, (size_t)i * a.B + j, (double)fc, io64);
-                        if (SYM && j != i) q_stany(a.K, (size_t)j * a.B + i, (double)fc, io64);
+                        store_any(a.K, (size_t)i * a.B + j, (double)fc, io64);
+                        if (SYM && j != i) store_any(a.K, (size_t)j * a.B + i, (double)fc, io64);
                         if (!GRAD && a.kflag) a.kflag[(size_t)i * a.B + j] = cancelled ? 1 : 0; // (gradient launches: after the last reverse sweep)
                     }
                     kfin_keep = kfin;
@@ -690,7 +613,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     for (int k = 0; k < 64; ++k) cs = __builtin_fmaf(fabsf(Ssl[k]), fabsf(Dsl[k]), cs);
                     cnd += cs;
                 }
-                SIG_QSTAMP(3)
+                SIG_STAMP(3)
                 // ---- seam rows for the hand-over pass: S[63][.] (band 0, lane 63), S[64][.] (band 1, lane 0) ------
                 // (slot k of lane l is local column (k - l) & 63; the index is formed from scalars: per-lane index vectors
                 //  are loop invariants that hipcc hoists out of the pair loop and spills -- 64 serialised scratch loads)
@@ -713,14 +636,14 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
                     for (int c = 0; c < DPAD; ++c) tacc[c] = 0.f;
                     float capA = 0.f, capB = 0.f;
-                    float Nc = q_shr_zero(Ssl[62]); // S[l-1][n-1]
-                    float Nb = q_shr_zero(Ssl[63]); // S[l-1][n]
+                    float Nc = shfl_up_zero(Ssl[62]); // S[l-1][n-1]
+                    float Nb = shfl_up_zero(Ssl[63]); // S[l-1][n]
                     float Sprev = Ssl[63];          // S[l][n-1]
                     const float *yfb = yf + (128 * h + 64 - lv) * YFS;
                     qf32x2 ynx[DPAD / 2]; // the y~ row of the next iteration (fetched one iteration ahead)
 #pragma unroll
                     for (int c = 0; c < DPAD / 2; ++c) ynx[c] = c < DC / 2 ? reinterpret_cast<const qf32x2 *>(yfb)[c] : qf32x2{0.f, 0.f};
-                    SIG_QSTAMP(6)
+                    SIG_STAMP(6)
 #pragma unroll
                     for (int it = 0; it < 64; ++it) {
                         qf32x2 yr2[DPAD / 2];
@@ -732,7 +655,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                             for (int c = 0; c < DC / 2; ++c) ynx[c] = yn[c];
                         }
                         const float Scur = Ssl[it];
-                        const float Na = q_shr_zero(Scur); // S[l-1][n+1]
+                        const float Na = shfl_up_zero(Scur); // S[l-1][n+1]
                         const bool wrap = lv == it;        // local column 0
                         float R = ((Nc - Nb) + (Scur - Sprev)) * rowmask;
                         capA = wrap ? Scur : capA;
@@ -764,7 +687,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
-                    SIG_QSTAMP(4)
+                    SIG_STAMP(4)
                     if (h == 0) {
                         cap0h0 = capA;
                         cap63h0 = capB;
@@ -778,14 +701,14 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                     }
                 }
 
-                SIG_QSTAMP(8)
+                SIG_STAMP(8)
                 // ---- the band's seam columns (after its left quadrant): point columns 0 and 64 ---------------------
                 if (h == 0) {
 #pragma unroll
                     for (int sc = 0; sc < 2; ++sc) {
                         // E_l = S[l][n-1] - S[l][n];  R[m][n] = E_{l-1} - E_l
                         const float E = sc ? (cap63h0 - cap0h1) : -cap0h0;
-                        const float R = (q_shr_zero(E) - E) * rowmask;
+                        const float R = (shfl_up_zero(E) - E) * rowmask;
                         qf32x2 ys2[DPAD / 2];
 #pragma unroll
                         for (int c = 0; c < DPAD / 2; ++c) ys2[c] = reinterpret_cast<const qf32x2 *>(yf + (128 * sc) * YFS)[c];
@@ -799,7 +722,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                             const float rgw = rg * w_ji;
 #pragma unroll
                             for (int c = 0; c < DPAD; ++c) {
-                                const float vsum = q_wave_sum63(rgw * dfs[c / 2][c % 2]);
+                                const float vsum = wave_sum_dpp<true>(rgw * dfs[c / 2][c % 2]);
                                 if (lv == 63) SIGQ_CRW[6 * CS * 64 + (2 * b + sc) * CS + c] = vsum; // seam record [band][column 0 / 64]
                             }
                         }
@@ -823,16 +746,16 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                         }
                     }
                 }
-                SIG_QSTAMP(5)
+                SIG_STAMP(5)
             } // quadrant visits
 
-            SIG_QSTAMP(0)
+            SIG_STAMP(0)
             if (GRAD && a.kflag) {
                 // the pair's verdict for the exact fp64 pass: cancellation of magnitudes (forward sweep) or, in <= 3 channels,
                 // the condition number c1 = sum |S D| / max(|K|, 0.1) > 150 (gram_fast.hip, "conditioning")
                 bool ill = false;
                 if (DPAD == 8 && d <= 3) {
-                    const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q_wave_sum63(cnd)), 63));
+                    const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
                     ill = kfin_keep == kfin_keep && c1 * 3.46410161513775459f > 150.f * fmaxf(fabsf(kfin_keep), 0.1f);
                 }
                 if (lanep == 0) a.kflag[(size_t)i * a.B + j] = (canc_keep || ill) ? 1 : 0;
@@ -870,14 +793,14 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                 // row 64 belongs to band 1's lane 0 accumulators
 #pragma unroll
                 for (int c = 0; c < DPAD; ++c) {
-                    const float v = q_wave_sum63(w_ij * m2h * part[c]); // total in lane 63
+                    const float v = wave_sum_dpp<true>(w_ij * m2h * part[c]); // total in lane 63
                     if (lanep == 63 && c < d) { // (row 64 receives nothing else: band 1's lane 0 is masked out of the band flush)
                         if (rowlds) atomicAdd(rowacc + 64 * RS + min(c, RS - 1) + (lanep - 63), v);
                         else unsafeAtomicAdd(SIGQ_RGW + 64 * 16 + c + (lanep - 63), v);
                     }
                 }
             }
-            SIG_QSTAMP(6)
+            SIG_STAMP(6)
         } // this wavefront's pair
 
         if (GRAD && SYM) {
@@ -923,7 +846,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                 }
                 if (n < T && c < d) dstc[n * d + c] = -m2h * sx;
             }
-            SIG_QSTAMP(9)
+            SIG_STAMP(9)
         }
     }
     if (GRAD && row_ok) { // the segment's row-side sums: consecutive lanes on consecutive addresses
@@ -939,13 +862,13 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                                       : __hip_atomic_load(SIGQ_RGW + m * 16 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         }
     }
-    SIG_QSTAMP(11)
+    SIG_STAMP(11)
     remaining -= ncol;
     ++kq;
     cstart = 0;
     } // row tiles of the range
 
-    SIG_QSTAMP(0)
+    SIG_STAMP(0)
 #ifdef SIGSVGD_PHASE_STAMPS
     if (lane == 0 && a.stamps)
         for (int k = 0; k < 12; ++k) atomicAdd(&a.stamps[k], ph_[k]);
@@ -987,12 +910,7 @@ int quad_launch_variant(const GramProblem &p, QuadArgs &a, const GradGeom &g, bo
     a.nitems = g.nitems;
     dim3 grid((unsigned)g.grid), block(QNW * 64);
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) (void)hipMalloc(&dbg, 12 * sizeof(unsigned long long));
-        (void)hipMemsetAsync(dbg, 0, 12 * sizeof(unsigned long long), p.stream);
-        a.stamps = dbg;
-    }
+    a.stamps = phase_stamps_begin(p.stream);
 #endif
     constexpr bool HAS_ROWG = DPAD == 16;
     const bool rowg = HAS_ROWG && grad && p.d > 14;
@@ -1021,43 +939,24 @@ int quad_launch_variant(const GramProblem &p, QuadArgs &a, const GradGeom &g, bo
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_quad_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
-    {
-        unsigned long long hst[12];
-        (void)hipStreamSynchronize(p.stream);
-        (void)hipMemcpy(hst, a.stamps, sizeof(hst), hipMemcpyDeviceToHost);
-        double tot = 0;
-        for (int k = 0; k < 12; ++k) tot += (double)hst[k];
-        static const char *nm[12] = {"staging/other", "phase 1 static kernel", "forward sweep", "reverse sweep",
-                                     "gradient pass", "seams + row sums", "row seam (+ gradient-pass prologue)", "Y staging",
-                                     "column-sum LDS adds", "closing barrier + column-side flush", "barrier before staging", "row-side flush"};
-        fprintf(stderr, "[phase stamps quad] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
-        for (int k = 0; k < 12; ++k) fprintf(stderr, "%s %.1f%% | ", nm[k], 100.0 * (double)hst[k] / tot);
-        fprintf(stderr, "total %.3e wave-cycles\n", tot);
-    }
+    static const char *const nm[] = {"staging/other", "phase 1 static kernel", "forward sweep", "reverse sweep", "gradient pass",
+                                      "seams + row sums", "row seam (+ gradient-pass prologue)", "Y staging", "column-sum LDS adds",
+                                      "closing barrier + column-side flush", "barrier before staging", "row-side flush"};
+    phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps quad] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad,
+                        (int)sym);
 #endif
     return SIGSVGD_OK;
 }
 
-void quad_fill_args(const GramProblem &p, QuadArgs &a)
-{
-    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
-    a.rseg = nullptr; a.cslab = nullptr; a.crec = nullptr; a.rowg = nullptr;
-    a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d;
-    a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
-    a.tm = make_tilemap(1, 0, 1, false); // (quad_launch_variant takes the plan's tile map)
-    a.nitems = 0; a.dcache = nullptr; a.kflag = nullptr;
-}
-
 // cut the workspace from the plan, enqueue the kernel, the fp64 pass and (gradient) the fixed-order reduction into `out` (the
 // I/O type, or fp64 for the partial solve)
-int quad_run(const GramProblem &p, QuadArgs &a, const WsPlan &w, bool sym, void *out, int out64)
+int quad_run(const GramProblem &p, const WsPlan &w, bool sym, void *out, int out64)
 {
     unsigned char *base = nullptr;
     int rc = ws_base(p, w, "quad", base);
     if (rc) return rc;
-    a.kflag = ws_at<unsigned char>(base, w.kflag);
-    a.rseg = ws_at<double>(base, w.rseg);
-    a.cslab = ws_at<float>(base, w.cslab);
+    QuadArgs a{}; // (quad_launch_variant takes the plan's tile map)
+    fill_sweep_args(a, p, w, base);
     a.crec = ws_at<float>(base, w.crec);
     a.rowg = ws_at<float>(base, w.rowg);
     a.dcache = ws_at<float>(base, w.dcache);
@@ -1071,10 +970,8 @@ int quad_run(const GramProblem &p, QuadArgs &a, const WsPlan &w, bool sym, void 
 int quad_launch(const GramProblem &p)
 {
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B; // Y is X: each unordered pair once
-    QuadArgs a;
-    quad_fill_args(p, a);
     const WsPlan w = quad_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym);
-    return quad_run(p, a, w, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
+    return quad_run(p, w, sym, p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
 // Sharded partial solve (sigsvgd_gram_sym_partial) for the long-path shapes: row tiles of 8 rows, tiles
@@ -1082,10 +979,8 @@ int quad_launch(const GramProblem &p)
 // OVERWRITTEN with this launch's share of the gradient.
 int quad_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial)
 {
-    QuadArgs a;
-    quad_fill_args(p, a);
     const WsPlan w = quad_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold);
-    return quad_run(p, a, w, true, grad_partial, 1);
+    return quad_run(p, w, true, grad_partial, 1);
 }
 
 } // namespace sigsvgd

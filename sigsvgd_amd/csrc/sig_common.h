@@ -3,6 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#ifdef SIGSVGD_PHASE_STAMPS
+#include <cstdarg>
+#include <cstdio>
+#endif
+
 #include "../../include/sigsvgd_hip.h"
 
 namespace sigsvgd {
@@ -39,66 +45,30 @@ __device__ __forceinline__ double exp64(double a0)
     return (a0 != a0) ? a0 : e; // a NaN in a path poisons its own row / column of K, as in the reference
 }
 
-// 2^t for the register-resident kernel: t arrives already scaled by log2(e) (the scale is folded into
-// the particle coordinates), so the reduction is exact: k = rint(t), f = t - k in [-1/2, 1/2], and
-// 2^f is a degree-8 Chebyshev-interpolant (max relative error 1.1e-12, measured on 2e4 points;
-// the 4-corner increments need ~1e-10).  12 fp64-rate instructions.
-__device__ __forceinline__ double exp2_p8(double t)
-{
-    const double kf = __builtin_rint(t);
-    const double f = t - kf;
-    double p = 1.3255197199834888e-06;
-    p = __builtin_fma(p, f, 1.5310079063632544e-05);
-    p = __builtin_fma(p, f, 1.5403455940423864e-04);
-    p = __builtin_fma(p, f, 1.3333450569733936e-03);
-    p = __builtin_fma(p, f, 9.618129159303683e-03);
-    p = __builtin_fma(p, f, 5.550410941203932e-02);
-    p = __builtin_fma(p, f, 2.4022650695813685e-01);
-    p = __builtin_fma(p, f, 6.931471805459342e-01);
-    p = __builtin_fma(p, f, 0.9999999999999997);
-    return ldexp(p, (int)kf);
-}
-
-// Degree-7 variant (max relative error 5.5e-11 on [-1/2, 1/2]) for the register-resident kernel, whose
-// increments are rounded to fp32 (6e-8 relative) right after: one Horner step fewer per static-kernel value.
-__device__ __forceinline__ double exp2_p7(double t)
-{
-    const double kf = __builtin_rint(t);
-    const double f = t - kf;
-    double p = 1.5303701161442145e-05;
-    p = __builtin_fma(p, f, 1.5469729221575116e-04);
-    p = __builtin_fma(p, f, 1.3333478471058548e-03);
-    p = __builtin_fma(p, f, 9.618025613268967e-03);
-    p = __builtin_fma(p, f, 5.5504109063307244e-02);
-    p = __builtin_fma(p, f, 2.4022651213498578e-01);
-    p = __builtin_fma(p, f, 6.931471805568296e-01);
-    p = __builtin_fma(p, f, 0.9999999999595621);
-    return ldexp(p, (int)kf);
-}
-
-// Same polynomial with the coefficients handed in by the caller, who keeps them in scalar registers inside
-// a rolled loop (empty `asm volatile("" : "+s"(c))` per iteration): hipcc otherwise hoists them into
-// VGPRs and pays one v_mov_b64 per Horner step to feed v_fmac_f64.
-struct Exp2Coef {
-    double c8, c7, c6, c5, c4, c3, c2, c1, c0;
+// 2^t for the register-resident kernels: t arrives already scaled by log2(e) (the scale is folded into the particle
+// coordinates), so the reduction is exact: k = rint(t), f = t - k in [-1/2, 1/2], and 2^f is a degree-7 polynomial (max
+// relative error 5.5e-11 on [-1/2, 1/2]; the kernels' increments are rounded to fp32, 6e-8 relative, right after).
+struct Exp2Coef7 {
+    double c7, c6, c5, c4, c3, c2, c1, c0;
 };
-__device__ __forceinline__ Exp2Coef exp2_coef()
+__device__ __forceinline__ Exp2Coef7 exp2_coef7()
 {
-    return Exp2Coef{1.3255197199834888e-06, 1.5310079063632544e-05, 1.5403455940423864e-04,
-                    1.3333450569733936e-03, 9.618129159303683e-03,  5.550410941203932e-02,
-                    2.4022650695813685e-01, 6.931471805459342e-01,  0.9999999999999997};
+    return Exp2Coef7{1.5303701161442145e-05, 1.5469729221575116e-04, 1.3333478471058548e-03, 9.618025613268967e-03,
+                     5.5504109063307244e-02, 2.4022651213498578e-01, 6.931471805568296e-01,  0.9999999999595621};
 }
-__device__ __forceinline__ void exp2_coef_pin(Exp2Coef &k)
+// A caller under register pressure keeps the coefficients in scalar registers: it makes them once and pins them in every
+// iteration of its rolled loop (an empty `asm volatile("" : "+s"(c))`); hipcc otherwise materialises them as VGPR pairs
+// (one v_mov_b64 per Horner step to feed v_fmac_f64) and may spill those (gram_quad.hip: 16 scratch round trips per use
+// site).
+__device__ __forceinline__ void exp2_coef7_pin(Exp2Coef7 &k)
 {
-    asm volatile("" : "+s"(k.c8), "+s"(k.c7), "+s"(k.c6), "+s"(k.c5), "+s"(k.c4), "+s"(k.c3), "+s"(k.c2), "+s"(k.c1),
-                 "+s"(k.c0));
+    asm volatile("" : "+s"(k.c7), "+s"(k.c6), "+s"(k.c5), "+s"(k.c4), "+s"(k.c3), "+s"(k.c2), "+s"(k.c1), "+s"(k.c0));
 }
-__device__ __forceinline__ double exp2_p8(double t, const Exp2Coef &k)
+__device__ __forceinline__ double exp2_p7(double t, const Exp2Coef7 &k)
 {
     const double kf = __builtin_rint(t);
     const double f = t - kf;
-    double p = __builtin_fma(k.c8, f, k.c7);
-    p = __builtin_fma(p, f, k.c6);
+    double p = __builtin_fma(k.c7, f, k.c6);
     p = __builtin_fma(p, f, k.c5);
     p = __builtin_fma(p, f, k.c4);
     p = __builtin_fma(p, f, k.c3);
@@ -107,6 +77,7 @@ __device__ __forceinline__ double exp2_p8(double t, const Exp2Coef &k)
     p = __builtin_fma(p, f, k.c0);
     return ldexp(p, (int)kf);
 }
+__device__ __forceinline__ double exp2_p7(double t) { return exp2_p7(t, exp2_coef7()); }
 
 // ---- Goursat stencils -------------------------------------------------------------------------
 // default (second order):  K11 = (K10 + K01)*(1 + g/2 + g^2/12) - K00*(1 - g^2/12)
@@ -124,33 +95,99 @@ __device__ __forceinline__ double stencil(double k10, double k01, double k00, do
     return __builtin_fma(k00, b, u);
 }
 
-template <typename T>
-__device__ __forceinline__ double ld_as_f64(const T *p, size_t i)
+// one element of the fp32 / fp64 (io64) I/O arrays as a double, and a double stored back
+__device__ __forceinline__ double load_any(const void *b, size_t i, int io64)
 {
-    return (double)p[i];
+    return io64 ? static_cast<const double *>(b)[i] : (double)static_cast<const float *>(b)[i];
+}
+__device__ __forceinline__ void store_any(void *b, size_t i, double v, int io64)
+{
+    if (io64)
+        static_cast<double *>(b)[i] = v;
+    else
+        static_cast<float *>(b)[i] = (float)v;
 }
 
-template <typename T>
-__device__ __forceinline__ void st_from_f64(T *p, size_t i, double v)
-{
-    p[i] = (T)v;
-}
-
-// Neighbour-lane moves of a double as two DPP moves (wave_shr:1 / wave_shl:1; the lane without a source keeps its own
-// value).  __shfl_up / __shfl_down lower to ds_bpermute: an LDS round trip (~100 cycles) on the dependent chain of
-// every PDE step, against ~8 cycles here.
-__device__ __forceinline__ double shfl_up_f64(double v)   // lane l <- lane l-1 (lane 0 keeps own)
+// Neighbour-lane moves as DPP moves (wave_shr:1 / wave_shl:1).  __shfl_up / __shfl_down lower to ds_bpermute: an LDS round
+// trip (~100 cycles) on the dependent chain of every PDE step, against ~8 cycles here.  Compiler-visible DPP: hipcc pads
+// their hazards itself.
+__device__ __forceinline__ double shfl_up_f64(double v) // lane l <- lane l-1 (lane 0 keeps own)
 {
     const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), 0x138, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), 0x138, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
 }
-__device__ __forceinline__ double shfl_down_f64(double v) // lane l <- lane l+1 (lane 63 keeps own)
+__device__ __forceinline__ double shfl_down_f64(double v, double old) // lane l <- lane l+1 (lane 63 gets `old`)
 {
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), 0x130, 0xF, 0xF, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), 0x130, 0xF, 0xF, false);
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), 0x130, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), 0x130, 0xF, 0xF, false);
     return __hiloint2double(hi, lo);
 }
+__device__ __forceinline__ double shfl_down_f64(double v) { return shfl_down_f64(v, v); } // (lane 63 keeps own)
+__device__ __forceinline__ float shfl_up_zero(float v) // lane l <- lane l-1, lane 0 gets 0
+{
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xF, 0xF, true));
+}
+
+// Sum over the lanes in DPP adds (no LDS round trip).  Lane 31 ends with the total of lanes 0 .. 31; lane 63 with the
+// total of ALL 64 lanes if `WHOLE`, else of lanes 32 .. 63 (two pairs per wavefront in gram_fast.hip).
+template <bool WHOLE>
+__device__ __forceinline__ float wave_sum_dpp(float v)
+{
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true)); // row_shr:1
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x112, 0xF, 0xF, true)); // row_shr:2
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x114, 0xF, 0xF, true)); // row_shr:4
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x118, 0xF, 0xF, true)); // row_shr:8 (lane 15 of a row: its total)
+    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xA, 0xF, true)); // row_bcast:15 into rows 1, 3
+    if (WHOLE) v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, true)); // row_bcast:31 into rows 2, 3
+    return v;
+}
+// max(m, |a|, |b|) in one v_max3_f32
+__device__ __forceinline__ float max3_abs(float m, float a, float b)
+{
+    asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b));
+    return m;
+}
+
+// ---- phase stamps (diagnostic build -DSIGSVGD_PHASE_STAMPS, scripts/dev/phase_stamps.py) -----------------------------------
+// s_memtime around the phases of a kernel, summed per wave in scalar registers (the kernel declares `ph_[phases]` and `tlast_`)
+// and added to a buffer no output depends on; the launcher prints each phase's share.  Compiled out of the product.
+#ifdef SIGSVGD_PHASE_STAMPS
+#define SIG_STAMP(i)                                                         \
+    {                                                                        \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime();        \
+        ph_[i] += now_ - tlast_;                                             \
+        tlast_ = now_;                                                       \
+    }
+constexpr int kMaxPhases = 16;
+// the per-phase totals of the next launch on `stream`, zeroed (one buffer: every report below synchronises)
+inline unsigned long long *phase_stamps_begin(hipStream_t stream)
+{
+    static unsigned long long *buf = nullptr;
+    if (!buf) (void)hipMalloc(&buf, kMaxPhases * sizeof(unsigned long long));
+    (void)hipMemsetAsync(buf, 0, kMaxPhases * sizeof(unsigned long long), stream);
+    return buf;
+}
+// after the launch: one stderr line "<printf(fmt, ...)><name> <share>% | ... total <n> wave-cycles" over the phases named
+template <int N>
+void phase_stamps_report(hipStream_t stream, const unsigned long long *buf, const char *const (&names)[N], const char *fmt, ...)
+{
+    static_assert(N <= kMaxPhases, "more phases than the buffer holds");
+    unsigned long long h[kMaxPhases];
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost);
+    double tot = 0;
+    for (int k = 0; k < kMaxPhases; ++k) tot += (double)h[k];
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    for (int k = 0; k < N; ++k) fprintf(stderr, "%s %.1f%% | ", names[k], 100.0 * (double)h[k] / tot);
+    fprintf(stderr, "total %.3e wave-cycles\n", tot);
+}
+#else
+#define SIG_STAMP(i)
+#endif
 
 // ---- EXEC discipline of the hand-written sweep statements ----------------------------------------------------------------
 // The sweep statements (gram_fast.hip sweep_fwd8 / sweep_rev8, quad_sweeps.h) move lane windows into EXEC and leave it at
@@ -276,6 +313,35 @@ int ws_base(const GramProblem &p, const WsPlan &w, const char *family, unsigned 
 // each), then the fixed-order gradient reduction into `out` (fp64 when out64; NULL: a forward-only launch)
 int finish_launch(const GramProblem &p, const WsPlan &w, unsigned char *base, bool sym, const TileMap &tm, int tile_rows,
                   void *out, int out64);
+
+// the arguments every fp32-sweep family (FastArgs, QuadArgs, DyadArgs, BandArgs) takes from the problem and from its plan's
+// workspace; the launchers set the rest
+template <typename Args>
+void fill_sweep_args(Args &a, const GramProblem &p, const WsPlan &w, unsigned char *base)
+{
+    a.X = p.X; a.Y = p.Y; a.go = p.grad_out; a.K = p.K_out;
+    a.kflag = ws_at<unsigned char>(base, w.kflag); a.rseg = ws_at<double>(base, w.rseg); a.cslab = ws_at<float>(base, w.cslab);
+    a.io64 = p.dtype == SIGSVGD_F64; a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d;
+    a.symw = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.inv_h = p.inv_h;
+}
+
+// Raises the dynamic-LDS limit of `KERNEL` to the 160 KB of a CU, once per instantiation and device: the call costs ~10 us
+// of host time, which a small launch -- the fp64 pass behind a 50-us kernel -- would pay every time, and the attribute
+// belongs to the current device's copy of the function (a process may drive several; devices >= 64: raised every time).
+template <auto KERNEL>
+hipError_t raise_lds_limit()
+{
+    static std::atomic<unsigned long long> raised{0}; // bit = device ordinal
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !((raised.load(std::memory_order_acquire) >> dev) & 1ull)) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           160 * 1024);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) raised.fetch_or(1ull << dev, std::memory_order_release);
+    }
+    return hipSuccess;
+}
 
 // ---- kernel families --------------------------------------------------------------------------------------------------
 // *_supported: the shapes a family's kernels take (dyadic order n; RBF static kernel, second-order solver).  Only gram_route
