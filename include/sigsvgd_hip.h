@@ -27,6 +27,8 @@
  *                          called by PathSigKernel, src/kernels/_traj_kernels.py:124-125
  *   sigsvgd_signature_backward  its autograd backward: PathSigKernel has analytic_grad=False (:92), so the reference
  *                          differentiates K THROUGH the signature (src/inference/score.py:50-55, svgd.py:41-43)
+ *   sigsvgd_pde_fwd        the PDE of sigkernel.SigKernel on a static kernel the CALLER evaluated (any object with
+ *   sigsvgd_pde_fwd_bwd    Gram_matrix / batch_kernel): K per grid, and the adjoint with respect to the grid
  *
  * Conventions
  *   - all pointers are DEVICE pointers (HIP), row-major contiguous; the caller owns every buffer
@@ -75,7 +77,7 @@
 extern "C" {
 #endif
 
-#define SIGSVGD_ABI_VERSION 9
+#define SIGSVGD_ABI_VERSION 10
 
 /* dtype */
 #define SIGSVGD_F32 0
@@ -251,6 +253,28 @@ int sigsvgd_signature(const void *X, int N, int L, int C, int depth, int basepoi
  * 6 * channels doubles of LDS (channels <= ~3000), else SIGSVGD_E_UNSUPPORTED. */
 int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L, int C, int depth, int basepoint, int dtype,
                                void *grad_X, void *stream);
+
+/* ---- signature PDE on a caller's static-kernel grid (ABI 10; user static kernels) -----------------
+ * Replaces the PDE part of sigkernel.SigKernel.compute_Gram / compute_kernel for a static kernel the library does not
+ * evaluate itself: the caller passes the static kernel's values G[npairs][M][N] (contiguous, fp32 or fp64 by `dtype`;
+ * Gram_matrix(X, Y) -> [A, B, M, N] is A*B pairs, batch_kernel(X, Y) -> [A, M, N] is A pairs; M != N allowed).  Per pair:
+ * the 4-corner increments D[a][b] = G[a+1][b+1] + G[a][b] - G[a+1][b] - G[a][b+1] in fp64 (fp32 input too), refined to
+ * g[p][q] = D[p >> n][q >> n] / r^2 on the P x Q grid (r = 2^dyadic_order, P = r (M-1), Q = r (N-1)), one Goursat sweep
+ * in fp64 with the second-order stencil (SIGSVGD_FLAG_NAIVE_SOLVER: the first-order one):
+ *   K_out[pair] = sol[P][Q]
+ * and, sigsvgd_pde_fwd_bwd, dG_out[pair][M][N] = d( sum_pair grad_out[pair] K[pair] ) / dG in the reference's convention
+ * (exact for the naive stencil; the one the built-in kernels return): GG[p][q] = K_fwd[p][q] K_rev[p+1][q+1],
+ * S[a][b] = r^-2 sum of GG over block (a, b), dG[m][n] = grad_out (S[m-1][n-1] + S[m][n] - S[m-1][n] - S[m][n-1]), S = 0
+ * outside.  grad_out == NULL means ones.  The stored forward solution and S are fp32, the sweeps fp64.
+ * Any flag bit other than SIGSVGD_FLAG_NAIVE_SOLVER is SIGSVGD_E_BADARG.  P and Q up to 8192 (upstream's GPU path takes
+ * P + 1, Q + 1 <= 1023); beyond that SIGSVGD_E_UNSUPPORTED.  Bit-reproducible (no floating-point atomics).
+ * The workspace is sized by the resident wavefronts, not by npairs (one pair per wavefront; forward-only launches need
+ * none and report 0 bytes); want_grad = 1 for sigsvgd_pde_fwd_bwd. */
+int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes);
+int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags, void *K_out,
+                    void *workspace, size_t workspace_bytes, void *stream);
+int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags,
+                        const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@ _CSRC = os.path.join(_PKG, "csrc")
 # SIGSVGD_LIB_PATH: A/B benchmarking of two builds on the same GPU box (scripts/ab.py); never set in tests
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
-           "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip"]
+           "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
+           "sig_pde.hip"]
 HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"),
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
@@ -25,7 +26,7 @@ STATIC_RBF, STATIC_LINEAR = 0, 1
 FLAG_NAIVE_SOLVER, FLAG_SYM, FLAG_Y_IS_X, FLAG_FORCE_GENERIC, FLAG_WS_CLEAN, FLAG_STORED_FORWARD = 1, 2, 4, 8, 16, 32
 FLAG_FOLD_TILES = 64
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 EXPORTS = [
     "sigsvgd_abi_version",
@@ -45,6 +46,9 @@ EXPORTS = [
     "sigsvgd_signature",
     "sigsvgd_signature_backward",
     "sigsvgd_obstacle_cost",
+    "sigsvgd_pde_workspace_bytes",
+    "sigsvgd_pde_fwd",
+    "sigsvgd_pde_fwd_bwd",
 ]
 
 _lib = None
@@ -178,6 +182,12 @@ def load():
     L.sigsvgd_signature.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ctypes.POINTER(ctypes.c_longlong), vp]
     L.sigsvgd_signature_backward.restype = ci
     L.sigsvgd_signature_backward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.sigsvgd_pde_workspace_bytes.restype = ci
+    L.sigsvgd_pde_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_pde_fwd.restype = ci
+    L.sigsvgd_pde_fwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_pde_fwd_bwd.restype = ci
+    L.sigsvgd_pde_fwd_bwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

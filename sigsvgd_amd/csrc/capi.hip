@@ -45,6 +45,9 @@ int signature_launch(const void *X, int N, int L, int C, int depth, int basepoin
                      hipStream_t stream);
 int signature_bwd_launch(const void *X, const void *gsig, int N, int L, int C, int depth, int basepoint, int dtype, void *gX,
                          long long sigdim, hipStream_t stream);
+int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes);
+int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, const void *grad_out, void *K_out,
+               void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream);
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
@@ -75,6 +78,29 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
     }
     if ((flags & SIGSVGD_FLAG_SYM) && A != B) {
         set_error("sym backward needs A == B");
+        return SIGSVGD_E_BADARG;
+    }
+    return SIGSVGD_OK;
+}
+
+// the shape, dtype, order and flag checks of the PDE entry points (sig_pde.hip): only SIGSVGD_FLAG_NAIVE_SOLVER means
+// anything there, every other bit is refused
+static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
+{
+    if (npairs < 1 || M < 2 || N < 2) {
+        set_error("pde: bad shape npairs=%d M=%d N=%d (need npairs >= 1, M, N >= 2)", npairs, M, N);
+        return SIGSVGD_E_BADARG;
+    }
+    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) {
+        set_error("pde: bad dtype %d", dtype);
+        return SIGSVGD_E_BADARG;
+    }
+    if (n < 0 || n > 10) {
+        set_error("pde: bad dyadic order %d", n);
+        return SIGSVGD_E_BADARG;
+    }
+    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER) {
+        set_error("pde: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
@@ -480,6 +506,45 @@ int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L
     }
     Range range("sigsvgd_signature_backward");
     return signature_bwd_launch(X, grad_sig, N, L, C, depth, basepoint, dtype, grad_X, ch, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes)
+{
+    if (!bytes) {
+        set_error("bytes == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags);
+    if (rc) return rc;
+    return pde_workspace(npairs, M, N, dyadic_order, want_grad ? 1 : 0, bytes);
+}
+
+int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags, void *K_out,
+                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!G || !K_out) {
+        set_error("pde_fwd: null pointer argument");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
+    if (rc) return rc;
+    Range range("sigsvgd_pde_fwd");
+    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, nullptr, K_out, nullptr,
+                      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags,
+                        const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!G || !K_out || !dG_out) {
+        set_error("pde_fwd_bwd: null pointer argument");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
+    if (rc) return rc;
+    Range range("sigsvgd_pde_fwd_bwd");
+    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, grad_out, K_out, dG_out,
+                      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

@@ -566,3 +566,85 @@ def obstacle_cost(x, start, target, basis, log_weights, mean, std, w_obstacle: f
                                      grad.data_ptr() if want_grad else None, _stream_ptr(dev))
     _lib.check(rc, "obstacle_cost")
     return cost, traj, grad
+
+
+# ---- signature PDE on a caller's static-kernel grid (user static kernels) -------------------------
+def _prep_grid(G: torch.Tensor) -> torch.Tensor:
+    if G.dim() != 3:
+        raise ValueError(f"static-kernel grids must be [npairs, M, N]; got {tuple(G.shape)}")
+    if G.shape[0] == 0:
+        raise ValueError("empty batch")
+    if G.shape[1] < 2 or G.shape[2] < 2:
+        raise ValueError(f"static-kernel grids need at least 2 x 2 points; got {tuple(G.shape)}")
+    _io_dtype(G)
+    return G.detach().contiguous()
+
+
+def pde_fwd(G, dyadic_order: int = 0, naive: bool = False) -> torch.Tensor:
+    """K[npairs] = signature kernel of each pair from its static-kernel grid G [npairs, M, N] (`sigsvgd_pde_fwd`): fp64
+    increments and sweeps, K in G's dtype."""
+    dev = _require_gpu(G)
+    L = _lib.load()
+    Gc = _prep_grid(G)
+    npairs, M, N = Gc.shape
+    flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_pde_workspace_bytes(npairs, M, N, int(dyadic_order), 0, flags, ctypes.byref(nbytes)),
+               "pde_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_pde_fwd(Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, K.data_ptr(),
+                               ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "pde_fwd")
+    return K
+
+
+def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = None,
+                naive: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(K[npairs], dG[npairs, M, N]) with dG = d sum(grad_out * K) / dG (`sigsvgd_pde_fwd_bwd`; grad_out None = ones), in
+    the reference's convention GG = K_fwd * K_rev (the exact adjoint for the naive stencil; what the built-in kernels
+    return).  Bit-reproducible."""
+    dev = _require_gpu(G, grad_out)
+    L = _lib.load()
+    Gc = _prep_grid(G)
+    npairs, M, N = Gc.shape
+    go = None
+    if grad_out is not None:
+        if grad_out.numel() != npairs:
+            raise ValueError(f"grad_out must have {npairs} entries, got {tuple(grad_out.shape)}")
+        go = grad_out.detach().reshape(npairs).to(Gc.dtype).contiguous()
+    flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_pde_workspace_bytes(npairs, M, N, int(dyadic_order), 1, flags, ctypes.byref(nbytes)),
+               "pde_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
+    dG = torch.empty_like(Gc)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_pde_fwd_bwd(Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags,
+                                   go.data_ptr() if go is not None else None, K.data_ptr(), dG.data_ptr(),
+                                   ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "pde_fwd_bwd")
+    return K, dG
+
+
+class PDESolve(torch.autograd.Function):
+    """K[...] = signature kernel of every static-kernel grid G[..., M, N] (any leading shape).  Backward: dG from one
+    `pde_fwd_bwd` launch with the incoming weights, so gradients reach whatever produced G -- the paths through a user's
+    `Gram_matrix`, and that static kernel's own parameters."""
+
+    @staticmethod
+    def forward(ctx, G, dyadic_order, naive):
+        lead, (M, N) = tuple(G.shape[:-2]), tuple(G.shape[-2:])
+        Gf = G.detach().reshape(-1, M, N)
+        ctx.cfg = (lead, int(dyadic_order), bool(naive))
+        ctx.save_for_backward(Gf)
+        return pde_fwd(Gf, dyadic_order, naive).reshape(lead)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (Gf,) = ctx.saved_tensors
+        lead, dyadic_order, naive = ctx.cfg
+        _, dG = pde_fwd_bwd(Gf, dyadic_order, grad_output.reshape(-1), naive)
+        return dG.reshape(lead + tuple(Gf.shape[-2:])), None, None

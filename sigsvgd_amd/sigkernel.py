@@ -13,6 +13,14 @@ This module provides those names on top of libsigsvgd_hip.so, so `sys.modules["s
 sigsvgd_amd.sigkernel` makes the reference's own code run on the MI355X path.
 `compute_Gram` is an autograd node: backward receives grad_output [A,B] and returns the gradient
 for X only (None for everything else), like upstream.
+
+Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
+`BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed).  Any other object
+with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally, `batch_kernel(X, Y) -> [A,M,N]`) is a USER static
+kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
+the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
+`Gram_matrix` and to the static kernel's own parameters.  The grid costs A*B*M*N elements of memory: large batches
+belong on the built-in kernels.  Objects without `Gram_matrix` raise NotImplementedError.
 """
 from __future__ import annotations
 
@@ -122,18 +130,20 @@ def inv_bandwidth_from_fn(get_bandwidth, X, Y) -> float:
 
 
 def _resolve_static(static_kernel, X, Y):
-    """-> (static_kind, inv_h).  Accepts this module's kernels, anything exposing `static_kind` +
-    `inv_bandwidth` (sigsvgd_amd.kernels.BatchGaussianKernel) and the REFERENCE's own unpatched
-    `BatchGaussianKernel` (recognised by `get_bandwidth` + `Gram_matrix`; it is an RBF with
-    exp(-dist/h), src/kernels/_traj_kernels.py:176-195).  Arbitrary user static kernels would need
-    their own device code and are rejected (no silent slow path)."""
+    """-> (static_kind, inv_h) for the fused kernels, or (None, None) for a user static kernel.  Fused: this module's
+    kernels, anything exposing `static_kind` + `inv_bandwidth` (sigsvgd_amd.kernels.BatchGaussianKernel) and the
+    REFERENCE's own unpatched `BatchGaussianKernel` (recognised by `get_bandwidth` + `Gram_matrix`; it is an RBF with
+    exp(-dist/h), src/kernels/_traj_kernels.py:176-195).  User: any other object with `Gram_matrix` (its grid goes
+    through ops.PDESolve).  Anything else raises NotImplementedError before any device work."""
     if hasattr(static_kernel, "static_kind") and hasattr(static_kernel, "inv_bandwidth"):
         return int(static_kernel.static_kind), float(static_kernel.inv_bandwidth(X, Y))
     if type(static_kernel).__name__ == "BatchGaussianKernel" and hasattr(static_kernel, "get_bandwidth"):
         return _lib.STATIC_RBF, inv_bandwidth_from_fn(static_kernel.get_bandwidth, X, Y)
+    if hasattr(static_kernel, "Gram_matrix"):
+        return None, None
     raise NotImplementedError(
-        f"static kernel {type(static_kernel).__name__} is not supported by the HIP path "
-        "(supported: RBFKernel, LinearKernel, BatchGaussianKernel)"
+        f"static kernel {type(static_kernel).__name__} is not supported by the HIP path: it needs upstream's "
+        "Gram_matrix(X, Y) (fused: RBFKernel, LinearKernel, BatchGaussianKernel)"
     )
 
 
@@ -196,6 +206,9 @@ class SigKernel:
         """K[i,j] = k_sig(X_i, Y_j), X [A,Tx,d], Y [B,Ty,d] on a HIP device; same dtype/device as X.  Paths of different
         lengths (upstream sigkernel takes them) are padded with their last point, which is exact (ops.pad_to_length)."""
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
+        if static_kind is None:  # user static kernel: its grid, the PDE on the device, autograd through both
+            G = self.static_kernel.Gram_matrix(X, Y if sym else Y.detach())
+            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
         y_is_x = (
             Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype
         )
@@ -213,8 +226,12 @@ class SigKernel:
     #    reference tree never calls these].  All go through compute_Gram, so gradients flow to the FIRST
     #    argument only, with `sym=True` giving the symmetrised weighting for Gram(X, X).
     def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
-        """Paired kernel k_sig(X_i, Y_i) -> [batch] (taken from the Gram launch: batch^2 solves)."""
+        """Paired kernel k_sig(X_i, Y_i) -> [batch] (taken from the Gram launch: batch^2 solves; a user static kernel with
+        `batch_kernel` solves the batch pairs only)."""
         assert X.shape[0] == Y.shape[0], "compute_kernel pairs X_i with Y_i"
+        if _resolve_static(self.static_kernel, X, Y)[0] is None and hasattr(self.static_kernel, "batch_kernel"):
+            G = self.static_kernel.batch_kernel(X, Y.detach())
+            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
         return self.compute_Gram(X, Y).diagonal()
 
     def compute_distance(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
@@ -234,8 +251,25 @@ class SigKernel:
         `K = compute_Gram(X, Y); g = autograd.grad((grad_out*K).sum(), X)` (score.py:68-69)."""
         Yv = X if Y is None else Y
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
+        if static_kind is None:
+            return self._user_gram_and_grad(X, Yv, grad_out, sym)
         return ops.gram_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
                                 y_is_x=Y is None)
+
+    def _user_gram_and_grad(self, X, Y, grad_out, sym):
+        """gram_and_grad for a user static kernel: its grid (with the graph to X), K and dG from one PDE launch, and dG
+        chained to X through the user's Gram_matrix.  Y is held fixed (first-slot derivative); sym weights grad_out +
+        grad_out^T."""
+        Xg = X.detach().requires_grad_(True)
+        with torch.enable_grad():
+            G = self.static_kernel.Gram_matrix(Xg, Y.detach())
+        A, B, M, N = G.shape
+        go = None if grad_out is None else grad_out.detach().to(G.dtype)
+        if sym:
+            go = torch.full((A, B), 2.0, dtype=G.dtype, device=G.device) if go is None else go + go.T
+        K, dG = ops.pde_fwd_bwd(G.detach().reshape(A * B, M, N), self.dyadic_order, go, self._naive_solver)
+        (gX,) = torch.autograd.grad(G, Xg, dG.reshape(A, B, M, N))
+        return K.reshape(A, B), gX
 
 
 def gram_and_grad(kernel: SigKernel, X, Y=None, grad_out=None):

@@ -1,0 +1,109 @@
+"""Host-side checks of the static-grid PDE entry points (`sigsvgd_pde_*`, include/sigsvgd_hip.h) and of the user
+static-kernel route of sigsvgd_amd.sigkernel; no device needed (every call below returns before any device work)."""
+import ctypes
+import re
+import subprocess
+
+import pytest
+import torch
+
+from sigsvgd_amd import _lib
+
+BADARG, UNSUPPORTED = -1, -2
+FAKE = ctypes.c_void_p(4096)  # never dereferenced: every call here fails its argument checks first
+
+
+def lib():
+    try:
+        return _lib.load()
+    except RuntimeError as e:
+        pytest.fail(f"library not built: {e}")
+
+
+def ws_bytes(npairs, M, N, n, want_grad, flags=0):
+    b = ctypes.c_size_t(0)
+    rc = lib().sigsvgd_pde_workspace_bytes(npairs, M, N, n, want_grad, flags, ctypes.byref(b))
+    return rc, b.value
+
+
+def test_pde_symbols_exported():
+    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
+    for name in ("sigsvgd_pde_workspace_bytes", "sigsvgd_pde_fwd", "sigsvgd_pde_fwd_bwd"):
+        assert name in exported and name in _lib.EXPORTS
+    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+
+
+@pytest.mark.parametrize("case", ["null_G", "null_K", "null_dG", "M<2", "N<2", "npairs<1", "dtype", "flag", "order<0",
+                                  "order>10"])
+def test_pde_bad_arguments(case):
+    L = lib()
+    args = dict(G=FAKE, npairs=4, M=5, N=6, dtype=_lib.F64, n=1, flags=0, K=FAKE, dG=FAKE)
+    upd = {"null_G": dict(G=None), "null_K": dict(K=None), "null_dG": dict(dG=None), "M<2": dict(M=1), "N<2": dict(N=1),
+           "npairs<1": dict(npairs=0), "dtype": dict(dtype=7), "flag": dict(flags=_lib.FLAG_SYM), "order<0": dict(n=-1),
+           "order>10": dict(n=11)}[case]
+    a = {**args, **upd}
+    rc = L.sigsvgd_pde_fwd_bwd(a["G"], a["npairs"], a["M"], a["N"], a["dtype"], a["n"], a["flags"], None, a["K"], a["dG"],
+                               FAKE, 1 << 30, None)
+    assert rc == BADARG, _lib.last_error()
+    if case != "null_dG":
+        rc = L.sigsvgd_pde_fwd(a["G"], a["npairs"], a["M"], a["N"], a["dtype"], a["n"], a["flags"], a["K"], FAKE, 1 << 30,
+                               None)
+        assert rc == BADARG, _lib.last_error()
+
+
+def test_pde_workspace_query():
+    rc, b = ws_bytes(100, 10, 10, 4, 1)
+    assert rc == 0 and b > 0
+    assert ws_bytes(100, 10, 10, 4, 1, _lib.FLAG_NAIVE_SOLVER) == (0, b)
+    assert ws_bytes(100, 10, 10, 4, 1, _lib.FLAG_Y_IS_X)[0] == BADARG
+    assert ws_bytes(100, 10, 10, 4, 0) == (0, 0)  # the forward sweep keeps nothing
+    # does not shrink as the grid grows
+    grow = (2, 3, 10, 33, 64, 65, 100, 129, 200, 257)
+    for n in (0, 2):
+        for shape in ([(M, M) for M in grow], [(M, 20) for M in grow], [(20, N) for N in grow]):
+            sizes = []
+            for (M, N) in shape:
+                rc, b = ws_bytes(4096, M, N, n, 1)
+                assert rc == 0, (M, N, n, _lib.last_error())
+                sizes.append(b)
+            assert sizes == sorted(sizes), (n, shape, sizes)
+    # sized by the resident waves: stops growing with npairs
+    sizes = [ws_bytes(k, 30, 30, 2, 1)[1] for k in (1, 10, 100, 10_000, 100_000, 1_000_000)]
+    assert sizes == sorted(sizes) and sizes[-1] == sizes[-2] == sizes[-3]
+    assert sizes[0] < sizes[-1]
+
+
+def test_pde_supported_range():
+    # upstream's GPU path: P + 1 <= 1023 and Q + 1 <= 1023
+    for (M, N, n) in [(1023, 1023, 0), (512, 512, 1), (2, 1023, 0), (1023, 2, 0), (64, 64, 4), (2, 2, 9), (33, 129, 3)]:
+        for g in (0, 1):
+            rc, _ = ws_bytes(1000, M, N, n, g)
+            assert rc == 0, (M, N, n, g, _lib.last_error())
+    for (M, N, n) in [(20000, 20000, 0), (2, 20000, 0), (2000, 2000, 3), (10, 10, 10)]:
+        rc, _ = ws_bytes(1000, M, N, n, 1)
+        assert rc == UNSUPPORTED, (M, N, n)
+        assert "B" in _lib.last_error()
+
+
+class _GramOnly:
+    """A static kernel with upstream's Gram_matrix and nothing else (an RBF in disguise)."""
+
+    def Gram_matrix(self, X, Y):
+        return torch.exp(-torch.cdist(X.flatten(0, 1), Y.flatten(0, 1)).pow(2).reshape(X.shape[0], X.shape[1], Y.shape[0],
+                                                                                       Y.shape[1]).permute(0, 2, 1, 3))
+
+
+def test_user_static_kernel_routing_on_cpu():
+    import sigsvgd_amd.sigkernel as sk
+
+    X = torch.randn(2, 4, 3, dtype=torch.float64)
+    with pytest.raises(NotImplementedError):
+        sk.SigKernel(object(), 1).compute_Gram(X, X)
+    assert sk._resolve_static(_GramOnly(), X, X) == (None, None)
+    assert sk._resolve_static(sk.RBFKernel(0.5), X, X) == (_lib.STATIC_RBF, 2.0)
+    assert sk._resolve_static(sk.LinearKernel(), X, X)[0] == _lib.STATIC_LINEAR
+    k = sk.SigKernel(_GramOnly(), 1)
+    for call in (lambda: k.compute_Gram(X, X), lambda: k.compute_kernel(X, X), lambda: k.gram_and_grad(X)):
+        with pytest.raises(RuntimeError, match="runs only on a HIP device"):
+            call()
