@@ -29,6 +29,8 @@
  *                          differentiates K THROUGH the signature (src/inference/score.py:50-55, svgd.py:41-43)
  *   sigsvgd_pde_fwd        the PDE of sigkernel.SigKernel on a static kernel the CALLER evaluated (any object with
  *   sigsvgd_pde_fwd_bwd    Gram_matrix / batch_kernel): K per grid, and the adjoint with respect to the grid
+ *   sigsvgd_gram_long_fwd  sigsvgd_gram_fwd / _fwd_bwd for the long paths those refuse (built-in static kernels,
+ *   sigsvgd_gram_long_fwd_bwd  static kernel evaluated inside the PDE sweep)
  *
  * Conventions
  *   - all pointers are DEVICE pointers (HIP), row-major contiguous; the caller owns every buffer
@@ -275,6 +277,30 @@ int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyad
                     void *workspace, size_t workspace_bytes, void *stream);
 int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags,
                         const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- long paths with the built-in static kernels (added in ABI 10) --------------------------------
+ * The same K[A,B] and gradX[A,TX,d] = d sum(grad_out*K)/dX (first argument only) as sigsvgd_gram_fwd / sigsvgd_gram_fwd_bwd,
+ * for the launches those refuse with SIGSVGD_E_UNSUPPORTED: paths whose per-pair tables outgrow the LDS (from about T = 250
+ * at dyadic order 0, and refined grids such as T = 200 at order 2).  X [A,TX,d] and Y [B,TY,d] keep their own lengths.
+ * The static kernel (SIGSVGD_STATIC_RBF or _LINEAR) is evaluated inside the kernel, in fp64, and its 4-corner increments are
+ * formed as the sweep needs them: nothing of size A*B*TX*TY exists.  Increments, sweeps and the gradient are fp64; the stored
+ * forward solution and the block sums S are fp32 (per-wave scratch).  Backward in the reference's GG convention, as
+ * sigsvgd_pde_fwd_bwd, chained through dk/dx.  Every ordered pair (i, j) is solved.
+ * Flags: SIGSVGD_FLAG_NAIVE_SOLVER; SIGSVGD_FLAG_SYM (weights grad_out + grad_out^T, needs A == B and TX == TY);
+ * SIGSVGD_FLAG_Y_IS_X is accepted and has no effect; any other bit is SIGSVGD_E_BADARG.  Limits: P = 2^n (TX-1) and
+ * Q = 2^n (TY-1) up to 8192, and the per-wave LDS (boundary row of Q + 2 doubles, 64 KB of increments, the band's points)
+ * within 160 KB; beyond them SIGSVGD_E_UNSUPPORTED.  Bit-reproducible: each work item (i, chunk of columns) adds its pairs
+ * into its own gradient slab in j order and the slabs are summed in a fixed order; no floating-point atomics.
+ * Workspace: per-wave scratch of 2 x P x (Q + 63) floats for the resident wavefronts (at most 1 GiB, fewer waves beyond)
+ * plus A x ceil(B / JC) x TX x d doubles of slabs; forward-only launches need none and report 0 bytes. */
+int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
+                                      unsigned flags, size_t *bytes);
+int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                          int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
+int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                              int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                              void *gradX_out, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
            "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
-           "sig_pde.hip"]
+           "sig_pde.hip", "gram_long.hip"]
 HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"),
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
@@ -26,6 +26,7 @@ STATIC_RBF, STATIC_LINEAR = 0, 1
 FLAG_NAIVE_SOLVER, FLAG_SYM, FLAG_Y_IS_X, FLAG_FORCE_GENERIC, FLAG_WS_CLEAN, FLAG_STORED_FORWARD = 1, 2, 4, 8, 16, 32
 FLAG_FOLD_TILES = 64
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
+E_BADARG, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 ABI_VERSION = 10
 
 EXPORTS = [
@@ -49,6 +50,9 @@ EXPORTS = [
     "sigsvgd_pde_workspace_bytes",
     "sigsvgd_pde_fwd",
     "sigsvgd_pde_fwd_bwd",
+    "sigsvgd_gram_long_workspace_bytes",
+    "sigsvgd_gram_long_fwd",
+    "sigsvgd_gram_long_fwd_bwd",
 ]
 
 _lib = None
@@ -188,6 +192,12 @@ def load():
     L.sigsvgd_pde_fwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
     L.sigsvgd_pde_fwd_bwd.restype = ci
     L.sigsvgd_pde_fwd_bwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_gram_long_workspace_bytes.restype = ci
+    L.sigsvgd_gram_long_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_gram_long_fwd.restype = ci
+    L.sigsvgd_gram_long_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_gram_long_fwd_bwd.restype = ci
+    L.sigsvgd_gram_long_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

@@ -48,6 +48,10 @@ int signature_bwd_launch(const void *X, const void *gsig, int N, int L, int C, i
 int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes);
 int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, const void *grad_out, void *K_out,
                void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream);
+int long_workspace(int A, int B, int M, int N, int d, int n, int want_grad, size_t *bytes);
+int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
+                bool naive, bool sym, const void *grad_out, void *K_out, void *gradX_out, void *ws, size_t ws_bytes,
+                hipStream_t stream);
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
@@ -101,6 +105,53 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
     }
     if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER) {
         set_error("pde: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
+        return SIGSVGD_E_BADARG;
+    }
+    return SIGSVGD_OK;
+}
+
+// the shape, order, kind and flag checks of the long-path Gram entry points (gram_long.hip): SIGSVGD_FLAG_NAIVE_SOLVER,
+// SIGSVGD_FLAG_SYM (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect) are taken, every other bit is refused
+static int check_long(int A, int B, int TX, int TY, int d, int n, int kind, unsigned flags)
+{
+    if (A < 1 || B < 1 || TX < 2 || TY < 2 || d < 1) {
+        set_error("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", A, B, TX, TY, d);
+        return SIGSVGD_E_BADARG;
+    }
+    if (kind != SIGSVGD_STATIC_RBF && kind != SIGSVGD_STATIC_LINEAR) {
+        set_error("gram_long: bad static kernel kind %d", kind);
+        return SIGSVGD_E_BADARG;
+    }
+    if (n < 0 || n > 10) {
+        set_error("gram_long: bad dyadic order %d", n);
+        return SIGSVGD_E_BADARG;
+    }
+    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X;
+    if (flags & ~known) {
+        set_error("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", flags & ~known);
+        return SIGSVGD_E_BADARG;
+    }
+    if ((flags & SIGSVGD_FLAG_SYM) && (A != B || TX != TY)) {
+        set_error("gram_long: sym backward needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
+        return SIGSVGD_E_BADARG;
+    }
+    return SIGSVGD_OK;
+}
+static int check_long_launch(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h, int n,
+                             int kind, unsigned flags, const void *K_out)
+{
+    if (!X || !Y || !K_out) {
+        set_error("gram_long: null pointer argument");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_long(A, B, TX, TY, d, n, kind, flags);
+    if (rc) return rc;
+    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) {
+        set_error("gram_long: bad dtype %d", dtype);
+        return SIGSVGD_E_BADARG;
+    }
+    if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) {
+        set_error("gram_long: RBF static kernel needs inv_h > 0 (got %g)", inv_h);
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
@@ -545,6 +596,45 @@ int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int 
     Range range("sigsvgd_pde_fwd_bwd");
     return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, grad_out, K_out, dG_out,
                       workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
+                                      unsigned flags, size_t *bytes)
+{
+    if (!bytes) {
+        set_error("bytes == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_long(A, B, TX, TY, d, dyadic_order, static_kind, flags);
+    if (rc) return rc;
+    return long_workspace(A, B, TX, TY, d, dyadic_order, want_grad ? 1 : 0, bytes);
+}
+
+int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                          int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
+                          size_t workspace_bytes, void *stream)
+{
+    const int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    if (rc) return rc;
+    Range range("sigsvgd_gram_long_fwd");
+    return long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                       false, nullptr, K_out, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                              int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                              void *gradX_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    if (rc) return rc;
+    if (!gradX_out) {
+        set_error("gradX_out == NULL (use sigsvgd_gram_long_fwd for forward only)");
+        return SIGSVGD_E_BADARG;
+    }
+    Range range("sigsvgd_gram_long_fwd_bwd");
+    return long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                       (flags & SIGSVGD_FLAG_SYM) != 0, grad_out, K_out, gradX_out, workspace, workspace_bytes,
+                       static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

@@ -177,6 +177,91 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     return K, fold_padded_grad(gX, X.shape[1])
 
 
+def gram_takes(A: int, B: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+               want_grad: bool = True, naive: bool = False, sym: bool = False, y_is_x: bool = False) -> bool:
+    """Whether `gram_fwd` (want_grad False) / `gram_fwd_bwd` take paths [A, T, d] x [B, T, d] with these settings: the
+    library's workspace query for the call's flags, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (the
+    per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those); any other error raises."""
+    L = _lib.load()
+    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False)
+    nbytes = ctypes.c_size_t(0)
+    rc = L.sigsvgd_gram_workspace_bytes(int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
+                                        1 if want_grad else 0, flags, ctypes.byref(nbytes))
+    if rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, "gram_workspace_bytes")
+    return True
+
+
+def _prep_long(X, Y):
+    """-> (X, Y) contiguous, detached, of X's dtype, each at its own length (the long route takes TX != TY)."""
+    if X.dim() != 3 or Y.dim() != 3:
+        raise ValueError(f"paths must be [batch, length, dim]; got {tuple(X.shape)} and {tuple(Y.shape)}")
+    if X.shape[2] != Y.shape[2]:
+        raise ValueError(f"X and Y must share the path dimension (got {tuple(X.shape)} vs {tuple(Y.shape)})")
+    if X.shape[0] == 0 or Y.shape[0] == 0:
+        raise ValueError("empty batch")
+    if X.shape[1] < 2 or Y.shape[1] < 2:
+        raise ValueError("paths need at least 2 points")
+    _io_dtype(X)
+    return X.detach().contiguous(), Y.detach().to(X.dtype).contiguous()
+
+
+def gram_long_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                  naive: bool = False) -> torch.Tensor:
+    """K[A,B] of the built-in static kernels on long paths (`sigsvgd_gram_long_fwd`, csrc/gram_long.hip): the launches
+    `gram_fwd` refuses for LDS.  X [A,TX,d] and Y [B,TY,d] at their own lengths; fp64 increments and sweeps, K in X's
+    dtype."""
+    L = _lib.load()
+    dev = _require_gpu(X, Y)
+    Xc, Yc = _prep_long(X, Y)
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    flags = _flags(naive, False, False, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_gram_long_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags,
+                                                   ctypes.byref(nbytes)), "gram_long_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_gram_long_fwd(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                     int(dyadic_order), int(static_kind), flags, K.data_ptr(),
+                                     ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "gram_long_fwd")
+    return K
+
+
+def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                      grad_out: Optional[torch.Tensor] = None, naive: bool = False,
+                      sym: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(K[A,B], gradX[A,TX,d]) with gradX = d sum(grad_out*K)/dX (first slot; grad_out None = ones; sym: grad_out +
+    grad_out^T) on the long route (`sigsvgd_gram_long_fwd_bwd`).  Bit-reproducible."""
+    L = _lib.load()
+    dev = _require_gpu(X, Y, grad_out)
+    Xc, Yc = _prep_long(X, Y)
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    go = None
+    if grad_out is not None:
+        if tuple(grad_out.shape) != (A, B):
+            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
+        go = grad_out.detach().to(Xc.dtype).contiguous()
+    if sym and (A != B or TX != TY):
+        raise ValueError("sym needs X and Y of one shape")
+    flags = _flags(naive, sym, False, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_gram_long_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags,
+                                                   ctypes.byref(nbytes)), "gram_long_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
+    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_gram_long_fwd_bwd(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                         int(dyadic_order), int(static_kind), flags,
+                                         go.data_ptr() if go is not None else None, K.data_ptr(), gX.data_ptr(),
+                                         ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "gram_long_fwd_bwd")
+    return K, gX
+
+
 def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, adagrad_state=None,
              inplace: bool = False):
     """v = -((K @ score - grad_k)/N) [* mask]; with X and lr also returns X - lr*v.

@@ -15,9 +15,10 @@ sigsvgd_amd.sigkernel` makes the reference's own code run o
 for X only (None for everything else), like upstream.
 
 Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
-`BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed).  Any other object
-with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally, `batch_kernel(X, Y) -> [A,M,N]`) is a USER static
-kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
+`BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
+the fused kernels' LDS take the long route (csrc/gram_long.hip), which evaluates the static kernel inside its PDE sweep
+(P, Q <= 8192 refined cells).  Any other object with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally,
+`batch_kernel(X, Y) -> [A,M,N]`) is a USER static kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
 the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
 `Gram_matrix` and to the static kernel's own parameters.  The grid costs A*B*M*N elements of memory: large batches
 belong on the built-in kernels.  Objects without `Gram_matrix` raise NotImplementedError.
@@ -147,6 +148,14 @@ def _resolve_static(static_kernel, X, Y):
     )
 
 
+def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x) -> bool:
+    """True where the fused Gram kernels refuse the launch (`ops.gram_takes`: their per-pair state outgrows the LDS); the
+    built-in static kernels then run on the long route (`ops.gram_long_fwd*`, csrc/gram_long.hip).  Every launch the
+    fused kernels take stays on them."""
+    T = max(X.shape[1], Y.shape[1])  # (the fused route pads the shorter batch to this length)
+    return not ops.gram_takes(X.shape[0], Y.shape[0], T, X.shape[2], dyadic_order, static_kind, want_grad, naive, sym, y_is_x)
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd node
 # ------------------------------------------------------------------------------------------------
@@ -165,8 +174,13 @@ class _SigKernelGram(torch.autograd.Function):
         Xd = X.detach()
         Yd = Y.detach()
         if ctx.needs_input_grad[0] and speculate:
-            K, g1 = ops.gram_fwd_bwd(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym, y_is_x)
+            if _long_route(Xd, Yd, static_kind, dyadic_order, True, naive, sym, y_is_x):
+                K, g1 = ops.gram_long_fwd_bwd(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym)
+            else:
+                K, g1 = ops.gram_fwd_bwd(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym, y_is_x)
             ctx.g_ones = g1
+        elif _long_route(Xd, Yd, static_kind, dyadic_order, False, naive, False, y_is_x):
+            K = ops.gram_long_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive)
         else:
             K = ops.gram_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x)
         ctx.save_for_backward(Xd, Yd)
@@ -187,7 +201,9 @@ class _SigKernelGram(torch.autograd.Function):
                     scalar = first
             if scalar is not None:
                 gX = ctx.g_ones * scalar.to(ctx.g_ones.dtype)
-        if gX is None:
+        if gX is None and _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, False):
+            _, gX = ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym)
+        elif gX is None:
             _, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym, False)
         return gX, None, None, None, None, None, None, None, None
 
@@ -253,6 +269,8 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
+        if _long_route(X, Yv, static_kind, self.dyadic_order, True, self._naive_solver, sym, Y is None):
+            return ops.gram_long_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym)
         return ops.gram_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
                                 y_is_x=Y is None)
 
