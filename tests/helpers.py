@@ -80,3 +80,76 @@ def patch_ops(monkeypatch):
     for name, fn in [("gram_fwd", gram_fwd), ("gram_fwd_bwd", gram_fwd_bwd), ("svgd_phi", svgd_phi),
                      ("gram_sym_partial", gram_sym_partial)]:
         monkeypatch.setattr(ops, name, fn)
+
+
+def long_plan(A, B, M, N, d, n, want_grad=True, cus=256):
+    """The launch plan of csrc/gram_long.hip (`long_make_plan`) for X [A, M, d] x Y [B, N, d] on `cus` compute units, as a
+    dict (nrow, W, JC, nchunks, items, grid, lds, bytes), or None where the library refuses the launch (E_UNSUPPORTED).
+    `bytes` is what sigsvgd_gram_long_workspace_bytes reports; tests/test_long_cabi.py pins the two together."""
+    r = 1 << n
+    P, Q = r * (M - 1), r * (N - 1)
+    nbands, nsteps = -(-P // 64), Q + 63
+    per_wave = (2 * nbands * nsteps * 64 + 64) * 4 if want_grad else 0
+    if P > 8192 or Q > 8192:
+        return None
+    nrow = 64 >> n if n <= 6 else 1
+    W = 1
+    while W < N - 1:
+        W <<= 1
+    Wcap = 1
+    while Wcap * 2 * nrow <= 8192:
+        Wcap <<= 1
+    W = min(W, Wcap)
+    lds = (nrow * W + Q + 2 + 64 + (nrow + 1) * d) * 8
+    if lds > 160 * 1024:
+        return None
+    resident = cus * min(160 * 1024 // lds, 8)
+    JC = 32
+    while JC > 1 and A * -(-B // JC) < resident:
+        JC >>= 1
+    nchunks = -(-B // JC)
+    items = A * nchunks
+    grid = min(resident, items)
+    if want_grad and per_wave * grid > (1 << 30):
+        grid = max(1, (1 << 30) // per_wave)
+    wsk_bytes = (per_wave * grid + 255) & ~255
+    partial_bytes = A * nchunks * M * d * 8 if want_grad else 0
+    total = wsk_bytes + partial_bytes + 256 if wsk_bytes + partial_bytes else 0
+    return dict(P=P, Q=Q, nrow=nrow, W=W, JC=JC, nchunks=nchunks, items=items, grid=grid, lds=lds, bytes=total)
+
+
+def pde_plan(npairs, M, N, n, want_grad=True, cus=256):
+    """The launch plan of csrc/sig_pde.hip (`pde_make_plan`) for npairs grids [M, N] on `cus` compute units, as a dict
+    (nrow, W, grid, lds, bytes), or None where the library refuses the launch.  `bytes` is what sigsvgd_pde_workspace_bytes
+    reports; tests/test_pde_cabi.py pins the two together."""
+    r = 1 << n
+    P, Q = r * (M - 1), r * (N - 1)
+    nbands, nsteps = -(-P // 64), Q + 63
+    per_wave = (2 * nbands * nsteps * 64 + 64) * 4 if want_grad else 0
+    if P > 8192 or Q > 8192:
+        return None
+    nrow = 64 >> n if n <= 6 else 1
+    W = 1
+    while W < N - 1:
+        W <<= 1
+    Wcap = 1
+    while Wcap * 2 * nrow <= 8192:
+        Wcap <<= 1
+    W = min(W, Wcap)
+    lds = (nrow * W + Q + 2 + 64) * 8
+    if lds > 160 * 1024:
+        return None
+    slots = min(cus * 8, npairs)
+    ws = per_wave * slots
+    if ws > (1 << 30):
+        slots = max(1, (1 << 30) // per_wave)
+        ws = max(per_wave, 1 << 30)
+    grid = min(cus * min(160 * 1024 // lds, 8), slots)
+    return dict(P=P, Q=Q, nrow=nrow, W=W, grid=grid, lds=lds, bytes=ws + 256 if ws else 0)
+
+
+def device_cus():
+    """The compute units the library plans for: the device's count, or its fallback of 256 without a device."""
+    import torch
+
+    return torch.cuda.get_device_properties(0).multi_processor_count if torch.cuda.is_available() else 256

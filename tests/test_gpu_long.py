@@ -81,19 +81,23 @@ def test_primitive_matches_oracle(gpu, A, B, T, d, n, kind, naive, io, weights):
 
 
 def test_refined_edge_8192(gpu):
-    """P = Q = 8192 (129 points at order 6): against the user route on the same inputs (the C oracle would hold two
-    8193^2 fp64 tables per thread)."""
+    """P = Q = 8192 (129 points at order 6): the long route and the user route (sig_pde, which shares its sweeps) against
+    each other and each against the C oracle (two 8193^2 fp64 tables per oracle thread: two threads)."""
     import sigsvgd_amd.sigkernel as sk
     from sigsvgd_amd import ops
 
     rng = np.random.default_rng(8192)
-    X = torch.as_tensor(paths(rng, 1, 129, 2), dtype=torch.float64, device=gpu)
-    Y = torch.as_tensor(paths(rng, 2, 129, 2), dtype=torch.float64, device=gpu)
+    Xn, Yn = paths(rng, 1, 129, 2), paths(rng, 2, 129, 2)
+    X = torch.as_tensor(Xn, dtype=torch.float64, device=gpu)
+    Y = torch.as_tensor(Yn, dtype=torch.float64, device=gpu)
     W = torch.tensor([[0.7, 1.3]], dtype=torch.float64, device=gpu)
     K, gX = ops.gram_long_fwd_bwd(X, Y, 1.0, 6, 0, W)
     Ku, gu = sk.SigKernel(DisguisedRBF(1.0), 6).gram_and_grad(X, Y, W)
     assert relK(np64(K), np64(Ku)) < 1e-9
     assert relmax(np64(gX), np64(gu)) < 1e-5
+    Kr, gr = c_oracle.gram_fwd_bwd(Xn, Yn, h=1.0, n=6, grad_out=np64(W), nthreads=2)
+    assert relK(np64(K), Kr) < 1e-9 and relK(np64(Ku), Kr) < 1e-9
+    assert relmax(np64(gX), gr) < 1e-5 and relmax(np64(gu), gr) < 1e-5
 
 
 def test_unequal_lengths(gpu):
@@ -216,3 +220,109 @@ def test_forward_memory_stays_small(gpu):
     assert K.shape == (16, 16) and bool(torch.isfinite(K).all())
     assert torch.cuda.max_memory_allocated(gpu) - base < (2 << 30)
     assert relK(np64(K), np64(K.T)) < 1e-9  # (each ordered pair is solved: K is symmetric to rounding)
+
+
+# ---- the plan's branches (tests/helpers.long_plan mirrors long_make_plan; test_long_cabi.py pins it to the library) ------
+def oracle_at_own_lengths(X, Y, h, n, naive, kind, go, nthreads=0):
+    """The C oracle for X [A, TX, d] x Y [B, TY, d]: the shorter batch padded with its last point (exact,
+    `ops.pad_to_length`), the gradient of a padded X folded back onto its points (`ops.fold_padded_grad`)."""
+    from sigsvgd_amd import ops
+
+    T = max(X.shape[1], Y.shape[1])
+    pad = lambda P: ops.pad_to_length(torch.as_tensor(P), T).numpy()
+    Kr, gr = c_oracle.gram_fwd_bwd(pad(X), pad(Y), h=h, n=n, naive=naive, kind=kind, grad_out=go, nthreads=nthreads)
+    return Kr, ops.fold_padded_grad(torch.as_tensor(gr), X.shape[1]).numpy()
+
+
+def _regime(tag, pl, M, N):
+    """the branch a case is there for, read off the launch plan"""
+    return {"full": N - 1 == pl["W"],                       # the ring holds every column exactly: no wrap
+            "wrap": N - 1 == pl["W"] + 1,                   # one column more than the ring: wraps once
+            "nrow1": pl["nrow"] == 1 and pl["P"] > 64,      # a band of 64 rows is part of one coarse row
+            "L1": pl["P"] % 64 == 1 and pl["P"] > 64,       # the last band has one row
+            "Q1": pl["Q"] == 1, "P1": pl["P"] == 1,         # a single coarse column / row
+            "short_x": M < N, "long_x": M > N,
+            "channels": True}[tag]                          # (d = 16 in registers, 17 and 33 from global memory)
+
+
+# (A, B, TX, TY, d, n, kind, naive, regime); nthreads of the oracle where its tables are large
+BRANCH_CASES = [
+    # ring: exactly full and wrapping once, at orders 0, 1, 2 (Wcap = 128, 256, 512 columns)
+    *[(2, 2, T, T, 2, n, kind, naive, reg) for (T, n, reg) in [(129, 0, "full"), (130, 0, "wrap"), (257, 1, "full"),
+                                                              (258, 1, "wrap"), (513, 2, "full"), (514, 2, "wrap")]
+      for kind in (0, 1) for naive in (False, True)],
+    # orders 7 to 10 (nrow = 1), square and not.  (The default stencil at P = Q = 8192 runs on the 8192 x 2048 grid: on
+    #  8192 x 8192 cells the oracle's own sweep, which forms 1 + g/2 + g^2/12 with g ~ D / 2^20, is 0.7 .. 1.5e-9 from a
+    #  long-double sweep of the same increments, the kernel's cancellation-free form within 5e-10 of it; on 8192 x 2048
+    #  the oracle is within 5e-10.)
+    *[(1, 2, 9, 9, 2, n, kind, naive, "nrow1") for n in (7, 8) for kind in (0, 1) for naive in (False, True)],
+    *[(1, 2, 9, 9, 2, 10, kind, True, "nrow1") for kind in (0, 1)],
+    (2, 2, 5, 9, 2, 8, 0, False, "nrow1"),
+    (1, 2, 9, 3, 3, 10, 0, False, "nrow1"),
+    (1, 2, 9, 3, 3, 10, 1, True, "nrow1"),
+    # a last band of one row; a single coarse column or row against a long path
+    (2, 2, 66, 66, 2, 0, 0, False, "L1"),
+    (2, 2, 258, 258, 3, 0, 0, True, "L1"),
+    (2, 3, 66, 66, 2, 0, 1, False, "L1"),
+    (2, 2, 300, 2, 2, 0, 0, False, "Q1"),
+    (2, 2, 2, 300, 2, 0, 0, False, "P1"),
+    (2, 2, 2, 300, 2, 0, 1, True, "P1"),
+    # X shorter than Y, and unequal lengths at refined orders
+    (3, 2, 150, 400, 2, 0, 0, False, "short_x"),
+    (2, 3, 60, 100, 3, 2, 0, False, "short_x"),
+    (2, 2, 40, 70, 2, 1, 1, True, "short_x"),
+    (2, 2, 200, 90, 2, 1, 1, False, "long_x"),
+    # channels past the 16 the fill keeps in registers (the gradient's 16-channel passes: 1, 2, 3) and at the LDS limit
+    *[(2, 2, 300, 300, d, 0, kind, False, "channels") for d in (16, 17, 33) for kind in (0, 1)],
+    (1, 2, 300, 300, 183, 0, 0, False, "channels"),
+]
+
+
+def _branch_id(c):
+    A, B, TX, TY, d, n, kind, naive, reg = c
+    return f"{reg}-{A}x{B}-T{TX}x{TY}-d{d}-n{n}-{'lin' if kind else 'rbf'}{'-naive' if naive else ''}"
+
+
+@pytest.mark.parametrize("A,B,TX,TY,d,n,kind,naive,regime", BRANCH_CASES, ids=[_branch_id(c) for c in BRANCH_CASES])
+def test_plan_branches_match_oracle(gpu, A, B, TX, TY, d, n, kind, naive, regime):
+    from helpers import device_cus, long_plan
+    from sigsvgd_amd import ops
+
+    pl = long_plan(A, B, TX, TY, d, n, True, device_cus())
+    assert pl is not None and _regime(regime, pl, TX, TY), pl
+    rng = np.random.default_rng(TX * 7 + TY + 100 * d + n + 13 * kind)
+    h = 0.5
+    X, Y = paths(rng, A, TX, d, d**-0.5), paths(rng, B, TY, d, d**-0.5)
+    go = rng.uniform(0.5, 1.5, (A, B))
+    Kr, gr = oracle_at_own_lengths(X, Y, h, n, naive, kind, go, nthreads=2 if max(pl["P"], pl["Q"]) > 4096 else 0)
+    Xt, Yt = torch.as_tensor(X, dtype=F64, device=gpu), torch.as_tensor(Y, dtype=F64, device=gpu)
+    K, gX = ops.gram_long_fwd_bwd(Xt, Yt, 1.0 / h, n, kind, torch.as_tensor(go, device=gpu), naive)
+    assert K.shape == (A, B) and gX.shape == Xt.shape
+    assert relK(np64(K), Kr) < 1e-9
+    assert relmax(np64(gX), gr) < 1e-5
+    assert torch.equal(ops.gram_long_fwd(Xt, Yt, 1.0 / h, n, kind, naive), K)
+
+
+@pytest.mark.parametrize("A,B,weights,io", [(64, 64, "rand", F64), (40, 60, "rand", F64), (64, 64, "sym", F64),
+                                            (64, 64, "sym", F32)])
+def test_work_items_with_several_pairs(gpu, A, B, weights, io):
+    """Work items of JC > 1 pairs (the in-slab accumulation of a row's gradient over j) and more items than resident waves
+    (the persistent item loop), with non-uniform weights, and sym=True (weights w_ij + w_ji) in fp64 and fp32 I/O."""
+    from helpers import device_cus, long_plan
+    from sigsvgd_amd import ops
+
+    T, d, n, h = 40, 2, 0, 0.5
+    pl = long_plan(A, B, T, T, d, n, True, device_cus())
+    assert pl["JC"] > 1, pl
+    if (A, B) == (40, 60):
+        assert pl["items"] > pl["grid"], pl
+    rng = np.random.default_rng(A + B + (weights == "sym") + (io == F32))
+    X = paths(rng, A, T, d)
+    Y = X.copy() if weights == "sym" else paths(rng, B, T, d)
+    go = rng.uniform(0.5, 1.5, (A, B))
+    Kr, gr = c_oracle.gram_fwd_bwd(X, Y, h=h, n=n, grad_out=go + go.T if weights == "sym" else go)
+    Xt, Yt = torch.as_tensor(X, dtype=io, device=gpu), torch.as_tensor(Y, dtype=io, device=gpu)
+    K, gX = ops.gram_long_fwd_bwd(Xt, Yt, 1.0 / h, n, 0, torch.as_tensor(go, device=gpu), sym=weights == "sym")
+    assert K.dtype == io and gX.dtype == io
+    assert relK(np64(K), Kr) < (1e-9 if io == F64 else 2.0**-23)
+    assert relmax(np64(gX), gr) < 1e-5

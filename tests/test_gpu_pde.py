@@ -265,3 +265,53 @@ def test_pde_determinism(gpu):
         K1, d1 = ops.pde_fwd_bwd(G, n, go)
         K2, d2 = ops.pde_fwd_bwd(G, n, go)
         assert torch.equal(K1, K2) and torch.equal(d1, d2)
+
+
+# ---- the plan's branches (tests/helpers.pde_plan mirrors pde_make_plan; test_pde_cabi.py pins it to the library) --------
+PDE_BRANCHES = [
+    # the increment ring exactly full, then wrapping once, at orders 0, 1, 2 (Wcap = 128, 256, 512 columns)
+    (70, 129, 0, "full"), (70, 130, 0, "wrap"), (40, 257, 1, "full"), (40, 258, 1, "wrap"), (20, 513, 2, "full"),
+    (20, 514, 2, "wrap"),
+    # orders 7 to 10 (nrow = 1: a band of 64 rows is part of one coarse row)
+    (9, 9, 7, "nrow1"), (9, 9, 8, "nrow1"), (3, 9, 10, "nrow1"), (9, 3, 10, "nrow1"),
+    # a last band of one row; a single coarse column or row against a long grid
+    (66, 40, 0, "L1"), (258, 20, 0, "L1"), (300, 2, 0, "Q1"), (2, 300, 0, "P1"),
+]
+
+
+@pytest.mark.parametrize("naive", [False, True])
+@pytest.mark.parametrize("M,N,n,regime", PDE_BRANCHES)
+def test_plan_branches_match_oracle(gpu, M, N, n, regime, naive):
+    from helpers import device_cus, pde_plan
+    from sigsvgd_amd import ops
+
+    pl = pde_plan(4, M, N, n, True, device_cus())
+    assert pl is not None and {"full": N - 1 == pl["W"], "wrap": N - 1 == pl["W"] + 1,
+                               "nrow1": pl["nrow"] == 1 and pl["P"] > 64, "L1": pl["P"] % 64 == 1 and pl["P"] > 64,
+                               "Q1": pl["Q"] == 1, "P1": pl["P"] == 1}[regime], pl
+    rng = np.random.default_rng(M * 1000 + N * 10 + n)
+    G = grids(rng, M, N, h=2.0)
+    go = rng.uniform(0.5, 1.5, G.shape[0])
+    Kr, dGr = ref_pde(G, n, naive, go)
+    Gt = torch.as_tensor(G, device=gpu)
+    K, dG = ops.pde_fwd_bwd(Gt, n, torch.as_tensor(go, device=gpu), naive)
+    assert relK(K.cpu().numpy(), Kr) < 1e-9
+    assert relmax(dG.cpu().numpy(), dGr) < 1e-5
+    assert torch.equal(ops.pde_fwd(Gt, n, naive), K)
+
+
+@pytest.mark.parametrize("naive", [False, True])
+def test_more_pairs_than_resident_waves(gpu, naive):
+    """2500 grids of 10 x 10: more pairs than the launch's waves, so each wave solves several pairs in turn."""
+    from helpers import device_cus, pde_plan
+    from sigsvgd_amd import ops
+
+    pl = pde_plan(2500, 10, 10, 0, True, device_cus())
+    assert pl["grid"] < 2500, pl
+    rng = np.random.default_rng(2500 + naive)
+    G = grids(rng, 10, 10, d=3, A=50, B=50)
+    go = rng.uniform(0.5, 1.5, G.shape[0])
+    Kr, dGr = ref_pde(G, 0, naive, go)
+    K, dG = ops.pde_fwd_bwd(torch.as_tensor(G, device=gpu), 0, torch.as_tensor(go, device=gpu), naive)
+    assert relK(K.cpu().numpy(), Kr) < 1e-9
+    assert relmax(dG.cpu().numpy(), dGr) < 1e-5

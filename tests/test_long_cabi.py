@@ -114,3 +114,59 @@ def test_routing_predicate():
     assert ops.gram_takes(2, 2, 20, 4, 2, want_grad=False, y_is_x=True) is True
     with pytest.raises(RuntimeError):  # a bad argument is an error, not a route
         ops.gram_takes(4, 4, 64, 7, 0, static_kind=9)
+
+
+def test_plan_helper_matches_workspace_query():
+    """tests/helpers.long_plan mirrors long_make_plan: its bytes are the library's over shapes that reach every branch of
+    the plan (ring wrap, nrow = 1, JC from 32 down to 1, the 1 GiB scratch cap, the LDS limit)."""
+    from helpers import device_cus, long_plan
+
+    cus = device_cus()
+    shapes = [(1, 1, 2, 2), (3, 4, 300, 300), (1, 2, 129, 129), (2, 3, 129, 130), (2, 2, 257, 258), (2, 2, 513, 514),
+              (2, 2, 9, 9), (2, 3, 5, 9), (1, 2, 9, 3), (3, 2, 150, 400), (2, 3, 66, 258), (1, 1, 300, 2), (1, 1, 2, 300),
+              (64, 64, 40, 40), (40, 60, 40, 40), (500, 700, 20, 20), (64, 64, 1025, 1025), (16, 16, 2048, 2048)]
+    seen = set()
+    for (A, B, M, N) in shapes:
+        for n in (0, 1, 2, 3, 6, 7, 8, 10):
+            for d in (1, 2, 17, 183, 184):
+                for want_grad in (0, 1):
+                    rc, b = long_ws(A, B, M, N, d, n, want_grad=want_grad)
+                    pl = long_plan(A, B, M, N, d, n, want_grad, cus)
+                    assert (rc == UNSUPPORTED) == (pl is None), (A, B, M, N, d, n, want_grad, rc)
+                    if pl is None:
+                        continue
+                    assert rc == 0 and b == pl["bytes"], (A, B, M, N, d, n, want_grad, b, pl)
+                    seen.add(pl["JC"])
+    assert {1, 2, 4, 32} <= seen
+
+
+def test_channel_limit():
+    """Up to 16 channels the ring fill keeps a point in registers, past 16 it reads global memory; the LDS holds the band's
+    points of X, so at T = 300 and order 0 the limit is 183 channels."""
+    from helpers import long_plan
+
+    assert long_ws(2, 2, 300, 300, 183, 0)[0] == 0
+    assert long_ws(2, 2, 300, 300, 183, 0, want_grad=0)[0] == 0
+    for want_grad in (0, 1):
+        rc, _ = long_ws(2, 2, 300, 300, 184, 0, want_grad=want_grad)
+        assert rc == UNSUPPORTED
+        assert "LDS" in _lib.last_error()
+    assert long_plan(2, 2, 300, 300, 183, 0) is not None and long_plan(2, 2, 300, 300, 184, 0) is None
+    for d in (16, 17, 33):  # (what SigKernel(RBFKernel) sends to the long route)
+        assert ops.gram_takes(4, 4, 300, d, 0) is False
+        assert long_ws(4, 4, 300, 300, d, 0)[0] == 0
+
+
+@pytest.mark.parametrize("n", [7, 8, 9, 10])
+def test_high_orders(n):
+    """Orders 7 to 10 (nrow = 1: a band of 64 rows is part of one coarse row): taken up to P = Q = 8192, refused past it."""
+    from helpers import long_plan
+
+    edge = 8192 // (1 << n) + 1  # points giving 8192 cells
+    for (TX, TY) in [(edge, edge), (edge, 3), (3, edge), (2, 2)]:
+        for want_grad in (0, 1):
+            assert long_ws(1, 2, TX, TY, 2, n, want_grad=want_grad)[0] == 0, _lib.last_error()
+        assert long_plan(1, 2, TX, TY, 2, n)["nrow"] == 1
+    for (TX, TY) in [(edge + 1, edge), (edge, edge + 1), (edge + 1, 2)]:
+        rc, _ = long_ws(1, 2, TX, TY, 2, n)
+        assert rc == UNSUPPORTED and "8192" in _lib.last_error()

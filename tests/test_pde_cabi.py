@@ -107,3 +107,33 @@ def test_user_static_kernel_routing_on_cpu():
     for call in (lambda: k.compute_Gram(X, X), lambda: k.compute_kernel(X, X), lambda: k.gram_and_grad(X)):
         with pytest.raises(RuntimeError, match="runs only on a HIP device"):
             call()
+
+
+def test_plan_helper_matches_workspace_query():
+    """tests/helpers.pde_plan mirrors pde_make_plan: its bytes are the library's (ring wrap, nrow = 1, more pairs than
+    resident waves, the 1 GiB scratch cap)."""
+    from helpers import device_cus, pde_plan
+
+    cus = device_cus()
+    for npairs in (1, 2, 100, 2500, 100_000):
+        for (M, N) in [(2, 2), (10, 10), (70, 129), (70, 130), (40, 257), (40, 258), (20, 513), (20, 514), (9, 9), (3, 9),
+                       (66, 40), (300, 2), (2, 300), (129, 129), (1023, 1023)]:
+            for n in (0, 1, 2, 6, 7, 8, 10):
+                for want_grad in (0, 1):
+                    rc, b = ws_bytes(npairs, M, N, n, want_grad)
+                    pl = pde_plan(npairs, M, N, n, want_grad, cus)
+                    assert (rc == UNSUPPORTED) == (pl is None), (npairs, M, N, n, want_grad, rc)
+                    if pl is not None:
+                        assert rc == 0 and b == pl["bytes"], (npairs, M, N, n, want_grad, b, pl)
+
+
+@pytest.mark.parametrize("n", [7, 8, 9, 10])
+def test_high_orders(n):
+    """Orders 7 to 10: taken up to P = Q = 8192 (nrow = 1), refused past it."""
+    edge = 8192 // (1 << n) + 1
+    for (M, N) in [(edge, edge), (edge, 3), (3, edge), (2, 2)]:
+        for want_grad in (0, 1):
+            assert ws_bytes(2, M, N, n, want_grad)[0] == 0, _lib.last_error()
+    for (M, N) in [(edge + 1, edge), (edge, edge + 1), (2, edge + 1)]:
+        rc, _ = ws_bytes(2, M, N, n, 1)
+        assert rc == UNSUPPORTED and "8192" in _lib.last_error()
