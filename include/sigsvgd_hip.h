@@ -31,6 +31,8 @@
  *   sigsvgd_pde_fwd_bwd    Gram_matrix / batch_kernel): K per grid, and the adjoint with respect to the grid
  *   sigsvgd_gram_long_fwd  sigsvgd_gram_fwd / _fwd_bwd for the long paths those refuse (built-in static kernels,
  *   sigsvgd_gram_long_fwd_bwd  static kernel evaluated inside the PDE sweep)
+ *   sigsvgd_pair_fwd       sigkernel.SigKernel.compute_kernel(X, Y) with a built-in static kernel: k_sig(X_i, Y_i) per
+ *   sigsvgd_pair_fwd_bwd   pair, and the gradients of both paths from one solve per pair
  *
  * Conventions
  *   - all pointers are DEVICE pointers (HIP), row-major contiguous; the caller owns every buffer
@@ -301,6 +303,29 @@ int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, in
 int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                               int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                               void *gradX_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- paired signature kernels with the built-in static kernels (ABI 10) -------------------------
+ * Replaces sigkernel.SigKernel.compute_kernel(X, Y) -> [A]: K_out[i] = k_sig(X_i, Y_i) for X [A,TX,d] and Y [A,TY,d]
+ * (TX != TY allowed; X and Y may be the same buffer), A solves instead of the A*A of a Gram launch.  It is the paired mode
+ * of the long-path kernel: the same fp64 static kernel, increments and sweeps, so K_out[i] is bit-identical to
+ * sigsvgd_gram_long_fwd(X_i, Y_i), and the same limits (P, Q up to 8192, per-wave LDS within 160 KB; beyond them
+ * SIGSVGD_E_UNSUPPORTED).  sigsvgd_pair_fwd_bwd: from the one reverse sweep of each pair (the reference's GG convention,
+ * as sigsvgd_gram_long_fwd_bwd), with w = grad_out (NULL = ones),
+ *   gradX_out[i][m] = w_i sum_n dG[m][n] dk(x_m, y_n)/dx_m     and     gradY_out[i][n] = w_i sum_m dG[m][n] dk(x_m, y_n)/dy_n,
+ * each in the I/O dtype; either may be NULL (not both).  Flags: SIGSVGD_FLAG_NAIVE_SOLVER only; any other bit, both
+ * gradient outputs NULL, bad shapes, kinds, orders, dtypes, inv_h <= 0 with RBF or null pointers are SIGSVGD_E_BADARG.
+ * One pair per wavefront, each gradient entry written by one lane in a fixed order: bit-reproducible, no floating-point
+ * atomics.  Workspace: per-wave scratch of 2 x P x (Q + 63) floats for min(resident wavefronts, A) waves (at most 1 GiB,
+ * fewer waves beyond); forward-only launches need none and report 0 bytes. */
+int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
+                                 unsigned flags, size_t *bytes);
+int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                     int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                         int dyadic_order, int static_kind, unsigned flags, const void *grad_out /* [A] or NULL = ones */,
+                         void *K_out, void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

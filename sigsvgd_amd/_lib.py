@@ -53,6 +53,9 @@ EXPORTS = [
     "sigsvgd_gram_long_workspace_bytes",
     "sigsvgd_gram_long_fwd",
     "sigsvgd_gram_long_fwd_bwd",
+    "sigsvgd_pair_workspace_bytes",
+    "sigsvgd_pair_fwd",
+    "sigsvgd_pair_fwd_bwd",
 ]
 
 _lib = None
@@ -198,6 +201,12 @@ def load():
     L.sigsvgd_gram_long_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
     L.sigsvgd_gram_long_fwd_bwd.restype = ci
     L.sigsvgd_gram_long_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_pair_workspace_bytes.restype = ci
+    L.sigsvgd_pair_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_pair_fwd.restype = ci
+    L.sigsvgd_pair_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_pair_fwd_bwd.restype = ci
+    L.sigsvgd_pair_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

@@ -52,6 +52,10 @@ int long_workspace(int A, int B, int M, int N, int d, int n, int want_grad, size
 int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
                 bool naive, bool sym, const void *grad_out, void *K_out, void *gradX_out, void *ws, size_t ws_bytes,
                 hipStream_t stream);
+int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes);
+int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
+                const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
+                hipStream_t stream);
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
@@ -155,6 +159,32 @@ static int check_long_launch(const void *X, const void *Y, int A, int B, int TX,
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
+}
+
+// the checks of the paired entry points (gram_long.hip's paired mode): check_long's for one column of pairs, with
+// SIGSVGD_FLAG_NAIVE_SOLVER the only flag taken
+static int check_pair(int A, int TX, int TY, int d, int n, int kind, unsigned flags)
+{
+    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER) {
+        set_error("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
+        return SIGSVGD_E_BADARG;
+    }
+    if (A < 1 || TX < 2 || TY < 2 || d < 1) {
+        set_error("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", A, TX, TY, d);
+        return SIGSVGD_E_BADARG;
+    }
+    return check_long(A, 1, TX, TY, d, n, kind, flags);
+}
+static int check_pair_launch(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h, int n,
+                             int kind, unsigned flags, const void *K_out)
+{
+    if (!X || !Y || !K_out) {
+        set_error("pair: null pointer argument");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_pair(A, TX, TY, d, n, kind, flags);
+    if (rc) return rc;
+    return check_long_launch(X, Y, A, 1, TX, TY, d, dtype, inv_h, n, kind, flags, K_out);
 }
 
 // ---- roctx ranges around the launches (the tracing hook of this path) ------------------------------
@@ -635,6 +665,44 @@ int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX
     return long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
                        (flags & SIGSVGD_FLAG_SYM) != 0, grad_out, K_out, gradX_out, workspace, workspace_bytes,
                        static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
+                                 unsigned flags, size_t *bytes)
+{
+    if (!bytes) {
+        set_error("bytes == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_pair(A, TX, TY, d, dyadic_order, static_kind, flags);
+    if (rc) return rc;
+    return pair_workspace(A, TX, TY, d, dyadic_order, want_grad ? 1 : 0, bytes);
+}
+
+int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                     int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    const int rc = check_pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    if (rc) return rc;
+    Range range("sigsvgd_pair_fwd");
+    return pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                       nullptr, K_out, nullptr, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                         int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                         void *gradX_out, void *gradY_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int rc = check_pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    if (rc) return rc;
+    if (!gradX_out && !gradY_out) {
+        set_error("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
+        return SIGSVGD_E_BADARG;
+    }
+    Range range("sigsvgd_pair_fwd_bwd");
+    return pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                       grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

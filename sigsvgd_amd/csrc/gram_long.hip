@@ -16,6 +16,13 @@
 // and dk/dx = -2 inv_h (x - y) k (RBF) or y (linear).  Lanes own points m; k is evaluated again there.  A work item is
 // (i, chunk of JC columns j): its pairs add into one [TX][d] fp64 slab in j order (the same lane always owns the same entry),
 // and long_reduce_kernel adds the slabs of a row i in chunk order.  No floating-point atomics: the bits depend on the inputs.
+//
+// Paired mode (PAIRED): work item i is the one pair (X_i, Y_i), K_out[i] = k_sig(X_i, Y_i) from the
+// same fill and sweeps.  From the pair's one S the gradient pass writes gX_i straight into the caller's buffer, and a second
+// pass, lanes owning points n of Y_i and walking m, chains S through dk/dy into gY_i[n] = w_i sum_m dG[m][n] dk(x_m, y_n)/dy_n
+// (dk/dy = 2 inv_h (x - y) k for RBF, x for linear).  Either output may be skipped; no slabs and no reduce kernel.
+#include <type_traits>
+
 #include "sig_common.h"
 
 namespace sigsvgd {
@@ -29,6 +36,11 @@ struct LongArgs {
     int A, B, M, N, d, n, r, P, Q, nbands, nsteps, nrow, W, JC, nchunks, sym;
     long long items;
     double inv_h, inv_r2;
+};
+// the paired mode's arguments: LongArgs (B = 1 chunk per row, partials unused) and the two gradient outputs (caller's dtype,
+// either may be NULL).  A type of its own, so the Gram kernels' argument layout stays as it is.
+struct PairArgs : LongArgs {
+    void *gradX, *gradY; // [A][TX][d], [A][TY][d]
 };
 
 namespace {
@@ -77,8 +89,8 @@ __device__ __forceinline__ double static_k16(const double *x, const double (&y)[
 }
 } // namespace
 
-template <typename IO, bool NAIVE, bool GRAD, int KIND>
-__global__ __launch_bounds__(64) void gram_long_kernel(LongArgs a)
+template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false>
+__global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED, PairArgs, LongArgs> a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
@@ -93,10 +105,10 @@ __global__ __launch_bounds__(64) void gram_long_kernel(LongArgs a)
     float *spare = GRAD ? wss + (size_t)a.nbands * nsteps * kWave + lane : nullptr;
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
-        const int i = (int)(item / a.nchunks);
-        const int j0 = (int)(item % a.nchunks) * a.JC, j1 = min(a.B, j0 + a.JC);
+        const int i = PAIRED ? (int)item : (int)(item / a.nchunks);
+        const int j0 = PAIRED ? i : (int)(item % a.nchunks) * a.JC, j1 = PAIRED ? i + 1 : min(a.B, j0 + a.JC);
         const IO *xi = static_cast<const IO *>(a.X) + (size_t)i * M * d;
-        double *slab = GRAD ? a.partials + (size_t)item * M * d : nullptr;
+        double *slab = GRAD && !PAIRED ? a.partials + (size_t)item * M * d : nullptr;
 
         for (int j = j0; j < j1; ++j) {
             const IO *yj = static_cast<const IO *>(a.Y) + (size_t)j * N * d;
@@ -176,7 +188,7 @@ __global__ __launch_bounds__(64) void gram_long_kernel(LongArgs a)
                 }
                 if (p == P - 1) Kval = cur;
             }
-            if (((P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)Kval;
+            if (((P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
                 continue;
@@ -262,11 +274,13 @@ __global__ __launch_bounds__(64) void gram_long_kernel(LongArgs a)
                 }
                 return in ? s : 0.0;
             };
-            double w = GO ? (double)GO[(size_t)i * a.B + j] : 1.0;
-            if (a.sym) w += GO ? (double)GO[(size_t)j * a.B + i] : 1.0;
+            double w = GO ? (double)GO[PAIRED ? (size_t)i : (size_t)i * a.B + j] : 1.0;
+            if (!PAIRED && a.sym) w += GO ? (double)GO[(size_t)j * a.B + i] : 1.0;
             // a pass of 63 points: lane l holds row m0 - 1 + l of S and, from lane 1 on, the gradient of point m = m0 - 1 + l
             // (S[m - 1][*] arrives from the lane below it)
-            for (int m0 = 0; m0 < M; m0 += kWave - 1) {
+            int mx_end = M;
+            if constexpr (PAIRED) mx_end = a.gradX ? M : 0; // (paired: gX skipped when its output is NULL)
+            for (int m0 = 0; m0 < mx_end; m0 += kWave - 1) {
                 const int m = m0 - 1 + lane;
                 const bool mvalid = lane >= 1 && m < M;
                 const IO *xm = xi + (size_t)min(max(m, 0), M - 1) * d;
@@ -303,8 +317,72 @@ __global__ __launch_bounds__(64) void gram_long_kernel(LongArgs a)
                         for (int c = 0; c < 16; ++c) {
                             if (c0 + c < d) {
                                 const double val = KIND == SIGSVGD_STATIC_RBF ? (-2.0 * a.inv_h) * accv[c] : accv[c];
-                                double *o = slab + (size_t)m * d + c0 + c;
-                                *o = j == j0 ? w * val : __builtin_fma(w, val, *o);
+                                if constexpr (PAIRED) {
+                                    static_cast<IO *>(a.gradX)[((size_t)i * M + m) * d + c0 + c] = (IO)(w * val);
+                                } else {
+                                    double *o = slab + (size_t)m * d + c0 + c;
+                                    *o = j == j0 ? w * val : __builtin_fma(w, val, *o);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+            if constexpr (PAIRED) {
+                // ---- paired: S -> dG -> dk/dy -> gY_i, the X pass with the roles of the two paths swapped -------------------
+                // lane l holds column n0 - 1 + l of S and, from lane 1 on, the gradient of point n = n0 - 1 + l of Y_i
+                // (S[*][n - 1] arrives from the lane below it); m walks the points of X_i in order (x_m is wave-uniform)
+                auto SatY = [&](int aa, int bb) -> double {
+                    const bool in = aa < Mm && bb >= 0 && bb < Nm;
+                    aa = min(aa, Mm - 1);
+                    bb = min(max(bb, 0), Nm - 1);
+                    double s = 0.0;
+                    for (int t = 0; t < r; ++t) {
+                        const int pp = aa * r + t, l = pp & (kWave - 1);
+                        s += (double)wss[((size_t)(pp >> 6) * nsteps + l + (size_t)bb * r) * kWave + l];
+                    }
+                    return in ? s : 0.0;
+                };
+                const int ny_end = a.gradY ? N : 0;
+                for (int n0 = 0; n0 < ny_end; n0 += kWave - 1) {
+                    const int nn = n0 - 1 + lane;
+                    const bool nvalid = lane >= 1 && nn < N;
+                    const IO *yn = yj + (size_t)min(max(nn, 0), N - 1) * d;
+                    for (int c0 = 0; c0 < d; c0 += 16) {
+                        double accv[16];
+#pragma unroll
+                        for (int c = 0; c < 16; ++c) accv[c] = 0.0;
+                        double s_prev = 0.0, sl_prev = 0.0; // S[m - 1][n], S[m - 1][n - 1]
+                        for (int mm = 0; mm < M; ++mm) {
+                            const double s_cur = SatY(mm, nn);
+                            const double sl = shfl_up_f64(s_cur); // S[m][n - 1]
+                            const double R = (sl_prev + s_cur) - (sl + s_prev); // dG[m][n] / w
+                            s_prev = s_cur;
+                            sl_prev = sl;
+                            const IO *xm = xi + (size_t)mm * d;
+                            if (KIND == SIGSVGD_STATIC_RBF) {
+                                double dist = 0.0;
+                                for (int c = 0; c < d; ++c) {
+                                    const double t = (double)xm[c] - (double)yn[c];
+                                    dist = __builtin_fma(t, t, dist);
+                                }
+                                const double rk = R * exp64(-dist * a.inv_h);
+#pragma unroll
+                                for (int c = 0; c < 16; ++c)
+                                    if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
+                            } else {
+#pragma unroll
+                                for (int c = 0; c < 16; ++c)
+                                    if (c0 + c < d) accv[c] = __builtin_fma(R, (double)xm[c0 + c], accv[c]);
+                            }
+                        }
+                        if (nvalid) {
+#pragma unroll
+                            for (int c = 0; c < 16; ++c) {
+                                if (c0 + c < d) {
+                                    const double val = KIND == SIGSVGD_STATIC_RBF ? (2.0 * a.inv_h) * accv[c] : accv[c];
+                                    static_cast<IO *>(a.gradY)[((size_t)i * N + nn) * d + c0 + c] = (IO)(w * val);
+                                }
                             }
                         }
                     }
@@ -335,7 +413,7 @@ struct LongPlan {
     size_t total() const { return wsk_bytes + partial_bytes ? wsk_bytes + partial_bytes + 256 : 0; }
 };
 
-int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, LongPlan &pl)
+int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, LongPlan &pl, const char *who = "gram_long")
 {
     pl.r = 1 << n;
     const long long P = (long long)pl.r * (M - 1), Q = (long long)pl.r * (N - 1);
@@ -343,7 +421,7 @@ int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, Long
     pl.nsteps = (int)(Q + kWave - 1);
     const size_t per_wave = want_grad ? ((size_t)2 * pl.nbands * pl.nsteps * kWave + kWave) * sizeof(float) : 0;
     if (P > kLongMaxCells || Q > kLongMaxCells) {
-        set_error("gram_long: refined grid %lld x %lld exceeds %d x %d (one wave's scratch would be %zu B)", P, Q,
+        set_error("%s: refined grid %lld x %lld exceeds %d x %d (one wave's scratch would be %zu B)", who, P, Q,
                   kLongMaxCells, kLongMaxCells, per_wave);
         return SIGSVGD_E_UNSUPPORTED;
     }
@@ -357,7 +435,7 @@ int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, Long
     pl.W = W < Wcap ? W : Wcap; // >= the (126 >> n) + 2 columns a block of 64 steps can touch
     pl.lds = long_lds_bytes(pl.nrow, pl.W, pl.Q, d);
     if (pl.lds > 160 * 1024) {
-        set_error("gram_long: per-wave state needs %zu B of LDS (> 160 KiB): d=%d", pl.lds, d);
+        set_error("%s: per-wave state needs %zu B of LDS (> 160 KiB): d=%d", who, pl.lds, d);
         return SIGSVGD_E_UNSUPPORTED;
     }
     const long long cus = device_cu_count();
@@ -381,25 +459,41 @@ int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, Long
     return SIGSVGD_OK;
 }
 
-template <typename IO, bool NAIVE, bool GRAD, int KIND>
-hipError_t long_launch_one(const LongPlan &pl, hipStream_t stream, const LongArgs &a)
+// the paired plan: the Gram plan of one column (items = A pairs, one per wavefront, grid = min(resident waves, A), the same
+// LDS, cell limits and 1 GiB scratch cap); the gradients are written straight to the outputs, so there are no slabs
+int pair_make_plan(int A, int M, int N, int d, int n, int want_grad, LongPlan &pl)
 {
-    const hipError_t e = raise_lds_limit<&gram_long_kernel<IO, NAIVE, GRAD, KIND>>();
+    const int rc = long_make_plan(A, 1, M, N, d, n, want_grad, pl, "pair");
+    if (rc) return rc;
+    pl.partial_bytes = 0;
+    return SIGSVGD_OK;
+}
+
+template <bool PAIRED>
+using LongArgsOf = std::conditional_t<PAIRED, PairArgs, LongArgs>;
+
+template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED>
+hipError_t long_launch_one(const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
+{
+    const hipError_t e = raise_lds_limit<&gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>>();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram_long_kernel<IO, NAIVE, GRAD, KIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
+    hipLaunchKernelGGL((gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
     return hipSuccess;
 }
-template <typename IO, int KIND>
-hipError_t long_dispatch2(bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgs &a)
+template <typename IO, int KIND, bool PAIRED>
+hipError_t long_dispatch2(bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
 {
-    if (naive) return grad ? long_launch_one<IO, true, true, KIND>(pl, stream, a) : long_launch_one<IO, true, false, KIND>(pl, stream, a);
-    return grad ? long_launch_one<IO, false, true, KIND>(pl, stream, a) : long_launch_one<IO, false, false, KIND>(pl, stream, a);
+    if (naive)
+        return grad ? long_launch_one<IO, true, true, KIND, PAIRED>(pl, stream, a)
+                    : long_launch_one<IO, true, false, KIND, PAIRED>(pl, stream, a);
+    return grad ? long_launch_one<IO, false, true, KIND, PAIRED>(pl, stream, a)
+                : long_launch_one<IO, false, false, KIND, PAIRED>(pl, stream, a);
 }
-template <typename IO>
-hipError_t long_dispatch(int kind, bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgs &a)
+template <typename IO, bool PAIRED = false>
+hipError_t long_dispatch(int kind, bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
 {
-    return kind == SIGSVGD_STATIC_RBF ? long_dispatch2<IO, SIGSVGD_STATIC_RBF>(naive, grad, pl, stream, a)
-                                      : long_dispatch2<IO, SIGSVGD_STATIC_LINEAR>(naive, grad, pl, stream, a);
+    return kind == SIGSVGD_STATIC_RBF ? long_dispatch2<IO, SIGSVGD_STATIC_RBF, PAIRED>(naive, grad, pl, stream, a)
+                                      : long_dispatch2<IO, SIGSVGD_STATIC_LINEAR, PAIRED>(naive, grad, pl, stream, a);
 }
 } // namespace
 
@@ -457,6 +551,50 @@ int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d,
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, "launch long_reduce_kernel");
     }
+    return SIGSVGD_OK;
+}
+
+// bytes of a paired launch's workspace (0 for forward-only launches)
+int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes)
+{
+    LongPlan pl;
+    const int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
+    if (rc) return rc;
+    *bytes = pl.total();
+    return SIGSVGD_OK;
+}
+
+// the argument checks are the entry points' (capi.hip); gradX_out and gradY_out both NULL: forward only
+int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
+                const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
+                hipStream_t stream)
+{
+    const int want_grad = gradX_out != nullptr || gradY_out != nullptr;
+    LongPlan pl;
+    const int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
+    if (rc) return rc;
+    const size_t need = pl.total();
+    if (ws_bytes < need || (need && !ws)) {
+        set_error("pair: workspace %zu B too small, required %zu B", ws_bytes, need);
+        return SIGSVGD_E_WORKSPACE;
+    }
+    unsigned char *base = need ? reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255)
+                               : nullptr;
+    PairArgs a;
+    a.X = X; a.Y = Y; a.grad_out = grad_out; a.K_out = K_out;
+    a.wsk = want_grad ? reinterpret_cast<float *>(base) : nullptr;
+    a.partials = nullptr;
+    a.wsk_per_block = pl.wsk_per_block;
+    a.A = A; a.B = 1; a.M = M; a.N = N; a.d = d; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
+    a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = 1; a.nchunks = 1;
+    a.sym = 0; a.items = pl.items; a.inv_h = inv_h;
+    a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
+    a.gradX = gradX_out; a.gradY = gradY_out;
+    const hipError_t e = dtype == SIGSVGD_F64 ? long_dispatch<double, true>(kind, naive, want_grad != 0, pl, stream, a)
+                                              : long_dispatch<float, true>(kind, naive, want_grad != 0, pl, stream, a);
+    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long paired)");
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) return hip_fail(le, "launch gram_long_kernel (paired)");
     return SIGSVGD_OK;
 }
 

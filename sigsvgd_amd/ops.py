@@ -262,6 +262,85 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
     return K, gX
 
 
+def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+               want_grad: bool = True) -> bool:
+    """Whether `pair_fwd` (want_grad False) / `pair_fwd_bwd` take pairs X [A, TX, d], Y [A, TY, d]: the library's workspace
+    query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
+    state beyond the LDS); any other error raises."""
+    L = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    rc = L.sigsvgd_pair_workspace_bytes(int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                        1 if want_grad else 0, 0, ctypes.byref(nbytes))
+    if rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, "pair_workspace_bytes")
+    return True
+
+
+def _prep_pair(X, Y):
+    if X.dim() != 3 or Y.dim() != 3 or X.shape[0] != Y.shape[0]:
+        raise ValueError(f"pairs need X [A, TX, d] and Y [A, TY, d]; got {tuple(X.shape)} and {tuple(Y.shape)}")
+    return _prep_long(X, Y)
+
+
+def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+             naive: bool = False) -> torch.Tensor:
+    """K[A] = k_sig(X_i, Y_i) of the built-in static kernels (`sigsvgd_pair_fwd`, the paired mode of csrc/gram_long.hip): one
+    solve per pair.  X [A,TX,d] and Y [A,TY,d] at their own lengths; fp64 increments and sweeps, K in X's dtype, bit-identical
+    to the diagonal of `gram_long_fwd(X, Y)`."""
+    L = _lib.load()
+    dev = _require_gpu(X, Y)
+    Xc, Yc = _prep_pair(X, Y)
+    (A, TX, d), TY = Xc.shape, Yc.shape[1]
+    flags = _flags(naive, False, False, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_pair_workspace_bytes(A, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags,
+                                              ctypes.byref(nbytes)), "pair_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_pair_fwd(Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                                int(static_kind), flags, K.data_ptr(), ws.data_ptr() if ws is not None else None, wsn,
+                                _stream_ptr(dev))
+    _lib.check(rc, "pair_fwd")
+    return K
+
+
+def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                 grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True,
+                 want_y: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(K[A], gX[A,TX,d] or None, gY[A,TY,d] or None): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each path's
+    own slot (grad_out None = ones), from one forward and one reverse sweep per pair (`sigsvgd_pair_fwd_bwd`).  Computed
+    and returned in X's dtype; bit-reproducible."""
+    if not (want_x or want_y):
+        raise ValueError("pair_fwd_bwd needs want_x or want_y (pair_fwd for the forward only)")
+    L = _lib.load()
+    dev = _require_gpu(X, Y, grad_out)
+    Xc, Yc = _prep_pair(X, Y)
+    (A, TX, d), TY = Xc.shape, Yc.shape[1]
+    go = None
+    if grad_out is not None:
+        if tuple(grad_out.shape) != (A,):
+            raise ValueError(f"grad_out must be [{A}], got {tuple(grad_out.shape)}")
+        go = grad_out.detach().to(Xc.dtype).contiguous()
+    flags = _flags(naive, False, False, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_pair_workspace_bytes(A, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags,
+                                              ctypes.byref(nbytes)), "pair_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
+    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
+    gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_pair_fwd_bwd(Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                    int(dyadic_order), int(static_kind), flags, go.data_ptr() if go is not None else None,
+                                    K.data_ptr(), gX.data_ptr() if gX is not None else None,
+                                    gY.data_ptr() if gY is not None else None,
+                                    ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "pair_fwd_bwd")
+    return K, gX, gY
+
+
 def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, adagrad_state=None,
              inplace: bool = False):
     """v = -((K @ score - grad_k)/N) [* mask]; with X and lr also returns X - lr*v.

@@ -12,7 +12,8 @@ The reference delegates the Goursat-PDE arithmetic to the third-party package `s
 This module provides those names on top of libsigsvgd_hip.so, so `sys.modules["sigkernel"] =
 sigsvgd_amd.sigkernel` makes the reference's own code run on the MI355X path.
 `compute_Gram` is an autograd node: backward receives grad_output [A,B] and returns the gradient
-for X only (None for everything else), like upstream.
+for X only (None for everything else), like upstream.  `compute_kernel` (and `compute_distance` on it) solves each pair
+(X_i, Y_i) once and differentiates both paths, each in its own slot.
 
 Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
 `BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
@@ -156,6 +157,22 @@ def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x) 
     return not ops.gram_takes(X.shape[0], Y.shape[0], T, X.shape[2], dyadic_order, static_kind, want_grad, naive, sym, y_is_x)
 
 
+def _device_cus(X) -> int:
+    return torch.cuda.get_device_properties(X.device).multi_processor_count if X.is_cuda else 256
+
+
+def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus) -> bool:
+    """True where `compute_kernel` with a built-in static kernel solves its pairs on the paired route (`ops.pair_fwd*`): every
+    shape `ops.pair_takes` takes, except forward-only calls of A^2 <= cus pairs that the fused Gram kernels take.  Such a Gram
+    launch is one round of the device, latency-bound like the paired launch but on the fused kernels' fp32 sweeps, so its
+    diagonal is the faster forward there (A = 6, T = 100, order 3: 1.23 ms against 1.31 ms)."""
+    if not ops.pair_takes(A, TX, TY, d, dyadic_order, static_kind, want_grad):
+        return False
+    if want_grad or A * A > cus:
+        return True
+    return not ops.gram_takes(A, A, max(TX, TY), d, dyadic_order, static_kind, False, naive)
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd node
 # ------------------------------------------------------------------------------------------------
@@ -208,6 +225,37 @@ class _SigKernelGram(torch.autograd.Function):
         return gX, None, None, None, None, None, None, None, None
 
 
+class _SigKernelPair(torch.autograd.Function):
+    """forward: K[i] = k_sig(X_i, Y_i) (`ops.pair_fwd*`, one solve per pair).  backward: X and Y each get the derivative of
+    their own slot (a tensor passed in both slots gets the sum from autograd).
+
+    When X or Y needs a gradient the forward runs `ops.pair_fwd_bwd` with unit weights for the outputs needed: pair i's
+    gradient is linear in its own weight alone, so backward scales row i by grad_output[i] (exact up to one rounding) and
+    there is one launch per call.  The launch computes in X's dtype; each gradient returns in its own input's dtype."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive):
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.dtypes = (X.dtype, Y.dtype)
+        if want_x or want_y:
+            K, gX, gY = ops.pair_fwd_bwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
+                                         want_y)
+            ctx.save_for_backward(gX, gY)
+        else:
+            K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive)
+        return K
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gX1, gY1 = ctx.saved_tensors
+        gX = gY = None
+        if gX1 is not None:
+            gX = (gX1 * grad_output.to(gX1.dtype)[:, None, None]).to(ctx.dtypes[0])
+        if gY1 is not None:
+            gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
+        return gX, gY, None, None, None, None
+
+
 class SigKernel:
     """Signature kernel with a static kernel and a dyadic refinement order (PDE solver)."""
 
@@ -239,15 +287,25 @@ class SigKernel:
                                     y_is_x, self.speculate_ones)
 
     # -- the rest of the upstream `sigkernel.SigKernel` surface [RECALLED from the public package; the
-    #    reference tree never calls these].  All go through compute_Gram, so gradients flow to the FIRST
-    #    argument only, with `sym=True` giving the symmetrised weighting for Gram(X, X).
+    #    reference tree never calls these].  compute_kernel / compute_distance differentiate both arguments (each its
+    #    own slot); compute_mmd goes through compute_Gram, so its gradients flow to the FIRST argument only, with
+    #    `sym=True` giving the symmetrised weighting for Gram(X, X).
     def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
-        """Paired kernel k_sig(X_i, Y_i) -> [batch] (taken from the Gram launch: batch^2 solves; a user static kernel with
-        `batch_kernel` solves the batch pairs only)."""
+        """Paired kernel k_sig(X_i, Y_i) -> [batch], one solve per pair, differentiable in X and in Y (each its own slot:
+        compute_kernel(X, X) differentiates to the sum of both).  Built-in static kernels run on the paired route
+        (`ops.pair_fwd*`, csrc/gram_long.hip) wherever `_pair_route` says so, else on the diagonal of compute_Gram (first
+        slot only) as before: where `ops.pair_takes` refuses the shape, and for forward-only calls of few pairs; a user static kernel with `batch_kernel` solves the batch pairs through
+        torch autograd; one without it takes the diagonal of its Gram launch."""
         assert X.shape[0] == Y.shape[0], "compute_kernel pairs X_i with Y_i"
-        if _resolve_static(self.static_kernel, X, Y)[0] is None and hasattr(self.static_kernel, "batch_kernel"):
-            G = self.static_kernel.batch_kernel(X, Y.detach())
+        static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
+        if static_kind is None and hasattr(self.static_kernel, "batch_kernel"):
+            G = self.static_kernel.batch_kernel(X, Y)
             return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
+        if static_kind is not None:
+            want_grad = torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)
+            if _pair_route(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], static_kind, self.dyadic_order, want_grad,
+                           self._naive_solver, _device_cus(X)):
+                return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver)
         return self.compute_Gram(X, Y).diagonal()
 
     def compute_distance(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
