@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
            "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
            "sig_pde.hip", "gram_long.hip"]
-HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"),
+HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"), os.path.join(_CSRC, "ring_sweep.h"),
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
 # mirror of include/sigsvgd_hip.h

@@ -1,29 +1,29 @@
 // Signature-kernel Gram matrix and gradient for the built-in static kernels on long paths.
 //
 // The fused Gram kernels keep a pair's whole-grid state in LDS and refuse paths past it (the coverage kernel from about
-// T = 250 at order 0, and refined grids whose tables outgrow 160 KB).  This kernel takes those launches with the layout of
-// sig_pde_kernel (sig_pde.hip): one wavefront per pair in a persistent grid, bands of 64 rows of the refined P x Q grid, one
-// row per lane, swept anti-diagonal by anti-diagonal, the band's boundary row in LDS, and an LDS ring of the band's fp64
-// increments refilled between blocks of 64 sweep steps.  What differs is where the ring's values come from: the fill
-// evaluates the static kernel itself,
+// T = 250 at order 0, and refined grids whose tables outgrow 160 KB).  This kernel takes those launches with the ring sweep of
+// ring_sweep.h, which sig_pde_kernel (sig_pde.hip) runs too: one wavefront per pair in a persistent grid, bands of 64 rows of
+// the refined P x Q grid, one row per lane, swept anti-diagonal by anti-diagonal, the band's boundary row in LDS, and an LDS
+// ring of the band's fp64 increments refilled between blocks of 64 sweep steps.  What differs is where the ring's values come
+// from: the fill evaluates the static kernel itself,
 //   D[a][b] = k(x_{a+1}, y_{b+1}) - k(x_{a+1}, y_b) - k(x_a, y_{b+1}) + k(x_a, y_b)      (fp64)
 // from the band's nrow + 1 points of X_i (staged in LDS) and the columns of Y_j (one static-kernel column per lane, read from
 // global memory), so the [A, B, M, N] grid never exists.  Increments, sweeps and the gradient are fp64; the stored forward
 // solution and the S partials are fp32, as in sig_pde.
 //
-// Backward: the reverse sweep is sig_pde's (the reference's GG convention), then the pair's coarse S is chained through the
+// Backward: the shared reverse sweep (the reference's GG convention), then the pair's coarse S is chained through the
 // static kernel into the gradient of x_i:  gX_i[m] += w_ij sum_n dG[m][n] dk(x_m, y_n)/dx_m, with dG the 4-corner scatter of S
 // and dk/dx = -2 inv_h (x - y) k (RBF) or y (linear).  Lanes own points m; k is evaluated again there.  A work item is
 // (i, chunk of JC columns j): its pairs add into one [TX][d] fp64 slab in j order (the same lane always owns the same entry),
 // and long_reduce_kernel adds the slabs of a row i in chunk order.  No floating-point atomics: the bits depend on the inputs.
 //
 // Paired mode (PAIRED): work item i is the one pair (X_i, Y_i), K_out[i] = k_sig(X_i, Y_i) from the
-// same fill and sweeps.  From the pair's one S the gradient pass writes gX_i straight into the caller's buffer, and a second
-// pass, lanes owning points n of Y_i and walking m, chains S through dk/dy into gY_i[n] = w_i sum_m dG[m][n] dk(x_m, y_n)/dy_n
+// same fill and sweeps.  From the pair's one S the gradient pass writes gX_i straight into the caller's buffer, and the same
+// pass with lanes owning points n of Y_i and walking m chains S through dk/dy into gY_i[n] = w_i sum_m dG[m][n] dk(x_m, y_n)/dy_n
 // (dk/dy = 2 inv_h (x - y) k for RBF, x for linear).  Either output may be skipped; no slabs and no reduce kernel.
 #include <type_traits>
 
-#include "sig_common.h"
+#include "ring_sweep.h"
 
 namespace sigsvgd {
 
@@ -44,16 +44,6 @@ struct PairArgs : LongArgs {
 };
 
 namespace {
-constexpr int kLongMaxCells = 8192;                 // P and Q
-constexpr size_t kLongRingDoubles = 8192;           // 64 KB of increments per wave
-constexpr size_t kLongMaxScratch = (size_t)1 << 30; // the per-wave scratch of a launch: the grid is lowered to stay below it
-
-// ring of nrow x W fp64 increments + boundary row [Q + 2] + per-lane dump cells [64] + the band's points of X_i [nrow + 1][d]
-size_t long_lds_bytes(int nrow, int W, int Q, int d)
-{
-    return ((size_t)nrow * W + Q + 2 + kWave + (size_t)(nrow + 1) * d) * sizeof(double);
-}
-
 // the static kernel of x (LDS, fp64) and y (global, the caller's dtype)
 template <int KIND, typename IO>
 __device__ __forceinline__ double static_k(const double *x, const IO *y, int d, double inv_h)
@@ -87,6 +77,61 @@ __device__ __forceinline__ double static_k16(const double *x, const double (&y)[
     }
     return KIND == SIGSVGD_STATIC_RBF ? exp64(-s * inv_h) : s;
 }
+
+// The pair's coarse S chained through the static kernel's derivative into the gradient of the points of one of its paths.
+// Lanes own points o of that path, 63 per pass (lane l holds o = o0 - 1 + l and, from lane 1 on, its gradient; S at o - 1
+// arrives from the lane below), and walk the points t of the other path in order.  dG[m][n] / w = (S[m-1][n-1] + S[m][n]) -
+// (S[m-1][n] + S[m][n-1]), S = 0 outside the coarse grid; store(o, c, g) takes coordinate c of own point o's gradient.
+// OWN_X: the points are X's, dk/dx = -2 inv_h (x - y) k (RBF) or y (linear); else Y's, dk/dy = 2 inv_h (x - y) k or x.
+template <int KIND, bool OWN_X, typename IO, typename Store>
+__device__ __forceinline__ void static_grad_pass(const RingWave &rw, const IO *own, int To, const IO *oth, int Tt, int d,
+                                                 double inv_h, Store &&store)
+{
+    const int lane = threadIdx.x;
+    for (int o0 = 0; o0 < To; o0 += kWave - 1) {
+        const int o = o0 - 1 + lane;
+        const bool valid = lane >= 1 && o < To;
+        const IO *po = own + (size_t)min(max(o, 0), To - 1) * d;
+        for (int c0 = 0; c0 < d; c0 += 16) {
+            double accv[16];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) accv[c] = 0.0;
+            double s_prev = 0.0, nb_prev = 0.0; // S at (o, t - 1), (o - 1, t - 1)
+            for (int t = 0; t < Tt; ++t) {
+                const int oc = min(max(o, 0), To - 2), tc = min(t, Tt - 2); // (read at a clamped block, then dropped)
+                const double s = OWN_X ? ring_S(rw, oc, tc) : ring_S(rw, tc, oc);
+                const double s_cur = o >= 0 && o < To - 1 && t < Tt - 1 ? s : 0.0;
+                const double nb = shfl_up_f64(s_cur); // S at (o - 1, t)
+                const double R = (nb_prev + s_cur) - (nb + s_prev); // dG / w
+                s_prev = s_cur;
+                nb_prev = nb;
+                const IO *pt = oth + (size_t)t * d;
+                const IO *xm = OWN_X ? po : pt, *yn = OWN_X ? pt : po;
+                if (KIND == SIGSVGD_STATIC_RBF) {
+                    double dist = 0.0;
+                    for (int c = 0; c < d; ++c) {
+                        const double u = (double)xm[c] - (double)yn[c];
+                        dist = __builtin_fma(u, u, dist);
+                    }
+                    const double rk = R * exp64(-dist * inv_h);
+#pragma unroll
+                    for (int c = 0; c < 16; ++c)
+                        if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 16; ++c)
+                        if (c0 + c < d) accv[c] = __builtin_fma(R, (double)pt[c0 + c], accv[c]);
+                }
+            }
+            if (valid) {
+#pragma unroll
+                for (int c = 0; c < 16; ++c)
+                    if (c0 + c < d)
+                        store(o, c0 + c, KIND == SIGSVGD_STATIC_RBF ? ((OWN_X ? -2.0 : 2.0) * inv_h) * accv[c] : accv[c]);
+            }
+        }
+    }
+}
 } // namespace
 
 template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false>
@@ -94,15 +139,11 @@ __global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
-    const int M = a.M, N = a.N, n = a.n, P = a.P, Q = a.Q, W = a.W, nrow = a.nrow, nsteps = a.nsteps, d = a.d;
-    double *ring = reinterpret_cast<double *>(smem_raw); // [nrow][W]: D[a0 + row][b] at column slot b & (W - 1)
-    double *rowbuf = ring + (size_t)nrow * W;            // [Q + 2]
-    double *dump = rowbuf + (Q + 2);                     // [64]: where the lanes that have nothing to hand over store
-    double *xs = dump + kWave;                           // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
+    const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
+    const RingWave rw = ring_wave<GRAD>(a, smem_raw);
+    double *ring = rw.ring;
+    double *xs = rw.dump + kWave; // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
     const IO *GO = static_cast<const IO *>(a.grad_out);
-    float *wsk = GRAD ? a.wsk + (size_t)blockIdx.x * a.wsk_per_block : nullptr;
-    float *wss = GRAD ? wsk + (size_t)a.nbands * nsteps * kWave : nullptr; // S partials, same order as the forward solution
-    float *spare = GRAD ? wss + (size_t)a.nbands * nsteps * kWave + lane : nullptr;
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
         const int i = PAIRED ? (int)item : (int)(item / a.nchunks);
@@ -144,249 +185,36 @@ __global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED
                 __syncthreads();
             };
 
-            // ---- forward sweep (sig_pde_kernel's) ---------------------------------------------------------------------
-            double Kval = 1.0;
-            for (int kb = 0; kb < a.nbands; ++kb) {
-                const int p = kb * kWave + lane;
-                const bool rowvalid = p < P;
-                const bool first = kb == 0;
-                const int a0 = (kb * kWave) >> n;
-                stage_x(a0);
-                const double *Drow = ring + (size_t)((min(p, P - 1) >> n) - a0) * W;
-                float *wp = GRAD ? wsk + (size_t)kb * nsteps * kWave + lane : nullptr;
-                double cur = 1.0, upprev = 1.0;
-                double rb = first ? 1.0 : rowbuf[1]; // lane 0's upper neighbour on step s: rowbuf[s + 1]
-                int have = -1;                       // coarse columns 0 .. have are in the ring (the last ones filled)
-                for (int s0 = 0; s0 < nsteps; s0 += kWave) {
-                    const int lo = max(s0 - (kWave - 1), 0) >> n, hi = min((s0 + kWave - 1) >> n, N - 2);
-                    if (hi > have) { // every column this block and as many later ones as the ring holds
-                        const int to = min(N - 2, lo + W - 1);
-                        fill(a0, have + 1, to);
-                        have = to;
-                    }
-                    double gf = Drow[(min(max(s0 - lane, 0), Q - 1) >> n) & (W - 1)];
-                    const int s1 = min(s0 + kWave, nsteps);
-                    for (int s = s0; s < s1; ++s) {
-                        const int q = s - lane;
-                        const bool active = rowvalid && q >= 0 && q < Q;
-                        const double gfn = Drow[(min(max(q + 1, 0), Q - 1) >> n) & (W - 1)];
-                        const double rbr = rowbuf[min(s + 2, Q)];
-                        const double rbn = first ? 1.0 : rbr;
-                        double up_in = shfl_up_f64(cur);
-                        up_in = (lane == 0) ? rb : up_in;
-                        const double nw = stencil(cur, up_in, upprev, gf * a.inv_r2, NAIVE);
-                        if (GRAD) { // K_fwd[p][q] at [step][lane] (issued from inline asm: no wait for the previous step's store)
-                            const float kst = (float)upprev;
-                            asm volatile("global_store_dword %0, %1, off" ::"v"(wp + (size_t)s * kWave), "v"(kst));
-                        }
-                        *((lane == kWave - 1 && active) ? rowbuf + (q + 1) : dump + lane) = nw;
-                        cur = active ? nw : cur;
-                        upprev = active ? up_in : upprev;
-                        gf = gfn;
-                        rb = rbn;
-                    }
-                }
-                if (p == P - 1) Kval = cur;
-            }
-            if (((P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
+            const double Kval = ring_forward<NAIVE, GRAD>(rw, fill, stage_x);
+            if (((rw.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
                 continue;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
             __syncthreads();
-
-            // ---- reverse sweep (sig_pde_kernel's): GG = K_fwd[p][q] K_rev[p+1][q+1], summed over the r columns of a block --
-            for (int kb = a.nbands - 1; kb >= 0; --kb) {
-                const int p = kb * kWave + lane;
-                const bool rowvalid = p < P;
-                const int L = min(kWave, P - kb * kWave);
-                const int a0 = (kb * kWave) >> n;
-                stage_x(a0);
-                const double *Drow = ring + (size_t)((min(p, P - 1) >> n) - a0) * W;
-                float *wsrow = wss + (size_t)kb * nsteps * kWave + lane;
-                const float *wrow = wsk + (size_t)kb * nsteps * kWave + lane; // K_fwd[p][q] at step lane + q
-                const bool lastband = kb == a.nbands - 1;
-                const bool hands_over = lane == 0 && kb > 0;
-                double cur = 1.0, dprev = 1.0, sb = 0.0;
-                const int nsp = Q + L - 1;
-                int q = Q - 1 + (L - 1 - lane);
-                int R = Q - 1 + L - 1; // row of the stored forward solution on reverse step 0
-                double rb = lastband ? 1.0 : rowbuf[Q - 1]; // lane L-1's lower neighbour on step sp: rowbuf[Q - 1 - sp]
-                constexpr int KPF = 8; // ring of the next KPF rows of the forward solution (an L2 round trip is ~8 steps long)
-                float kfr[KPF];
-#pragma unroll
-                for (int u = 0; u < KPF; ++u) kfr[u] = wrow[(size_t)max(R - u, 0) * kWave];
-                int low = N - 1; // coarse columns low .. N - 2 are in the ring
-                for (int sp0 = 0; sp0 < nsp; sp0 += kWave) {
-                    const int qhi = Q + L - 2 - sp0; // the columns of this block: qhi - 126 .. qhi
-                    const int need_hi = min(qhi, Q - 1) >> n, need_lo = max(qhi - 2 * (kWave - 1), 0) >> n;
-                    if (need_lo < low) {
-                        const int from = max(0, need_hi - W + 1);
-                        fill(a0, from, low - 1);
-                        low = from;
-                    }
-                    double gf = Drow[(min(max(q, 0), Q - 1) >> n) & (W - 1)];
-                    double rbk = rowbuf[max(Q - 1 - sp0, 0)];
-                    rb = lastband ? 1.0 : rbk;
-                    for (int sp1 = sp0; sp1 < sp0 + kWave; sp1 += KPF) {
-#pragma unroll
-                        for (int u = 0; u < KPF; ++u, --q, --R) {
-                            const int sp = sp1 + u;
-                            const bool active = rowvalid && q >= 0 && q < Q;
-                            const double gfn = Drow[(min(max(q - 1, 0), Q - 1) >> n) & (W - 1)];
-                            const double rbr = rowbuf[max(Q - 2 - sp, 0)];
-                            const double rbn = lastband ? 1.0 : rbr;
-                            const double kf = (double)kfr[u];
-                            kfr[u] = wrow[(size_t)max(R - KPF, 0) * kWave];
-                            double down_in = shfl_down_f64(cur);
-                            down_in = (lane == L - 1) ? rb : down_in;
-                            sb = active ? __builtin_fma(kf, dprev, sb) : sb;
-                            const bool done = active && (q & (a.r - 1)) == 0; // the block's last (lowest) column
-                            const float sst = done ? (float)(sb * a.inv_r2) : 0.f;
-                            asm volatile("global_store_dword %0, %1, off" ::"v"(R >= 0 ? wsrow + (size_t)R * kWave : spare), "v"(sst));
-                            sb = done ? 0.0 : sb;
-                            const double nw = stencil(cur, down_in, dprev, gf * a.inv_r2, NAIVE);
-                            *((hands_over && active) ? rowbuf + q : dump + lane) = nw;
-                            cur = active ? nw : cur;
-                            dprev = active ? down_in : dprev;
-                            gf = gfn;
-                            rb = rbn;
-                        }
-                    }
-                }
-            }
+            ring_reverse<NAIVE>(rw, fill, stage_x);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
             __syncthreads();
 
-            // ---- gradient: S -> dG (4-corner scatter) -> static-kernel derivative -> gX_i -------------------------------
-            // S[aa][bb] = the r lane partials of block (aa, bb) in row order (lane pp & 63 of band pp >> 6 filed the partial
-            // of row pp, block column bb, on reverse step (pp & 63) + bb r); S = 0 outside the coarse grid.
-            const int r = a.r, Mm = M - 1, Nm = N - 1;
-            auto Sat = [&](int aa, int bb) -> double {
-                const bool in = aa >= 0 && aa < Mm && bb < Nm;
-                aa = min(max(aa, 0), Mm - 1);
-                bb = min(bb, Nm - 1);
-                double s = 0.0;
-                for (int t = 0; t < r; ++t) {
-                    const int pp = aa * r + t, l = pp & (kWave - 1);
-                    s += (double)wss[((size_t)(pp >> 6) * nsteps + l + (size_t)bb * r) * kWave + l];
-                }
-                return in ? s : 0.0;
-            };
+            // ---- gradient: S -> dG (4-corner scatter) -> static-kernel derivative -> gX_i (and gY_i, paired) ---------------
             double w = GO ? (double)GO[PAIRED ? (size_t)i : (size_t)i * a.B + j] : 1.0;
             if (!PAIRED && a.sym) w += GO ? (double)GO[(size_t)j * a.B + i] : 1.0;
-            // a pass of 63 points: lane l holds row m0 - 1 + l of S and, from lane 1 on, the gradient of point m = m0 - 1 + l
-            // (S[m - 1][*] arrives from the lane below it)
-            int mx_end = M;
-            if constexpr (PAIRED) mx_end = a.gradX ? M : 0; // (paired: gX skipped when its output is NULL)
-            for (int m0 = 0; m0 < mx_end; m0 += kWave - 1) {
-                const int m = m0 - 1 + lane;
-                const bool mvalid = lane >= 1 && m < M;
-                const IO *xm = xi + (size_t)min(max(m, 0), M - 1) * d;
-                for (int c0 = 0; c0 < d; c0 += 16) {
-                    double accv[16];
-#pragma unroll
-                    for (int c = 0; c < 16; ++c) accv[c] = 0.0;
-                    double s_prev = 0.0, su_prev = 0.0; // S[m][n - 1], S[m - 1][n - 1]
-                    for (int nn = 0; nn < N; ++nn) {
-                        const double s_cur = Sat(m, nn);
-                        const double su = shfl_up_f64(s_cur);
-                        const double R = (su_prev + s_cur) - (su + s_prev); // dG[m][nn] / w
-                        s_prev = s_cur;
-                        su_prev = su;
-                        const IO *yn = yj + (size_t)nn * d;
-                        if (KIND == SIGSVGD_STATIC_RBF) {
-                            double dist = 0.0;
-                            for (int c = 0; c < d; ++c) {
-                                const double t = (double)xm[c] - (double)yn[c];
-                                dist = __builtin_fma(t, t, dist);
-                            }
-                            const double rk = R * exp64(-dist * a.inv_h);
-#pragma unroll
-                            for (int c = 0; c < 16; ++c)
-                                if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
-                        } else {
-#pragma unroll
-                            for (int c = 0; c < 16; ++c)
-                                if (c0 + c < d) accv[c] = __builtin_fma(R, (double)yn[c0 + c], accv[c]);
-                        }
-                    }
-                    if (mvalid) {
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) {
-                            if (c0 + c < d) {
-                                const double val = KIND == SIGSVGD_STATIC_RBF ? (-2.0 * a.inv_h) * accv[c] : accv[c];
-                                if constexpr (PAIRED) {
-                                    static_cast<IO *>(a.gradX)[((size_t)i * M + m) * d + c0 + c] = (IO)(w * val);
-                                } else {
-                                    double *o = slab + (size_t)m * d + c0 + c;
-                                    *o = j == j0 ? w * val : __builtin_fma(w, val, *o);
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-            if constexpr (PAIRED) {
-                // ---- paired: S -> dG -> dk/dy -> gY_i, the X pass with the roles of the two paths swapped -------------------
-                // lane l holds column n0 - 1 + l of S and, from lane 1 on, the gradient of point n = n0 - 1 + l of Y_i
-                // (S[*][n - 1] arrives from the lane below it); m walks the points of X_i in order (x_m is wave-uniform)
-                auto SatY = [&](int aa, int bb) -> double {
-                    const bool in = aa < Mm && bb >= 0 && bb < Nm;
-                    aa = min(aa, Mm - 1);
-                    bb = min(max(bb, 0), Nm - 1);
-                    double s = 0.0;
-                    for (int t = 0; t < r; ++t) {
-                        const int pp = aa * r + t, l = pp & (kWave - 1);
-                        s += (double)wss[((size_t)(pp >> 6) * nsteps + l + (size_t)bb * r) * kWave + l];
-                    }
-                    return in ? s : 0.0;
-                };
-                const int ny_end = a.gradY ? N : 0;
-                for (int n0 = 0; n0 < ny_end; n0 += kWave - 1) {
-                    const int nn = n0 - 1 + lane;
-                    const bool nvalid = lane >= 1 && nn < N;
-                    const IO *yn = yj + (size_t)min(max(nn, 0), N - 1) * d;
-                    for (int c0 = 0; c0 < d; c0 += 16) {
-                        double accv[16];
-#pragma unroll
-                        for (int c = 0; c < 16; ++c) accv[c] = 0.0;
-                        double s_prev = 0.0, sl_prev = 0.0; // S[m - 1][n], S[m - 1][n - 1]
-                        for (int mm = 0; mm < M; ++mm) {
-                            const double s_cur = SatY(mm, nn);
-                            const double sl = shfl_up_f64(s_cur); // S[m][n - 1]
-                            const double R = (sl_prev + s_cur) - (sl + s_prev); // dG[m][n] / w
-                            s_prev = s_cur;
-                            sl_prev = sl;
-                            const IO *xm = xi + (size_t)mm * d;
-                            if (KIND == SIGSVGD_STATIC_RBF) {
-                                double dist = 0.0;
-                                for (int c = 0; c < d; ++c) {
-                                    const double t = (double)xm[c] - (double)yn[c];
-                                    dist = __builtin_fma(t, t, dist);
-                                }
-                                const double rk = R * exp64(-dist * a.inv_h);
-#pragma unroll
-                                for (int c = 0; c < 16; ++c)
-                                    if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
-                            } else {
-#pragma unroll
-                                for (int c = 0; c < 16; ++c)
-                                    if (c0 + c < d) accv[c] = __builtin_fma(R, (double)xm[c0 + c], accv[c]);
-                            }
-                        }
-                        if (nvalid) {
-#pragma unroll
-                            for (int c = 0; c < 16; ++c) {
-                                if (c0 + c < d) {
-                                    const double val = KIND == SIGSVGD_STATIC_RBF ? (2.0 * a.inv_h) * accv[c] : accv[c];
-                                    static_cast<IO *>(a.gradY)[((size_t)i * N + nn) * d + c0 + c] = (IO)(w * val);
-                                }
-                            }
-                        }
-                    }
-                }
+            if constexpr (PAIRED) { // (either output skipped when NULL)
+                IO *gX = static_cast<IO *>(a.gradX), *gY = static_cast<IO *>(a.gradY);
+                if (gX)
+                    static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
+                        gX[((size_t)i * M + m) * d + c] = (IO)(w * g);
+                    });
+                if (gY)
+                    static_grad_pass<KIND, false>(rw, yj, N, xi, M, d, a.inv_h, [&](int nn, int c, double g) {
+                        gY[((size_t)i * N + nn) * d + c] = (IO)(w * g);
+                    });
+            } else { // into the item's slab, in j order
+                static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
+                    double *o = slab + (size_t)m * d + c;
+                    *o = j == j0 ? w * g : __builtin_fma(w, g, *o);
+                });
             }
             __syncthreads(); // (the next pair's forward sweep overwrites the scratch and the ring)
         }
@@ -406,55 +234,30 @@ __global__ void long_reduce_kernel(const double *partials, IO *gradX, int A, int
 }
 
 namespace {
-struct LongPlan {
-    int r, P, Q, nbands, nsteps, nrow, W, JC, nchunks, grid;
+struct LongPlan : RingPlan {
+    int JC, nchunks, grid;
     long long items;
-    size_t lds, wsk_per_block, wsk_bytes, partial_bytes;
-    size_t total() const { return wsk_bytes + partial_bytes ? wsk_bytes + partial_bytes + 256 : 0; }
+    size_t wsk_bytes, partial_bytes;
+    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes); }
 };
 
 int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, LongPlan &pl, const char *who = "gram_long")
 {
-    pl.r = 1 << n;
-    const long long P = (long long)pl.r * (M - 1), Q = (long long)pl.r * (N - 1);
-    pl.nbands = (int)((P + kWave - 1) / kWave);
-    pl.nsteps = (int)(Q + kWave - 1);
-    const size_t per_wave = want_grad ? ((size_t)2 * pl.nbands * pl.nsteps * kWave + kWave) * sizeof(float) : 0;
-    if (P > kLongMaxCells || Q > kLongMaxCells) {
-        set_error("%s: refined grid %lld x %lld exceeds %d x %d (one wave's scratch would be %zu B)", who, P, Q,
-                  kLongMaxCells, kLongMaxCells, per_wave);
-        return SIGSVGD_E_UNSUPPORTED;
-    }
-    pl.P = (int)P;
-    pl.Q = (int)Q;
-    pl.nrow = n <= 6 ? (kWave >> n) : 1; // coarse rows of a band of 64 rows
-    int W = 1;
-    while (W < N - 1) W <<= 1;
-    int Wcap = 1;
-    while ((size_t)Wcap * 2 * pl.nrow <= kLongRingDoubles) Wcap <<= 1;
-    pl.W = W < Wcap ? W : Wcap; // >= the (126 >> n) + 2 columns a block of 64 steps can touch
-    pl.lds = long_lds_bytes(pl.nrow, pl.W, pl.Q, d);
-    if (pl.lds > 160 * 1024) {
-        set_error("%s: per-wave state needs %zu B of LDS (> 160 KiB): d=%d", who, pl.lds, d);
-        return SIGSVGD_E_UNSUPPORTED;
-    }
-    const long long cus = device_cu_count();
-    const int per_cu = (int)((160 * 1024) / pl.lds);
-    const long long resident = cus * (per_cu > 8 ? 8 : per_cu);
+    const int rc = ring_make_plan(M, N, n, want_grad, d, who, pl); // (+ the band's nrow + 1 points of X_i in LDS)
+    if (rc) return rc;
     // work items (i, chunk of JC columns): enough to give every resident wave one, few enough gradient slabs
     int JC = 32;
-    while (JC > 1 && (long long)A * ((B + JC - 1) / JC) < resident) JC >>= 1;
+    while (JC > 1 && (long long)A * ((B + JC - 1) / JC) < pl.resident) JC >>= 1;
     pl.JC = JC;
     pl.nchunks = (B + JC - 1) / JC;
     pl.items = (long long)A * pl.nchunks;
-    long long grid = resident < pl.items ? resident : pl.items;
-    if (want_grad && per_wave * (size_t)grid > kLongMaxScratch) {
-        grid = (long long)(kLongMaxScratch / per_wave);
+    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
+    if (want_grad && pl.per_wave * (size_t)grid > kRingMaxScratch) {
+        grid = (long long)(kRingMaxScratch / pl.per_wave);
         if (grid < 1) grid = 1;
     }
     pl.grid = (int)grid;
-    pl.wsk_per_block = per_wave / sizeof(float);
-    pl.wsk_bytes = ((per_wave * (size_t)grid) + 255) & ~(size_t)255;
+    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
     pl.partial_bytes = want_grad ? (size_t)A * pl.nchunks * M * d * sizeof(double) : 0;
     return SIGSVGD_OK;
 }
@@ -465,7 +268,27 @@ int pair_make_plan(int A, int M, int N, int d, int n, int want_grad, LongPlan &p
 {
     const int rc = long_make_plan(A, 1, M, N, d, n, want_grad, pl, "pair");
     if (rc) return rc;
+    pl.JC = 1;
     pl.partial_bytes = 0;
+    return SIGSVGD_OK;
+}
+
+// the arguments of a Gram launch (B columns) or a paired one (B = 1, no sym), from the plan and the caller's workspace
+// (checked against the plan; the Gram mode's slabs follow the forward scratch)
+int long_args(const char *who, const LongPlan &pl, void *ws, size_t ws_bytes, const void *X, const void *Y, const void *grad_out,
+              void *K_out, int A, int B, int M, int N, int d, int n, bool sym, double inv_h, LongArgs &a)
+{
+    unsigned char *base = nullptr;
+    const int rc = ring_ws_base(who, ws, ws_bytes, pl.total(), base);
+    if (rc) return rc;
+    a.X = X; a.Y = Y; a.grad_out = grad_out; a.K_out = K_out;
+    a.wsk = reinterpret_cast<float *>(base);
+    a.partials = pl.partial_bytes ? reinterpret_cast<double *>(base + pl.wsk_bytes) : nullptr;
+    a.wsk_per_block = pl.per_wave / sizeof(float);
+    a.A = A; a.B = B; a.M = M; a.N = N; a.d = d; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
+    a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = pl.JC; a.nchunks = pl.nchunks;
+    a.sym = sym ? 1 : 0; a.items = pl.items; a.inv_h = inv_h;
+    a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
     return SIGSVGD_OK;
 }
 
@@ -514,24 +337,10 @@ int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d,
 {
     const int want_grad = gradX_out != nullptr;
     LongPlan pl;
-    const int rc = long_make_plan(A, B, M, N, d, n, want_grad, pl);
-    if (rc) return rc;
-    const size_t need = pl.total();
-    if (ws_bytes < need || (need && !ws)) {
-        set_error("gram_long: workspace %zu B too small, required %zu B", ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    unsigned char *base = need ? reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255)
-                               : nullptr;
     LongArgs a;
-    a.X = X; a.Y = Y; a.grad_out = grad_out; a.K_out = K_out;
-    a.wsk = want_grad ? reinterpret_cast<float *>(base) : nullptr;
-    a.partials = want_grad ? reinterpret_cast<double *>(base + pl.wsk_bytes) : nullptr;
-    a.wsk_per_block = pl.wsk_per_block;
-    a.A = A; a.B = B; a.M = M; a.N = N; a.d = d; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
-    a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = pl.JC; a.nchunks = pl.nchunks;
-    a.sym = sym ? 1 : 0; a.items = pl.items; a.inv_h = inv_h;
-    a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
+    int rc = long_make_plan(A, B, M, N, d, n, want_grad, pl);
+    if (!rc) rc = long_args("gram_long", pl, ws, ws_bytes, X, Y, grad_out, K_out, A, B, M, N, d, n, sym, inv_h, a);
+    if (rc) return rc;
     hipError_t e = dtype == SIGSVGD_F64 ? long_dispatch<double>(kind, naive, want_grad != 0, pl, stream, a)
                                         : long_dispatch<float>(kind, naive, want_grad != 0, pl, stream, a);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long)");
@@ -571,24 +380,10 @@ int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dt
 {
     const int want_grad = gradX_out != nullptr || gradY_out != nullptr;
     LongPlan pl;
-    const int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
-    if (rc) return rc;
-    const size_t need = pl.total();
-    if (ws_bytes < need || (need && !ws)) {
-        set_error("pair: workspace %zu B too small, required %zu B", ws_bytes, need);
-        return SIGSVGD_E_WORKSPACE;
-    }
-    unsigned char *base = need ? reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255)
-                               : nullptr;
     PairArgs a;
-    a.X = X; a.Y = Y; a.grad_out = grad_out; a.K_out = K_out;
-    a.wsk = want_grad ? reinterpret_cast<float *>(base) : nullptr;
-    a.partials = nullptr;
-    a.wsk_per_block = pl.wsk_per_block;
-    a.A = A; a.B = 1; a.M = M; a.N = N; a.d = d; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
-    a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = 1; a.nchunks = 1;
-    a.sym = 0; a.items = pl.items; a.inv_h = inv_h;
-    a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
+    int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
+    if (!rc) rc = long_args("pair", pl, ws, ws_bytes, X, Y, grad_out, K_out, A, 1, M, N, d, n, false, inv_h, a);
+    if (rc) return rc;
     a.gradX = gradX_out; a.gradY = gradY_out;
     const hipError_t e = dtype == SIGSVGD_F64 ? long_dispatch<double, true>(kind, naive, want_grad != 0, pl, stream, a)
                                               : long_dispatch<float, true>(kind, naive, want_grad != 0, pl, stream, a);

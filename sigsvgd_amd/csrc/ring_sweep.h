@@ -1,0 +1,241 @@
+// The long-path PDE sweep shared by sig_pde_kernel (sig_pde.hip) and gram_long_kernel (gram_long.hip), DESIGN.md sections
+// 5.9 - 5.11: the ring plan's geometry, the forward and reverse sweeps of one pair, and the reader of the pair's coarse S.
+//
+// One wavefront per pair; the refined P x Q grid is swept in bands of 64 rows, one row per lane, anti-diagonal by
+// anti-diagonal (lane l is at column s - l on step s); the band's boundary row is in LDS.  The band's fp64 increments live in
+// an LDS ring of W coarse columns of the band's nrow coarse rows; the caller's fill refills it between blocks of 64 sweep
+// steps (never inside a step), with every column the next block can touch, so W = 128 columns at dyadic order 0 hold grids
+// of any width.  For the backward pass the forward solution goes to the wave's scratch in [band][step][lane] order (fp32,
+// coalesced 256-B rows); the reverse sweep writes each lane's partial block sum of GG (over the r columns of a block) in the
+// same order, and ring_S adds the r rows of a block in row order: no floating-point atomics, the bits depend on the inputs.
+#pragma once
+
+#include "sig_common.h"
+
+namespace sigsvgd {
+namespace {
+constexpr int kRingMaxCells = 8192;                 // P and Q
+constexpr size_t kRingDoubles = 8192;               // 64 KB of increments per wave
+constexpr size_t kRingMaxScratch = (size_t)1 << 30; // the launch's scratch: each family lowers its grid to stay below it
+constexpr size_t kRingMaxLds = 160 * 1024;
+
+struct RingPlan {
+    int r, P, Q, nbands, nsteps, nrow, W;
+    size_t per_wave;    // bytes of one wave's scratch (0 for forward-only launches: the forward sweep keeps nothing)
+    size_t lds;         // bytes of one wave's LDS
+    long long resident; // waves the device holds at that LDS (at most 8 per CU)
+};
+
+// The geometry of a launch on M x N coarse grids at dyadic order n.  The LDS is the ring of nrow x W fp64 increments, the
+// boundary row [Q + 2], the per-lane dump cells [64], and the caller's [nrow + 1][row_doubles] behind them.  Refuses grids
+// past kRingMaxCells and LDS past 160 KiB (messages prefixed by `who`).
+int ring_make_plan(int M, int N, int n, int want_grad, int row_doubles, const char *who, RingPlan &pl)
+{
+    pl.r = 1 << n;
+    const long long P = (long long)pl.r * (M - 1), Q = (long long)pl.r * (N - 1);
+    pl.nbands = (int)((P + kWave - 1) / kWave);
+    pl.nsteps = (int)(Q + kWave - 1);
+    pl.per_wave = want_grad ? ((size_t)2 * pl.nbands * pl.nsteps * kWave + kWave) * sizeof(float) : 0;
+    if (P > kRingMaxCells || Q > kRingMaxCells) {
+        set_error("%s: refined grid %lld x %lld exceeds %d x %d (one wave's scratch would be %zu B)", who, P, Q,
+                  kRingMaxCells, kRingMaxCells, pl.per_wave);
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    pl.P = (int)P;
+    pl.Q = (int)Q;
+    pl.nrow = n <= 6 ? (kWave >> n) : 1; // coarse rows of a band of 64 rows
+    int W = 1;
+    while (W < N - 1) W <<= 1;
+    int Wcap = 1;
+    while ((size_t)Wcap * 2 * pl.nrow <= kRingDoubles) Wcap <<= 1;
+    pl.W = W < Wcap ? W : Wcap; // >= the (126 >> n) + 2 columns a block of 64 steps can touch
+    pl.lds = ((size_t)pl.nrow * pl.W + pl.Q + 2 + kWave + (size_t)(pl.nrow + 1) * row_doubles) * sizeof(double);
+    if (pl.lds > kRingMaxLds) {
+        set_error("%s: per-wave state needs %zu B of LDS (> 160 KiB)", who, pl.lds);
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    const int per_cu = (int)(kRingMaxLds / pl.lds);
+    pl.resident = (long long)device_cu_count() * (per_cu > 8 ? 8 : per_cu);
+    return SIGSVGD_OK;
+}
+
+// the bytes a caller gives for `bytes` of workspace (+ the slack of aligning its pointer; 0 when nothing is needed)
+size_t ring_ws_total(size_t bytes) { return bytes ? bytes + 256 : 0; }
+
+// `base` = ws aligned to 256 B (NULL when need is 0); SIGSVGD_E_WORKSPACE when the caller's buffer is smaller than `need`
+int ring_ws_base(const char *who, void *ws, size_t ws_bytes, size_t need, unsigned char *&base)
+{
+    if (ws_bytes < need || (need && !ws)) {
+        set_error("%s: workspace %zu B too small, required %zu B", who, ws_bytes, need);
+        return SIGSVGD_E_WORKSPACE;
+    }
+    base = need ? reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255) : nullptr;
+    return SIGSVGD_OK;
+}
+
+// one wave's view of the plan: its geometry, its LDS and (GRAD) its scratch
+struct RingWave {
+    int N, n, r, P, Q, W, nbands, nsteps;
+    double inv_r2;
+    double *ring;   // [nrow][W]: D[a0 + row][b] at column slot b & (W - 1)
+    double *rowbuf; // [Q + 2]
+    double *dump;   // [64]: where the lanes that have nothing to hand over store; the caller's LDS follows
+    float *wsk;     // forward solution [band][step][lane]
+    float *wss;     // S partials, same order as the forward solution
+    float *spare;   // the lane's cell of the spare row
+};
+template <bool GRAD, typename Args>
+__device__ __forceinline__ RingWave ring_wave(const Args &a, unsigned char *smem)
+{
+    RingWave w;
+    w.N = a.N; w.n = a.n; w.r = a.r; w.P = a.P; w.Q = a.Q; w.W = a.W; w.nbands = a.nbands; w.nsteps = a.nsteps;
+    w.inv_r2 = a.inv_r2;
+    w.ring = reinterpret_cast<double *>(smem);
+    w.rowbuf = w.ring + (size_t)a.nrow * a.W;
+    w.dump = w.rowbuf + (a.Q + 2);
+    const size_t area = (size_t)a.nbands * a.nsteps * kWave;
+    w.wsk = GRAD ? a.wsk + (size_t)blockIdx.x * a.wsk_per_block : nullptr;
+    w.wss = GRAD ? w.wsk + area : nullptr;
+    w.spare = GRAD ? w.wss + area + threadIdx.x : nullptr;
+    return w;
+}
+
+// ---- forward sweep of one pair over all bands: returns the final value of the lane that holds row P - 1 ----------------------
+// fill(a0, b_lo, b_hi): coarse columns b_lo .. b_hi of the increment rows a0 .. a0 + nrow - 1 into the ring, between barriers;
+// band(a0): called as each band starts, before its first fill.  (The step of gram_generic_kernel: branch-free, results of
+// lanes outside the grid dropped by selects, the operands of step s + 1 fetched during step s.)
+template <bool NAIVE, bool GRAD, typename Fill, typename Band>
+__device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, Band &&band)
+{
+    const int lane = threadIdx.x;
+    const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
+    double *rowbuf = w.rowbuf;
+    double Kval = 1.0;
+    for (int kb = 0; kb < w.nbands; ++kb) {
+        const int p = kb * kWave + lane;
+        const bool rowvalid = p < P;
+        const bool first = kb == 0;
+        const int a0 = (kb * kWave) >> n;
+        band(a0);
+        const double *Drow = w.ring + (size_t)((min(p, P - 1) >> n) - a0) * W;
+        float *wp = GRAD ? w.wsk + (size_t)kb * nsteps * kWave + lane : nullptr;
+        double cur = 1.0, upprev = 1.0;
+        double rb = first ? 1.0 : rowbuf[1]; // lane 0's upper neighbour on step s: rowbuf[s + 1]
+        int have = -1;                       // coarse columns 0 .. have are in the ring (the last ones filled)
+        for (int s0 = 0; s0 < nsteps; s0 += kWave) {
+            const int lo = max(s0 - (kWave - 1), 0) >> n, hi = min((s0 + kWave - 1) >> n, N - 2);
+            if (hi > have) { // every column this block and as many later ones as the ring holds
+                const int to = min(N - 2, lo + W - 1);
+                fill(a0, have + 1, to);
+                have = to;
+            }
+            double gf = Drow[(min(max(s0 - lane, 0), Q - 1) >> n) & (W - 1)];
+            const int s1 = min(s0 + kWave, nsteps);
+            for (int s = s0; s < s1; ++s) {
+                const int q = s - lane;
+                const bool active = rowvalid && q >= 0 && q < Q;
+                const double gfn = Drow[(min(max(q + 1, 0), Q - 1) >> n) & (W - 1)];
+                const double rbr = rowbuf[min(s + 2, Q)];
+                const double rbn = first ? 1.0 : rbr;
+                double up_in = shfl_up_f64(cur);
+                up_in = (lane == 0) ? rb : up_in;
+                const double nw = stencil(cur, up_in, upprev, gf * w.inv_r2, NAIVE);
+                if (GRAD) { // K_fwd[p][q] at [step][lane] (issued from inline asm: no wait for the previous step's store)
+                    const float kst = (float)upprev;
+                    asm volatile("global_store_dword %0, %1, off" ::"v"(wp + (size_t)s * kWave), "v"(kst));
+                }
+                *((lane == kWave - 1 && active) ? rowbuf + (q + 1) : w.dump + lane) = nw;
+                cur = active ? nw : cur;
+                upprev = active ? up_in : upprev;
+                gf = gfn;
+                rb = rbn;
+            }
+        }
+        if (p == P - 1) Kval = cur;
+    }
+    return Kval;
+}
+
+// ---- reverse sweep: GG = K_fwd[p][q] K_rev[p+1][q+1], summed over the r columns of a block per lane, into w.wss -------------
+// (fill and band as in ring_forward; the caller makes the forward solution visible first)
+template <bool NAIVE, typename Fill, typename Band>
+__device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Band &&band)
+{
+    const int lane = threadIdx.x;
+    const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
+    double *rowbuf = w.rowbuf;
+    for (int kb = w.nbands - 1; kb >= 0; --kb) {
+        const int p = kb * kWave + lane;
+        const bool rowvalid = p < P;
+        const int L = min(kWave, P - kb * kWave);
+        const int a0 = (kb * kWave) >> n;
+        band(a0);
+        const double *Drow = w.ring + (size_t)((min(p, P - 1) >> n) - a0) * W;
+        float *wsrow = w.wss + (size_t)kb * nsteps * kWave + lane;
+        const float *wrow = w.wsk + (size_t)kb * nsteps * kWave + lane; // K_fwd[p][q] at step lane + q
+        const bool lastband = kb == w.nbands - 1;
+        const bool hands_over = lane == 0 && kb > 0;
+        double cur = 1.0, dprev = 1.0, sb = 0.0;
+        const int nsp = Q + L - 1;
+        int q = Q - 1 + (L - 1 - lane);
+        int R = Q - 1 + L - 1; // row of the stored forward solution on reverse step 0
+        double rb = lastband ? 1.0 : rowbuf[Q - 1]; // lane L-1's lower neighbour on step sp: rowbuf[Q - 1 - sp]
+        constexpr int KPF = 8; // ring of the next KPF rows of the forward solution (an L2 round trip is ~8 steps long)
+        float kfr[KPF];
+#pragma unroll
+        for (int u = 0; u < KPF; ++u) kfr[u] = wrow[(size_t)max(R - u, 0) * kWave];
+        int low = N - 1; // coarse columns low .. N - 2 are in the ring
+        for (int sp0 = 0; sp0 < nsp; sp0 += kWave) {
+            const int qhi = Q + L - 2 - sp0; // the columns of this block: qhi - 126 .. qhi
+            const int need_hi = min(qhi, Q - 1) >> n, need_lo = max(qhi - 2 * (kWave - 1), 0) >> n;
+            if (need_lo < low) {
+                const int from = max(0, need_hi - W + 1);
+                fill(a0, from, low - 1);
+                low = from;
+            }
+            double gf = Drow[(min(max(q, 0), Q - 1) >> n) & (W - 1)];
+            double rbk = rowbuf[max(Q - 1 - sp0, 0)];
+            rb = lastband ? 1.0 : rbk;
+            // (the groups past nsp have no lane inside the grid and change nothing; their S stores go to the spare row)
+            for (int sp1 = sp0; sp1 < sp0 + kWave; sp1 += KPF) {
+#pragma unroll
+                for (int u = 0; u < KPF; ++u, --q, --R) {
+                    const int sp = sp1 + u;
+                    const bool active = rowvalid && q >= 0 && q < Q;
+                    const double gfn = Drow[(min(max(q - 1, 0), Q - 1) >> n) & (W - 1)];
+                    const double rbr = rowbuf[max(Q - 2 - sp, 0)];
+                    const double rbn = lastband ? 1.0 : rbr;
+                    const double kf = (double)kfr[u];
+                    kfr[u] = wrow[(size_t)max(R - KPF, 0) * kWave];
+                    double down_in = shfl_down_f64(cur);
+                    down_in = (lane == L - 1) ? rb : down_in;
+                    sb = active ? __builtin_fma(kf, dprev, sb) : sb;
+                    const bool done = active && (q & (w.r - 1)) == 0; // the block's last (lowest) column
+                    const float sst = done ? (float)(sb * w.inv_r2) : 0.f;
+                    asm volatile("global_store_dword %0, %1, off" ::"v"(R >= 0 ? wsrow + (size_t)R * kWave : w.spare), "v"(sst));
+                    sb = done ? 0.0 : sb;
+                    const double nw = stencil(cur, down_in, dprev, gf * w.inv_r2, NAIVE);
+                    *((hands_over && active) ? rowbuf + q : w.dump + lane) = nw;
+                    cur = active ? nw : cur;
+                    dprev = active ? down_in : dprev;
+                    gf = gfn;
+                    rb = rbn;
+                }
+            }
+        }
+    }
+}
+
+// S[aa][bb]: the r lane partials of block (aa, bb) in row order (lane pp & 63 of band pp >> 6 filed the partial of row pp,
+// block column bb, on reverse step (pp & 63) + bb r); the caller makes the reverse sweep's stores visible first
+__device__ __forceinline__ double ring_S(const RingWave &w, int aa, int bb)
+{
+    double s = 0.0;
+    for (int i = 0; i < w.r; ++i) {
+        const int pp = aa * w.r + i, l = pp & (kWave - 1);
+        s += (double)w.wss[((size_t)(pp >> 6) * w.nsteps + l + (size_t)bb * w.r) * kWave + l];
+    }
+    return s;
+}
+} // namespace
+} // namespace sigsvgd

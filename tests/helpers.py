@@ -82,14 +82,12 @@ def patch_ops(monkeypatch):
         monkeypatch.setattr(ops, name, fn)
 
 
-def long_plan(A, B, M, N, d, n, want_grad=True, cus=256):
-    """The launch plan of csrc/gram_long.hip (`long_make_plan`) for X [A, M, d] x Y [B, N, d] on `cus` compute units, as a
-    dict (nrow, W, JC, nchunks, items, grid, lds, bytes), or None where the library refuses the launch (E_UNSUPPORTED).
-    `bytes` is what sigsvgd_gram_long_workspace_bytes reports; tests/test_long_cabi.py pins the two together."""
+def ring_plan(M, N, n, want_grad, row_doubles, cus):
+    """The geometry of csrc/ring_sweep.h (`ring_make_plan`) for M x N coarse grids at order n on `cus` compute units, as a
+    dict (P, Q, nrow, W, lds, per_wave, resident), or None where the library refuses the launch (E_UNSUPPORTED).
+    `row_doubles`: the caller's LDS per point of a band's nrow + 1 coarse rows (0 for sig_pde, d for gram_long)."""
     r = 1 << n
     P, Q = r * (M - 1), r * (N - 1)
-    nbands, nsteps = -(-P // 64), Q + 63
-    per_wave = (2 * nbands * nsteps * 64 + 64) * 4 if want_grad else 0
     if P > 8192 or Q > 8192:
         return None
     nrow = 64 >> n if n <= 6 else 1
@@ -100,52 +98,58 @@ def long_plan(A, B, M, N, d, n, want_grad=True, cus=256):
     while Wcap * 2 * nrow <= 8192:
         Wcap <<= 1
     W = min(W, Wcap)
-    lds = (nrow * W + Q + 2 + 64 + (nrow + 1) * d) * 8
+    lds = (nrow * W + Q + 2 + 64 + (nrow + 1) * row_doubles) * 8
     if lds > 160 * 1024:
         return None
-    resident = cus * min(160 * 1024 // lds, 8)
+    per_wave = (2 * -(-P // 64) * (Q + 63) * 64 + 64) * 4 if want_grad else 0
+    return dict(P=P, Q=Q, nrow=nrow, W=W, lds=lds, per_wave=per_wave, resident=cus * min(160 * 1024 // lds, 8))
+
+
+def long_plan(A, B, M, N, d, n, want_grad=True, cus=256):
+    """The launch plan of csrc/gram_long.hip (`long_make_plan`) for X [A, M, d] x Y [B, N, d] on `cus` compute units, as a
+    dict (nrow, W, JC, nchunks, items, grid, lds, bytes), or None where the library refuses the launch (E_UNSUPPORTED).
+    `bytes` is what sigsvgd_gram_long_workspace_bytes reports; tests/test_long_cabi.py pins the two together."""
+    pl = ring_plan(M, N, n, want_grad, d, cus)
+    if pl is None:
+        return None
     JC = 32
-    while JC > 1 and A * -(-B // JC) < resident:
+    while JC > 1 and A * -(-B // JC) < pl["resident"]:
         JC >>= 1
     nchunks = -(-B // JC)
-    items = A * nchunks
-    grid = min(resident, items)
-    if want_grad and per_wave * grid > (1 << 30):
-        grid = max(1, (1 << 30) // per_wave)
-    wsk_bytes = (per_wave * grid + 255) & ~255
+    grid = min(pl["resident"], A * nchunks)
+    if want_grad and pl["per_wave"] * grid > (1 << 30):
+        grid = max(1, (1 << 30) // pl["per_wave"])
+    wsk_bytes = (pl["per_wave"] * grid + 255) & ~255
     partial_bytes = A * nchunks * M * d * 8 if want_grad else 0
     total = wsk_bytes + partial_bytes + 256 if wsk_bytes + partial_bytes else 0
-    return dict(P=P, Q=Q, nrow=nrow, W=W, JC=JC, nchunks=nchunks, items=items, grid=grid, lds=lds, bytes=total)
+    return dict(pl, JC=JC, nchunks=nchunks, items=A * nchunks, grid=grid, bytes=total)
+
+
+def pair_plan(A, M, N, d, n, want_grad=True, cus=256):
+    """The paired launch plan of csrc/gram_long.hip (`pair_make_plan`) for X [A, M, d] and Y [A, N, d] on `cus` compute
+    units, as a dict (P, Q, nrow, W, resident, grid, lds, bytes), or None where the library refuses the launch (E_UNSUPPORTED).
+    One pair per wavefront: grid = min(resident waves, A), lowered to keep the per-wave scratch within 1 GiB; no slabs."""
+    pl = long_plan(A, 1, M, N, d, n, want_grad, cus)
+    if pl is None:
+        return None
+    wsk_bytes = (pl["per_wave"] * pl["grid"] + 255) & ~255
+    return dict(pl, bytes=wsk_bytes + 256 if wsk_bytes else 0)
 
 
 def pde_plan(npairs, M, N, n, want_grad=True, cus=256):
     """The launch plan of csrc/sig_pde.hip (`pde_make_plan`) for npairs grids [M, N] on `cus` compute units, as a dict
     (nrow, W, grid, lds, bytes), or None where the library refuses the launch.  `bytes` is what sigsvgd_pde_workspace_bytes
     reports; tests/test_pde_cabi.py pins the two together."""
-    r = 1 << n
-    P, Q = r * (M - 1), r * (N - 1)
-    nbands, nsteps = -(-P // 64), Q + 63
-    per_wave = (2 * nbands * nsteps * 64 + 64) * 4 if want_grad else 0
-    if P > 8192 or Q > 8192:
+    pl = ring_plan(M, N, n, want_grad, 0, cus)
+    if pl is None:
         return None
-    nrow = 64 >> n if n <= 6 else 1
-    W = 1
-    while W < N - 1:
-        W <<= 1
-    Wcap = 1
-    while Wcap * 2 * nrow <= 8192:
-        Wcap <<= 1
-    W = min(W, Wcap)
-    lds = (nrow * W + Q + 2 + 64) * 8
-    if lds > 160 * 1024:
-        return None
+    per_wave = pl["per_wave"]
     slots = min(cus * 8, npairs)
     ws = per_wave * slots
     if ws > (1 << 30):
         slots = max(1, (1 << 30) // per_wave)
         ws = max(per_wave, 1 << 30)
-    grid = min(cus * min(160 * 1024 // lds, 8), slots)
-    return dict(P=P, Q=Q, nrow=nrow, W=W, grid=grid, lds=lds, bytes=ws + 256 if ws else 0)
+    return dict(pl, grid=min(pl["resident"], slots), bytes=ws + 256 if ws else 0)
 
 
 def device_cus():

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import pair_plan
 from oracle import sigkernel_oracle as O
 from sigsvgd_amd import _lib, ops
 
@@ -28,35 +29,6 @@ def pair_ws(A, TX, TY, d, n, kind=_lib.STATIC_RBF, want_grad=1, flags=0, out=Tru
     b = ctypes.c_size_t(12345)
     rc = lib().sigsvgd_pair_workspace_bytes(A, TX, TY, d, n, kind, want_grad, flags, ctypes.byref(b) if out else None)
     return rc, b.value
-
-
-def pair_plan(A, M, N, d, n, want_grad=True, cus=256):
-    """The paired launch plan of csrc/gram_long.hip (`pair_make_plan`) for X [A, M, d] and Y [A, N, d] on `cus` compute
-    units, as a dict (P, Q, nrow, W, grid, lds, bytes), or None where the library refuses the launch (E_UNSUPPORTED).  One
-    pair per wavefront: grid = min(resident waves, A), lowered to keep the per-wave scratch within 1 GiB; no slabs."""
-    r = 1 << n
-    P, Q = r * (M - 1), r * (N - 1)
-    nbands, nsteps = -(-P // 64), Q + 63
-    per_wave = (2 * nbands * nsteps * 64 + 64) * 4 if want_grad else 0
-    if P > 8192 or Q > 8192:
-        return None
-    nrow = 64 >> n if n <= 6 else 1
-    W = 1
-    while W < N - 1:
-        W <<= 1
-    Wcap = 1
-    while Wcap * 2 * nrow <= 8192:
-        Wcap <<= 1
-    W = min(W, Wcap)
-    lds = (nrow * W + Q + 2 + 64 + (nrow + 1) * d) * 8
-    if lds > 160 * 1024:
-        return None
-    resident = cus * min(160 * 1024 // lds, 8)
-    grid = min(resident, A)
-    if want_grad and per_wave * grid > (1 << 30):
-        grid = max(1, (1 << 30) // per_wave)
-    wsk_bytes = (per_wave * grid + 255) & ~255
-    return dict(P=P, Q=Q, nrow=nrow, W=W, resident=resident, grid=grid, lds=lds, bytes=wsk_bytes + 256 if wsk_bytes else 0)
 
 
 def test_pair_symbols_exported():
