@@ -33,6 +33,8 @@
  *   sigsvgd_gram_long_fwd_bwd  static kernel evaluated inside the PDE sweep)
  *   sigsvgd_pair_fwd       sigkernel.SigKernel.compute_kernel(X, Y) with a built-in static kernel: k_sig(X_i, Y_i) per
  *   sigsvgd_pair_fwd_bwd   pair, and the gradients of both paths from one solve per pair
+ *   sigsvgd_gram_long_fwd_bwd2  sigsvgd_gram_long_fwd_bwd with the gradients of both slots from one solve per pair
+ *                          (sigkernel's compute_mmd with a trainable Y), and with Y = X each unordered pair once (SVGD)
  *
  * Conventions
  *   - all pointers are DEVICE pointers (HIP), row-major contiguous; the caller owns every buffer
@@ -287,7 +289,8 @@ int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int 
  * The static kernel (SIGSVGD_STATIC_RBF or _LINEAR) is evaluated inside the kernel, in fp64, and its 4-corner increments are
  * formed as the sweep needs them: nothing of size A*B*TX*TY exists.  Increments, sweeps and the gradient are fp64; the stored
  * forward solution and the block sums S are fp32 (per-wave scratch).  Backward in the reference's GG convention, as
- * sigsvgd_pde_fwd_bwd, chained through dk/dx.  Every ordered pair (i, j) is solved.
+ * sigsvgd_pde_fwd_bwd, chained through dk/dx.  Every ordered pair (i, j) is solved (sigsvgd_gram_long_fwd_bwd2 below solves
+ * Y = X once per unordered pair, and gives the gradient of Y).
  * Flags: SIGSVGD_FLAG_NAIVE_SOLVER; SIGSVGD_FLAG_SYM (weights grad_out + grad_out^T, needs A == B and TX == TY);
  * SIGSVGD_FLAG_Y_IS_X is accepted and has no effect; any other bit is SIGSVGD_E_BADARG.  Limits: P = 2^n (TX-1) and
  * Q = 2^n (TY-1) up to 8192, and the per-wave LDS (boundary row of Q + 2 doubles, 64 KB of increments, the band's points)
@@ -326,6 +329,28 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
                          int dyadic_order, int static_kind, unsigned flags, const void *grad_out /* [A] or NULL = ones */,
                          void *K_out, void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- long-path Gram, both slots and Y = X (ABI 10, additive) ---------------------------------------
+ * The two-sided launch of the long-path kernel: the K[A,B] of sigsvgd_gram_long_fwd, bit for bit, and from each pair's one
+ * reverse sweep
+ *   gradX_out[i][m] = sum_j w_ij sum_n dG_ij[m][n] dk(x_im, y_jn)/dx_im     (first slot, as sigsvgd_gram_long_fwd_bwd)
+ *   gradY_out[j][n] = sum_i w_ij sum_m dG_ij[m][n] dk(x_im, y_jn)/dy_jn     (second slot, the same GG convention),
+ * w = grad_out (NULL = ones).  Either output may be NULL; both NULL is a forward-only launch.
+ * SIGSVGD_FLAG_Y_IS_X (A == B, TX == TY, gradY_out == NULL; the caller guarantees Y holds X's values): only the pairs i <= j
+ * are solved, K_out[j][i] is a copy of K_out[i][j], and gradX_out is the first-slot gradient of the ordered launch: pair
+ * (i, j), i < j, gives w_ij d1 k(X_i, X_j) to row i and w_ji d2 k(X_i, X_j) = w_ji d1 k(X_j, X_i) to row j.
+ * SIGSVGD_FLAG_SYM (A == B, TX == TY, gradY_out == NULL): weights w_ij + w_ji.  SIGSVGD_FLAG_NAIVE_SOLVER as elsewhere;
+ * any other bit is SIGSVGD_E_BADARG.  Limits and refusals are sigsvgd_gram_long_fwd's.
+ * Work items are tiles of IC rows x JC columns (with Y_IS_X: the tiles of the upper triangle); a tile adds its pairs into
+ * one fp64 slab per row and one per column in a fixed order, and the slabs of a row (a column) are summed in tile order:
+ * bit-reproducible, no floating-point atomics.  Workspace: the per-wave scratch of sigsvgd_gram_long_fwd_bwd plus at most
+ * (A ceil(B / JC) TX + B ceil(A / IC) TY) d doubles of slabs; forward-only launches need none and report 0 bytes. */
+int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
+                                       int want_gradX, int want_gradY, unsigned flags, size_t *bytes);
+int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                               int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                               void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

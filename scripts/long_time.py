@@ -3,11 +3,19 @@ same inputs.
 
     python scripts/long_time.py [--reps 10]
 
-Prints one JSON line per shape: milliseconds per launch (median of `reps` timed with device events after warm-up) of
-  long_fwd_bwd          ops.gram_long_fwd_bwd(X, X): K and the gradient, the static kernel evaluated inside the sweep;
+Prints one JSON line per shape: milliseconds per launch, [median, min, max] of `reps` timed with device events after
+warm-up, of
+  long_fwd_bwd          ops.gram_long_fwd_bwd(X, X): K and the gradient, the static kernel evaluated inside the sweep,
+                        every ordered pair solved;
+  long2_y_is_x          ops.gram_long_fwd_bwd2(X, X, y_is_x=True): the same K and gradient, each unordered pair once;
+  long_fwd, long2_y_is_x_fwd   the two forward-only launches;
+  long_two_ordered      ops.gram_long_fwd_bwd(X, Y, W) then ops.gram_long_fwd_bwd(Y, X, W^T): both slots' gradients from
+                        two ordered launches;
+  long2_two_slot        ops.gram_long_fwd_bwd2(X, Y, W): both from one launch;
   user_gram_and_grad    SigKernel(<RBF behind Gram_matrix only>).gram_and_grad(X, X): torch builds the [A, B, T, T] grid,
-                        sig_pde.hip solves it, torch autograd chains dG to X.
-Shapes: A = B = 32, T = 512, d = 4, order 0; A = B = 16, T = 200, d = 3, order 2 (both refused by the fused kernels).
+                        sig_pde.hip solves it, torch autograd chains dG to X (the first two shapes).
+Shapes: A = B = 32, T = 512, d = 4, order 0; A = B = 16, T = 200, d = 3, order 2; A = B = 64, T = 300, d = 7, order 0 (all
+refused by the fused kernels).
 """
 import argparse
 import json
@@ -43,7 +51,7 @@ def timed(fn, reps, warmup=2):
         b.synchronize()
         ts.append(a.elapsed_time(b))
     ts.sort()
-    return ts[len(ts) // 2]
+    return [round(ts[len(ts) // 2], 4), round(ts[0], 4), round(ts[-1], 4)]
 
 
 def main():
@@ -53,14 +61,26 @@ def main():
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    for (N, T, d, order) in [(32, 512, 4, 0), (16, 200, 3, 2)]:
+    for (N, T, d, order, user) in [(32, 512, 4, 0, True), (16, 200, 3, 2, True), (64, 300, 7, 0, False)]:
         X = (torch.randn(N, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).to(dev)
+        Y = (torch.randn(N, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).to(dev)
+        W = torch.rand(N, N, generator=g, dtype=torch.float64).to(dev) + 0.5
+        Wt = W.T.contiguous()
         assert not ops.gram_takes(N, N, T, d, order)
+        ih = 1.0 / a.h
         res = {"shape": [N, T, d], "order": order}
-        res["long_fwd_bwd"] = timed(lambda: ops.gram_long_fwd_bwd(X, X, 1.0 / a.h, order), a.reps)
-        k = sk.SigKernel(_GramOnlyRBF(a.h), order)
-        res["user_gram_and_grad"] = timed(lambda: k.gram_and_grad(X, X), a.reps)
-        print(json.dumps({k_: (round(v, 4) if isinstance(v, float) else v) for k_, v in res.items()}), flush=True)
+        res["long_fwd_bwd"] = timed(lambda: ops.gram_long_fwd_bwd(X, X, ih, order), a.reps)
+        res["long2_y_is_x"] = timed(lambda: ops.gram_long_fwd_bwd2(X, X, ih, order, y_is_x=True), a.reps)
+        res["long_fwd"] = timed(lambda: ops.gram_long_fwd(X, X, ih, order), a.reps)
+        res["long2_y_is_x_fwd"] = timed(lambda: ops.gram_long_fwd_bwd2(X, X, ih, order, y_is_x=True, want_gradX=False,
+                                                                       want_gradY=False), a.reps)
+        res["long_two_ordered"] = timed(lambda: (ops.gram_long_fwd_bwd(X, Y, ih, order, grad_out=W),
+                                                 ops.gram_long_fwd_bwd(Y, X, ih, order, grad_out=Wt)), a.reps)
+        res["long2_two_slot"] = timed(lambda: ops.gram_long_fwd_bwd2(X, Y, ih, order, grad_out=W), a.reps)
+        if user:  # (the third shape's grid and its autograd copies are several GB)
+            k = sk.SigKernel(_GramOnlyRBF(a.h), order)
+            res["user_gram_and_grad"] = timed(lambda: k.gram_and_grad(X, X), a.reps)
+        print(json.dumps(res), flush=True)
 
 
 if __name__ == "__main__":

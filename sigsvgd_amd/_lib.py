@@ -56,6 +56,8 @@ EXPORTS = [
     "sigsvgd_pair_workspace_bytes",
     "sigsvgd_pair_fwd",
     "sigsvgd_pair_fwd_bwd",
+    "sigsvgd_gram_long2_workspace_bytes",
+    "sigsvgd_gram_long_fwd_bwd2",
 ]
 
 _lib = None
@@ -207,6 +209,11 @@ def load():
     L.sigsvgd_pair_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
     L.sigsvgd_pair_fwd_bwd.restype = ci
     L.sigsvgd_pair_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_gram_long2_workspace_bytes.restype = ci
+    L.sigsvgd_gram_long2_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_gram_long_fwd_bwd2.restype = ci
+    L.sigsvgd_gram_long_fwd_bwd2.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                             vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

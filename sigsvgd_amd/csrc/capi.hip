@@ -52,6 +52,10 @@ int long_workspace(int A, int B, int M, int N, int d, int n, int want_grad, size
 int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
                 bool naive, bool sym, const void *grad_out, void *K_out, void *gradX_out, void *ws, size_t ws_bytes,
                 hipStream_t stream);
+int long2_workspace(int A, int B, int M, int N, int d, int n, int want_gradX, int want_gradY, bool yx, size_t *bytes);
+int long2_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
+                 bool naive, bool sym, bool yx, const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws,
+                 size_t ws_bytes, hipStream_t stream);
 int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes);
 int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
                 const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
@@ -156,6 +160,23 @@ static int check_long_launch(const void *X, const void *Y, int A, int B, int TX,
     }
     if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) {
         set_error("gram_long: RBF static kernel needs inv_h > 0 (got %g)", inv_h);
+        return SIGSVGD_E_BADARG;
+    }
+    return SIGSVGD_OK;
+}
+
+// the two-sided entry points (gram_long.hip's two-sided mode): check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says:
+// one batch in both slots (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
+static int check_long2(int A, int B, int TX, int TY, int d, int n, int kind, unsigned flags, bool want_gradY)
+{
+    const int rc = check_long(A, B, TX, TY, d, n, kind, flags);
+    if (rc) return rc;
+    if ((flags & SIGSVGD_FLAG_Y_IS_X) && (A != B || TX != TY)) {
+        set_error("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
+        return SIGSVGD_E_BADARG;
+    }
+    if ((flags & (SIGSVGD_FLAG_Y_IS_X | SIGSVGD_FLAG_SYM)) && want_gradY) {
+        set_error("gram_long2: Y_IS_X and SYM give the first-slot gradient only (gradY_out must be NULL)");
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
@@ -703,6 +724,33 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
     Range range("sigsvgd_pair_fwd_bwd");
     return pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
                        grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
+                                       int want_gradX, int want_gradY, unsigned flags, size_t *bytes)
+{
+    if (!bytes) {
+        set_error("bytes == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_long2(A, B, TX, TY, d, dyadic_order, static_kind, flags, want_gradY != 0);
+    if (rc) return rc;
+    return long2_workspace(A, B, TX, TY, d, dyadic_order, want_gradX ? 1 : 0, want_gradY ? 1 : 0,
+                           (flags & SIGSVGD_FLAG_Y_IS_X) != 0, bytes);
+}
+
+int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                               int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                               void *gradX_out, void *gradY_out, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    if (!rc) rc = check_long2(A, B, TX, TY, d, dyadic_order, static_kind, flags, gradY_out != nullptr);
+    if (rc) return rc;
+    Range range("sigsvgd_gram_long_fwd_bwd2");
+    return long2_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind,
+                        (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, (flags & SIGSVGD_FLAG_SYM) != 0,
+                        (flags & SIGSVGD_FLAG_Y_IS_X) != 0, grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes,
+                        static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

@@ -234,7 +234,9 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
                       grad_out: Optional[torch.Tensor] = None, naive: bool = False,
                       sym: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(K[A,B], gradX[A,TX,d]) with gradX = d sum(grad_out*K)/dX (first slot; grad_out None = ones; sym: grad_out +
-    grad_out^T) on the long route (`sigsvgd_gram_long_fwd_bwd`).  Bit-reproducible."""
+    grad_out^T) on the long route (`sigsvgd_gram_long_fwd_bwd`).  Bit-reproducible.  Every ordered pair is solved, also
+    when Y holds X's values, and Y gets no gradient: `gram_long_fwd_bwd2` solves Y = X once per unordered pair and returns
+    the gradients of both slots."""
     L = _lib.load()
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
@@ -260,6 +262,62 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
                                          ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
     _lib.check(rc, "gram_long_fwd_bwd")
     return K, gX
+
+
+def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                     want_gradX: bool = True, want_gradY: bool = True, y_is_x: bool = False) -> bool:
+    """Whether `gram_long_fwd_bwd2` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
+    query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
+    state beyond the LDS); any other error raises."""
+    L = _lib.load()
+    nbytes = ctypes.c_size_t(0)
+    rc = L.sigsvgd_gram_long2_workspace_bytes(int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                              1 if want_gradX else 0, 1 if want_gradY else 0,
+                                              _lib.FLAG_Y_IS_X if y_is_x else 0, ctypes.byref(nbytes))
+    if rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, "gram_long2_workspace_bytes")
+    return True
+
+
+def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                       grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
+                       y_is_x: bool = False, want_gradX: bool = True,
+                       want_gradY: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+    """(K[A,B], gX[A,TX,d] or None, gY[B,TY,d] or None) on the long route from one solve per pair
+    (`sigsvgd_gram_long_fwd_bwd2`): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each its own slot (grad_out
+    None = ones), K bit-identical to `gram_long_fwd`.  y_is_x (Y holds X's values; A == B, TX == TY): each unordered pair is
+    solved once, K's lower triangle mirrors the upper one, and gX is the first-slot gradient `gram_long_fwd_bwd` returns;
+    sym: weights grad_out + grad_out^T.  Both give no gY (it is returned as None).  Neither gradient wanted: forward only.
+    Computed and returned in X's dtype; bit-reproducible."""
+    L = _lib.load()
+    dev = _require_gpu(X, Y, grad_out)
+    Xc, Yc = _prep_long(X, Y)
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    if (sym or y_is_x) and (A != B or TX != TY):
+        raise ValueError("sym and y_is_x need X and Y of one shape")
+    want_gradY = bool(want_gradY) and not (sym or y_is_x)
+    go = None
+    if grad_out is not None:
+        if tuple(grad_out.shape) != (A, B):
+            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
+        go = grad_out.detach().to(Xc.dtype).contiguous()
+    flags = _flags(naive, sym, y_is_x, False)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_gram_long2_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind),
+                                                    1 if want_gradX else 0, 1 if want_gradY else 0, flags,
+                                                    ctypes.byref(nbytes)), "gram_long2_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
+    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
+    gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_gram_long_fwd_bwd2(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                          int(dyadic_order), int(static_kind), flags, p(go), K.data_ptr(), p(gX), p(gY),
+                                          p(ws), wsn, _stream_ptr(dev))
+    _lib.check(rc, "gram_long_fwd_bwd2")
+    return K, gX, gY
 
 
 def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,

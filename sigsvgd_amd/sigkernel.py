@@ -12,7 +12,7 @@ The reference delegates the Goursat-PDE arithmetic to the third-party package `s
 This module provides those names on top of libsigsvgd_hip.so, so `sys.modules["sigkernel"] =
 sigsvgd_amd.sigkernel` makes the reference's own code run on the MI355X path.
 `compute_Gram` is an autograd node: backward receives grad_output [A,B] and returns the gradient
-for X only (None for everything else), like upstream.  `compute_kernel` (and `compute_distance` on it) solves each pair
+for X only (None for everything else), like upstream; `grad_Y=True` adds the second-slot gradient for Y.  `compute_kernel` (and `compute_distance` on it) solves each pair
 (X_i, Y_i) once and differentiates both paths, each in its own slot.
 
 Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
@@ -157,6 +157,22 @@ def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x) 
     return not ops.gram_takes(X.shape[0], Y.shape[0], T, X.shape[2], dyadic_order, static_kind, want_grad, naive, sym, y_is_x)
 
 
+def _long_yx_route(y_is_x: bool, A: int, want_grad: bool, cus: int) -> bool:
+    """True where a long-route launch with Y = X solves each unordered pair once (`ops.gram_long_fwd_bwd2`, y_is_x) instead
+    of every ordered pair (`ops.gram_long_fwd*`).  Measured on the MI355X: the gradient launch wins
+    where its work items are single pairs (A = 16, 32, 33: 1.36 to 1.51 times faster) and loses to the ordered launch where
+    they are tiles whose count just passes the resident waves (A = 64, T = 300: 528 tiles of 2 x 2 for 512 waves, 0.91);
+    the forward-only launch ties while a wave has one pair either way (A = 16, 32) and wins from A = 64 on.  So: gradient
+    launches where the tiles of 2 x 2 would not give every compute unit one (single pairs then, whatever the LDS lets a
+    unit hold: A <= 44 at 256 units); forward-only launches where the unordered pairs alone fill 8 waves per unit."""
+    if not y_is_x:
+        return False
+    if want_grad:
+        half = (A + 1) // 2
+        return half * (half + 1) // 2 < cus
+    return A * (A + 1) // 2 >= 8 * cus
+
+
 def _device_cus(X) -> int:
     return torch.cuda.get_device_properties(X.device).multi_processor_count if X.is_cuda else 256
 
@@ -177,27 +193,54 @@ def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus) 
 # autograd node
 # ------------------------------------------------------------------------------------------------
 class _SigKernelGram(torch.autograd.Function):
-    """forward: K = Gram(X, Y).  backward: d sum(grad_output*K)/dX, nothing for Y.
+    """forward: K = Gram(X, Y).  backward: d sum(grad_output*K)/dX, and with grad_Y d sum(grad_output*K)/dY (the second
+    slot), else nothing for Y.
 
-    When X needs a gradient the forward already runs the fused forward+backward kernel for
+    When X (or, with grad_Y, Y) needs a gradient the forward already runs the forward+backward kernel for
     grad_output = 1 (the only grad_output the reference ever produces: callers differentiate
     K.sum(), score.py:69 / trajectory_svgd.py:65), so the usual backward is a scale by a scalar.
-    Any other grad_output triggers one more fused launch with the real weights."""
+    Any other grad_output triggers one more launch with the real weights.
+
+    The long route gets K and both gradients from one `ops.gram_long_fwd_bwd2` launch (one solve per pair), and with
+    y_is_x solves each unordered pair once.  The fused route has no second-slot kernel: gY is the first slot of the swapped
+    launch `ops.gram_fwd_bwd(Y, X, grad_output^T)`, a second launch."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate):
+    def _launch(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
+        """-> (K, gX or None, gY or None) for the outputs wanted (at least one); fused_yx: whether a launch of the fused
+        kernels with Y = X is told so (the speculated launch is, a launch with real weights never was)"""
+        static_kind, inv_h, dyadic_order, naive, sym, y_is_x = cfg
+        yx = y_is_x and not want_y  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
+        if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx):
+            if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
+                return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x,
+                                              want_y)
+            return (*ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym), None)
+        K = gX = gY = None
+        if want_x:
+            K, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx and fused_yx)
+        if want_y:  # the second slot is the first slot of the swapped launch
+            Kt, gY = ops.gram_fwd_bwd(Y, X, inv_h, dyadic_order, static_kind, None if grad_out is None else grad_out.T,
+                                      naive, False, False)
+            K = Kt.T.contiguous() if K is None else K
+        return K, gX, gY
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y):
         ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x)
-        ctx.g_ones = None
+        ctx.g_ones = ctx.gy_ones = None
+        ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
+        ctx.y_dtype = Y.dtype
         Xd = X.detach()
         Yd = Y.detach()
-        if ctx.needs_input_grad[0] and speculate:
-            if _long_route(Xd, Yd, static_kind, dyadic_order, True, naive, sym, y_is_x):
-                K, g1 = ops.gram_long_fwd_bwd(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym)
-            else:
-                K, g1 = ops.gram_fwd_bwd(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym, y_is_x)
-            ctx.g_ones = g1
+        if any(ctx.want) and speculate:
+            K, ctx.g_ones, ctx.gy_ones = _SigKernelGram._launch(Xd, Yd, ctx.cfg, None, *ctx.want, True)
         elif _long_route(Xd, Yd, static_kind, dyadic_order, False, naive, False, y_is_x):
-            K = ops.gram_long_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive)
+            if _long_yx_route(y_is_x, Xd.shape[0], False, _device_cus(Xd)):
+                K = ops.gram_long_fwd_bwd2(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, y_is_x=True,
+                                           want_gradX=False, want_gradY=False)[0]
+            else:
+                K = ops.gram_long_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive)
         else:
             K = ops.gram_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x)
         ctx.save_for_backward(Xd, Yd)
@@ -206,9 +249,9 @@ class _SigKernelGram(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         X, Y = ctx.saved_tensors
-        static_kind, inv_h, dyadic_order, naive, sym, y_is_x = ctx.cfg
-        gX = None
-        if ctx.g_ones is not None:
+        want_x, want_y = ctx.want
+        gX = gY = None
+        if ctx.g_ones is not None or ctx.gy_ones is not None:
             scalar = None
             if grad_output.stride() == (0, 0):  # expanded scalar, e.g. from K.sum().backward()
                 scalar = grad_output.reshape(-1)[:1]
@@ -217,12 +260,13 @@ class _SigKernelGram(torch.autograd.Function):
                 if bool((grad_output == first).all()):  # one host sync; uniform weights => scale
                     scalar = first
             if scalar is not None:
-                gX = ctx.g_ones * scalar.to(ctx.g_ones.dtype)
-        if gX is None and _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, False):
-            _, gX = ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym)
-        elif gX is None:
-            _, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym, False)
-        return gX, None, None, None, None, None, None, None, None
+                gX = None if ctx.g_ones is None else ctx.g_ones * scalar.to(ctx.g_ones.dtype)
+                gY = None if ctx.gy_ones is None else ctx.gy_ones * scalar.to(ctx.gy_ones.dtype)
+        if gX is None and gY is None and (want_x or want_y):
+            _, gX, gY = _SigKernelGram._launch(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
+        if gY is not None:
+            gY = gY.to(ctx.y_dtype)
+        return gX, gY, None, None, None, None, None, None, None, None
 
 
 class _SigKernelPair(torch.autograd.Function):
@@ -266,12 +310,18 @@ class SigKernel:
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
-    def compute_Gram(self, X: torch.Tensor, Y: torch.Tensor, sym: bool = False) -> torch.Tensor:
+    def compute_Gram(self, X: torch.Tensor, Y: torch.Tensor, sym: bool = False, grad_Y: bool = False) -> torch.Tensor:
         """K[i,j] = k_sig(X_i, Y_j), X [A,Tx,d], Y [B,Ty,d] on a HIP device; same dtype/device as X.  Paths of different
-        lengths (upstream sigkernel takes them) are padded with their last point, which is exact (ops.pad_to_length)."""
+        lengths (upstream sigkernel takes them) are padded with their last point, which is exact (ops.pad_to_length).
+        Gradients flow to X (the first slot).  grad_Y=True: a Y that requires grad receives its second-slot gradient too (one
+        tensor in both slots then gets the sum of both, which is what sym=True gives; the two together raise ValueError).
+        The default leaves Y without a gradient, as callers that pass one leaf tensor in both slots rely on."""
+        if grad_Y and sym:
+            raise ValueError("compute_Gram: grad_Y=True differentiates the second slot itself; sym=True folds it into the "
+                             "first.  Use one of them")
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
         if static_kind is None:  # user static kernel: its grid, the PDE on the device, autograd through both
-            G = self.static_kernel.Gram_matrix(X, Y if sym else Y.detach())
+            G = self.static_kernel.Gram_matrix(X, Y if sym or grad_Y else Y.detach())
             return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
         y_is_x = (
             Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype
@@ -284,12 +334,12 @@ class SigKernel:
             # unordered pair once instead of every ordered pair, i.e. half the launch at these batch sizes.
             y_is_x = True
         return _SigKernelGram.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver, bool(sym),
-                                    y_is_x, self.speculate_ones)
+                                    y_is_x, self.speculate_ones, bool(grad_Y))
 
     # -- the rest of the upstream `sigkernel.SigKernel` surface [RECALLED from the public package; the
     #    reference tree never calls these].  compute_kernel / compute_distance differentiate both arguments (each its
-    #    own slot); compute_mmd goes through compute_Gram, so its gradients flow to the FIRST argument only, with
-    #    `sym=True` giving the symmetrised weighting for Gram(X, X).
+    #    own slot); compute_mmd goes through compute_Gram, so its cross term's gradient flows to the FIRST argument only
+    #    unless grad_Y=True, with `sym=True` giving the symmetrised weighting for Gram(X, X).
     def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
         """Paired kernel k_sig(X_i, Y_i) -> [batch], one solve per pair, differentiable in X and in Y (each its own slot:
         compute_kernel(X, X) differentiates to the sum of both).  Built-in static kernels run on the paired route
@@ -313,11 +363,12 @@ class SigKernel:
         return (self.compute_kernel(X, X).mean() + self.compute_kernel(Y, Y).mean()
                 - 2.0 * self.compute_kernel(X, Y).mean())
 
-    def compute_mmd(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
-        """Biased squared MMD: mean K_XX + mean K_YY - 2 mean K_XY."""
+    def compute_mmd(self, X: torch.Tensor, Y: torch.Tensor, grad_Y: bool = False) -> torch.Tensor:
+        """Biased squared MMD: mean K_XX + mean K_YY - 2 mean K_XY.  grad_Y=True differentiates Y through the cross term
+        too (`compute_Gram(X, Y, grad_Y=True)`); the default gives Y the gradient of mean K_YY alone."""
         K_XX = self.compute_Gram(X, X, sym=True)
         K_YY = self.compute_Gram(Y, Y, sym=True)
-        K_XY = self.compute_Gram(X, Y, sym=False)
+        K_XY = self.compute_Gram(X, Y, sym=False, grad_Y=grad_Y)
         return K_XX.mean() + K_YY.mean() - 2.0 * K_XY.mean()
 
     def gram_and_grad(self, X: torch.Tensor, Y: Optional[torch.Tensor] = None, grad_out=None, sym: bool = False):
@@ -328,6 +379,9 @@ class SigKernel:
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
         if _long_route(X, Yv, static_kind, self.dyadic_order, True, self._naive_solver, sym, Y is None):
+            if _long_yx_route(Y is None, X.shape[0], True, _device_cus(X)):  # each unordered pair once
+                return ops.gram_long_fwd_bwd2(X, X, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
+                                              y_is_x=True, want_gradY=False)[:2]
             return ops.gram_long_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym)
         return ops.gram_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
                                 y_is_x=Y is None)
