@@ -352,6 +352,37 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
                                void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---- long-path Gram, one rank's share of the Y = X solve (ABI 10, additive) -----------------------
+ * The partial mode of the two-sided Y-is-X launch, for the sharded SVGD step: the launch of rank tile_offset of tile_stride
+ * owns the row tiles tile_offset + k tile_stride of tile_rows rows each -- with SIGSVGD_FLAG_FOLD_TILES also their mirror
+ * images ntile - 1 - t (the ownership of sigsvgd_gram_sym_partial) -- and a row tile owns the pairs (i, j), i in the tile,
+ * j >= i.  For the owned pairs K_partial[i][j] = K_partial[j][i] = the K of sigsvgd_gram_long_fwd, bit for bit (I/O dtype;
+ * entries of other pairs are not touched: the caller zeroes the buffer), and grad_partial [N, T, d], always fp64 and fully
+ * overwritten (zero in rows that received nothing), holds the owned pairs' contributions to the first-slot gradient of
+ * sigsvgd_gram_long_fwd_bwd2 with Y_IS_X: w_ij d1 k(X_i, X_j) to row i and w_ji d1 k(X_j, X_i) to row j, w = grad_out (NULL =
+ * ones), SIGSVGD_FLAG_SYM: w_ij + w_ji.  Summed over tile_offset = 0 .. tile_stride - 1 they give that launch's K and
+ * gradient.  SIGSVGD_FLAG_NAIVE_SOLVER as elsewhere; SIGSVGD_FLAG_Y_IS_X is implied; any other bit, tile_stride < 1 or
+ * tile_offset outside [0, tile_stride) is SIGSVGD_E_BADARG.  Limits and refusals are sigsvgd_gram_long_fwd's.  A rank that
+ * owns no tile (more ranks than tiles) is a valid launch: grad_partial is zeroed, K_partial not touched.
+ * Work items are rectangles of tile_rows x tile_cols pairs of an owned row tile, from the tile's first row on;
+ * sigsvgd_gram_long_partial_plan reports the two, which depend on (N, T, d, dyadic_order, tile_stride) and the device only,
+ * never on tile_offset or the fold flag: every rank of a step has the same tiles.  An item adds its pairs into one fp64 slab
+ * per row and one per column in a fixed order, and a row's slabs are summed in a fixed order: bit-reproducible, no
+ * floating-point atomics.  Workspace (sigsvgd_gram_long_partial_workspace_bytes, per rank): the per-wave scratch of
+ * sigsvgd_gram_long_fwd_bwd plus the slabs of the owned tiles only; 0 bytes for a rank without tiles.  The query is exact
+ * per rank.  The tile is chosen for the folded ownership on the device's resident wavefronts: there a share's slabs are at
+ * most N N / 4 x T d doubles where it holds more than 16 pairs per resident wavefront and (2 pairs + N) x T d doubles below,
+ * and its schedule keeps at least 0.9 of the resident waves busy.  Cyclic ownership (its first rank owns more) and launches
+ * whose grid the 1 GiB scratch cap lowers run on the same tile without those two guarantees. */
+int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags, int tile_stride,
+                                   int *tile_rows, int *tile_cols);
+int sigsvgd_gram_long_partial_workspace_bytes(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags,
+                                              int tile_offset, int tile_stride, size_t *bytes);
+int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h, int dyadic_order,
+                                  int static_kind, unsigned flags, int tile_offset, int tile_stride,
+                                  const void *grad_out /* [N,N] or NULL = ones */, void *K_partial, double *grad_partial,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

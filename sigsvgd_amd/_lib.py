@@ -58,6 +58,9 @@ EXPORTS = [
     "sigsvgd_pair_fwd_bwd",
     "sigsvgd_gram_long2_workspace_bytes",
     "sigsvgd_gram_long_fwd_bwd2",
+    "sigsvgd_gram_long_partial_plan",
+    "sigsvgd_gram_long_partial_workspace_bytes",
+    "sigsvgd_gram_long_sym_partial",
 ]
 
 _lib = None
@@ -214,6 +217,12 @@ def load():
     L.sigsvgd_gram_long_fwd_bwd2.restype = ci
     L.sigsvgd_gram_long_fwd_bwd2.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t,
                                              vp]
+    L.sigsvgd_gram_long_partial_plan.restype = ci
+    L.sigsvgd_gram_long_partial_plan.argtypes = [ci, ci, ci, ci, ci, cu, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.sigsvgd_gram_long_partial_workspace_bytes.restype = ci
+    L.sigsvgd_gram_long_partial_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_gram_long_sym_partial.restype = ci
+    L.sigsvgd_gram_long_sym_partial.argtypes = [vp, ci, ci, ci, ci, cd, ci, ci, cu, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

@@ -56,6 +56,11 @@ int long2_workspace(int A, int B, int M, int N, int d, int n, int want_gradX, in
 int long2_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
                  bool naive, bool sym, bool yx, const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws,
                  size_t ws_bytes, hipStream_t stream);
+int long_part_tiles(int A, int T, int d, int n, int stride, int *R, int *JC);
+int long_part_workspace(int A, int T, int d, int n, int off, int stride, bool fold, size_t *bytes);
+int long_part_launch(const void *X, int A, int T, int d, int dtype, double inv_h, int n, int kind, bool naive, bool sym,
+                     int off, int stride, bool fold, const void *grad_out, void *K_partial, double *grad_partial, void *ws,
+                     size_t ws_bytes, hipStream_t stream);
 int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes);
 int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
                 const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
@@ -177,6 +182,19 @@ static int check_long2(int A, int B, int TX, int TY, int d, int n, int kind, uns
     }
     if ((flags & (SIGSVGD_FLAG_Y_IS_X | SIGSVGD_FLAG_SYM)) && want_gradY) {
         set_error("gram_long2: Y_IS_X and SYM give the first-slot gradient only (gradY_out must be NULL)");
+        return SIGSVGD_E_BADARG;
+    }
+    return SIGSVGD_OK;
+}
+
+// the partial entry points (gram_long.hip's partial mode): check_long's for one batch in both slots, SIGSVGD_FLAG_FOLD_TILES
+// taken too, and the rank's tiles: tile_offset in [0, tile_stride)
+static int check_long_partial(int N, int T, int d, int n, int kind, unsigned flags, int tile_offset, int tile_stride)
+{
+    const int rc = check_long(N, N, T, T, d, n, kind, flags & ~(unsigned)SIGSVGD_FLAG_FOLD_TILES);
+    if (rc) return rc;
+    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
+        set_error("gram_long_sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
         return SIGSVGD_E_BADARG;
     }
     return SIGSVGD_OK;
@@ -751,6 +769,48 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
                         (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, (flags & SIGSVGD_FLAG_SYM) != 0,
                         (flags & SIGSVGD_FLAG_Y_IS_X) != 0, grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes,
                         static_cast<hipStream_t>(stream));
+}
+
+int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags, int tile_stride,
+                                   int *tile_rows, int *tile_cols)
+{
+    if (!tile_rows || !tile_cols) {
+        set_error("gram_long_partial_plan: tile_rows / tile_cols == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, 0, tile_stride);
+    if (rc) return rc;
+    return long_part_tiles(N, T, d, dyadic_order, tile_stride, tile_rows, tile_cols);
+}
+
+int sigsvgd_gram_long_partial_workspace_bytes(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags,
+                                              int tile_offset, int tile_stride, size_t *bytes)
+{
+    if (!bytes) {
+        set_error("bytes == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    const int rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, tile_offset, tile_stride);
+    if (rc) return rc;
+    return long_part_workspace(N, T, d, dyadic_order, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0, bytes);
+}
+
+int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h, int dyadic_order,
+                                  int static_kind, unsigned flags, int tile_offset, int tile_stride, const void *grad_out,
+                                  void *K_partial, double *grad_partial, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_long_launch(X, X, N, N, T, T, d, dtype, inv_h, dyadic_order, static_kind,
+                               flags & ~(unsigned)SIGSVGD_FLAG_FOLD_TILES, K_partial);
+    if (!rc) rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, tile_offset, tile_stride);
+    if (rc) return rc;
+    if (!grad_partial) {
+        set_error("gram_long_sym_partial: grad_partial == NULL");
+        return SIGSVGD_E_BADARG;
+    }
+    Range range("sigsvgd_gram_long_sym_partial");
+    return long_part_launch(X, N, T, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                            (flags & SIGSVGD_FLAG_SYM) != 0, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0,
+                            grad_out, K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

@@ -27,7 +27,17 @@
 // row i and the column-side pass adds w_col dk/dy into its slab of column j; long2_reduce_kernel adds a row's (a column's)
 // slabs in tile order.  With Y = X (yx) the items are the tiles of the upper triangle, only pairs i <= j are solved, K is
 // mirrored, and the column side of pair (i, j) is row j's first-slot gradient of the pair (j, i): both sides meet in gX.
+//
+// Partial mode (gram_long_part_kernel): one rank's share of the Y-is-X launch for the sharded SVGD
+// step.  The launch owns row tiles (TileMap, folded or cyclic), an item is a rectangle of R rows x JC columns of an owned
+// tile from its first row on, the slabs cover the owned tiles only, and long_part_reduce_kernel writes the fp64 partial
+// gradient of every row (zero where nothing arrived).  The host picks (R, JC) by search (part_pick).
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <type_traits>
+#include <vector>
 
 #include "ring_sweep.h"
 
@@ -54,6 +64,15 @@ struct PairArgs : LongArgs {
 struct Long2Args : LongArgs {
     double *colpart; // [B][nti][TY * d] (NULL with yx, or when gradY is not wanted)
     int IC, nti, yx, want_row, want_col;
+};
+// the partial mode's arguments: LongArgs (A = B paths of M = N points; JC: the columns of an item;
+// partials: the row-side slabs, one [TX * d] per (row of an owned tile, column chunk), owned tiles in the order of `tm`) and
+// the column-side slabs, one per (owned tile, row j from the tile's first row on): TileMap::start gives a tile's first.
+struct PartArgs : LongArgs {
+    double *colpart;
+    TileMap tm;      // the row tiles this launch owns, R rows each
+    int R;
+    long long nfull; // items of the first pass (the chunks strictly between a tile's first and last)
 };
 
 namespace {
@@ -342,6 +361,166 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(Long2Args a)
     }
 }
 
+// ---- partial mode: this launch's share of the Y-is-X solve --------------------------------------
+// Row tile t (R rows) owns the pairs (i, j), i in the tile, j >= i; the launch owns the tiles of `tm`.  An item is (owned
+// tile kq, chunk c): the tile's rows x the columns i0 + c JC .. i0 + (c + 1) JC - 1 (i0 the tile's first row; the first chunk
+// is ragged by the diagonal, the last by the matrix edge).  Items are taken in three passes -- the chunks strictly between a
+// tile's first and last (whole rectangles when JC >= R), then every tile's first chunk, then the last chunks -- so the grid's
+// last, partly filled round gets the small items.  The helpers below are the host plan's too.
+__host__ __device__ inline int part_rows(const TileMap &tm, int kq, int A, int R)
+{
+    const int i0 = tm.tile_of(kq) * R;
+    return (A < i0 + R ? A : i0 + R) - i0;
+}
+__host__ __device__ inline int part_chunks(const TileMap &tm, int kq, int A, int R, int JC)
+{
+    return (A - tm.tile_of(kq) * R + JC - 1) / JC;
+}
+// item -> (kq, c)
+__host__ __device__ inline void part_decode(const TileMap &tm, long long item, long long nfull, int A, int R, int JC, int &kq,
+                                            int &c)
+{
+    kq = 0;
+    if (item < nfull) {
+        for (;; ++kq) {
+            const int n = part_chunks(tm, kq, A, R, JC) - 2;
+            if (n > 0) {
+                if (item < n) break;
+                item -= n;
+            }
+        }
+        c = 1 + (int)item;
+    } else if ((item -= nfull) < tm.owned) {
+        kq = (int)item;
+        c = 0;
+    } else {
+        item -= tm.owned;
+        for (;; ++kq)
+            if (part_chunks(tm, kq, A, R, JC) >= 2 && item-- == 0) break;
+        c = part_chunks(tm, kq, A, R, JC) - 1;
+    }
+}
+// row-side slabs of the owned tiles before kq
+__host__ __device__ inline long long part_row_base(const TileMap &tm, int kq, int A, int R, int JC)
+{
+    long long s = 0;
+    for (int q = 0; q < kq; ++q) s += (long long)part_rows(tm, q, A, R) * part_chunks(tm, q, A, R, JC);
+    return s;
+}
+
+// A kernel of its own, as the two-sided mode is: gram_long_kernel's and gram_long2_kernel's instantiations keep their code.
+// Per pair the staging, fill, sweeps and gradient passes are gram_long2_kernel's with Y = X (K has the same bits).
+template <typename IO, bool NAIVE, int KIND>
+__global__ __launch_bounds__(64) void gram_long_part_kernel(PartArgs a)
+{
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    const int lane = threadIdx.x;
+    const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d, TD = a.M * a.d;
+    const RingWave rw = ring_wave<true>(a, smem_raw);
+    double *ring = rw.ring;
+    double *xs = rw.dump + kWave; // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
+    const IO *GO = static_cast<const IO *>(a.grad_out);
+
+    for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
+        int kq, c;
+        part_decode(a.tm, item, a.nfull, a.A, a.R, a.JC, kq, c);
+        const int nck = part_chunks(a.tm, kq, a.A, a.R, a.JC);
+        const int i0 = a.tm.tile_of(kq) * a.R, i1 = min(a.A, i0 + a.R), j0 = i0 + c * a.JC, j1 = min(a.A, j0 + a.JC);
+        double *rowslabs = a.partials + (size_t)part_row_base(a.tm, kq, a.A, a.R, a.JC) * TD; // [rows][nck][TD]
+        double *colslabs = a.colpart + (size_t)a.tm.start(kq, a.A, a.R, 1) * TD;              // [j - i0][TD]
+
+        for (int i = i0; i < i1; ++i) {
+            const IO *xi = static_cast<const IO *>(a.X) + (size_t)i * M * d;
+            const int jfirst = max(j0, i); // the pairs i <= j only
+
+            for (int j = jfirst; j < j1; ++j) {
+                const IO *yj = static_cast<const IO *>(a.X) + (size_t)j * N * d;
+                // staging and fill: gram_long_kernel's, statement for statement (K must have its bits)
+                auto stage_x = [&](int a0) {
+                    for (int e = lane; e < (nrow + 1) * d; e += kWave) {
+                        const int k = e / d;
+                        xs[e] = (double)xi[(size_t)min(a0 + k, M - 1) * d + (e - k * d)];
+                    }
+                };
+                auto fill = [&](int a0, int b_lo, int b_hi) {
+                    __syncthreads(); // (the sweep's reads of the slots this overwrites are done; xs is staged)
+                    for (int b0 = b_lo; b0 <= b_hi; b0 += kWave - 1) {
+                        const int b = b0 + lane;
+                        const bool ok = lane < kWave - 1 && b <= b_hi;
+                        const IO *yb = yj + (size_t)min(b, N - 1) * d;
+                        double yv[16];
+#pragma unroll
+                        for (int cc = 0; cc < 16; ++cc) yv[cc] = (double)yb[min(cc, d - 1)];
+                        double rd_prev = 0.0;
+                        for (int k = 0; k <= nrow; ++k) {
+                            const double g = d <= 16 ? static_k16<KIND>(xs + k * d, yv, d, a.inv_h)
+                                                     : static_k<KIND>(xs + k * d, yb, d, a.inv_h);
+                            const double rd = shfl_down_f64(g) - g; // k(x_{a0+k}, y_{b+1}) - k(x_{a0+k}, y_b)
+                            if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < M) ? rd - rd_prev : 0.0;
+                            rd_prev = rd;
+                        }
+                    }
+                    __syncthreads();
+                };
+
+                const double Kval = ring_forward<NAIVE, true>(rw, fill, stage_x);
+                if (((rw.P - 1) & (kWave - 1)) == lane) {
+                    static_cast<IO *>(a.K_out)[(size_t)i * a.A + j] = (IO)Kval;
+                    static_cast<IO *>(a.K_out)[(size_t)j * a.A + i] = (IO)Kval; // the mirror: same bits
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
+                __syncthreads();
+                ring_reverse<NAIVE>(rw, fill, stage_x);
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
+                __syncthreads();
+
+                // ---- gradient: both sides from the pair's one S, each into its slab in the item's pair order ----------------
+                double w = GO ? (double)GO[(size_t)i * a.A + j] : 1.0; // the row side's weight
+                double wc = GO ? (double)GO[(size_t)j * a.A + i] : 1.0; // the column side is d k(X_j, X_i) / d X_j
+                if (a.sym) w = wc = w + wc;
+                double *rs = rowslabs + ((size_t)(i - i0) * nck + c) * TD, *cs = colslabs + (size_t)(j - i0) * TD;
+                static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int cc, double g) {
+                    double *o = rs + (size_t)m * d + cc;
+                    *o = j == jfirst ? w * g : __builtin_fma(w, g, *o);
+                });
+                if (i != j) // (a diagonal pair has one slot: the row side took it)
+                    static_grad_pass<KIND, false>(rw, yj, N, xi, M, d, a.inv_h, [&](int nn, int cc, double g) {
+                        double *o = cs + (size_t)nn * d + cc;
+                        *o = i == i0 ? wc * g : __builtin_fma(wc, g, *o);
+                    });
+                __syncthreads(); // (the next pair's forward sweep overwrites the scratch and the ring)
+            }
+        }
+    }
+}
+
+// grad_partial[k][e] (fp64, whatever the I/O dtype) = row k's column-side slabs in the order of the owned tiles, then, where
+// the launch owns k's tile, its row-side slabs in chunk order; slabs no pair wrote are skipped (the column side of a tile's
+// first row; chunks that end at or before the diagonal), and a row that received nothing gets zero.  One block per row.
+__global__ void long_part_reduce_kernel(const double *rowpart, const double *colpart, double *out, int A, int TD, int R, int JC,
+                                        TileMap tm)
+{
+    const int k = blockIdx.x;
+    const int own = tm.kq_of_tile(k / R);
+    int oi0 = 0, onc = 0;
+    const double *rows = nullptr;
+    if (own >= 0) {
+        oi0 = tm.tile_of(own) * R;
+        onc = part_chunks(tm, own, A, R, JC);
+        rows = rowpart + ((size_t)part_row_base(tm, own, A, R, JC) + (size_t)(k - oi0) * onc) * TD;
+    }
+    for (int e = threadIdx.x; e < TD; e += blockDim.x) {
+        double s = 0.0;
+        for (int kq = 0; kq < tm.owned; ++kq) {
+            const int i0 = tm.tile_of(kq) * R;
+            if (i0 < k) s += colpart[(size_t)(tm.start(kq, A, R, 1) + (k - i0)) * TD + e];
+        }
+        for (int c = 0; c < onc; ++c)
+            if (oi0 + (c + 1) * JC > k) s += rows[(size_t)c * TD + e];
+        out[(size_t)k * TD + e] = s;
+    }
+}
+
 // gradX[i][e] = sum over the chunks of row i of partials[i][chunk][e], in chunk order (reproducible bits)
 template <typename IO>
 __global__ void long_reduce_kernel(const double *partials, IO *gradX, int A, int nchunks, int TD)
@@ -455,6 +634,139 @@ int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, boo
     const size_t rowslabs = yx ? (want_grad ? pl.nti + 1 : 0) : (want_row ? pl.nchunks : 0);
     pl.partial_bytes = (size_t)A * rowslabs * M * d * sizeof(double);
     pl.col_bytes = !yx && want_col ? (size_t)B * pl.nti * N * d * sizeof(double) : 0;
+    return SIGSVGD_OK;
+}
+
+// ---- the partial plan ------------------------------------------------------------------------------
+// One rank's share under a candidate (R, JC): its pairs, the most pairs one wavefront walks when item k goes to wave
+// k % grid (the kernel's persistent loop), its slabs (units of TX * d doubles) and its items.  The items are enumerated in
+// the order of part_decode.
+struct PartShare {
+    long long pairs = 0, makespan = 0, slabs = 0, items = 0, nfull = 0;
+    TileMap tm;
+};
+PartShare part_share(int A, int R, int JC, int off, int stride, bool fold, long long resident)
+{
+    PartShare sh;
+    sh.tm = make_tilemap((A + R - 1) / R, off, stride, fold);
+    const TileMap &tm = sh.tm;
+    for (int kq = 0; kq < tm.owned; ++kq) {
+        const int nc = part_chunks(tm, kq, A, R, JC);
+        sh.items += nc;
+        sh.nfull += nc > 2 ? nc - 2 : 0;
+        sh.slabs += (long long)part_rows(tm, kq, A, R) * nc + (A - tm.tile_of(kq) * R);
+    }
+    const long long grid = sh.items < resident ? (sh.items > 0 ? sh.items : 1) : resident;
+    std::vector<long long> load((size_t)grid, 0);
+    long long k = 0;
+    auto take = [&](int kq, int c) {
+        const int i0 = tm.tile_of(kq) * R, i1 = std::min(A, i0 + R), j0 = i0 + c * JC, j1 = std::min(A, j0 + JC);
+        long long p = 0;
+        for (int i = i0; i < i1; ++i) p += std::max(0, j1 - std::max(j0, i));
+        sh.pairs += p;
+        load[(size_t)(k++ % grid)] += p;
+    };
+    for (int kq = 0; kq < tm.owned; ++kq)
+        for (int c = 1; c < part_chunks(tm, kq, A, R, JC) - 1; ++c) take(kq, c);
+    for (int kq = 0; kq < tm.owned; ++kq) take(kq, 0);
+    for (int kq = 0; kq < tm.owned; ++kq)
+        if (part_chunks(tm, kq, A, R, JC) >= 2) take(kq, part_chunks(tm, kq, A, R, JC) - 1);
+    sh.makespan = *std::max_element(load.begin(), load.end());
+    return sh;
+}
+
+// The item rule: the largest R * JC (R a power of two <= 32 with at least two row tiles per rank, JC <= 64; ties: the larger
+// R) under which, for every rank of `stride` with folded ownership,
+//   schedule  ceil(pairs / resident) / makespan >= 0.9,
+//   memory    slabs <= A * A / 4 where the share holds more than 16 pairs per resident wave, else <= 2 pairs + A (what
+//             single-pair items cost),
+//   balance   the fullest rank's pairs <= 1.05 x the mean.
+// A share of no more pairs than resident waves gets single pairs by the schedule condition alone.  Where nothing meets all
+// three (few rows on many ranks), the memory condition holds and the best balance, then schedule, is taken.  It depends on
+// (A, stride, resident) only -- never on the rank -- and is searched once per such triple and process.
+void part_pick(int A, int stride, long long resident, int &R_out, int &JC_out)
+{
+    static std::mutex mu;
+    static std::map<std::tuple<int, int, long long>, std::pair<int, int>> cache;
+    const auto key = std::make_tuple(A, stride, resident);
+    std::lock_guard<std::mutex> lock(mu);
+    const auto hit = cache.find(key);
+    if (hit != cache.end()) {
+        R_out = hit->second.first;
+        JC_out = hit->second.second;
+        return;
+    }
+    std::vector<std::pair<int, int>> cands;
+    for (int R = 32; R >= 1; R >>= 1)
+        for (int JC = 64; JC >= 1; --JC) cands.emplace_back(R, JC);
+    std::stable_sort(cands.begin(), cands.end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) {
+        return x.first * x.second > y.first * y.second;
+    });
+    const long long total = (long long)A * (A + 1) / 2;
+    std::pair<int, int> best{1, 1};
+    bool have = false, best_bal = false;
+    double best_eff = -1.0;
+    for (const auto &cd : cands) {
+        const int R = cd.first, JC = cd.second;
+        if (R > 1 && (A + R - 1) / R < 2 * stride) continue;
+        bool mem_ok = true;
+        double eff = 1.0;
+        long long most = 0;
+        for (int off = 0; off < stride && mem_ok; ++off) {
+            const PartShare sh = part_share(A, R, JC, off, stride, true, resident);
+            const long long bound = sh.pairs > 16 * resident ? (long long)A * A / 4 : 2 * sh.pairs + A;
+            mem_ok = sh.slabs <= bound;
+            if (sh.pairs > 0) eff = std::min(eff, (double)((sh.pairs + resident - 1) / resident) / (double)sh.makespan);
+            most = std::max(most, sh.pairs);
+        }
+        if (!mem_ok) continue;
+        const bool bal = (double)most * stride <= 1.05 * (double)total;
+        if (eff >= 0.9 && bal) {
+            best = cd;
+            break;
+        }
+        if (!have || (bal && !best_bal) || (bal == best_bal && eff > best_eff)) {
+            have = true;
+            best = cd;
+            best_bal = bal;
+            best_eff = eff;
+        }
+    }
+    cache[key] = best;
+    R_out = best.first;
+    JC_out = best.second;
+}
+
+struct PartPlan : LongPlan {
+    int R;
+    TileMap tm;
+    long long nfull;
+    size_t col_bytes;
+    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes + col_bytes); }
+};
+
+// the plan of rank `off` of `stride`; off < 0: the tile size only (sigsvgd_gram_long_partial_plan)
+int part_make_plan(int A, int T, int d, int n, int off, int stride, bool fold, PartPlan &pl)
+{
+    const int rc = ring_make_plan(T, T, n, 1, d, "gram_long", pl);
+    if (rc) return rc;
+    part_pick(A, stride, pl.resident, pl.R, pl.JC);
+    if (off < 0) return SIGSVGD_OK;
+    const PartShare sh = part_share(A, pl.R, pl.JC, off, stride, fold, pl.resident);
+    pl.tm = sh.tm;
+    pl.items = sh.items;
+    pl.nfull = sh.nfull;
+    pl.nchunks = 0;
+    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
+    if (pl.per_wave * (size_t)grid > kRingMaxScratch) {
+        grid = (long long)(kRingMaxScratch / pl.per_wave);
+        if (grid < 1) grid = 1;
+    }
+    pl.grid = (int)grid;
+    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
+    const size_t TD = (size_t)T * d;
+    pl.col_bytes = (size_t)sh.tm.start(sh.tm.owned, A, pl.R, 1) * TD * sizeof(double);
+    pl.partial_bytes = (size_t)sh.slabs * TD * sizeof(double) - pl.col_bytes;
     return SIGSVGD_OK;
 }
 
@@ -657,6 +969,78 @@ int long2_launch(const void *X, const void *Y, int A, int B, int M, int N, int d
                 : long2_reduce<float>(stream, a.colpart, gradY_out, B, pl.nti, N * d, 0);
         if (e != hipSuccess) return hip_fail(e, "launch long2_reduce_kernel (columns)");
     }
+    return SIGSVGD_OK;
+}
+
+// the partial mode's tile: R rows x JC columns, the same for every rank of `stride` (host only)
+int long_part_tiles(int A, int T, int d, int n, int stride, int *R, int *JC)
+{
+    PartPlan pl;
+    const int rc = part_make_plan(A, T, d, n, -1, stride, true, pl);
+    if (rc) return rc;
+    *R = pl.R;
+    *JC = pl.JC;
+    return SIGSVGD_OK;
+}
+
+// bytes of the workspace of rank `off` of `stride` (0 for a rank that owns no tile)
+int long_part_workspace(int A, int T, int d, int n, int off, int stride, bool fold, size_t *bytes)
+{
+    PartPlan pl;
+    const int rc = part_make_plan(A, T, d, n, off, stride, fold, pl);
+    if (rc) return rc;
+    *bytes = pl.total();
+    return SIGSVGD_OK;
+}
+
+namespace {
+template <typename IO, bool NAIVE, int KIND>
+hipError_t part_launch_one(const PartPlan &pl, hipStream_t stream, const PartArgs &a)
+{
+    const hipError_t e = raise_lds_limit<&gram_long_part_kernel<IO, NAIVE, KIND>>();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((gram_long_part_kernel<IO, NAIVE, KIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
+    return hipSuccess;
+}
+template <typename IO>
+hipError_t part_dispatch(int kind, bool naive, const PartPlan &pl, hipStream_t stream, const PartArgs &a)
+{
+    if (kind == SIGSVGD_STATIC_RBF)
+        return naive ? part_launch_one<IO, true, SIGSVGD_STATIC_RBF>(pl, stream, a)
+                     : part_launch_one<IO, false, SIGSVGD_STATIC_RBF>(pl, stream, a);
+    return naive ? part_launch_one<IO, true, SIGSVGD_STATIC_LINEAR>(pl, stream, a)
+                 : part_launch_one<IO, false, SIGSVGD_STATIC_LINEAR>(pl, stream, a);
+}
+} // namespace
+
+// the argument checks are the entry point's (capi.hip).  K_partial gets the owned pairs and their mirror images, grad_partial
+// (fp64) is overwritten whole; a rank that owns no tile launches the reduction alone, which writes zeros.
+int long_part_launch(const void *X, int A, int T, int d, int dtype, double inv_h, int n, int kind, bool naive, bool sym,
+                     int off, int stride, bool fold, const void *grad_out, void *K_partial, double *grad_partial, void *ws,
+                     size_t ws_bytes, hipStream_t stream)
+{
+    PartPlan pl;
+    PartArgs a;
+    int rc = part_make_plan(A, T, d, n, off, stride, fold, pl);
+    if (!rc)
+        rc = long_args("gram_long_sym_partial", pl, pl.total(), ws, ws_bytes, X, X, grad_out, K_partial, A, A, T, T, d, n, sym,
+                       inv_h, a);
+    if (rc) return rc;
+    a.colpart = pl.col_bytes // (behind the forward scratch and the row-side slabs)
+                    ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(a.wsk) + pl.wsk_bytes + pl.partial_bytes)
+                    : nullptr;
+    a.tm = pl.tm; a.R = pl.R; a.nfull = pl.nfull;
+    if (pl.items > 0) {
+        hipError_t e = dtype == SIGSVGD_F64 ? part_dispatch<double>(kind, naive, pl, stream, a)
+                                            : part_dispatch<float>(kind, naive, pl, stream, a);
+        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long_part)");
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "launch gram_long_part_kernel");
+    }
+    hipLaunchKernelGGL(long_part_reduce_kernel, dim3(A), dim3(256), 0, stream, a.partials, a.colpart, grad_partial, A, T * d,
+                       pl.R, pl.JC, pl.tm);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, "launch long_part_reduce_kernel");
     return SIGSVGD_OK;
 }
 

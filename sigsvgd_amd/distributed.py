@@ -14,6 +14,10 @@ natural sharding: N^2/2 independent pair solves followed by one reduction over p
                     its mirror image always hold the same number of pairs and every rank gets the same
                     share; cyclic ownership alone gives the first rank 5.4 % more than the mean at N=1024,
                     G=8), on the gathered X:  K_partial [N,N], grad_partial [N,T,d]
+                    LONG ROUTE (launches the fused kernels refuse: long paths, refined grids past the LDS; and any shape
+                    with long_partial=True): the same ownership, folded or cyclic, on row tiles of
+                    ops.gram_long_partial_tiles(...)[0] rows, solved by ops.gram_long_sym_partial at the step's dyadic
+                    order and static kernel -- each unordered pair once across the node there too
                     v_partial = -((K_partial @ score - grad_partial)/N)   (linear in the partials)
     3. reduce-scatter(sum) v_partial -> this rank's rows of v;  X_shard <- X_shard - lr * v  (one launch)
 All per-step buffers (gathered operands, partials, velocity) are allocated once and reused.
@@ -29,7 +33,7 @@ from typing import Callable, Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import _lib, ops
 
 
 def _world(group=None) -> Tuple[int, int]:
@@ -118,15 +122,32 @@ class ShardedSigSVGD:
 
     partial_fn(X_full, inv_h, tile_offset, tile_stride[, out=, fold=]) -> (K_partial, grad_partial) defaults to the
     HIP library's symmetric partial solve with folded tile ownership; phi_fn(K, score, grad_k) -> v to the MFMA velocity
-    kernel.  (The CPU tests substitute oracle-backed callables to exercise the sharding algebra under gloo.)"""
+    kernel.  (The CPU tests substitute oracle-backed callables to exercise the sharding algebra under gloo.)
+
+    dyadic_order / static_kind: the step's refinement and built-in static kernel.  The route of a step, in this order:
+    rowwise=True -> (own rows) x (all columns); the fused partial solve where it takes the shape (order 0, RBF, T <= 128,
+    d <= 16); the row-wise solve where the fused kernels take the launch, and always with a caller's rows_fn (unless a
+    long_partial_fn is given too: a caller's row solver keeps the launches it got before); else the long partial solve
+    long_partial_fn(X_full, inv_h, tile_offset, tile_stride, dyadic_order=, static_kind=, out=, fold=) -> (K_partial,
+    grad_partial), by default `ops.gram_long_sym_partial`; else the row-wise call's own error.  long_partial=True sends every
+    shape the long partial takes to it (each pair once also at 129 <= T <= 190), long_partial=False never uses it.
+    `last_route` names the last step's route ("partial", "rowwise" or "long_partial")."""
 
     def __init__(self, inv_h: float, lr: float, group=None, partial_fn: Optional[Callable] = None,
                  phi_fn: Optional[Callable] = None, rows_fn: Optional[Callable] = None, rowwise: bool = False,
-                 fold: bool = True):
+                 fold: bool = True, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                 long_partial: Optional[bool] = None, long_partial_fn: Optional[Callable] = None):
         self.inv_h = float(inv_h)
         self.lr = float(lr)
         self.group = group
         self.fold = bool(fold)
+        self.dyadic_order = int(dyadic_order)
+        self.static_kind = int(static_kind)
+        self.long_partial = None if long_partial is None else bool(long_partial)
+        self.long_partial_fn = long_partial_fn or ops.gram_long_sym_partial
+        self._long_fold = bool(fold)  # (the 4-argument fallback below concerns partial_fn only)
+        self.last_route = None
+        self._routes = {}
         self.partial_fn = partial_fn or ops.gram_sym_partial
         # `out=` / `fold=` are passed only to callables that take them (the 4-argument contract of rounds 1-2 still works;
         # such a callable owns cyclic tiles and allocates its results)
@@ -141,6 +162,11 @@ class ShardedSigSVGD:
         if not self._partial_kwargs and self.fold and partial_fn is not None:
             self.fold = False  # (cyclic ownership is what a 4-argument callable implements)
         self.phi_fn = phi_fn or (lambda K, s, gk: ops.svgd_phi(K, s, gk))
+        # the long route is taken by itself only in place of the library's own row-wise solve: a caller's rows_fn keeps the
+        # launches it got before, unless the caller asks for the long partial (long_partial=True or a long_partial_fn)
+        self._auto_long = rows_fn is None or long_partial_fn is not None
+        if rows_fn is None and (self.dyadic_order != 0 or self.static_kind != _lib.STATIC_RBF):
+            rows_fn = lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind)
         self.rows_fn = rows_fn or (lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h))
         self.rowwise = bool(rowwise)
         self.last_K_partial = None  # ALIASES the step's preallocated buffer: the next step() overwrites it (clone to keep it)
@@ -178,13 +204,18 @@ class ShardedSigSVGD:
         self.last_gather_grouped = all_gather_rows_pair(X_shard, score_shard.to(X_shard.dtype), X_full, s_full, self.group)
         if mark:
             mark("all_gather")
-        if self.rowwise or not self._partial_supported(X_full):
+        route = self.last_route = self._route(X_shard.shape[0], X_full, world)
+        if route == "rowwise":
             out = self._step_rowwise(X_shard, X_full, s_full)
             if mark:
                 mark("rowwise_solve_and_update")
                 self.phase_ms = mark.result()
             return out
-        if self._partial_kwargs:  # (a user callable written to the 4-argument contract gets no preallocated outputs)
+        if route == "long_partial":
+            Kp, gp = self.long_partial_fn(X_full, self.inv_h, rank, world, dyadic_order=self.dyadic_order,
+                                          static_kind=self.static_kind, out=(buf["K_partial"], buf["grad_partial"]),
+                                          fold=self._long_fold)
+        elif self._partial_kwargs:  # (a user callable written to the 4-argument contract gets no preallocated outputs)
             Kp, gp = self.partial_fn(X_full, self.inv_h, rank, world, out=(buf["K_partial"], buf["grad_partial"]),
                                      fold=self.fold)
         else:
@@ -203,6 +234,28 @@ class ShardedSigSVGD:
             mark("update")
             self.phase_ms = mark.result()
         return out
+
+    def _route(self, n_own: int, X_full, world: int) -> str:
+        """"partial" (fused), "rowwise" or "long_partial" for this step's shape; see the class docstring for the order"""
+        N, T, d = X_full.shape
+        if self.rowwise:
+            return "rowwise"
+        key = (n_own, N, T, d, world)
+        if key not in self._routes:  # (host-only queries of the library, asked once per shape)
+            self._routes[key] = self._route_of(n_own, X_full, world)
+        return self._routes[key]
+
+    def _route_of(self, n_own: int, X_full, world: int) -> str:
+        N, T, d = X_full.shape
+        takes_long = lambda: ops.gram_long_partial_takes(N, T, d, self.dyadic_order, self.static_kind, world)
+        if self.long_partial and takes_long():
+            return "long_partial"
+        if self.dyadic_order == 0 and self.static_kind == _lib.STATIC_RBF and self._partial_supported(X_full):
+            return "partial"
+        if self.long_partial is None and self._auto_long \
+                and not ops.gram_takes(n_own, N, T, d, self.dyadic_order, self.static_kind) and takes_long():
+            return "long_partial"
+        return "rowwise"
 
     @staticmethod
     def _partial_supported(X_full) -> bool:

@@ -539,6 +539,76 @@ def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static
     return Kp, gp
 
 
+def gram_long_partial_tiles(N: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                            tile_stride: int = 1) -> Tuple[int, int]:
+    """(R, JC): rows per owned tile and columns per work item of `gram_long_sym_partial` on N paths [T, d] shared among
+    tile_stride ranks (`sigsvgd_gram_long_partial_plan`, host only).  The same for every rank and for folded and cyclic
+    ownership; R is the ownership unit of the sharded step on the long route."""
+    L = _lib.load()
+    R, JC = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(L.sigsvgd_gram_long_partial_plan(int(N), int(T), int(d), int(dyadic_order), int(static_kind), 0,
+                                                int(tile_stride), ctypes.byref(R), ctypes.byref(JC)), "gram_long_partial_plan")
+    return int(R.value), int(JC.value)
+
+
+def gram_long_partial_takes(N: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                            tile_stride: int = 1) -> bool:
+    """Whether `gram_long_sym_partial` takes N paths [T, d] with these settings: the library's plan query, host only.  False
+    exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave state beyond the LDS); any
+    other error raises."""
+    L = _lib.load()
+    R, JC = ctypes.c_int(0), ctypes.c_int(0)
+    rc = L.sigsvgd_gram_long_partial_plan(int(N), int(T), int(d), int(dyadic_order), int(static_kind), 0, int(tile_stride),
+                                          ctypes.byref(R), ctypes.byref(JC))
+    if rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, "gram_long_partial_plan")
+    return True
+
+
+def gram_long_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, dyadic_order: int = 0,
+                          static_kind: int = _lib.STATIC_RBF, grad_out: Optional[torch.Tensor] = None, naive: bool = False,
+                          sym: bool = False, out=None, fold: bool = False):
+    """This rank's share of the Y-is-X Gram + gradient of the long route on the gathered particles X [N,T,d]
+    (`sigsvgd_gram_long_sym_partial`): returns (K_partial [N,N] X.dtype, grad_partial [N,T,d] fp64), zero outside the owned
+    pairs.  Summed over tile_offset = 0..tile_stride-1 they equal gram_long_fwd_bwd2(X, X, y_is_x=True): K bit for bit, the
+    gradient up to the order of the fp64 sums.  Any T >= 2, dyadic order and built-in static kernel the long route takes.
+    The launch owns the row tiles (`gram_long_partial_tiles(...)[0]` rows each) tile_offset + k*tile_stride; with fold=True
+    also their mirror images, which gives every rank the same number of pairs (SIGSVGD_FLAG_FOLD_TILES).
+    `out=(K_partial, grad_partial)` reuses the caller's buffers (K_partial is re-zeroed, grad_partial overwritten)."""
+    L = _lib.load()
+    dev = _require_gpu(X, grad_out)
+    Xc, _ = _prep_long(X, X)
+    N, T, d = Xc.shape
+    go = None
+    if grad_out is not None:
+        if tuple(grad_out.shape) != (N, N):
+            raise ValueError(f"grad_out must be [{N},{N}], got {tuple(grad_out.shape)}")
+        go = grad_out.detach().to(Xc.dtype).contiguous()
+    if out is not None:
+        Kp, gp = out
+        if (tuple(Kp.shape) != (N, N) or Kp.dtype != Xc.dtype or not Kp.is_contiguous() or tuple(gp.shape) != (N, T, d)
+                or gp.dtype != torch.float64 or not gp.is_contiguous()):
+            raise ValueError("out must be (K_partial [N,N] of X's dtype, grad_partial [N,T,d] float64), contiguous")
+        Kp.zero_()
+    else:
+        Kp = torch.zeros((N, N), dtype=Xc.dtype, device=dev)
+        gp = torch.empty((N, T, d), dtype=torch.float64, device=dev)  # fully overwritten by the library
+    flags = _flags(naive, sym, True, False) | (_lib.FLAG_FOLD_TILES if fold else 0)
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_gram_long_partial_workspace_bytes(N, T, d, int(dyadic_order), int(static_kind), flags,
+                                                           int(tile_offset), int(tile_stride), ctypes.byref(nbytes)),
+               "gram_long_partial_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_gram_long_sym_partial(Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                                             int(static_kind), flags, int(tile_offset), int(tile_stride),
+                                             go.data_ptr() if go is not None else None, Kp.data_ptr(), gp.data_ptr(),
+                                             ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
+    _lib.check(rc, "gram_long_sym_partial")
+    return Kp, gp
+
+
 def sym_tile_rows(T: int, d: int) -> int:
     """Rows per tile of the symmetric / partial solve (the ownership unit of the sharded step); 0 for shapes the partial
     solve does not take.  Host-only query of the library."""
