@@ -20,8 +20,9 @@
 // overwrites K_fwd in its slot); phase 4 scatter R, R*G and both contractions in a second wrap-around
 // pass (66 iterations, all lanes busy).  The two sweeps have on average half of their lanes outside the
 // grid: their steps are hand-written (8 VALU + 2 SALU) and the idle lanes are switched off through EXEC windows
-// read from a constant table.  The kernel is bound by vector-instruction issue at two waves per SIMD, i.e. by
-// its instruction count (5,430 per pair at C4): see DESIGN.md 5.1 / 5.1.1.
+// read from a constant table (gradient launches of 64-point paths: built from immediates, "fixed windows" below).
+// The kernel is bound by vector-instruction issue at two waves per SIMD, i.e. by its instruction count (5,430 per
+// pair at C4): see DESIGN.md 5.1 / 5.1.1.
 //
 // A workgroup is NW wavefronts = NW consecutive rows i of X against a chunk of columns j; the
 // column trajectory (centred on its first point, fp64 + fp32 copies) is staged once per j in LDS
@@ -35,6 +36,7 @@
 // Reference semantics: sigkernel _SigKernelGram.forward/backward [RECALLED, SURVEY.md App. A];
 // static kernel src/kernels/_traj_kernels.py:176-195; callers src/inference/score.py:68-69.
 #include <atomic>
+#include <cstdlib>
 
 #include "sig_common.h"
 
@@ -195,25 +197,30 @@ struct SweepMasks32 {
 };
 __constant__ const SweepMasks32 SWEEP_MASK32 = SweepMasks32();
 
-#define SIG_FWD_STEP(UP, DIAG, G, KSL, M)                                                     \
+// EXECW writes the step's window into EXEC: SIG_WIN_TAB from the SGPR pair the table load filled, SIG_WIN_FIX (path length
+// known at compile time, see "fixed windows" below) from two inline constants.
+#define SIG_WIN_TAB(M) "s_mov_b64 exec, %[" M "]\n\t"
+#define SIG_WIN_FIX(N) "s_bfm_b64 exec, %[w" N "], %[o" N "]\n\t"
+#define SIG_FWD_STEP_X(UP, DIAG, G, KSL, EXECW)                                               \
     "s_mov_b64 exec, -1\n\t"                                                                  \
     "v_mov_b32_dpp %[" UP "], %[cur] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t"               \
-    "s_mov_b64 exec, %[" M "]\n\t"                                                            \
+    EXECW                                                                                     \
     "v_add_f32 %[t], %[cur], %[" UP "]\n\t"                                                   \
     "v_mul_f32 %[y], %[r3], %[t]\n\t"                                                         \
     "v_add_f32 %[t], %[t], %[" DIAG "]\n\t"                                                   \
     "v_fmac_f32 %[y], %[t], %[" G "]\n\t"                                                     \
     "v_fmac_f32 %[V], %[" G "], %[y]\n\t"                                                     \
     "v_add_f32 %[cur], %[" UP "], %[V]\n\t" KSL
+#define SIG_FWD_STEP(UP, DIAG, G, KSL, M) SIG_FWD_STEP_X(UP, DIAG, G, KSL, SIG_WIN_TAB(M))
 #define SIG_FWD_KSL(DIAG, K) "v_mov_b32 %[" K "], %[" DIAG "]\n\t"
 #define SIG_FWD_NOKSL "v_max_f32 %[km], |%[cur]|, %[km]\n\t" // (forward-only launches: the largest |K| of the grid, in the hazard slot)
 // few-channel forward-only launches also sum |K[l][q] * gamma[l][q]| over the cells: the forward half of the condition
 // estimate sum |S * D| / |K| that decides whether the pair goes to the exact fp64 pass (see the kernel, "conditioning")
 #define SIG_FWD_NOKSL_SD(DIAG, G) "v_max_f32 %[km], |%[cur]|, %[km]\n\tv_fma_f32 %[sd], |%[" DIAG "]|, |%[" G "]|, %[sd]\n\t"
-#define SIG_REV_STEP(DN, DDIAG, G, K, M)                                                      \
+#define SIG_REV_STEP_X(DN, DDIAG, G, K, EXECW)                                                \
     "s_mov_b64 exec, -1\n\t"                                                                  \
     "v_mov_b32_dpp %[" DN "], %[cur] wave_shl:1 row_mask:0xf bank_mask:0xf\n\t"               \
-    "s_mov_b64 exec, %[" M "]\n\t"                                                            \
+    EXECW                                                                                     \
     "v_add_f32 %[t], %[cur], %[" DN "]\n\t"                                                   \
     "v_mul_f32 %[y], %[r3], %[t]\n\t"                                                         \
     "v_add_f32 %[t], %[t], %[" DDIAG "]\n\t"                                                  \
@@ -221,6 +228,7 @@ __constant__ const SweepMasks32 SWEEP_MASK32 = SweepMasks32();
     "v_fmac_f32 %[V], %[" G "], %[y]\n\t"                                                     \
     "v_add_f32 %[cur], %[" DN "], %[V]\n\t"                                                   \
     "v_mul_f32 %[" K "], %[" K "], %[" DDIAG "]\n\t"
+#define SIG_REV_STEP(DN, DDIAG, G, K, M) SIG_REV_STEP_X(DN, DDIAG, G, K, SIG_WIN_TAB(M))
 
 // steps sigma0 .. sigma0+7 of the forward sweep (sigma0 even): g, ksl point at slots sigma0 & 63 ..; mk at the
 // windows of sigma0 ..
@@ -291,6 +299,129 @@ __device__ __forceinline__ void sweep_rev8(float &cur, float &dnA, float &dnB, f
                    [m4] "s"(m4), [m5] "s"(m5), [m6] "s"(m6), [m7] "s"(m7));
 }
 
+// ---- fixed windows: the sweep statements of a path length known at compile time ---------------------------------------------
+// The table costs every statement a 16-SGPR scalar load and a wait on it, and the load cannot start before the statement
+// before has ended (the same SGPRs hold its windows).  Where P is a template constant (the kernel's PFIX: paths of PFIX + 1
+// points) the window of step sigma, lanes lo .. hi, is `s_bfm_b64 exec, hi - lo + 1, lo` with two inline constants (both
+// <= 63; an empty window is width 0): no table, no load, no mask operands.  Everything else of a step -- instructions, order,
+// operand roles, the alternating up / down registers, the slot stores, the EXEC = -1 around the DPP move and at the end of
+// the statement -- is the table form's, so the results are the same bit for bit.  The windows differ from round to round, so
+// each round has statements of its own; steps past 2P - 2 have no cell and no statement (they only shifted `cur` into an up /
+// down register nobody reads again: forward, or that holds the same 1.0 already: reverse), so the last statement of a
+// sweep of 2P - 1 = 125 (61) steps has five steps.
+constexpr int sweep_win_lo(int P, int s) { return s - P + 1 > 0 ? s - P + 1 : 0; }
+constexpr int sweep_win_hi(int P, int s) { return s < P - 1 ? s : P - 1; }
+constexpr int sweep_win_w(int P, int s) { return sweep_win_hi(P, s) >= sweep_win_lo(P, s) ? sweep_win_hi(P, s) - sweep_win_lo(P, s) + 1 : 0; }
+constexpr int sweep_win_o(int P, int s) { return sweep_win_w(P, s) ? sweep_win_lo(P, s) : 0; }
+// what s_bfm_b64 D, w, o computes: ((1 << w[5:0]) - 1) << o[5:0]
+constexpr unsigned long long sweep_bfm64(int w, int o) { return ((1ull << (w & 63)) - 1ull) << (o & 63); }
+constexpr unsigned sweep_bfm32(int w, int o) { return ((1u << (w & 31)) - 1u) << (o & 31); }
+// the immediates reproduce the tables bit for bit, empty steps included (the 32-slot ring: the same window in both halves of EXEC,
+// one s_bfm_b32 each)
+constexpr bool sweep_windows_match(int P)
+{
+    const SweepMasks tab;
+    const SweepMasks32 tab32;
+    for (int s = 0; s < 128; ++s) {
+        const int w = sweep_win_w(P, s), o = sweep_win_o(P, s);
+        if (w < 0 || w > 63 || o < 0 || o > 63) return false;
+        if (sweep_bfm64(w, o) != tab.m[P][s]) return false;
+        if (P < 32 && s < 64) {
+            if (w > 31 || o > 31) return false;
+            const unsigned h = sweep_bfm32(w, o);
+            if ((((unsigned long long)h << 32) | h) != tab32.m[P][s]) return false;
+        }
+    }
+    return true;
+}
+static_assert(sweep_windows_match(63), "fixed EXEC windows differ from SWEEP_MASK at P = 63");
+static_assert(sweep_windows_match(31), "fixed EXEC windows differ from SWEEP_MASK / SWEEP_MASK32 at P = 31");
+
+#define SIG_WIN_OPS(k) [w##k] "n"(sweep_win_w(PFIX, SIGMA0 + k)), [o##k] "n"(sweep_win_o(PFIX, SIGMA0 + k))
+// steps SIGMA0 .. SIGMA0 + NS - 1 of the forward sweep of a gradient launch (sweep_fwd8<0> with immediates); NS = 8, or 5 for
+// the statement that ends the sweep
+template <int PFIX, int SIGMA0, int NS>
+__device__ __forceinline__ void sweep_fwd_fixed(float &cur, float &upA, float &upB, float &V, const float *g, float *ksl, const float r3)
+{
+    static_assert((NS == 8 || NS == 5) && SIGMA0 % 8 == 0 && SIGMA0 + NS <= 2 * PFIX - 1, "statement shape");
+    float t, y;
+    SIG_EXEC_MUST_BE_FULL("sweep_fwd_fixed");
+    if constexpr (NS == 8)
+        asm volatile(SIG_FWD_STEP_X("upA", "upB", "g0", SIG_FWD_KSL("upB", "k0"), SIG_WIN_FIX("0"))
+                     SIG_FWD_STEP_X("upB", "upA", "g1", SIG_FWD_KSL("upA", "k1"), SIG_WIN_FIX("1"))
+                     SIG_FWD_STEP_X("upA", "upB", "g2", SIG_FWD_KSL("upB", "k2"), SIG_WIN_FIX("2"))
+                     SIG_FWD_STEP_X("upB", "upA", "g3", SIG_FWD_KSL("upA", "k3"), SIG_WIN_FIX("3"))
+                     SIG_FWD_STEP_X("upA", "upB", "g4", SIG_FWD_KSL("upB", "k4"), SIG_WIN_FIX("4"))
+                     SIG_FWD_STEP_X("upB", "upA", "g5", SIG_FWD_KSL("upA", "k5"), SIG_WIN_FIX("5"))
+                     SIG_FWD_STEP_X("upA", "upB", "g6", SIG_FWD_KSL("upB", "k6"), SIG_WIN_FIX("6"))
+                     SIG_FWD_STEP_X("upB", "upA", "g7", SIG_FWD_KSL("upA", "k7"), SIG_WIN_FIX("7"))
+                     "s_mov_b64 exec, -1\n\t"
+                     : [cur] "+v"(cur), [upA] "+v"(upA), [upB] "+v"(upB), [V] "+v"(V), [t] "=&v"(t), [y] "=&v"(y),
+                       [k0] "+v"(ksl[0]), [k1] "+v"(ksl[1]), [k2] "+v"(ksl[2]), [k3] "+v"(ksl[3]), [k4] "+v"(ksl[4]),
+                       [k5] "+v"(ksl[5]), [k6] "+v"(ksl[6]), [k7] "+v"(ksl[7])
+                     : [g0] "v"(g[0]), [g1] "v"(g[1]), [g2] "v"(g[2]), [g3] "v"(g[3]), [g4] "v"(g[4]), [g5] "v"(g[5]),
+                       [g6] "v"(g[6]), [g7] "v"(g[7]), [r3] "s"(r3), SIG_WIN_OPS(0), SIG_WIN_OPS(1), SIG_WIN_OPS(2),
+                       SIG_WIN_OPS(3), SIG_WIN_OPS(4), SIG_WIN_OPS(5), SIG_WIN_OPS(6), SIG_WIN_OPS(7));
+    else
+        asm volatile(SIG_FWD_STEP_X("upA", "upB", "g0", SIG_FWD_KSL("upB", "k0"), SIG_WIN_FIX("0"))
+                     SIG_FWD_STEP_X("upB", "upA", "g1", SIG_FWD_KSL("upA", "k1"), SIG_WIN_FIX("1"))
+                     SIG_FWD_STEP_X("upA", "upB", "g2", SIG_FWD_KSL("upB", "k2"), SIG_WIN_FIX("2"))
+                     SIG_FWD_STEP_X("upB", "upA", "g3", SIG_FWD_KSL("upA", "k3"), SIG_WIN_FIX("3"))
+                     SIG_FWD_STEP_X("upA", "upB", "g4", SIG_FWD_KSL("upB", "k4"), SIG_WIN_FIX("4"))
+                     "s_mov_b64 exec, -1\n\t"
+                     : [cur] "+v"(cur), [upA] "+v"(upA), [upB] "+v"(upB), [V] "+v"(V), [t] "=&v"(t), [y] "=&v"(y),
+                       [k0] "+v"(ksl[0]), [k1] "+v"(ksl[1]), [k2] "+v"(ksl[2]), [k3] "+v"(ksl[3]), [k4] "+v"(ksl[4])
+                     : [g0] "v"(g[0]), [g1] "v"(g[1]), [g2] "v"(g[2]), [g3] "v"(g[3]), [g4] "v"(g[4]), [r3] "s"(r3),
+                       SIG_WIN_OPS(0), SIG_WIN_OPS(1), SIG_WIN_OPS(2), SIG_WIN_OPS(3), SIG_WIN_OPS(4));
+}
+// steps SIGMA0 + NS - 1 .. SIGMA0 of the reverse sweep (sweep_rev8 with immediates): a step keeps the down registers it has
+// in the 8-step statement (even steps dnB, odd steps dnA), so the 5-step statement starts on dnB
+template <int PFIX, int SIGMA0, int NS>
+__device__ __forceinline__ void sweep_rev_fixed(float &cur, float &dnA, float &dnB, float &V, const float *g, float *ksl, const float r3)
+{
+    static_assert((NS == 8 || NS == 5) && SIGMA0 % 8 == 0 && SIGMA0 + NS <= 2 * PFIX - 1, "statement shape");
+    float t, y;
+    SIG_EXEC_MUST_BE_FULL("sweep_rev_fixed");
+    if constexpr (NS == 8)
+        asm volatile(SIG_REV_STEP_X("dnA", "dnB", "g7", "k7", SIG_WIN_FIX("7")) SIG_REV_STEP_X("dnB", "dnA", "g6", "k6", SIG_WIN_FIX("6"))
+                     SIG_REV_STEP_X("dnA", "dnB", "g5", "k5", SIG_WIN_FIX("5")) SIG_REV_STEP_X("dnB", "dnA", "g4", "k4", SIG_WIN_FIX("4"))
+                     SIG_REV_STEP_X("dnA", "dnB", "g3", "k3", SIG_WIN_FIX("3")) SIG_REV_STEP_X("dnB", "dnA", "g2", "k2", SIG_WIN_FIX("2"))
+                     SIG_REV_STEP_X("dnA", "dnB", "g1", "k1", SIG_WIN_FIX("1")) SIG_REV_STEP_X("dnB", "dnA", "g0", "k0", SIG_WIN_FIX("0"))
+                     "s_mov_b64 exec, -1\n\t"
+                     : [cur] "+v"(cur), [dnA] "+v"(dnA), [dnB] "+v"(dnB), [V] "+v"(V), [t] "=&v"(t), [y] "=&v"(y),
+                       [k0] "+v"(ksl[0]), [k1] "+v"(ksl[1]), [k2] "+v"(ksl[2]), [k3] "+v"(ksl[3]), [k4] "+v"(ksl[4]),
+                       [k5] "+v"(ksl[5]), [k6] "+v"(ksl[6]), [k7] "+v"(ksl[7])
+                     : [g0] "v"(g[0]), [g1] "v"(g[1]), [g2] "v"(g[2]), [g3] "v"(g[3]), [g4] "v"(g[4]), [g5] "v"(g[5]),
+                       [g6] "v"(g[6]), [g7] "v"(g[7]), [r3] "s"(r3), SIG_WIN_OPS(0), SIG_WIN_OPS(1), SIG_WIN_OPS(2),
+                       SIG_WIN_OPS(3), SIG_WIN_OPS(4), SIG_WIN_OPS(5), SIG_WIN_OPS(6), SIG_WIN_OPS(7));
+    else
+        asm volatile(SIG_REV_STEP_X("dnB", "dnA", "g4", "k4", SIG_WIN_FIX("4"))
+                     SIG_REV_STEP_X("dnA", "dnB", "g3", "k3", SIG_WIN_FIX("3")) SIG_REV_STEP_X("dnB", "dnA", "g2", "k2", SIG_WIN_FIX("2"))
+                     SIG_REV_STEP_X("dnA", "dnB", "g1", "k1", SIG_WIN_FIX("1")) SIG_REV_STEP_X("dnB", "dnA", "g0", "k0", SIG_WIN_FIX("0"))
+                     "s_mov_b64 exec, -1\n\t"
+                     : [cur] "+v"(cur), [dnA] "+v"(dnA), [dnB] "+v"(dnB), [V] "+v"(V), [t] "=&v"(t), [y] "=&v"(y),
+                       [k0] "+v"(ksl[0]), [k1] "+v"(ksl[1]), [k2] "+v"(ksl[2]), [k3] "+v"(ksl[3]), [k4] "+v"(ksl[4])
+                     : [g0] "v"(g[0]), [g1] "v"(g[1]), [g2] "v"(g[2]), [g3] "v"(g[3]), [g4] "v"(g[4]), [r3] "s"(r3),
+                       SIG_WIN_OPS(0), SIG_WIN_OPS(1), SIG_WIN_OPS(2), SIG_WIN_OPS(3), SIG_WIN_OPS(4));
+}
+// the statements of steps S0 .. S1 - 1 of one round (S0 a multiple of 8), ascending / descending; slots are sigma & 63
+template <int PFIX, int S0, int S1>
+__device__ __forceinline__ void sweep_fwd_fixed_round(float &cur, float &upA, float &upB, float &V, const float *Dsl, float *Ksl, const float r3)
+{
+    if constexpr (S0 < S1) {
+        sweep_fwd_fixed<PFIX, S0, (S1 - S0 < 8 ? S1 - S0 : 8)>(cur, upA, upB, V, Dsl + (S0 & 63), Ksl + (S0 & 63), r3);
+        sweep_fwd_fixed_round<PFIX, S0 + 8, S1>(cur, upA, upB, V, Dsl, Ksl, r3);
+    }
+}
+template <int PFIX, int S0, int S1>
+__device__ __forceinline__ void sweep_rev_fixed_round(float &cur, float &dnA, float &dnB, float &V, const float *Dsl, float *Ksl, const float r3)
+{
+    if constexpr (S0 < S1) {
+        sweep_rev_fixed_round<PFIX, S0 + 8, S1>(cur, dnA, dnB, V, Dsl, Ksl, r3);
+        sweep_rev_fixed<PFIX, S0, (S1 - S0 < 8 ? S1 - S0 : 8)>(cur, dnA, dnB, V, Dsl + (S0 & 63), Ksl + (S0 & 63), r3);
+    }
+}
+
 // ---- fp64 forward sweep of a pair whose fp32 solution cancelled ----------------------------------------------------
 // The fp32 sweeps resolve K to ~1e-7 of the LARGEST value on the pair's grid.  Where the discrete solution oscillates
 // (rough paths in few channels against a narrow static kernel: K(x, y) passes through zero, turns negative), the value at
@@ -353,7 +484,9 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // consecutive lanes, and the two sums of a column (they end 32 lanes apart) are added when the workgroup's waves are --
 // exactly the sum over the tile's rows the column side wants.  (Round 2 let lanes 32..63 mirror lanes 0..31: the same
 // work twice.)
-template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64>
+// PFIX: 0, or the launch's P = T - 1 as a compile-time constant: the sweeps then build their EXEC windows from immediates (see
+// "fixed windows" above; gradient kernels of the 64-slot ring at T = 64).  Nothing else of the kernel depends on it.
+template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : 2),
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgs a)
@@ -591,6 +724,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                     for (int k = 0; k < RING; ++k) Ksl[k] = 0.f;
                 }
+                if constexpr (PFIX != 0) { // windows from immediates: a round of 64 steps, then the 61 that are left
+                    static_assert(GRAD && RING == 64 && PFIX == 63, "fixed windows: gradient kernels of the 64-slot ring at T = 64");
+                    float r3 = 1.7320508075688772f;
+                    asm volatile("" : "+s"(r3));
+                    sweep_fwd_fixed_round<PFIX, 0, 64>(cur, upA, upB, V, Dsl, Ksl, r3);
+                    asm volatile("" : "+s"(r3));
+                    sweep_fwd_fixed_round<PFIX, 64, 2 * PFIX - 1>(cur, upA, upB, V, Dsl, Ksl, r3);
+                } else
                 for (int rnd = 0; rnd < (RING == 64 ? 2 : 1); ++rnd) { // (RING = 32: 2P-2 <= 60, one round of 64 steps)
                     if (rnd * 64 > smax) break;
                     float r3 = 1.7320508075688772f;
@@ -758,6 +899,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     }
                 };
 
+                if constexpr (PFIX != 0) {
+                    asm volatile("" : "+v"(yfrow), "+v"(gsoff)); // (as in the table form below, once per round)
+                    float r3 = 1.7320508075688772f;
+                    asm volatile("" : "+s"(r3));
+                    sweep_rev_fixed_round<PFIX, 64, 2 * PFIX - 1>(cur, downA, downB, V, Dsl, Ksl, r3);
+                    asm volatile("" : "+v"(yfrow), "+v"(gsoff));
+                    asm volatile("" : "+s"(r3));
+                    sweep_rev_fixed_round<PFIX, 0, 64>(cur, downA, downB, V, Dsl, Ksl, r3);
+                } else
                 for (int rnd = (RING == 64 ? 1 : 0); rnd >= 0; --rnd) {
                     if (rnd * 64 > smax) continue;
                     // (keeps the phase-4 LDS addresses out of this loop's invariants: without the pin hipcc
@@ -1076,10 +1226,21 @@ GradGeom fast_geometry(int A, int B, int T, int d, bool sym, int off, int stride
 
 int sym_tile_rows_fast(int T, int d) { return grad_nw(T, d); }
 
+// Gradient launches of 64-point paths run the kernel whose sweeps build their EXEC windows from immediates (PFIX = 63).
+// SIGSVGD_SWEEP_WINDOWS=table (read per launch, here, like SIGSVGD_BAND_MODE in capi.hip) keeps them on the table form: the tests compare
+// the two on one build.  Every other length, and the forward-only launches, have the table form only.
+static bool fixed_windows(int T, int want_grad)
+{
+    if (T != 64 || !want_grad) return false;
+    const char *e = getenv("SIGSVGD_SWEEP_WINDOWS");
+    return !(e && e[0] == 't');
+}
+
 // [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold)
 {
     WsPlan w;
+    w.fixed_windows = fixed_windows(T, want_grad) ? 1 : 0;
     if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
     if (want_grad) {
         w.g = fast_geometry(A, B, T, d, sym, off, stride, fold);
@@ -1090,6 +1251,19 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
 }
 
 namespace {
+// a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths
+template <int DPAD, int NW, bool SYM, bool LP, int RING>
+void launch_grad(bool fix, dim3 grid, dim3 block, hipStream_t stream, const FastArgs &a)
+{
+    if constexpr (RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
+        if (fix) {
+            hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63>), grid, block, 0, stream, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING>), grid, block, 0, stream, a);
+}
+
 template <int DPAD, int NW, int RING = 64>
 int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
 {
@@ -1119,18 +1293,19 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     }
     constexpr bool HAS_LP = DPAD <= 8; // the d == DPAD - 1 instantiations exist for the 4- and 8-channel layouts
     const bool lp = HAS_LP && grad && p.d == DPAD - 1;
+    const bool fix = grad && w.fixed_windows && p.T == 64; // (the kernel's PFIX must be the launch's T - 1)
     if (!grad && sym)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING>), grid, block, 0, p.stream, a);
     else if (!grad)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING>), grid, block, 0, p.stream, a);
     else if (sym && lp)
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, true, HAS_LP, RING>), grid, block, 0, p.stream, a);
+        launch_grad<DPAD, NW, true, HAS_LP, RING>(fix, grid, block, p.stream, a);
     else if (sym)
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, true, false, RING>), grid, block, 0, p.stream, a);
+        launch_grad<DPAD, NW, true, false, RING>(fix, grid, block, p.stream, a);
     else if (lp)
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, false, HAS_LP, RING>), grid, block, 0, p.stream, a);
+        launch_grad<DPAD, NW, false, HAS_LP, RING>(fix, grid, block, p.stream, a);
     else
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, false, false, RING>), grid, block, 0, p.stream, a);
+        launch_grad<DPAD, NW, false, false, RING>(fix, grid, block, p.stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS

@@ -291,6 +291,7 @@ struct WsPlan {
     WsArea crec, rowg, dcache; // gram_quad.hip: column records, row accumulators, increment scratch
     WsArea wsk;          // forward-solution scratch (gram_band.hip, gram_generic.hip)
     WsArea counter, partials, colslab; // gram_generic.hip: work counter, gradient partials, column-side slab
+    int fixed_windows = 0; // gram_fast.hip: the launch runs the kernel whose sweeps have their EXEC windows as immediates
     size_t end = 0; // bytes of the areas
     WsArea take(size_t bytes) // the next area, behind the ones taken so far
     {
