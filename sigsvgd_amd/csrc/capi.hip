@@ -10,11 +10,13 @@ namespace sigsvgd {
 
 static thread_local char g_err[512] = "";
 
+static void set_error_v(const char *fmt, va_list ap) { vsnprintf(g_err, sizeof(g_err), fmt, ap); }
+
 void set_error(const char *fmt, ...)
 {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    set_error_v(fmt, ap);
     va_end(ap);
 }
 
@@ -22,6 +24,16 @@ int hip_fail(hipError_t e, const char *what)
 {
     set_error("%s: %s", what, hipGetErrorString(e));
     return SIGSVGD_E_HIP;
+}
+
+// a refused argument: set_error with the message, and the status every such refusal returns
+static int bad_arg(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    set_error_v(fmt, ap);
+    va_end(ap);
+    return SIGSVGD_E_BADARG;
 }
 
 int phi_launch(const float *K, const float *score, const float *grad_k, const float *mask, int N, int D,
@@ -48,55 +60,35 @@ int signature_bwd_launch(const void *X, const void *gsig, int N, int L, int C, i
 int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes);
 int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, const void *grad_out, void *K_out,
                void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream);
-int long_workspace(int A, int B, int M, int N, int d, int n, int want_grad, size_t *bytes);
-int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
-                bool naive, bool sym, const void *grad_out, void *K_out, void *gradX_out, void *ws, size_t ws_bytes,
-                hipStream_t stream);
-int long2_workspace(int A, int B, int M, int N, int d, int n, int want_gradX, int want_gradY, bool yx, size_t *bytes);
-int long2_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
-                 bool naive, bool sym, bool yx, const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws,
-                 size_t ws_bytes, hipStream_t stream);
-int long_part_tiles(int A, int T, int d, int n, int stride, int *R, int *JC);
-int long_part_workspace(int A, int T, int d, int n, int off, int stride, bool fold, size_t *bytes);
-int long_part_launch(const void *X, int A, int T, int d, int dtype, double inv_h, int n, int kind, bool naive, bool sym,
-                     int off, int stride, bool fold, const void *grad_out, void *K_partial, double *grad_partial, void *ws,
-                     size_t ws_bytes, hipStream_t stream);
-int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes);
-int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
-                const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
-                hipStream_t stream);
+// the long-path route (gram_long.hip); the queries read the problem's shape, order and flags only
+int long_workspace(const LongProblem &p, int want_grad, size_t *bytes);
+int long_launch(const LongProblem &p);
+int pair_workspace(const LongProblem &p, int want_grad, size_t *bytes);
+int pair_launch(const LongProblem &p);
+int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes);
+int long2_launch(const LongProblem &p);
+int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC);
+int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes);
+int long_part_launch(const LongProblem &p, int off, int stride);
+
+// the refusal of a workspace query without a place for its answer
+static bool no_bytes(const size_t *bytes)
+{
+    if (!bytes) set_error("bytes == NULL");
+    return !bytes;
+}
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
-    if (!X || !Y || !K_out) {
-        set_error("null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
-    if (A < 1 || B < 1 || T < 2 || d < 1) {
-        set_error("bad shape A=%d B=%d T=%d d=%d (need A,B,d >= 1 and T >= 2)", A, B, T, d);
-        return SIGSVGD_E_BADARG;
-    }
-    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) {
-        set_error("bad dtype %d", dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind != SIGSVGD_STATIC_RBF && kind != SIGSVGD_STATIC_LINEAR) {
-        set_error("bad static kernel kind %d", kind);
-        return SIGSVGD_E_BADARG;
-    }
-    if (n < 0 || n > 10) {
-        set_error("bad dyadic order %d", n);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) {
-        set_error("RBF static kernel needs inv_h > 0 (got %g)", inv_h);
-        return SIGSVGD_E_BADARG;
-    }
-    if ((flags & SIGSVGD_FLAG_SYM) && A != B) {
-        set_error("sym backward needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!X || !Y || !K_out) return bad_arg("null pointer argument");
+    if (A < 1 || B < 1 || T < 2 || d < 1)
+        return bad_arg("bad shape A=%d B=%d T=%d d=%d (need A,B,d >= 1 and T >= 2)", A, B, T, d);
+    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("bad dtype %d", dtype);
+    if (kind != SIGSVGD_STATIC_RBF && kind != SIGSVGD_STATIC_LINEAR) return bad_arg("bad static kernel kind %d", kind);
+    if (n < 0 || n > 10) return bad_arg("bad dyadic order %d", n);
+    if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) return bad_arg("RBF static kernel needs inv_h > 0 (got %g)", inv_h);
+    if ((flags & SIGSVGD_FLAG_SYM) && A != B) return bad_arg("sym backward needs A == B");
     return SIGSVGD_OK;
 }
 
@@ -104,126 +96,75 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
 // anything there, every other bit is refused
 static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
 {
-    if (npairs < 1 || M < 2 || N < 2) {
-        set_error("pde: bad shape npairs=%d M=%d N=%d (need npairs >= 1, M, N >= 2)", npairs, M, N);
-        return SIGSVGD_E_BADARG;
-    }
-    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) {
-        set_error("pde: bad dtype %d", dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (n < 0 || n > 10) {
-        set_error("pde: bad dyadic order %d", n);
-        return SIGSVGD_E_BADARG;
-    }
-    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER) {
-        set_error("pde: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
-        return SIGSVGD_E_BADARG;
-    }
+    if (npairs < 1 || M < 2 || N < 2)
+        return bad_arg("pde: bad shape npairs=%d M=%d N=%d (need npairs >= 1, M, N >= 2)", npairs, M, N);
+    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("pde: bad dtype %d", dtype);
+    if (n < 0 || n > 10) return bad_arg("pde: bad dyadic order %d", n);
+    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER)
+        return bad_arg("pde: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
     return SIGSVGD_OK;
 }
 
-// the shape, order, kind and flag checks of the long-path Gram entry points (gram_long.hip): SIGSVGD_FLAG_NAIVE_SOLVER,
-// SIGSVGD_FLAG_SYM (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect) are taken, every other bit is refused
-static int check_long(int A, int B, int TX, int TY, int d, int n, int kind, unsigned flags)
+// The checks of the long-path entry points (gram_long.hip), each condition in one place.  check_long: the Gram mode's, which
+// every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
+// know.  SIGSVGD_FLAG_NAIVE_SOLVER, SIGSVGD_FLAG_SYM (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram
+// mode) are taken, every other bit is refused.
+static int check_long(const LongProblem &p, bool launch)
 {
-    if (A < 1 || B < 1 || TX < 2 || TY < 2 || d < 1) {
-        set_error("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", A, B, TX, TY, d);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind != SIGSVGD_STATIC_RBF && kind != SIGSVGD_STATIC_LINEAR) {
-        set_error("gram_long: bad static kernel kind %d", kind);
-        return SIGSVGD_E_BADARG;
-    }
-    if (n < 0 || n > 10) {
-        set_error("gram_long: bad dyadic order %d", n);
-        return SIGSVGD_E_BADARG;
-    }
+    if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
+    if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
+        return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
+                       p.TY, p.d);
+    if (p.kind != SIGSVGD_STATIC_RBF && p.kind != SIGSVGD_STATIC_LINEAR)
+        return bad_arg("gram_long: bad static kernel kind %d", p.kind);
+    if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
     const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X;
-    if (flags & ~known) {
-        set_error("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", flags & ~known);
-        return SIGSVGD_E_BADARG;
-    }
-    if ((flags & SIGSVGD_FLAG_SYM) && (A != B || TX != TY)) {
-        set_error("gram_long: sym backward needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
-        return SIGSVGD_E_BADARG;
-    }
-    return SIGSVGD_OK;
-}
-static int check_long_launch(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h, int n,
-                             int kind, unsigned flags, const void *K_out)
-{
-    if (!X || !Y || !K_out) {
-        set_error("gram_long: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_long(A, B, TX, TY, d, n, kind, flags);
-    if (rc) return rc;
-    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) {
-        set_error("gram_long: bad dtype %d", dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) {
-        set_error("gram_long: RBF static kernel needs inv_h > 0 (got %g)", inv_h);
-        return SIGSVGD_E_BADARG;
-    }
+    if (p.flags & ~known)
+        return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
+    if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
+        return bad_arg("gram_long: sym backward needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
+    if (launch && p.dtype != SIGSVGD_F32 && p.dtype != SIGSVGD_F64) return bad_arg("gram_long: bad dtype %d", p.dtype);
+    if (launch && p.kind == SIGSVGD_STATIC_RBF && !(p.inv_h > 0.0))
+        return bad_arg("gram_long: RBF static kernel needs inv_h > 0 (got %g)", p.inv_h);
     return SIGSVGD_OK;
 }
 
-// the two-sided entry points (gram_long.hip's two-sided mode): check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says:
-// one batch in both slots (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
-static int check_long2(int A, int B, int TX, int TY, int d, int n, int kind, unsigned flags, bool want_gradY)
+// the two-sided entry points: check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says: one batch in both slots
+// (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
+static int check_long2(const LongProblem &p, bool launch, bool want_gradY)
 {
-    const int rc = check_long(A, B, TX, TY, d, n, kind, flags);
+    const int rc = check_long(p, launch);
     if (rc) return rc;
-    if ((flags & SIGSVGD_FLAG_Y_IS_X) && (A != B || TX != TY)) {
-        set_error("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
-        return SIGSVGD_E_BADARG;
-    }
-    if ((flags & (SIGSVGD_FLAG_Y_IS_X | SIGSVGD_FLAG_SYM)) && want_gradY) {
-        set_error("gram_long2: Y_IS_X and SYM give the first-slot gradient only (gradY_out must be NULL)");
-        return SIGSVGD_E_BADARG;
-    }
+    if ((p.flags & SIGSVGD_FLAG_Y_IS_X) && (p.A != p.B || p.TX != p.TY))
+        return bad_arg("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
+    if ((p.flags & (SIGSVGD_FLAG_Y_IS_X | SIGSVGD_FLAG_SYM)) && want_gradY)
+        return bad_arg("gram_long2: Y_IS_X and SYM give the first-slot gradient only (gradY_out must be NULL)");
     return SIGSVGD_OK;
 }
 
-// the partial entry points (gram_long.hip's partial mode): check_long's for one batch in both slots, SIGSVGD_FLAG_FOLD_TILES
-// taken too, and the rank's tiles: tile_offset in [0, tile_stride)
-static int check_long_partial(int N, int T, int d, int n, int kind, unsigned flags, int tile_offset, int tile_stride)
+// the partial entry points: check_long's for one batch in both slots with SIGSVGD_FLAG_FOLD_TILES taken too, and the rank's
+// tiles: tile_offset in [0, tile_stride)
+static int check_long_partial(const LongProblem &p, bool launch, int tile_offset, int tile_stride)
 {
-    const int rc = check_long(N, N, T, T, d, n, kind, flags & ~(unsigned)SIGSVGD_FLAG_FOLD_TILES);
+    LongProblem q = p;
+    q.flags &= ~(unsigned)SIGSVGD_FLAG_FOLD_TILES;
+    const int rc = check_long(q, launch);
     if (rc) return rc;
-    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
-        set_error("gram_long_sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
-        return SIGSVGD_E_BADARG;
-    }
+    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride)
+        return bad_arg("gram_long_sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
     return SIGSVGD_OK;
 }
 
-// the checks of the paired entry points (gram_long.hip's paired mode): check_long's for one column of pairs, with
-// SIGSVGD_FLAG_NAIVE_SOLVER the only flag taken
-static int check_pair(int A, int TX, int TY, int d, int n, int kind, unsigned flags)
+// the paired entry points (B = 1: one column of pairs): the pointers, flags (SIGSVGD_FLAG_NAIVE_SOLVER only) and shape under
+// the mode's own name, then check_long's remaining conditions
+static int check_pair(const LongProblem &p, bool launch)
 {
-    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER) {
-        set_error("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
-        return SIGSVGD_E_BADARG;
-    }
-    if (A < 1 || TX < 2 || TY < 2 || d < 1) {
-        set_error("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", A, TX, TY, d);
-        return SIGSVGD_E_BADARG;
-    }
-    return check_long(A, 1, TX, TY, d, n, kind, flags);
-}
-static int check_pair_launch(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h, int n,
-                             int kind, unsigned flags, const void *K_out)
-{
-    if (!X || !Y || !K_out) {
-        set_error("pair: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_pair(A, TX, TY, d, n, kind, flags);
-    if (rc) return rc;
-    return check_long_launch(X, Y, A, 1, TX, TY, d, dtype, inv_h, n, kind, flags, K_out);
+    if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
+    if (p.flags & ~SIGSVGD_FLAG_NAIVE_SOLVER)
+        return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
+    if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
+        return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
+    return check_long(p, launch);
 }
 
 // ---- roctx ranges around the launches (the tracing hook of this path) ------------------------------
@@ -365,14 +306,9 @@ const char *sigsvgd_last_error(void) { return g_err; }
 int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, int static_kind, int want_grad,
                                  unsigned flags, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    if (static_kind != SIGSVGD_STATIC_RBF && static_kind != SIGSVGD_STATIC_LINEAR) {
-        set_error("bad static kernel kind %d", static_kind);
-        return SIGSVGD_E_BADARG;
-    }
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    if (static_kind != SIGSVGD_STATIC_RBF && static_kind != SIGSVGD_STATIC_LINEAR)
+        return bad_arg("bad static kernel kind %d", static_kind);
     // The largest plan of the launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B
     // the symmetric launch and -- gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch
     // and, when A == B, the symmetric one.
@@ -413,14 +349,8 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
 {
     int rc = check_common(X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
     if (rc) return rc;
-    if (!gradX_out) {
-        set_error("gradX_out == NULL (use sigsvgd_gram_fwd for forward only)");
-        return SIGSVGD_E_BADARG;
-    }
-    if ((flags & SIGSVGD_FLAG_Y_IS_X) && A != B) {
-        set_error("Y_IS_X needs A == B");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_fwd for forward only)");
+    if ((flags & SIGSVGD_FLAG_Y_IS_X) && A != B) return bad_arg("Y_IS_X needs A == B");
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out,
                   K_out, gradX_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     Range range("sigsvgd_gram_fwd_bwd");
@@ -434,10 +364,7 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
 {
     int rc = check_common(X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags, K_partial);
     if (rc) return rc;
-    if (!grad_partial) {
-        set_error("grad_partial == NULL");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!grad_partial) return bad_arg("grad_partial == NULL");
     GramProblem p{X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags | SIGSVGD_FLAG_Y_IS_X, grad_out,
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     const GramRoute r = gram_route(p, true);
@@ -445,10 +372,8 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
         set_error("sym_partial: shape/kernel outside the register-resident and quadrant kernels (need 3<=T<=128, d<=16, RBF)");
         return SIGSVGD_E_UNSUPPORTED;
     }
-    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride) {
-        set_error("sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
-        return SIGSVGD_E_BADARG;
-    }
+    if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride)
+        return bad_arg("sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
     Range range("sigsvgd_gram_sym_partial");
     const bool fold = (flags & SIGSVGD_FLAG_FOLD_TILES) != 0;
     return r == GramRoute::Fast ? fast_sym_partial(p, tile_offset, tile_stride, fold, grad_partial)
@@ -483,14 +408,10 @@ int sigsvgd_svgd_adam_step(const float *K, const float *score, const float *grad
                            float *v_out, const float *X_in, float *X_out, double lr, double beta1, double beta2, double eps,
                            float *exp_avg, float *exp_avg_sq, int *step_dev, void *stream)
 {
-    if (!exp_avg || !exp_avg_sq || !step_dev || !X_in || !X_out) {
-        set_error("svgd_adam_step: null state / particle pointer");
-        return SIGSVGD_E_BADARG;
-    }
-    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0)) {
-        set_error("svgd_adam_step: bad hyper-parameters beta1=%g beta2=%g eps=%g", beta1, beta2, eps);
-        return SIGSVGD_E_BADARG;
-    }
+    if (!exp_avg || !exp_avg_sq || !step_dev || !X_in || !X_out)
+        return bad_arg("svgd_adam_step: null state / particle pointer");
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
+        return bad_arg("svgd_adam_step: bad hyper-parameters beta1=%g beta2=%g eps=%g", beta1, beta2, eps);
     Range range("sigsvgd_svgd_adam_step");
     return phi_launch(K, score, grad_k, mask, N, D, v_out, X_in, X_out, (float)lr, nullptr,
                       static_cast<hipStream_t>(stream), exp_avg, exp_avg_sq, step_dev, lr, beta1, beta2, (float)eps);
@@ -499,23 +420,17 @@ int sigsvgd_svgd_adam_step(const float *K, const float *score, const float *grad
 int sigsvgd_vec_sqdist(const void *X, const void *Y, const void *XM, const void *YM, int A, int B, int D, int dtype,
                        void *sq_out, void *stream)
 {
-    if (!X || !Y || !sq_out || (XM == nullptr) != (YM == nullptr)) {
-        set_error("vec_sqdist: null pointer argument (XM and YM must both be given or both be NULL)");
-        return SIGSVGD_E_BADARG;
-    }
-    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64)) {
-        set_error("vec_sqdist: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
-        return SIGSVGD_E_BADARG;
-    }
+    if (!X || !Y || !sq_out || (XM == nullptr) != (YM == nullptr))
+        return bad_arg("vec_sqdist: null pointer argument (XM and YM must both be given or both be NULL)");
+    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64))
+        return bad_arg("vec_sqdist: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
     return vec_sqdist_launch(X, Y, XM, YM, A, B, D, dtype, sq_out, static_cast<hipStream_t>(stream));
 }
 
 int sigsvgd_vec_fused_workspace_bytes(int A, int B, int D, size_t *bytes)
 {
-    if (!bytes || A < 1 || B < 1 || D < 1) {
-        set_error("vec_fused_workspace_bytes: bad arguments A=%d B=%d D=%d", A, B, D);
-        return SIGSVGD_E_BADARG;
-    }
+    if (!bytes || A < 1 || B < 1 || D < 1)
+        return bad_arg("vec_fused_workspace_bytes: bad arguments A=%d B=%d D=%d", A, B, D);
     *bytes = vec_fused_workspace_bytes(A, B, D);
     return SIGSVGD_OK;
 }
@@ -524,18 +439,12 @@ int sigsvgd_vec_kernel_fused(const void *X, const void *Y, const void *XM, const
                              int B, int D, int dtype, int kind, double inv_h2, double grad_scale, void *K_out,
                              void *dK_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!X || !Y || (!K_out && !dK_out) || (XM == nullptr) != (YM == nullptr)) {
-        set_error("vec_kernel_fused: null pointer argument (XM and YM must both be given or both be NULL)");
-        return SIGSVGD_E_BADARG;
-    }
-    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64)) {
-        set_error("vec_kernel_fused: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind != SIGSVGD_VEC_GAUSSIAN && kind != SIGSVGD_VEC_IMQ && kind != SIGSVGD_VEC_UNIT) {
-        set_error("vec_kernel_fused: bad kind %d", kind);
-        return SIGSVGD_E_BADARG;
-    }
+    if (!X || !Y || (!K_out && !dK_out) || (XM == nullptr) != (YM == nullptr))
+        return bad_arg("vec_kernel_fused: null pointer argument (XM and YM must both be given or both be NULL)");
+    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64))
+        return bad_arg("vec_kernel_fused: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
+    if (kind != SIGSVGD_VEC_GAUSSIAN && kind != SIGSVGD_VEC_IMQ && kind != SIGSVGD_VEC_UNIT)
+        return bad_arg("vec_kernel_fused: bad kind %d", kind);
     if (!vec_fused_supported(D, dtype)) {
         set_error("vec_kernel_fused: fp32 with D <= 512 only (got dtype=%d D=%d); use sigsvgd_vec_sqdist + sigsvgd_vec_kernel",
                   dtype, D);
@@ -549,26 +458,14 @@ int sigsvgd_vec_kernel_fused(const void *X, const void *Y, const void *XM, const
 int sigsvgd_vec_kernel(const void *sq, const void *XM, const void *YM, const void *grad_out, int A, int B, int D,
                        int dtype, int kind, double inv_h2, double grad_scale, void *K_out, void *dK_out, void *stream)
 {
-    if (!sq || (!K_out && !dK_out) || (dK_out && (!XM || !YM))) {
-        set_error("vec_kernel: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
-    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64)) {
-        set_error("vec_kernel: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind != SIGSVGD_VEC_GAUSSIAN && kind != SIGSVGD_VEC_IMQ && kind != SIGSVGD_VEC_UNIT) {
-        set_error("vec_kernel: bad kind %d", kind);
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind == SIGSVGD_VEC_UNIT && (K_out || !dK_out)) {
-        set_error("vec_kernel: SIGSVGD_VEC_UNIT computes only dK_out (K_out must be NULL)");
-        return SIGSVGD_E_BADARG;
-    }
-    if (kind != SIGSVGD_VEC_UNIT && !(inv_h2 > 0.0)) {
-        set_error("vec_kernel: needs 1/h^2 > 0 (got %g)", inv_h2);
-        return SIGSVGD_E_BADARG;
-    }
+    if (!sq || (!K_out && !dK_out) || (dK_out && (!XM || !YM))) return bad_arg("vec_kernel: null pointer argument");
+    if (A < 1 || B < 1 || D < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64))
+        return bad_arg("vec_kernel: bad arguments A=%d B=%d D=%d dtype=%d", A, B, D, dtype);
+    if (kind != SIGSVGD_VEC_GAUSSIAN && kind != SIGSVGD_VEC_IMQ && kind != SIGSVGD_VEC_UNIT)
+        return bad_arg("vec_kernel: bad kind %d", kind);
+    if (kind == SIGSVGD_VEC_UNIT && (K_out || !dK_out))
+        return bad_arg("vec_kernel: SIGSVGD_VEC_UNIT computes only dK_out (K_out must be NULL)");
+    if (kind != SIGSVGD_VEC_UNIT && !(inv_h2 > 0.0)) return bad_arg("vec_kernel: needs 1/h^2 > 0 (got %g)", inv_h2);
     return vec_kgrad_launch(sq, XM, YM, grad_out, A, B, D, dtype, kind, inv_h2, grad_scale, K_out, dK_out,
                             static_cast<hipStream_t>(stream));
 }
@@ -586,10 +483,8 @@ int sigsvgd_obstacle_cost(const float *x, int N, int knots, int d, const float *
 int sigsvgd_signature(const void *X, int N, int L, int C, int depth, int basepoint, int dtype, void *out,
                       long long *channels, void *stream)
 {
-    if (N < 1 || L < 1 || C < 1 || depth < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64)) {
-        set_error("signature: bad arguments N=%d L=%d C=%d depth=%d dtype=%d", N, L, C, depth, dtype);
-        return SIGSVGD_E_BADARG;
-    }
+    if (N < 1 || L < 1 || C < 1 || depth < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64))
+        return bad_arg("signature: bad arguments N=%d L=%d C=%d depth=%d dtype=%d", N, L, C, depth, dtype);
     const long long ch = signature_channels(C, depth);
     if (ch < 0) {
         set_error("signature: C=%d depth=%d overflows", C, depth);
@@ -598,27 +493,18 @@ int sigsvgd_signature(const void *X, int N, int L, int C, int depth, int basepoi
     if (channels) *channels = ch;
     if (!out) {
         if (channels) return SIGSVGD_OK;
-        set_error("signature: out == NULL and channels == NULL");
-        return SIGSVGD_E_BADARG;
+        return bad_arg("signature: out == NULL and channels == NULL");
     }
-    if (!X) {
-        set_error("signature: X == NULL");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!X) return bad_arg("signature: X == NULL");
     return signature_launch(X, N, L, C, depth, basepoint, dtype, out, static_cast<hipStream_t>(stream));
 }
 
 int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L, int C, int depth, int basepoint, int dtype,
                                void *grad_X, void *stream)
 {
-    if (N < 1 || L < 1 || C < 1 || depth < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64)) {
-        set_error("signature_backward: bad arguments N=%d L=%d C=%d depth=%d dtype=%d", N, L, C, depth, dtype);
-        return SIGSVGD_E_BADARG;
-    }
-    if (!X || !grad_sig || !grad_X) {
-        set_error("signature_backward: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
+    if (N < 1 || L < 1 || C < 1 || depth < 1 || (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64))
+        return bad_arg("signature_backward: bad arguments N=%d L=%d C=%d depth=%d dtype=%d", N, L, C, depth, dtype);
+    if (!X || !grad_sig || !grad_X) return bad_arg("signature_backward: null pointer argument");
     const long long ch = signature_channels(C, depth);
     if (ch < 0) {
         set_error("signature_backward: C=%d depth=%d overflows", C, depth);
@@ -630,10 +516,7 @@ int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L
 
 int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags);
     if (rc) return rc;
     return pde_workspace(npairs, M, N, dyadic_order, want_grad ? 1 : 0, bytes);
@@ -642,10 +525,7 @@ int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int 
 int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags, void *K_out,
                     void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!G || !K_out) {
-        set_error("pde_fwd: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!G || !K_out) return bad_arg("pde_fwd: null pointer argument");
     const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd");
@@ -656,10 +536,7 @@ int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyad
 int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags,
                         const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!G || !K_out || !dG_out) {
-        set_error("pde_fwd_bwd: null pointer argument");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!G || !K_out || !dG_out) return bad_arg("pde_fwd_bwd: null pointer argument");
     const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd_bwd");
@@ -667,150 +544,132 @@ int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int 
                       workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+// ---- the long-path route (gram_long.hip): each entry point fills one LongProblem, checks it and hands it on ----------------
+// (a workspace or plan query fills the shape, order, kind and flags)
 int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
                                       unsigned flags, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_long(A, B, TX, TY, d, dyadic_order, static_kind, flags);
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_long(p, false);
     if (rc) return rc;
-    return long_workspace(A, B, TX, TY, d, dyadic_order, want_grad ? 1 : 0, bytes);
+    return long_workspace(p, want_grad ? 1 : 0, bytes);
 }
 
 int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                           int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
                           size_t workspace_bytes, void *stream)
 {
-    const int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr, K_out, nullptr, nullptr,
+                        workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_long(p, true);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd");
-    return long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
-                       false, nullptr, K_out, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return long_launch(p);
 }
 
 int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                               int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                               void *gradX_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
+                        nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_long(p, true);
     if (rc) return rc;
-    if (!gradX_out) {
-        set_error("gradX_out == NULL (use sigsvgd_gram_long_fwd for forward only)");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_long_fwd for forward only)");
     Range range("sigsvgd_gram_long_fwd_bwd");
-    return long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
-                       (flags & SIGSVGD_FLAG_SYM) != 0, grad_out, K_out, gradX_out, workspace, workspace_bytes,
-                       static_cast<hipStream_t>(stream));
+    return long_launch(p);
 }
 
 int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
                                  unsigned flags, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_pair(A, TX, TY, d, dyadic_order, static_kind, flags);
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_pair(p, false);
     if (rc) return rc;
-    return pair_workspace(A, TX, TY, d, dyadic_order, want_grad ? 1 : 0, bytes);
+    return pair_workspace(p, want_grad ? 1 : 0, bytes);
 }
 
 int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
                      int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
                      size_t workspace_bytes, void *stream)
 {
-    const int rc = check_pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr, K_out, nullptr, nullptr,
+                        workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_pair(p, true);
     if (rc) return rc;
     Range range("sigsvgd_pair_fwd");
-    return pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
-                       nullptr, K_out, nullptr, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return pair_launch(p);
 }
 
 int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
                          int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                          void *gradX_out, void *gradY_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    const int rc = check_pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
+    const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
+                        gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_pair(p, true);
     if (rc) return rc;
-    if (!gradX_out && !gradY_out) {
-        set_error("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!gradX_out && !gradY_out)
+        return bad_arg("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
     Range range("sigsvgd_pair_fwd_bwd");
-    return pair_launch(X, Y, A, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
-                       grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return pair_launch(p);
 }
 
 int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
                                        int want_gradX, int want_gradY, unsigned flags, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_long2(A, B, TX, TY, d, dyadic_order, static_kind, flags, want_gradY != 0);
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_long2(p, false, want_gradY != 0);
     if (rc) return rc;
-    return long2_workspace(A, B, TX, TY, d, dyadic_order, want_gradX ? 1 : 0, want_gradY ? 1 : 0,
-                           (flags & SIGSVGD_FLAG_Y_IS_X) != 0, bytes);
+    return long2_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
 
 int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                                int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                                void *gradX_out, void *gradY_out, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_long_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, K_out);
-    if (!rc) rc = check_long2(A, B, TX, TY, d, dyadic_order, static_kind, flags, gradY_out != nullptr);
+    const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
+                        gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_long2(p, true, gradY_out != nullptr);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
-    return long2_launch(X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind,
-                        (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, (flags & SIGSVGD_FLAG_SYM) != 0,
-                        (flags & SIGSVGD_FLAG_Y_IS_X) != 0, grad_out, K_out, gradX_out, gradY_out, workspace, workspace_bytes,
-                        static_cast<hipStream_t>(stream));
+    return long2_launch(p);
 }
 
 int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags, int tile_stride,
                                    int *tile_rows, int *tile_cols)
 {
-    if (!tile_rows || !tile_cols) {
-        set_error("gram_long_partial_plan: tile_rows / tile_cols == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, 0, tile_stride);
+    if (!tile_rows || !tile_cols) return bad_arg("gram_long_partial_plan: tile_rows / tile_cols == NULL");
+    const LongProblem p{nullptr, nullptr, N, N, T, T, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_long_partial(p, false, 0, tile_stride);
     if (rc) return rc;
-    return long_part_tiles(N, T, d, dyadic_order, tile_stride, tile_rows, tile_cols);
+    return long_part_tiles(p, tile_stride, tile_rows, tile_cols);
 }
 
 int sigsvgd_gram_long_partial_workspace_bytes(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags,
                                               int tile_offset, int tile_stride, size_t *bytes)
 {
-    if (!bytes) {
-        set_error("bytes == NULL");
-        return SIGSVGD_E_BADARG;
-    }
-    const int rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, tile_offset, tile_stride);
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, N, N, T, T, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_long_partial(p, false, tile_offset, tile_stride);
     if (rc) return rc;
-    return long_part_workspace(N, T, d, dyadic_order, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0, bytes);
+    return long_part_workspace(p, tile_offset, tile_stride, bytes);
 }
 
 int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h, int dyadic_order,
                                   int static_kind, unsigned flags, int tile_offset, int tile_stride, const void *grad_out,
                                   void *K_partial, double *grad_partial, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = check_long_launch(X, X, N, N, T, T, d, dtype, inv_h, dyadic_order, static_kind,
-                               flags & ~(unsigned)SIGSVGD_FLAG_FOLD_TILES, K_partial);
-    if (!rc) rc = check_long_partial(N, T, d, dyadic_order, static_kind, flags, tile_offset, tile_stride);
+    const LongProblem p{X, X, N, N, T, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_partial, grad_partial,
+                        nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const int rc = check_long_partial(p, true, tile_offset, tile_stride);
     if (rc) return rc;
-    if (!grad_partial) {
-        set_error("gram_long_sym_partial: grad_partial == NULL");
-        return SIGSVGD_E_BADARG;
-    }
+    if (!grad_partial) return bad_arg("gram_long_sym_partial: grad_partial == NULL");
     Range range("sigsvgd_gram_long_sym_partial");
-    return long_part_launch(X, N, T, d, dtype, inv_h, dyadic_order, static_kind, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
-                            (flags & SIGSVGD_FLAG_SYM) != 0, tile_offset, tile_stride, (flags & SIGSVGD_FLAG_FOLD_TILES) != 0,
-                            grad_out, K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return long_part_launch(p, tile_offset, tile_stride);
 }
 
 } // extern "C"

@@ -15,7 +15,7 @@
 // static kernel into the gradient of x_i:  gX_i[m] += w_ij sum_n dG[m][n] dk(x_m, y_n)/dx_m, with dG the 4-corner scatter of S
 // and dk/dx = -2 inv_h (x - y) k (RBF) or y (linear).  Lanes own points m; k is evaluated again there.  A work item is
 // (i, chunk of JC columns j): its pairs add into one [TX][d] fp64 slab in j order (the same lane always owns the same entry),
-// and long_reduce_kernel adds the slabs of a row i in chunk order.  No floating-point atomics: the bits depend on the inputs.
+// and long2_reduce_kernel adds the slabs of a row i in chunk order.  No floating-point atomics: the bits depend on the inputs.
 //
 // Paired mode (PAIRED): work item i is the one pair (X_i, Y_i), K_out[i] = k_sig(X_i, Y_i) from the
 // same fill and sweeps.  From the pair's one S the gradient pass writes gX_i straight into the caller's buffer, and the same
@@ -32,6 +32,12 @@
 // step.  The launch owns row tiles (TileMap, folded or cyclic), an item is a rectangle of R rows x JC columns of an owned
 // tile from its first row on, the slabs cover the owned tiles only, and long_part_reduce_kernel writes the fp64 partial
 // gradient of every row (zero where nothing arrived).  The host picks (R, JC) by search (part_pick).
+//
+// The per-pair solve (staging, fill, forward sweep, K store, reverse sweep) is written out in each of the three kernels, and K's
+// bit-identity across the modes rests on the copies staying equal.  One shared function (long_solve_pair over a PairSource, with
+// one two_sided_grad block) gave the same bits and the same registers, scratch and occupancy, but was measured slower on the
+// MI355X: forward-only launches by 1.5-4 %, the partial kernel by 1-1.4 %, ranges of run-medians apart
+// (profiles/long_shared_solve_ab.txt).  So the copies stay.
 #include <algorithm>
 #include <map>
 #include <mutex>
@@ -287,7 +293,8 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(Long2Args a)
 
             for (int j = jfirst; j < j1; ++j) {
                 const IO *yj = static_cast<const IO *>(a.Y) + (size_t)j * N * d;
-                // staging and fill: gram_long_kernel's, statement for statement (K must have its bits)
+                // staging and fill: gram_long_kernel's, statement for statement (K must have its bits); a copy because
+                // the shared helper measured slower (profiles/long_shared_solve_ab.txt)
                 auto stage_x = [&](int a0) {
                     for (int e = lane; e < (nrow + 1) * d; e += kWave) {
                         const int k = e / d;
@@ -435,7 +442,8 @@ __global__ __launch_bounds__(64) void gram_long_part_kernel(PartArgs a)
 
             for (int j = jfirst; j < j1; ++j) {
                 const IO *yj = static_cast<const IO *>(a.X) + (size_t)j * N * d;
-                // staging and fill: gram_long_kernel's, statement for statement (K must have its bits)
+                // staging and fill: gram_long_kernel's, statement for statement (K must have its bits); a copy because
+                // the shared helper measured slower (profiles/long_shared_solve_ab.txt)
                 auto stage_x = [&](int a0) {
                     for (int e = lane; e < (nrow + 1) * d; e += kWave) {
                         const int k = e / d;
@@ -521,18 +529,6 @@ __global__ void long_part_reduce_kernel(const double *rowpart, const double *col
     }
 }
 
-// gradX[i][e] = sum over the chunks of row i of partials[i][chunk][e], in chunk order (reproducible bits)
-template <typename IO>
-__global__ void long_reduce_kernel(const double *partials, IO *gradX, int A, int nchunks, int TD)
-{
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)A * TD) return;
-    const size_t i = idx / TD, e = idx % TD;
-    double s = 0.0;
-    for (int c = 0; c < nchunks; ++c) s += partials[(i * nchunks + c) * TD + e];
-    gradX[idx] = (IO)s;
-}
-
 // out[k][e] = sum over slab c of partials[k][c][e], c = 0 .. nslabs - 1 in order (reproducible bits).  skip > 0 (yx): row k's
 // column-side slab of its own diagonal tile, c = k / skip, was never written when k is that tile's first row (no pair i < k
 // in it), and is left out.
@@ -553,9 +549,22 @@ namespace {
 struct LongPlan : RingPlan {
     int JC, nchunks, grid;
     long long items;
-    size_t wsk_bytes, partial_bytes;
-    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes); }
+    size_t wsk_bytes, partial_bytes, col_bytes = 0; // the forward scratch, the row-side slabs, the column-side slabs
+    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes + col_bytes); }
 };
+
+// The grid of a launch of pl.items work items and its forward scratch: one wavefront per item up to what the device holds,
+// fewer (at least one) where their scratch would pass kRingMaxScratch; the scratch is rounded to 256 B.
+void long_set_grid(LongPlan &pl)
+{
+    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
+    if (pl.per_wave * (size_t)grid > kRingMaxScratch) { // (per_wave is 0 for forward-only launches)
+        grid = (long long)(kRingMaxScratch / pl.per_wave);
+        if (grid < 1) grid = 1;
+    }
+    pl.grid = (int)grid;
+    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
+}
 
 int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, LongPlan &pl, const char *who = "gram_long")
 {
@@ -567,13 +576,7 @@ int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, Long
     pl.JC = JC;
     pl.nchunks = (B + JC - 1) / JC;
     pl.items = (long long)A * pl.nchunks;
-    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
-    if (want_grad && pl.per_wave * (size_t)grid > kRingMaxScratch) {
-        grid = (long long)(kRingMaxScratch / pl.per_wave);
-        if (grid < 1) grid = 1;
-    }
-    pl.grid = (int)grid;
-    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
+    long_set_grid(pl);
     pl.partial_bytes = want_grad ? (size_t)A * pl.nchunks * M * d * sizeof(double) : 0;
     return SIGSVGD_OK;
 }
@@ -595,8 +598,6 @@ int pair_make_plan(int A, int M, int N, int d, int n, int want_grad, LongPlan &p
 // (column side: tile rows 0 .. its own, row side: its own .. nti - 1) in one array.
 struct Long2Plan : LongPlan {
     int IC, nti;
-    size_t col_bytes;
-    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes + col_bytes); }
 };
 
 int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, bool want_col, bool yx, Long2Plan &pl)
@@ -624,13 +625,7 @@ int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, boo
     pl.JC = JC;
     pl.nti = tiles(A, IC);
     pl.nchunks = tiles(B, JC);
-    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
-    if (want_grad && pl.per_wave * (size_t)grid > kRingMaxScratch) {
-        grid = (long long)(kRingMaxScratch / pl.per_wave);
-        if (grid < 1) grid = 1;
-    }
-    pl.grid = (int)grid;
-    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
+    long_set_grid(pl);
     const size_t rowslabs = yx ? (want_grad ? pl.nti + 1 : 0) : (want_row ? pl.nchunks : 0);
     pl.partial_bytes = (size_t)A * rowslabs * M * d * sizeof(double);
     pl.col_bytes = !yx && want_col ? (size_t)B * pl.nti * N * d * sizeof(double) : 0;
@@ -741,8 +736,6 @@ struct PartPlan : LongPlan {
     int R;
     TileMap tm;
     long long nfull;
-    size_t col_bytes;
-    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes + col_bytes); }
 };
 
 // the plan of rank `off` of `stride`; off < 0: the tile size only (sigsvgd_gram_long_partial_plan)
@@ -757,288 +750,186 @@ int part_make_plan(int A, int T, int d, int n, int off, int stride, bool fold, P
     pl.items = sh.items;
     pl.nfull = sh.nfull;
     pl.nchunks = 0;
-    long long grid = pl.resident < pl.items ? pl.resident : pl.items;
-    if (pl.per_wave * (size_t)grid > kRingMaxScratch) {
-        grid = (long long)(kRingMaxScratch / pl.per_wave);
-        if (grid < 1) grid = 1;
-    }
-    pl.grid = (int)grid;
-    pl.wsk_bytes = ((pl.per_wave * (size_t)grid) + 255) & ~(size_t)255;
+    long_set_grid(pl);
     const size_t TD = (size_t)T * d;
     pl.col_bytes = (size_t)sh.tm.start(sh.tm.owned, A, pl.R, 1) * TD * sizeof(double);
     pl.partial_bytes = (size_t)sh.slabs * TD * sizeof(double) - pl.col_bytes;
     return SIGSVGD_OK;
 }
 
-// the arguments of a Gram launch (B columns) or a paired one (B = 1, no sym), from the plan and the caller's workspace
-// (checked against `need`, the plan's total; the Gram mode's slabs follow the forward scratch)
-int long_args(const char *who, const LongPlan &pl, size_t need, void *ws, size_t ws_bytes, const void *X, const void *Y,
-              const void *grad_out, void *K_out, int A, int B, int M, int N, int d, int n, bool sym, double inv_h, LongArgs &a)
+// The arguments every mode takes from the problem, its plan and the caller's workspace (checked against the plan's total; the
+// row-side slabs follow the forward scratch).  B: the columns of the launch (1 in the paired mode).
+int long_args(const char *who, const LongPlan &pl, const LongProblem &p, int B, LongArgs &a)
 {
     unsigned char *base = nullptr;
-    const int rc = ring_ws_base(who, ws, ws_bytes, need, base);
+    const int rc = ring_ws_base(who, p.ws, p.ws_bytes, pl.total(), base);
     if (rc) return rc;
-    a.X = X; a.Y = Y; a.grad_out = grad_out; a.K_out = K_out;
+    a.X = p.X; a.Y = p.Y; a.grad_out = p.grad_out; a.K_out = p.K_out;
     a.wsk = reinterpret_cast<float *>(base);
     a.partials = pl.partial_bytes ? reinterpret_cast<double *>(base + pl.wsk_bytes) : nullptr;
     a.wsk_per_block = pl.per_wave / sizeof(float);
-    a.A = A; a.B = B; a.M = M; a.N = N; a.d = d; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
+    a.A = p.A; a.B = B; a.M = p.TX; a.N = p.TY; a.d = p.d; a.n = p.n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
     a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = pl.JC; a.nchunks = pl.nchunks;
-    a.sym = sym ? 1 : 0; a.items = pl.items; a.inv_h = inv_h;
+    a.sym = (p.flags & SIGSVGD_FLAG_SYM) ? 1 : 0; a.items = pl.items; a.inv_h = p.inv_h;
     a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
     return SIGSVGD_OK;
 }
+// the column-side slabs of the two-sided and partial modes: behind the forward scratch and the row-side slabs
+double *long_colpart(const LongPlan &pl, const LongArgs &a)
+{
+    return pl.col_bytes ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(a.wsk) + pl.wsk_bytes + pl.partial_bytes)
+                        : nullptr;
+}
+bool long_naive(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0; }
+bool long_yx(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_Y_IS_X) != 0; }
+bool long_fold(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_FOLD_TILES) != 0; }
 
+// the kernel families of this file for ring_launch (ring_sweep.h)
 template <bool PAIRED>
-using LongArgsOf = std::conditional_t<PAIRED, PairArgs, LongArgs>;
+struct LongFamily {
+    using Args = std::conditional_t<PAIRED, PairArgs, LongArgs>;
+    static constexpr bool has_kind = true, has_fwd_only = true;
+    static constexpr const char *attr_failed = PAIRED ? "hipFuncSetAttribute(gram_long paired)"
+                                                      : "hipFuncSetAttribute(gram_long)";
+    static constexpr const char *launch_failed = PAIRED ? "launch gram_long_kernel (paired)" : "launch gram_long_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>; }
+};
+struct Long2Family {
+    using Args = Long2Args;
+    static constexpr bool has_kind = true, has_fwd_only = true;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2)", *launch_failed = "launch gram_long2_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, GRAD, KIND>; }
+};
+struct PartFamily { // (always with the gradient)
+    using Args = PartArgs;
+    static constexpr bool has_kind = true, has_fwd_only = false;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long_part)",
+                                *launch_failed = "launch gram_long_part_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel()
+    {
+        static_assert(GRAD, "gram_long_part_kernel has no forward-only form");
+        return &gram_long_part_kernel<IO, NAIVE, KIND>;
+    }
+};
 
-template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED>
-hipError_t long_launch_one(const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
-{
-    const hipError_t e = raise_lds_limit<&gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>>();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
-    return hipSuccess;
-}
-template <typename IO, int KIND, bool PAIRED>
-hipError_t long_dispatch2(bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
-{
-    if (naive)
-        return grad ? long_launch_one<IO, true, true, KIND, PAIRED>(pl, stream, a)
-                    : long_launch_one<IO, true, false, KIND, PAIRED>(pl, stream, a);
-    return grad ? long_launch_one<IO, false, true, KIND, PAIRED>(pl, stream, a)
-                : long_launch_one<IO, false, false, KIND, PAIRED>(pl, stream, a);
-}
-template <typename IO, bool PAIRED = false>
-hipError_t long_dispatch(int kind, bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const LongArgsOf<PAIRED> &a)
-{
-    return kind == SIGSVGD_STATIC_RBF ? long_dispatch2<IO, SIGSVGD_STATIC_RBF, PAIRED>(naive, grad, pl, stream, a)
-                                      : long_dispatch2<IO, SIGSVGD_STATIC_LINEAR, PAIRED>(naive, grad, pl, stream, a);
-}
-
-// the two-sided kernel's launch
-template <typename IO, bool NAIVE, bool GRAD, int KIND>
-hipError_t long2_launch_one(const LongPlan &pl, hipStream_t stream, const Long2Args &a)
-{
-    const hipError_t e = raise_lds_limit<&gram_long2_kernel<IO, NAIVE, GRAD, KIND>>();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram_long2_kernel<IO, NAIVE, GRAD, KIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
-    return hipSuccess;
-}
-template <typename IO, int KIND>
-hipError_t long2_dispatch2(bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const Long2Args &a)
-{
-    if (naive)
-        return grad ? long2_launch_one<IO, true, true, KIND>(pl, stream, a)
-                    : long2_launch_one<IO, true, false, KIND>(pl, stream, a);
-    return grad ? long2_launch_one<IO, false, true, KIND>(pl, stream, a)
-                : long2_launch_one<IO, false, false, KIND>(pl, stream, a);
-}
-template <typename IO>
-hipError_t long2_dispatch(int kind, bool naive, bool grad, const LongPlan &pl, hipStream_t stream, const Long2Args &a)
-{
-    return kind == SIGSVGD_STATIC_RBF ? long2_dispatch2<IO, SIGSVGD_STATIC_RBF>(naive, grad, pl, stream, a)
-                                      : long2_dispatch2<IO, SIGSVGD_STATIC_LINEAR>(naive, grad, pl, stream, a);
-}
-
-template <typename IO>
-hipError_t long2_reduce(hipStream_t stream, const double *partials, void *out, int rows, int nslabs, int TD, int skip)
+// out (the launch's dtype) = the sums of `rows` rows' slabs, long2_reduce_kernel
+int long2_reduce(const LongProblem &p, const double *partials, void *out, int rows, int nslabs, int TD, int skip,
+                 const char *what)
 {
     const int bs = 256;
     const unsigned gs = (unsigned)(((size_t)rows * TD + bs - 1) / bs);
-    hipLaunchKernelGGL(long2_reduce_kernel<IO>, dim3(gs), dim3(bs), 0, stream, partials, static_cast<IO *>(out), rows, nslabs,
-                       TD, skip);
-    return hipGetLastError();
+    if (p.dtype == SIGSVGD_F64)
+        hipLaunchKernelGGL(long2_reduce_kernel<double>, dim3(gs), dim3(bs), 0, p.stream, partials, static_cast<double *>(out),
+                           rows, nslabs, TD, skip);
+    else
+        hipLaunchKernelGGL(long2_reduce_kernel<float>, dim3(gs), dim3(bs), 0, p.stream, partials, static_cast<float *>(out),
+                           rows, nslabs, TD, skip);
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? hip_fail(e, what) : SIGSVGD_OK;
 }
 } // namespace
 
-// bytes of the launch's workspace (0 for forward-only launches: the forward sweep keeps nothing)
-int long_workspace(int A, int B, int M, int N, int d, int n, int want_grad, size_t *bytes)
+// ---- workspace queries and launches; the argument checks are the entry points' (capi.hip) ----------------------------------
+// Bytes of a launch's workspace (0 for forward-only launches: the forward sweep keeps nothing; 0 for a rank of the partial mode
+// that owns no tile).  The queries read the problem's shape, order and flags only.
+int long_workspace(const LongProblem &p, int want_grad, size_t *bytes)
 {
-    LongPlan pl;
-    const int rc = long_make_plan(A, B, M, N, d, n, want_grad, pl);
-    if (rc) return rc;
-    *bytes = pl.total();
-    return SIGSVGD_OK;
+    return ring_plan_total<LongPlan>(
+        bytes, [&](LongPlan &pl) { return long_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_grad, pl); });
 }
-
-// the argument checks are the entry points' (capi.hip); gradX_out == NULL: forward only
-int long_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
-                bool naive, bool sym, const void *grad_out, void *K_out, void *gradX_out, void *ws, size_t ws_bytes,
-                hipStream_t stream)
+int pair_workspace(const LongProblem &p, int want_grad, size_t *bytes)
 {
-    const int want_grad = gradX_out != nullptr;
-    LongPlan pl;
-    LongArgs a;
-    int rc = long_make_plan(A, B, M, N, d, n, want_grad, pl);
-    if (!rc) rc = long_args("gram_long", pl, pl.total(), ws, ws_bytes, X, Y, grad_out, K_out, A, B, M, N, d, n, sym, inv_h, a);
-    if (rc) return rc;
-    hipError_t e = dtype == SIGSVGD_F64 ? long_dispatch<double>(kind, naive, want_grad != 0, pl, stream, a)
-                                        : long_dispatch<float>(kind, naive, want_grad != 0, pl, stream, a);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long)");
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch gram_long_kernel");
-    if (want_grad) {
-        const int TD = M * d;
-        const size_t tot = (size_t)A * TD;
-        const int bs = 256;
-        const unsigned gs = (unsigned)((tot + bs - 1) / bs);
-        if (dtype == SIGSVGD_F64)
-            hipLaunchKernelGGL(long_reduce_kernel<double>, dim3(gs), dim3(bs), 0, stream, a.partials,
-                               static_cast<double *>(gradX_out), A, pl.nchunks, TD);
-        else
-            hipLaunchKernelGGL(long_reduce_kernel<float>, dim3(gs), dim3(bs), 0, stream, a.partials,
-                               static_cast<float *>(gradX_out), A, pl.nchunks, TD);
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "launch long_reduce_kernel");
-    }
-    return SIGSVGD_OK;
+    return ring_plan_total<LongPlan>(
+        bytes, [&](LongPlan &pl) { return pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl); });
 }
-
-// bytes of a paired launch's workspace (0 for forward-only launches)
-int pair_workspace(int A, int M, int N, int d, int n, int want_grad, size_t *bytes)
+int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes)
 {
-    LongPlan pl;
-    const int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
-    if (rc) return rc;
-    *bytes = pl.total();
-    return SIGSVGD_OK;
+    return ring_plan_total<Long2Plan>(bytes, [&](Long2Plan &pl) {
+        return long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl);
+    });
 }
-
-// the argument checks are the entry points' (capi.hip); gradX_out and gradY_out both NULL: forward only
-int pair_launch(const void *X, const void *Y, int A, int M, int N, int d, int dtype, double inv_h, int n, int kind, bool naive,
-                const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws, size_t ws_bytes,
-                hipStream_t stream)
+int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes)
 {
-    const int want_grad = gradX_out != nullptr || gradY_out != nullptr;
-    LongPlan pl;
-    PairArgs a;
-    int rc = pair_make_plan(A, M, N, d, n, want_grad, pl);
-    if (!rc) rc = long_args("pair", pl, pl.total(), ws, ws_bytes, X, Y, grad_out, K_out, A, 1, M, N, d, n, false, inv_h, a);
-    if (rc) return rc;
-    a.gradX = gradX_out; a.gradY = gradY_out;
-    const hipError_t e = dtype == SIGSVGD_F64 ? long_dispatch<double, true>(kind, naive, want_grad != 0, pl, stream, a)
-                                              : long_dispatch<float, true>(kind, naive, want_grad != 0, pl, stream, a);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long paired)");
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) return hip_fail(le, "launch gram_long_kernel (paired)");
-    return SIGSVGD_OK;
+    return ring_plan_total<PartPlan>(
+        bytes, [&](PartPlan &pl) { return part_make_plan(p.A, p.TX, p.d, p.n, off, stride, long_fold(p), pl); });
 }
-
-// bytes of a two-sided launch's workspace (0 for forward-only launches)
-int long2_workspace(int A, int B, int M, int N, int d, int n, int want_gradX, int want_gradY, bool yx, size_t *bytes)
-{
-    Long2Plan pl;
-    const int rc = long2_make_plan(A, B, M, N, d, n, want_gradX != 0, want_gradY != 0, yx, pl);
-    if (rc) return rc;
-    *bytes = pl.total();
-    return SIGSVGD_OK;
-}
-
-// the argument checks are the entry point's (capi.hip); gradX_out and gradY_out both NULL: forward only.  yx: A == B,
-// M == N, no gradY_out; gradX_out then gets both sides of every unordered pair.
-int long2_launch(const void *X, const void *Y, int A, int B, int M, int N, int d, int dtype, double inv_h, int n, int kind,
-                 bool naive, bool sym, bool yx, const void *grad_out, void *K_out, void *gradX_out, void *gradY_out, void *ws,
-                 size_t ws_bytes, hipStream_t stream)
-{
-    const bool want_row = gradX_out != nullptr, want_col = gradY_out != nullptr || (yx && want_row);
-    const bool want_grad = want_row || want_col;
-    Long2Plan pl;
-    Long2Args a;
-    int rc = long2_make_plan(A, B, M, N, d, n, want_row, gradY_out != nullptr, yx, pl);
-    if (!rc) rc = long_args("gram_long", pl, pl.total(), ws, ws_bytes, X, Y, grad_out, K_out, A, B, M, N, d, n, sym, inv_h, a);
-    if (rc) return rc;
-    a.colpart = pl.col_bytes // (behind the forward scratch and the row slabs)
-                    ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(a.wsk) + pl.wsk_bytes + pl.partial_bytes)
-                    : nullptr;
-    a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
-    hipError_t e = dtype == SIGSVGD_F64 ? long2_dispatch<double>(kind, naive, want_grad, pl, stream, a)
-                                        : long2_dispatch<float>(kind, naive, want_grad, pl, stream, a);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long2)");
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch gram_long2_kernel");
-    const bool f64 = dtype == SIGSVGD_F64;
-    if (want_row) { // yx: a row's nti + 1 slabs, column side first
-        const int nslabs = yx ? pl.nti + 1 : pl.nchunks, skip = yx ? pl.IC : 0;
-        e = f64 ? long2_reduce<double>(stream, a.partials, gradX_out, A, nslabs, M * d, skip)
-                : long2_reduce<float>(stream, a.partials, gradX_out, A, nslabs, M * d, skip);
-        if (e != hipSuccess) return hip_fail(e, "launch long2_reduce_kernel (rows)");
-    }
-    if (gradY_out) {
-        e = f64 ? long2_reduce<double>(stream, a.colpart, gradY_out, B, pl.nti, N * d, 0)
-                : long2_reduce<float>(stream, a.colpart, gradY_out, B, pl.nti, N * d, 0);
-        if (e != hipSuccess) return hip_fail(e, "launch long2_reduce_kernel (columns)");
-    }
-    return SIGSVGD_OK;
-}
-
 // the partial mode's tile: R rows x JC columns, the same for every rank of `stride` (host only)
-int long_part_tiles(int A, int T, int d, int n, int stride, int *R, int *JC)
+int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC)
 {
     PartPlan pl;
-    const int rc = part_make_plan(A, T, d, n, -1, stride, true, pl);
+    const int rc = part_make_plan(p.A, p.TX, p.d, p.n, -1, stride, true, pl);
     if (rc) return rc;
     *R = pl.R;
     *JC = pl.JC;
     return SIGSVGD_OK;
 }
 
-// bytes of the workspace of rank `off` of `stride` (0 for a rank that owns no tile)
-int long_part_workspace(int A, int T, int d, int n, int off, int stride, bool fold, size_t *bytes)
+// gradX_out == NULL: forward only
+int long_launch(const LongProblem &p)
 {
-    PartPlan pl;
-    const int rc = part_make_plan(A, T, d, n, off, stride, fold, pl);
+    const bool want_grad = p.gradX_out != nullptr;
+    LongPlan pl;
+    LongArgs a;
+    int rc = long_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_grad, pl);
+    if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
+    if (!rc) rc = ring_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
+    if (!rc && want_grad) // a row's slabs in chunk order
+        rc = long2_reduce(p, a.partials, p.gradX_out, p.A, pl.nchunks, p.TX * p.d, 0, "launch long2_reduce_kernel (rows)");
+    return rc;
+}
+
+// gradX_out and gradY_out both NULL: forward only
+int pair_launch(const LongProblem &p)
+{
+    const bool want_grad = p.gradX_out != nullptr || p.gradY_out != nullptr;
+    LongPlan pl;
+    PairArgs a;
+    int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
+    if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
-    *bytes = pl.total();
-    return SIGSVGD_OK;
+    a.gradX = p.gradX_out; a.gradY = p.gradY_out;
+    return ring_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
 }
 
-namespace {
-template <typename IO, bool NAIVE, int KIND>
-hipError_t part_launch_one(const PartPlan &pl, hipStream_t stream, const PartArgs &a)
+// gradX_out and gradY_out both NULL: forward only.  Y_IS_X: A == B, TX == TY, no gradY_out; gradX_out then gets both sides of
+// every unordered pair.
+int long2_launch(const LongProblem &p)
 {
-    const hipError_t e = raise_lds_limit<&gram_long_part_kernel<IO, NAIVE, KIND>>();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram_long_part_kernel<IO, NAIVE, KIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
-    return hipSuccess;
+    const bool yx = long_yx(p), want_row = p.gradX_out != nullptr, want_col = p.gradY_out != nullptr || (yx && want_row);
+    Long2Plan pl;
+    Long2Args a;
+    int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_row, p.gradY_out != nullptr, yx, pl);
+    if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
+    if (rc) return rc;
+    a.colpart = long_colpart(pl, a);
+    a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
+    rc = ring_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
+    if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
+        rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,
+                          "launch long2_reduce_kernel (rows)");
+    if (!rc && p.gradY_out)
+        rc = long2_reduce(p, a.colpart, p.gradY_out, p.B, pl.nti, p.TY * p.d, 0, "launch long2_reduce_kernel (columns)");
+    return rc;
 }
-template <typename IO>
-hipError_t part_dispatch(int kind, bool naive, const PartPlan &pl, hipStream_t stream, const PartArgs &a)
-{
-    if (kind == SIGSVGD_STATIC_RBF)
-        return naive ? part_launch_one<IO, true, SIGSVGD_STATIC_RBF>(pl, stream, a)
-                     : part_launch_one<IO, false, SIGSVGD_STATIC_RBF>(pl, stream, a);
-    return naive ? part_launch_one<IO, true, SIGSVGD_STATIC_LINEAR>(pl, stream, a)
-                 : part_launch_one<IO, false, SIGSVGD_STATIC_LINEAR>(pl, stream, a);
-}
-} // namespace
 
-// the argument checks are the entry point's (capi.hip).  K_partial gets the owned pairs and their mirror images, grad_partial
-// (fp64) is overwritten whole; a rank that owns no tile launches the reduction alone, which writes zeros.
-int long_part_launch(const void *X, int A, int T, int d, int dtype, double inv_h, int n, int kind, bool naive, bool sym,
-                     int off, int stride, bool fold, const void *grad_out, void *K_partial, double *grad_partial, void *ws,
-                     size_t ws_bytes, hipStream_t stream)
+// The share of rank `off` of `stride` (Y = X: B = A, TY = TX).  K_out gets the owned pairs and their mirror images, gradX_out
+// (fp64 whatever the dtype) is overwritten whole; a rank that owns no tile launches the reduction alone, which writes zeros.
+int long_part_launch(const LongProblem &p, int off, int stride)
 {
     PartPlan pl;
     PartArgs a;
-    int rc = part_make_plan(A, T, d, n, off, stride, fold, pl);
-    if (!rc)
-        rc = long_args("gram_long_sym_partial", pl, pl.total(), ws, ws_bytes, X, X, grad_out, K_partial, A, A, T, T, d, n, sym,
-                       inv_h, a);
+    int rc = part_make_plan(p.A, p.TX, p.d, p.n, off, stride, long_fold(p), pl);
+    if (!rc) rc = long_args("gram_long_sym_partial", pl, p, p.A, a);
     if (rc) return rc;
-    a.colpart = pl.col_bytes // (behind the forward scratch and the row-side slabs)
-                    ? reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(a.wsk) + pl.wsk_bytes + pl.partial_bytes)
-                    : nullptr;
+    a.colpart = long_colpart(pl, a);
     a.tm = pl.tm; a.R = pl.R; a.nfull = pl.nfull;
-    if (pl.items > 0) {
-        hipError_t e = dtype == SIGSVGD_F64 ? part_dispatch<double>(kind, naive, pl, stream, a)
-                                            : part_dispatch<float>(kind, naive, pl, stream, a);
-        if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(gram_long_part)");
-        e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "launch gram_long_part_kernel");
-    }
-    hipLaunchKernelGGL(long_part_reduce_kernel, dim3(A), dim3(256), 0, stream, a.partials, a.colpart, grad_partial, A, T * d,
-                       pl.R, pl.JC, pl.tm);
+    if (pl.items > 0) rc = ring_launch<PartFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
+    if (rc) return rc;
+    hipLaunchKernelGGL(long_part_reduce_kernel, dim3(p.A), dim3(256), 0, p.stream, a.partials, a.colpart,
+                       static_cast<double *>(p.gradX_out), p.A, p.TX * p.d, pl.R, pl.JC, pl.tm);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch long_part_reduce_kernel");
     return SIGSVGD_OK;

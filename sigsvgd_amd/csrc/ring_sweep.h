@@ -1,5 +1,6 @@
-// The long-path PDE sweep shared by sig_pde_kernel (sig_pde.hip) and gram_long_kernel (gram_long.hip), DESIGN.md sections
-// 5.9 - 5.11: the ring plan's geometry, the forward and reverse sweeps of one pair, and the reader of the pair's coarse S.
+// The long-path PDE sweep shared by sig_pde_kernel (sig_pde.hip) and the kernels of gram_long.hip, DESIGN.md sections
+// 5.9 - 5.13: the ring plan's geometry, the launch of a kernel family on it, the forward and reverse sweeps of one pair, and
+// the reader of the pair's coarse S.
 //
 // One wavefront per pair; the refined P x Q grid is swept in bands of 64 rows, one row per lane, anti-diagonal by
 // anti-diagonal (lane l is at column s - l on step s); the band's boundary row is in LDS.  The band's fp64 increments live in
@@ -70,6 +71,61 @@ int ring_ws_base(const char *who, void *ws, size_t ws_bytes, size_t need, unsign
         return SIGSVGD_E_WORKSPACE;
     }
     base = need ? reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255) : nullptr;
+    return SIGSVGD_OK;
+}
+
+// a workspace query: *bytes = the total() of the plan that make(plan) fills
+template <typename Plan, typename Make>
+int ring_plan_total(size_t *bytes, Make &&make)
+{
+    Plan pl;
+    const int rc = make(pl);
+    if (rc) return rc;
+    *bytes = pl.total();
+    return SIGSVGD_OK;
+}
+
+// ---- the launch of a kernel family on the ring sweep -----------------------------------------------------------------------
+// A family F names its kernels: F::Args (the kernel's one argument), F::kernel<IO, NAIVE, GRAD, KIND>() (the instantiation's
+// address), F::has_kind (false: one kernel for every static kernel, KIND = 0), F::has_fwd_only (false: GRAD = true only) and
+// the two texts of a failure.  ring_launch maps the runtime (dtype, kind, naive, grad) to the instantiation, raises its LDS
+// limit and launches pl.grid wavefronts with pl.lds bytes of LDS each; only instantiations the family has are named.
+template <typename F, typename IO, bool NAIVE, bool GRAD, int KIND, typename Plan>
+hipError_t ring_launch_one(const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    constexpr auto kernel = F::template kernel<IO, NAIVE, GRAD, KIND>();
+    const hipError_t e = raise_lds_limit<kernel>();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
+    return hipSuccess;
+}
+template <typename F, typename IO, int KIND, typename Plan>
+hipError_t ring_launch_solver(bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if constexpr (F::has_fwd_only) {
+        if (!grad)
+            return naive ? ring_launch_one<F, IO, true, false, KIND>(pl, stream, a)
+                         : ring_launch_one<F, IO, false, false, KIND>(pl, stream, a);
+    }
+    return naive ? ring_launch_one<F, IO, true, true, KIND>(pl, stream, a)
+                 : ring_launch_one<F, IO, false, true, KIND>(pl, stream, a);
+}
+template <typename F, typename IO, typename Plan>
+hipError_t ring_launch_kind(int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if constexpr (F::has_kind) {
+        if (kind != SIGSVGD_STATIC_RBF) return ring_launch_solver<F, IO, SIGSVGD_STATIC_LINEAR>(naive, grad, pl, stream, a);
+    }
+    return ring_launch_solver<F, IO, SIGSVGD_STATIC_RBF>(naive, grad, pl, stream, a);
+}
+template <typename F, typename Plan>
+int ring_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    hipError_t e = dtype == SIGSVGD_F64 ? ring_launch_kind<F, double>(kind, naive, grad, pl, stream, a)
+                                        : ring_launch_kind<F, float>(kind, naive, grad, pl, stream, a);
+    if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, F::launch_failed);
     return SIGSVGD_OK;
 }
 

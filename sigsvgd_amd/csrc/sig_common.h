@@ -233,6 +233,23 @@ struct GramProblem {
     hipStream_t stream;
 };
 
+// A launch of the long-path route (gram_long.hip): the Gram and two-sided modes, the paired mode (B unused) and the partial
+// mode (Y = X, B = A, TY = TX; gradX_out is the fp64 partial gradient).  The workspace queries read shape, order and flags only.
+struct LongProblem {
+    const void *X, *Y;
+    int A, B, TX, TY, d, dtype;
+    double inv_h;
+    int n;            // dyadic order
+    int kind;         // SIGSVGD_STATIC_*
+    unsigned flags;
+    const void *grad_out; // nullable
+    void *K_out;
+    void *gradX_out, *gradY_out; // nullable; both NULL => forward only
+    void *ws;
+    size_t ws_bytes;
+    hipStream_t stream;
+};
+
 // fixed-order reduction of the gradient partial sums shared by the register-resident and the quadrant kernel -- gram_fast.hip
 // Which row tiles a launch owns and the order it enumerates them in (kq = 0 .. owned-1).  A full launch owns all of
 // them (off 0, stride 1).  The sharded partial solve of rank `off` of `stride` owns the tiles off + k*stride (cyclic), or

@@ -85,8 +85,10 @@ namespace {
 struct PdePlan : RingPlan {
     int grid;
     size_t ws_bytes;
+    size_t total() const { return ring_ws_total(ws_bytes); }
 };
 
+// (not gram_long.hip's long_set_grid: this scratch is sized for 8 waves per CU and does not shrink with the grid)
 int pde_make_plan(int npairs, int M, int N, int n, int want_grad, PdePlan &pl)
 {
     const int rc = ring_make_plan(M, N, n, want_grad, 0, "pde", pl);
@@ -106,30 +108,20 @@ int pde_make_plan(int npairs, int M, int N, int n, int want_grad, PdePlan &pl)
     return SIGSVGD_OK;
 }
 
-template <typename IO, bool NAIVE, bool GRAD>
-hipError_t pde_launch_one(const PdePlan &pl, hipStream_t stream, const PdeArgs &a)
-{
-    const hipError_t e = raise_lds_limit<&sig_pde_kernel<IO, NAIVE, GRAD>>();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sig_pde_kernel<IO, NAIVE, GRAD>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
-    return hipSuccess;
-}
-template <typename IO>
-hipError_t pde_dispatch(bool naive, bool grad, const PdePlan &pl, hipStream_t stream, const PdeArgs &a)
-{
-    if (naive) return grad ? pde_launch_one<IO, true, true>(pl, stream, a) : pde_launch_one<IO, true, false>(pl, stream, a);
-    return grad ? pde_launch_one<IO, false, true>(pl, stream, a) : pde_launch_one<IO, false, false>(pl, stream, a);
-}
+// the kernel family for ring_launch (ring_sweep.h): one kernel, whatever static kernel made the grid
+struct PdeFamily {
+    using Args = PdeArgs;
+    static constexpr bool has_kind = false, has_fwd_only = true;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(sig_pde)", *launch_failed = "launch sig_pde_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &sig_pde_kernel<IO, NAIVE, GRAD>; }
+};
 } // namespace
 
 // bytes of the launch's scratch (0 for forward-only launches: the forward sweep keeps nothing)
 int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes)
 {
-    PdePlan pl;
-    const int rc = pde_make_plan(npairs, M, N, n, want_grad, pl);
-    if (rc) return rc;
-    *bytes = ring_ws_total(pl.ws_bytes);
-    return SIGSVGD_OK;
+    return ring_plan_total<PdePlan>(bytes, [&](PdePlan &pl) { return pde_make_plan(npairs, M, N, n, want_grad, pl); });
 }
 
 // the argument checks are the entry points' (capi.hip); dG_out == NULL: forward only
@@ -140,7 +132,7 @@ int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool n
     PdePlan pl;
     int rc = pde_make_plan(npairs, M, N, n, want_grad, pl);
     unsigned char *base = nullptr;
-    if (!rc) rc = ring_ws_base("pde", ws, ws_bytes, ring_ws_total(pl.ws_bytes), base);
+    if (!rc) rc = ring_ws_base("pde", ws, ws_bytes, pl.total(), base);
     if (rc) return rc;
     PdeArgs a;
     a.G = G; a.grad_out = grad_out; a.K_out = K_out; a.dG_out = dG_out;
@@ -149,12 +141,7 @@ int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool n
     a.npairs = npairs; a.M = M; a.N = N; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
     a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W;
     a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
-    hipError_t e = dtype == SIGSVGD_F64 ? pde_dispatch<double>(naive, want_grad != 0, pl, stream, a)
-                                        : pde_dispatch<float>(naive, want_grad != 0, pl, stream, a);
-    if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(sig_pde)");
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "launch sig_pde_kernel");
-    return SIGSVGD_OK;
+    return ring_launch<PdeFamily>(dtype, SIGSVGD_STATIC_RBF, naive, want_grad != 0, pl, stream, a);
 }
 
 } // namespace sigsvgd
