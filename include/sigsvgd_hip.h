@@ -35,6 +35,9 @@
  *   sigsvgd_pair_fwd_bwd   pair, and the gradients of both paths from one solve per pair
  *   sigsvgd_gram_long_fwd_bwd2  sigsvgd_gram_long_fwd_bwd with the gradients of both slots from one solve per pair
  *                          (sigkernel's compute_mmd with a trainable Y), and with Y = X each unordered pair once (SVGD)
+ *   sigsvgd_sqdist_select  torch.median of the [A,B,TX,TY] distance tensor inside bw_median (src/utils/math.py:28-34), the
+ *                          default bandwidth of BatchGaussianKernel (src/kernels/_traj_kernels.py:186-194): an exact order
+ *                          statistic of the point distances without that tensor
  *
  * Conventions
  *   - all pointers are DEVICE pointers (HIP), row-major contiguous; the caller owns every buffer
@@ -387,6 +390,25 @@ int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype,
                                   int static_kind, unsigned flags, int tile_offset, int tile_stride,
                                   const void *grad_out /* [N,N] or NULL = ones */, void *K_partial, double *grad_partial,
                                   void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- order statistic of the point distances (ABI 10, additive) ------------------------------------
+ * out_device[0] = the element of rank `rank` (zero-based, ascending) of the multiset
+ *   { |X_ip - Y_jq|^2 : i < A, j < B, p < TX, q < TY },     n = A B TX TY elements,
+ * X [A, TX, d], Y [B, TY, d] in `dtype`.  rank = (n - 1) / 2 is the lower median, which the reference's default bandwidth
+ * takes of the [A, B, TX, TY] tensor (bw_median, src/utils/math.py:28-34); nothing of that size is stored here.  Each value
+ * is computed in fp64 as sum_k (x_k - y_k)^2 in channel order (fp32 inputs converted exactly): never negative, and the same
+ * bits for (i, j, p, q) and (j, i, q, p).  The select is exact on those values: counting passes over the 64-bit pattern, at
+ * most six, each recomputing the distances until the remaining candidates fit a buffer in the workspace.  The state stays
+ * on the device: no host synchronisation, no allocation, graph-capturable; integer counts only, so the result does not
+ * depend on the order of arrival.  With non-finite inputs the call ends and returns some value.
+ * SIGSVGD_FLAG_Y_IS_X (A == B, TX == TY; the caller guarantees Y holds X's values): each unordered pair of paths is visited
+ * once and counted twice; the result is the unflagged call's, bit for bit.  Any other flag bit, a shape below 1, a bad
+ * dtype, null pointers, rank >= n or n >= 2^63 are SIGSVGD_E_BADARG, a workspace below the query's size is
+ * SIGSVGD_E_WORKSPACE, all before any device work.  The workspace (a constant size, independent of the shape) needs no
+ * zeroing: the call clears its counters on the stream. */
+int sigsvgd_sqdist_select_workspace_bytes(int A, int B, int TX, int TY, int d, unsigned flags, size_t *bytes);
+int sigsvgd_sqdist_select(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, unsigned flags,
+                          unsigned long long rank, double *out_device, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
            "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
-           "sig_pde.hip", "gram_long.hip"]
+           "sig_pde.hip", "gram_long.hip", "sqdist_select.hip"]
 HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"), os.path.join(_CSRC, "ring_sweep.h"),
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
@@ -61,6 +61,8 @@ EXPORTS = [
     "sigsvgd_gram_long_partial_plan",
     "sigsvgd_gram_long_partial_workspace_bytes",
     "sigsvgd_gram_long_sym_partial",
+    "sigsvgd_sqdist_select_workspace_bytes",
+    "sigsvgd_sqdist_select",
 ]
 
 _lib = None
@@ -223,6 +225,10 @@ def load():
     L.sigsvgd_gram_long_partial_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
     L.sigsvgd_gram_long_sym_partial.restype = ci
     L.sigsvgd_gram_long_sym_partial.argtypes = [vp, ci, ci, ci, ci, cd, ci, ci, cu, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
+    L.sigsvgd_sqdist_select_workspace_bytes.restype = ci
+    L.sigsvgd_sqdist_select_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
+    L.sigsvgd_sqdist_select.restype = ci
+    L.sigsvgd_sqdist_select.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cu, ctypes.c_ulonglong, vp, vp, ctypes.c_size_t, vp]
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

@@ -70,6 +70,10 @@ int long2_launch(const LongProblem &p);
 int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC);
 int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes);
 int long_part_launch(const LongProblem &p, int off, int stride);
+// the distance select (sqdist_select.hip)
+size_t select_workspace_bytes();
+int select_launch(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, unsigned flags,
+                  unsigned long long rank, unsigned long long n, double *out, void *ws, size_t ws_bytes, hipStream_t stream);
 
 // the refusal of a workspace query without a place for its answer
 static bool no_bytes(const size_t *bytes)
@@ -165,6 +169,23 @@ static int check_pair(const LongProblem &p, bool launch)
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
     return check_long(p, launch);
+}
+
+// the distance select's (sqdist_select.hip): the shape, the one flag it takes (SIGSVGD_FLAG_Y_IS_X: one batch in both slots)
+// and the element count n = A B TX TY, which must stay below 2^63
+static int check_select(int A, int B, int TX, int TY, int d, unsigned flags, unsigned long long *n)
+{
+    if (A < 1 || B < 1 || TX < 1 || TY < 1 || d < 1)
+        return bad_arg("sqdist_select: bad shape A=%d B=%d TX=%d TY=%d d=%d (need all >= 1)", A, B, TX, TY, d);
+    if (flags & ~SIGSVGD_FLAG_Y_IS_X)
+        return bad_arg("sqdist_select: unknown flag bits 0x%x (only SIGSVGD_FLAG_Y_IS_X)", flags & ~SIGSVGD_FLAG_Y_IS_X);
+    if ((flags & SIGSVGD_FLAG_Y_IS_X) && (A != B || TX != TY))
+        return bad_arg("sqdist_select: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
+    const unsigned __int128 count = (unsigned __int128)((unsigned long long)A * (unsigned long long)B) *
+                                    ((unsigned long long)TX * (unsigned long long)TY);
+    if (count >> 63) return bad_arg("sqdist_select: A B TX TY = %d x %d x %d x %d elements, 2^63 or more", A, B, TX, TY);
+    *n = (unsigned long long)count;
+    return SIGSVGD_OK;
 }
 
 // ---- roctx ranges around the launches (the tracing hook of this path) ------------------------------
@@ -670,6 +691,31 @@ int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype,
     if (!grad_partial) return bad_arg("gram_long_sym_partial: grad_partial == NULL");
     Range range("sigsvgd_gram_long_sym_partial");
     return long_part_launch(p, tile_offset, tile_stride);
+}
+
+// ---- the distance select (sqdist_select.hip) ------------------------------------------------------------------------------
+int sigsvgd_sqdist_select_workspace_bytes(int A, int B, int TX, int TY, int d, unsigned flags, size_t *bytes)
+{
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    unsigned long long n = 0;
+    const int rc = check_select(A, B, TX, TY, d, flags, &n);
+    if (rc) return rc;
+    *bytes = select_workspace_bytes();
+    return SIGSVGD_OK;
+}
+
+int sigsvgd_sqdist_select(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, unsigned flags,
+                          unsigned long long rank, double *out_device, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!X || !Y || !out_device) return bad_arg("sqdist_select: null pointer argument");
+    unsigned long long n = 0;
+    const int rc = check_select(A, B, TX, TY, d, flags, &n);
+    if (rc) return rc;
+    if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("sqdist_select: bad dtype %d", dtype);
+    if (rank >= n) return bad_arg("sqdist_select: rank %llu outside the %llu elements", rank, n);
+    Range range("sigsvgd_sqdist_select");
+    return select_launch(X, Y, A, B, TX, TY, d, dtype, flags, rank, n, out_device, workspace, workspace_bytes,
+                         static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

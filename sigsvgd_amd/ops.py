@@ -399,6 +399,50 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     return K, gX, gY
 
 
+def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] = None) -> torch.Tensor:
+    """The element of rank `rank` (zero-based, ascending; default the lower median (n - 1) // 2, what `torch.median` returns)
+    of the n = A B TX TY squared distances |X_ip - Y_jq|^2 between the points of X [A,TX,d] and Y [B,TY,d], as a 0-dim fp64
+    tensor on the device (`sigsvgd_sqdist_select`, csrc/sqdist_select.hip).  Exact on the fp64 difference-form values; the
+    [A,B,TX,TY] tensor is never formed and nothing is read back.  Y None: Y = X, each unordered pair of paths visited once
+    (the same result, bit for bit)."""
+    L = _lib.load()
+    dev = _require_gpu(X, Y)
+    if X.dim() != 3 or (Y is not None and Y.dim() != 3):
+        raise ValueError("paths must be [batch, length, dim]")
+    if Y is not None and X.shape[2] != Y.shape[2]:
+        raise ValueError(f"X and Y must share the path dimension (got {tuple(X.shape)} vs {tuple(Y.shape)})")
+    _io_dtype(X)
+    Xc = X.detach().contiguous()
+    Yc = Xc if Y is None else Y.detach().to(X.dtype).contiguous()
+    if Xc.numel() == 0 or Yc.numel() == 0:
+        raise ValueError("empty batch")
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    n = A * B * TX * TY
+    rank = (n - 1) // 2 if rank is None else int(rank)
+    if not 0 <= rank < n:
+        raise ValueError(f"rank {rank} outside the {n} elements")
+    flags = _lib.FLAG_Y_IS_X if Y is None else 0
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.sigsvgd_sqdist_select_workspace_bytes(A, B, TX, TY, d, flags, ctypes.byref(nbytes)),
+               "sqdist_select_workspace_bytes")
+    ws, wsn = _workspace(dev, nbytes.value)
+    out = torch.empty((), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_sqdist_select(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), flags, rank,
+                                     out.data_ptr(), ws.data_ptr(), wsn, _stream_ptr(dev))
+    _lib.check(rc, "sqdist_select")
+    return out
+
+
+def path_sqdist_select_passes(dev: torch.device) -> int:
+    """How many passes of the last `path_sqdist_select` on this device and stream recomputed the distances (at most 6): the
+    counter the select keeps at the start of its workspace (csrc/sqdist_select.hip, SelState).  Synchronises; for
+    scripts/median_time.py."""
+    ws = _WS[(dev.index, torch.cuda.current_stream(dev).cuda_stream)]
+    off = (-ws.data_ptr()) % 256
+    return int(ws[off + 28:off + 32].view(torch.int32).item())
+
+
 def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, adagrad_state=None,
              inplace: bool = False):
     """v = -((K @ score - grad_k)/N) [* mask]; with X and lr also returns X - lr*v.

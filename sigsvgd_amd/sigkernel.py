@@ -18,7 +18,8 @@ for X only (None for everything else), like upstream; `grad_Y=True` adds the sec
 Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
 `BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
 the fused kernels' LDS take the long route (csrc/gram_long.hip), which evaluates the static kernel inside its PDE sweep
-(P, Q <= 8192 refined cells).  Any other object with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally,
+(P, Q <= 8192 refined cells).  A `BatchGaussianKernel` without a `bandwidth_fn` (the reference's default, the median
+heuristic) takes its median from an exact select on the device (`ops.path_sqdist_select`), at any batch size.  Any other object with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally,
 `batch_kernel(X, Y) -> [A,M,N]`) is a USER static kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
 the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
 `Gram_matrix` and to the static kernel's own parameters.  The grid costs A*B*M*N elements of memory: large batches
@@ -114,15 +115,59 @@ def gram_sqdist(X, Y):
     return dist
 
 
+# Device launches of fewer distance elements than this keep the torch median (0: every device launch with `bw_median` takes
+# `ops.path_sqdist_select`; DESIGN.md section 5.14 has the measurement behind the value)
+MEDIAN_DEVICE_MIN_ELEMS = 0
+
+
+def _median_keywords(get_bandwidth):
+    """-> the `bw_scale` / `tol` keywords if `get_bandwidth` is `utils.math.bw_median` itself or a `functools.partial` of it
+    with those keywords alone, else None"""
+    import functools
+
+    from .utils.math import bw_median
+
+    if get_bandwidth is bw_median:
+        return {}
+    if (isinstance(get_bandwidth, functools.partial) and get_bandwidth.func is bw_median and not get_bandwidth.args
+            and set(get_bandwidth.keywords) <= {"bw_scale", "tol"}):
+        return dict(get_bandwidth.keywords)
+    return None
+
+
+def _median_route(get_bandwidth, on_device: bool, nelem: int) -> bool:
+    """True where a data-dependent bandwidth is computed without the distance tensor: the function is the median heuristic
+    (`_median_keywords`), the paths are on the device and the launch has at least MEDIAN_DEVICE_MIN_ELEMS distance elements.
+    The median then comes from `ops.path_sqdist_select` (csrc/sqdist_select.hip) at any size.  Everything else -- CPU
+    tensors, any other data-dependent function -- gets the [A,B,TX,TY] tensor from torch, up to _MAX_DIST_BYTES."""
+    return bool(on_device) and nelem >= MEDIAN_DEVICE_MIN_ELEMS and _median_keywords(get_bandwidth) is not None
+
+
+def _dist_elems(X, Y) -> int:
+    return X.shape[0] * Y.shape[0] * X.shape[1] * Y.shape[1]
+
+
+def _on_device(X, Y) -> bool:
+    return X.device.type == "cuda" and Y.device.type == "cuda"
+
+
 def inv_bandwidth_from_fn(get_bandwidth, X, Y) -> float:
     """1/h for the fused HIP path from a reference-style bandwidth function.  Constant functions are
-    resolved without forming the distance tensor; data-dependent ones (the bw_median default) get the
+    resolved without forming the distance tensor; the median heuristic on device tensors takes the median from
+    `ops.path_sqdist_select` (`_median_route`); other data-dependent ones get the
     real [A,B,T,T] fp64 tensor, exactly what the reference passes (_traj_kernels.py:191-194)."""
     try:
         return 1.0 / float(get_bandwidth(_ConstantProbe()))
     except _ConstantProbe.Touched:
         pass
-    nbytes = X.shape[0] * Y.shape[0] * X.shape[1] * Y.shape[1] * 8
+    nelem = _dist_elems(X, Y)
+    if _median_route(get_bandwidth, _on_device(X, Y), nelem):
+        from .utils.math import bw_from_median
+
+        same = (Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype)
+        median = ops.path_sqdist_select(X.detach(), None if same else Y.detach())
+        return 1.0 / float(bw_from_median(median, X.shape[0], **_median_keywords(get_bandwidth)))
+    nbytes = nelem * 8
     if nbytes > _MAX_DIST_BYTES:
         raise RuntimeError(
             f"data-dependent bandwidth needs the full distance tensor ({nbytes / 2**30:.1f} GiB here); "

@@ -10,6 +10,12 @@ def bw_median(sq_dists: torch.Tensor, bw_scale: float = 1.0, tol: float = 1.0e-8
 
     `torch.median` of the flattened tensor is the LOWER median; rows = sq_dists.shape[0].  The divisor is the
     log of a float32 0-dim tensor, as in the reference, so it carries float32 rounding (the fixtures pin that)."""
-    divisor = torch.log(torch.tensor(float(sq_dists.shape[0]) + 1.0))
-    bandwidth = bw_scale * torch.sqrt(torch.median(sq_dists) / divisor)
+    return bw_from_median(torch.median(sq_dists), sq_dists.shape[0], bw_scale, tol)
+
+
+def bw_from_median(median: torch.Tensor, rows: int, bw_scale: float = 1.0, tol: float = 1.0e-8) -> torch.Tensor:
+    """The tail of `bw_median` for a median computed elsewhere (`ops.path_sqdist_select` on the device):
+    bw_median(sq) == bw_from_median(torch.median(sq), sq.shape[0], ...), bit for bit."""
+    divisor = torch.log(torch.tensor(float(rows) + 1.0))
+    bandwidth = bw_scale * torch.sqrt(median / divisor)
     return bandwidth.clamp_min_(tol)
