@@ -1,7 +1,9 @@
 """Diagnostic build of the library with in-kernel phase stamps (-DSIGSVGD_PHASE_STAMPS): where a wave of
 gram_fast_kernel spends its cycles.  Builds sigsvgd_amd/_exp/libsigsvgd_stamps.so (git-ignored scratch directory that travels to the GPU
 box while it exists; never the product library; delete it after the profiling pass) and
-runs a few launches; the library prints the split to stderr after each launch.
+runs a few launches; the library prints the split to stderr after each launch.  gram_fast_kernel's window between the pair's closing
+barrier and the next pair comes as three parts: "block sum + stage store", "second barrier" and "loop top" (up to the first stamp
+of the next pair: flags, addresses and issue of the next column's loads).
 usage (on the GPU box): python scripts/dev/phase_stamps.py [N T d [sym|ordered|fwd|fwdsym|dyadic<k>]]      (build only: --build)"""
 import os
 import subprocess

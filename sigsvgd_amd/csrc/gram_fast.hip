@@ -51,6 +51,8 @@ namespace sigsvgd {
 #define SIG_PRIO(n)                                                          \
     if (!GRAD || !SYM || (RING == 32 && NW == 4)) __builtin_amdgcn_s_setprio(n);
 
+constexpr int SIG_FAST_PHASES = 9; // stamp slots of the diagnostic build (launch_variant names them)
+
 struct FastArgs {
     const void *X, *Y, *go;
     void *K;
@@ -65,7 +67,7 @@ struct FastArgs {
     unsigned char *kflag;         // [A][B] (d <= 4 only): 1 where the pair's fp32 solution cancelled or K is ill-conditioned in
                                   // the increments: the launcher lets the coverage kernel solve those pairs exactly (fp64)
 #ifdef SIGSVGD_PHASE_STAMPS
-    unsigned long long *stamps; // diagnostic build only: [8] shader-clock totals per phase, summed over waves
+    unsigned long long *stamps; // diagnostic build only: [SIG_FAST_PHASES] shader-clock totals per phase, summed over waves
 #endif
 };
 
@@ -526,7 +528,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     // in advance, so its loads are in flight during the current pair (the round-1/2 work queue exposed an atomic and a
     // load round trip per chunk: 63 % of the wave cycles at N=128, T=32 with its single-column chunks).
 #ifdef SIGSVGD_PHASE_STAMPS
-    unsigned long long ph_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
+    unsigned long long ph_[SIG_FAST_PHASES] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast_ = __builtin_amdgcn_s_memtime();
 #endif
     int j0 = 0, j1 = 0;
     float *Gs = Gs_all + (GRAD ? wave * GSW : 0);
@@ -543,15 +545,47 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 
     // ---- staging of column trajectory y_j: element e -> (t = e / DPAD, c = e % DPAD) -------------
     constexpr int EPT = (64 * DPAD + NT - 1) / NT; // elements per thread
+    // RAW_STAGE: the loads of the next column are issued at the top of a pair "to be in flight during it", but load_any's
+    // conversion is a use: an s_waitcnt vmcnt(0) after each of two dependent round trips to memory at the top of every pair,
+    // in all waves of the workgroup at once (the "loop top" stamp: 2.7 % of the wave-cycles of a C4 launch).  With RAW_STAGE
+    // stage_load keeps the raw bits and stage_store converts; the row x_i is consumed once per tile and the staged words
+    // once before the pair's closing barrier (below), so that no wait stands between the top of a pair and its end.
+    // Measured per launch kind against the build without it: the symmetric 8-channel gradient kernels of
+    // the 64-slot ring gain (C4: -1 ... -2 %); ordered and forward-only launches, the 4-channel kernels and the 32-slot ring
+    // LOSE 0.5-4 % and keep the conversion at the load.
+    constexpr bool RAW_STAGE = GRAD && SYM && RING == 64 && DPAD == 8;
+    struct RawElem { unsigned lo, hi; }; // the element's bits: an fp32 value in `lo`, an fp64 value in both words
+    RawElem raw_v[EPT], raw_r[EPT];      // (RAW_STAGE)
     double stage_v[EPT], stage_r[EPT];
+    // (word by word, the high word under its own condition: one register per word on both paths, nothing to move or widen
+    //  -- which would be a use -- after the load)
+    auto load_raw = [&](const void *b, size_t idx) -> RawElem {
+        const char *p = static_cast<const char *>(b) + (idx << (io64 ? 3 : 2));
+        RawElem r;
+        r.lo = *reinterpret_cast<const unsigned *>(p);
+        r.hi = 0u;
+        if (io64) r.hi = *reinterpret_cast<const unsigned *>(p + 4);
+        return r;
+    };
+    auto raw_value = [&](const RawElem &r) -> double { // what load_any returns for the same element
+        return io64 ? __hiloint2double((int)r.hi, (int)r.lo) : (double)__uint_as_float(r.lo);
+    };
     auto stage_load = [&](int j) {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const int e = tid + k * NT;
             const int t = e / DPAD, c = e % DPAD;
             const bool ok = e < RING * DPAD && t < T && c < d && j < a.B;
-            stage_v[k] = ok ? load_any(a.Y, ((size_t)j * T + t) * d + c, io64) : 0.0;
-            stage_r[k] = ok ? load_any(a.Y, (size_t)j * T * d + c, io64) : 0.0;
+            if constexpr (RAW_STAGE) {
+                raw_v[k] = raw_r[k] = RawElem{0u, 0u}; // (+0.0 in either format)
+                if (ok) {
+                    raw_v[k] = load_raw(a.Y, ((size_t)j * T + t) * d + c);
+                    raw_r[k] = load_raw(a.Y, (size_t)j * T * d + c);
+                }
+            } else {
+                stage_v[k] = ok ? load_any(a.Y, ((size_t)j * T + t) * d + c, io64) : 0.0;
+                stage_r[k] = ok ? load_any(a.Y, (size_t)j * T * d + c, io64) : 0.0;
+            }
         }
     };
     const double nscale = -inv_h * 1.4426950408889634074; // exponent scale: exp(-d/h) = 2^(nscale*d)
@@ -561,6 +595,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             const int e = tid + k * NT;
             if (e < RING * DPAD) {
                 const int t = e / DPAD, c = e % DPAD;
+                if constexpr (RAW_STAGE) {
+                    stage_v[k] = raw_value(raw_v[k]);
+                    stage_r[k] = raw_value(raw_r[k]);
+                }
                 const double v = stage_v[k] - stage_r[k];
                 if (!(LP && c == DPAD - 1)) { // (LP: that slot receives the norm below)
                     yd[t * YDS + c] = v;
@@ -614,6 +652,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     for (int c = 0; c < DPAD; ++c) {
         gacc[c] = 0.0;
         xraw[c] = (row_ok && lrow < T && c < d) ? load_any(a.X, ((size_t)i * T + lrow) * d + c, io64) : 0.0;
+    }
+    if constexpr (RAW_STAGE) {
+        // (the row has arrived HERE, once per tile: left pending, its first use in the column loop -- phase 0 -- waits for
+        //  every load issued before it, the next column's included)
+#pragma unroll
+        for (int c = 0; c < DPAD; ++c) asm volatile("" : "+v"(xraw[c]));
     }
     j0 = cfirst + cstart;
     j1 = j0 + ncol;
@@ -995,6 +1039,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
             for (int c = 0; c < DPAD; ++c) Gs[lane * DPAD + c] = 0.f; // idle wave contributes nothing
         }
+        // (RAW_STAGE: the next column arrived long ago; saying so HERE, on every path, keeps that wait out of the window
+        //  after the barrier: the compiler cannot see that the loads at the loop top and the store that consumes them run
+        //  under the same condition)
+        if constexpr (RAW_STAGE) {
+#pragma unroll
+            for (int k = 0; k < EPT; ++k)
+                asm volatile("" : "+v"(raw_v[k].lo), "+v"(raw_v[k].hi), "+v"(raw_r[k].lo), "+v"(raw_r[k].hi));
+        }
         SIG_STAMP(5)
 #ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER // timing experiment only (results are garbage without it)
         __syncthreads(); // every wave is done with y_j (and has parked its column-side result)
@@ -1020,9 +1072,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         }
         ++item;
         if (more) stage_store();
+        SIG_STAMP(7)
 #ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER
         __syncthreads();
 #endif
+        SIG_STAMP(8)
     }
 
     if (GRAD && row_ok && lrow < T) { // this (workgroup, row tile) segment's own slot: segments are numbered kq + workgroup
@@ -1039,7 +1093,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #ifdef SIGSVGD_PHASE_STAMPS
     SIG_STAMP(0)
     if (lane == 0 && a.stamps)
-        for (int k = 0; k < 8; ++k) atomicAdd(&a.stamps[k], ph_[k]);
+        for (int k = 0; k < SIG_FAST_PHASES; ++k) atomicAdd(&a.stamps[k], ph_[k]);
 #endif
 }
 
@@ -1309,8 +1363,11 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
-    static const char *const nm[] = {"staging/other", "phase 0+1 static kernel", "phase 2 forward sweep", "phase 3 reverse sweep",
-                                      "phase 4 gradient pass", "pair epilogue", "barrier after the pair"};
+    // ("loop top" + "block sum + stage store" + "second barrier" = the "staging/other" of the profiles before the split)
+    static const char *const nm[] = {"loop top", "phase 0+1 static kernel", "phase 2 forward sweep", "phase 3 reverse sweep",
+                                      "phase 4 gradient pass", "pair epilogue", "barrier after the pair",
+                                      "block sum + stage store", "second barrier"};
+    static_assert(sizeof(nm) / sizeof(nm[0]) == SIG_FAST_PHASES, "one name per stamp slot");
     phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
 #endif
     return SIGSVGD_OK;
