@@ -1110,23 +1110,44 @@ struct GradReduceArgs {
     TileMap tm;
     long long nitems;
 };
-// grid (ceil(T*d / 64), A), 4 wavefronts: a workgroup serves 64 elements of one row i, so everything that depends on the
-// row only -- its tile, the tile's item range, the workgroups that met it, the slab row of column i in every owned
+// grid (ceil(T*d / (64 V)), A), 4 wavefronts: a workgroup serves 64 V elements of one row i, so everything that depends on
+// the row only -- its tile, the tile's item range, the workgroups that met it, the slab row of column i in every owned
 // tile -- is wave-uniform SCALAR arithmetic, and the slab rows are walked incrementally (a tile's items follow the
 // previous tile's: one 64-bit add per tile; evaluating the closed forms per load made the kernel scalar-bound: 27.5 us
 // at N=128, T=32, d=7 -- a third of the iteration -- and 100-137 us per C4 launch whatever the thread layout).  An
 // element is a sum over up to N / NW slab rows (column side) and one segment per workgroup that met the row's tile (row
 // side: a handful in large launches, up to ~100 in small ones, where a workgroup owns one or two columns): wavefront w
-// adds the w-th quarter of each list, sixteen loads in flight, and the four partial sums are joined in wavefront order.
+// adds the w-th quarter of each list and the four partial sums are joined in wavefront order.
+// V: elements per thread.  V = 1 takes any T*d (4-byte loads, sixteen in flight).  V = 4 -- T*d a multiple of 4 and every
+// base aligned to 4 of its elements, grad_reduce_launch decides -- gives a thread 4 consecutive elements of the block: one 16-byte load
+// per slab row (two per fp64 segment), eight slab rows in flight, a quarter of the scalar work per byte.  Each element
+// sees the same fp64 additions in the same order under either V: same bits.
 constexpr int RED_W = 4; // (8 wavefronts of half the share each: 78 us instead of 66 at C4)
+template <int V> struct RedVec;
+template <> struct RedVec<1> { using F = float; using D = double; };
+template <> struct RedVec<4> {
+    using F = __attribute__((ext_vector_type(4))) float;
+    using D = __attribute__((ext_vector_type(4))) double;
+};
+template <int V> __device__ __forceinline__ double red_elem(const typename RedVec<V>::D &v, int k) { return v[k]; }
+template <> __device__ __forceinline__ double red_elem<1>(const double &v, int) { return v; }
+template <int V> __device__ __forceinline__ float red_elem(const typename RedVec<V>::F &v, int k) { return v[k]; }
+template <> __device__ __forceinline__ float red_elem<1>(const float &v, int) { return v; }
+
+template <int V>
 __global__ __launch_bounds__(RED_W * 64) void grad_reduce_kernel(GradReduceArgs r)
 {
-    __shared__ double part[RED_W][64];
+    using FV = typename RedVec<V>::F;
+    using DV = typename RedVec<V>::D;
+    constexpr int UR = (V == 1) ? 8 : 4, UC = (V == 1) ? 16 : 8; // segments / slab rows in flight per thread
+    __shared__ double part[RED_W][V][64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int e = blockIdx.x * 64 + lane;
+    const int e = (blockIdx.x * 64 + lane) * V;
     const int i = r.A - 1 - (int)blockIdx.y; // rows with the longest column sums first (66 -> 60 us at C4)
-    const bool live = e < r.TD;
-    double s = 0.0;
+    const bool live = e < r.TD;              // (V = 4: T*d is a multiple of 4, a live thread has all four)
+    double s[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) s[k] = 0.0;
     if (live) {
         // row side: the segments of the row's tile, one per workgroup whose item range met it
         const int ti = i / r.NW, wv = i % r.NW;
@@ -1140,12 +1161,14 @@ __global__ __launch_bounds__(RED_W * 64) void grad_reduce_kernel(GradReduceArgs 
             const int w0 = wlo + wave * per, w1 = min(whi + 1, w0 + per);
             const size_t sstride = (size_t)r.NW * r.TD;
             const double *base = r.rseg + ((size_t)kqr * r.NW + wv) * r.TD + e + (size_t)w0 * sstride;
-            for (int w = w0; w < w1; w += 8, base += 8 * sstride) {
-                double v[8];
+            for (int w = w0; w < w1; w += UR, base += UR * sstride) {
+                DV v[UR];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = (w + u < w1) ? base[u * sstride] : 0.0;
+                for (int u = 0; u < UR; ++u) v[u] = (w + u < w1) ? *reinterpret_cast<const DV *>(base + u * sstride) : DV(0.0);
 #pragma unroll
-                for (int u = 0; u < 8; ++u) s += v[u];
+                for (int u = 0; u < UR; ++u)
+#pragma unroll
+                    for (int k = 0; k < V; ++k) s[k] += red_elem<V>(v[u], k);
             }
         }
         // column side: the items (owned tile, column i) of the tiles whose first row is <= i, in the order of the enumeration
@@ -1154,32 +1177,49 @@ __global__ __launch_bounds__(RED_W * 64) void grad_reduce_kernel(GradReduceArgs 
             const int k0 = wave * per, k1 = min(r.tm.owned, k0 + per);
             // slab row of item (tile kq, column i) = start(kq) + i - tile * NW; start(kq + 1) = start(kq) + B - tile * NW
             const float *row = r.cslab + (size_t)(k0 < k1 ? r.tm.start(k0, r.B, r.NW, 1) : 0) * r.TD + e;
-            for (int kq = k0; kq < k1; kq += 16) {
-                float v[16];
+            for (int kq = k0; kq < k1; kq += UC) {
+                FV v[UC];
 #pragma unroll
-                for (int u = 0; u < 16; ++u) {
+                for (int u = 0; u < UC; ++u) {
                     const bool have = kq + u < k1;
                     const int first = have ? r.tm.tile_of(kq + u) * r.NW : r.B; // first row of the tile
                     const bool in = first <= i;
-                    v[u] = in ? row[(size_t)(in ? i - first : 0) * r.TD] : 0.f;
+                    v[u] = in ? *reinterpret_cast<const FV *>(row + (size_t)(in ? i - first : 0) * r.TD) : FV(0.f);
                     row += have ? (size_t)(r.B - first) * r.TD : 0;
                 }
 #pragma unroll
-                for (int u = 0; u < 16; ++u) s += (double)v[u];
+                for (int u = 0; u < UC; ++u)
+#pragma unroll
+                    for (int k = 0; k < V; ++k) s[k] += (double)red_elem<V>(v[u], k);
             }
         }
     }
-    part[wave][lane] = s;
+#pragma unroll
+    for (int k = 0; k < V; ++k) part[wave][k][lane] = s[k];
     __syncthreads();
     if (wave != 0 || !live) return;
-    s = part[0][lane];
 #pragma unroll
-    for (int w = 1; w < RED_W; ++w) s += part[w][lane];
+    for (int k = 0; k < V; ++k) {
+        s[k] = part[0][k][lane];
+#pragma unroll
+        for (int w = 1; w < RED_W; ++w) s[k] += part[w][k][lane];
+    }
     const size_t idx = (size_t)i * r.TD + e;
-    if (r.out64)
-        static_cast<double *>(r.out)[idx] = s;
-    else
-        static_cast<float *>(r.out)[idx] = (float)s;
+    if (r.out64) {
+        DV o;
+        if constexpr (V == 1) o = s[0];
+        else
+#pragma unroll
+            for (int k = 0; k < V; ++k) o[k] = s[k];
+        *reinterpret_cast<DV *>(static_cast<double *>(r.out) + idx) = o;
+    } else {
+        FV o;
+        if constexpr (V == 1) o = (float)s[0];
+        else
+#pragma unroll
+            for (int k = 0; k < V; ++k) o[k] = (float)s[k];
+        *reinterpret_cast<FV *>(static_cast<float *>(r.out) + idx) = o;
+    }
 }
 
 // ---- host side ---------------------------------------------------------------------------------
@@ -1240,7 +1280,15 @@ int grad_reduce_launch(const GradGeom &g, const double *rseg, const float *cslab
         set_error("gradient reduction: %d rows exceed the grid limit", A);
         return SIGSVGD_E_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)((TD + 63) / 64), (unsigned)A), dim3(RED_W * 64), 0, stream, r);
+    // four elements per thread where every 4-element access is aligned: T*d a multiple of 4 (the rows of the slab, of the
+    // segments and of the output then start on multiples of 4 elements) and bases aligned to 4 elements of their type
+    // (16 B of floats, 32 B of doubles; the workspace areas are 256-B aligned); any other shape one per thread
+    auto aligned = [](const void *p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; };
+    const bool vec4 = TD % 4 == 0 && aligned(rseg, 32) && aligned(cslab, 16) && aligned(out, out64 ? 32 : 16);
+    if (vec4)
+        hipLaunchKernelGGL(grad_reduce_kernel<4>, dim3((unsigned)((TD + 255) / 256), (unsigned)A), dim3(RED_W * 64), 0, stream, r);
+    else
+        hipLaunchKernelGGL(grad_reduce_kernel<1>, dim3((unsigned)((TD + 63) / 64), (unsigned)A), dim3(RED_W * 64), 0, stream, r);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch grad_reduce_kernel");
     return SIGSVGD_OK;
