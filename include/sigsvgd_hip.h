@@ -17,6 +17,8 @@
  *   sigsvgd_svgd_step      the same with the adaptive_gradient=True scaling fused (svgd.py:110-113)
  *   sigsvgd_svgd_adam_step the same with the update of the reference's DEFAULT optimizer fused: torch.optim.Adam
  *                          stepped through a closure that sets X.grad to the velocity (svgd.py:20,100-107)
+ *   sigsvgd_svgd_update    the three update rules above (optimizer=None, adaptive_gradient=True, Adam) and the mask on a
+ *                          velocity that is given: the particle-sharded step, after its reduction over ranks
  *   sigsvgd_vec_sqdist     src/utils/math.py:69-86 pw_dist_sq, :116-144 scaled_pw_dist_sq
  *   sigsvgd_vec_kernel     src/kernels/_kernels.py:64-299 GaussianKernel / ScaledGaussianKernel /
  *                          IMQKernel / ScaledIMQKernel: K and d_K.sum(1) without the [A,B,D] tensor
@@ -208,6 +210,25 @@ int sigsvgd_svgd_step(const float *K, const float *score, const float *grad_k, c
 int sigsvgd_svgd_adam_step(const float *K, const float *score, const float *grad_k, const float *mask,
                            int N, int D, float *v_out, const float *X_in, float *X_out, double lr, double beta1,
                            double beta2, double eps, float *exp_avg, float *exp_avg_sq, int *step_dev, void *stream);
+
+/* The update rules of the three launches above on a velocity the caller ALREADY HAS, v_in[N,D] = -((K @ score - grad_k)/N)
+ * (what sigsvgd_svgd_phi writes without a mask): the particle-sharded step, whose velocity is a sum over ranks, applies
+ * mask, Adagrad and Adam -- none of them linear -- to its own rows after the reduction.  One elementwise launch, the same
+ * device function as the fused epilogues, so the results have their bits:
+ *   v = v_in * (mask ? mask : 1)
+ *   adagrad_state != NULL:  state += v^2;  v = v / sqrt(state + 1e-12)            (sigsvgd_svgd_step)
+ *   v_out (may be NULL) = v      -- the velocity after mask and Adagrad, what sigsvgd_svgd_step writes to v_out
+ *   exp_avg != NULL:        torch.optim.Adam's update of X along v, the counter on the device and incremented by a
+ *                           one-thread launch behind the update                    (sigsvgd_svgd_adam_step)
+ *   else, X given:          X_out = X_in - lr * v
+ * X_in and X_out are given both or neither and may be the same buffer, as may v_in and v_out (every element is read and
+ * then written by the same thread).  Adam needs exp_avg, exp_avg_sq, step_dev and X (any one of the three state pointers
+ * asks for Adam), with beta1, beta2 in [0, 1) and eps >= 0; Adam together with adagrad_state is an error, as is a call
+ * with nothing to write (v_out, X_out and the state all NULL): SIGSVGD_E_BADARG, before any device work.  beta1, beta2
+ * and eps are ignored without Adam.  16-byte accesses where D % 4 == 0 and every pointer is 16-byte aligned. */
+int sigsvgd_svgd_update(const float *v_in, const float *mask, int N, int D, float *v_out, const float *X_in,
+                        float *X_out, double lr, float *adagrad_state, float *exp_avg, float *exp_avg_sq,
+                        int *step_dev, double beta1, double beta2, double eps, void *stream);
 
 /* ---- vector kernels on particles X[A,D], Y[B,D] ---------------------------------
  * sq[i,j] = max(0, sum_c (XM[i,c] - YM[j,c]) * (X[i,c] - Y[j,c])).  XM = X @ M, YM = Y @ M for a metric

@@ -40,6 +40,7 @@ EXPORTS = [
     "sigsvgd_svgd_phi",
     "sigsvgd_svgd_step",
     "sigsvgd_svgd_adam_step",
+    "sigsvgd_svgd_update",
     "sigsvgd_vec_sqdist",
     "sigsvgd_vec_kernel",
     "sigsvgd_vec_kernel_fused",
@@ -182,6 +183,8 @@ def load():
     L.sigsvgd_svgd_step.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, cf, vp, vp]
     L.sigsvgd_svgd_adam_step.restype = ci
     L.sigsvgd_svgd_adam_step.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, cd, cd, cd, cd, vp, vp, vp, vp]
+    L.sigsvgd_svgd_update.restype = ci
+    L.sigsvgd_svgd_update.argtypes = [vp, vp, ci, ci, vp, vp, vp, cd, vp, vp, vp, vp, cd, cd, cd, vp]
     L.sigsvgd_vec_sqdist.restype = ci
     L.sigsvgd_vec_sqdist.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]
     L.sigsvgd_vec_kernel.restype = ci

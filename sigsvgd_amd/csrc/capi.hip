@@ -40,6 +40,9 @@ int phi_launch(const float *K, const float *score, const float *grad_k, const fl
                float *v_out, const float *X_in, float *X_out, float lr, float *adagrad, hipStream_t stream,
                float *exp_avg = nullptr, float *exp_avg_sq = nullptr, int *step_dev = nullptr, double lr_adam = 0.0,
                double beta1 = 0.0, double beta2 = 0.0, float eps = 0.f);
+int update_launch(const float *v_in, const float *mask, int N, int D, float *v_out, const float *X_in, float *X_out,
+                  float lr, float *adagrad, hipStream_t stream, float *exp_avg, float *exp_avg_sq, int *step_dev,
+                  double lr_adam, double beta1, double beta2, float eps);
 
 int vec_sqdist_launch(const void *X, const void *Y, const void *XM, const void *YM, int A, int B, int D, int dtype,
                       void *sq, hipStream_t stream);
@@ -436,6 +439,17 @@ int sigsvgd_svgd_adam_step(const float *K, const float *score, const float *grad
     Range range("sigsvgd_svgd_adam_step");
     return phi_launch(K, score, grad_k, mask, N, D, v_out, X_in, X_out, (float)lr, nullptr,
                       static_cast<hipStream_t>(stream), exp_avg, exp_avg_sq, step_dev, lr, beta1, beta2, (float)eps);
+}
+
+int sigsvgd_svgd_update(const float *v_in, const float *mask, int N, int D, float *v_out, const float *X_in, float *X_out,
+                        double lr, float *adagrad_state, float *exp_avg, float *exp_avg_sq, int *step_dev, double beta1,
+                        double beta2, double eps, void *stream)
+{
+    if ((exp_avg || exp_avg_sq || step_dev) && !(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0))
+        return bad_arg("svgd_update: bad hyper-parameters beta1=%g beta2=%g eps=%g", beta1, beta2, eps);
+    Range range("sigsvgd_svgd_update");
+    return update_launch(v_in, mask, N, D, v_out, X_in, X_out, (float)lr, adagrad_state, static_cast<hipStream_t>(stream),
+                         exp_avg, exp_avg_sq, step_dev, lr, beta1, beta2, (float)eps);
 }
 
 int sigsvgd_vec_sqdist(const void *X, const void *Y, const void *XM, const void *YM, int A, int B, int D, int dtype,

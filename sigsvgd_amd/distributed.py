@@ -20,7 +20,10 @@ natural sharding: N^2/2 independent pair solves followed by one reduction over p
                     order and static kernel -- each unordered pair once across the node there too
                     v_partial = -((K_partial @ score - grad_partial)/N)   (linear in the partials)
     3. reduce-scatter(sum) v_partial -> this rank's rows of v;  X_shard <- X_shard - lr * v  (one launch)
-All per-step buffers (gathered operands, partials, velocity) are allocated once and reused.
+                    With a mask, update="adagrad" or update="adam" the update is ops.svgd_update on the rank's rows instead
+                    (one launch, the fused single-GPU launches' device function): mask, Adagrad and Adam are not linear in
+                    the partials, so they run behind the reduce-scatter, on state this rank keeps for its own rows.
+All per-step buffers (gathered operands, partials, velocity, optimizer state) are allocated once and reused.
 K itself stays distributed (each rank keeps its partial; `gather_gram` sums it on demand).
 
 Both collectives are latency-bound at these sizes (a 229 KB shard per peer over a dedicated xGMI
@@ -131,12 +134,35 @@ class ShardedSigSVGD:
     long_partial_fn(X_full, inv_h, tile_offset, tile_stride, dyadic_order=, static_kind=, out=, fold=) -> (K_partial,
     grad_partial), by default `ops.gram_long_sym_partial`; else the row-wise call's own error.  long_partial=True sends every
     shape the long partial takes to it (each pair once also at 129 <= T <= 190), long_partial=False never uses it.
-    `last_route` names the last step's route ("partial", "rowwise" or "long_partial")."""
+    `last_route` names the last step's route ("partial", "rowwise" or "long_partial").
+
+    update: "manual" (X - lr * v, the reference's optimizer=None), "adagrad" (its adaptive_gradient=True) or "adam"
+    (torch.optim.Adam with `betas`, `eps`; lr is its learning rate); mask: multiplies the velocity, broadcastable to the
+    shard [n, T, d] (TrajectorySVGD's gradient_mask, this rank's rows of it).  All three routes end in one call
+    update_fn(v_rows, X_shard, lr, mask=, adagrad_state=, adam=, want_v=False) -> (None, X_new), by default
+    `ops.svgd_update` (the CPU tests pass a torch restatement); update="manual" without a mask keeps the plain torch.add.
+    That call computes in fp32 (state and arithmetic, as the fused single-GPU launches do) and the result is cast back to
+    the shard's dtype: an fp64 shard keeps its dtype but not fp64 updates, unlike on the plain path.  The state covers
+    this rank's rows, is zeroed once per shard shape and is saved / restored with `state_dict()` / `load_state_dict()`.
+    `last_v_rows` is the last step's reduced velocity on this rank's rows BEFORE mask and update; on the partial routes it
+    ALIASES the step's preallocated buffer, which the next step() overwrites (clone to keep it)."""
 
     def __init__(self, inv_h: float, lr: float, group=None, partial_fn: Optional[Callable] = None,
                  phi_fn: Optional[Callable] = None, rows_fn: Optional[Callable] = None, rowwise: bool = False,
                  fold: bool = True, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                 long_partial: Optional[bool] = None, long_partial_fn: Optional[Callable] = None):
+                 long_partial: Optional[bool] = None, long_partial_fn: Optional[Callable] = None,
+                 update: str = "manual", betas=(0.9, 0.999), eps: float = 1e-8, mask=None,
+                 update_fn: Optional[Callable] = None):
+        if update not in ("manual", "adagrad", "adam"):
+            raise ValueError(f'update must be "manual", "adagrad" or "adam", got {update!r}')
+        self.update = update
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        self.mask = mask
+        self.update_fn = update_fn or ops.svgd_update
+        self.last_v_rows = None  # ALIASES the step's buffer, like last_K_partial
+        self._steps = 0          # updates done (what state_dict() saves as "step")
+        self._loaded = None      # a load_state_dict() waiting for the first step's buffers
         self.inv_h = float(inv_h)
         self.lr = float(lr)
         self.group = group
@@ -188,13 +214,93 @@ class ShardedSigSVGD:
                 "grad_partial": torch.empty((N, T, d), dtype=torch.float64, device=dev),
                 "v_rows": torch.empty((n, T, d), dtype=dt, device=dev),
             }
-            self._buf = {key: b}  # one shape at a time: a new shape releases the old buffers
+            # the update's operands for this rank's rows: the mask spelled out once, the optimizer state zeroed once
+            if self.mask is not None:
+                b["mask"] = torch.broadcast_to(torch.as_tensor(self.mask, dtype=torch.float32, device=dev),
+                                               (n, T, d)).contiguous()
+            if self.update == "adagrad":
+                b["adagrad"] = torch.zeros((n, T * d), dtype=torch.float32, device=dev)
+            elif self.update == "adam":
+                b["adam"] = ops.AdamState(X_shard, self.betas, self.eps)
+            if self._buf:
+                self._steps = 0  # a new shape releases the old buffers and the optimizer state: the count starts again
+            self._buf = {key: b}  # one shape at a time
+            if self._loaded is not None:
+                self._adopt(b, self._loaded)
+                self._loaded = None
         return b
 
+    def _state_tensors(self, b) -> dict:
+        if self.update == "adagrad":
+            return {"adagrad": b["adagrad"]}
+        if self.update == "adam":
+            return {"exp_avg": b["adam"].exp_avg, "exp_avg_sq": b["adam"].exp_avg_sq}
+        return {}
+
+    def state_dict(self) -> dict:
+        """The optimizer state of THIS RANK'S rows (every rank saves its own): the mode, the number of updates done, the
+        rank and world size it belongs to, and clones of `adagrad` [n, T*d] or `exp_avg` / `exp_avg_sq` [n, T*d]."""
+        rank, world = _world(self.group)
+        sd = {"update": self.update, "step": self._steps, "rank": rank, "world_size": world}
+        if self._loaded is not None:  # loaded and not stepped since
+            sd.update({k: t.clone() for k, t in self._loaded.items() if isinstance(t, torch.Tensor)})
+        elif self._buf:
+            sd.update({k: t.clone() for k, t in self._state_tensors(next(iter(self._buf.values()))).items()})
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restores `state_dict()` of the same rank under the same world size and mode (ValueError otherwise: a saved state
+        is not resharded); the tensors are copied, onto the particles' device at the latest with the next step."""
+        rank, world = _world(self.group)
+        if sd["update"] != self.update:
+            raise ValueError(f'state of update="{sd["update"]}" loaded into update="{self.update}"')
+        if int(sd["world_size"]) != world or int(sd["rank"]) != rank:
+            raise ValueError(f'state of rank {sd["rank"]} of {sd["world_size"]} loaded into rank {rank} of {world}')
+        want = {"manual": set(), "adagrad": {"adagrad"}, "adam": {"exp_avg", "exp_avg_sq"}}[self.update]
+        loaded = {k: sd[k].detach().clone() for k in want if k in sd}
+        if set(loaded) != want and (loaded or int(sd["step"]) > 0):
+            raise ValueError(f'update="{self.update}" after {sd["step"]} steps needs {sorted(want)}, got {sorted(loaded)}')
+        self._steps = int(sd["step"])
+        self._loaded = None
+        if not loaded:  # a manual step has no tensors, nor has a state saved before the first step: zeroed state
+            for b in self._buf.values():  # (in place: the step's other buffers stay)
+                for t in self._state_tensors(b).values():
+                    t.zero_()
+                if self.update == "adam":
+                    b["adam"].step.zero_()
+                    b["adam"].t_host = 0
+            return
+        loaded["step"] = self._steps
+        if self._buf:
+            self._adopt(next(iter(self._buf.values())), loaded)
+        else:
+            self._loaded = loaded
+
+    def _adopt(self, b, loaded) -> None:
+        for k, dst in self._state_tensors(b).items():
+            if tuple(loaded[k].shape) != tuple(dst.shape):
+                raise ValueError(f"saved {k} {tuple(loaded[k].shape)} does not fit this rank's rows {tuple(dst.shape)}")
+            dst.copy_(loaded[k])
+        if self.update == "adam":
+            b["adam"].step.fill_(int(loaded["step"]))
+            b["adam"].t_host = int(loaded["step"])
+
+    def _apply(self, X_shard, v_rows, buf, rowwise: bool = False):
+        """The one update of every route, on this rank's rows of the reduced velocity (which `last_v_rows` keeps, untouched)."""
+        self.last_v_rows = v_rows
+        if self.update == "manual" and self.mask is None:  # the plain step, as it always ran
+            out = X_shard - self.lr * v_rows if rowwise else torch.add(X_shard, v_rows, alpha=-self.lr)  # one launch
+        else:  # fp32 arithmetic whatever the shard's dtype (the kernel's; the state is fp32), returned in the shard's dtype
+            _, X_new = self.update_fn(v_rows, X_shard, self.lr, mask=buf.get("mask"), adagrad_state=buf.get("adagrad"),
+                                      adam=buf.get("adam"), want_v=False)
+            out = X_new.to(X_shard.dtype)
+        self._steps += 1  # (behind the update: a call that raised has changed neither the state nor the count)
+        return out
+
     def step(self, X_shard: torch.Tensor, score_shard: torch.Tensor, profile: bool = False) -> torch.Tensor:
-        """Returns the updated shard X_shard - lr * v_rows (a new tensor; the step's internal buffers are reused by the
-        next call).  profile=True brackets the phases with events on the current stream (device tensors) or host clocks
-        (CPU rehearsal) and leaves the per-phase milliseconds in `self.phase_ms`; it synchronises, so never use it in a
+        """Returns the updated shard: X_shard - lr * v_rows, or what the chosen update rule makes of v_rows (a new tensor;
+        the step's internal buffers are reused by the next call).  profile=True brackets the phases with events on the
+        current stream (device tensors) or host clocks (CPU rehearsal) and leaves the per-phase milliseconds in `self.phase_ms`; it synchronises, so never use it in a
         timed loop."""
         rank, world = _world(self.group)
         mark = _PhaseClock(X_shard.device) if profile else None
@@ -206,7 +312,7 @@ class ShardedSigSVGD:
             mark("all_gather")
         route = self.last_route = self._route(X_shard.shape[0], X_full, world)
         if route == "rowwise":
-            out = self._step_rowwise(X_shard, X_full, s_full)
+            out = self._step_rowwise(X_shard, X_full, s_full, buf)
             if mark:
                 mark("rowwise_solve_and_update")
                 self.phase_ms = mark.result()
@@ -229,7 +335,7 @@ class ShardedSigSVGD:
         v_rows = reduce_scatter_rows(v_part.reshape(X_full.shape), self.group, out=buf["v_rows"])
         if mark:
             mark("reduce_scatter")
-        out = torch.add(X_shard, v_rows, alpha=-self.lr)  # one launch
+        out = self._apply(X_shard, v_rows, buf)
         if mark:
             mark("update")
             self.phase_ms = mark.result()
@@ -262,7 +368,7 @@ class ShardedSigSVGD:
         """shapes the symmetric partial solve takes (the library's routing rule)"""
         return ops.sym_tile_rows(X_full.shape[1], X_full.shape[2]) > 0
 
-    def _step_rowwise(self, X_shard, X_full, s_full):
+    def _step_rowwise(self, X_shard, X_full, s_full, buf):
         """Fallback for shapes outside the symmetric partial solve (e.g. T > 128): each rank solves
         the ordered pairs (own rows) x (all columns), so its rows of K, grad_k and v are complete
         locally and no reduce-scatter is needed -- at twice the pair solves."""
@@ -271,7 +377,7 @@ class ShardedSigSVGD:
         self.last_K_rows = K_rows
         n_all = X_full.shape[0]
         v_rows = -((K_rows.to(s_full.dtype) @ s_full.flatten(1) - g_rows.flatten(1).to(s_full.dtype)) / n_all)
-        return X_shard - self.lr * v_rows.reshape(X_shard.shape)
+        return self._apply(X_shard, v_rows.reshape(X_shard.shape), buf, rowwise=True)
 
     def gather_gram(self) -> torch.Tensor:
         """Full K (sum of the partials), on demand -- the per-iteration path never needs it."""

@@ -546,6 +546,57 @@ def svgd_adam(K, score, grad_k, X, lr: float, state: AdamState, mask=None, inpla
     return v.reshape(shape), (X if inplace else Xn.reshape(X.shape))
 
 
+def svgd_update(v, X, lr: float, mask=None, adagrad_state=None, adam: Optional[AdamState] = None, inplace: bool = False,
+                want_v: bool = True):
+    """The update rules of `svgd_phi` / `svgd_adam` on a velocity that is GIVEN: v [N, ...] = -((K @ score - grad_k)/N), what
+    `svgd_phi(K, score, grad_k)` returns (`sigsvgd_svgd_update`: one elementwise launch that shares the fused launches' device
+    function, so the results have their bits).  The sharded step runs it on its own rows behind the reduce-scatter.
+
+    mask / adagrad_state / inplace as in `svgd_phi`; adam: an `AdamState` shaped like v (then torch.optim.Adam's update
+    along the masked velocity, plus the one-thread launch that advances the device counter; not together with
+    adagrad_state).  v is left as it was.  Returns (v_applied, X_new): the velocity after mask and Adagrad, shaped like v,
+    and the updated particles (X itself with inplace=True).  want_v=False: v_applied is neither allocated nor stored (the
+    entry point's v_out == NULL) and None is returned in its place."""
+    L = _lib.load()
+    dev = _require_gpu(v, X, mask, adagrad_state, adam.exp_avg if adam is not None else None)
+    if adam is not None and adagrad_state is not None:
+        raise ValueError("svgd_update: Adam and Adagrad state together")
+    N, shape = v.shape[0], v.shape
+    f = lambda t: t.detach().to(torch.float32).reshape(N, -1).contiguous()
+    vc, Xc = f(v), f(X)
+    D = vc.shape[1]
+    if Xc.shape != vc.shape:
+        raise ValueError(f"X shape {tuple(X.shape)} does not match the velocity {tuple(v.shape)}")
+    m = None
+    if mask is not None:
+        m = torch.broadcast_to(torch.as_tensor(mask, dtype=torch.float32, device=dev), shape).reshape(N, -1).contiguous()
+    if inplace:  # every element is read and written by the same thread
+        if Xc.data_ptr() != X.data_ptr():
+            raise ValueError("inplace update needs contiguous float32 particles")
+        Xn = Xc
+    else:
+        Xn = torch.empty_like(Xc)
+    ag = None
+    if adagrad_state is not None:
+        if adagrad_state.dtype != torch.float32 or not adagrad_state.is_contiguous() or adagrad_state.numel() != N * D:
+            raise ValueError("adagrad_state must be a contiguous float32 tensor with the shape of the velocity")
+        ag = adagrad_state
+    if adam is not None and (tuple(adam.exp_avg.shape) != (N, D) or tuple(adam.exp_avg_sq.shape) != (N, D)):
+        raise ValueError("the velocity, X and the Adam state must share the shape [N, D]")
+    vo = torch.empty_like(vc) if want_v else None
+    p = lambda t: t.data_ptr() if t is not None else None
+    b1, b2, eps = (adam.betas[0], adam.betas[1], adam.eps) if adam is not None else (0.0, 0.0, 0.0)
+    with torch.cuda.device(dev):
+        rc = L.sigsvgd_svgd_update(vc.data_ptr(), p(m), N, D, p(vo), Xc.data_ptr(), Xn.data_ptr(), float(lr), p(ag),
+                                   p(adam.exp_avg if adam is not None else None),
+                                   p(adam.exp_avg_sq if adam is not None else None),
+                                   p(adam.step if adam is not None else None), b1, b2, eps, _stream_ptr(dev))
+    _lib.check(rc, "svgd_update")
+    if adam is not None:
+        adam.t_host += 1
+    return (vo.reshape(shape) if want_v else None), (X if inplace else Xn.reshape(X.shape))
+
+
 def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static_kind: int = _lib.STATIC_RBF,
                      grad_out: Optional[torch.Tensor] = None, sym: bool = False, out=None, fold: bool = False):
     """This rank's share of the symmetric Gram + gradient on the gathered particles X [N,T,d]:
