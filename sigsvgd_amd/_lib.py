@@ -29,42 +29,48 @@ VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 ABI_VERSION = 10
 
-EXPORTS = [
-    "sigsvgd_abi_version",
-    "sigsvgd_last_error",
-    "sigsvgd_gram_workspace_bytes",
-    "sigsvgd_gram_fwd",
-    "sigsvgd_gram_fwd_bwd",
-    "sigsvgd_gram_sym_partial",
-    "sigsvgd_gram_sym_tile_rows",
-    "sigsvgd_svgd_phi",
-    "sigsvgd_svgd_step",
-    "sigsvgd_svgd_adam_step",
-    "sigsvgd_svgd_update",
-    "sigsvgd_vec_sqdist",
-    "sigsvgd_vec_kernel",
-    "sigsvgd_vec_kernel_fused",
-    "sigsvgd_vec_fused_workspace_bytes",
-    "sigsvgd_signature",
-    "sigsvgd_signature_backward",
-    "sigsvgd_obstacle_cost",
-    "sigsvgd_pde_workspace_bytes",
-    "sigsvgd_pde_fwd",
-    "sigsvgd_pde_fwd_bwd",
-    "sigsvgd_gram_long_workspace_bytes",
-    "sigsvgd_gram_long_fwd",
-    "sigsvgd_gram_long_fwd_bwd",
-    "sigsvgd_pair_workspace_bytes",
-    "sigsvgd_pair_fwd",
-    "sigsvgd_pair_fwd_bwd",
-    "sigsvgd_gram_long2_workspace_bytes",
-    "sigsvgd_gram_long_fwd_bwd2",
-    "sigsvgd_gram_long_partial_plan",
-    "sigsvgd_gram_long_partial_workspace_bytes",
-    "sigsvgd_gram_long_sym_partial",
-    "sigsvgd_sqdist_select_workspace_bytes",
-    "sigsvgd_sqdist_select",
-]
+# Every entry point of include/sigsvgd_hip.h with its argtypes: a new one is declared here and nowhere else (`load` applies the
+# table, EXPORTS lists its names).  All return int except sigsvgd_last_error, a string.
+_vp, _ci, _cd, _cu, _cf, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_uint, ctypes.c_float, ctypes.c_size_t
+_out = ctypes.POINTER
+ARGTYPES = {
+    "sigsvgd_abi_version": [],
+    "sigsvgd_last_error": [],
+    "sigsvgd_gram_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_gram_fwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_fwd_bwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_sym_partial": [_vp, _ci, _ci, _ci, _ci, _cd, _ci, _cu, _ci, _ci, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_sym_tile_rows": [_ci, _ci],
+    "sigsvgd_svgd_phi": [_vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cf, _vp],
+    "sigsvgd_svgd_step": [_vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cf, _vp, _vp],
+    "sigsvgd_svgd_adam_step": [_vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _cd, _cd, _cd, _vp, _vp, _vp, _vp],
+    "sigsvgd_svgd_update": [_vp, _vp, _ci, _ci, _vp, _vp, _vp, _cd, _vp, _vp, _vp, _vp, _cd, _cd, _cd, _vp],
+    "sigsvgd_vec_sqdist": [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp],
+    "sigsvgd_vec_kernel": [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp],
+    "sigsvgd_vec_kernel_fused": [_vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_vec_fused_workspace_bytes": [_ci, _ci, _ci, _out(_sz)],
+    "sigsvgd_signature": [_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _out(ctypes.c_longlong), _vp],
+    "sigsvgd_signature_backward": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp],
+    "sigsvgd_obstacle_cost": [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _cf, _cf, _vp, _vp, _vp, _vp],
+    "sigsvgd_pde_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_pde_fwd": [_vp, _ci, _ci, _ci, _ci, _ci, _cu, _vp, _vp, _sz, _vp],
+    "sigsvgd_pde_fwd_bwd": [_vp, _ci, _ci, _ci, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_long_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_gram_long_fwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_long_fwd_bwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_pair_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_pair_fwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _sz, _vp],
+    "sigsvgd_pair_fwd_bwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_gram_long2_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_gram_long_fwd_bwd2": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _sz,
+                                   _vp],
+    "sigsvgd_gram_long_partial_plan": [_ci, _ci, _ci, _ci, _ci, _cu, _ci, _out(_ci), _out(_ci)],
+    "sigsvgd_gram_long_partial_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _cu, _ci, _ci, _out(_sz)],
+    "sigsvgd_gram_long_sym_partial": [_vp, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _ci, _ci, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_sqdist_select_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_sqdist_select": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cu, ctypes.c_ulonglong, _vp, _vp, _sz, _vp],
+}
+EXPORTS = list(ARGTYPES)
 
 _lib = None
 
@@ -162,76 +168,10 @@ def load():
     import torch  # noqa: F401
 
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci, cd, cu, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_uint, ctypes.c_float
-    L.sigsvgd_abi_version.restype = ci
-    L.sigsvgd_abi_version.argtypes = []
-    L.sigsvgd_last_error.restype = ctypes.c_char_p
-    L.sigsvgd_last_error.argtypes = []
-    L.sigsvgd_gram_workspace_bytes.restype = ci
-    L.sigsvgd_gram_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_gram_fwd.restype = ci
-    L.sigsvgd_gram_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_fwd_bwd.restype = ci
-    L.sigsvgd_gram_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_sym_partial.restype = ci
-    L.sigsvgd_gram_sym_partial.argtypes = [vp, ci, ci, ci, ci, cd, ci, cu, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_sym_tile_rows.restype = ci
-    L.sigsvgd_gram_sym_tile_rows.argtypes = [ci, ci]
-    L.sigsvgd_svgd_phi.restype = ci
-    L.sigsvgd_svgd_phi.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, cf, vp]
-    L.sigsvgd_svgd_step.restype = ci
-    L.sigsvgd_svgd_step.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, cf, vp, vp]
-    L.sigsvgd_svgd_adam_step.restype = ci
-    L.sigsvgd_svgd_adam_step.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, cd, cd, cd, cd, vp, vp, vp, vp]
-    L.sigsvgd_svgd_update.restype = ci
-    L.sigsvgd_svgd_update.argtypes = [vp, vp, ci, ci, vp, vp, vp, cd, vp, vp, vp, vp, cd, cd, cd, vp]
-    L.sigsvgd_vec_sqdist.restype = ci
-    L.sigsvgd_vec_sqdist.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]
-    L.sigsvgd_vec_kernel.restype = ci
-    L.sigsvgd_vec_kernel.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, cd, cd, vp, vp, vp]
-    L.sigsvgd_vec_kernel_fused.restype = ci
-    L.sigsvgd_vec_kernel_fused.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cd, cd, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_vec_fused_workspace_bytes.restype = ci
-    L.sigsvgd_vec_fused_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_obstacle_cost.restype = ci
-    L.sigsvgd_obstacle_cost.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, vp, vp, vp, vp]
-    L.sigsvgd_signature.restype = ci
-    L.sigsvgd_signature.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, ctypes.POINTER(ctypes.c_longlong), vp]
-    L.sigsvgd_signature_backward.restype = ci
-    L.sigsvgd_signature_backward.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, vp]
-    L.sigsvgd_pde_workspace_bytes.restype = ci
-    L.sigsvgd_pde_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_pde_fwd.restype = ci
-    L.sigsvgd_pde_fwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_pde_fwd_bwd.restype = ci
-    L.sigsvgd_pde_fwd_bwd.argtypes = [vp, ci, ci, ci, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_long_workspace_bytes.restype = ci
-    L.sigsvgd_gram_long_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_gram_long_fwd.restype = ci
-    L.sigsvgd_gram_long_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_long_fwd_bwd.restype = ci
-    L.sigsvgd_gram_long_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_pair_workspace_bytes.restype = ci
-    L.sigsvgd_pair_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_pair_fwd.restype = ci
-    L.sigsvgd_pair_fwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_pair_fwd_bwd.restype = ci
-    L.sigsvgd_pair_fwd_bwd.argtypes = [vp, vp, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_gram_long2_workspace_bytes.restype = ci
-    L.sigsvgd_gram_long2_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_gram_long_fwd_bwd2.restype = ci
-    L.sigsvgd_gram_long_fwd_bwd2.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cd, ci, ci, cu, vp, vp, vp, vp, vp, ctypes.c_size_t,
-                                             vp]
-    L.sigsvgd_gram_long_partial_plan.restype = ci
-    L.sigsvgd_gram_long_partial_plan.argtypes = [ci, ci, ci, ci, ci, cu, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    L.sigsvgd_gram_long_partial_workspace_bytes.restype = ci
-    L.sigsvgd_gram_long_partial_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ci, ci, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_gram_long_sym_partial.restype = ci
-    L.sigsvgd_gram_long_sym_partial.argtypes = [vp, ci, ci, ci, ci, cd, ci, ci, cu, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    L.sigsvgd_sqdist_select_workspace_bytes.restype = ci
-    L.sigsvgd_sqdist_select_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, cu, ctypes.POINTER(ctypes.c_size_t)]
-    L.sigsvgd_sqdist_select.restype = ci
-    L.sigsvgd_sqdist_select.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cu, ctypes.c_ulonglong, vp, vp, ctypes.c_size_t, vp]
+    for name, argtypes in ARGTYPES.items():
+        fn = getattr(L, name)
+        fn.restype = ctypes.c_char_p if name == "sigsvgd_last_error" else ctypes.c_int
+        fn.argtypes = argtypes
     if L.sigsvgd_abi_version() != ABI_VERSION:
         raise RuntimeError("sigsvgd_amd: libsigsvgd_hip.so ABI version mismatch; rebuild it")
     _lib = L

@@ -48,6 +48,45 @@ def _workspace(dev: torch.device, nbytes: int) -> Tuple[Optional[torch.Tensor], 
     return ws, ws.numel()
 
 
+def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def _query(query: str, args, outs, may_refuse: bool = False) -> bool:
+    """Host-only query `sigsvgd_<query>(*args, &out...)`.  -> True; False where the library reports SIGSVGD_E_UNSUPPORTED
+    and the caller asked whether it takes the launch (`may_refuse`, the `*_takes` predicates); any other error raises."""
+    rc = getattr(_lib.load(), "sigsvgd_" + query)(*args, *map(ctypes.byref, outs))
+    if may_refuse and rc == _lib.E_UNSUPPORTED:
+        return False
+    _lib.check(rc, query)
+    return True
+
+
+def _launch(dev: torch.device, name: str, args, query: Optional[str] = None, qargs=()) -> None:
+    """The call protocol of every entry point that enqueues work: `sigsvgd_<name>(*args, [workspace, workspace bytes,]
+    stream)` on `dev` and its current stream, status turned into RuntimeError.  `query`: the entry point's
+    `*_workspace_bytes` query, asked with `qargs`; the workspace is the cached one of (device, stream)."""
+    L = _lib.load()
+    if query is not None:
+        nbytes = ctypes.c_size_t(0)
+        _query(query, qargs, (nbytes,))
+        ws, wsn = _workspace(dev, nbytes.value)
+        args = (*args, _ptr(ws), wsn)
+    with torch.cuda.device(dev):
+        rc = getattr(L, "sigsvgd_" + name)(*args, _stream_ptr(dev))
+    _lib.check(rc, name)
+
+
+def _weights(grad_out: Optional[torch.Tensor], shape, dtype) -> Optional[torch.Tensor]:
+    """grad_out as the library reads it: None (unit weights), or detached, `dtype`, contiguous -- of exactly `shape`, since
+    the kernels index it by the launch's own sizes"""
+    if grad_out is None:
+        return None
+    if tuple(grad_out.shape) != tuple(shape):
+        raise ValueError(f"grad_out must be [{','.join(map(str, shape))}], got {tuple(grad_out.shape)}")
+    return grad_out.detach().to(dtype).contiguous()
+
+
 def _io_dtype(t: torch.Tensor) -> int:
     if t.dtype == torch.float32:
         return _lib.F32
@@ -113,7 +152,6 @@ def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
              stored_forward: bool = False) -> torch.Tensor:
     """K[A,B] = signature-kernel Gram matrix (forward only).  y_is_x: the caller states that Y holds the
     same values as X, so each unordered pair is solved once and K is mirrored."""
-    L = _lib.load()
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_paths(X, Y)
     A, T, d = Xc.shape
@@ -121,16 +159,10 @@ def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
     if y_is_x and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x needs X and Y of one shape")
     flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_workspace_bytes(A, B, T, d, dyadic_order, int(static_kind), 0, flags, ctypes.byref(nbytes)),
-               "gram_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_fwd(Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h),
-                                int(dyadic_order), int(static_kind), flags, K.data_ptr(),
-                                ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_fwd")
+    _launch(dev, "gram_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                              int(static_kind), flags, K.data_ptr()),
+            "gram_workspace_bytes", (A, B, T, d, int(dyadic_order), int(static_kind), 0, flags))
     return K
 
 
@@ -149,31 +181,19 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     relative to the largest gradient entry of the launch).  `force_generic=True`: fp64 sweeps for K and the gradient alike.
     `check_regime` and `stored_forward` are accepted for callers written against earlier versions (when long paths
     could run on a kernel that regenerated the forward solution and declined rough pairs) and have no effect."""
-    L = _lib.load()
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_paths(X, Y)
     A, T, d = Xc.shape
     B = Yc.shape[0]
-    go = None
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A, B):
-            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(Xc.dtype).contiguous()
+    go = _weights(grad_out, (A, B), Xc.dtype)
     if (y_is_x or sym) and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x / sym need X and Y of one shape")
     flags = _flags(naive, sym, y_is_x, force_generic, stored_forward)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_workspace_bytes(A, B, T, d, dyadic_order, int(static_kind), 1, flags, ctypes.byref(nbytes)),
-               "gram_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, T, d), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_fwd_bwd(Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h),
-                                    int(dyadic_order), int(static_kind), flags,
-                                    go.data_ptr() if go is not None else None, K.data_ptr(), gX.data_ptr(),
-                                    ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_fwd_bwd")
+    _launch(dev, "gram_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                                  int(static_kind), flags, _ptr(go), K.data_ptr(), gX.data_ptr()),
+            "gram_workspace_bytes", (A, B, T, d, int(dyadic_order), int(static_kind), 1, flags))
     return K, fold_padded_grad(gX, X.shape[1])
 
 
@@ -182,15 +202,9 @@ def gram_takes(A: int, B: int, T: int, d: int, dyadic_order: int = 0, static_kin
     """Whether `gram_fwd` (want_grad False) / `gram_fwd_bwd` take paths [A, T, d] x [B, T, d] with these settings: the
     library's workspace query for the call's flags, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (the
     per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those); any other error raises."""
-    L = _lib.load()
     flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False)
-    nbytes = ctypes.c_size_t(0)
-    rc = L.sigsvgd_gram_workspace_bytes(int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
-                                        1 if want_grad else 0, flags, ctypes.byref(nbytes))
-    if rc == _lib.E_UNSUPPORTED:
-        return False
-    _lib.check(rc, "gram_workspace_bytes")
-    return True
+    return _query("gram_workspace_bytes", (int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
+                                           1 if want_grad else 0, flags), (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def _prep_long(X, Y):
@@ -212,21 +226,14 @@ def gram_long_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = 
     """K[A,B] of the built-in static kernels on long paths (`sigsvgd_gram_long_fwd`, csrc/gram_long.hip): the launches
     `gram_fwd` refuses for LDS.  X [A,TX,d] and Y [B,TY,d] at their own lengths; fp64 increments and sweeps, K in X's
     dtype."""
-    L = _lib.load()
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
     flags = _flags(naive, False, False, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_long_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags,
-                                                   ctypes.byref(nbytes)), "gram_long_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_long_fwd(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                     int(dyadic_order), int(static_kind), flags, K.data_ptr(),
-                                     ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_long_fwd")
+    _launch(dev, "gram_long_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                   int(dyadic_order), int(static_kind), flags, K.data_ptr()),
+            "gram_long_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags))
     return K
 
 
@@ -237,30 +244,18 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
     grad_out^T) on the long route (`sigsvgd_gram_long_fwd_bwd`).  Bit-reproducible.  Every ordered pair is solved, also
     when Y holds X's values, and Y gets no gradient: `gram_long_fwd_bwd2` solves Y = X once per unordered pair and returns
     the gradients of both slots."""
-    L = _lib.load()
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
-    go = None
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A, B):
-            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(Xc.dtype).contiguous()
+    go = _weights(grad_out, (A, B), Xc.dtype)
     if sym and (A != B or TX != TY):
         raise ValueError("sym needs X and Y of one shape")
     flags = _flags(naive, sym, False, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_long_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags,
-                                                   ctypes.byref(nbytes)), "gram_long_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_long_fwd_bwd(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                         int(dyadic_order), int(static_kind), flags,
-                                         go.data_ptr() if go is not None else None, K.data_ptr(), gX.data_ptr(),
-                                         ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_long_fwd_bwd")
+    _launch(dev, "gram_long_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                       int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), gX.data_ptr()),
+            "gram_long_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags))
     return K, gX
 
 
@@ -269,15 +264,9 @@ def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int
     """Whether `gram_long_fwd_bwd2` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS); any other error raises."""
-    L = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    rc = L.sigsvgd_gram_long2_workspace_bytes(int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                              1 if want_gradX else 0, 1 if want_gradY else 0,
-                                              _lib.FLAG_Y_IS_X if y_is_x else 0, ctypes.byref(nbytes))
-    if rc == _lib.E_UNSUPPORTED:
-        return False
-    _lib.check(rc, "gram_long2_workspace_bytes")
-    return True
+    return _query("gram_long2_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                                 1 if want_gradX else 0, 1 if want_gradY else 0,
+                                                 _lib.FLAG_Y_IS_X if y_is_x else 0), (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -290,33 +279,22 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
     solved once, K's lower triangle mirrors the upper one, and gX is the first-slot gradient `gram_long_fwd_bwd` returns;
     sym: weights grad_out + grad_out^T.  Both give no gY (it is returned as None).  Neither gradient wanted: forward only.
     Computed and returned in X's dtype; bit-reproducible."""
-    L = _lib.load()
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
     if (sym or y_is_x) and (A != B or TX != TY):
         raise ValueError("sym and y_is_x need X and Y of one shape")
     want_gradY = bool(want_gradY) and not (sym or y_is_x)
-    go = None
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A, B):
-            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(Xc.dtype).contiguous()
+    go = _weights(grad_out, (A, B), Xc.dtype)
     flags = _flags(naive, sym, y_is_x, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_long2_workspace_bytes(A, B, TX, TY, d, int(dyadic_order), int(static_kind),
-                                                    1 if want_gradX else 0, 1 if want_gradY else 0, flags,
-                                                    ctypes.byref(nbytes)), "gram_long2_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
     gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
-    p = lambda t: t.data_ptr() if t is not None else None
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_long_fwd_bwd2(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                          int(dyadic_order), int(static_kind), flags, p(go), K.data_ptr(), p(gX), p(gY),
-                                          p(ws), wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_long_fwd_bwd2")
+    _launch(dev, "gram_long_fwd_bwd2", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                        int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX),
+                                        _ptr(gY)),
+            "gram_long2_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1 if want_gradX else 0,
+                                           1 if want_gradY else 0, flags))
     return K, gX, gY
 
 
@@ -325,14 +303,8 @@ def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_k
     """Whether `pair_fwd` (want_grad False) / `pair_fwd_bwd` take pairs X [A, TX, d], Y [A, TY, d]: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS); any other error raises."""
-    L = _lib.load()
-    nbytes = ctypes.c_size_t(0)
-    rc = L.sigsvgd_pair_workspace_bytes(int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                        1 if want_grad else 0, 0, ctypes.byref(nbytes))
-    if rc == _lib.E_UNSUPPORTED:
-        return False
-    _lib.check(rc, "pair_workspace_bytes")
-    return True
+    return _query("pair_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                           1 if want_grad else 0, 0), (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def _prep_pair(X, Y):
@@ -346,21 +318,14 @@ def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
     """K[A] = k_sig(X_i, Y_i) of the built-in static kernels (`sigsvgd_pair_fwd`, the paired mode of csrc/gram_long.hip): one
     solve per pair.  X [A,TX,d] and Y [A,TY,d] at their own lengths; fp64 increments and sweeps, K in X's dtype, bit-identical
     to the diagonal of `gram_long_fwd(X, Y)`."""
-    L = _lib.load()
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
     flags = _flags(naive, False, False, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_pair_workspace_bytes(A, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags,
-                                              ctypes.byref(nbytes)), "pair_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_pair_fwd(Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
-                                int(static_kind), flags, K.data_ptr(), ws.data_ptr() if ws is not None else None, wsn,
-                                _stream_ptr(dev))
-    _lib.check(rc, "pair_fwd")
+    _launch(dev, "pair_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                              int(static_kind), flags, K.data_ptr()),
+            "pair_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags))
     return K
 
 
@@ -372,30 +337,17 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     and returned in X's dtype; bit-reproducible."""
     if not (want_x or want_y):
         raise ValueError("pair_fwd_bwd needs want_x or want_y (pair_fwd for the forward only)")
-    L = _lib.load()
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
-    go = None
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A,):
-            raise ValueError(f"grad_out must be [{A}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(Xc.dtype).contiguous()
+    go = _weights(grad_out, (A,), Xc.dtype)
     flags = _flags(naive, False, False, False)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_pair_workspace_bytes(A, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags,
-                                              ctypes.byref(nbytes)), "pair_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
     gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_pair_fwd_bwd(Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                    int(dyadic_order), int(static_kind), flags, go.data_ptr() if go is not None else None,
-                                    K.data_ptr(), gX.data_ptr() if gX is not None else None,
-                                    gY.data_ptr() if gY is not None else None,
-                                    ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "pair_fwd_bwd")
+    _launch(dev, "pair_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                  int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX), _ptr(gY)),
+            "pair_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags))
     return K, gX, gY
 
 
@@ -405,7 +357,6 @@ def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] 
     tensor on the device (`sigsvgd_sqdist_select`, csrc/sqdist_select.hip).  Exact on the fp64 difference-form values; the
     [A,B,TX,TY] tensor is never formed and nothing is read back.  Y None: Y = X, each unordered pair of paths visited once
     (the same result, bit for bit)."""
-    L = _lib.load()
     dev = _require_gpu(X, Y)
     if X.dim() != 3 or (Y is not None and Y.dim() != 3):
         raise ValueError("paths must be [batch, length, dim]")
@@ -422,15 +373,9 @@ def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] 
     if not 0 <= rank < n:
         raise ValueError(f"rank {rank} outside the {n} elements")
     flags = _lib.FLAG_Y_IS_X if Y is None else 0
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_sqdist_select_workspace_bytes(A, B, TX, TY, d, flags, ctypes.byref(nbytes)),
-               "sqdist_select_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     out = torch.empty((), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_sqdist_select(Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), flags, rank,
-                                     out.data_ptr(), ws.data_ptr(), wsn, _stream_ptr(dev))
-    _lib.check(rc, "sqdist_select")
+    _launch(dev, "sqdist_select", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), flags, rank, out.data_ptr()),
+            "sqdist_select_workspace_bytes", (A, B, TX, TY, d, flags))
     return out
 
 
@@ -443,6 +388,29 @@ def path_sqdist_select_passes(dev: torch.device) -> int:
     return int(ws[off + 28:off + 32].view(torch.int32).item())
 
 
+def _flat32(t: torch.Tensor, N: int) -> torch.Tensor:
+    return t.detach().to(torch.float32).reshape(N, -1).contiguous()
+
+
+def _update_operands(dev, shape, D: int, X, mask, inplace: bool, adagrad_state, like: str):
+    """-> (X, mask) as the update launches read them, each [N, D] fp32 or None, for a velocity of `shape` = [N, ...]: the mask
+    broadcast to it, X refused for `inplace` unless it is its own flattening, adagrad_state refused unless the launch can
+    add to it where it is.  `like`: what the error text calls the velocity's shape."""
+    N = shape[0]
+    Xc = None
+    if X is not None:
+        Xc = _flat32(X, N)
+        if inplace and Xc.data_ptr() != X.data_ptr():  # (in place, every element is read and written by the same thread)
+            raise ValueError("inplace update needs contiguous float32 particles")
+    m = None
+    if mask is not None:
+        m = torch.broadcast_to(torch.as_tensor(mask, dtype=torch.float32, device=dev), shape).reshape(N, -1).contiguous()
+    if adagrad_state is not None and (adagrad_state.dtype != torch.float32 or not adagrad_state.is_contiguous()
+                                      or adagrad_state.numel() != N * D):
+        raise ValueError(f"adagrad_state must be a contiguous float32 tensor with the shape of {like}")
+    return Xc, m
+
+
 def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, adagrad_state=None,
              inplace: bool = False):
     """v = -((K @ score - grad_k)/N) [* mask]; with X and lr also returns X - lr*v.
@@ -451,46 +419,23 @@ def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, ad
     adagrad_state: contiguous fp32 tensor shaped like score, updated IN PLACE (state += v^2) and applied
     (v / sqrt(state + 1e-12)) before the update -- the reference's adaptive_gradient=True (svgd.py:110-113).
     Returns v (shaped like score) or (v, X_new)."""
-    L = _lib.load()
-    dev = _require_gpu(K, score, grad_k, mask, X)
+    dev = _require_gpu(K, score, grad_k, mask, X, adagrad_state)
     N = K.shape[0]
     if K.dim() != 2 or K.shape[1] != N:
         raise ValueError(f"K must be square, got {tuple(K.shape)}")
+    if X is not None and lr is None:
+        raise ValueError("lr is required with X")
     shape = score.shape
-    f = lambda t: t.detach().to(torch.float32).reshape(N, -1).contiguous()
     Kc = K.detach().to(torch.float32).contiguous()
-    s, gk = f(score), f(grad_k)
+    s, gk = _flat32(score, N), _flat32(grad_k, N)
     D = s.shape[1]
     if gk.shape != s.shape:
         raise ValueError(f"grad_k shape {tuple(grad_k.shape)} does not match score {tuple(score.shape)}")
-    m = None
-    if mask is not None:
-        m = torch.broadcast_to(torch.as_tensor(mask, dtype=torch.float32, device=dev), shape)
-        m = m.reshape(N, -1).contiguous()
+    Xc, m = _update_operands(dev, shape, D, X, mask, inplace, adagrad_state, "score")
     v = torch.empty_like(s)
-    Xc = Xn = None
-    if X is not None:
-        if lr is None:
-            raise ValueError("lr is required with X")
-        Xc = f(X)
-        if inplace:  # every element is read and written by the same thread
-            if Xc.data_ptr() != X.data_ptr():
-                raise ValueError("inplace update needs contiguous float32 particles")
-            Xn = Xc
-        else:
-            Xn = torch.empty_like(Xc)
-    ag = None
-    if adagrad_state is not None:
-        _require_gpu(adagrad_state)
-        if adagrad_state.dtype != torch.float32 or not adagrad_state.is_contiguous() or adagrad_state.numel() != N * D:
-            raise ValueError("adagrad_state must be a contiguous float32 tensor with the shape of score")
-        ag = adagrad_state
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_svgd_step(Kc.data_ptr(), s.data_ptr(), gk.data_ptr(), m.data_ptr() if m is not None else None,
-                                 N, D, v.data_ptr(), Xc.data_ptr() if Xc is not None else None,
-                                 Xn.data_ptr() if Xn is not None else None, float(lr or 0.0),
-                                 ag.data_ptr() if ag is not None else None, _stream_ptr(dev))
-    _lib.check(rc, "svgd_step")
+    Xn = Xc if inplace or Xc is None else torch.empty_like(Xc)
+    _launch(dev, "svgd_step", (Kc.data_ptr(), s.data_ptr(), gk.data_ptr(), _ptr(m), N, D, v.data_ptr(), _ptr(Xc), _ptr(Xn),
+                               float(lr or 0.0), _ptr(adagrad_state)))
     v = v.reshape(shape)
     if X is not None:
         return v, (X if inplace else Xn.reshape(X.shape))
@@ -514,34 +459,22 @@ def svgd_adam(K, score, grad_k, X, lr: float, state: AdamState, mask=None, inpla
     """v = -((K @ score - grad_k)/N) [* mask] and torch.optim.Adam's update of X along it, one launch (plus a
     one-thread launch that advances the device-side step counter).  Returns (v shaped like score, X_new);
     inplace=True writes the update into X itself (X must be contiguous fp32) and returns X."""
-    L = _lib.load()
     dev = _require_gpu(K, score, grad_k, mask, X, state.exp_avg)
     N = K.shape[0]
     if K.dim() != 2 or K.shape[1] != N:
         raise ValueError(f"K must be square, got {tuple(K.shape)}")
     shape = score.shape
-    f = lambda t: t.detach().to(torch.float32).reshape(N, -1).contiguous()
     Kc = K.detach().to(torch.float32).contiguous()
-    s, gk, Xc = f(score), f(grad_k), f(X)
+    s, gk = _flat32(score, N), _flat32(grad_k, N)
     D = s.shape[1]
+    Xc, m = _update_operands(dev, shape, D, X, mask, inplace, None, "score")
     if gk.shape != s.shape or Xc.shape != s.shape or tuple(state.exp_avg.shape) != (N, D):
         raise ValueError("score, grad_k, X and the Adam state must share the shape [N, D]")
-    m = None
-    if mask is not None:
-        m = torch.broadcast_to(torch.as_tensor(mask, dtype=torch.float32, device=dev), shape).reshape(N, -1).contiguous()
     v = torch.empty_like(s)
-    if inplace:
-        if Xc.data_ptr() != X.data_ptr():
-            raise ValueError("inplace Adam update needs contiguous float32 particles")
-        Xn = Xc  # every element is read and written by the same thread
-    else:
-        Xn = torch.empty_like(Xc)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_svgd_adam_step(Kc.data_ptr(), s.data_ptr(), gk.data_ptr(), m.data_ptr() if m is not None else None,
-                                      N, D, v.data_ptr(), Xc.data_ptr(), Xn.data_ptr(), float(lr), state.betas[0],
-                                      state.betas[1], state.eps, state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(),
-                                      state.step.data_ptr(), _stream_ptr(dev))
-    _lib.check(rc, "svgd_adam_step")
+    Xn = Xc if inplace else torch.empty_like(Xc)
+    _launch(dev, "svgd_adam_step", (Kc.data_ptr(), s.data_ptr(), gk.data_ptr(), _ptr(m), N, D, v.data_ptr(), Xc.data_ptr(),
+                                    Xn.data_ptr(), float(lr), state.betas[0], state.betas[1], state.eps,
+                                    state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step.data_ptr()))
     state.t_host += 1
     return v.reshape(shape), (X if inplace else Xn.reshape(X.shape))
 
@@ -557,44 +490,42 @@ def svgd_update(v, X, lr: float, mask=None, adagrad_state=None, adam: Optional[A
     adagrad_state).  v is left as it was.  Returns (v_applied, X_new): the velocity after mask and Adagrad, shaped like v,
     and the updated particles (X itself with inplace=True).  want_v=False: v_applied is neither allocated nor stored (the
     entry point's v_out == NULL) and None is returned in its place."""
-    L = _lib.load()
     dev = _require_gpu(v, X, mask, adagrad_state, adam.exp_avg if adam is not None else None)
     if adam is not None and adagrad_state is not None:
         raise ValueError("svgd_update: Adam and Adagrad state together")
     N, shape = v.shape[0], v.shape
-    f = lambda t: t.detach().to(torch.float32).reshape(N, -1).contiguous()
-    vc, Xc = f(v), f(X)
+    vc = _flat32(v, N)
     D = vc.shape[1]
+    Xc, m = _update_operands(dev, shape, D, X, mask, inplace, adagrad_state, "the velocity")
     if Xc.shape != vc.shape:
         raise ValueError(f"X shape {tuple(X.shape)} does not match the velocity {tuple(v.shape)}")
-    m = None
-    if mask is not None:
-        m = torch.broadcast_to(torch.as_tensor(mask, dtype=torch.float32, device=dev), shape).reshape(N, -1).contiguous()
-    if inplace:  # every element is read and written by the same thread
-        if Xc.data_ptr() != X.data_ptr():
-            raise ValueError("inplace update needs contiguous float32 particles")
-        Xn = Xc
-    else:
-        Xn = torch.empty_like(Xc)
-    ag = None
-    if adagrad_state is not None:
-        if adagrad_state.dtype != torch.float32 or not adagrad_state.is_contiguous() or adagrad_state.numel() != N * D:
-            raise ValueError("adagrad_state must be a contiguous float32 tensor with the shape of the velocity")
-        ag = adagrad_state
     if adam is not None and (tuple(adam.exp_avg.shape) != (N, D) or tuple(adam.exp_avg_sq.shape) != (N, D)):
         raise ValueError("the velocity, X and the Adam state must share the shape [N, D]")
+    Xn = Xc if inplace else torch.empty_like(Xc)
     vo = torch.empty_like(vc) if want_v else None
-    p = lambda t: t.data_ptr() if t is not None else None
-    b1, b2, eps = (adam.betas[0], adam.betas[1], adam.eps) if adam is not None else (0.0, 0.0, 0.0)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_svgd_update(vc.data_ptr(), p(m), N, D, p(vo), Xc.data_ptr(), Xn.data_ptr(), float(lr), p(ag),
-                                   p(adam.exp_avg if adam is not None else None),
-                                   p(adam.exp_avg_sq if adam is not None else None),
-                                   p(adam.step if adam is not None else None), b1, b2, eps, _stream_ptr(dev))
-    _lib.check(rc, "svgd_update")
+    if adam is not None:
+        moments = (adam.exp_avg.data_ptr(), adam.exp_avg_sq.data_ptr(), adam.step.data_ptr(), *adam.betas, adam.eps)
+    else:
+        moments = (None, None, None, 0.0, 0.0, 0.0)
+    _launch(dev, "svgd_update", (vc.data_ptr(), _ptr(m), N, D, _ptr(vo), Xc.data_ptr(), Xn.data_ptr(), float(lr),
+                                 _ptr(adagrad_state), *moments))
     if adam is not None:
         adam.t_host += 1
     return (vo.reshape(shape) if want_v else None), (X if inplace else Xn.reshape(X.shape))
+
+
+def _partial_out(out, Xc: torch.Tensor, dev: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """-> (K_partial [N,N] of X's dtype, zeroed; grad_partial [N,T,d] fp64, which the library overwrites in full) of a
+    partial solve on Xc [N,T,d]: the caller's `out` pair if it fits, else new tensors"""
+    N, T, d = Xc.shape
+    if out is None:
+        return torch.zeros((N, N), dtype=Xc.dtype, device=dev), torch.empty((N, T, d), dtype=torch.float64, device=dev)
+    Kp, gp = out
+    if (tuple(Kp.shape) != (N, N) or Kp.dtype != Xc.dtype or not Kp.is_contiguous() or tuple(gp.shape) != (N, T, d)
+            or gp.dtype != torch.float64 or not gp.is_contiguous()):
+        raise ValueError("out must be (K_partial [N,N] of X's dtype, grad_partial [N,T,d] float64), contiguous")
+    Kp.zero_()
+    return Kp, gp
 
 
 def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static_kind: int = _lib.STATIC_RBF,
@@ -605,33 +536,25 @@ def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static
     The launch owns the row tiles (`sym_tile_rows(T, d)` rows each) tile_offset + k*tile_stride; with fold=True also
     their mirror images, which gives every rank the same number of pairs (SIGSVGD_FLAG_FOLD_TILES).
     `out=(K_partial, grad_partial)` reuses the caller's buffers (K_partial is re-zeroed, grad_partial overwritten)."""
-    L = _lib.load()
     dev = _require_gpu(X, grad_out)
     Xc, _ = _prep_paths(X, X)
     N, T, d = Xc.shape
-    go = None
-    if grad_out is not None:
-        go = grad_out.detach().to(Xc.dtype).contiguous()
-    if out is not None:
-        Kp, gp = out
-        if (tuple(Kp.shape) != (N, N) or Kp.dtype != Xc.dtype or not Kp.is_contiguous() or tuple(gp.shape) != (N, T, d)
-                or gp.dtype != torch.float64 or not gp.is_contiguous()):
-            raise ValueError("out must be (K_partial [N,N] of X's dtype, grad_partial [N,T,d] float64), contiguous")
-        Kp.zero_()
-    else:
-        Kp = torch.zeros((N, N), dtype=Xc.dtype, device=dev)
-        gp = torch.empty((N, T, d), dtype=torch.float64, device=dev)  # fully overwritten by the library
+    go = _weights(grad_out, (N, N), Xc.dtype)
+    Kp, gp = _partial_out(out, Xc, dev)
     flags = _flags(False, sym, True, False) | (_lib.FLAG_FOLD_TILES if fold else 0)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_workspace_bytes(N, N, T, d, 0, int(static_kind), 1, flags, ctypes.byref(nbytes)), "gram_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_sym_partial(Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(static_kind),
-                                        flags, int(tile_offset), int(tile_stride),
-                                        go.data_ptr() if go is not None else None, Kp.data_ptr(), gp.data_ptr(),
-                                        ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_sym_partial")
+    _launch(dev, "gram_sym_partial", (Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(static_kind), flags,
+                                      int(tile_offset), int(tile_stride), _ptr(go), Kp.data_ptr(), gp.data_ptr()),
+            "gram_workspace_bytes", (N, N, T, d, 0, int(static_kind), 1, flags))
     return Kp, gp
+
+
+def _long_partial_plan(N, T, d, dyadic_order, static_kind, tile_stride, may_refuse: bool) -> Optional[Tuple[int, int]]:
+    """(R, JC) of `sigsvgd_gram_long_partial_plan`, or None where the library refuses the shape and `may_refuse`"""
+    R, JC = ctypes.c_int(0), ctypes.c_int(0)
+    if not _query("gram_long_partial_plan", (int(N), int(T), int(d), int(dyadic_order), int(static_kind), 0,
+                                             int(tile_stride)), (R, JC), may_refuse):
+        return None
+    return int(R.value), int(JC.value)
 
 
 def gram_long_partial_tiles(N: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -639,11 +562,7 @@ def gram_long_partial_tiles(N: int, T: int, d: int, dyadic_order: int = 0, stati
     """(R, JC): rows per owned tile and columns per work item of `gram_long_sym_partial` on N paths [T, d] shared among
     tile_stride ranks (`sigsvgd_gram_long_partial_plan`, host only).  The same for every rank and for folded and cyclic
     ownership; R is the ownership unit of the sharded step on the long route."""
-    L = _lib.load()
-    R, JC = ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(L.sigsvgd_gram_long_partial_plan(int(N), int(T), int(d), int(dyadic_order), int(static_kind), 0,
-                                                int(tile_stride), ctypes.byref(R), ctypes.byref(JC)), "gram_long_partial_plan")
-    return int(R.value), int(JC.value)
+    return _long_partial_plan(N, T, d, dyadic_order, static_kind, tile_stride, may_refuse=False)
 
 
 def gram_long_partial_takes(N: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -651,14 +570,7 @@ def gram_long_partial_takes(N: int, T: int, d: int, dyadic_order: int = 0, stati
     """Whether `gram_long_sym_partial` takes N paths [T, d] with these settings: the library's plan query, host only.  False
     exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave state beyond the LDS); any
     other error raises."""
-    L = _lib.load()
-    R, JC = ctypes.c_int(0), ctypes.c_int(0)
-    rc = L.sigsvgd_gram_long_partial_plan(int(N), int(T), int(d), int(dyadic_order), int(static_kind), 0, int(tile_stride),
-                                          ctypes.byref(R), ctypes.byref(JC))
-    if rc == _lib.E_UNSUPPORTED:
-        return False
-    _lib.check(rc, "gram_long_partial_plan")
-    return True
+    return _long_partial_plan(N, T, d, dyadic_order, static_kind, tile_stride, may_refuse=True) is not None
 
 
 def gram_long_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, dyadic_order: int = 0,
@@ -671,36 +583,17 @@ def gram_long_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, d
     The launch owns the row tiles (`gram_long_partial_tiles(...)[0]` rows each) tile_offset + k*tile_stride; with fold=True
     also their mirror images, which gives every rank the same number of pairs (SIGSVGD_FLAG_FOLD_TILES).
     `out=(K_partial, grad_partial)` reuses the caller's buffers (K_partial is re-zeroed, grad_partial overwritten)."""
-    L = _lib.load()
     dev = _require_gpu(X, grad_out)
     Xc, _ = _prep_long(X, X)
     N, T, d = Xc.shape
-    go = None
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (N, N):
-            raise ValueError(f"grad_out must be [{N},{N}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(Xc.dtype).contiguous()
-    if out is not None:
-        Kp, gp = out
-        if (tuple(Kp.shape) != (N, N) or Kp.dtype != Xc.dtype or not Kp.is_contiguous() or tuple(gp.shape) != (N, T, d)
-                or gp.dtype != torch.float64 or not gp.is_contiguous()):
-            raise ValueError("out must be (K_partial [N,N] of X's dtype, grad_partial [N,T,d] float64), contiguous")
-        Kp.zero_()
-    else:
-        Kp = torch.zeros((N, N), dtype=Xc.dtype, device=dev)
-        gp = torch.empty((N, T, d), dtype=torch.float64, device=dev)  # fully overwritten by the library
+    go = _weights(grad_out, (N, N), Xc.dtype)
+    Kp, gp = _partial_out(out, Xc, dev)
     flags = _flags(naive, sym, True, False) | (_lib.FLAG_FOLD_TILES if fold else 0)
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_gram_long_partial_workspace_bytes(N, T, d, int(dyadic_order), int(static_kind), flags,
-                                                           int(tile_offset), int(tile_stride), ctypes.byref(nbytes)),
-               "gram_long_partial_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_gram_long_sym_partial(Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
-                                             int(static_kind), flags, int(tile_offset), int(tile_stride),
-                                             go.data_ptr() if go is not None else None, Kp.data_ptr(), gp.data_ptr(),
-                                             ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "gram_long_sym_partial")
+    _launch(dev, "gram_long_sym_partial", (Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
+                                           int(static_kind), flags, int(tile_offset), int(tile_stride), _ptr(go),
+                                           Kp.data_ptr(), gp.data_ptr()),
+            "gram_long_partial_workspace_bytes", (N, T, d, int(dyadic_order), int(static_kind), flags, int(tile_offset),
+                                                  int(tile_stride)))
     return Kp, gp
 
 
@@ -742,7 +635,6 @@ def _prep_vec(t: torch.Tensor, dtype=None) -> torch.Tensor:
 
 def vec_sqdist(X, Y, XM=None, YM=None) -> torch.Tensor:
     """sq[A,B] = clamp(sum_c (XM - YM)_c (X - Y)_c, 0); XM = YM = None: |x_i - y_j|^2.  X [A,D], Y [B,D]."""
-    L = _lib.load()
     dev = _require_gpu(X, Y, XM, YM)
     Xc = _prep_vec(X)
     dt = _io_dtype(Xc)
@@ -761,42 +653,29 @@ def vec_sqdist(X, Y, XM=None, YM=None) -> torch.Tensor:
     if A == 0 or B == 0 or D == 0:
         raise ValueError("empty batch")
     sq = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_vec_sqdist(Xc.data_ptr(), Yc.data_ptr(), XMc.data_ptr() if XMc is not None else None,
-                                  YMc.data_ptr() if YMc is not None else None, A, B, D, dt, sq.data_ptr(),
-                                  _stream_ptr(dev))
-    _lib.check(rc, "vec_sqdist")
+    _launch(dev, "vec_sqdist", (Xc.data_ptr(), Yc.data_ptr(), _ptr(XMc), _ptr(YMc), A, B, D, dt, sq.data_ptr()))
     return sq
 
 
 def vec_kernel(sq, XM, YM, kind: int, inv_h2: float, grad_scale: float, grad_out=None, want_K: bool = True,
                want_grad: bool = True):
     """(K[A,B] or None, dK[A,D] or None): K = f(sq), dK = grad_scale * sum_j grad_out_ij w(sq_ij) (XM_i - YM_j)."""
-    L = _lib.load()
     dev = _require_gpu(sq, XM, YM, grad_out)
     sqc = sq.detach().contiguous()
     dt = _io_dtype(sqc)
     A, B = sqc.shape
-    XMc = YMc = go = None
+    XMc = YMc = None
     D = 1
     if want_grad:
         XMc, YMc = _prep_vec(XM, sqc.dtype), _prep_vec(YM, sqc.dtype)
         D = XMc.shape[1]
         if XMc.shape[0] != A or YMc.shape != (B, D):
             raise ValueError(f"XM {tuple(XMc.shape)} / YM {tuple(YMc.shape)} do not match sq {tuple(sqc.shape)}")
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A, B):
-            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(sqc.dtype).contiguous()
+    go = _weights(grad_out, (A, B), sqc.dtype)
     K = torch.empty((A, B), dtype=sqc.dtype, device=dev) if want_K else None
     dK = torch.empty((A, D), dtype=sqc.dtype, device=dev) if want_grad else None
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_vec_kernel(sqc.data_ptr(), XMc.data_ptr() if XMc is not None else None,
-                                  YMc.data_ptr() if YMc is not None else None,
-                                  go.data_ptr() if go is not None else None, A, B, D, dt, int(kind), float(inv_h2),
-                                  float(grad_scale), K.data_ptr() if K is not None else None,
-                                  dK.data_ptr() if dK is not None else None, _stream_ptr(dev))
-    _lib.check(rc, "vec_kernel")
+    _launch(dev, "vec_kernel", (sqc.data_ptr(), _ptr(XMc), _ptr(YMc), _ptr(go), A, B, D, dt, int(kind), float(inv_h2),
+                                float(grad_scale), _ptr(K), _ptr(dK)))
     return K, dK
 
 
@@ -812,7 +691,6 @@ def vec_kernel_fused(X, Y, kind: int, inv_h2: float, grad_scale: float, XM=None,
     scaled kernels (both or neither).  reproducible (default): the column splits of the launch store their partial sums
     in a workspace and a second small launch adds them in a fixed order -- two calls return the same bits; False: one
     launch, the splits meet in fp32 atomics."""
-    L = _lib.load()
     dev = _require_gpu(X, Y, XM, YM, grad_out)
     Xc, Yc = _prep_vec(X, torch.float32), _prep_vec(Y, torch.float32)
     A, D = Xc.shape
@@ -821,57 +699,46 @@ def vec_kernel_fused(X, Y, kind: int, inv_h2: float, grad_scale: float, XM=None,
         raise ValueError(f"X {tuple(Xc.shape)} / Y {tuple(Yc.shape)} channel mismatch")
     if (XM is None) != (YM is None):
         raise ValueError("XM and YM must both be given or both be None")
-    XMc = YMc = go = None
+    XMc = YMc = None
     if XM is not None:
         XMc, YMc = _prep_vec(XM, torch.float32), _prep_vec(YM, torch.float32)
         if XMc.shape != Xc.shape or YMc.shape != Yc.shape:
             raise ValueError(f"XM {tuple(XMc.shape)} / YM {tuple(YMc.shape)} do not match X / Y")
-    if grad_out is not None:
-        if tuple(grad_out.shape) != (A, B):
-            raise ValueError(f"grad_out must be [{A},{B}], got {tuple(grad_out.shape)}")
-        go = grad_out.detach().to(torch.float32).contiguous()
+    go = _weights(grad_out, (A, B), torch.float32)
     K = torch.empty((A, B), dtype=torch.float32, device=dev) if want_K else None
     dK = torch.empty((A, D), dtype=torch.float32, device=dev) if want_grad else None
-    p = lambda t: t.data_ptr() if t is not None else None
-    ws, wsn = None, 0
+    args = (Xc.data_ptr(), Yc.data_ptr(), _ptr(XMc), _ptr(YMc), _ptr(go), A, B, D, _lib.F32, int(kind), float(inv_h2),
+            float(grad_scale), _ptr(K), _ptr(dK))
     if want_grad and reproducible:  # per-split partial sums joined in a fixed order (the header's reproducible route)
-        nbytes = ctypes.c_size_t(0)
-        _lib.check(L.sigsvgd_vec_fused_workspace_bytes(A, B, D, ctypes.byref(nbytes)), "vec_fused_workspace_bytes")
-        ws, wsn = _workspace(dev, nbytes.value)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_vec_kernel_fused(Xc.data_ptr(), Yc.data_ptr(), p(XMc), p(YMc), p(go), A, B, D, _lib.F32, int(kind),
-                                        float(inv_h2), float(grad_scale), p(K), p(dK), p(ws), wsn, _stream_ptr(dev))
-    _lib.check(rc, "vec_kernel_fused")
+        _launch(dev, "vec_kernel_fused", args, "vec_fused_workspace_bytes", (A, B, D))
+    else:  # no workspace: the splits meet in atomics (or there is no gradient to split)
+        _launch(dev, "vec_kernel_fused", (*args, None, 0))
     return K, dK
 
 
-def signature_channels(channels: int, depth: int) -> int:
-    L = _lib.load()
+def _signature_query(N: int, Ln: int, C: int, depth: int, basepoint: bool, dt: int) -> int:
+    """channels of the signature: the entry point itself, asked without data (host only)"""
     n = ctypes.c_longlong(0)
-    _lib.check(L.sigsvgd_signature(None, 1, 1, int(channels), int(depth), 0, _lib.F32, None, ctypes.byref(n), None),
-               "signature (channel query)")
+    _lib.check(_lib.load().sigsvgd_signature(None, N, Ln, C, int(depth), int(bool(basepoint)), dt, None, ctypes.byref(n),
+                                             None), "signature (channel query)")
     return int(n.value)
 
 
+def signature_channels(channels: int, depth: int) -> int:
+    return _signature_query(1, 1, int(channels), depth, False, _lib.F32)
+
+
 def _signature_fwd(Xc: torch.Tensor, depth: int, basepoint: bool) -> torch.Tensor:
-    L = _lib.load()
     dev = Xc.device
     dt = _io_dtype(Xc)
     N, Ln, C = Xc.shape
-    n = ctypes.c_longlong(0)
-    _lib.check(L.sigsvgd_signature(None, N, Ln, C, int(depth), int(bool(basepoint)), dt, None, ctypes.byref(n), None),
-               "signature (channel query)")
-    out = torch.empty((N, int(n.value)), dtype=Xc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_signature(Xc.data_ptr(), N, Ln, C, int(depth), int(bool(basepoint)), dt, out.data_ptr(), None,
-                                 _stream_ptr(dev))
-    _lib.check(rc, "signature")
+    out = torch.empty((N, _signature_query(N, Ln, C, depth, basepoint, dt)), dtype=Xc.dtype, device=dev)
+    _launch(dev, "signature", (Xc.data_ptr(), N, Ln, C, int(depth), int(bool(basepoint)), dt, out.data_ptr(), None))
     return out
 
 
 def signature_backward(X, grad_sig, depth: int, basepoint: bool = False) -> torch.Tensor:
     """d sum(grad_sig * signature(X, depth, basepoint)) / dX  -> [N, L, C] (`sigsvgd_signature_backward`)."""
-    L = _lib.load()
     dev = _require_gpu(X, grad_sig)
     Xc = X.detach().contiguous()
     dt = _io_dtype(Xc)
@@ -880,10 +747,8 @@ def signature_backward(X, grad_sig, depth: int, basepoint: bool = False) -> torc
     if g.dim() != 2 or g.shape[0] != N or g.shape[1] != signature_channels(C, depth):
         raise ValueError(f"grad_sig must be [{N}, {signature_channels(C, depth)}], got {tuple(g.shape)}")
     gX = torch.empty_like(Xc)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_signature_backward(Xc.data_ptr(), g.data_ptr(), N, Ln, C, int(depth), int(bool(basepoint)), dt,
-                                          gX.data_ptr(), _stream_ptr(dev))
-    _lib.check(rc, "signature_backward")
+    _launch(dev, "signature_backward", (Xc.data_ptr(), g.data_ptr(), N, Ln, C, int(depth), int(bool(basepoint)), dt,
+                                        gX.data_ptr()))
     return gX
 
 
@@ -907,7 +772,6 @@ def signature(X, depth: int, basepoint: bool = False) -> torch.Tensor:
     """Truncated signature of paths X [N, L, C] -> [N, C + ... + C^depth] (signatory's layout).  Differentiable with
     respect to X (reference: `signatory.signature` inside PathSigKernel, src/kernels/_traj_kernels.py:124-125, reached by
     autograd from src/inference/score.py:50-55)."""
-    _lib.load()
     _require_gpu(X)
     if X.dim() != 3:
         raise ValueError(f"paths must be [batch, length, channels]; got {tuple(X.shape)}")
@@ -926,7 +790,6 @@ def obstacle_cost(x, start, target, basis, log_weights, mean, std, w_obstacle: f
 
     x [N, knots, d] interior knots, start/target [d], basis [samples, knots + 2], mixture log_weights [M]
     (normalised), mean/std [M, d].  Returns (cost [N], traj [N, samples, d] or None, d cost / d x or None)."""
-    L = _lib.load()
     dev = _require_gpu(x, basis, mean, std, log_weights, start, target)
     if x.dim() != 3:
         raise ValueError(f"knots must be [batch, knots, channels]; got {tuple(x.shape)}")
@@ -946,12 +809,9 @@ def obstacle_cost(x, start, target, basis, log_weights, mean, std, w_obstacle: f
     cost = torch.empty(N, dtype=torch.float32, device=dev)
     traj = torch.empty((N, Tt, d), dtype=torch.float32, device=dev) if want_traj else None
     grad = torch.empty((N, Kx, d), dtype=torch.float32, device=dev) if want_grad else None
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_obstacle_cost(xc.data_ptr(), N, Kx, d, st.data_ptr(), tg.data_ptr(), bc.data_ptr(), Tt,
-                                     lw.data_ptr(), mc.data_ptr(), sc.data_ptr(), mc.shape[0], float(w_obstacle),
-                                     float(w_length), cost.data_ptr(), traj.data_ptr() if want_traj else None,
-                                     grad.data_ptr() if want_grad else None, _stream_ptr(dev))
-    _lib.check(rc, "obstacle_cost")
+    _launch(dev, "obstacle_cost", (xc.data_ptr(), N, Kx, d, st.data_ptr(), tg.data_ptr(), bc.data_ptr(), Tt, lw.data_ptr(),
+                                   mc.data_ptr(), sc.data_ptr(), mc.shape[0], float(w_obstacle), float(w_length),
+                                   cost.data_ptr(), _ptr(traj), _ptr(grad)))
     return cost, traj, grad
 
 
@@ -971,19 +831,12 @@ def pde_fwd(G, dyadic_order: int = 0, naive: bool = False) -> torch.Tensor:
     """K[npairs] = signature kernel of each pair from its static-kernel grid G [npairs, M, N] (`sigsvgd_pde_fwd`): fp64
     increments and sweeps, K in G's dtype."""
     dev = _require_gpu(G)
-    L = _lib.load()
     Gc = _prep_grid(G)
     npairs, M, N = Gc.shape
     flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_pde_workspace_bytes(npairs, M, N, int(dyadic_order), 0, flags, ctypes.byref(nbytes)),
-               "pde_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_pde_fwd(Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, K.data_ptr(),
-                               ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "pde_fwd")
+    _launch(dev, "pde_fwd", (Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, K.data_ptr()),
+            "pde_workspace_bytes", (npairs, M, N, int(dyadic_order), 0, flags))
     return K
 
 
@@ -993,7 +846,6 @@ def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = Non
     the reference's convention GG = K_fwd * K_rev (the exact adjoint for the naive stencil; what the built-in kernels
     return).  Bit-reproducible."""
     dev = _require_gpu(G, grad_out)
-    L = _lib.load()
     Gc = _prep_grid(G)
     npairs, M, N = Gc.shape
     go = None
@@ -1002,17 +854,11 @@ def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = Non
             raise ValueError(f"grad_out must have {npairs} entries, got {tuple(grad_out.shape)}")
         go = grad_out.detach().reshape(npairs).to(Gc.dtype).contiguous()
     flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.sigsvgd_pde_workspace_bytes(npairs, M, N, int(dyadic_order), 1, flags, ctypes.byref(nbytes)),
-               "pde_workspace_bytes")
-    ws, wsn = _workspace(dev, nbytes.value)
     K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
     dG = torch.empty_like(Gc)
-    with torch.cuda.device(dev):
-        rc = L.sigsvgd_pde_fwd_bwd(Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags,
-                                   go.data_ptr() if go is not None else None, K.data_ptr(), dG.data_ptr(),
-                                   ws.data_ptr() if ws is not None else None, wsn, _stream_ptr(dev))
-    _lib.check(rc, "pde_fwd_bwd")
+    _launch(dev, "pde_fwd_bwd", (Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, _ptr(go),
+                                 K.data_ptr(), dG.data_ptr()),
+            "pde_workspace_bytes", (npairs, M, N, int(dyadic_order), 1, flags))
     return K, dG
 
 

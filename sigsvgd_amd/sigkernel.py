@@ -151,6 +151,11 @@ def _on_device(X, Y) -> bool:
     return X.device.type == "cuda" and Y.device.type == "cuda"
 
 
+def _same_storage(X, Y) -> bool:
+    """one tensor in both slots: the same elements at the same addresses"""
+    return Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype
+
+
 def inv_bandwidth_from_fn(get_bandwidth, X, Y) -> float:
     """1/h for the fused HIP path from a reference-style bandwidth function.  Constant functions are
     resolved without forming the distance tensor; the median heuristic on device tensors takes the median from
@@ -164,8 +169,7 @@ def inv_bandwidth_from_fn(get_bandwidth, X, Y) -> float:
     if _median_route(get_bandwidth, _on_device(X, Y), nelem):
         from .utils.math import bw_from_median
 
-        same = (Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype)
-        median = ops.path_sqdist_select(X.detach(), None if same else Y.detach())
+        median = ops.path_sqdist_select(X.detach(), None if _same_storage(X, Y) else Y.detach())
         return 1.0 / float(bw_from_median(median, X.shape[0], **_median_keywords(get_bandwidth)))
     nbytes = nelem * 8
     if nbytes > _MAX_DIST_BYTES:
@@ -234,6 +238,39 @@ def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus) 
     return not ops.gram_takes(A, A, max(TX, TY), d, dyadic_order, static_kind, False, naive)
 
 
+def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
+    """-> (K, gX or None, gY or None): the one place that chooses the launch of a Gram request with a built-in static kernel.
+    cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x); want_x / want_y: the gradients wanted (neither: forward
+    only, grad_out unused); fused_yx: whether a gradient launch of the fused kernels with Y = X is told so (the speculated
+    unit-weight launch and `gram_and_grad` are, a backward with real weights is not).
+
+    The fused kernels take every launch `ops.gram_takes` grants; the long route takes the rest, each unordered pair once
+    where `_long_yx_route` says so.  The long route gets K and both gradients from one `ops.gram_long_fwd_bwd2` launch (one
+    solve per pair).  The fused route has no second-slot kernel: gY is the first slot of the swapped launch
+    `ops.gram_fwd_bwd(Y, X, grad_out^T)`, a second launch."""
+    static_kind, inv_h, dyadic_order, naive, sym, y_is_x = cfg
+    if not (want_x or want_y):
+        if not _long_route(X, Y, static_kind, dyadic_order, False, naive, False, y_is_x):
+            return ops.gram_fwd(X, Y, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x), None, None
+        if _long_yx_route(y_is_x, X.shape[0], False, _device_cus(X)):
+            return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, None, naive, y_is_x=True,
+                                          want_gradX=False, want_gradY=False)
+        return ops.gram_long_fwd(X, Y, inv_h, dyadic_order, static_kind, naive), None, None
+    yx = y_is_x and not want_y  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
+    if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx):
+        if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
+            return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x, want_y)
+        return (*ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym), None)
+    K = gX = gY = None
+    if want_x:
+        K, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx and fused_yx)
+    if want_y:  # the second slot is the first slot of the swapped launch
+        Kt, gY = ops.gram_fwd_bwd(Y, X, inv_h, dyadic_order, static_kind, None if grad_out is None else grad_out.T, naive,
+                                  False, False)
+        K = Kt.T.contiguous() if K is None else K
+    return K, gX, gY
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd node
 # ------------------------------------------------------------------------------------------------
@@ -244,31 +281,7 @@ class _SigKernelGram(torch.autograd.Function):
     When X (or, with grad_Y, Y) needs a gradient the forward already runs the forward+backward kernel for
     grad_output = 1 (the only grad_output the reference ever produces: callers differentiate
     K.sum(), score.py:69 / trajectory_svgd.py:65), so the usual backward is a scale by a scalar.
-    Any other grad_output triggers one more launch with the real weights.
-
-    The long route gets K and both gradients from one `ops.gram_long_fwd_bwd2` launch (one solve per pair), and with
-    y_is_x solves each unordered pair once.  The fused route has no second-slot kernel: gY is the first slot of the swapped
-    launch `ops.gram_fwd_bwd(Y, X, grad_output^T)`, a second launch."""
-
-    @staticmethod
-    def _launch(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
-        """-> (K, gX or None, gY or None) for the outputs wanted (at least one); fused_yx: whether a launch of the fused
-        kernels with Y = X is told so (the speculated launch is, a launch with real weights never was)"""
-        static_kind, inv_h, dyadic_order, naive, sym, y_is_x = cfg
-        yx = y_is_x and not want_y  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
-        if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx):
-            if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
-                return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x,
-                                              want_y)
-            return (*ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym), None)
-        K = gX = gY = None
-        if want_x:
-            K, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx and fused_yx)
-        if want_y:  # the second slot is the first slot of the swapped launch
-            Kt, gY = ops.gram_fwd_bwd(Y, X, inv_h, dyadic_order, static_kind, None if grad_out is None else grad_out.T,
-                                      naive, False, False)
-            K = Kt.T.contiguous() if K is None else K
-        return K, gX, gY
+    Any other grad_output triggers one more launch with the real weights.  `_solve_gram` chooses every launch."""
 
     @staticmethod
     def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y):
@@ -279,15 +292,9 @@ class _SigKernelGram(torch.autograd.Function):
         Xd = X.detach()
         Yd = Y.detach()
         if any(ctx.want) and speculate:
-            K, ctx.g_ones, ctx.gy_ones = _SigKernelGram._launch(Xd, Yd, ctx.cfg, None, *ctx.want, True)
-        elif _long_route(Xd, Yd, static_kind, dyadic_order, False, naive, False, y_is_x):
-            if _long_yx_route(y_is_x, Xd.shape[0], False, _device_cus(Xd)):
-                K = ops.gram_long_fwd_bwd2(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, y_is_x=True,
-                                           want_gradX=False, want_gradY=False)[0]
-            else:
-                K = ops.gram_long_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive)
+            K, ctx.g_ones, ctx.gy_ones = _solve_gram(Xd, Yd, ctx.cfg, None, *ctx.want, True)
         else:
-            K = ops.gram_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x)
+            K = _solve_gram(Xd, Yd, ctx.cfg, None, False, False, False)[0]
         ctx.save_for_backward(Xd, Yd)
         return K
 
@@ -308,7 +315,7 @@ class _SigKernelGram(torch.autograd.Function):
                 gX = None if ctx.g_ones is None else ctx.g_ones * scalar.to(ctx.g_ones.dtype)
                 gY = None if ctx.gy_ones is None else ctx.gy_ones * scalar.to(ctx.gy_ones.dtype)
         if gX is None and gY is None and (want_x or want_y):
-            _, gX, gY = _SigKernelGram._launch(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
+            _, gX, gY = _solve_gram(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
         if gY is not None:
             gY = gY.to(ctx.y_dtype)
         return gX, gY, None, None, None, None, None, None, None, None
@@ -368,9 +375,7 @@ class SigKernel:
         if static_kind is None:  # user static kernel: its grid, the PDE on the device, autograd through both
             G = self.static_kernel.Gram_matrix(X, Y if sym or grad_Y else Y.detach())
             return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
-        y_is_x = (
-            Y.data_ptr() == X.data_ptr() and Y.shape == X.shape and Y.stride() == X.stride() and Y.dtype == X.dtype
-        )
+        y_is_x = _same_storage(X, Y)
         if (not y_is_x and Y.shape == X.shape and Y.dtype == X.dtype and X.shape[0] >= self.value_check_min_batch
                 and bool(torch.equal(X.detach(), Y.detach()))):
             # The reference's callers pass two BUFFERS with the same values -- `compute_Gram(X.double(),
@@ -423,13 +428,8 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
-        if _long_route(X, Yv, static_kind, self.dyadic_order, True, self._naive_solver, sym, Y is None):
-            if _long_yx_route(Y is None, X.shape[0], True, _device_cus(X)):  # each unordered pair once
-                return ops.gram_long_fwd_bwd2(X, X, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
-                                              y_is_x=True, want_gradY=False)[:2]
-            return ops.gram_long_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym)
-        return ops.gram_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, grad_out, self._naive_solver, sym,
-                                y_is_x=Y is None)
+        cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None)
+        return _solve_gram(X, Yv, cfg, grad_out, True, False, True)[:2]
 
     def _user_gram_and_grad(self, X, Y, grad_out, sym):
         """gram_and_grad for a user static kernel: its grid (with the graph to X), K and dG from one PDE launch, and dG

@@ -295,6 +295,20 @@ def test_weighted_partial_shares_in_the_multi_item_regime(gpu, N, T, d, fold, we
     assert _rel(gs.cpu().numpy(), g.double().cpu().numpy()) < TOL
 
 
+def test_partial_solve_refuses_weights_of_another_shape(gpu):
+    """The kernel reads N * N weights whatever it is given: `ops.gram_sym_partial` refuses a grad_out that is not [N, N] like
+    every other weighted launch, before anything is launched (the caller's `out` buffers keep what they held)."""
+    from sigsvgd_amd import ops
+
+    N, T, d = 8, 8, 2
+    Xg = torch.as_tensor(_paths(N, T, d, 31), device=gpu)
+    Kp = torch.full((N, N), 7.0, device=gpu, dtype=Xg.dtype)
+    gp = torch.full((N, T, d), 7.0, device=gpu, dtype=torch.float64)
+    with pytest.raises(ValueError, match="grad_out must be"):
+        ops.gram_sym_partial(Xg, 1.0, 0, 1, grad_out=torch.ones(N, N - 1, device=gpu, dtype=Xg.dtype), out=(Kp, gp))
+    assert bool((Kp == 7.0).all()) and bool((gp == 7.0).all())
+
+
 def test_paths_beyond_128_points(gpu):
     """T > 128 (dyadic order 0) is the coverage kernel's: its long-path layout (fp64 increments per band of 64 rows, S in the
     launch's scratch; round 4) takes paths while 64 (T-1) + 2 T d doubles fit 160 KB of LDS -- T = 190 with the gradient,
