@@ -102,6 +102,13 @@ extern "C" {
 /* static kernel kinds */
 #define SIGSVGD_STATIC_RBF 0    /* k(x,y) = exp(-|x-y|^2 * inv_h)   (reference: exp(-dist/h)) */
 #define SIGSVGD_STATIC_LINEAR 1 /* k(x,y) = <x,y>                                              */
+/* The heavy-tailed radial kinds, s = |x-y|^2 * inv_h with inv_h > 0 as for RBF.  Accepted from the
+ * second revision of ABI 10 on (no new symbol, no changed signature: a library of the first revision answers
+ * SIGSVGD_E_BADARG).  They run on the fp64 kernels: sigsvgd_gram_fwd / _fwd_bwd wherever the coverage kernel's plan fits,
+ * and the long-path entry points (sigsvgd_gram_long_*, sigsvgd_pair_*) with the default stencil only --
+ * SIGSVGD_FLAG_NAIVE_SOLVER with them is SIGSVGD_E_UNSUPPORTED there.  sigsvgd_gram_sym_partial stays RBF-only. */
+#define SIGSVGD_STATIC_IMQ 2    /* k(x,y) = (1 + s)^(-1/2)          (inverse multiquadric)     */
+#define SIGSVGD_STATIC_RQ 3     /* k(x,y) = (1 + s)^(-1)            (rational quadratic)       */
 
 /* vector kernels (sigsvgd_vec_kernel) */
 #define SIGSVGD_VEC_GAUSSIAN 0 /* k = exp(-sq / (2 h^2))          src/kernels/_kernels.py:106 */

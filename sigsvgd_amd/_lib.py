@@ -22,7 +22,7 @@ HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps
 
 # mirror of include/sigsvgd_hip.h
 F32, F64 = 0, 1
-STATIC_RBF, STATIC_LINEAR = 0, 1
+STATIC_RBF, STATIC_LINEAR, STATIC_IMQ, STATIC_RQ = 0, 1, 2, 3
 FLAG_NAIVE_SOLVER, FLAG_SYM, FLAG_Y_IS_X, FLAG_FORCE_GENERIC, FLAG_WS_CLEAN, FLAG_STORED_FORWARD = 1, 2, 4, 8, 16, 32
 FLAG_FOLD_TILES = 64
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2

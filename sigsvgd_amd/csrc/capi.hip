@@ -85,6 +85,14 @@ static bool no_bytes(const size_t *bytes)
     return !bytes;
 }
 
+// the static kernels the library evaluates itself, and those of them that are functions of |x - y|^2 inv_h (inv_h > 0)
+static bool static_kind_known(int kind) { return kind >= SIGSVGD_STATIC_RBF && kind <= SIGSVGD_STATIC_RQ; }
+static bool static_kind_radial(int kind) { return static_kind_known(kind) && kind != SIGSVGD_STATIC_LINEAR; }
+static const char *static_kind_name(int kind)
+{
+    return kind == SIGSVGD_STATIC_RBF ? "RBF" : kind == SIGSVGD_STATIC_IMQ ? "IMQ" : "rational-quadratic";
+}
+
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
@@ -92,9 +100,10 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
     if (A < 1 || B < 1 || T < 2 || d < 1)
         return bad_arg("bad shape A=%d B=%d T=%d d=%d (need A,B,d >= 1 and T >= 2)", A, B, T, d);
     if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("bad dtype %d", dtype);
-    if (kind != SIGSVGD_STATIC_RBF && kind != SIGSVGD_STATIC_LINEAR) return bad_arg("bad static kernel kind %d", kind);
+    if (!static_kind_known(kind)) return bad_arg("bad static kernel kind %d", kind);
     if (n < 0 || n > 10) return bad_arg("bad dyadic order %d", n);
-    if (kind == SIGSVGD_STATIC_RBF && !(inv_h > 0.0)) return bad_arg("RBF static kernel needs inv_h > 0 (got %g)", inv_h);
+    if (static_kind_radial(kind) && !(inv_h > 0.0))
+        return bad_arg("%s static kernel needs inv_h > 0 (got %g)", static_kind_name(kind), inv_h);
     if ((flags & SIGSVGD_FLAG_SYM) && A != B) return bad_arg("sym backward needs A == B");
     return SIGSVGD_OK;
 }
@@ -114,16 +123,15 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
 
 // The checks of the long-path entry points (gram_long.hip), each condition in one place.  check_long: the Gram mode's, which
 // every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
-// know.  SIGSVGD_FLAG_NAIVE_SOLVER, SIGSVGD_FLAG_SYM (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram
-// mode) are taken, every other bit is refused.
+// know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ and rational quadratic), SIGSVGD_FLAG_SYM
+// (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, every other bit is refused.
 static int check_long(const LongProblem &p, bool launch)
 {
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
                        p.TY, p.d);
-    if (p.kind != SIGSVGD_STATIC_RBF && p.kind != SIGSVGD_STATIC_LINEAR)
-        return bad_arg("gram_long: bad static kernel kind %d", p.kind);
+    if (!static_kind_known(p.kind)) return bad_arg("gram_long: bad static kernel kind %d", p.kind);
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
     const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X;
     if (p.flags & ~known)
@@ -131,8 +139,14 @@ static int check_long(const LongProblem &p, bool launch)
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long: sym backward needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
     if (launch && p.dtype != SIGSVGD_F32 && p.dtype != SIGSVGD_F64) return bad_arg("gram_long: bad dtype %d", p.dtype);
-    if (launch && p.kind == SIGSVGD_STATIC_RBF && !(p.inv_h > 0.0))
-        return bad_arg("gram_long: RBF static kernel needs inv_h > 0 (got %g)", p.inv_h);
+    if (launch && static_kind_radial(p.kind) && !(p.inv_h > 0.0))
+        return bad_arg("gram_long: %s static kernel needs inv_h > 0 (got %g)", static_kind_name(p.kind), p.inv_h);
+    // (the long-path kernels are built with the default stencil only for the two newer kinds: DESIGN.md section 5.15)
+    if ((p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) && (p.kind == SIGSVGD_STATIC_IMQ || p.kind == SIGSVGD_STATIC_RQ)) {
+        set_error("gram_long: SIGSVGD_FLAG_NAIVE_SOLVER is not built for the %s static kernel on the long-path route "
+                  "(default stencil only)", static_kind_name(p.kind));
+        return SIGSVGD_E_UNSUPPORTED;
+    }
     return SIGSVGD_OK;
 }
 
@@ -254,7 +268,8 @@ static bool band_parallel(int A, int B, int T, int d, int n, bool sym)
 }
 
 // The kernel of a launch: FORCE_GENERIC first, then the first family in the order below whose shapes hold it.  The fp32-sweep
-// families (everything but the coverage kernel) take the RBF static kernel with the second-order solver only.
+// families (everything but the coverage kernel) take the RBF static kernel with the second-order solver only; the linear, IMQ
+// and rational-quadratic kernels always take the coverage kernel.
 // Gram + gradient of paths in ONE channel at dyadic order 0 runs on the coverage kernel with fp64 increments and sweeps (what
 // SIGSVGD_FLAG_FORCE_GENERIC does).  Very smooth one-channel paths (|step|^2 / h ~ 1e-5: K = 1 + O(1e-4)) left the gradient of
 // the fp32-sweep kernels at 1.2 .. 2.0e-5 of its largest entry (T = 20, 33: register-resident kernel; T = 128: quadrant
@@ -269,6 +284,9 @@ static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigne
 {
     const bool fp32 = kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
     if (flags & SIGSVGD_FLAG_FORCE_GENERIC) return GramRoute::GenericPrecise;
+    // IMQ and the rational quadratic kernel have fp64 kernels only and are held to fp64 results: the plan that keeps the
+    // increments in fp64 wherever their table (or the per-band layout) fits, what FORCE_GENERIC selects
+    if (!partial && (kind == SIGSVGD_STATIC_IMQ || kind == SIGSVGD_STATIC_RQ)) return GramRoute::GenericPrecise;
     if (!partial && fp32 && want_grad && d == 1 && n == 0 && T >= 3 && T <= 128) return GramRoute::GenericOneChannel;
     if (fp32 && fast_supported(T, d, n)) return GramRoute::Fast;
     if (fp32 && quad_supported(T, d, n)) return GramRoute::Quad;
@@ -331,8 +349,7 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
                                  unsigned flags, size_t *bytes)
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
-    if (static_kind != SIGSVGD_STATIC_RBF && static_kind != SIGSVGD_STATIC_LINEAR)
-        return bad_arg("bad static kernel kind %d", static_kind);
+    if (!static_kind_known(static_kind)) return bad_arg("bad static kernel kind %d", static_kind);
     // The largest plan of the launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B
     // the symmetric launch and -- gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch
     // and, when A == B, the symmetric one.

@@ -44,6 +44,24 @@ struct GenericArgs {
 #endif
 };
 
+// The radial static kernels k = phi(s), s = |x - y|^2 inv_h, from the argument t = -s the kernel forms for RBF's exponential
+// (DESIGN.md section 5.15).  NEWKIND is gram_generic_kernel's compile-time parameter: false is RBF (and the linear kernel, which
+// never gets here) with the code it always had, true is IMQ or the rational quadratic kernel, told apart by the wave-uniform
+// `kind`.  radial_k: phi; radial_slope: -phi'(s), RBF's exp(-s) in the gradient contraction (IMQ: k^3 / 2, RQ: k^2).
+template <bool NEWKIND>
+__device__ __forceinline__ double radial_k(int kind, double t)
+{
+    if constexpr (!NEWKIND) return exp64(t);
+    return kind == SIGSVGD_STATIC_IMQ ? rsqrt(1.0 - t) : 1.0 / (1.0 - t);
+}
+template <bool NEWKIND>
+__device__ __forceinline__ double radial_slope(int kind, double t)
+{
+    if constexpr (!NEWKIND) return exp64(t);
+    const double k = radial_k<NEWKIND>(kind, t);
+    return kind == SIGSVGD_STATIC_IMQ ? 0.5 * (k * k * k) : k * k;
+}
+
 __host__ __device__ inline size_t generic_lds_bytes(int T, int d, int n, int want_grad, int big, int dd = 0)
 {
     const int dp = (d % 2 == 0) ? d + 1 : d;
@@ -70,14 +88,17 @@ __host__ __device__ inline size_t generic_lds_bytes(int T, int d, int n, int wan
 // a small remainder of much larger values and inherits ~3e-7 .. 3e-6 (T = 64 .. 128) of their ratio to it from the rounded
 // increments, whatever the precision of the sweeps.  double wherever the table fits next to the rest (always for the
 // reference's own shapes; the fp64 pass over flagged pairs and force_generic whenever 160 KB allow).
-template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT>
+// NEWKIND: the static kernel is IMQ or the rational quadratic (a.kind says which); false: RBF or linear, the instantiations
+// the kernel had before those kinds, instruction for instruction.
+template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, bool NEWKIND = false>
 __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int T = a.T, d = a.d, dp = a.dp, Tm = a.Tm, TmS = a.TmS, P = a.P, n = a.n, r = a.r;
     constexpr bool naive = NAIVE;
-    const bool rbf = a.kind == SIGSVGD_STATIC_RBF;
+    const int kind = a.kind;
+    const bool radial = NEWKIND || a.kind == SIGSVGD_STATIC_RBF; // RBF, IMQ, rational quadratic: functions of |x - y|^2 inv_h
 
     double *xs = reinterpret_cast<double *>(smem_raw);
     double *ys = xs + (size_t)T * dp;
@@ -109,7 +130,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             double dot = 0.0;
             const int pr = a0 + nrows; // <= T - 1
             for (int c = 0; c < d; ++c) dot = __builtin_fma(xs[pr * dp + c], ys[q * dp + c], dot);
-            gnext[q] = rbf ? exp64((2.0 * dot - xn[pr] - yn[q]) * a.inv_h) : dot;
+            gnext[q] = radial ? radial_k<NEWKIND>(kind, (2.0 * dot - xn[pr] - yn[q]) * a.inv_h) : dot;
         }
         __syncthreads();
         const int p = a0 + lane;
@@ -120,7 +141,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             if (valid) {
                 double dot = 0.0;
                 for (int c = 0; c < d; ++c) dot = __builtin_fma(xs[p * dp + c], ys[q * dp + c], dot);
-                gq = rbf ? exp64((2.0 * dot - xn[p] - yn[q]) * a.inv_h) : dot;
+                gq = radial ? radial_k<NEWKIND>(kind, (2.0 * dot - xn[p] - yn[q]) * a.inv_h) : dot;
             }
             const double rd = gq - g_prev;
             g_prev = gq;
@@ -162,12 +183,12 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
         double *slab = GRAD ? a.partials + ((size_t)i * a.nchunks + chunk) * T * d : nullptr;
         if (GRAD && big)
             for (int e = lane; e < T * d; e += kWave) slab[e] = 0.0; // accumulated in place (L2 resident)
-        // ---- stage x_i (centred on its first point for the translation-invariant RBF) ----------
+        // ---- stage x_i (centred on its first point for the translation-invariant radial kernels) ----
         __syncthreads();
         for (int e = lane; e < T * dp; e += kWave) {
             const int t = e / dp, c = e % dp;
             double v = 0.0;
-            if (c < d) v = (double)xi[t * d + c] - (rbf ? (double)xi[c] : 0.0);
+            if (c < d) v = (double)xi[t * d + c] - (radial ? (double)xi[c] : 0.0);
             xs[e] = v;
             if (GRAD && !big) acc[e] = 0.0;
         }
@@ -198,7 +219,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
             for (int e = lane; e < T * dp; e += kWave) {
                 const int t = e / dp, c = e % dp;
                 double v = 0.0;
-                if (c < d) v = (double)yj[t * d + c] - (rbf ? (double)xi[c] : 0.0);
+                if (c < d) v = (double)yj[t * d + c] - (radial ? (double)xi[c] : 0.0);
                 ys[e] = v;
             }
             if (GRAD && !big)
@@ -222,7 +243,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                     if (valid) {
                         double dot = 0.0;
                         for (int c = 0; c < d; ++c) dot = __builtin_fma(xs[p * dp + c], ys[q * dp + c], dot);
-                        gq = rbf ? exp64((2.0 * dot - xn[p] - yn[q]) * a.inv_h) : dot;
+                        gq = radial ? radial_k<NEWKIND>(kind, (2.0 * dot - xn[p] - yn[q]) * a.inv_h) : dot;
                     }
                     const double rd = gq - g_prev;
                     g_prev = gq;
@@ -376,10 +397,10 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                         if (m >= 1 && nn < Tm) R -= Sat(m - 1, nn);
                         if (m < Tm && nn >= 1) R -= Sat(m, nn - 1);
                         double rg = R;
-                        if (rbf) {
+                        if (radial) {
                             double dot = 0.0;
                             for (int c = 0; c < d; ++c) dot = __builtin_fma(xs[m * dp + c], ys[nn * dp + c], dot);
-                            rg = R * exp64((2.0 * dot - xn[m] - yn[nn]) * a.inv_h);
+                            rg = R * radial_slope<NEWKIND>(kind, (2.0 * dot - xn[m] - yn[nn]) * a.inv_h);
                             s0 += rg;
                         }
 #pragma unroll
@@ -396,7 +417,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
 #pragma unroll
                         for (int c = 0; c < 16; ++c) {
                             if (c0 + c < d) {
-                                const double val = rbf ? (-2.0 * a.inv_h) * (xs[m * dp + c0 + c] * s0 - accv[c]) : accv[c];
+                                const double val = radial ? (-2.0 * a.inv_h) * (xs[m * dp + c0 + c] * s0 - accv[c]) : accv[c];
                                 if (big)
                                     slab[m * d + c0 + c] = __builtin_fma(w, val, slab[m * d + c0 + c]);
                                 else
@@ -429,10 +450,10 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                             if (m >= 1 && nn < Tm) R -= Sat(m - 1, nn);
                             if (m < Tm && nn >= 1) R -= Sat(m, nn - 1);
                             double rg = R;
-                            if (rbf) {
+                            if (radial) {
                                 double dot = 0.0;
                                 for (int c = 0; c < d; ++c) dot = __builtin_fma(xs[m * dp + c], ys[nn * dp + c], dot);
-                                rg = R * exp64((2.0 * dot - xn[m] - yn[nn]) * a.inv_h);
+                                rg = R * radial_slope<NEWKIND>(kind, (2.0 * dot - xn[m] - yn[nn]) * a.inv_h);
                                 s0 += rg;
                             }
 #pragma unroll
@@ -442,7 +463,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
 #pragma unroll
                         for (int c = 0; c < 16; ++c) {
                             if (c0 + c < d) {
-                                const double val = rbf ? (-2.0 * a.inv_h) * (ys[nn * dp + c0 + c] * s0 - accv[c]) : accv[c];
+                                const double val = radial ? (-2.0 * a.inv_h) * (ys[nn * dp + c0 + c] * s0 - accv[c]) : accv[c];
                                 a.colslab[(((size_t)i * a.B + j) * T + nn) * d + c0 + c] = wc * val;
                             }
                         }
@@ -580,34 +601,36 @@ int generic_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, boo
 }
 
 namespace {
-template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT>
+template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, bool NEWKIND>
 hipError_t generic_launch_one(const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     // (the largest size any plan can ask for)
-    const hipError_t e = raise_lds_limit<&gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT>>();
+    const hipError_t e = raise_lds_limit<&gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT, NEWKIND>>();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
+    hipLaunchKernelGGL((gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT, NEWKIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
     return hipSuccess;
 }
-template <typename IO, bool NAIVE, typename DT>
+template <typename IO, bool NAIVE, typename DT, bool NEWKIND>
 hipError_t generic_dispatch2(bool grad, bool big, const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     if constexpr (sizeof(DT) == 8) { // (the long-path layout is fp64 only: make_plan)
-        if (big) return grad ? generic_launch_one<IO, NAIVE, true, true, DT>(pl, stream, a) : generic_launch_one<IO, NAIVE, false, true, DT>(pl, stream, a);
+        if (big) return grad ? generic_launch_one<IO, NAIVE, true, true, DT, NEWKIND>(pl, stream, a) : generic_launch_one<IO, NAIVE, false, true, DT, NEWKIND>(pl, stream, a);
     }
-    return grad ? generic_launch_one<IO, NAIVE, true, false, DT>(pl, stream, a) : generic_launch_one<IO, NAIVE, false, false, DT>(pl, stream, a);
+    return grad ? generic_launch_one<IO, NAIVE, true, false, DT, NEWKIND>(pl, stream, a) : generic_launch_one<IO, NAIVE, false, false, DT, NEWKIND>(pl, stream, a);
 }
-template <typename IO>
+template <typename IO, bool NEWKIND>
 hipError_t generic_dispatch1(bool naive, bool grad, bool big, const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     if (pl.dd)
-        return naive ? generic_dispatch2<IO, true, double>(grad, big, pl, stream, a) : generic_dispatch2<IO, false, double>(grad, big, pl, stream, a);
-    return naive ? generic_dispatch2<IO, true, float>(grad, big, pl, stream, a) : generic_dispatch2<IO, false, float>(grad, big, pl, stream, a);
+        return naive ? generic_dispatch2<IO, true, double, NEWKIND>(grad, big, pl, stream, a) : generic_dispatch2<IO, false, double, NEWKIND>(grad, big, pl, stream, a);
+    return naive ? generic_dispatch2<IO, true, float, NEWKIND>(grad, big, pl, stream, a) : generic_dispatch2<IO, false, float, NEWKIND>(grad, big, pl, stream, a);
 }
 hipError_t generic_dispatch(bool f64, bool naive, bool grad, bool big, const GenericPlan &pl, hipStream_t stream,
                             const GenericArgs &a)
 {
-    return f64 ? generic_dispatch1<double>(naive, grad, big, pl, stream, a) : generic_dispatch1<float>(naive, grad, big, pl, stream, a);
+    if (a.kind == SIGSVGD_STATIC_IMQ || a.kind == SIGSVGD_STATIC_RQ)
+        return f64 ? generic_dispatch1<double, true>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, true>(naive, grad, big, pl, stream, a);
+    return f64 ? generic_dispatch1<double, false>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, false>(naive, grad, big, pl, stream, a);
 }
 } // namespace
 

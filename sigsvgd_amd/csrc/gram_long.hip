@@ -82,11 +82,34 @@ struct PartArgs : LongArgs {
 };
 
 namespace {
+// The radial kinds beside RBF: k = phi(s), s = |x - y|^2 inv_h.  radial_phi: phi(s); radial_slope:
+// -phi'(s), which takes the place of RBF's exp(-s) in the gradient contraction (IMQ: k^3 / 2, rational quadratic: k^2).
+template <int KIND>
+inline constexpr bool kRadialKind = KIND == SIGSVGD_STATIC_IMQ || KIND == SIGSVGD_STATIC_RQ;
+template <int KIND>
+__device__ __forceinline__ double radial_phi(double s)
+{
+    return KIND == SIGSVGD_STATIC_IMQ ? rsqrt(1.0 + s) : 1.0 / (1.0 + s);
+}
+template <int KIND>
+__device__ __forceinline__ double radial_slope(double s)
+{
+    const double k = radial_phi<KIND>(s);
+    return KIND == SIGSVGD_STATIC_IMQ ? 0.5 * (k * k * k) : k * k;
+}
+
 // the static kernel of x (LDS, fp64) and y (global, the caller's dtype)
 template <int KIND, typename IO>
 __device__ __forceinline__ double static_k(const double *x, const IO *y, int d, double inv_h)
 {
     double s = 0.0;
+    if constexpr (kRadialKind<KIND>) {
+        for (int c = 0; c < d; ++c) {
+            const double t = x[c] - (double)y[c];
+            s = __builtin_fma(t, t, s);
+        }
+        return radial_phi<KIND>(s * inv_h);
+    }
     if (KIND == SIGSVGD_STATIC_RBF) {
         for (int c = 0; c < d; ++c) {
             const double t = x[c] - (double)y[c];
@@ -102,6 +125,16 @@ template <int KIND>
 __device__ __forceinline__ double static_k16(const double *x, const double (&y)[16], int d, double inv_h)
 {
     double s = 0.0;
+    if constexpr (kRadialKind<KIND>) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            if (c < d) {
+                const double t = x[c] - y[c];
+                s = __builtin_fma(t, t, s);
+            }
+        }
+        return radial_phi<KIND>(s * inv_h);
+    }
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
         if (c < d) {
@@ -121,6 +154,7 @@ __device__ __forceinline__ double static_k16(const double *x, const double (&y)[
 // arrives from the lane below), and walk the points t of the other path in order.  dG[m][n] / w = (S[m-1][n-1] + S[m][n]) -
 // (S[m-1][n] + S[m][n-1]), S = 0 outside the coarse grid; store(o, c, g) takes coordinate c of own point o's gradient.
 // OWN_X: the points are X's, dk/dx = -2 inv_h (x - y) k (RBF) or y (linear); else Y's, dk/dy = 2 inv_h (x - y) k or x.
+// The radial kinds: RBF's with -phi'(s) for k.
 template <int KIND, bool OWN_X, typename IO, typename Store>
 __device__ __forceinline__ void static_grad_pass(const RingWave &rw, const IO *own, int To, const IO *oth, int Tt, int d,
                                                  double inv_h, Store &&store)
@@ -145,7 +179,17 @@ __device__ __forceinline__ void static_grad_pass(const RingWave &rw, const IO *o
                 nb_prev = nb;
                 const IO *pt = oth + (size_t)t * d;
                 const IO *xm = OWN_X ? po : pt, *yn = OWN_X ? pt : po;
-                if (KIND == SIGSVGD_STATIC_RBF) {
+                if constexpr (kRadialKind<KIND>) { // RBF's contraction with -phi'(s) in place of exp(-s)
+                    double dist = 0.0;
+                    for (int c = 0; c < d; ++c) {
+                        const double u = (double)xm[c] - (double)yn[c];
+                        dist = __builtin_fma(u, u, dist);
+                    }
+                    const double rk = R * radial_slope<KIND>(dist * inv_h);
+#pragma unroll
+                    for (int c = 0; c < 16; ++c)
+                        if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
+                } else if (KIND == SIGSVGD_STATIC_RBF) {
                     double dist = 0.0;
                     for (int c = 0; c < d; ++c) {
                         const double u = (double)xm[c] - (double)yn[c];
@@ -165,7 +209,9 @@ __device__ __forceinline__ void static_grad_pass(const RingWave &rw, const IO *o
 #pragma unroll
                 for (int c = 0; c < 16; ++c)
                     if (c0 + c < d)
-                        store(o, c0 + c, KIND == SIGSVGD_STATIC_RBF ? ((OWN_X ? -2.0 : 2.0) * inv_h) * accv[c] : accv[c]);
+                        store(o, c0 + c, KIND == SIGSVGD_STATIC_RBF || kRadialKind<KIND>
+                                             ? ((OWN_X ? -2.0 : 2.0) * inv_h) * accv[c]
+                                             : accv[c]);
             }
         }
     }

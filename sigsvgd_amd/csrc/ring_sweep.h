@@ -89,7 +89,8 @@ int ring_plan_total(size_t *bytes, Make &&make)
 // A family F names its kernels: F::Args (the kernel's one argument), F::kernel<IO, NAIVE, GRAD, KIND>() (the instantiation's
 // address), F::has_kind (false: one kernel for every static kernel, KIND = 0), F::has_fwd_only (false: GRAD = true only) and
 // the two texts of a failure.  ring_launch maps the runtime (dtype, kind, naive, grad) to the instantiation, raises its LDS
-// limit and launches pl.grid wavefronts with pl.lds bytes of LDS each; only instantiations the family has are named.
+// limit and launches pl.grid wavefronts with pl.lds bytes of LDS each; only instantiations the family has are named.  The
+// kinds SIGSVGD_STATIC_IMQ and _RQ are instantiated with the default stencil only.
 template <typename F, typename IO, bool NAIVE, bool GRAD, int KIND, typename Plan>
 hipError_t ring_launch_one(const Plan &pl, hipStream_t stream, const typename F::Args &a)
 {
@@ -102,18 +103,30 @@ hipError_t ring_launch_one(const Plan &pl, hipStream_t stream, const typename F:
 template <typename F, typename IO, int KIND, typename Plan>
 hipError_t ring_launch_solver(bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
 {
-    if constexpr (F::has_fwd_only) {
-        if (!grad)
-            return naive ? ring_launch_one<F, IO, true, false, KIND>(pl, stream, a)
-                         : ring_launch_one<F, IO, false, false, KIND>(pl, stream, a);
+    // (IMQ and rational quadratic have the default stencil only: the entry points refuse NAIVE_SOLVER before this)
+    constexpr bool has_naive = KIND == SIGSVGD_STATIC_RBF || KIND == SIGSVGD_STATIC_LINEAR;
+    if constexpr (!has_naive) {
+        if (naive) return hipErrorInvalidValue;
+        if constexpr (F::has_fwd_only) {
+            if (!grad) return ring_launch_one<F, IO, false, false, KIND>(pl, stream, a);
+        }
+        return ring_launch_one<F, IO, false, true, KIND>(pl, stream, a);
+    } else {
+        if constexpr (F::has_fwd_only) {
+            if (!grad)
+                return naive ? ring_launch_one<F, IO, true, false, KIND>(pl, stream, a)
+                             : ring_launch_one<F, IO, false, false, KIND>(pl, stream, a);
+        }
+        return naive ? ring_launch_one<F, IO, true, true, KIND>(pl, stream, a)
+                     : ring_launch_one<F, IO, false, true, KIND>(pl, stream, a);
     }
-    return naive ? ring_launch_one<F, IO, true, true, KIND>(pl, stream, a)
-                 : ring_launch_one<F, IO, false, true, KIND>(pl, stream, a);
 }
 template <typename F, typename IO, typename Plan>
 hipError_t ring_launch_kind(int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
 {
     if constexpr (F::has_kind) {
+        if (kind == SIGSVGD_STATIC_IMQ) return ring_launch_solver<F, IO, SIGSVGD_STATIC_IMQ>(naive, grad, pl, stream, a);
+        if (kind == SIGSVGD_STATIC_RQ) return ring_launch_solver<F, IO, SIGSVGD_STATIC_RQ>(naive, grad, pl, stream, a);
         if (kind != SIGSVGD_STATIC_RBF) return ring_launch_solver<F, IO, SIGSVGD_STATIC_LINEAR>(naive, grad, pl, stream, a);
     }
     return ring_launch_solver<F, IO, SIGSVGD_STATIC_RBF>(naive, grad, pl, stream, a);

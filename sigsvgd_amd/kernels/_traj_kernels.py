@@ -1,4 +1,5 @@
-"""Trajectory kernels: `BatchGaussianKernel` (static RBF on path points) and `SignatureKernel` (signature
+"""Trajectory kernels: `BatchGaussianKernel` (static RBF on path points; `BatchIMQKernel` and
+`BatchRationalQuadraticKernel` are its heavy-tailed siblings) and `SignatureKernel` (signature
 kernel via the Goursat PDE) -- reference src/kernels/_traj_kernels.py:147-206 -- backed by the HIP library
 instead of `sigkernel`; `PathSigKernel` (static kernel on truncated signatures, :72-144) backed by the HIP
 signature kernel instead of `signatory`; `TrajectoryKernel` (:14-69)."""
@@ -7,7 +8,7 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
-from ..sigkernel import SigKernel, gram_sqdist, inv_bandwidth_from_fn
+from ..sigkernel import SigKernel, batch_sqdist, gram_sqdist, inv_bandwidth_from_fn, radial_power
 from ._kernels import BaseKernel, GaussianKernel, _SqDist, kernel_output, scalar_function
 
 class TrajectoryKernel(BaseKernel):
@@ -86,13 +87,58 @@ class BatchGaussianKernel(BaseKernel):
         return inv_bandwidth_from_fn(self.get_bandwidth, X, Y)
 
 
-class SignatureKernel:
-    """Signature kernel with an RBF static kernel; `depth` is the DYADIC ORDER of the PDE solver
-    (not a truncation level).  Unknown keyword arguments are accepted and ignored, as in the
-    reference (examples/script_planning_robot.py:391 passes `bandwidth=`)."""
+class BatchIMQKernel(BaseKernel):
+    """Inverse multiquadric on path points, k(x, y) = (1 + |x-y|^2 / h)^(-1/2), h = bandwidth_fn(dist): heavy-tailed where
+    the RBF kernel underflows.  Bandwidths resolve as BatchGaussianKernel's do (`inv_bandwidth_from_fn`: constant functions
+    form no distances, the default median comes from the select on the device)."""
 
-    def __init__(self, bandwidth_fn: scalar_function = None, depth: int = 3, **kwargs):
-        static_kernel = BatchGaussianKernel(bandwidth_fn=bandwidth_fn)
+    static_kind = _lib.STATIC_IMQ
+    power = -0.5
+
+    def __init__(self, bandwidth_fn: scalar_function = None, **kwargs):
+        super().__init__(bandwidth_fn, analytic_grad=False, **kwargs)
+
+    def __call__(self, X: torch.Tensor, Y: torch.Tensor, **kwargs) -> kernel_output:
+        return self.batch_kernel(X, Y, **kwargs)
+
+    def _of(self, dist, h):
+        return radial_power(dist, self.get_bandwidth(dist) if h is None else float(h), self.power)
+
+    def batch_kernel(self, X, Y, h=None):
+        """X [batch, len_X, dim], Y [batch, len_Y, dim] -> k(X^i_s, Y^i_t) [batch, len_X, len_Y]."""
+        return self._of(batch_sqdist(X, Y), h)
+
+    def Gram_matrix(self, X, Y, h=None):
+        """X [A, len_X, dim], Y [B, len_Y, dim] -> k(X^i_s, Y^j_t) [A, B, len_X, len_Y]."""
+        return self._of(gram_sqdist(X, Y), h)
+
+    def inv_bandwidth(self, X, Y) -> float:
+        """1/h for the fused HIP path (constant bandwidth functions never form the distance tensor)."""
+        return inv_bandwidth_from_fn(self.get_bandwidth, X, Y)
+
+
+class BatchRationalQuadraticKernel(BatchIMQKernel):
+    """Rational quadratic kernel on path points, k(x, y) = (1 + |x-y|^2 / h)^(-1), h = bandwidth_fn(dist)."""
+
+    static_kind = _lib.STATIC_RQ
+    power = -1.0
+
+
+_STATIC_BY_NAME = {"rbf": BatchGaussianKernel, "imq": BatchIMQKernel, "rq": BatchRationalQuadraticKernel}
+
+
+class SignatureKernel:
+    """Signature kernel with a static kernel on path points; `depth` is the DYADIC ORDER of the PDE solver
+    (not a truncation level).  static_kernel: None or "rbf" (the reference's RBF), "imq", "rq" (each built on
+    `bandwidth_fn`), or a static-kernel instance, used as it is.  Unknown keyword arguments are accepted and ignored, as in
+    the reference (examples/script_planning_robot.py:391 passes `bandwidth=`)."""
+
+    def __init__(self, bandwidth_fn: scalar_function = None, depth: int = 3, static_kernel=None, **kwargs):
+        if static_kernel is None or isinstance(static_kernel, str):
+            name = "rbf" if static_kernel is None else static_kernel.lower()
+            if name not in _STATIC_BY_NAME:
+                raise ValueError(f'static_kernel must be one of {sorted(_STATIC_BY_NAME)} or an instance, got {static_kernel!r}')
+            static_kernel = _STATIC_BY_NAME[name](bandwidth_fn=bandwidth_fn)
         self.kernel = SigKernel(static_kernel, dyadic_order=depth)
 
     def __call__(self, X, Y, **kwargs):

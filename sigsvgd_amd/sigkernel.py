@@ -15,10 +15,12 @@ sigsvgd_amd.sigkernel` makes the reference's own code run o
 for X only (None for everything else), like upstream; `grad_Y=True` adds the second-slot gradient for Y.  `compute_kernel` (and `compute_distance` on it) solves each pair
 (X_i, Y_i) once and differentiates both paths, each in its own slot.
 
-Static kernels.  `RBFKernel`, `LinearKernel`, anything with `static_kind` + `inv_bandwidth` and the reference's own
-`BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
+Static kernels.  `RBFKernel`, `LinearKernel`, the heavy-tailed `IMQStaticKernel` and `RationalQuadraticKernel`, anything with
+`static_kind` + `inv_bandwidth` (`sigsvgd_amd.kernels.BatchGaussianKernel`, `BatchIMQKernel`, `BatchRationalQuadraticKernel`)
+and the reference's own `BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
 the fused kernels' LDS take the long route (csrc/gram_long.hip), which evaluates the static kernel inside its PDE sweep
-(P, Q <= 8192 refined cells).  A `BatchGaussianKernel` without a `bandwidth_fn` (the reference's default, the median
+(P, Q <= 8192 refined cells).  RBF alone has the fp32-sweep kernels; the linear, IMQ and rational-quadratic kernels run
+on the fp64 coverage kernel and the long route (there with the default stencil only: DESIGN.md section 5.15).  A `BatchGaussianKernel` without a `bandwidth_fn` (the reference's default, the median
 heuristic) takes its median from an exact select on the device (`ops.path_sqdist_select`), at any batch size.  Any other object with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally,
 `batch_kernel(X, Y) -> [A,M,N]`) is a USER static kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
 the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
@@ -33,7 +35,7 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["SigKernel", "RBFKernel", "LinearKernel", "gram_and_grad"]
+__all__ = ["SigKernel", "RBFKernel", "LinearKernel", "IMQStaticKernel", "RationalQuadraticKernel", "gram_and_grad"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -78,6 +80,46 @@ class RBFKernel:
         dist = -2.0 * torch.einsum("ipk,jqk->ijpq", X, Y)
         dist = dist + Xs[:, None, :, None] + Ys[None, :, None, :]
         return torch.exp(-dist / self.sigma)
+
+
+def batch_sqdist(X, Y):
+    """dist[i,p,q] = |X_ip - Y_iq|^2 of paired batches X [A,M,d], Y [A,N,d]"""
+    Xs = torch.sum(X**2, dim=2)
+    Ys = torch.sum(Y**2, dim=2)
+    dist = -2.0 * torch.bmm(X, Y.permute(0, 2, 1))
+    return dist + Xs[:, :, None] + Ys[:, None, :]
+
+
+def radial_power(dist, h, power):
+    """(1 + dist / h)^power: the IMQ (power -1/2) and rational-quadratic (power -1) kernels of a squared distance"""
+    return (1.0 + dist / h) ** power
+
+
+class IMQStaticKernel:
+    """k(x, y) = (1 + |x-y|^2 / sigma)^(-1/2): the inverse multiquadric, whose tail decays like 1/|x-y| where RBF's
+    underflows (distant paths keep a non-zero signature-kernel gradient)."""
+
+    static_kind = _lib.STATIC_IMQ
+    power = -0.5
+
+    def __init__(self, sigma):
+        self.sigma = sigma
+
+    def inv_bandwidth(self, X, Y) -> float:
+        return 1.0 / float(self.sigma)
+
+    def batch_kernel(self, X, Y):
+        return radial_power(batch_sqdist(X, Y), self.sigma, self.power)
+
+    def Gram_matrix(self, X, Y):
+        return radial_power(gram_sqdist(X, Y), self.sigma, self.power)
+
+
+class RationalQuadraticKernel(IMQStaticKernel):
+    """k(x, y) = (1 + |x-y|^2 / sigma)^(-1): the rational quadratic kernel of shape parameter 1."""
+
+    static_kind = _lib.STATIC_RQ
+    power = -1.0
 
 
 # refuse to materialise distance tensors larger than this for data-dependent bandwidths
@@ -194,7 +236,8 @@ def _resolve_static(static_kernel, X, Y):
         return None, None
     raise NotImplementedError(
         f"static kernel {type(static_kernel).__name__} is not supported by the HIP path: it needs upstream's "
-        "Gram_matrix(X, Y) (fused: RBFKernel, LinearKernel, BatchGaussianKernel)"
+        "Gram_matrix(X, Y) (fused: RBFKernel, LinearKernel, IMQStaticKernel, RationalQuadraticKernel, BatchGaussianKernel, "
+        "BatchIMQKernel, BatchRationalQuadraticKernel)"
     )
 
 
