@@ -9,26 +9,11 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import sigkernel_oracle as O
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5  # north_star tolerance (K per entry; gradients relative to max-abs)
-
-
-def _paths(A, T, d, seed, scale=0.3, offset=0.0):
-    rng = np.random.default_rng(seed)
-    return (np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1) + offset).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
-
-
-def _relK(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    # (round 4: plain relative error per entry -- rounds 2-3 floored the denominator at 0.1; the 1e-6 only keeps an exact zero
-    #  out of it.  Pairs whose K is small against their grid are solved by the exact fp64 pass now: DESIGN.md section 3)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 # T, dyadic order, d  (refined cells per side = (T - 1) * 2^n)
@@ -53,7 +38,7 @@ def test_dyadic_general_xy(gpu, T, n, d, dtype):
     from sigsvgd_amd import ops
 
     A, B = 11, 9
-    X, Y = _paths(A, T, d, 1), _paths(B, T, d, 2)
+    X, Y = walks(A, T, d, 1, 0.3), walks(B, T, d, 2, 0.3)
     h = 1.7
     go = np.random.default_rng(3).standard_normal((A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, n, grad_out=go.astype(np.float64))
@@ -62,10 +47,11 @@ def test_dyadic_general_xy(gpu, T, n, d, dtype):
     K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, n, grad_out=gog)
     torch.cuda.synchronize()
     assert K2.dtype == dtype and g2.dtype == dtype
-    assert _relK(K1.cpu().numpy(), Kref) < TOL and _relK(K2.cpu().numpy(), Kref) < TOL
-    assert _rel(g2.cpu().numpy(), gref) < TOL
+    assert rel_entry(K1.cpu().numpy(), Kref, 1e-6) < TOL and rel_entry(K2.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g2.cpu().numpy(), gref) < TOL
     K3, g3 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, n, grad_out=gog, force_generic=True)
-    assert _relK(K2.cpu().numpy(), K3.double().cpu().numpy()) < TOL and _rel(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
+    assert rel_entry(K2.cpu().numpy(), K3.double().cpu().numpy(), 1e-6) < TOL
+    assert rel_max(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
 
 
 @pytest.mark.parametrize("T,n,d", SHAPES)
@@ -75,7 +61,7 @@ def test_dyadic_symmetric(gpu, T, n, d, weights):
     from sigsvgd_amd import ops
 
     N = 19
-    X = _paths(N, T, d, 5)
+    X = walks(N, T, d, 5, 0.3)
     h = 0.9
     go, sym = None, False
     if weights != "ones":
@@ -88,12 +74,12 @@ def test_dyadic_symmetric(gpu, T, n, d, weights):
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, grad_out=gog, sym=sym, y_is_x=True)
     torch.cuda.synchronize()
     Kn = K.cpu().numpy()
-    assert _relK(Kn, Kref) < TOL and np.array_equal(Kn, Kn.T)
-    assert _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(Kn, Kref, 1e-6) < TOL and np.array_equal(Kn, Kn.T)
+    assert rel_max(g.cpu().numpy(), gref) < TOL
     K2, g2 = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, grad_out=gog, sym=sym, y_is_x=True)
     assert torch.equal(K, K2) and torch.equal(g, g2)  # reproducible bits
     Kf = ops.gram_fwd(Xg, Xg, 1.0 / h, n, y_is_x=True)
-    assert _relK(Kf.cpu().numpy(), Kref) < TOL
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
 
 
 def test_refined_grid_kernel_large_launch(gpu, monkeypatch):
@@ -103,15 +89,15 @@ def test_refined_grid_kernel_large_launch(gpu, monkeypatch):
 
     monkeypatch.setenv("SIGSVGD_BAND_MODE", "serial")
     N, T, d, n, h = 300, 5, 2, 5, 1.0
-    X = _paths(N, T, d, 12, 0.3)
+    X = walks(N, T, d, 12, 0.3)
     Xg = torch.as_tensor(X, device=gpu)
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, y_is_x=True)
     Kref, gref = C.gram_fwd_bwd(X, X, h, n, rows=(0, 6))
-    assert _relK(K.cpu().numpy()[:6], Kref) < TOL
+    assert rel_entry(K.cpu().numpy()[:6], Kref, 1e-6) < TOL
     assert np.abs(g.cpu().numpy()[:6] - gref).max() / np.abs(g.cpu().numpy()).max() < TOL
     monkeypatch.setenv("SIGSVGD_BAND_MODE", "parallel")
     Kp, gp = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, y_is_x=True)
-    assert _relK(Kp.cpu().numpy(), K.double().cpu().numpy()) < TOL and _rel(gp.cpu().numpy(), g.double().cpu().numpy()) < TOL
+    assert rel_entry(Kp.cpu().numpy(), K.double().cpu().numpy(), 1e-6) < TOL and rel_max(gp.cpu().numpy(), g.double().cpu().numpy()) < TOL
 
 
 def test_dyadic_reference_shapes_at_their_sizes(gpu):
@@ -124,17 +110,18 @@ def test_dyadic_reference_shapes_at_their_sizes(gpu):
     #  launcher's own rule; the notebook and maze sizes take the band-parallel kernel)
     for N, T, d, n, h in [(30, 5, 2, 5, 0.9), (16, 20, 2, 2, 1.0), (300, 5, 2, 5, 1.0), (100, 10, 2, 4, 5.0), (35, 30, 2, 3, 5.6),
                           (150, 10, 2, 4, 5.0)]:
-        X = _paths(N, T, d, 11, 0.3)
+        X = walks(N, T, d, 11, 0.3)
         Xg = torch.as_tensor(X, device=gpu)
         K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, y_is_x=True)
         rows = (0, min(N, 6))
         Kref, gref = C.gram_fwd_bwd(X, X, h, n, rows=rows)
-        assert _relK(K.cpu().numpy()[rows[0]:rows[1]], Kref) < TOL
+        assert rel_entry(K.cpu().numpy()[rows[0]:rows[1]], Kref, 1e-6) < TOL
         gfull = np.abs(g.cpu().numpy()).max()
         assert np.abs(g.cpu().numpy()[rows[0]:rows[1]] - gref).max() / gfull < TOL
         Ko, go_ = ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0 / h, n)
-        assert _relK(Ko.cpu().numpy(), K.double().cpu().numpy()) < TOL  # (two orientations of a pair: both within TOL of the oracle)
-        assert _rel(go_.cpu().numpy(), g.double().cpu().numpy()) < TOL
+        # (two orientations of a pair: both within TOL of the oracle)
+        assert rel_entry(Ko.cpu().numpy(), K.double().cpu().numpy(), 1e-6) < TOL
+        assert rel_max(go_.cpu().numpy(), g.double().cpu().numpy()) < TOL
 
 
 @pytest.mark.parametrize("T,n,d,scale,h,offset", [(30, 3, 2, 0.5, 3.0, 100.0), (30, 3, 2, 0.5, 1.0, 100.0), (30, 3, 2, 0.1, 0.1, 0.0),
@@ -145,14 +132,14 @@ def test_band_kernel_rough_and_smooth_extremes(gpu, T, n, d, scale, h, offset):
     full-magnitude add of the forward sweep runs in two floats (order 6, 256 cells, smooth paths: 1.2e-5 without)."""
     from sigsvgd_amd import ops
 
-    X = _paths(12, T, d, 0, scale=scale, offset=offset)
+    X = walks(12, T, d, 0, scale=scale, offset=offset)
     Kref, gref = C.gram_fwd_bwd(X, X, h, n)
     Xg = torch.as_tensor(X, device=gpu)
     for K, g in [ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, y_is_x=True), ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0 / h, n)]:
-        assert _relK(K.cpu().numpy(), Kref) < 5e-6
-        assert _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 5e-6
+        assert rel_max(g.cpu().numpy(), gref) < TOL
     for K in [ops.gram_fwd(Xg, Xg, 1.0 / h, n, y_is_x=True), ops.gram_fwd(Xg, Xg.clone(), 1.0 / h, n)]:
-        assert _relK(K.cpu().numpy(), Kref) < 5e-6
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 5e-6
 
 
 @pytest.mark.parametrize("T,n,d", BAND_SHAPES)
@@ -166,8 +153,8 @@ def test_band_kernels_agree(gpu, monkeypatch, T, n, d, sym):
     from sigsvgd_amd import ops
 
     A, B = 11, 11 if sym else 7
-    X = _paths(A, T, d, 21, 0.2)
-    Y = X if sym else _paths(B, T, d, 22, 0.2)
+    X = walks(A, T, d, 21, 0.2)
+    Y = X if sym else walks(B, T, d, 22, 0.2)
     go = np.random.default_rng(3).uniform(0.5, 1.5, (A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, 1.0, n, grad_out=go.astype(np.float64))
     Xg, gog = torch.as_tensor(X, device=gpu), torch.as_tensor(go, device=gpu)
@@ -180,12 +167,12 @@ def test_band_kernels_agree(gpu, monkeypatch, T, n, d, sym):
         K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0, n, grad_out=gog, y_is_x=sym)
         torch.cuda.synchronize()
         assert torch.equal(K, K2) and torch.equal(g, g2)  # (reproducible, each of them)
-        assert _relK(K.cpu().numpy(), Kref) < TOL and _relK(Kf.cpu().numpy(), Kref) < TOL
-        assert _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
+        assert rel_max(g.cpu().numpy(), gref) < TOL
         res[mode] = (K.cpu().numpy(), Kf.cpu().numpy(), g.cpu().numpy())
     assert np.array_equal(res["serial"][0], res["parallel"][0])
     assert np.array_equal(res["serial"][1], res["parallel"][1])
-    assert _rel(res["parallel"][2], res["serial"][2].astype(np.float64)) < 2e-6
+    assert rel_max(res["parallel"][2], res["serial"][2].astype(np.float64)) < 2e-6
 
 
 @pytest.mark.parametrize("T,n,d", [s for s in SHAPES if 64 < (s[0] - 1) << s[1] <= 128 and s[1] >= 2])
@@ -197,8 +184,8 @@ def test_refined_shapes_on_both_kernels(gpu, monkeypatch, T, n, d, sym):
     from sigsvgd_amd import ops
 
     A, B = 11, 11 if sym else 7
-    X = _paths(A, T, d, 31, 0.2)
-    Y = X if sym else _paths(B, T, d, 32, 0.2)
+    X = walks(A, T, d, 31, 0.2)
+    Y = X if sym else walks(B, T, d, 32, 0.2)
     go = np.random.default_rng(4).uniform(0.5, 1.5, (A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, 1.0, n, grad_out=go.astype(np.float64))
     Xg, gog = torch.as_tensor(X, device=gpu), torch.as_tensor(go, device=gpu)
@@ -211,7 +198,7 @@ def test_refined_shapes_on_both_kernels(gpu, monkeypatch, T, n, d, sym):
         K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0, n, grad_out=gog, y_is_x=sym)
         torch.cuda.synchronize()
         assert torch.equal(K, K2) and torch.equal(g, g2)
-        assert _relK(K.cpu().numpy(), Kref) < TOL and _relK(Kf.cpu().numpy(), Kref) < TOL
-        assert _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
+        assert rel_max(g.cpu().numpy(), gref) < TOL
         res[mode] = K.cpu().numpy()
-    assert _relK(res["parallel"], res["serial"].astype(np.float64)) < TOL
+    assert rel_entry(res["parallel"], res["serial"].astype(np.float64), 1e-6) < TOL

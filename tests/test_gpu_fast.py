@@ -5,6 +5,7 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import sigkernel_oracle as O
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 
@@ -12,23 +13,6 @@ TOL = 1e-5  # north_star tolerance (relative; gradients relative to max-abs)
 # two fp32-sweep solves of one pair that differ in orientation (the symmetric launch solves (i, j), the ordered one also
 # (j, i)) or launch geometry agree to a few ulps PER ENTRY; both are within TOL of the fp64 oracle
 SELF = 4e-6
-
-
-def _paths(A, T, d, seed, scale=0.05, offset=0.0):
-    rng = np.random.default_rng(seed)
-    return (np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1) + offset).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
-
-
-def _relK(a, b):
-    """K parity as north_star states it: max over entries of |K - K_ref| / |K_ref| (K > 0 always)"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    # (round 4: plain relative error per entry -- rounds 2-3 floored the denominator at 0.1; the 1e-6 only keeps an exact zero
-    #  out of it.  Pairs whose K is small against their grid are solved by the exact fp64 pass now: DESIGN.md section 3)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 SHAPES = [
@@ -50,7 +34,7 @@ def test_fast_general_xy(gpu, A, B, T, d, dtype):
     """X != Y: ordered pairs, row-side gradient only, arbitrary grad_out."""
     from sigsvgd_amd import ops
 
-    X, Y = _paths(A, T, d, 1), _paths(B, T, d, 2)
+    X, Y = walks(A, T, d, 1, 0.05), walks(B, T, d, 2, 0.05)
     h = 1.3
     go = np.random.default_rng(3).standard_normal((A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go.astype(np.float64))
@@ -58,12 +42,12 @@ def test_fast_general_xy(gpu, A, B, T, d, dtype):
     K1 = ops.gram_fwd(Xg, Yg, 1.0 / h)
     K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog)
     torch.cuda.synchronize()
-    assert _relK(K1.cpu().numpy(), Kref) < TOL
-    assert _relK(K2.cpu().numpy(), Kref) < TOL
-    assert _rel(g2.cpu().numpy(), gref) < TOL
+    assert rel_entry(K1.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_entry(K2.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g2.cpu().numpy(), gref) < TOL
     # and it agrees with the generic kernel
     K3, g3 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog, force_generic=True)
-    assert _rel(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
+    assert rel_max(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
 
 
 @pytest.mark.parametrize("N,T,d", [(19, 64, 7), (8, 64, 7), (33, 32, 7), (12, 64, 3), (16, 20, 2), (13, 40, 14)])
@@ -72,7 +56,7 @@ def test_fast_symmetric(gpu, N, T, d, weights):
     """Y is X: unordered pairs solved once, row- and column-side gradients."""
     from sigsvgd_amd import ops
 
-    X = _paths(N, T, d, 5)
+    X = walks(N, T, d, 5, 0.05)
     h = 0.9
     go = None
     sym = False
@@ -86,20 +70,20 @@ def test_fast_symmetric(gpu, N, T, d, weights):
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, grad_out=gog, sym=sym, y_is_x=True)
     torch.cuda.synchronize()
     Kn = K.cpu().numpy()
-    assert _relK(Kn, Kref) < TOL
+    assert rel_entry(Kn, Kref, 1e-6) < TOL
     assert np.array_equal(Kn, Kn.T)  # mirrored entries are the same solve
-    assert _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_max(g.cpu().numpy(), gref) < TOL
 
 
 def test_fast_far_from_origin(gpu):
     """Per-pair centring: particles far from the origin keep full accuracy."""
     from sigsvgd_amd import ops
 
-    X = _paths(12, 64, 7, 11, offset=100.0)
+    X = walks(12, 64, 7, 11, 0.05, offset=100.0)
     Kref, gref = O.gram_backward(X, X, None, O.RBF, 1.0, 0)
     K, g = ops.gram_fwd_bwd(torch.as_tensor(X, device=gpu), torch.as_tensor(X, device=gpu), 1.0, y_is_x=True)
-    assert _relK(K.cpu().numpy(), Kref) < TOL
-    assert _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g.cpu().numpy(), gref) < TOL
 
 
 def test_fast_c4_rows(gpu):
@@ -116,7 +100,7 @@ def test_fast_c4_rows(gpu):
     assert np.array_equal(Kn, Kn.T)
     for rows in [(0, 4), (511, 515), (1020, 1024)]:
         Kref, gref = C.gram_fwd_bwd(X.numpy(), X.numpy(), 1.0, 0, rows=rows)
-        assert _relK(Kn[rows[0]:rows[1]], Kref) < TOL
+        assert rel_entry(Kn[rows[0]:rows[1]], Kref, 1e-6) < TOL
         assert np.abs(gn[rows[0]:rows[1]] - gref).max() / np.abs(gref).max() < TOL
 
 
@@ -125,15 +109,15 @@ def test_fast_edge_shapes(gpu, A, B, T, d):
     """single rows/columns, ragged row tiles, exact-fit channel padding (d = 8, 16)"""
     from sigsvgd_amd import ops
 
-    X, Y = _paths(A, T, d, 21), _paths(B, T, d, 22)
+    X, Y = walks(A, T, d, 21, 0.05), walks(B, T, d, 22, 0.05)
     Kref, gref = C.gram_fwd_bwd(X, Y, 0.8, 0)
     Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
     K, g = ops.gram_fwd_bwd(Xg, Yg, 1 / 0.8)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
     if A == B:
         Kr, gr = C.gram_fwd_bwd(X, X, 0.8, 0)
         K2, g2 = ops.gram_fwd_bwd(Xg, Xg, 1 / 0.8, y_is_x=True)
-        assert _relK(K2.cpu().numpy(), Kr) < TOL and _rel(g2.cpu().numpy(), gr) < TOL
+        assert rel_entry(K2.cpu().numpy(), Kr, 1e-6) < TOL and rel_max(g2.cpu().numpy(), gr) < TOL
 
 
 def test_fast_fp64_io_symmetric_and_noncontiguous(gpu):
@@ -141,13 +125,13 @@ def test_fast_fp64_io_symmetric_and_noncontiguous(gpu):
     and a non-contiguous view as input"""
     from sigsvgd_amd import ops
 
-    Xbig = torch.as_tensor(_paths(20, 64, 14, 31), device=gpu).double()
+    Xbig = torch.as_tensor(walks(20, 64, 14, 31, 0.05), device=gpu).double()
     Xv = Xbig[:, :, ::2]  # [20, 64, 7] strided view
     assert not Xv.is_contiguous()
     Kref, gref = O.gram_backward(Xv.cpu().numpy(), Xv.cpu().numpy(), None, O.RBF, 1.0, 0)
     K, g = ops.gram_fwd_bwd(Xv, Xv, 1.0, y_is_x=True)
     assert K.dtype == torch.float64 and g.dtype == torch.float64
-    assert _relK(K.cpu().numpy(), Kref) < SELF and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < SELF and rel_max(g.cpu().numpy(), gref) < TOL
 
 
 def test_argument_errors(gpu):
@@ -176,11 +160,11 @@ def test_forward_only_symmetric_solve(gpu, N, T, d):
     """gram_fwd(X, X, y_is_x=True): each unordered pair once, K mirrored == the ordered forward launch"""
     from sigsvgd_amd import ops
 
-    X = torch.as_tensor(_paths(N, T, d, 31), device=gpu)
+    X = torch.as_tensor(walks(N, T, d, 31, 0.05), device=gpu)
     K1 = ops.gram_fwd(X, X, 1.0, y_is_x=True)
     K0 = ops.gram_fwd(X, X.clone(), 1.0)
     assert torch.equal(K1, K1.T)
-    assert _relK(K1.cpu().numpy(), K0.double().cpu().numpy()) < SELF
+    assert rel_entry(K1.cpu().numpy(), K0.double().cpu().numpy(), 1e-6) < SELF
 
 
 @pytest.mark.parametrize("T,d,scale,h", [(64, 2, 0.1, 0.1), (64, 2, 0.2, 0.1), (64, 2, 0.5, 1.0), (64, 2, 0.05, 0.02),
@@ -192,7 +176,7 @@ def test_fast_oscillating_solutions_per_entry(gpu, T, d, scale, h):
     resweep_fwd_fp64): every entry is inside the tolerance, in every launch form."""
     from sigsvgd_amd import ops
 
-    X = _paths(12, T, d, 0, scale=scale)
+    X = walks(12, T, d, 0, scale=scale)
     Kref, gref = C.gram_fwd_bwd(X, X, h, 0)
     assert Kref.min() < 0.5  # (the regime the test is about: solutions that cancel)
     Xg = torch.as_tensor(X, device=gpu)
@@ -200,7 +184,7 @@ def test_fast_oscillating_solutions_per_entry(gpu, T, d, scale, h):
     fwd = [ops.gram_fwd(Xg, Xg, 1.0 / h, y_is_x=True), ops.gram_fwd(Xg, Xg.clone(), 1.0 / h)]
     torch.cuda.synchronize()
     for K, g in outs:
-        assert _relK(K.cpu().numpy(), Kref) < 5e-6
-        assert _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 5e-6
+        assert rel_max(g.cpu().numpy(), gref) < TOL
     for K in fwd:
-        assert _relK(K.cpu().numpy(), Kref) < 5e-6
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 5e-6

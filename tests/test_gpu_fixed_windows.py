@@ -9,32 +9,18 @@ forms, 14 the unpadded one), ordered and Y-is-X launches with signed weights, si
 (asserted from the launch geometry), and both shares of a two-rank partial solve.  One launch per shape is also held to the
 fp64 C oracle at the neighbouring files' 1e-5.  At T = 63 and T = 65, and for forward-only launches at T = 64, the variable
 changes nothing."""
-import numpy as np
 import pytest
 import torch
 
-from helpers import device_cus, gram_geometry, signed_weights
 from oracle import c_oracle as C
+from parity import rel_entry, rel_max, signed_weights, walks
+from plans import device_cus, gram_geometry
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5  # tests/test_gpu_partition.py, tests/test_gpu_fast.py
 HOOK = "SIGSVGD_SWEEP_WINDOWS"
 DS = [3, 7, 14]
-
-
-def _paths(A, T, d, seed, scale=0.05):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _relK(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 def _both(monkeypatch, run):
@@ -65,7 +51,7 @@ def test_ordered_launch_equals_table_path(gpu, monkeypatch, d):
 
     A, B, T, h = 67, 131, 64, 0.9
     _several_items(A, B, T, d, False)
-    X, Y = _paths(A, T, d, 11), _paths(B, T, d, 12)
+    X, Y = walks(A, T, d, 11, 0.05), walks(B, T, d, 12, 0.05)
     go = signed_weights(A, B, 13)
     Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
     gog = torch.as_tensor(go, device=gpu, dtype=torch.float32)
@@ -73,7 +59,7 @@ def test_ordered_launch_equals_table_path(gpu, monkeypatch, d):
     assert torch.equal(K, Kt)
     assert torch.equal(gx, gxt)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go)
-    eK, eg = _relK(K.cpu().numpy(), Kref), _rel(gx.cpu().numpy(), gref)
+    eK, eg = rel_entry(K.cpu().numpy(), Kref, 1e-6), rel_max(gx.cpu().numpy(), gref)
     print(f"against the oracle: K {eK:.2e} gradient {eg:.2e}")
     assert eK < TOL and eg < TOL
 
@@ -86,7 +72,7 @@ def test_symmetric_launch_equals_table_path(gpu, monkeypatch, d, weights):
 
     N, T, h = 264, 64, 1.1
     _several_items(N, N, T, d, True)
-    X = _paths(N, T, d, 21)
+    X = walks(N, T, d, 21, 0.05)
     Xg = torch.as_tensor(X, device=gpu)
     gog = None if weights == "ones" else torch.as_tensor(signed_weights(N, N, 23), device=gpu, dtype=torch.float32)
     sym = weights == "signed-sym"
@@ -102,7 +88,7 @@ def test_fp64_io_equals_table_path(gpu, monkeypatch, d):
     from sigsvgd_amd import ops
 
     N, T, h = 93, 64, 1.0
-    Xg = torch.as_tensor(_paths(N, T, d, 25), device=gpu).double()
+    Xg = torch.as_tensor(walks(N, T, d, 25, 0.05), device=gpu).double()
     gog = torch.as_tensor(signed_weights(N, N, 26), device=gpu, dtype=torch.float64)
     (K, gx), (Kt, gxt) = _both(monkeypatch, lambda: ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, 0, grad_out=gog, y_is_x=True))
     assert K.dtype == torch.float64 and torch.equal(K, Kt)
@@ -116,7 +102,7 @@ def test_partial_shares_equal_table_path(gpu, monkeypatch, d, fold):
     from sigsvgd_amd import ops
 
     N, T, h, world = 264, 64, 1.0, 2
-    X = _paths(N, T, d, 31)
+    X = walks(N, T, d, 31, 0.05)
     Xg = torch.as_tensor(X, device=gpu)
     gog = torch.as_tensor(signed_weights(N, N, 33), device=gpu, dtype=torch.float32)
     Ks = None
@@ -137,7 +123,7 @@ def test_hook_changes_nothing_at_other_lengths(gpu, monkeypatch, T, d):
     from sigsvgd_amd import ops
 
     N, h = 93, 1.0
-    X = _paths(N, T, d, 41)
+    X = walks(N, T, d, 41, 0.05)
     Xg = torch.as_tensor(X, device=gpu)
     go = signed_weights(N, N, 43)
     gog = torch.as_tensor(go, device=gpu, dtype=torch.float32)
@@ -148,7 +134,7 @@ def test_hook_changes_nothing_at_other_lengths(gpu, monkeypatch, T, d):
     assert torch.equal(Ko, Kot)
     assert torch.equal(gxo, gxot)
     Kref, gref = C.gram_fwd_bwd(X, X, h, 0, grad_out=go)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(gx.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(gx.cpu().numpy(), gref) < TOL
 
 
 @pytest.mark.parametrize("d", DS)
@@ -156,6 +142,6 @@ def test_forward_only_launch_has_the_table_path_only(gpu, monkeypatch, d):
     from sigsvgd_amd import ops
 
     N, T, h = 109, 64, 1.0
-    Xg = torch.as_tensor(_paths(N, T, d, 51), device=gpu)
+    Xg = torch.as_tensor(walks(N, T, d, 51, 0.05), device=gpu)
     K, Kt = _both(monkeypatch, lambda: ops.gram_fwd(Xg, Xg, 1.0 / h, 0, y_is_x=True))
     assert torch.equal(K, Kt)

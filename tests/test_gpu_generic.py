@@ -5,27 +5,11 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import sigkernel_oracle as O
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5  # north_star: within 1e-5 relative fp32
-
-
-def _paths(A, T, d, seed, scale=0.3):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
-
-
-def _relK(a, b):
-    """K parity as north_star states it: max over entries of |K - K_ref| / |K_ref| (K > 0 always)"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    # (round 4: plain relative error per entry -- rounds 2-3 floored the denominator at 0.1; the 1e-6 only keeps an exact zero
-    #  out of it.  Pairs whose K is small against their grid are solved by the exact fp64 pass now: DESIGN.md section 3)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 CASES = [
@@ -50,8 +34,8 @@ CASES = [
 def test_generic_fwd_bwd(gpu, A, B, T, d, n, kind, naive, dtype):
     from sigsvgd_amd import ops
 
-    X = _paths(A, T, d, 1)
-    Y = _paths(B, T, d, 2)
+    X = walks(A, T, d, 1, 0.3)
+    Y = walks(B, T, d, 2, 0.3)
     h = 1.7
     rng = np.random.default_rng(3)
     go = rng.standard_normal((A, B))
@@ -62,14 +46,14 @@ def test_generic_fwd_bwd(gpu, A, B, T, d, n, kind, naive, dtype):
     K1 = ops.gram_fwd(Xg, Yg, 1.0 / h, n, kind, naive=naive, force_generic=True)
     K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, n, kind, grad_out=gog, naive=naive, force_generic=True)
     torch.cuda.synchronize()
-    assert _relK(K1.cpu().numpy(), Kref) < TOL
-    assert _relK(K2.cpu().numpy(), Kref) < TOL
+    assert rel_entry(K1.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_entry(K2.cpu().numpy(), Kref, 1e-6) < TOL
     # grad_out is rounded to the I/O dtype on the way in
     gref_io = O.gram_backward(X, Y, gog.cpu().numpy().astype(np.float64), kind, h, n, naive)[1]
-    assert _rel(g2.cpu().numpy(), gref_io) < TOL
+    assert rel_max(g2.cpu().numpy(), gref_io) < TOL
     # ones path (NULL grad_out)
     K3, g3 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, n, kind, naive=naive, force_generic=True)
-    assert _rel(g3.cpu().numpy(), O.gram_backward(X, Y, None, kind, h, n, naive)[1]) < TOL
+    assert rel_max(g3.cpu().numpy(), O.gram_backward(X, Y, None, kind, h, n, naive)[1]) < TOL
 
 
 def test_phi(gpu):
@@ -84,10 +68,10 @@ def test_phi(gpu):
         X = rng.standard_normal((N, D)).astype(np.float32)
         vref = O.svgd_velocity(K, s, gk, m)
         v, Xn = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk, m)), X=torch.as_tensor(X, device=gpu), lr=0.1)
-        assert _rel(v.cpu().numpy(), vref) < TOL
-        assert _rel(Xn.cpu().numpy(), X - 0.1 * vref) < TOL
+        assert rel_max(v.cpu().numpy(), vref) < TOL
+        assert rel_max(Xn.cpu().numpy(), X - 0.1 * vref) < TOL
         v2 = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk)))
-        assert _rel(v2.cpu().numpy(), O.svgd_velocity(K, s, gk)) < TOL
+        assert rel_max(v2.cpu().numpy(), O.svgd_velocity(K, s, gk)) < TOL
 
 
 @pytest.mark.parametrize("N,T,d,n,kind", [(70, 10, 2, 4, 0), (66, 20, 2, 2, 0), (64, 5, 3, 5, 0), (65, 30, 2, 2, 0), (67, 12, 3, 1, 1),
@@ -111,9 +95,9 @@ def test_generic_symmetric_solve(gpu, N, T, d, n, kind, weights):
     gog = None if go is None else torch.as_tensor(go, device=gpu)
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, n, static_kind=kind, grad_out=gog, sym=sym, y_is_x=True, force_generic=True)
     assert torch.equal(K, K.T)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
     Kf = ops.gram_fwd(Xg, Xg, 1.0 / h, n, static_kind=kind, force_generic=True, y_is_x=True)
-    assert _relK(Kf.cpu().numpy(), Kref) < TOL
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
 
 
 @pytest.mark.parametrize("T,d,n,scale,h", [(64, 1, 0, 0.5, 1.0), (100, 1, 0, 0.1, 0.1), (100, 1, 0, 0.2, 0.1), (33, 1, 2, 0.2, 0.1),
@@ -132,8 +116,8 @@ def test_coverage_kernel_is_fp64_end_to_end(gpu, T, d, n, scale, h):
     Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
     K, g = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, n, force_generic=True)
     Kf = ops.gram_fwd(Xg, Yg, 1.0 / h, n, force_generic=True)
-    assert _relK(K.cpu().numpy(), Kref) < 2e-7
-    assert _relK(Kf.cpu().numpy(), Kref) < 2e-7
-    assert _rel(g.cpu().numpy(), gref) < 1e-6
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 2e-7
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < 2e-7
+    assert rel_max(g.cpu().numpy(), gref) < 1e-6
     K64, g64 = ops.gram_fwd_bwd(Xg.double(), Yg.double(), 1.0 / h, n, force_generic=True)
-    assert _relK(K64.cpu().numpy(), Kref) < 1e-10
+    assert rel_entry(K64.cpu().numpy(), Kref, 1e-6) < 1e-10

@@ -10,23 +10,12 @@ import pytest
 import torch
 
 from oracle import c_oracle
-from test_gpu_long import BRANCH_CASES, _branch_id, _regime, np64, oracle_at_own_lengths, paths, relK, relmax
-from test_long2_cabi import long2_plan
+from parity import DisguisedRBF, np64, rel_entry, rel_max, sized_walks
+from plans import BRANCH_CASES, branch_id, branch_regime, device_cus, long2_plan, oracle_at_own_lengths
 
 pytestmark = pytest.mark.gpu
 
 F64, F32 = torch.float64, torch.float32
-
-
-class DisguisedRBF:
-    """exp(-|x - y|^2 / sigma) behind upstream's interface only: the library cannot recognise it (user route)."""
-
-    def __init__(self, sigma):
-        self.sigma = sigma
-
-    def Gram_matrix(self, X, Y):
-        dist = (X**2).sum(-1)[:, None, :, None] + (Y**2).sum(-1)[None, :, None, :] - 2.0 * torch.einsum("ipk,jqk->ijpq", X, Y)
-        return torch.exp(-dist / self.sigma)
 
 
 def oracle_both_slots(X, Y, h, n, naive, kind, W, nthreads=0):
@@ -49,7 +38,7 @@ def check_two_slot(gpu, X, Y, h, n, kind, naive, io, W, nthreads=0):
     K, gX, gY = ops.gram_long_fwd_bwd2(Xt, Yt, 1.0 / h, n, kind, Wt, naive)
     assert K.shape == Kr.shape and gX.shape == Xt.shape and gY.shape == Yt.shape
     assert K.dtype == gX.dtype == gY.dtype == io
-    eK, eX, eY = relK(np64(K), Kr), relmax(np64(gX), gXr), relmax(np64(gY), gYr)
+    eK, eX, eY = rel_entry(np64(K), Kr, 0.0), rel_max(np64(gX), gXr), rel_max(np64(gY), gYr)
     print(f"two-slot K {eK:.3e} gX {eX:.3e} gY {eY:.3e}")
     assert eK < (1e-9 if io == F64 else 2.0**-23)
     assert eX < 1e-5
@@ -84,21 +73,19 @@ CASES = [
 @pytest.mark.parametrize("A,B,TX,TY,d,n,kind,naive,io,weights", CASES)
 def test_two_slot_matches_oracle(gpu, A, B, TX, TY, d, n, kind, naive, io, weights):
     rng = np.random.default_rng(A * 100 + TX + TY + n + kind)
-    X, Y = paths(rng, A, TX, d), paths(rng, B, TY, d)
+    X, Y = sized_walks(rng, A, TX, d), sized_walks(rng, B, TY, d)
     W = rng.uniform(0.5, 1.5, (A, B)) if weights == "rand" else None
     check_two_slot(gpu, X, Y, 0.5, n, kind, naive, io, W)
 
 
-@pytest.mark.parametrize("A,B,TX,TY,d,n,kind,naive,regime", BRANCH_CASES, ids=[_branch_id(c) for c in BRANCH_CASES])
+@pytest.mark.parametrize("A,B,TX,TY,d,n,kind,naive,regime", BRANCH_CASES, ids=[branch_id(c) for c in BRANCH_CASES])
 def test_two_slot_plan_branches(gpu, A, B, TX, TY, d, n, kind, naive, regime):
     """The regimes of test_gpu_long.py's plan-branch test (ring full / wrapping, nrow = 1, one-row last band, single coarse
     row or column, unequal lengths, channels past 16), now with the column side."""
-    from helpers import device_cus
-
     pl = long2_plan(A, B, TX, TY, d, n, True, True, False, device_cus())
-    assert pl is not None and _regime(regime, pl, TX, TY), pl
+    assert pl is not None and branch_regime(regime, pl, TX, TY), pl
     rng = np.random.default_rng(TX * 7 + TY + 100 * d + n + 13 * kind)
-    X, Y = paths(rng, A, TX, d, d**-0.5), paths(rng, B, TY, d, d**-0.5)
+    X, Y = sized_walks(rng, A, TX, d, d**-0.5), sized_walks(rng, B, TY, d, d**-0.5)
     W = rng.uniform(0.5, 1.5, (A, B))
     check_two_slot(gpu, X, Y, 0.5, n, kind, naive, F64, W, nthreads=2 if max(pl["P"], pl["Q"]) > 4096 else 0)
 
@@ -109,15 +96,13 @@ TILE_CASES = [(210, 330, 12, 16, F64), (150, 250, 16, 20, F32), (5, 70, 40, 40, 
 
 @pytest.mark.parametrize("A,B,TX,TY,io", TILE_CASES)
 def test_two_slot_tiles(gpu, A, B, TX, TY, io):
-    from helpers import device_cus
-
     pl = long2_plan(A, B, TX, TY, 2, 0, True, True, False, device_cus())
     if (A, B) == (5, 70):  # few pairs: one pair per item, every column slab reduced over 5 tile rows
         assert pl["IC"] == pl["JC"] == 1 and pl["items"] == 350, pl
     else:  # several pairs per item both ways, ragged last tiles, a grid-stride loop
         assert pl["IC"] > 1 and pl["JC"] > 1 and A % pl["IC"] and B % pl["JC"] and pl["items"] > pl["grid"], pl
     rng = np.random.default_rng(A + B)
-    X, Y = paths(rng, A, TX, 2), paths(rng, B, TY, 2)
+    X, Y = sized_walks(rng, A, TX, 2), sized_walks(rng, B, TY, 2)
     check_two_slot(gpu, X, Y, 0.5, 0, 0, False, io, rng.uniform(0.5, 1.5, (A, B)))
 
 
@@ -137,7 +122,6 @@ YX_CASES = [
 
 @pytest.mark.parametrize("A,T,d,n,kind,naive,io", YX_CASES)
 def test_y_is_x_matches_oracle(gpu, A, T, d, n, kind, naive, io):
-    from helpers import device_cus
     from sigsvgd_amd import ops
 
     pl = long2_plan(A, A, T, T, d, n, True, False, True, device_cus())
@@ -145,7 +129,7 @@ def test_y_is_x_matches_oracle(gpu, A, T, d, n, kind, naive, io):
         assert pl["IC"] > 1 and A % pl["IC"] and pl["nti"] > 1 and pl["items"] > pl["grid"], pl
     rng = np.random.default_rng(A * 10 + T + n + kind)
     h = 0.5
-    X = paths(rng, A, T, d)
+    X = sized_walks(rng, A, T, d)
     Xt = torch.as_tensor(X, dtype=io, device=gpu)
     Kf = ops.gram_long_fwd(Xt, Xt, 1.0 / h, n, kind, naive)
     iu = torch.triu_indices(A, A, device=gpu)
@@ -158,7 +142,7 @@ def test_y_is_x_matches_oracle(gpu, A, T, d, n, kind, naive, io):
         assert none_y is None and K.dtype == gX.dtype == io and gX.shape == Xt.shape
         assert torch.equal(K[iu[0], iu[1]], Kf[iu[0], iu[1]])  # the upper triangle and diagonal keep the ordered launch's bits
         assert torch.equal(K, K.T)
-        eK, eX = relK(np64(K), Kr), relmax(np64(gX), gr)
+        eK, eX = rel_entry(np64(K), Kr, 0.0), rel_max(np64(gX), gr)
         print(f"y-is-x sym={sym} weighted={weights is not None} K {eK:.3e} gX {eX:.3e}")
         assert eK < (1e-9 if io == F64 else 2.0**-23)
         assert eX < 1e-5
@@ -172,17 +156,17 @@ def test_y_is_x_agrees_with_ordered_launch(gpu):
     from sigsvgd_amd import ops
 
     rng = np.random.default_rng(4)
-    X = torch.as_tensor(paths(rng, 9, 300, 3), dtype=F64, device=gpu)
+    X = torch.as_tensor(sized_walks(rng, 9, 300, 3), dtype=F64, device=gpu)
     W = torch.as_tensor(rng.standard_normal((9, 9)), device=gpu)
     Ko, go = ops.gram_long_fwd_bwd(X, X, 2.0, 0, 0, W)
     K, g, _ = ops.gram_long_fwd_bwd2(X, X, 2.0, 0, 0, W, y_is_x=True)
-    assert relK(np64(K), np64(Ko)) < 1e-9 and relmax(np64(g), np64(go)) < 1e-9
+    assert rel_entry(np64(K), np64(Ko), 0.0) < 1e-9 and rel_max(np64(g), np64(go)) < 1e-9
 
 
 # ---- the autograd surface --------------------------------------------------------------------------------------------------
 def _leafs(gpu, A, B, TX, TY, d, seed, dtype=F64):
     rng = np.random.default_rng(seed)
-    Xn, Yn = paths(rng, A, TX, d), paths(rng, B, TY, d)
+    Xn, Yn = sized_walks(rng, A, TX, d), sized_walks(rng, B, TY, d)
     X = torch.as_tensor(Xn, dtype=dtype, device=gpu).requires_grad_(True)
     Y = torch.as_tensor(Yn, dtype=dtype, device=gpu).requires_grad_(True)
     return Xn, Yn, X, Y, rng
@@ -207,19 +191,19 @@ def test_compute_gram_grad_Y(gpu, route, A, B, T, d, n, weighted):
     K = kernel.compute_Gram(X, Y, grad_Y=True)
     (K.sum() if W is None else (K * torch.as_tensor(W, device=gpu)).sum()).backward()
     tolK = 1e-9 if route != "fused" else 1e-5  # (the fused kernels' own bound: fp32 sweeps)
-    assert relK(np64(K), Kr) < tolK
-    assert relmax(np64(X.grad), gXr) < 1e-5
+    assert rel_entry(np64(K), Kr, 0.0) < tolK
+    assert rel_max(np64(X.grad), gXr) < 1e-5
     assert Y.grad is not None and Y.grad.shape == Y.shape and Y.grad.dtype == Y.dtype
-    assert relmax(np64(Y.grad), gYr) < 1e-5
+    assert rel_max(np64(Y.grad), gYr) < 1e-5
     # the default: the first slot only
     X2, Y2 = X.detach().clone().requires_grad_(True), Y.detach().clone().requires_grad_(True)
     kernel.compute_Gram(X2, Y2).sum().backward()
-    assert Y2.grad is None and relmax(np64(X2.grad), oracle_both_slots(Xn, Yn, 0.8, n, False, 0, None)[1]) < 1e-5
+    assert Y2.grad is None and rel_max(np64(X2.grad), oracle_both_slots(Xn, Yn, 0.8, n, False, 0, None)[1]) < 1e-5
     # Y alone
     Y3 = Y.detach().clone().requires_grad_(True)
     K3 = kernel.compute_Gram(X.detach(), Y3, grad_Y=True)
     (K3.sum() if W is None else (K3 * torch.as_tensor(W, device=gpu)).sum()).backward()
-    assert relmax(np64(Y3.grad), gYr) < 1e-5 and relK(np64(K3), Kr) < tolK
+    assert rel_max(np64(Y3.grad), gYr) < 1e-5 and rel_entry(np64(K3), Kr, 0.0) < tolK
 
 
 @pytest.mark.parametrize("route,A,T,d,n", [("long", 5, 300, 3, 0), ("fused", 6, 16, 3, 1)])
@@ -228,7 +212,7 @@ def test_one_tensor_in_both_slots(gpu, route, A, T, d, n):
     import sigsvgd_amd.sigkernel as sk
 
     rng = np.random.default_rng(31)
-    Xn = paths(rng, A, T, d)
+    Xn = sized_walks(rng, A, T, d)
     kernel = sk.SigKernel(sk.RBFKernel(0.8), n)
     grads = []
     for kw in (dict(grad_Y=True), dict(sym=True)):
@@ -236,8 +220,8 @@ def test_one_tensor_in_both_slots(gpu, route, A, T, d, n):
         kernel.compute_Gram(X, X, **kw).sum().backward()
         grads.append(np64(X.grad))
     _, gr = c_oracle.gram_fwd_bwd(Xn, Xn, h=0.8, n=n, grad_out=np.full((A, A), 2.0))
-    assert relmax(grads[0], gr) < 1e-5 and relmax(grads[1], gr) < 1e-5
-    assert relmax(grads[0], grads[1]) < 1e-5
+    assert rel_max(grads[0], gr) < 1e-5 and rel_max(grads[1], gr) < 1e-5
+    assert rel_max(grads[0], grads[1]) < 1e-5
     with pytest.raises(ValueError):
         kernel.compute_Gram(X, X, sym=True, grad_Y=True)
 
@@ -255,10 +239,10 @@ def test_compute_mmd_grad_Y(gpu, route, A, B, T, d, n):
     ref = gyy / B**2 - 2.0 * gxy / (A * B)
     kernel = sk.SigKernel(sk.RBFKernel(h), n)
     kernel.compute_mmd(X, Y, grad_Y=True).backward()
-    assert relmax(np64(Y.grad), ref) < 1e-5
+    assert rel_max(np64(Y.grad), ref) < 1e-5
     Y2 = Y.detach().clone().requires_grad_(True)
     kernel.compute_mmd(X.detach(), Y2).backward()
-    assert relmax(np64(Y2.grad), gyy / B**2) < 1e-5  # (the default: the self term alone)
+    assert rel_max(np64(Y2.grad), gyy / B**2) < 1e-5  # (the default: the self term alone)
 
 
 def test_user_static_kernel_grad_Y(gpu):
@@ -274,8 +258,8 @@ def test_user_static_kernel_grad_Y(gpu):
         K = sk.SigKernel(static, 0).compute_Gram(Xl, Yl, grad_Y=True)
         (K * W).sum().backward()
         out.append((np64(K), np64(Xl.grad), np64(Yl.grad)))
-    assert relK(out[0][0], out[1][0]) < 1e-9
-    assert relmax(out[0][1], out[1][1]) < 1e-5 and relmax(out[0][2], out[1][2]) < 1e-5
+    assert rel_entry(out[0][0], out[1][0], 0.0) < 1e-9
+    assert rel_max(out[0][1], out[1][1]) < 1e-5 and rel_max(out[0][2], out[1][2]) < 1e-5
     Yd = Y.detach().clone().requires_grad_(True)
     sk.SigKernel(DisguisedRBF(0.8), 0).compute_Gram(X.detach().clone().requires_grad_(True), Yd).sum().backward()
     assert Yd.grad is None  # the default detaches Y, as before
@@ -305,7 +289,7 @@ def test_svgd_step_runs_the_y_is_x_launch(gpu, monkeypatch):
 
     rng = np.random.default_rng(2)
     N, T, d, h, lr = 8, 300, 3, 2.0, 0.05
-    Xn = paths(rng, N, T, d)
+    Xn = sized_walks(rng, N, T, d)
     sn = rng.standard_normal((N, T, d))
     Kr, gr = c_oracle.gram_fwd_bwd(Xn, Xn, h=h, n=0)
     X_ref, v_ref, _ = O.svgd_step_manual(Xn, sn, Kr, gr, lr)
@@ -317,8 +301,8 @@ def test_svgd_step_runs_the_y_is_x_launch(gpu, monkeypatch):
         Xnew, info = SVGD(kernel, optimizer_class=None, lr=lr).step(X.clone(), score)
         out.append((np64(Xnew), np64(info["grad"]).reshape(N, T, d)))
     assert calls == [True]  # (the user route launches the PDE on its grid, not this kernel)
-    assert relmax(out[0][0], X_ref) < 1e-5 and relmax(out[0][1], v_ref) < 1e-5
-    assert relmax(out[0][0], out[1][0]) < 1e-5 and relmax(out[0][1], out[1][1]) < 1e-5
+    assert rel_max(out[0][0], X_ref) < 1e-5 and rel_max(out[0][1], v_ref) < 1e-5
+    assert rel_max(out[0][0], out[1][0]) < 1e-5 and rel_max(out[0][1], out[1][1]) < 1e-5
 
 
 def test_y_is_x_routing_of_the_surface(gpu, monkeypatch):
@@ -326,14 +310,13 @@ def test_y_is_x_routing_of_the_surface(gpu, monkeypatch):
     value check -- the launch is the Y-is-X one wherever `_long_yx_route` says so (gradient launches
     of single-pair items, forward-only launches of many pairs); a distinct Y takes the ordered launch."""
     import sigsvgd_amd.sigkernel as sk
-    from helpers import device_cus
 
     cus = device_cus()
     route = lambda A, want_grad: sk._long_yx_route(True, A, want_grad, cus)
     assert route(8, True) and route(32, True) and not route(8, False) and not sk._long_yx_route(False, 8, True, cus)
     rng = np.random.default_rng(7)
-    X = torch.as_tensor(paths(rng, 6, 300, 2), dtype=F64, device=gpu)
-    Y = torch.as_tensor(paths(rng, 6, 300, 2), dtype=F64, device=gpu)
+    X = torch.as_tensor(sized_walks(rng, 6, 300, 2), dtype=F64, device=gpu)
+    Y = torch.as_tensor(sized_walks(rng, 6, 300, 2), dtype=F64, device=gpu)
     kernel = sk.SigKernel(sk.RBFKernel(1.0), 0)
     calls = _count_calls(monkeypatch)
     K0 = kernel.compute_Gram(X, X)  # forward only, few pairs: the ordered launch
@@ -345,17 +328,17 @@ def test_y_is_x_routing_of_the_surface(gpu, monkeypatch):
     assert calls == [True, True]
     iu = torch.triu_indices(6, 6, device=gpu)
     assert torch.equal(K1.detach(), K2) and torch.equal(K2, K2.T) and torch.equal(K0[iu[0], iu[1]], K2[iu[0], iu[1]])
-    assert relmax(np64(Xg.grad), np64(g2)) < 1e-12
+    assert rel_max(np64(Xg.grad), np64(g2)) < 1e-12
     kernel.compute_Gram(X, Y)
     kernel.gram_and_grad(X, Y)
     assert calls == [True, True]
-    big = torch.as_tensor(paths(rng, 32, 300, 2), dtype=F64, device=gpu)  # (the value check starts at 32 paths)
+    big = torch.as_tensor(sized_walks(rng, 32, 300, 2), dtype=F64, device=gpu)  # (the value check starts at 32 paths)
     kernel.compute_Gram(big.clone().requires_grad_(True), big.clone())
     assert calls == [True, True, True]
     # past single-pair items the gradient launch stays ordered; many pairs send the forward-only launch through Y-is-X
     A = 64
     assert not route(A, True) and route(A, False), cus
-    wide = torch.as_tensor(paths(rng, A, 300, 2), dtype=F64, device=gpu)
+    wide = torch.as_tensor(sized_walks(rng, A, 300, 2), dtype=F64, device=gpu)
     Kg, _ = kernel.gram_and_grad(wide)
     assert calls == [True, True, True]
     Kw = kernel.compute_Gram(wide, wide)

@@ -4,7 +4,6 @@ long route's own (tests/test_gpu_long.py): K within 1e-9 per entry with fp64 I/O
 1e-5 of its largest entry, against the C oracle; against the full Y-is-X launch, whose pairs and products the shares
 repeat, K bit for bit and the fp64 gradient within 1e-9 (another order of the same fp64 sums)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -12,31 +11,13 @@ import torch
 
 from oracle import c_oracle
 from oracle import sigkernel_oracle as O
-
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from parity import np64, rel_entry, rel_max, signed_weights, sized_walks
+from plans import device_cus, item_size, part_items, part_plan
 
 pytestmark = pytest.mark.gpu
 
 F64, F32 = torch.float64, torch.float32
 RBF, LINEAR = 0, 1
-
-
-def paths(rng, B, T, d, scale=1.0):
-    """random walks of about `scale` overall size whatever their length"""
-    return np.cumsum(scale / np.sqrt(T) * rng.standard_normal((B, T, d)), axis=1).astype(np.float32)
-
-
-def relK(K, Kr):  # plain relative error per entry
-    return float((np.abs(np.asarray(K, np.float64) - Kr) / np.abs(Kr)).max())
-
-
-def relmax(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def np64(t):
-    return t.detach().double().cpu().numpy()
 
 
 def touched_rows(N, R, owned):
@@ -71,13 +52,12 @@ def _oracle(case, weights, X, W):
 @pytest.mark.parametrize("fold", [True, False])
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "N%d-T%d-d%d-n%d-k%d-%s-G%d" % (c[0], c[1], c[2], c[3], c[4], "f64" if c[5] == F64 else "f32", c[6]))
 def test_shares_add_up(gpu, case, fold, weights):
-    from helpers import signed_weights
     from sigsvgd_amd import ops
 
     N, T, d, n, kind, io, stride = case
     rng = np.random.default_rng(N * 100 + T + n + kind)
     h = 0.5
-    X = paths(rng, N, T, d)
+    X = sized_walks(rng, N, T, d)
     W = signed_weights(N, N, N + T)
     Kr, gr = _oracle(case, weights, X, W)
     Xt = torch.as_tensor(X, dtype=io, device=gpu)
@@ -115,18 +95,16 @@ def test_shares_add_up(gpu, case, fold, weights):
     assert sorted(all_owned) == list(range(ntile))
     assert torch.equal(Ksum, Kf)
     assert torch.equal(torch.triu(Ksum), torch.triu(K1))
-    assert relK(np64(Ksum), Kr) < (1e-9 if io == F64 else 2.0**-23)
-    assert relmax(np64(gsum), gr) < 1e-5
+    assert rel_entry(np64(Ksum), Kr, 0.0) < (1e-9 if io == F64 else 2.0**-23)
+    assert rel_max(np64(gsum), gr) < 1e-5
     if io == F64:
-        assert relmax(np64(gsum), np64(gf)) < 1e-9
+        assert rel_max(np64(gsum), np64(gf)) < 1e-9
 
 
 def _multi_item_case(gpu, N, T, d, stride, several_rounds):
     """a share whose items hold several pairs, first rectangle ragged by the diagonal over several rows, a ragged last one,
     JC not a power of two, in one round of the grid or past it -- asserted from the plan -- against the full Y-is-X launch"""
-    from helpers import device_cus
     from sigsvgd_amd import ops
-    from test_long_partial_cabi import item_size, part_items, part_plan
 
     R, JC = ops.gram_long_partial_tiles(N, T, d, 0, RBF, stride)
     pl = part_plan(N, T, d, 0, 0, stride, True, device_cus())
@@ -141,7 +119,7 @@ def _multi_item_case(gpu, N, T, d, stride, several_rounds):
         assert pl["items"] == pl["grid"], (pl["items"], pl["grid"])
 
     rng = np.random.default_rng(N + T)
-    Xt = torch.as_tensor(paths(rng, N, T, d), dtype=F64, device=gpu)
+    Xt = torch.as_tensor(sized_walks(rng, N, T, d), dtype=F64, device=gpu)
     Kf, gf, _ = ops.gram_long_fwd_bwd2(Xt, Xt, 2.0, y_is_x=True)
     Ksum, gsum = torch.zeros_like(Kf), torch.zeros_like(gf)
     for off in range(stride):
@@ -149,7 +127,7 @@ def _multi_item_case(gpu, N, T, d, stride, several_rounds):
         Ksum += Kp
         gsum += gp
     assert torch.equal(Ksum, Kf)
-    assert relmax(np64(gsum), np64(gf)) < 1e-9
+    assert rel_max(np64(gsum), np64(gf)) < 1e-9
 
 
 def test_items_of_several_pairs_one_round(gpu):
@@ -167,7 +145,7 @@ def test_reproducible(gpu):
     from sigsvgd_amd import ops
 
     rng = np.random.default_rng(11)
-    Xt = torch.as_tensor(paths(rng, 40, 140, 3), dtype=F32, device=gpu)
+    Xt = torch.as_tensor(sized_walks(rng, 40, 140, 3), dtype=F32, device=gpu)
     a = ops.gram_long_sym_partial(Xt, 2.0, 1, 2, fold=True)
     junk = torch.full((1 << 22,), float("nan"), device=gpu)  # (other bytes in the allocator's pools in between)
     b = ops.gram_long_sym_partial(Xt, 2.0, 1, 2, fold=True)
@@ -231,7 +209,7 @@ def test_sharded_step_default_routes_stay_rowwise_where_the_fused_kernels_run(gp
             lp = ShardedSigSVGD(1.0, 1e-3, long_partial=True, **kw)
             Xl = lp.step(Xg, sg)
             assert lp.last_route == "long_partial"
-            assert relK(np64(Ka), np64(lp.gather_gram())) < 1e-5
-            assert relmax(np64(Xa), np64(Xl)) < 1e-6
+            assert rel_entry(np64(Ka), np64(lp.gather_gram()), 0.0) < 1e-5
+            assert rel_max(np64(Xa), np64(Xl)) < 1e-6
     finally:
         dist.destroy_process_group()

@@ -6,6 +6,7 @@ import torch
 
 from oracle import c_oracle as C
 from oracle import sigkernel_oracle as O
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -14,30 +15,13 @@ TOL = 1e-5
 SELF = 4e-6
 
 
-def _paths(A, T, d, seed, scale=0.05):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
-
-
-def _relK(a, b):
-    """K parity as north_star states it: max over entries of |K - K_ref| / |K_ref| (K > 0 always)"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    # (round 4: plain relative error per entry -- rounds 2-3 floored the denominator at 0.1; the 1e-6 only keeps an exact zero
-    #  out of it.  Pairs whose K is small against their grid are solved by the exact fp64 pass now: DESIGN.md section 3)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
-
-
 @pytest.mark.parametrize("A,B,T,d", [(5, 6, 128, 14), (3, 9, 128, 7), (6, 5, 65, 3), (4, 4, 66, 2),
                                      (7, 3, 100, 7), (2, 5, 127, 16), (9, 2, 97, 1)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
 def test_long_fwd_bwd(gpu, A, B, T, d, dtype):
     from sigsvgd_amd import ops
 
-    X, Y = _paths(A, T, d, 1), _paths(B, T, d, 2)
+    X, Y = walks(A, T, d, 1, 0.05), walks(B, T, d, 2, 0.05)
     h = 1.1
     go = np.random.default_rng(3).standard_normal((A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go.astype(np.float64))
@@ -45,12 +29,12 @@ def test_long_fwd_bwd(gpu, A, B, T, d, dtype):
     K1 = ops.gram_fwd(Xg, Yg, 1.0 / h)
     K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog)
     torch.cuda.synchronize()
-    assert _relK(K1.cpu().numpy(), Kref) < TOL
-    assert _relK(K2.cpu().numpy(), Kref) < TOL
-    assert _rel(g2.cpu().numpy(), gref) < TOL
+    assert rel_entry(K1.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_entry(K2.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g2.cpu().numpy(), gref) < TOL
     if T * d <= 128 * 14:  # the coverage kernel's compact layout tops out at T=128, d=14 (LDS)
         K3, g3 = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog, force_generic=True)
-        assert _rel(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
+        assert rel_max(g2.cpu().numpy(), g3.double().cpu().numpy()) < TOL
 
 
 def test_long_self_gram_c5_shape(gpu):
@@ -61,9 +45,9 @@ def test_long_self_gram_c5_shape(gpu):
     Xg = X.to(gpu)
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0, y_is_x=True)
     Kref, gref = C.gram_fwd_bwd(X.numpy(), X.numpy(), 1.0, 0)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
     K2, g2 = ops.gram_fwd_bwd(Xg, Xg, 1.0, sym=True, y_is_x=True)
-    assert _rel(g2.cpu().numpy(), 2 * gref) < TOL
+    assert rel_max(g2.cpu().numpy(), 2 * gref) < TOL
 
 
 @pytest.mark.parametrize("N,T,d", [(9, 128, 14), (13, 65, 3), (6, 100, 7), (5, 127, 16), (1, 96, 2), (17, 128, 1)])
@@ -73,24 +57,24 @@ def test_long_symmetric_solve_equals_ordered_pairs(gpu, N, T, d, dtype):
     travelling accumulators); with asymmetric weights it must still equal the ordered-pair result."""
     from sigsvgd_amd import ops
 
-    X = _paths(N, T, d, 5)
+    X = walks(N, T, d, 5, 0.05)
     h = 0.9
     go = np.random.default_rng(6).standard_normal((N, N)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, X, h, 0, grad_out=go.astype(np.float64))
     Xg, gog = torch.as_tensor(X, device=gpu).to(dtype), torch.as_tensor(go, device=gpu).to(dtype)
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, grad_out=gog, y_is_x=True)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
     assert torch.equal(K, K.T)  # mirrored stores
     Ko, g_o = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, grad_out=gog)  # ordered pairs on the same kernel family
-    assert _relK(K.cpu().numpy(), Ko.double().cpu().numpy()) < SELF
-    assert _rel(g.cpu().numpy(), g_o.double().cpu().numpy()) < 1e-5
+    assert rel_entry(K.cpu().numpy(), Ko.double().cpu().numpy(), 1e-6) < SELF
+    assert rel_max(g.cpu().numpy(), g_o.double().cpu().numpy()) < 1e-5
     # ones weights, and the sym=True weighting (grad_out symmetrised)
     K1, g1 = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, y_is_x=True)
     _, gref1 = C.gram_fwd_bwd(X, X, h, 0)
-    assert _rel(g1.cpu().numpy(), gref1) < TOL
+    assert rel_max(g1.cpu().numpy(), gref1) < TOL
     _, g2 = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, grad_out=gog, sym=True, y_is_x=True)
     _, gref2 = C.gram_fwd_bwd(X, X, h, 0, grad_out=(go + go.T).astype(np.float64))
-    assert _rel(g2.cpu().numpy(), gref2) < TOL
+    assert rel_max(g2.cpu().numpy(), gref2) < TOL
 
 
 @pytest.mark.parametrize("fold", [False, True])
@@ -100,7 +84,7 @@ def test_long_partials_sum_to_full(gpu, N, T, d, world, fold):
     to the full symmetric solve, and each owned pair appears in exactly one partial."""
     from sigsvgd_amd import ops
 
-    X = _paths(N, T, d, 8)
+    X = walks(N, T, d, 8, 0.05)
     Xg = torch.as_tensor(X, device=gpu)
     go = torch.as_tensor(np.random.default_rng(9).uniform(0.5, 1.5, (N, N)).astype(np.float32), device=gpu)
     Kf, gf = ops.gram_fwd_bwd(Xg, Xg, 1.0, grad_out=go, y_is_x=True)
@@ -114,9 +98,9 @@ def test_long_partials_sum_to_full(gpu, N, T, d, world, fold):
         cover += (Kp != 0).float()
     assert torch.equal(cover, torch.ones_like(cover))
     assert torch.equal(Ks, Kf)
-    assert _rel(gs.cpu().numpy(), gf.double().cpu().numpy()) < 1e-6
+    assert rel_max(gs.cpu().numpy(), gf.double().cpu().numpy()) < 1e-6
     Kref, gref = C.gram_fwd_bwd(X, X, 1.0, 0, grad_out=go.double().cpu().numpy())
-    assert _rel(gs.cpu().numpy(), gref) < TOL
+    assert rel_max(gs.cpu().numpy(), gref) < TOL
 
 
 def test_long_symmetric_large_property(gpu):
@@ -129,8 +113,8 @@ def test_long_symmetric_large_property(gpu):
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0, y_is_x=True)
     Ko, g_o = ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0)
     assert torch.equal(K, K.T)
-    assert _relK(K.cpu().numpy(), Ko.double().cpu().numpy()) < SELF
-    assert _rel(g.cpu().numpy(), g_o.double().cpu().numpy()) < 1e-5
+    assert rel_entry(K.cpu().numpy(), Ko.double().cpu().numpy(), 1e-6) < SELF
+    assert rel_max(g.cpu().numpy(), g_o.double().cpu().numpy()) < 1e-5
     assert torch.isfinite(g).all()
 
 
@@ -152,19 +136,19 @@ def test_stored_forward_quadrant_kernel(gpu, A, B, T, d, sym, scale):
     K, g = ops.gram_fwd_bwd(Xg, Xg if sym else Yg, 1.0, y_is_x=sym, stored_forward=True)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(g).all())
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
     # forward-only launch of the same kernel, and fp64 I/O
     Kf = ops.gram_fwd(Xg, Xg if sym else Yg, 1.0, y_is_x=sym, stored_forward=True)
-    assert _relK(Kf.cpu().numpy(), Kref) < TOL
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
     K64, g64 = ops.gram_fwd_bwd(Xg.double(), (Xg if sym else Yg).double(), 1.0, y_is_x=sym, stored_forward=True)
-    assert K64.dtype == torch.float64 and _relK(K64.cpu().numpy(), Kref) < TOL and _rel(g64.cpu().numpy(), gref) < TOL
+    assert K64.dtype == torch.float64 and rel_entry(K64.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g64.cpu().numpy(), gref) < TOL
     if sym:
         assert np.array_equal(K.cpu().numpy(), K.cpu().numpy().T)
         # weighted backward (grad_out) and the sharded partial solve: two shares sum to the full result
         go = torch.as_tensor(rng.standard_normal((A, A)).astype(np.float32), device=gpu)
         Kw, gw = ops.gram_fwd_bwd(Xg, Xg, 1.0, grad_out=go, y_is_x=True, stored_forward=True)
         _, gwref = C.gram_fwd_bwd(X, X, 1.0, 0, grad_out=go.double().cpu().numpy())
-        assert _rel(gw.cpu().numpy(), gwref) < TOL
+        assert rel_max(gw.cpu().numpy(), gwref) < TOL
         if True:
             Ks = torch.zeros_like(K)
             gs = torch.zeros((A, T, d), dtype=torch.float64, device=gpu)
@@ -172,7 +156,7 @@ def test_stored_forward_quadrant_kernel(gpu, A, B, T, d, sym, scale):
                 Kp, gp = ops.gram_sym_partial(Xg, 1.0, off, 2)
                 Ks += Kp
                 gs += gp
-            assert torch.equal(Ks, K) and _rel(gs.cpu().numpy(), gref) < TOL
+            assert torch.equal(Ks, K) and rel_max(gs.cpu().numpy(), gref) < TOL
 
 
 @pytest.mark.parametrize("T,d,scale,h", [(100, 2, 0.2, 0.1), (100, 2, 0.5, 1.0), (128, 2, 0.2, 1.0), (80, 2, 0.2, 0.1)])
@@ -190,12 +174,12 @@ def test_long_oscillating_solutions_per_entry(gpu, T, d, scale, h):
     assert Kref.min() < 0.5  # (the regime the test is about: solutions that cancel)
     Xg = torch.as_tensor(X, device=gpu)
     for K, g in [ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, y_is_x=True), ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0 / h)]:
-        assert _relK(K.cpu().numpy(), Kref) < 8e-6
-        assert _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 8e-6
+        assert rel_max(g.cpu().numpy(), gref) < TOL
     for K in [ops.gram_fwd(Xg, Xg, 1.0 / h, y_is_x=True), ops.gram_fwd(Xg, Xg.clone(), 1.0 / h)]:
-        assert _relK(K.cpu().numpy(), Kref) < 8e-6
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < 8e-6
     Ks = torch.zeros(N, N, device=gpu)
     for r in range(2):
         Kp, _ = ops.gram_sym_partial(Xg, 1.0 / h, r, 2, fold=True)
         Ks += Kp
-    assert _relK(Ks.cpu().numpy(), Kref) < 8e-6
+    assert rel_entry(Ks.cpu().numpy(), Kref, 1e-6) < 8e-6

@@ -14,24 +14,11 @@ import pytest
 import torch
 
 from oracle import c_oracle as C
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-def _paths(A, T, d, seed, scale):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / np.abs(b).max())
-
-
-def _relK(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 # (A, B, T, d, h, scale, Y is X): the regimes of the nine soak cases of round 3 (gpurun_out/soak_r3m.log: 213, 492, 1118, 1995,
@@ -55,8 +42,8 @@ def test_soak_regimes_default_dispatch(gpu, A, B, T, d, h, scale, yx, seed):
     """every launch form of the default dispatch (Gram + gradient, forward only, the sharded partial solve) per entry"""
     from sigsvgd_amd import ops
 
-    X = _paths(A, T, d, 100 * T + 10 * d + seed, scale)
-    Y = X if yx else _paths(B, T, d, 100 * T + 10 * d + seed + 5, scale)
+    X = walks(A, T, d, 100 * T + 10 * d + seed, scale)
+    Y = X if yx else walks(B, T, d, 100 * T + 10 * d + seed + 5, scale)
     go = np.random.default_rng(seed).uniform(0.5, 1.5, (A, B)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go.astype(np.float64))
     Xg, gog = torch.as_tensor(X, device=gpu), torch.as_tensor(go, device=gpu)
@@ -64,9 +51,9 @@ def test_soak_regimes_default_dispatch(gpu, A, B, T, d, h, scale, yx, seed):
     K, g = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog, y_is_x=yx)
     Kf = ops.gram_fwd(Xg, Yg, 1.0 / h, y_is_x=yx)
     torch.cuda.synchronize()
-    assert _relK(K.cpu().numpy(), Kref) < TOL
-    assert _relK(Kf.cpu().numpy(), Kref) < TOL
-    assert _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g.cpu().numpy(), gref) < TOL
     if yx:
         Ks = torch.zeros(A, A, device=gpu)
         gs = torch.zeros(A, T, d, device=gpu, dtype=torch.float64)
@@ -74,8 +61,8 @@ def test_soak_regimes_default_dispatch(gpu, A, B, T, d, h, scale, yx, seed):
             Kp, gp = ops.gram_sym_partial(Xg, 1.0 / h, r, 2, grad_out=gog, fold=True)
             Ks += Kp
             gs += gp
-        assert _relK(Ks.cpu().numpy(), Kref) < TOL
-        assert _rel(gs.cpu().numpy(), gref) < TOL
+        assert rel_entry(Ks.cpu().numpy(), Kref, 1e-6) < TOL
+        assert rel_max(gs.cpu().numpy(), gref) < TOL
 
 
 @pytest.mark.parametrize("h", [0.02, 0.1, 0.5, 1.0])
@@ -85,16 +72,16 @@ def test_one_channel_sweep_rows(gpu, N, T, scale, h):
     """the d = 1 rows of the roughness x bandwidth sweep where the discrete solution oscillates (round 3: up to 1.9e-5)"""
     from sigsvgd_amd import ops
 
-    X = _paths(N, T, 1, 0, scale)
+    X = walks(N, T, 1, 0, scale)
     Kref, gref = C.gram_fwd_bwd(X, X, h, 0)
     if not np.isfinite(Kref).all() or np.abs(Kref).max() > 1e30:
         pytest.skip("K beyond the fp32 range: no fp32 answer exists")
     Xg = torch.as_tensor(X, device=gpu)
     for sym in (True, False):
         K, g = ops.gram_fwd_bwd(Xg, Xg if sym else Xg.clone(), 1.0 / h, y_is_x=sym)
-        assert _relK(K.cpu().numpy(), Kref) < TOL
-        assert _rel(g.cpu().numpy(), gref) < TOL
-        assert _relK(ops.gram_fwd(Xg, Xg if sym else Xg.clone(), 1.0 / h, y_is_x=sym).cpu().numpy(), Kref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL
+        assert rel_max(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(ops.gram_fwd(Xg, Xg if sym else Xg.clone(), 1.0 / h, y_is_x=sym).cpu().numpy(), Kref, 1e-6) < TOL
 
 
 @pytest.mark.parametrize("N,T,d", [(64, 64, 3), (48, 64, 1), (40, 100, 3), (64, 32, 2)])
@@ -110,7 +97,7 @@ def test_smooth_few_channel_launches_flag_nothing(gpu, N, T, d):
     K = ops.gram_fwd(Xg, Xg, 1.0, y_is_x=True)
     Kx = ops.gram_fwd(Xg, Xg, 1.0, y_is_x=True, force_generic=True)
     torch.cuda.synchronize()
-    assert _relK(K.cpu().numpy(), Kx.double().cpu().numpy()) < 3e-6
+    assert rel_entry(K.cpu().numpy(), Kx.double().cpu().numpy(), 1e-6) < 3e-6
     same = (K == Kx).float().mean().item()
     assert same < 0.9, same  # (an exact pass over every pair would make the two identical)
 
@@ -124,7 +111,7 @@ def test_exact_pass_long_paths(gpu, A, B, T, d, h, scale, dtype):
     without the gradient, symmetric and ordered."""
     from sigsvgd_amd import ops
 
-    X, Y = _paths(A, T, d, 3, scale), _paths(B, T, d, 4, scale)
+    X, Y = walks(A, T, d, 3, scale), walks(B, T, d, 4, scale)
     go = np.random.default_rng(5).uniform(0.5, 1.5, (A, B))
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go)
     Xg, Yg, gog = (torch.as_tensor(t, device=gpu).to(dtype) for t in (X, Y, go))
@@ -132,14 +119,14 @@ def test_exact_pass_long_paths(gpu, A, B, T, d, h, scale, dtype):
     K, g = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, grad_out=gog, force_generic=True)
     Kf = ops.gram_fwd(Xg, Yg, 1.0 / h, force_generic=True)
     torch.cuda.synchronize()
-    assert _relK(K.cpu().numpy(), Kref) < tol
-    assert _relK(Kf.cpu().numpy(), Kref) < tol
-    assert _rel(g.cpu().numpy(), gref) < 1e-6  # (the stored forward solution and S are fp32 whatever the I/O type)
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < tol
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < tol
+    assert rel_max(g.cpu().numpy(), gref) < 1e-6  # (the stored forward solution and S are fp32 whatever the I/O type)
     if A == B:
         Ks, gs = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, y_is_x=True, force_generic=True)
         Kr2, gr2 = C.gram_fwd_bwd(X, X, h, 0)
-        assert _relK(Ks.cpu().numpy(), Kr2) < tol
-        assert _rel(gs.cpu().numpy(), gr2) < 1e-6
+        assert rel_entry(Ks.cpu().numpy(), Kr2, 1e-6) < tol
+        assert rel_max(gs.cpu().numpy(), gr2) < 1e-6
 
 
 def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
@@ -153,7 +140,7 @@ def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
 
     L = _lib.load()
     for (A, B, T, d, n) in [(9, 7, 30, 3, 2), (9, 7, 30, 3, 3), (6, 6, 20, 2, 0), (5, 5, 100, 2, 0)]:
-        X, Y = _paths(A, T, d, 1, 0.05), _paths(B, T, d, 2, 0.05)
+        X, Y = walks(A, T, d, 1, 0.05), walks(B, T, d, 2, 0.05)
         Kref, gref = O.gram_backward(X.astype(np.float64), Y.astype(np.float64), None, O.LINEAR, 1.0, n)
         Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
         nb = ctypes.c_size_t(0)
@@ -165,7 +152,7 @@ def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
                                     K.data_ptr(), g.data_ptr(), ws.data_ptr(), nb.value, None)
         assert rc == 0, _lib.last_error()
         torch.cuda.synchronize()
-        assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
         K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0, n, static_kind=_lib.STATIC_LINEAR)
         assert torch.equal(K, K2) and torch.equal(g, g2)
 
@@ -203,16 +190,16 @@ def _parity_all_forms(gpu, X, Y, h, seed, partial=False, ones=True):
     Kf = ops.gram_fwd(Xg, Xg, 1.0 / h, y_is_x=True)
     Kfo = ops.gram_fwd(Xg, Yg, 1.0 / h)
     torch.cuda.synchronize()
-    err = {"sym K": _relK(K.cpu().numpy(), Ks_ref), "sym grad": _rel(g.cpu().numpy(), gs_ref),
-           "ordered K": _relK(Ko.cpu().numpy(), Ko_ref), "ordered grad": _rel(go.cpu().numpy(), go_ref),
-           "fwd sym K": _relK(Kf.cpu().numpy(), Ks_ref), "fwd ordered K": _relK(Kfo.cpu().numpy(), Ko_ref)}
+    err = {"sym K": rel_entry(K.cpu().numpy(), Ks_ref, 1e-6), "sym grad": rel_max(g.cpu().numpy(), gs_ref),
+           "ordered K": rel_entry(Ko.cpu().numpy(), Ko_ref, 1e-6), "ordered grad": rel_max(go.cpu().numpy(), go_ref),
+           "fwd sym K": rel_entry(Kf.cpu().numpy(), Ks_ref, 1e-6), "fwd ordered K": rel_entry(Kfo.cpu().numpy(), Ko_ref, 1e-6)}
     if ones:  # grad_out = None: the gradient sums the partners with equal weights and can cancel far below the weighted one's
         for name, Z, Zg, yx in (("ones sym", X, Xg, True), ("ones ordered", Y, Yg, False)):
             K1_ref, g1_ref = C.gram_fwd_bwd(X, Z, h, 0)
             K1, g1 = ops.gram_fwd_bwd(Xg, Zg, 1.0 / h, y_is_x=yx)
             torch.cuda.synchronize()
-            err[name + " K"] = _relK(K1.cpu().numpy(), K1_ref)
-            err[name + " grad"] = _rel(g1.cpu().numpy(), g1_ref)
+            err[name + " K"] = rel_entry(K1.cpu().numpy(), K1_ref, 1e-6)
+            err[name + " grad"] = rel_max(g1.cpu().numpy(), g1_ref)
     if partial:
         Kp = torch.zeros(A, A, device=gpu)
         gp = torch.zeros(X.shape, device=gpu, dtype=torch.float64)
@@ -221,8 +208,8 @@ def _parity_all_forms(gpu, X, Y, h, seed, partial=False, ones=True):
             Kp += k_r
             gp += g_r
         torch.cuda.synchronize()
-        err["partial K"] = _relK(Kp.cpu().numpy(), Ks_ref)
-        err["partial grad"] = _rel(gp.cpu().numpy(), gs_ref)
+        err["partial K"] = rel_entry(Kp.cpu().numpy(), Ks_ref, 1e-6)
+        err["partial grad"] = rel_max(gp.cpu().numpy(), gs_ref)
     return err
 
 
@@ -249,7 +236,7 @@ def test_smooth_one_channel_order0(gpu, A, T, d, step, h, src):
     if src == "probe":
         X = _probe_paths(A, T, d, step, h)
     else:
-        X = _paths(A, T, d, 1000 * T + 10 * d + src, step)
+        X = walks(A, T, d, 1000 * T + 10 * d + src, step)
     Y = X.copy()  # the ordered launch: Y a separate tensor with X's values (the probe's form)
     err = _parity_all_forms(gpu, X, Y, h, 7 + (0 if src == "probe" else src))
     assert max(err.values()) < TOL, err
@@ -266,8 +253,8 @@ def test_rough_wide_paths_default_dispatch(gpu, d, T, step, h):
     for conditioning (the 8- and 16-channel register-resident instantiations have no exact pass at all, only the fp64 re-sweep
     of a cancelled pair), so this is what holds them to 1e-5 where the discrete solution oscillates and K is large."""
     A, B = 12, 9
-    X = _paths(A, T, d, 10000 + 100 * d + T, step)
-    Y = _paths(B, T, d, 20000 + 100 * d + T, step)
+    X = walks(A, T, d, 10000 + 100 * d + T, step)
+    Y = walks(B, T, d, 20000 + 100 * d + T, step)
     Kref = np.concatenate([C.gram_fwd_bwd(X, X, h, 0, want_grad=False)[0], C.gram_fwd_bwd(X, Y, h, 0, want_grad=False)[0]], 1)
     if not np.isfinite(Kref).all() or np.abs(Kref).max() > 1e30:
         pytest.skip("K beyond the fp32 range: no fp32 answer exists")
@@ -282,8 +269,8 @@ def test_third_caller_order3_coverage(gpu, yx):
     from sigsvgd_amd import ops
 
     h = 1.0
-    X = _paths(6, 100, 3, 31, 0.05)
-    Y = X if yx else _paths(6, 100, 3, 32, 0.05)
+    X = walks(6, 100, 3, 31, 0.05)
+    Y = X if yx else walks(6, 100, 3, 32, 0.05)
     go = np.random.default_rng(33).uniform(0.5, 1.5, (6, 6)).astype(np.float32)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, 3, grad_out=go.astype(np.float64))
     Xg, gog = torch.as_tensor(X, device=gpu), torch.as_tensor(go, device=gpu)
@@ -291,6 +278,6 @@ def test_third_caller_order3_coverage(gpu, yx):
     K, g = ops.gram_fwd_bwd(Xg, Yg, 1.0 / h, 3, grad_out=gog, y_is_x=yx)
     Kf = ops.gram_fwd(Xg, Yg, 1.0 / h, 3, y_is_x=yx)
     torch.cuda.synchronize()
-    assert _relK(K.cpu().numpy(), Kref) < TOL
-    assert _relK(Kf.cpu().numpy(), Kref) < TOL
-    assert _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_entry(Kf.cpu().numpy(), Kref, 1e-6) < TOL
+    assert rel_max(g.cpu().numpy(), gref) < TOL

@@ -6,26 +6,10 @@ import pytest
 import torch
 
 from oracle import c_oracle as C
+from parity import rel_entry, rel_max, walks
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-
-
-def _paths(A, T, d, seed, scale):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _relK(a, b):
-    """K parity as north_star states it: max over entries of |K - K_ref| / |K_ref| (K > 0 always)"""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    # (round 4: plain relative error per entry -- rounds 2-3 floored the denominator at 0.1; the 1e-6 only keeps an exact zero
-    #  out of it.  Pairs whose K is small against their grid are solved by the exact fp64 pass now: DESIGN.md section 3)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 @pytest.mark.parametrize("T,d", [(64, 7), (33, 3), (128, 14), (96, 5)])
@@ -35,7 +19,7 @@ def test_regimes_self_gram(gpu, T, d, scale, h):
     from sigsvgd_amd import ops
 
     N = 10
-    X = _paths(N, T, d, 21, scale)
+    X = walks(N, T, d, 21, scale)
     Kref, gref = C.gram_fwd_bwd(X, X, h, 0)
     if not np.isfinite(Kref).all() or Kref.max() > 1e30:
         pytest.skip("regime overflows the oracle")
@@ -43,10 +27,10 @@ def test_regimes_self_gram(gpu, T, d, scale, h):
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / h, y_is_x=True)
     Ko, go_ = ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0 / h)
     assert torch.isfinite(K).all() and torch.isfinite(g).all()
-    assert _relK(K.cpu().numpy(), Kref) < TOL, ("K sym", Kref.max())
-    assert _relK(Ko.cpu().numpy(), Kref) < TOL, ("K ordered", Kref.max())
-    assert _rel(g.cpu().numpy(), gref) < TOL, ("grad sym", Kref.max(), np.abs(gref).max())
-    assert _rel(go_.cpu().numpy(), gref) < TOL, ("grad ordered", Kref.max(), np.abs(gref).max())
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL, ("K sym", Kref.max())
+    assert rel_entry(Ko.cpu().numpy(), Kref, 1e-6) < TOL, ("K ordered", Kref.max())
+    assert rel_max(g.cpu().numpy(), gref) < TOL, ("grad sym", Kref.max(), np.abs(gref).max())
+    assert rel_max(go_.cpu().numpy(), gref) < TOL, ("grad ordered", Kref.max(), np.abs(gref).max())
 
 
 @pytest.mark.parametrize("T,d,n", [(20, 2, 2), (10, 3, 4), (30, 2, 3)])
@@ -54,10 +38,10 @@ def test_regimes_self_gram(gpu, T, d, scale, h):
 def test_regimes_coverage_kernel(gpu, T, d, n, scale, h):
     from sigsvgd_amd import ops
 
-    X, Y = _paths(6, T, d, 31, scale), _paths(7, T, d, 32, scale)
+    X, Y = walks(6, T, d, 31, scale), walks(7, T, d, 32, scale)
     Kref, gref = C.gram_fwd_bwd(X, Y, h, n)
     K, g = ops.gram_fwd_bwd(torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu), 1.0 / h, n)
-    assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL
+    assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
 
 
 @pytest.mark.parametrize("T,d", [(64, 7), (128, 14), (40, 2)])
@@ -67,7 +51,7 @@ def test_degenerate_paths(gpu, T, d):
     from sigsvgd_amd import ops
 
     const = np.tile(np.random.default_rng(1).standard_normal((3, 1, d)).astype(np.float32), (1, T, 1))
-    mov = _paths(4, T, d, 2, 0.05)
+    mov = walks(4, T, d, 2, 0.05)
     K, g = ops.gram_fwd_bwd(torch.as_tensor(const, device=gpu), torch.as_tensor(mov, device=gpu), 1.0)
     assert torch.equal(K, torch.ones_like(K))
     K2, g2 = ops.gram_fwd_bwd(torch.as_tensor(mov, device=gpu), torch.as_tensor(const, device=gpu), 1.0)
@@ -78,13 +62,13 @@ def test_degenerate_paths(gpu, T, d):
     K3, g3 = ops.gram_fwd_bwd(torch.as_tensor(same, device=gpu), torch.as_tensor(same, device=gpu), 1.0, y_is_x=True)
     assert float((K3 - K3[0, 0]).abs().max()) <= 1e-6 * float(K3[0, 0])
     # (identical rows up to the order of the fp32 column-side sums)
-    assert _rel(g3[1:].cpu().numpy(), g3[:1].double().cpu().numpy().repeat(4, 0)) < 3e-6
+    assert rel_max(g3[1:].cpu().numpy(), g3[:1].double().cpu().numpy().repeat(4, 0)) < 3e-6
     # a repeated point: path of length T with x[t] == x[t+1] at one place vs the oracle
     rep = mov.copy()
     rep[:, T // 2] = rep[:, T // 2 - 1]
     Kref, gref = C.gram_fwd_bwd(rep, mov, 1.0, 0)
     K4, g4 = ops.gram_fwd_bwd(torch.as_tensor(rep, device=gpu), torch.as_tensor(mov, device=gpu), 1.0)
-    assert _relK(K4.cpu().numpy(), Kref) < TOL and _rel(g4.cpu().numpy(), gref) < TOL
+    assert rel_entry(K4.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g4.cpu().numpy(), gref) < TOL
 
 
 @pytest.mark.parametrize("T,d,n,generic", [(64, 7, 0, False), (32, 2, 0, False), (100, 5, 0, False), (20, 2, 2, False),
@@ -95,7 +79,7 @@ def test_non_finite_inputs_propagate_without_hanging(gpu, T, d, n, generic):
     exponential hands a NaN through)"""
     from sigsvgd_amd import ops
 
-    X = _paths(9, T, d, 5, 0.05)
+    X = walks(9, T, d, 5, 0.05)
     X[3, min(10, T - 2), d - 1] = np.nan
     Xg = torch.as_tensor(X, device=gpu)
     K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0, n, y_is_x=True, force_generic=generic)
@@ -115,11 +99,11 @@ def test_rough_long_paths_are_solved(gpu):
     from sigsvgd_amd import ops
 
     for (T, d, scale) in [(100, 7, 0.25), (128, 14, 0.15), (66, 3, 0.4), (128, 2, 0.5)]:
-        X = _paths(6, T, d, 21, scale)
+        X = walks(6, T, d, 21, scale)
         Kref, gref = C.gram_fwd_bwd(X, X, 1.0, 0)
         Xg = torch.as_tensor(X, device=gpu)
         K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0, y_is_x=True)
         assert torch.isfinite(g).all()
-        assert _relK(K.cpu().numpy(), Kref) < TOL and _rel(g.cpu().numpy(), gref) < TOL, (T, d, float(Kref.max()))
+        assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL, (T, d, float(Kref.max()))
         K2, g2 = ops.gram_fwd_bwd(Xg, Xg.clone(), 1.0)
-        assert _relK(K2.cpu().numpy(), Kref) < TOL and _rel(g2.cpu().numpy(), gref) < TOL
+        assert rel_entry(K2.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g2.cpu().numpy(), gref) < TOL

@@ -9,7 +9,7 @@ range, a race between the block sum of the column-side gradient and the next pai
 without a pair that misses a barrier.  (The file was written with a variant that stores the next column's fp64 side into a
 second buffer during the pair and moves the second barrier into the next pair; it passed here and lost time, DESIGN.md
 5.1.  The cases are the ones that variant needs, so a next attempt finds them in place.)  Every case below therefore
-asserts, from `helpers.gram_geometry` with the device's CU count, the regime of
+asserts, from `plans.gram_geometry` with the device's CU count, the regime of
 tests/test_gpu_partition.py (items >= 2 grid + 1, a range that starts inside a tile, one that crosses a tile boundary, a
 tile met by two workgroups), that ranges of three items exist and -- Y-is-X launches, whose size is free -- that one of them
 crosses a tile boundary, at sizes ragged against the tile height, with signed weights where the launch takes them.
@@ -30,9 +30,9 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import device_cus, gram_geometry, gram_item_ranges, gram_multi_item_regime, signed_weights
 from oracle import c_oracle as C
-from test_gram_geometry import probes
+from parity import rel_entry, rel_max, signed_weights, walks
+from plans import device_cus, gram_geometry, gram_item_ranges, gram_multi_item_regime, probes
 
 pytestmark = pytest.mark.gpu
 
@@ -55,20 +55,6 @@ CASES = [
 
 def _id(c):
     return f"{c.launch}-T{c.T}-d{c.d}"
-
-
-def _paths(A, T, d, seed, scale=0.05):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _relK(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 def _claim(c):
@@ -98,8 +84,8 @@ def _launched(c, gpu):
     if c not in _cache:
         A, B, sym, grad, g = _claim(c)
         h = 1.1 if sym else 0.9
-        X = _paths(A, c.T, c.d, 21 if sym else 11)
-        Y = X if sym else _paths(B, c.T, c.d, 12)
+        X = walks(A, c.T, c.d, 21 if sym else 11, 0.05)
+        Y = X if sym else walks(B, c.T, c.d, 12, 0.05)
         go = signed_weights(A, B, 23 if sym else 13) if grad else None
         Kref, gref = C.gram_fwd_bwd(X, Y, h, 0, grad_out=go, want_grad=grad)
         Xg = torch.as_tensor(X, device=gpu)
@@ -122,8 +108,8 @@ def _launched(c, gpu):
 @pytest.mark.parametrize("c", CASES, ids=_id)
 def test_against_the_oracle(gpu, c):
     s = _launched(c, gpu)
-    eK = _relK(s["K"].cpu().numpy(), s["Kref"])
-    eg = _rel(s["gx"].cpu().numpy(), s["gref"]) if s["grad"] else 0.0
+    eK = rel_entry(s["K"].cpu().numpy(), s["Kref"], 1e-6)
+    eg = rel_max(s["gx"].cpu().numpy(), s["gref"]) if s["grad"] else 0.0
     print(f"K {eK:.2e} gradient {eg:.2e}")
     assert eK < TOL and eg < TOL
     if s["sym"]:

@@ -15,6 +15,7 @@ import torch
 
 import radial_reference as RR
 from oracle import sigkernel_oracle as O
+from parity import np64, rel_entry, rel_max
 
 pytestmark = pytest.mark.gpu
 
@@ -25,20 +26,6 @@ H = 1.0
 
 def ktol(io):
     return 1e-9 if io == F64 else 2.0**-23  # (fp32 I/O: K within its one rounding to fp32)
-
-
-def relK(K, Kr):  # plain relative error per entry
-    assert np.abs(Kr).min() >= 0.5, np.abs(Kr).min()
-    return float((np.abs(np.asarray(K, np.float64) - Kr) / np.abs(Kr)).max())
-
-
-def relmax(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def np64(t):
-    return t.detach().double().cpu().numpy()
 
 
 @functools.lru_cache(maxsize=None)
@@ -78,10 +65,10 @@ def test_long_route_ordered_pairs(gpu, A, B, TX, TY, d, n, sym, io, kind):
     Kr, gr, _ = reference(A, B, TX, TY, d, n, kind, True, sym)
     X, Y, go = dev(inputs(A, TX, d, 0), gpu, io), dev(inputs(B, TY, d, 5), gpu, io), dev(weights(A, B), gpu, io)
     K, gX = ops.gram_long_fwd_bwd(X, Y, 1.0 / H, n, kind, go, sym=sym)
-    print("long", (A, B, TX, TY, d, n, sym, io, kind), relK(np64(K), Kr), relmax(np64(gX), gr))
+    print("long", (A, B, TX, TY, d, n, sym, io, kind), rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(gX), gr))
     assert K.dtype == io and gX.dtype == io and gX.shape == X.shape
-    assert relK(np64(K), Kr) < ktol(io)
-    assert relmax(np64(gX), gr) < 1e-5
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < ktol(io)
+    assert rel_max(np64(gX), gr) < 1e-5
     assert torch.equal(ops.gram_long_fwd(X, Y, 1.0 / H, n, kind), K)
     K2, g2 = ops.gram_long_fwd_bwd(X, Y, 1.0 / H, n, kind, go, sym=sym)
     assert torch.equal(K, K2) and torch.equal(gX, g2)
@@ -97,9 +84,9 @@ def test_two_sided_both_slots(gpu, kind, io):
     Kr, gxr, gyr = reference(A, B, TX, TY, d, n, kind)
     X, Y, go = dev(inputs(A, TX, d, 0), gpu, io), dev(inputs(B, TY, d, 5), gpu, io), dev(weights(A, B), gpu, io)
     K, gX, gY = ops.gram_long_fwd_bwd2(X, Y, 1.0 / H, n, kind, go)
-    print("long2", kind, io, relK(np64(K), Kr), relmax(np64(gX), gxr), relmax(np64(gY), gyr))
-    assert relK(np64(K), Kr) < ktol(io)
-    assert relmax(np64(gX), gxr) < 1e-5 and relmax(np64(gY), gyr) < 1e-5
+    print("long2", kind, io, rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(gX), gxr), rel_max(np64(gY), gyr))
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < ktol(io)
+    assert rel_max(np64(gX), gxr) < 1e-5 and rel_max(np64(gY), gyr) < 1e-5
     assert torch.equal(K, ops.gram_long_fwd(X, Y, 1.0 / H, n, kind))
     K2, gX2, gY2 = ops.gram_long_fwd_bwd2(X, Y, 1.0 / H, n, kind, go)
     assert torch.equal(K, K2) and torch.equal(gX, gX2) and torch.equal(gY, gY2)
@@ -116,10 +103,10 @@ def test_two_sided_y_is_x(gpu, kind):
     X, go = dev(inputs(A, T, d, 0), gpu), dev(weights(A, A), gpu)
     K, gX, gY = ops.gram_long_fwd_bwd2(X, X, 1.0 / H, n, kind, go, y_is_x=True)
     assert gY is None and torch.equal(K, K.T)
-    print("long2 yx", kind, relK(np64(K), Kr), relmax(np64(gX), gxr))
-    assert relK(np64(K), Kr) < 1e-9 and relmax(np64(gX), gxr) < 1e-5
+    print("long2 yx", kind, rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(gX), gxr))
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(gX), gxr) < 1e-5
     Ks, gs, _ = ops.gram_long_fwd_bwd2(X, X, 1.0 / H, n, kind, go, sym=True, y_is_x=True)
-    assert torch.equal(Ks, K) and relmax(np64(gs), gxr + gyr) < 1e-5
+    assert torch.equal(Ks, K) and rel_max(np64(gs), gxr + gyr) < 1e-5
 
 
 # ---- 3. paired ---------------------------------------------------------------------------------------------------------------
@@ -132,9 +119,9 @@ def test_paired(gpu, A, TX, TY, d, n, io, kind):
     Kr, gxr, gyr = RR.pair_backward(Xn, Yn, w, kind, H, n)
     X, Y = dev(Xn, gpu, io), dev(Yn, gpu, io)
     K, gX, gY = ops.pair_fwd_bwd(X, Y, 1.0 / H, n, kind, dev(w, gpu, io))
-    print("pair", (A, TX, TY, d, n, io, kind), relK(np64(K), Kr), relmax(np64(gX), gxr), relmax(np64(gY), gyr))
-    assert relK(np64(K), Kr) < ktol(io)
-    assert relmax(np64(gX), gxr) < 1e-5 and relmax(np64(gY), gyr) < 1e-5
+    print("pair", (A, TX, TY, d, n, io, kind), rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(gX), gxr), rel_max(np64(gY), gyr))
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < ktol(io)
+    assert rel_max(np64(gX), gxr) < 1e-5 and rel_max(np64(gY), gyr) < 1e-5
     assert torch.equal(K, ops.gram_long_fwd(X, Y, 1.0 / H, n, kind).diagonal())
     assert torch.equal(K, ops.pair_fwd(X, Y, 1.0 / H, n, kind))
     K2, gX2, gY2 = ops.pair_fwd_bwd(X, Y, 1.0 / H, n, kind, dev(w, gpu, io))
@@ -150,7 +137,7 @@ def test_partial_shares_add_up(gpu, N, T, d, n, io, kind):
     Kr, gr, _ = reference(N, N, T, T, d, n, kind, yseed=0)
     X, go = dev(inputs(N, T, d, 0), gpu, io), dev(weights(N, N), gpu, io)
     Kf, gf, _ = ops.gram_long_fwd_bwd2(X, X, 1.0 / H, n, kind, go, y_is_x=True)
-    assert relK(np64(Kf), Kr) < ktol(io) and relmax(np64(gf), gr) < 1e-5
+    assert rel_entry(np64(Kf), Kr, 0.0, min_ref=0.5) < ktol(io) and rel_max(np64(gf), gr) < 1e-5
     for world in (2, 3):
         for fold in (True, False):
             Ks, gs = torch.zeros_like(Kf), torch.zeros(N, T, d, dtype=F64, device=gpu)
@@ -162,10 +149,10 @@ def test_partial_shares_add_up(gpu, N, T, d, n, io, kind):
                 Ks += Kp
                 gs += gp
             assert torch.equal(Ks, Kf), (world, fold)  # (every pair is in one share: the sum adds zeros)
-            print("partial", (N, T, d, n, io, kind, world, fold), relmax(np64(gs), np64(gf)), relmax(np64(gs), gr))
+            print("partial", (N, T, d, n, io, kind, world, fold), rel_max(np64(gs), np64(gf)), rel_max(np64(gs), gr))
             if io == F64:
-                assert relmax(np64(gs), np64(gf)) < 1e-9
-            assert relmax(np64(gs), gr) < 1e-5
+                assert rel_max(np64(gs), np64(gf)) < 1e-9
+            assert rel_max(np64(gs), gr) < 1e-5
 
 
 # ---- 5. coverage kernel ------------------------------------------------------------------------------------------------------
@@ -189,14 +176,15 @@ def test_coverage_kernel(gpu, A, B, T, d, n, sym, io, kind):
     for forced in (False, True):
         K, gX = ops.gram_fwd_bwd(X, Y, 1.0 / H, n, kind, go, sym=sym, force_generic=forced)
         K1 = ops.gram_fwd(X, Y, 1.0 / H, n, kind, force_generic=forced)
-        print("coverage", (A, B, T, d, n, sym, io, kind, forced), relK(np64(K), Kr), relK(np64(K1), Kr), relmax(np64(gX), gr))
-        assert relK(np64(K), Kr) < ktol(io) and relK(np64(K1), Kr) < ktol(io)
-        assert relmax(np64(gX), gr) < 1e-5
+        eK, eK1 = rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_entry(np64(K1), Kr, 0.0, min_ref=0.5)
+        print("coverage", (A, B, T, d, n, sym, io, kind, forced), eK, eK1, rel_max(np64(gX), gr))
+        assert eK < ktol(io) and eK1 < ktol(io)
+        assert rel_max(np64(gX), gr) < 1e-5
         K2, g2 = ops.gram_fwd_bwd(X, Y, 1.0 / H, n, kind, go, sym=sym, force_generic=forced)
         assert torch.equal(K, K2) and torch.equal(gX, g2) and torch.equal(K1, ops.gram_fwd(X, Y, 1.0 / H, n, kind, force_generic=forced))
     if (T, n) == (10, 2) and not sym:  # the first-order solver is the coverage kernel's too
         Kn = ops.gram_fwd(X, Y, 1.0 / H, n, kind, naive=True)
-        assert 1e-7 < relmax(np64(Kn), Kr) < 1e-2  # (another stencil: close to, not equal to, the second-order solution)
+        assert 1e-7 < rel_max(np64(Kn), Kr) < 1e-2  # (another stencil: close to, not equal to, the second-order solution)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -208,9 +196,9 @@ def test_coverage_kernel_symmetric_solve(gpu, kind):
     Kr, gr, _ = reference(N, N, T, T, d, 0, kind, yseed=0)
     X, go = dev(inputs(N, T, d, 0), gpu), dev(weights(N, N), gpu)
     K, gX = ops.gram_fwd_bwd(X, X, 1.0 / H, 0, kind, go, y_is_x=True)
-    print("coverage yx", kind, relK(np64(K), Kr), relmax(np64(gX), gr))
+    print("coverage yx", kind, rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(gX), gr))
     assert torch.equal(K, K.T)
-    assert relK(np64(K), Kr) < 1e-9 and relmax(np64(gX), gr) < 1e-5
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(gX), gr) < 1e-5
     K2, g2 = ops.gram_fwd_bwd(X, X, 1.0 / H, 0, kind, go, y_is_x=True)
     assert torch.equal(K, K2) and torch.equal(gX, g2)
 
@@ -225,8 +213,8 @@ def test_coverage_kernel_and_long_route_agree(gpu, kind):
     Kl, gl = ops.gram_long_fwd_bwd(X, Y, 1.0 / H, n, kind, go)
     for forced in (False, True):
         Kc, gc = ops.gram_fwd_bwd(X, Y, 1.0 / H, n, kind, go, force_generic=forced)
-        print("overlap", kind, forced, relK(np64(Kc), np64(Kl)), relmax(np64(gc), np64(gl)))
-        assert relK(np64(Kc), np64(Kl)) < 1e-9 and relmax(np64(gc), np64(gl)) < 1e-5
+        print("overlap", kind, forced, rel_entry(np64(Kc), np64(Kl), 0.0, min_ref=0.5), rel_max(np64(gc), np64(gl)))
+        assert rel_entry(np64(Kc), np64(Kl), 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(gc), np64(gl)) < 1e-5
 
 
 # ---- 6. public surface -------------------------------------------------------------------------------------------------------
@@ -265,18 +253,19 @@ def test_compute_gram(gpu, kind, T, n):
         (W * k.compute_Gram(X, Y)).sum().backward()
         out.append((np64(K), np64(g1), np64(X.grad)))
     (K, g1, gw), (Ku, g1u, gwu) = out
-    print("compute_Gram", kind, T, n, relK(K, Kr), relmax(g1, gr1), relmax(gw, gr), relK(K, Ku), relmax(gw, gwu))
-    assert relK(K, Kr) < 1e-9 and relmax(g1, gr1) < 1e-5 and relmax(gw, gr) < 1e-5
-    assert relK(K, Ku) < 1e-9 and relmax(g1, g1u) < 1e-5 and relmax(gw, gwu) < 1e-5  # the user route on the same kernel
+    eK, eKu = rel_entry(K, Kr, 0.0, min_ref=0.5), rel_entry(K, Ku, 0.0, min_ref=0.5)
+    print("compute_Gram", kind, T, n, eK, rel_max(g1, gr1), rel_max(gw, gr), eKu, rel_max(gw, gwu))
+    assert eK < 1e-9 and rel_max(g1, gr1) < 1e-5 and rel_max(gw, gr) < 1e-5
+    assert eKu < 1e-9 and rel_max(g1, g1u) < 1e-5 and rel_max(gw, gwu) < 1e-5  # the user route on the same kernel
     # grad_Y: the second slot
     k = sk.SigKernel(_static(kind, H), n)
     X, Yg = dev(inputs(A, T, d, 0), gpu).requires_grad_(True), Y.clone().requires_grad_(True)
     (W * k.compute_Gram(X, Yg, grad_Y=True)).sum().backward()
-    assert relmax(np64(X.grad), gr) < 1e-5 and relmax(np64(Yg.grad), gyr) < 1e-5
+    assert rel_max(np64(X.grad), gr) < 1e-5 and rel_max(np64(Yg.grad), gyr) < 1e-5
     # sym and gram_and_grad
     Ks, gs = k.gram_and_grad(dev(inputs(A, T, d, 0), gpu), None, dev(weights(A, A), gpu), sym=True)
     Krs, grs, _ = reference(A, A, T, T, d, n, kind, True, True, yseed=0)
-    assert relK(np64(Ks), Krs) < 1e-9 and relmax(np64(gs), grs) < 1e-5
+    assert rel_entry(np64(Ks), Krs, 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(gs), grs) < 1e-5
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -290,7 +279,7 @@ def test_compute_kernel_and_mmd(gpu, kind):
     X, Y = dev(Xn, gpu).requires_grad_(True), dev(Yn, gpu).requires_grad_(True)
     K = k.compute_kernel(X, Y)
     K.sum().backward()
-    assert relK(np64(K), Kr) < 1e-9 and relmax(np64(X.grad), gxr) < 1e-5 and relmax(np64(Y.grad), gyr) < 1e-5
+    assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(X.grad), gxr) < 1e-5 and rel_max(np64(Y.grad), gyr) < 1e-5
     # mmd = mean K_XX + mean K_YY - 2 mean K_XY, every gradient through its own slot(s)
     T = 20
     Xn, Yn = inputs(4, T, d, 0), inputs(5, T, d, 5)
@@ -302,8 +291,8 @@ def test_compute_kernel_and_mmd(gpu, kind):
     mmd.backward()
     ref = Kxx.mean() + Kyy.mean() - 2.0 * Kxy.mean()
     assert abs(float(mmd) - ref) < 1e-9 * max(1.0, abs(ref))
-    assert relmax(np64(X.grad), gxx / 16.0 - 2.0 * gxy / 20.0) < 1e-5
-    assert relmax(np64(Y.grad), gyy / 25.0 - 2.0 * gyx / 20.0) < 1e-5
+    assert rel_max(np64(X.grad), gxx / 16.0 - 2.0 * gxy / 20.0) < 1e-5
+    assert rel_max(np64(Y.grad), gyy / 25.0 - 2.0 * gyx / 20.0) < 1e-5
     d0 = float(k.compute_distance(X.detach(), X.detach()))
     assert abs(d0) < 1e-12
 
@@ -323,15 +312,15 @@ def test_median_bandwidth_and_svgd_step(gpu, kind):
     Km = sk.SigKernel(cls(), 0).compute_Gram(Xg.double(), Xg.double())  # the default median, selected on the device
     Kh = sk.SigKernel(cls(lambda _: h), 0).compute_Gram(Xg.double(), Xg.double())
     Kr, gr, _ = RR.gram_backward(Xn, Xn, None, kind, h, 0)
-    print("median", kind, h, relK(np64(Km), np64(Kh)), relK(np64(Km), Kr))
-    assert relK(np64(Km), np64(Kh)) < 1e-9 and relK(np64(Km), Kr) < 1e-9
+    print("median", kind, h, rel_entry(np64(Km), np64(Kh), 0.0, min_ref=0.5), rel_entry(np64(Km), Kr, 0.0, min_ref=0.5))
+    assert rel_entry(np64(Km), np64(Kh), 0.0, min_ref=0.5) < 1e-9 and rel_entry(np64(Km), Kr, 0.0, min_ref=0.5) < 1e-9
     # one SVGD step with the named static kernel against the reference's velocity
     kernel = SignatureKernel(lambda _: h, depth=0, static_kernel=RR.NAMES[kind])
     assert type(kernel.kernel.static_kernel) is cls
     Xnew, info = SVGD(kernel, optimizer_class=None, lr=0.05).step(Xg.clone(), score.to(gpu))
     v = O.svgd_velocity(Kr, score.numpy(), gr)
-    print("svgd", kind, relmax(np64(info["grad"]), v), relmax(np64(Xnew), Xn - 0.05 * v))
-    assert relmax(np64(info["grad"]), v) < 1e-5 and relmax(np64(Xnew), Xn - 0.05 * v) < 1e-5
+    print("svgd", kind, rel_max(np64(info["grad"]), v), rel_max(np64(Xnew), Xn - 0.05 * v))
+    assert rel_max(np64(info["grad"]), v) < 1e-5 and rel_max(np64(Xnew), Xn - 0.05 * v) < 1e-5
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -362,11 +351,11 @@ def test_sharded_step(gpu, kind):
             else:
                 K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / H, 0, kind)
             _, Xb = ops.svgd_phi(K, sg, g, X=Xg, lr=1e-3)
-            assert relmax(np64(Xa), np64(Xb)) < 1e-6
+            assert rel_max(np64(Xa), np64(Xb)) < 1e-6
             Kr, gr, _ = reference(N, N, T, T, d, 0, kind, weighted=False, yseed=0)  # (inputs(N, T, d, 0) is X)
             v = O.svgd_velocity(Kr, s.numpy(), gr)
-            print("sharded", kind, T, route, relmax(np64(Xa), X.double().numpy() - 1e-3 * v))
-            assert relmax(np64(Xa), X.double().numpy() - 1e-3 * v) < 1e-5
+            print("sharded", kind, T, route, rel_max(np64(Xa), X.double().numpy() - 1e-3 * v))
+            assert rel_max(np64(Xa), X.double().numpy() - 1e-3 * v) < 1e-5
     finally:
         dist.destroy_process_group()
 
@@ -389,6 +378,6 @@ def test_distant_bundles_repel_under_imq_and_not_under_rbf(gpu):
         for kind in KINDS:
             Kr, gr, _ = RR.gram_backward(Xn, Xn, cross, kind, h, 0)
             K, g = launch(kind)
-            print("bundles", kind, relK(np64(K), Kr), relmax(np64(g), gr), np.abs(gr).max())
-            assert relK(np64(K), Kr) < 1e-9 and relmax(np64(g), gr) < 1e-5
+            print("bundles", kind, rel_entry(np64(K), Kr, 0.0, min_ref=0.5), rel_max(np64(g), gr), np.abs(gr).max())
+            assert rel_entry(np64(K), Kr, 0.0, min_ref=0.5) < 1e-9 and rel_max(np64(g), gr) < 1e-5
             assert bool((K[:4, 4:] != 1.0).all()) and float(g.abs().amax(dim=(1, 2)).min()) > 0.0

@@ -8,15 +8,10 @@ import pytest
 import torch
 
 from oracle import vector_oracle as VO
+from parity import rel_max
 
 pytestmark = pytest.mark.gpu
 G = np.load(os.path.join(os.path.dirname(__file__), "golden", "ref_vector_kernels.npz"))
-
-
-def rel(a, b):
-    a = a.detach().double().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, np.float64)
-    b = np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
 def t64(a, gpu):
@@ -32,12 +27,12 @@ def test_plain_kernels_reference_fixtures(gpu, name):
     X, Y = t64(G["X"], gpu), t64(G["Y"], gpu)
     K, dK = ker(X, Y, h=0.8)
     assert K.dtype == torch.float64 and K.shape == (7, 7) and dK.shape == (7, 5)
-    assert rel(K, G[f"{name}_h0.8_K"]) < 1e-11 and rel(dK, G[f"{name}_h0.8_dK"]) < 1e-11
-    assert rel(ker(X, Y, h=0.8, compute_grad=False), G[f"{name}_h0.8_Konly"]) < 1e-11
+    assert rel_max(K, G[f"{name}_h0.8_K"]) < 1e-11 and rel_max(dK, G[f"{name}_h0.8_dK"]) < 1e-11
+    assert rel_max(ker(X, Y, h=0.8, compute_grad=False), G[f"{name}_h0.8_Konly"]) < 1e-11
     K, dK = ker(X, Y)  # median heuristic (float32 log inside, as in the reference)
-    assert rel(K, G[f"{name}_med_K"]) < 1e-6 and rel(dK, G[f"{name}_med_dK"]) < 1e-6
+    assert rel_max(K, G[f"{name}_med_K"]) < 1e-6 and rel_max(dK, G[f"{name}_med_dK"]) < 1e-6
     K, dK = ker(X, X, h=1.1)
-    assert rel(K, G[f"{name}_xx_K"]) < 1e-11 and rel(dK, G[f"{name}_xx_dK"]) < 1e-11
+    assert rel_max(K, G[f"{name}_xx_K"]) < 1e-11 and rel_max(dK, G[f"{name}_xx_dK"]) < 1e-11
 
 
 @pytest.mark.parametrize("name", ["sgauss", "simq"])
@@ -48,10 +43,10 @@ def test_scaled_kernels_reference_fixtures(gpu, name):
     X, Y, M, Mns = (t64(G[k], gpu) for k in ("X", "Y", "M", "Mns"))
     for key, kw in [("I_h0.8", dict(h=0.8)), ("M_h0.8", dict(M=M, h=0.8)), ("Mns_h1.3", dict(M=Mns, h=1.3))]:
         K, dK = ker(X, Y, **kw)
-        assert rel(K, G[f"{name}_{key}_K"]) < 1e-11, key
-        assert rel(dK, G[f"{name}_{key}_dK"]) < 1e-11, key
+        assert rel_max(K, G[f"{name}_{key}_K"]) < 1e-11, key
+        assert rel_max(dK, G[f"{name}_{key}_dK"]) < 1e-11, key
     K, dK = ker(X, Y, M=M)
-    assert rel(K, G[f"{name}_M_med_K"]) < 1e-6 and rel(dK, G[f"{name}_M_med_dK"]) < 1e-6
+    assert rel_max(K, G[f"{name}_M_med_K"]) < 1e-6 and rel_max(dK, G[f"{name}_M_med_dK"]) < 1e-6
 
 
 def test_three_dimensional_particles_fixture(gpu):
@@ -60,7 +55,7 @@ def test_three_dimensional_particles_fixture(gpu):
     X3 = t64(G["X3"], gpu)
     K, dK = GaussianKernel()(X3, X3, h=1.7)
     assert dK.shape == (6, 12)
-    assert rel(K, G["gauss_X3_K"]) < 1e-11 and rel(dK, G["gauss_X3_dK"]) < 1e-11
+    assert rel_max(K, G["gauss_X3_K"]) < 1e-11 and rel_max(dK, G["gauss_X3_dK"]) < 1e-11
 
 
 # ---- fp32 against the fp64 oracle at awkward and larger sizes -----------------------------------------
@@ -76,14 +71,14 @@ def test_vec_ops_fp32_vs_oracle(gpu, A, B, D, kind):
     h = float(np.sqrt(D))
     sq = ops.vec_sqdist(torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu))
     want_sq = VO.pw_dist_sq(X, Y)
-    assert rel(sq, want_sq) < 1e-5
+    assert rel_max(sq, want_sq) < 1e-5
     k = _lib.VEC_GAUSSIAN if kind == "gaussian" else _lib.VEC_IMQ
     K, dK = ops.vec_kernel(sq, torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu), k, 1 / h**2, -1 / h**2,
                            grad_out=torch.as_tensor(go, device=gpu))
     wantK = np.exp(-0.5 / h**2 * want_sq) if kind == "gaussian" else (1 + 0.5 * want_sq / h**2) ** -0.5
-    assert rel(K, wantK) < 1e-5
+    assert rel_max(K, wantK) < 1e-5
     want = VO.vec_kernel_weighted_grad(want_sq, X, Y, go, kind, h, -1 / h**2)
-    assert rel(dK, want) < 1e-5
+    assert rel_max(dK, want) < 1e-5
     # gradient only / kernel only
     assert ops.vec_kernel(sq, None, None, k, 1 / h**2, 0.0, want_grad=False)[1] is None
     K2, dK2 = ops.vec_kernel(sq, torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu), k, 1 / h**2, -1 / h**2,
@@ -101,7 +96,7 @@ def test_metric_sqdist_fp32_vs_oracle(gpu):
     Xg, Yg, Mg = (torch.as_tensor(a, device=gpu) for a in (X, Y, M))
     sq = ops.vec_sqdist(Xg, Yg, Xg @ Mg, Yg @ Mg)
     want, _ = VO.scaled_pw_dist_sq(X, Y, M)
-    assert rel(sq, want) < 1e-5
+    assert rel_max(sq, want) < 1e-5
     assert float(sq.min()) >= 0.0
 
 
@@ -127,8 +122,8 @@ def test_autograd_through_K_matches_torch(gpu):
         sq = ((diff @ kw["M"]) * diff).sum(-1) if kw else (diff * diff).sum(-1)
         Kc = f(sq, ker.get_bandwidth(sq))
         (gc,) = torch.autograd.grad(Kc.sum(), xc)
-        assert rel(K, Kc.detach().numpy()) < 1e-6
-        assert rel(gx, gc.numpy()) < 1e-6
+        assert rel_max(K, Kc.detach().numpy()) < 1e-6
+        assert rel_max(gx, gc.numpy()) < 1e-6
 
 
 def test_sqdist_autograd_second_slot(gpu):
@@ -144,7 +139,7 @@ def test_sqdist_autograd_second_slot(gpu):
     xc, yc = X.clone().requires_grad_(True), Y.clone().requires_grad_(True)
     sqc = ((xc[:, None] - yc[None]) ** 2).sum(-1)
     gxc, gyc = torch.autograd.grad((sqc * W).sum(), (xc, yc))
-    assert rel(gx, gxc.numpy()) < 1e-12 and rel(gy, gyc.numpy()) < 1e-12
+    assert rel_max(gx, gxc.numpy()) < 1e-12 and rel_max(gy, gyc.numpy()) < 1e-12
 
 
 # ---- truncated signature ---------------------------------------------------------------------------------
@@ -160,7 +155,7 @@ def test_signature_vs_oracle(gpu, N, L, C, depth, bp, dtype):
     assert S.dtype == dtype and tuple(S.shape) == (N, VO.signature_channels(C, depth))
     assert ops.signature_channels(C, depth) == S.shape[1]
     want = VO.signature(X.astype(np.float32) if dtype == torch.float32 else X, depth, bp)
-    assert rel(S, want) < (1e-6 if dtype == torch.float32 else 1e-13)
+    assert rel_max(S, want) < (1e-6 if dtype == torch.float32 else 1e-13)
 
 
 def test_signature_straight_line_and_single_point(gpu):
@@ -189,10 +184,10 @@ def test_path_sig_kernel_fixture_and_oracle(gpu):
     psk = PathSigKernel()
     K, dK = psk(P1, P2, depth=3, h=0.9)  # h is ignored, as in the reference
     assert K.shape == (6, 6) and dK.shape == (6, 14)
-    assert rel(K, G["psk_d3_h0.9_K"]) < 1e-6 and rel(dK, G["psk_d3_h0.9_dK"]) < 1e-6
+    assert rel_max(K, G["psk_d3_h0.9_K"]) < 1e-6 and rel_max(dK, G["psk_d3_h0.9_dK"]) < 1e-6
     K, dK = psk(P1, P2, depth=2)
-    assert rel(K, G["psk_d2_med_K"]) < 1e-6 and rel(dK, G["psk_d2_med_dK"]) < 1e-6
-    assert rel(psk(P1, P1, depth=3, compute_grad=False), G["psk_d3_Konly"]) < 1e-6
+    assert rel_max(K, G["psk_d2_med_K"]) < 1e-6 and rel_max(dK, G["psk_d2_med_dK"]) < 1e-6
+    assert rel_max(psk(P1, P1, depth=3, compute_grad=False), G["psk_d3_Konly"]) < 1e-6
     # the reference's test shape (tests/test_traj_kernels.py: batch 128, 25 points, (cos, sin) channels), fp32
     g = torch.Generator().manual_seed(0)
     X = torch.randn(128, 25, 1, generator=g)
@@ -200,7 +195,7 @@ def test_path_sig_kernel_fixture_and_oracle(gpu):
     phi = lambda t: torch.cat((t.cos(), t.sin()), -1)
     K, dK = psk(phi(X).to(gpu), phi(Y).to(gpu), X.to(gpu), depth=3, h=2.0**0.5)
     wK, wdK, _ = VO.path_sig_kernel(phi(X).numpy(), phi(Y).numpy(), depth=3)
-    assert rel(K, wK) < 1e-5 and rel(dK, wdK) < 1e-5
+    assert rel_max(K, wK) < 1e-5 and rel_max(dK, wdK) < 1e-5
 
 
 @pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
@@ -226,7 +221,7 @@ def test_signature_backward_vs_oracle(gpu, N, L, C, depth, bp, dtype):
     (g,) = torch.autograd.grad((S * torch.as_tensor(W, dtype=dtype, device=gpu)).sum(), x)
     tol = 1e-11 if dtype == torch.float64 else 1e-5
     assert g.dtype == dtype and g.shape == x.shape
-    assert rel(S.detach(), sig_ref) < tol and rel(g, g_ref) < tol
+    assert rel_max(S.detach(), sig_ref) < tol and rel_max(g, g_ref) < tol
     # the explicit entry point gives the same bits, twice
     g2 = ops.signature_backward(x.detach(), torch.as_tensor(W, dtype=dtype, device=gpu), depth, bp)
     assert torch.equal(g, g2) and torch.equal(g2, ops.signature_backward(x.detach(), torch.as_tensor(W, dtype=dtype, device=gpu), depth, bp))
@@ -257,12 +252,12 @@ def test_path_sig_kernel_is_differentiable_through_the_signature(gpu):
             return Kc
 
         Kref = Ksum(X)
-        assert rel(K.detach(), Kref) < 1e-10
+        assert rel_max(K.detach(), Kref) < 1e-10
         # oracle chain rule: dK_ij/dS_i = -(S_i - S_j)/h^2 K_ij, then the signature's vjp
         Sx = VO.signature(X, depth, True)
         dS = -((Sx[:, None, :] - Sx[None, :, :]) / h**2 * Kref[..., None]).sum(1)
         _, g_chain = VO.signature_vjp(X, dS, depth, True)
-        assert rel(gk, g_chain) < 1e-9
+        assert rel_max(gk, g_chain) < 1e-9
         eps, fd = 1e-6, np.zeros_like(X)
         for idx in [(0, 0, 0), (3, 4, 1), (6, 7, 0), (2, 2, 1), (5, 0, 1)]:
             Xp, Xm = X.copy(), X.copy()
@@ -277,9 +272,9 @@ def test_path_sig_kernel_is_differentiable_through_the_signature(gpu):
     assert est.score.__func__ is ScoreEstimator._svgd_ag_score
     glp, aux = est.score(xs)
     assert aux["grad_k"].shape == xs.shape and bool(torch.isfinite(aux["grad_k"]).all())
-    assert rel(aux["grad_k"], g_chain) < 1e-4 and rel(aux["k_xx"], Kref) < 1e-5
+    assert rel_max(aux["grad_k"], g_chain) < 1e-4 and rel_max(aux["k_xx"], Kref) < 1e-5
     k2, g2 = SVGD(psk32, optimizer_class=None)._compute_kernel(xs.detach().requires_grad_(True))
-    assert rel(g2.reshape(xs.shape), g_chain) < 1e-4
+    assert rel_max(g2.reshape(xs.shape), g_chain) < 1e-4
 
 
 def test_svgd_with_default_gaussian_kernel_matches_closed_form(gpu):
@@ -293,8 +288,8 @@ def test_svgd_with_default_gaussian_kernel_matches_closed_form(gpu):
     Xn, it = s.step(torch.as_tensor(X, device=gpu), torch.as_tensor(score, device=gpu), None)
     K, dK, _ = VO.gaussian(X, X)
     v = -((K @ score.astype(np.float64) - dK) / 40)
-    assert rel(it["k_xx"], K) < 1e-5
-    assert rel(Xn, X - 0.1 * v) < 1e-5
+    assert rel_max(it["k_xx"], K) < 1e-5
+    assert rel_max(Xn, X - 0.1 * v) < 1e-5
 
 
 def test_trajectory_kernel_autograd_to_actions(gpu):
@@ -310,7 +305,7 @@ def test_trajectory_kernel_autograd_to_actions(gpu):
     sq = ((tc[:, None] - tc.detach()[None]) ** 2).sum(-1)
     Kc = (-0.5 / 1.4**2 * sq).exp()
     (dc,) = torch.autograd.grad(Kc.sum(), ac)
-    assert rel(K, Kc.detach().numpy()) < 1e-12 and rel(dK, dc.numpy()) < 1e-12
+    assert rel_max(K, Kc.detach().numpy()) < 1e-12 and rel_max(dK, dc.numpy()) < 1e-12
 
 
 def test_vector_kernel_argument_errors(gpu):
@@ -349,13 +344,13 @@ def test_vec_kernel_fused_fp32_vs_oracle(gpu, A, B, D, kind, offset):
     K, dK = ops.vec_kernel_fused(Xg, Yg, k, 1 / h**2, -1 / h**2, grad_out=gog)
     want_sq = VO.pw_dist_sq(X.astype(np.float64), Y.astype(np.float64))
     wantK = np.exp(-0.5 / h**2 * want_sq) if kind == "gaussian" else (1 + 0.5 * want_sq / h**2) ** -0.5
-    assert rel(K, wantK) < 1e-5
+    assert rel_max(K, wantK) < 1e-5
     want = VO.vec_kernel_weighted_grad(want_sq, X.astype(np.float64), Y.astype(np.float64), go, kind, h, -1 / h**2)
-    assert rel(dK, want) < 2e-5
+    assert rel_max(dK, want) < 2e-5
     K2, none = ops.vec_kernel_fused(Xg, Yg, k, 1 / h**2, -1 / h**2, want_grad=False)
     assert none is None and torch.equal(K2, K)
     none, dK2 = ops.vec_kernel_fused(Xg, Yg, k, 1 / h**2, -1 / h**2, grad_out=gog, want_K=False)
-    assert none is None and rel(dK2, want) < 2e-5
+    assert none is None and rel_max(dK2, want) < 2e-5
 
 
 @pytest.mark.parametrize("A,B,D", [(1024, 1024, 448), (700, 513, 64), (130, 130, 129), (64, 64, 7)])
@@ -399,7 +394,7 @@ def test_vec_kernel_fused_metric_and_classes(gpu):
         K, dK = ops.vec_kernel_fused(Xg, Yg, _lib.VEC_GAUSSIAN, 1 / 3.0**2, -1 / 3.0**2, XM=XM, YM=YM)
         sq = ops.vec_sqdist(Xg, Yg, XM, YM)
         K0, dK0 = ops.vec_kernel(sq, XM, YM, _lib.VEC_GAUSSIAN, 1 / 3.0**2, -1 / 3.0**2)
-        assert rel(K, K0.double().cpu().numpy()) < 1e-5 and rel(dK, dK0.double().cpu().numpy()) < 2e-5
+        assert rel_max(K, K0.double().cpu().numpy()) < 1e-5 and rel_max(dK, dK0.double().cpu().numpy()) < 2e-5
     Xs = torch.as_tensor(rng.normal(size=(40, 96)).astype(np.float32), device=gpu)
     two_launch = GaussianKernel()  # median heuristic: distance matrix needed
     K1, d1 = two_launch(Xs, Xs)
@@ -407,7 +402,7 @@ def test_vec_kernel_fused_metric_and_classes(gpu):
     K2, d2 = GaussianKernel()(Xs, Xs, h=hmed)                       # fused: h given
     K3, d3 = GaussianKernel(bandwidth_fn=lambda _: hmed)(Xs, Xs)    # fused: constant bandwidth function
     for Kx, dx in ((K2, d2), (K3, d3)):
-        assert rel(Kx, K1.double().cpu().numpy()) < 1e-5 and rel(dx, d1.double().cpu().numpy()) < 2e-5
+        assert rel_max(Kx, K1.double().cpu().numpy()) < 1e-5 and rel_max(dx, d1.double().cpu().numpy()) < 2e-5
     Ki, di = ScaledIMQKernel()(Xs, Xs, M=torch.eye(96, device=gpu), h=2.0)
     assert Ki.shape == (40, 40) and di.shape == (40, 96) and bool(torch.isfinite(di).all())
 
@@ -430,6 +425,6 @@ def test_vec_kernel_fused_several_tiles_per_workgroup(gpu, A, B, D, metric):
     K, dK = ops.vec_kernel_fused(Xg, Yg, _lib.VEC_GAUSSIAN, 1 / h**2, -1 / h**2, XM=XM, YM=YM)
     sq = ops.vec_sqdist(Xg, Yg, XM, YM)
     K0, dK0 = ops.vec_kernel(sq, XM if metric else Xg, YM if metric else Yg, _lib.VEC_GAUSSIAN, 1 / h**2, -1 / h**2)
-    assert rel(K, K0.double().cpu().numpy()) < 1e-5 and rel(dK, dK0.double().cpu().numpy()) < 2e-5
+    assert rel_max(K, K0.double().cpu().numpy()) < 1e-5 and rel_max(dK, dK0.double().cpu().numpy()) < 2e-5
     K2, dK2 = ops.vec_kernel_fused(Xg, Yg, _lib.VEC_GAUSSIAN, 1 / h**2, -1 / h**2, XM=XM, YM=YM)
     assert torch.equal(K, K2) and torch.equal(dK, dK2)

@@ -8,31 +8,17 @@ where a workgroup walks several items, ranges cross tile boundaries, the last ti
 entry point -- the reduction inverts a strided or folded tile map.  Every launch runs twice and must return the same
 bytes.  Tolerances: tests/test_gpu_partition.py (K per entry, the gradient relative to its largest entry).
 """
-import numpy as np
 import pytest
 import torch
 
-from helpers import device_cus, gram_geometry
 from oracle import c_oracle as C
+from parity import rel_entry, rel_max, walks
+from plans import device_cus, gram_geometry
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
 H = 1.1
-
-
-def _paths(A, T, d, seed, scale=0.05):
-    rng = np.random.default_rng(seed)
-    return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1).astype(np.float32)
-
-
-def _rel(a, b):
-    return float(np.abs(np.asarray(a, np.float64) - b).max() / max(np.abs(b).max(), 1e-300))
-
-
-def _relK(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float((np.abs(a - b) / np.maximum(np.abs(b), 1e-6)).max())
 
 
 _cache = {}
@@ -44,7 +30,7 @@ def _case(N, T, d, gpu):
     if key not in _cache:
         from sigsvgd_amd import ops
 
-        X = _paths(N, T, d, 51)
+        X = walks(N, T, d, 51, 0.05)
         Kref, gref = C.gram_fwd_bwd(X, X, H, 0)
         Xg = torch.as_tensor(X, device=gpu)
         K, g = ops.gram_fwd_bwd(Xg, Xg, 1.0 / H, 0, y_is_x=True)
@@ -67,7 +53,7 @@ def test_full_launch_against_the_oracle_twice(gpu, N, T, d):
     else:
         assert (T * d) % 4 != 0  # one element per thread
     s = _case(N, T, d, gpu)
-    eK, eg = _relK(s["K"].cpu().numpy(), s["Kref"]), _rel(s["g"].cpu().numpy(), s["gref"])
+    eK, eg = rel_entry(s["K"].cpu().numpy(), s["Kref"], 1e-6), rel_max(s["g"].cpu().numpy(), s["gref"])
     print(f"N={N} T={T} d={d}: {geom['items']} items on {geom['grid']} workgroups, K {eK:.2e} gradient {eg:.2e}")
     K2, g2 = ops.gram_fwd_bwd(s["Xg"], s["Xg"], 1.0 / H, 0, y_is_x=True)
     torch.cuda.synchronize()
@@ -99,8 +85,8 @@ def test_two_owners_add_up_to_the_full_launch(gpu, fold):
         assert sameK and sameg
         Ks += Kp
         gs += gp
-    eK, eg = _relK(Ks.cpu().numpy(), s["Kref"]), _rel(gs.cpu().numpy(), s["gref"])
-    es = _rel(gs.cpu().numpy(), s["g"].double().cpu().numpy())
+    eK, eg = rel_entry(Ks.cpu().numpy(), s["Kref"], 1e-6), rel_max(gs.cpu().numpy(), s["gref"])
+    es = rel_max(gs.cpu().numpy(), s["g"].double().cpu().numpy())
     print(f"sum of the shares: K {eK:.2e} gradient {eg:.2e} against the oracle, gradient {es:.2e} against the full launch")
     assert torch.equal(Ks, s["K"])
     assert eK < TOL and eg < TOL and es < TOL

@@ -1,4 +1,4 @@
-"""Host-side checks behind tests/test_gpu_partition.py; no device needed.  `helpers.gram_geometry` restates how a Gram launch
+"""Host-side checks behind tests/test_gpu_partition.py; no device needed.  `plans.gram_geometry` restates how a Gram launch
 of the fp32-sweep kernels is split into items and workgroups: pinned here to the library's own queries.  Every case of the
 partition file's matrix is in the multi-item regime it claims on 256 compute units.  And, on the fp64 oracle alone, the
 gradient metric of that file (largest error over the launch's largest entry, below 1e-5) would notice a single lost or
@@ -8,27 +8,14 @@ import ctypes
 import numpy as np
 import pytest
 
-from helpers import (gram_geometry, gram_item_ranges, gram_multi_item_regime, gram_ordered_grad_bytes, device_cus,
-                     signed_weights)
+from cabi import lib
 from oracle import c_oracle as C
+from parity import signed_weights, walks
+from plans import (claim_regime, device_cus, gram_geometry, gram_item_ranges, gram_multi_item_regime,
+                   gram_ordered_grad_bytes, PARTITION_CASES, probes, set_band_mode, step_scale)
 from sigsvgd_amd import _lib
-from test_gpu_partition import CASES, _paths, claim_regime, step_scale
 
 MODES = (None, "serial", "parallel")
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
-
-
-def _set_mode(monkeypatch, mode):
-    if mode is None:
-        monkeypatch.delenv("SIGSVGD_BAND_MODE", raising=False)
-    else:
-        monkeypatch.setenv("SIGSVGD_BAND_MODE", mode)
 
 
 def test_rows_per_tile_match_sym_tile_rows():
@@ -44,13 +31,13 @@ def test_geometry_matches_workspace_query(monkeypatch):
     workgroup-tile meetings][the family's scratch]: the bytes fix rows_per_tile and grid, and the family through its scratch.
     Shapes of every family, both band schedules and the launcher's own rule, from one item to far past the resident grid."""
     cus = device_cus()
-    shapes = [(c.T, c.d, c.n) for c in CASES] + [(3, 2, 0), (32, 8, 0), (33, 8, 0), (64, 4, 0), (64, 5, 0), (64, 9, 0), (65, 2, 0),
-                                                  (112, 15, 0), (113, 14, 0), (128, 16, 0), (3, 7, 6), (33, 5, 2), (9, 3, 3),
-                                                  (17, 14, 2), (33, 3, 3), (3, 2, 7), (5, 16, 6), (27, 2, 3), (17, 9, 4)]
+    shapes = [(c.T, c.d, c.n) for c in PARTITION_CASES]
+    shapes += [(3, 2, 0), (32, 8, 0), (33, 8, 0), (64, 4, 0), (64, 5, 0), (64, 9, 0), (65, 2, 0), (112, 15, 0), (113, 14, 0),
+               (128, 16, 0), (3, 7, 6), (33, 5, 2), (9, 3, 3), (17, 14, 2), (33, 3, 3), (3, 2, 7), (5, 16, 6), (27, 2, 3), (17, 9, 4)]
     sizes = [(1, 2), (2, 1), (5, 9), (9, 113), (33, 77), (43, 97), (67, 263), (300, 8), (8, 300), (301, 517)]
     families = set()
     for mode in MODES:
-        _set_mode(monkeypatch, mode)
+        set_band_mode(monkeypatch, mode)
         for (T, d, n) in shapes:
             for (A, B) in sizes:
                 g = gram_geometry(A, B, T, d, n, True, False, cus)
@@ -90,8 +77,8 @@ def test_partition_cases_are_in_their_regime(monkeypatch):
     regime conditions of the gradient and of the forward-only launch, ordered and Y is X (the GPU tests assert the same with
     the device's CU count)"""
     seen = set()
-    for c in CASES:
-        _set_mode(monkeypatch, c.mode)
+    for c in PARTITION_CASES:
+        set_band_mode(monkeypatch, c.mode)
         for (A, B, sym) in [(*c.AB, False), (c.N, c.N, True)]:
             g = claim_regime(A, B, c.T, c.d, c.n, True, sym, c.regime, cus=256)
             assert (g["family"], g["rows_per_tile"]) == (c.family, c.rows), (c, g)
@@ -105,7 +92,7 @@ def test_partition_cases_are_in_their_regime(monkeypatch):
             for (A, B, sym) in [(*c.ABf, False), (c.Nf, c.Nf, True)]:
                 gf = claim_regime(A, B, c.T, c.d, c.n, False, sym, c.regime, cus=256)
                 seen.add((gf["family"] + " forward", gf["rows_per_tile"], gf["resident"]))
-    _set_mode(monkeypatch, None)
+    set_band_mode(monkeypatch, None)
     claim_regime(67, 263, 16, 3, 0, True, False, "full", cus=256)
     claim_regime(257, 257, 12, 2, 0, True, True, "full", cus=256)
     assert {("fast", 8, 768), ("fast", 8, 256), ("fast", 4, 256), ("fast forward", 4, 768), ("fast forward", 4, 512),
@@ -124,23 +111,6 @@ def test_partition_cases_are_in_their_regime(monkeypatch):
     assert past_grid > 100
 
 
-def probes(A, B, geom, sym, seed):
-    """about 32 pairs (i, j): the first and the last item of twelve workgroup ranges spread over the launch -- a row of the
-    item's tile that owns the pair -- and eight random ones"""
-    bounds, starts = gram_item_ranges(A, B, geom, sym)
-    rows, rng = geom["rows_per_tile"], np.random.default_rng(seed)
-    items = [it for w in np.linspace(0, geom["grid"] - 1, 12).astype(int) for it in (bounds[w], bounds[w + 1] - 1)]
-    items += list(rng.integers(0, geom["items"], 8))
-    out = []
-    for k, it in enumerate(items):
-        t = int(np.searchsorted(starts, it, side="right")) - 1
-        j = int(it - starts[t]) + (t * rows if sym else 0)
-        i = min(t * rows + k % rows, A - 1, j if sym else A - 1)
-        assert t * rows <= i < A and 0 <= j < B and (not sym or i <= j)
-        out.append((i, j))
-    return out
-
-
 # one small case per launch form of the partition file: (form, T, d, size): the ordered launch and the three weightings
 # of the Y-is-X launch
 FORMS = [("ordered", 16, 3, (67, 263)), ("signed", 16, 3, 155), ("signed-sym", 64, 7, 93), ("ones", 33, 9, 67)]
@@ -155,8 +125,8 @@ def test_gradient_metric_notices_one_pair(form, T, d, size):
     largest entry is at least 1e-2 of it.  Seeds, shapes and weights are those of tests/test_gpu_partition.py."""
     sym = form != "ordered"
     (A, B), h = ((size, size), 1.1) if sym else (size, 0.9)
-    X = _paths(A, T, d, 21 if sym else 11, step_scale(0))
-    Y = X if sym else _paths(B, T, d, 12, step_scale(0))
+    X = walks(A, T, d, 21 if sym else 11, step_scale(0))
+    Y = X if sym else walks(B, T, d, 12, step_scale(0))
     w = np.ones((A, B)) if form == "ones" else signed_weights(A, B, 23 if sym else 13)
 
     def effective(w):

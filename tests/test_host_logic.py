@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from helpers import golden, patch_ops
+from parity import path_cost_fn
 
 ATOL = 2e-6
 
@@ -168,11 +169,6 @@ def test_trajectory_svgd_mask_fixture(monkeypatch):
 
 
 # ---- signature-kernel wiring (C1-sized fixtures captured through the reference's own classes) -----------
-def _cost_fn(x, w):
-    c = w * (x**2).sum((1, 2)) + ((x[:, 1:] - x[:, :-1]) ** 2).sum((1, 2))
-    return c, {"aux": c.detach() * 2}
-
-
 def test_signature_kernel_call_and_autograd_fixture(monkeypatch):
     from sigsvgd_amd.kernels import SignatureKernel
 
@@ -206,7 +202,7 @@ def test_score_estimator_fixture(monkeypatch):
     patch_ops(monkeypatch)
     G = golden()
     sk = SignatureKernel(bandwidth_fn=lambda _: 1.5, depth=2)
-    est = ScoreEstimator(sk, _cost_fn, {"w": 0.5}, scheduler=SquareRootScheduler(1.0))
+    est = ScoreEstimator(sk, path_cost_fn, {"w": 0.5}, scheduler=SquareRootScheduler(1.0))
     assert est.score == est._pathsig_score
     x = torch.as_tensor(G["c1_X"]).clone().requires_grad_(True)
     glp, sd = est.score(x)
@@ -225,7 +221,7 @@ def test_svgd_optimize_with_signature_kernel_fixture(monkeypatch, mode):
     patch_ops(monkeypatch)
     G = golden()
     sk = SignatureKernel(bandwidth_fn=lambda _: 1.5, depth=2)
-    est = ScoreEstimator(sk, _cost_fn, {"w": 0.5}, scheduler=None)
+    est = ScoreEstimator(sk, path_cost_fn, {"w": 0.5}, scheduler=None)
     s = SVGD(sk, optimizer_class=torch.optim.Adam, lr=0.05) if mode == "adam" else SVGD(sk, optimizer_class=None, lr=0.01)
     Xp = torch.as_tensor(G["c1_X"]).clone()
     data, _ = s.optimize(Xp, est.score, n_steps=3)

@@ -3,27 +3,18 @@
 its slab bound, and the identity the GPU tests take their second-slot reference from.  No device needed (every call below
 returns before any device work)."""
 import ctypes
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from cabi import assert_exported, BADARG, FAKE, lib, UNSUPPORTED
+from plans import device_cus, long2_plan, long_plan, pair_plan
 from sigsvgd_amd import _lib, ops
 
-BADARG, UNSUPPORTED = -1, -2
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NAMES = ("sigsvgd_gram_long2_workspace_bytes", "sigsvgd_gram_long_fwd_bwd2")
 # the launch modes: (want_gradX, want_gradY, flags)
 MODES = {"two-slot": (1, 1, 0), "x-only": (1, 0, 0), "y-only": (0, 1, 0), "yx": (1, 0, _lib.FLAG_Y_IS_X),
          "yx-forward": (0, 0, _lib.FLAG_Y_IS_X)}
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def long2_ws(A, B, TX, TY, d, n, kind=_lib.STATIC_RBF, want_x=1, want_y=1, flags=0, out=True):
@@ -33,52 +24,8 @@ def long2_ws(A, B, TX, TY, d, n, kind=_lib.STATIC_RBF, want_x=1, want_y=1, flags
     return rc, b.value
 
 
-def long2_plan(A, B, M, N, d, n, want_x=True, want_y=True, yx=False, cus=256):
-    """The launch plan of csrc/gram_long.hip's two-sided mode (`long2_make_plan`) on top of helpers.ring_plan, as a dict (IC,
-    JC, nti, ntj, items, grid, slab_bytes, bytes), or None where the library refuses the launch (E_UNSUPPORTED).  Tiles of
-    IC rows x JC columns, the largest powers of two <= 32 that still give every resident wave an item (the wider side is
-    halved first); yx: square tiles of the upper triangle, and a row keeps nti + 1 slabs."""
-    from helpers import ring_plan
-
-    want_grad = want_x or want_y
-    pl = ring_plan(M, N, n, want_grad, d, cus)
-    if pl is None:
-        return None
-    tiles = lambda rows, c: -(-rows // c)
-    IC = JC = 32
-    if yx:
-        tri = lambda c: tiles(A, c) * (tiles(A, c) + 1) // 2
-        while IC > 1 and tri(IC) < pl["resident"]:
-            IC >>= 1
-        JC, items = IC, tri(IC)
-    else:
-        while (IC > 1 or JC > 1) and tiles(A, IC) * tiles(B, JC) < pl["resident"]:
-            if JC >= IC:
-                JC >>= 1
-            else:
-                IC >>= 1
-        items = tiles(A, IC) * tiles(B, JC)
-    nti, ntj = tiles(A, IC), tiles(B, JC)
-    grid = min(pl["resident"], items)
-    if want_grad and pl["per_wave"] * grid > (1 << 30):
-        grid = max(1, (1 << 30) // pl["per_wave"])
-    wsk_bytes = (pl["per_wave"] * grid + 255) & ~255
-    if yx:
-        slab_bytes = A * (nti + 1) * M * d * 8 if want_grad else 0
-    else:
-        slab_bytes = (A * ntj * M * d * 8 if want_x else 0) + (B * nti * N * d * 8 if want_y else 0)
-    total = wsk_bytes + slab_bytes
-    return dict(pl, IC=IC, JC=JC, nti=nti, ntj=ntj, items=items, grid=grid, slab_bytes=slab_bytes,
-                bytes=total + 256 if total else 0)
-
-
 def test_long2_symbols_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
-    for name in NAMES:
-        assert name in exported and name in _lib.EXPORTS
-        getattr(lib(), name)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+    assert_exported(NAMES, abi=10)
 
 
 def _launch(a, gX=FAKE, gY=FAKE, X=FAKE, K=FAKE, dtype=_lib.F32, inv_h=1.0):
@@ -135,10 +82,8 @@ def test_long2_refusals_are_the_long_routes():
 
 
 def test_long2_plan_mirror_matches_workspace_query():
-    """`long2_plan` above mirrors long2_make_plan over the shape list of test_long_cabi.py's plan test and every launch mode,
+    """`plans.long2_plan` mirrors long2_make_plan over the shape list of test_long_cabi.py's plan test and every launch mode,
     and refuses exactly where the query does.  (Y-is-X modes need a square launch: there B and TY follow A and TX.)"""
-    from helpers import device_cus
-
     cus = device_cus()
     shapes = [(1, 1, 2, 2), (3, 4, 300, 300), (1, 2, 129, 129), (2, 3, 129, 130), (2, 2, 257, 258), (2, 2, 513, 514),
               (2, 2, 9, 9), (2, 3, 5, 9), (1, 2, 9, 3), (3, 2, 150, 400), (2, 3, 66, 258), (1, 1, 300, 2), (1, 1, 2, 300),
@@ -174,8 +119,6 @@ def test_long2_forward_needs_no_workspace():
 def test_long2_slab_bound():
     """Slab memory does not grow like A * B * T * d: at A = B = 256, T = 300, d = 4 it is within the bound of the tiling,
     (A ceil(B / JC) TX + B ceil(A / IC) TY) d 8, and below a quarter of A * B * TX * d * 8, in every mode."""
-    from helpers import device_cus
-
     A = B = 256
     TX = TY = 300
     d = 4
@@ -190,8 +133,6 @@ def test_long2_slab_bound():
 
 
 def test_existing_long_and_pair_queries_unchanged():
-    from helpers import device_cus, long_plan, pair_plan
-
     cus = device_cus()
     for (A, B, M, N, d, n) in [(3, 4, 300, 300, 3, 0), (2, 2, 200, 200, 4, 2), (40, 60, 40, 40, 2, 0), (64, 64, 1025, 1025, 4, 0),
                                (3, 2, 150, 400, 2, 1)]:

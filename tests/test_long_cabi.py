@@ -1,23 +1,14 @@
 """Host-side checks of the long-path Gram entry points (`sigsvgd_gram_long_*`, include/sigsvgd_hip.h) and of the routing
 predicate `ops.gram_takes`; no device needed (every call below returns before any device work)."""
 import ctypes
-import re
-import subprocess
 
 import pytest
 
+from cabi import assert_exported, BADARG, FAKE, lib, UNSUPPORTED
+from plans import device_cus, long_plan
 from sigsvgd_amd import _lib, ops
 
-BADARG, UNSUPPORTED = -1, -2
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NAMES = ("sigsvgd_gram_long_workspace_bytes", "sigsvgd_gram_long_fwd", "sigsvgd_gram_long_fwd_bwd")
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def long_ws(A, B, TX, TY, d, n, kind=_lib.STATIC_RBF, want_grad=1, flags=0, out=True):
@@ -32,12 +23,7 @@ def gram_ws_rc(A, B, T, d, n, want_grad=1):
 
 
 def test_long_symbols_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
-    for name in NAMES:
-        assert name in exported and name in _lib.EXPORTS
-        getattr(lib(), name)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+    assert_exported(NAMES, abi=10)
 
 
 @pytest.mark.parametrize("A,B,TX,TY,d,n,old", [(4, 4, 400, 400, 3, 0, True), (2, 2, 200, 200, 4, 2, True),
@@ -117,10 +103,8 @@ def test_routing_predicate():
 
 
 def test_plan_helper_matches_workspace_query():
-    """tests/helpers.long_plan mirrors long_make_plan: its bytes are the library's over shapes that reach every branch of
+    """tests/plans.long_plan mirrors long_make_plan: its bytes are the library's over shapes that reach every branch of
     the plan (ring wrap, nrow = 1, JC from 32 down to 1, the 1 GiB scratch cap, the LDS limit)."""
-    from helpers import device_cus, long_plan
-
     cus = device_cus()
     shapes = [(1, 1, 2, 2), (3, 4, 300, 300), (1, 2, 129, 129), (2, 3, 129, 130), (2, 2, 257, 258), (2, 2, 513, 514),
               (2, 2, 9, 9), (2, 3, 5, 9), (1, 2, 9, 3), (3, 2, 150, 400), (2, 3, 66, 258), (1, 1, 300, 2), (1, 1, 2, 300),
@@ -143,8 +127,6 @@ def test_plan_helper_matches_workspace_query():
 def test_channel_limit():
     """Up to 16 channels the ring fill keeps a point in registers, past 16 it reads global memory; the LDS holds the band's
     points of X, so at T = 300 and order 0 the limit is 183 channels."""
-    from helpers import long_plan
-
     assert long_ws(2, 2, 300, 300, 183, 0)[0] == 0
     assert long_ws(2, 2, 300, 300, 183, 0, want_grad=0)[0] == 0
     for want_grad in (0, 1):
@@ -160,8 +142,6 @@ def test_channel_limit():
 @pytest.mark.parametrize("n", [7, 8, 9, 10])
 def test_high_orders(n):
     """Orders 7 to 10 (nrow = 1: a band of 64 rows is part of one coarse row): taken up to P = Q = 8192, refused past it."""
-    from helpers import long_plan
-
     edge = 8192 // (1 << n) + 1  # points giving 8192 cells
     for (TX, TY) in [(edge, edge), (edge, 3), (3, edge), (2, 2)]:
         for want_grad in (0, 1):

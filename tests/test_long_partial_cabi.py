@@ -1,117 +1,22 @@
 """Host-side checks of the long route's partial solve (`sigsvgd_gram_long_partial_plan`,
 `sigsvgd_gram_long_partial_workspace_bytes`, `sigsvgd_gram_long_sym_partial`, include/sigsvgd_hip.h):
-exports, argument checks, a Python mirror of the item rule pinned to the two queries, and the four conditions the plan has
-to meet (partition, balance, schedule, memory).  No device needed: every call below returns before any device work."""
+exports, argument checks, the Python mirror of the item rule (tests/plans.py) pinned to the two queries, and the four
+conditions the plan has to meet (partition, balance, schedule, memory).  No device needed: every call below returns before
+any device work."""
 import ctypes
 import re
-import subprocess
-from functools import lru_cache
 
 import pytest
 
+from cabi import assert_exported, BADARG, FAKE, lib, UNSUPPORTED, WORKSPACE
+from plans import device_cus, item_pairs, item_size, part_items, part_pick, part_plan, part_share, ring_plan, tiles
 from sigsvgd_amd import _lib, ops
 
-BADARG, UNSUPPORTED, WORKSPACE = -1, -2, -3
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its checks first
 NAMES = ("sigsvgd_gram_long_partial_plan", "sigsvgd_gram_long_partial_workspace_bytes", "sigsvgd_gram_long_sym_partial")
 GRID_N, GRID_G, GRID_RES = (64, 128, 200, 256, 512, 1024), (2, 4, 8), (256, 512, 1024, 2048)
 
 
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
-
-
-# ---- the mirror of csrc/gram_long.hip's partial plan -------------------------------------------------------------------
-def tiles(n, c):
-    return -(-n // c)
-
-
-def part_items(N, R, JC, owned):
-    """The items (kq, c) of a launch that owns the row tiles `owned` (R rows each), in the order the kernel takes them
-    (`part_decode`): the chunks strictly between a tile's first and last, then every tile's first chunk, then the last."""
-    nc = [tiles(N - t * R, JC) for t in owned]
-    out = [(k, c) for k in range(len(owned)) for c in range(1, nc[k] - 1)]
-    out += [(k, 0) for k in range(len(owned))]
-    out += [(k, nc[k] - 1) for k in range(len(owned)) if nc[k] >= 2]
-    return out
-
-
-def item_pairs(N, R, JC, t, c):
-    """The pairs of item (row tile t, chunk c) in the order the kernel walks them: row by row, i <= j only."""
-    i0, i1 = t * R, min(N, (t + 1) * R)
-    j0 = i0 + c * JC
-    j1 = min(N, j0 + JC)
-    return [(i, j) for i in range(i0, i1) for j in range(max(j0, i), j1)]
-
-
-def item_size(N, R, JC, t, c):
-    i0, i1 = t * R, min(N, (t + 1) * R)
-    j0 = i0 + c * JC
-    j1 = min(N, j0 + JC)
-    whole = max(0, min(i1, j0 + 1) - i0)  # rows at or above the chunk's first column: j1 - j0 pairs each
-    lo, hi = max(i0, j0 + 1), min(i1, j1) - 1  # rows cut by the diagonal: j1 - i pairs
-    cut = (hi - lo + 1) * j1 - (lo + hi) * (hi - lo + 1) // 2 if hi >= lo else 0
-    return whole * (j1 - j0) + cut
-
-
-def part_share(N, R, JC, off, stride, fold, res):
-    """One rank's share: dict(pairs, makespan, slabs, items, owned); slabs in units of T * d doubles (a row-side slab per
-    (row of an owned tile, chunk), a column-side slab per (owned tile, row from the tile's first on)); makespan = the most
-    pairs one wavefront walks when item k goes to wave k % grid, grid = min(resident waves, items)."""
-    owned = ops.owned_tiles(tiles(N, R), off, stride, fold)
-    sizes = [item_size(N, R, JC, owned[k], c) for (k, c) in part_items(N, R, JC, owned)]
-    slabs = sum((min(N, (t + 1) * R) - t * R) * tiles(N - t * R, JC) + (N - t * R) for t in owned)
-    grid = max(1, min(res, len(sizes)))
-    load = [0] * grid
-    for k, p in enumerate(sizes):
-        load[k % grid] += p
-    return dict(pairs=sum(sizes), makespan=max(load), slabs=slabs, items=len(sizes), owned=owned)
-
-
-@lru_cache(maxsize=None)
-def part_pick(N, stride, res):
-    """(R, JC) of `part_pick`: the largest R * JC (ties: the larger R) whose every rank, folded, meets the schedule
-    (eff >= 0.9), memory and balance (fullest <= 1.05 x mean) conditions; else, memory holding, best balance then schedule."""
-    cands = sorted(((R, JC) for R in (32, 16, 8, 4, 2, 1) for JC in range(64, 0, -1)), key=lambda x: -x[0] * x[1])
-    total = N * (N + 1) // 2
-    best, best_key = (1, 1), None
-    for (R, JC) in cands:
-        if R > 1 and tiles(N, R) < 2 * stride:
-            continue
-        shares = [part_share(N, R, JC, off, stride, True, res) for off in range(stride)]
-        if not all(s["slabs"] <= (N * N // 4 if s["pairs"] > 16 * res else 2 * s["pairs"] + N) for s in shares):
-            continue
-        eff = min([1.0] + [-(-s["pairs"] // res) / s["makespan"] for s in shares if s["pairs"]])
-        bal = max(s["pairs"] for s in shares) * stride <= 1.05 * total
-        if eff >= 0.9 and bal:
-            return R, JC
-        if best_key is None or (bal, eff) > best_key:
-            best, best_key = (R, JC), (bal, eff)
-    return best
-
-
-def part_plan(N, T, d, n, off, stride, fold, cus=256):
-    """The plan of rank `off` of `stride` (`part_make_plan`) as a dict (R, JC, items, grid, pairs, makespan, eff, slabs,
-    bytes), or None where the library refuses the launch."""
-    from helpers import ring_plan
-
-    pl = ring_plan(T, T, n, True, d, cus)
-    if pl is None:
-        return None
-    res = pl["resident"]
-    R, JC = part_pick(N, stride, res)
-    sh = part_share(N, R, JC, off, stride, fold, res)
-    grid = min(res, sh["items"])
-    if pl["per_wave"] * grid > (1 << 30):
-        grid = max(1, (1 << 30) // pl["per_wave"])
-    total = ((pl["per_wave"] * grid + 255) & ~255) + sh["slabs"] * T * d * 8
-    eff = -(-sh["pairs"] // res) / sh["makespan"] if sh["pairs"] else 1.0
-    return dict(pl, R=R, JC=JC, grid=grid, eff=eff, bytes=total + 256 if total else 0, **sh)
-
-
+# ---- the library's own answers (the Python mirror of the plan is plans.part_plan) ---------------------------------------
 def q_plan(N, T, d, n=0, kind=_lib.STATIC_RBF, flags=0, stride=1, out=True):
     R, JC = ctypes.c_int(-7), ctypes.c_int(-7)
     rc = lib().sigsvgd_gram_long_partial_plan(N, T, d, n, kind, flags, stride, ctypes.byref(R) if out else None,
@@ -134,14 +39,10 @@ def _launch(a, X=FAKE, K=FAKE, g=FAKE, dtype=_lib.F32, inv_h=1.0, ws_bytes=1 << 
 def test_symbols_exported_and_declared():
     import os
 
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
+    assert_exported(NAMES, abi=10)
     header = open(os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "..", "include", "sigsvgd_hip.h")).read()
     for name in NAMES:
-        assert name in exported and name in _lib.EXPORTS
         assert re.search(r"\bint %s\(" % name, header)
-        getattr(lib(), name)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
 
 
 @pytest.mark.parametrize("case", ["N<1", "T<2", "d<1", "kind", "order", "force_generic", "unknown_flag", "stride<1", "off<0",
@@ -210,10 +111,8 @@ def test_a_rank_without_tiles_is_a_valid_launch_without_workspace():
 
 # ---- the mirror is the library's rule -------------------------------------------------------------------------------------
 def test_plan_mirror_matches_the_queries():
-    """`part_plan` above against sigsvgd_gram_long_partial_plan and ..._workspace_bytes: shapes with 1, 2, 4 and 8 resident
+    """`plans.part_plan` against sigsvgd_gram_long_partial_plan and ..._workspace_bytes: shapes with 1, 2, 4 and 8 resident
     waves per CU, orders 0 and 2, d = 3 and 20, strides 1 .. 8 and more ranks than tiles, folded and cyclic, and refusals."""
-    from helpers import device_cus
-
     cus = device_cus()
     shapes = [(20, 300, 0), (33, 200, 2), (9, 257, 0), (5, 300, 0), (70, 140, 0), (64, 300, 0), (128, 300, 0), (256, 130, 0),
               (300, 16, 0), (200, 40, 2), (256, 1025, 0), (131, 2, 0), (1, 300, 0), (2, 9, 2), (512, 64, 0), (16, 2049, 0),
@@ -297,8 +196,6 @@ def test_conditions_balance_schedule_memory():
 def test_the_grid_of_the_conditions_is_the_librarys_plan():
     """The (R, JC) the conditions above were checked on are the library's: its plan query at every N and rank count of the
     grid, on shapes that leave a CU 1, 2, 4 and 8 resident waves (256 CUs: the grid's 256 .. 2048)."""
-    from helpers import device_cus, ring_plan
-
     cus = device_cus()
     for (T, d, per_cu) in [(2049, 2, 1), (300, 4, 2), (60, 3, 4), (30, 3, 8)]:
         res = ring_plan(T, T, 0, True, d, cus)["resident"]

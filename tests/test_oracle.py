@@ -10,7 +10,7 @@ from oracle import c_oracle as C
 from oracle import sigkernel_oracle as O
 
 
-def _paths(A, T, d, seed, scale=0.3):
+def _walks64(A, T, d, seed, scale=0.3):
     rng = np.random.default_rng(seed)
     return np.cumsum(scale * rng.standard_normal((A, T, d)), axis=1)
 
@@ -47,7 +47,7 @@ def _signature(path, depth):
 
 
 def test_truncated_signature_limit():
-    x, y = _paths(1, 5, 2, 1, 0.25)[0], _paths(1, 5, 2, 2, 0.25)[0]
+    x, y = _walks64(1, 5, 2, 1, 0.25)[0], _walks64(1, 5, 2, 2, 0.25)[0]
     depth = 8
     sx, sy = _signature(x, depth), _signature(y, depth)
     exact = 1.0 + sum(float((a * b).sum()) for a, b in zip(sx, sy))
@@ -58,8 +58,8 @@ def test_truncated_signature_limit():
 # ---- (3)(4) invariances -------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", [O.RBF, O.LINEAR])
 def test_constant_path_symmetry_boundary(kind):
-    X = _paths(4, 6, 3, 3)
-    const = np.repeat(_paths(1, 1, 3, 4), 6, axis=1)
+    X = _walks64(4, 6, 3, 3)
+    const = np.repeat(_walks64(1, 1, 3, 4), 6, axis=1)
     assert np.allclose(O.gram(X, const, kind, 1.3, 2), 1.0, atol=1e-14)
     K = O.gram(X, X, kind, 1.3, 1)
     assert np.allclose(K, K.T, rtol=1e-13)
@@ -68,7 +68,7 @@ def test_constant_path_symmetry_boundary(kind):
 
 
 def test_repeated_point_invariance():
-    X, Y = _paths(2, 6, 2, 5), _paths(3, 6, 2, 6)
+    X, Y = _walks64(2, 6, 2, 5), _walks64(3, 6, 2, 6)
     Xr = np.concatenate([X[:, :3], X[:, 2:3], X[:, 3:]], axis=1)  # repeat point 2: zero increments
     Yr = np.concatenate([Y[:, :3], Y[:, 2:3], Y[:, 3:]], axis=1)
     assert np.allclose(O.gram(X, Y, O.RBF, 0.8, 0), O.gram(Xr, Yr, O.RBF, 0.8, 0), rtol=1e-13)
@@ -78,7 +78,7 @@ def test_repeated_point_invariance():
 def test_naive_stencil_gg_is_exact_adjoint():
     """with the first-order stencil GG == dK/dg, so the reference-style gradient equals finite
     differences of the forward to FD accuracy"""
-    X, Y = _paths(3, 5, 2, 7), _paths(2, 5, 2, 8)
+    X, Y = _walks64(3, 5, 2, 7), _walks64(2, 5, 2, 8)
     _, g = O.gram_backward(X, Y, None, O.RBF, 2.0, 1, naive=True)
     num = np.zeros_like(X)
     eps = 1e-6
@@ -94,7 +94,7 @@ def test_naive_stencil_gg_is_exact_adjoint():
 def test_closed_form_backward_equals_recalled_fd_assembly(n):
     """the closed-form chain rule reproduces upstream's finite-difference Diff_1/Diff_2/grad_points
     assembly (to FD noise ~1e-7), also with a non-trivial grad_output"""
-    X, Y = _paths(4, 7, 3, 9), _paths(5, 7, 3, 10)
+    X, Y = _walks64(4, 7, 3, 9), _walks64(5, 7, 3, 10)
     go = np.random.default_rng(0).standard_normal((4, 5))
     K1, g1 = O.gram_backward(X, Y, go, O.RBF, 2.0, n)
     K2, g2 = O.gram_backward_fd_literal(X, Y, go, 2.0, n)
@@ -104,7 +104,7 @@ def test_closed_form_backward_equals_recalled_fd_assembly(n):
 
 def test_default_stencil_gradient_converges_first_order():
     """GG is NOT the adjoint of the second-order stencil; the mismatch shrinks ~1/r"""
-    X, Y = _paths(2, 5, 2, 11), _paths(2, 5, 2, 12)
+    X, Y = _walks64(2, 5, 2, 11), _walks64(2, 5, 2, 12)
     errs = []
     for n in (0, 2, 4):
         _, g = O.gram_backward(X, Y, None, O.RBF, 2.0, n)
@@ -120,7 +120,7 @@ def test_default_stencil_gradient_converges_first_order():
 
 
 def test_sym_flag_weights():
-    X = _paths(4, 5, 2, 13)
+    X = _walks64(4, 5, 2, 13)
     go = np.random.default_rng(1).standard_normal((4, 4))
     _, gs = O.gram_backward(X, X, go, O.RBF, 1.0, 1, sym=True)
     _, g2 = O.gram_backward(X, X, go + go.T, O.RBF, 1.0, 1)
@@ -128,7 +128,7 @@ def test_sym_flag_weights():
 
 
 def test_sweep_vectorised_equals_scalar_loop():
-    g = O.refine(O.increments(O.static_gram(_paths(1, 6, 2, 14), _paths(1, 6, 2, 15), O.RBF, 1.0)), 2)[0, 0]
+    g = O.refine(O.increments(O.static_gram(_walks64(1, 6, 2, 14), _walks64(1, 6, 2, 15), O.RBF, 1.0)), 2)[0, 0]
     for naive in (False, True):
         assert np.array_equal(O.pde_sweep(g, naive), O.pde_sweep_scalar(g, naive))
 
@@ -174,8 +174,8 @@ def test_reference_wiring_fixture_is_consistent_with_oracle():
 # ---- C restatement ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind,n,naive", [(0, 0, False), (0, 2, False), (0, 1, True), (1, 1, False)])
 def test_c_oracle_matches_numpy_oracle(kind, n, naive):
-    X = _paths(6, 9, 3, 20).astype(np.float32)
-    Y = _paths(5, 9, 3, 21).astype(np.float32)
+    X = _walks64(6, 9, 3, 20).astype(np.float32)
+    Y = _walks64(5, 9, 3, 21).astype(np.float32)
     go = np.random.default_rng(2).standard_normal((6, 5))
     K1, g1 = O.gram_backward(X, Y, go, kind, 1.7, n, naive)
     K2, g2 = C.gram_fwd_bwd(X, Y, 1.7, n, naive, kind, go)

@@ -2,27 +2,17 @@
 `ops.pair_takes` and of the routing of `SigKernel.compute_kernel`; no device needed (every library call below returns before
 any device work, and the routing tests run on oracle-backed doubles of the ops)."""
 import ctypes
-import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import pair_plan
+from cabi import assert_exported, BADARG, FAKE, lib, UNSUPPORTED
 from oracle import sigkernel_oracle as O
+from plans import device_cus, pair_plan
 from sigsvgd_amd import _lib, ops
 
-BADARG, UNSUPPORTED = -1, -2
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NAMES = ("sigsvgd_pair_workspace_bytes", "sigsvgd_pair_fwd", "sigsvgd_pair_fwd_bwd")
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def pair_ws(A, TX, TY, d, n, kind=_lib.STATIC_RBF, want_grad=1, flags=0, out=True):
@@ -32,12 +22,7 @@ def pair_ws(A, TX, TY, d, n, kind=_lib.STATIC_RBF, want_grad=1, flags=0, out=Tru
 
 
 def test_pair_symbols_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
-    for name in NAMES:
-        assert name in exported and name in _lib.EXPORTS
-        getattr(lib(), name)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+    assert_exported(NAMES, abi=10)
 
 
 @pytest.mark.parametrize("case", ["A<1", "TX<2", "TY<2", "d<1", "kind", "order", "order<0", "sym", "y_is_x", "generic",
@@ -107,8 +92,6 @@ def test_pair_channel_limit():
 def test_pair_plan_matches_workspace_query():
     """pair_plan mirrors pair_make_plan: its bytes are the library's over shapes that reach every branch of the plan (ring
     wrap, nrow = 1, more pairs than resident waves, the 1 GiB scratch cap, the LDS limit), with TX != TY."""
-    from helpers import device_cus
-
     cus = device_cus()
     shapes = [(1, 2, 2), (3, 300, 200), (2, 129, 129), (2, 129, 130), (5, 257, 258), (2, 9, 9), (3, 5, 9), (1, 9, 3),
               (7, 150, 400), (1, 300, 2), (1, 2, 300), (64, 40, 60), (1000, 64, 64), (5000, 20, 20), (100000, 10, 10),

@@ -1,24 +1,13 @@
 """Host-side checks of the static-grid PDE entry points (`sigsvgd_pde_*`, include/sigsvgd_hip.h) and of the user
 static-kernel route of sigsvgd_amd.sigkernel; no device needed (every call below returns before any device work)."""
 import ctypes
-import re
-import subprocess
 
 import pytest
 import torch
 
+from cabi import assert_exported, BADARG, FAKE, lib, UNSUPPORTED
+from plans import device_cus, pde_plan
 from sigsvgd_amd import _lib
-
-BADARG, UNSUPPORTED = -1, -2
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every call here fails its argument checks first
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
-
 
 def ws_bytes(npairs, M, N, n, want_grad, flags=0):
     b = ctypes.c_size_t(0)
@@ -27,11 +16,7 @@ def ws_bytes(npairs, M, N, n, want_grad, flags=0):
 
 
 def test_pde_symbols_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
-    for name in ("sigsvgd_pde_workspace_bytes", "sigsvgd_pde_fwd", "sigsvgd_pde_fwd_bwd"):
-        assert name in exported and name in _lib.EXPORTS
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+    assert_exported(("sigsvgd_pde_workspace_bytes", "sigsvgd_pde_fwd", "sigsvgd_pde_fwd_bwd"), abi=10)
 
 
 @pytest.mark.parametrize("case", ["null_G", "null_K", "null_dG", "M<2", "N<2", "npairs<1", "dtype", "flag", "order<0",
@@ -110,10 +95,8 @@ def test_user_static_kernel_routing_on_cpu():
 
 
 def test_plan_helper_matches_workspace_query():
-    """tests/helpers.pde_plan mirrors pde_make_plan: its bytes are the library's (ring wrap, nrow = 1, more pairs than
+    """tests/plans.pde_plan mirrors pde_make_plan: its bytes are the library's (ring wrap, nrow = 1, more pairs than
     resident waves, the 1 GiB scratch cap)."""
-    from helpers import device_cus, pde_plan
-
     cus = device_cus()
     for npairs in (1, 2, 100, 2500, 100_000):
         for (M, N) in [(2, 2), (10, 10), (70, 129), (70, 130), (40, 257), (40, 258), (20, 513), (20, 514), (9, 9), (3, 9),

@@ -10,13 +10,13 @@ import radial_reference as RR
 from oracle import sigkernel_oracle as O
 
 
-def _paths(A, T, d, seed):
+def _synthetic(A, T, d, seed):
     return O.synthetic_inputs(A, T, d, seed_x=seed)[0].double().numpy()
 
 
 @pytest.mark.parametrize("n,sym", [(0, False), (1, False), (2, True)])
 def test_helper_reproduces_the_oracle_for_rbf(n, sym):
-    X, Y = _paths(3, 9, 3, 0), _paths(3, 9 if sym else 7, 3, 5)
+    X, Y = _synthetic(3, 9, 3, 0), _synthetic(3, 9 if sym else 7, 3, 5)
     w = np.random.default_rng(1).standard_normal((3, 3))
     Kr, gr = O.gram_backward(X, Y, w, O.RBF, 0.7, n, sym=sym)
     K, gX, _ = RR.gram_backward(X, Y, w, RR.RBF, 0.7, n, sym=sym)
@@ -34,7 +34,7 @@ def test_slope_matches_central_differences(kind):
 
 @pytest.mark.parametrize("kind", [RR.IMQ, RR.RQ])
 def test_second_slot_is_the_first_slot_of_the_swapped_call(kind):
-    X, Y = _paths(3, 8, 2, 0), _paths(4, 6, 2, 5)
+    X, Y = _synthetic(3, 8, 2, 0), _synthetic(4, 6, 2, 5)
     w = np.random.default_rng(2).standard_normal((3, 4))
     K, gX, gY = RR.gram_backward(X, Y, w, kind, 1.3, 1)
     Kt, gXt, gYt = RR.gram_backward(Y, X, w.T, kind, 1.3, 1)
@@ -51,7 +51,7 @@ def test_second_slot_is_the_first_slot_of_the_swapped_call(kind):
 
 @pytest.mark.parametrize("kind", [RR.IMQ, RR.RQ])
 def test_pairs_are_the_diagonal(kind):
-    X, Y = _paths(3, 8, 2, 0), _paths(3, 6, 2, 5)
+    X, Y = _synthetic(3, 8, 2, 0), _synthetic(3, 6, 2, 5)
     K, gX, gY = RR.pair_backward(X, Y, np.array([1.0, -2.0, 0.5]), kind, 0.9, 1)
     Kg, gXg, gYg = RR.gram_backward(X, Y, np.diag([1.0, -2.0, 0.5]), kind, 0.9, 1)
     assert np.allclose(K, np.diag(Kg), rtol=0, atol=1e-14)
@@ -63,7 +63,7 @@ def test_torch_restatements_match_the_helper():
     from sigsvgd_amd.kernels import BatchIMQKernel, BatchRationalQuadraticKernel
     from sigsvgd_amd.sigkernel import IMQStaticKernel, RationalQuadraticKernel, _resolve_static
 
-    X, Y = _paths(3, 8, 2, 0), _paths(3, 6, 2, 5)
+    X, Y = _synthetic(3, 8, 2, 0), _synthetic(3, 6, 2, 5)
     Xt, Yt = torch.as_tensor(X), torch.as_tensor(Y)
     for kind, cls, bcls in [(RR.IMQ, IMQStaticKernel, BatchIMQKernel), (RR.RQ, RationalQuadraticKernel, BatchRationalQuadraticKernel)]:
         G = RR.static_gram(X, Y, kind, 0.8)

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from helpers import golden, patch_ops
+from parity import path_cost_fn
 
 REF = "/root/reference"
 pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="reference tree not present")
@@ -36,11 +37,6 @@ def ref_modules(monkeypatch):
         sys.modules.pop(name, None)
 
 
-def _cost_fn(x, w):
-    c = w * (x**2).sum((1, 2)) + ((x[:, 1:] - x[:, :-1]) ** 2).sum((1, 2))
-    return c, {"aux": c.detach() * 2}
-
-
 def test_reference_classes_run_on_our_sigkernel(ref_modules):
     ker, inf = ref_modules
     import sigsvgd_amd.sigkernel as ours
@@ -51,7 +47,7 @@ def test_reference_classes_run_on_our_sigkernel(ref_modules):
     x = torch.as_tensor(G["c1_X"]).clone().requires_grad_(True)
     K = sk(x, x.detach())
     assert np.allclose(K.detach().numpy(), G["c1_K"], rtol=2e-6)
-    est = inf.ScoreEstimator(sk, _cost_fn, {"w": 0.5}, scheduler=None)
+    est = inf.ScoreEstimator(sk, path_cost_fn, {"w": 0.5}, scheduler=None)
     s = inf.SVGD(sk, optimizer_class=torch.optim.Adam, lr=0.05)
     Xp = torch.as_tensor(G["c1_X"]).clone()
     data, _ = s.optimize(Xp, est.score, n_steps=3)

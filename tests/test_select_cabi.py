@@ -5,28 +5,19 @@ import ctypes
 import functools
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+from cabi import assert_exported, BADARG, FAKE, lib, WORKSPACE
 from helpers import golden
 from oracle import sigkernel_oracle as O
 from sigsvgd_amd import _lib, ops
 from sigsvgd_amd.utils.math import bw_from_median, bw_median
 
-BADARG, WORKSPACE = -1, -3
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NAMES = ("sigsvgd_sqdist_select_workspace_bytes", "sigsvgd_sqdist_select")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def select_ws(A, B, TX, TY, d, flags=0, out=True):
@@ -40,14 +31,11 @@ def select(A=3, B=4, TX=5, TY=6, d=2, dtype=_lib.F32, flags=0, rank=0, X=FAKE, Y
 
 
 def test_select_symbols_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
+    assert_exported(NAMES, abi=10)
     header = open(os.path.join(ROOT, "include", "sigsvgd_hip.h")).read()
     declared = re.findall(r"\b(sigsvgd_[a-z_0-9]+)\s*\(", re.sub(r"/\*.*?\*/", "", header, flags=re.S))
     for name in NAMES:
-        assert name in exported and name in _lib.EXPORTS and declared.count(name) == 1
-        getattr(lib(), name)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10
+        assert declared.count(name) == 1
     assert int(re.search(r"#define SIGSVGD_ABI_VERSION (\d+)", header).group(1)) == 10
 
 
@@ -130,7 +118,7 @@ def test_median_route_predicate():
     assert sk._median_route(torch.median, True, 2**32) is False
 
 
-def _paths(A, T, d, seed):
+def _torch_walks(A, T, d, seed):
     g = torch.Generator().manual_seed(seed)
     return (0.3 * torch.randn(A, T, d, generator=g, dtype=torch.float64)).cumsum(1)
 
@@ -143,7 +131,7 @@ def test_constant_bandwidth_never_reaches_the_predicate(monkeypatch):
 
     monkeypatch.setattr(sk, "_median_route", refuse)
     monkeypatch.setattr(ops, "path_sqdist_select", refuse)
-    X = _paths(3, 4, 2, 0)
+    X = _torch_walks(3, 4, 2, 0)
     assert sk.inv_bandwidth_from_fn(lambda _: 0.25, X, X) == 4.0
 
 
@@ -153,7 +141,7 @@ def test_median_bandwidth_takes_the_select_past_the_size_limit(monkeypatch):
     1 / bw_median; other data-dependent functions and CPU tensors keep the torch path and its refusal."""
     import sigsvgd_amd.sigkernel as sk
 
-    X, Y = _paths(5, 6, 3, 1), _paths(4, 7, 3, 2)
+    X, Y = _torch_walks(5, 6, 3, 1), _torch_walks(4, 7, 3, 2)
     sq = O.pairwise_sqdist(X.numpy(), Y.numpy())
     calls = []
 

@@ -5,20 +5,12 @@ import ctypes
 
 import pytest
 
+from cabi import BADARG, FAKE, lib, OK, UNSUPPORTED
 from sigsvgd_amd import _lib, ops
 
-OK, BADARG, UNSUPPORTED = 0, -1, -2
 RBF, LINEAR, IMQ, RQ = _lib.STATIC_RBF, _lib.STATIC_LINEAR, _lib.STATIC_IMQ, _lib.STATIC_RQ
 NAIVE = _lib.FLAG_NAIVE_SOLVER
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NEW = [IMQ, RQ]
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def query(name, *args):

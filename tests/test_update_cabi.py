@@ -1,25 +1,15 @@
 """Host-side checks of `sigsvgd_svgd_update` (include/sigsvgd_hip.h): the symbol, the ABI version it leaves alone, and every
 argument rule, each refused with SIGSVGD_E_BADARG and a message before any device work (no device needed: no call below gets
 past its argument checks), and of the checks `ops.svgd_update` makes before it reaches the library."""
-import ctypes
 import re
-import subprocess
 
 import pytest
 import torch
 
+from cabi import assert_exported, BADARG, FAKE, lib
 from sigsvgd_amd import _lib, ops
 
-BADARG = -1
-FAKE = ctypes.c_void_p(4096)  # never dereferenced: every launch here fails its argument checks first
 NAME = "sigsvgd_svgd_update"
-
-
-def lib():
-    try:
-        return _lib.load()
-    except RuntimeError as e:
-        pytest.fail(f"library not built: {e}")
 
 
 def update(v_in=FAKE, mask=None, N=4, D=6, v_out=FAKE, X_in=FAKE, X_out=FAKE, lr=0.1, adagrad=None, exp_avg=None,
@@ -29,11 +19,7 @@ def update(v_in=FAKE, mask=None, N=4, D=6, v_out=FAKE, X_in=FAKE, X_out=FAKE, lr
 
 
 def test_update_symbol_exported():
-    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    exported = set(re.findall(r"\bT (sigsvgd_\w+)", syms))
-    assert NAME in exported and NAME in _lib.EXPORTS
-    getattr(lib(), NAME)
-    assert lib().sigsvgd_abi_version() == _lib.ABI_VERSION == 10  # an added entry point: the version stays
+    assert_exported((NAME,), abi=10)  # an added entry point: the version stays
     with open(_lib.HEADERS[-1]) as f:
         assert len(re.findall(r"^int " + NAME + r"\(", f.read(), flags=re.M)) == 1
 
