@@ -78,11 +78,13 @@
  *     geometry (no floating-point atomics), so two calls on the same inputs return the same bits.
  *     sigsvgd_vec_kernel_fused is reproducible when it is given its workspace (sigsvgd_vec_fused_workspace_bytes);
  *     without one its column splits meet in fp32 atomics and the last bits of dK_out may differ between calls.
- *   - environment, read per launch, for tests and measurements only (results do not depend on either, bit for bit):
+ *   - environment, read per launch, for tests and measurements only (results do not depend on any of them, bit for bit):
  *     SIGSVGD_BAND_MODE=serial|parallel pins the schedule of the refined-grid launches;
  *     SIGSVGD_SWEEP_WINDOWS=table keeps Gram + gradient launches of 64-point paths on the register-resident kernel
  *     whose PDE sweeps read their lane windows from the constant table (what every other path length runs) instead
- *     of its twin with the windows as immediates, so that the two can be compared on one build.
+ *     of its twin with the windows as immediates, so that the two can be compared on one build;
+ *     SIGSVGD_WAVE_BALANCE=off sends symmetric Gram + gradient launches of 64-point paths in up to 8 channels to the
+ *     fixed-window kernel without the per-half wave priorities instead of the twin that sets them.
  */
 #ifndef SIGSVGD_HIP_H
 #define SIGSVGD_HIP_H

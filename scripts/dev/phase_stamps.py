@@ -3,7 +3,10 @@ gram_fast_kernel spends its cycles.  Builds sigsvgd_amd/_exp/libsigsvgd_stamps.s
 box while it exists; never the product library; delete it after the profiling pass) and
 runs a few launches; the library prints the split to stderr after each launch.  gram_fast_kernel's window between the pair's closing
 barrier and the next pair comes as three parts: "block sum + stage store", "second barrier" and "loop top" (up to the first stamp
-of the next pair: flags, addresses and issue of the next column's loads).
+of the next pair: flags, addresses and issue of the next column's loads).  After that line gram_fast_kernel prints a second one with
+the older half of the workgroups (waves 0 .. NW/2 - 1) and the younger half side by side, "older % | younger %" per phase, each of its
+own half's total: the half that waits longer at "barrier after the pair" is the one that arrives first.
+SIGSVGD_WAVE_BALANCE=off in the environment shows the kernel without the wave-balance schedule.
 usage (on the GPU box): python scripts/dev/phase_stamps.py [N T d [sym|ordered|fwd|fwdsym|dyadic<k>]]      (build only: --build)"""
 import os
 import subprocess

@@ -51,7 +51,38 @@ namespace sigsvgd {
 #define SIG_PRIO(n)                                                          \
     if (!GRAD || !SYM || (RING == 32 && NW == 4)) __builtin_amdgcn_s_setprio(n);
 
-constexpr int SIG_FAST_PHASES = 9; // stamp slots of the diagnostic build (launch_variant names them)
+// Wave balance (the kernel's BAL): the launches that opt out of SIG_PRIO -- symmetric gradient kernels of
+// 8-wave workgroups with fixed windows -- give the two waves of a SIMD one favoured stretch of a pair each instead.  A uniform
+// schedule cannot separate two waves that are in the same phase, and a fixed priority only swaps winner and loser; here the
+// half of the workgroup that goes first (the younger one, waves NW/2 .. NW-1: the loser of the default arbitration; BAL & 4:
+// the older one) holds `s_setprio 1` from the top of the pair to a switch point, the other half from there to the pair's
+// closing barrier.  BAL & 3 is the switch point: 1 the end of phase 1, 2 the end of phase 2, 3 between the two rounds of the
+// reverse sweep.  Two s_setprio per wave and pair, each under a SCALAR branch on the wave index (s_setprio ignores EXEC: under a
+// per-lane condition it would run in every wave).  Priorities change no arithmetic: the results are the BAL = 0 twin's bit for bit.
+template <int BAL>
+__device__ __forceinline__ void bal_top(bool first)
+{
+    if constexpr (BAL != 0) {
+        if (first) __builtin_amdgcn_s_setprio(1);
+    }
+}
+template <int BAL, int AT>
+__device__ __forceinline__ void bal_switch(bool first)
+{
+    if constexpr (BAL != 0 && (BAL & 3) == AT) {
+        if (first) __builtin_amdgcn_s_setprio(0);
+        else __builtin_amdgcn_s_setprio(1);
+    }
+}
+template <int BAL>
+__device__ __forceinline__ void bal_end(bool first)
+{
+    if constexpr (BAL != 0) {
+        if (!first) __builtin_amdgcn_s_setprio(0);
+    }
+}
+
+constexpr int SIG_FAST_PHASES = 9; // stamp slots of the diagnostic build (launch_variant names them), per half of the workgroup
 
 struct FastArgs {
     const void *X, *Y, *go;
@@ -67,7 +98,8 @@ struct FastArgs {
     unsigned char *kflag;         // [A][B] (d <= 4 only): 1 where the pair's fp32 solution cancelled or K is ill-conditioned in
                                   // the increments: the launcher lets the coverage kernel solve those pairs exactly (fp64)
 #ifdef SIGSVGD_PHASE_STAMPS
-    unsigned long long *stamps; // diagnostic build only: [SIG_FAST_PHASES] shader-clock totals per phase, summed over waves
+    unsigned long long *stamps; // diagnostic build only: [2][SIG_FAST_PHASES] shader-clock totals per phase, summed over the
+                                // waves of the older and of the younger half of every workgroup
 #endif
 };
 
@@ -488,7 +520,8 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // work twice.)
 // PFIX: 0, or the launch's P = T - 1 as a compile-time constant: the sweeps then build their EXEC windows from immediates (see
 // "fixed windows" above; gradient kernels of the 64-slot ring at T = 64).  Nothing else of the kernel depends on it.
-template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0>
+// BAL: 0, or the wave-balance schedule of the pair (see bal_top above); it adds the s_setprio and their branches, nothing else.
+template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : 2),
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgs a)
@@ -498,6 +531,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     constexpr int RM = RING - 1;
     constexpr int RPW = (RING == 32) ? 2 : 1; // rows (trajectories i) per wavefront
     constexpr int NWR = NW * RPW;             // rows per tile
+    static_assert(BAL == 0 || (GRAD && SYM && RING == 64 && NW == 8 && PFIX != 0 && (BAL & 3) != 0 && BAL < 8),
+                  "wave balance: the symmetric gradient kernels with fixed windows on 8-wave workgroups (the ones SIG_PRIO leaves alone)");
     // y rows are stored twice (row r and r + 64) so that the skewed row (t - lane) & 63 becomes
     // (64 - lane) + t: a per-lane base plus a compile-time offset.
     // Row strides are padded (YDS doubles / YFS floats) so that the 16 lanes a ds_read_b128 services per
@@ -519,6 +554,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     //  row's element addresses out of the column loop as 64-bit VGPR pairs and spills them)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & RM; // the row this lane owns
+    const bool bal_first = (BAL & 4) ? wave < NW / 2 : wave >= NW / 2; // (BAL: this wave's half holds the priority first; scalar)
     const int T = a.T, d = a.d, P = T - 1, io64 = a.io64;
     // Work distribution: the items of a launch -- (owned row tile, column), tile-major; symmetric launches only the
     // columns from the tile's first row on -- all cost the same (the NW waves of a workgroup meet at a barrier per
@@ -682,6 +718,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         SIG_STAMP(0)
         SIG_PRIO(3)
         if (pair_ok) {
+            bal_top<BAL>(bal_first);
             // ---- phase 0: centre x_i on y_j[0] ----------------------------------------------------
             // x~ pre-scaled so that the exponent argument in base 2 is one fused dot product:
             //   log2(e) * (-|x~ - y~|^2 / h) = xn + ynd[q] + sum_c xs[c] * y~[q][c]
@@ -746,6 +783,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 
             SIG_STAMP(1)
             SIG_PRIO(2)
+            bal_switch<BAL, 1>(bal_first);
             float kf_keep = 0.f;                   // K[P][P] of this lane's pair and the cancellation verdicts of phase 2, for the
             bool x0_keep = false, x1_keep = false; // conditioning check after the reverse sweep (4-channel gradient kernels)
             // ---- phase 2: forward sweep, anti-diagonal sigma = 0 .. 2P-2, in fp32 DIFFERENCE FORM ----------
@@ -857,6 +895,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 
             SIG_STAMP(2)
             SIG_PRIO(1)
+            bal_switch<BAL, 2>(bal_first);
             if (GRAD) {
                 // weights of this lane's pair: row side w_ij, column side w_ji (per lane with two rows per wavefront,
                 // uniform otherwise; fetched here so that the loads are long back when the gradient pass needs them)
@@ -948,6 +987,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     float r3 = 1.7320508075688772f;
                     asm volatile("" : "+s"(r3));
                     sweep_rev_fixed_round<PFIX, 64, 2 * PFIX - 1>(cur, downA, downB, V, Dsl, Ksl, r3);
+                    bal_switch<BAL, 3>(bal_first);
                     asm volatile("" : "+v"(yfrow), "+v"(gsoff));
                     asm volatile("" : "+s"(r3));
                     sweep_rev_fixed_round<PFIX, 0, 64>(cur, downA, downB, V, Dsl, Ksl, r3);
@@ -1047,6 +1087,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             for (int k = 0; k < EPT; ++k)
                 asm volatile("" : "+v"(raw_v[k].lo), "+v"(raw_v[k].hi), "+v"(raw_r[k].lo), "+v"(raw_r[k].hi));
         }
+        bal_end<BAL>(bal_first); // (a wave without a pair never raised it: then this changes nothing)
         SIG_STAMP(5)
 #ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER // timing experiment only (results are garbage without it)
         __syncthreads(); // every wave is done with y_j (and has parked its column-side result)
@@ -1092,8 +1133,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     } // row tiles of the range
 #ifdef SIGSVGD_PHASE_STAMPS
     SIG_STAMP(0)
-    if (lane == 0 && a.stamps)
-        for (int k = 0; k < SIG_FAST_PHASES; ++k) atomicAdd(&a.stamps[k], ph_[k]);
+    if (lane == 0 && a.stamps) // the older half of the workgroup (waves 0 .. NW/2 - 1) and the younger one apart
+        for (int k = 0; k < SIG_FAST_PHASES; ++k) atomicAdd(&a.stamps[(wave >= NW / 2 ? SIG_FAST_PHASES : 0) + k], ph_[k]);
 #endif
 }
 
@@ -1338,11 +1379,33 @@ static bool fixed_windows(int T, int want_grad)
     return !(e && e[0] == 't');
 }
 
+// The symmetric 4- and 8-channel gradient kernels with fixed windows have a twin with the wave-balance schedule (BAL, see bal_top);
+// launches that reach them run the twin.  SIGSVGD_WAVE_BALANCE=off, read per launch next to SIGSVGD_SWEEP_WINDOWS, keeps them
+// on the kernel without it: the tests compare the two on one build, and so do the A/B runs.
+// FAST_BAL: the schedule the twin is built with: 6, the older half first, the younger half from the end of phase 2 on -- the
+// fastest of the six measured at C4 (1, 2, 3 and their mirror images: profiles/wave_balance_ab.txt).
+// -DSIG_EXPERIMENT_BALANCE=n builds another one to measure; 0: no twin.
+#ifndef SIG_EXPERIMENT_BALANCE
+#define SIG_EXPERIMENT_BALANCE 6
+#endif
+constexpr int FAST_BAL = SIG_EXPERIMENT_BALANCE;
+// Which kernels have the twin: the symmetric ones on 8-wave workgroups, 8 channels (C4: -1.6 ... -2.2 %) and 4 channels (C3: -4 ... -5 %).  The
+// ordered 8-channel kernel was built with it in place of SIG_PRIO and lost 0.6-1.3 %: it keeps SIG_PRIO.
+template <int DPAD, bool SYM>
+constexpr bool fast_has_balance() { return FAST_BAL != 0 && SYM && DPAD <= 8; }
+static bool wave_balance(int T, int d, int want_grad, bool sym)
+{
+    if (!sym || d > 8 || !fast_has_balance<8, true>() || !fixed_windows(T, want_grad)) return false;
+    const char *e = getenv("SIGSVGD_WAVE_BALANCE");
+    return !(e && e[0] == 'o' && e[1] == 'f');
+}
+
 // [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold)
 {
     WsPlan w;
     w.fixed_windows = fixed_windows(T, want_grad) ? 1 : 0;
+    w.wave_balance = wave_balance(T, d, want_grad, sym) ? 1 : 0;
     if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
     if (want_grad) {
         w.g = fast_geometry(A, B, T, d, sym, off, stride, fold);
@@ -1353,11 +1416,18 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
 }
 
 namespace {
-// a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths
+// a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths, or
+// (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule
 template <int DPAD, int NW, bool SYM, bool LP, int RING>
-void launch_grad(bool fix, dim3 grid, dim3 block, hipStream_t stream, const FastArgs &a)
+void launch_grad(bool fix, bool bal, dim3 grid, dim3 block, hipStream_t stream, const FastArgs &a)
 {
     if constexpr (RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
+        if constexpr (fast_has_balance<DPAD, SYM>()) {
+            if (fix && bal) {
+                hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, FAST_BAL>), grid, block, 0, stream, a);
+                return;
+            }
+        }
         if (fix) {
             hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63>), grid, block, 0, stream, a);
             return;
@@ -1396,18 +1466,19 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     constexpr bool HAS_LP = DPAD <= 8; // the d == DPAD - 1 instantiations exist for the 4- and 8-channel layouts
     const bool lp = HAS_LP && grad && p.d == DPAD - 1;
     const bool fix = grad && w.fixed_windows && p.T == 64; // (the kernel's PFIX must be the launch's T - 1)
+    const bool bal = fix && w.wave_balance;
     if (!grad && sym)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING>), grid, block, 0, p.stream, a);
     else if (!grad)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING>), grid, block, 0, p.stream, a);
     else if (sym && lp)
-        launch_grad<DPAD, NW, true, HAS_LP, RING>(fix, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, true, HAS_LP, RING>(fix, bal, grid, block, p.stream, a);
     else if (sym)
-        launch_grad<DPAD, NW, true, false, RING>(fix, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, true, false, RING>(fix, bal, grid, block, p.stream, a);
     else if (lp)
-        launch_grad<DPAD, NW, false, HAS_LP, RING>(fix, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, false, HAS_LP, RING>(fix, bal, grid, block, p.stream, a);
     else
-        launch_grad<DPAD, NW, false, false, RING>(fix, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, false, false, RING>(fix, bal, grid, block, p.stream, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
@@ -1416,7 +1487,7 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
                                       "phase 4 gradient pass", "pair epilogue", "barrier after the pair",
                                       "block sum + stage store", "second barrier"};
     static_assert(sizeof(nm) / sizeof(nm[0]) == SIG_FAST_PHASES, "one name per stamp slot");
-    phase_stamps_report(p.stream, a.stamps, nm, "[phase stamps] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
+    phase_stamps_report_halves(p.stream, a.stamps, nm, "[phase stamps] A=%d T=%d d=%d grad=%d sym=%d: ", p.A, p.T, p.d, (int)grad, (int)sym);
 #endif
     return SIGSVGD_OK;
 }

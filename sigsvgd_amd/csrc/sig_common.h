@@ -159,7 +159,7 @@ __device__ __forceinline__ float max3_abs(float m, float a, float b)
         ph_[i] += now_ - tlast_;                                             \
         tlast_ = now_;                                                       \
     }
-constexpr int kMaxPhases = 16;
+constexpr int kMaxPhases = 32; // (gram_fast.hip keeps two sets of its 9: one per half of the workgroup)
 // the per-phase totals of the next launch on `stream`, zeroed (one buffer: every report below synchronises)
 inline unsigned long long *phase_stamps_begin(hipStream_t stream)
 {
@@ -184,6 +184,34 @@ void phase_stamps_report(hipStream_t stream, const unsigned long long *buf, cons
     va_end(ap);
     for (int k = 0; k < N; ++k) fprintf(stderr, "%s %.1f%% | ", names[k], 100.0 * (double)h[k] / tot);
     fprintf(stderr, "total %.3e wave-cycles\n", tot);
+}
+// The same for a kernel that keeps the N phases twice, [0, N) summed over the older half of every workgroup (waves 0 ..
+// NW/2 - 1) and [N, 2N) over the younger half: the line above over both halves together, then one line with the two halves side
+// by side, each phase as a share of its own half's total.
+template <int N>
+void phase_stamps_report_halves(hipStream_t stream, const unsigned long long *buf, const char *const (&names)[N], const char *fmt, ...)
+{
+    static_assert(2 * N <= kMaxPhases, "more phases than the buffer holds");
+    unsigned long long h[kMaxPhases];
+    (void)hipStreamSynchronize(stream);
+    (void)hipMemcpy(h, buf, sizeof(h), hipMemcpyDeviceToHost);
+    double tot[2] = {0, 0};
+    for (int k = 0; k < N; ++k) {
+        tot[0] += (double)h[k];
+        tot[1] += (double)h[N + k];
+    }
+    char head[256];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(head, sizeof(head), fmt, ap);
+    va_end(ap);
+    fprintf(stderr, "%s", head);
+    for (int k = 0; k < N; ++k) fprintf(stderr, "%s %.1f%% | ", names[k], 100.0 * (double)(h[k] + h[N + k]) / (tot[0] + tot[1]));
+    fprintf(stderr, "total %.3e wave-cycles\n", tot[0] + tot[1]);
+    fprintf(stderr, "%solder | younger half: ", head);
+    for (int k = 0; k < N; ++k)
+        fprintf(stderr, "%s %.1f%% | %.1f%% ; ", names[k], 100.0 * (double)h[k] / tot[0], 100.0 * (double)h[N + k] / tot[1]);
+    fprintf(stderr, "total %.3e | %.3e wave-cycles\n", tot[0], tot[1]);
 }
 #else
 #define SIG_STAMP(i)
@@ -309,6 +337,7 @@ struct WsPlan {
     WsArea wsk;          // forward-solution scratch (gram_band.hip, gram_generic.hip)
     WsArea counter, partials, colslab; // gram_generic.hip: work counter, gradient partials, column-side slab
     int fixed_windows = 0; // gram_fast.hip: the launch runs the kernel whose sweeps have their EXEC windows as immediates
+    int wave_balance = 0;  // gram_fast.hip: ... and, where that kernel has a wave-balance twin, the twin
     size_t end = 0; // bytes of the areas
     WsArea take(size_t bytes) // the next area, behind the ones taken so far
     {
