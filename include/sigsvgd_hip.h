@@ -80,6 +80,9 @@
  *     without one its column splits meet in fp32 atomics and the last bits of dK_out may differ between calls.
  *   - environment, read per launch, for tests and measurements only (results do not depend on any of them, bit for bit):
  *     SIGSVGD_BAND_MODE=serial|parallel pins the schedule of the refined-grid launches;
+ *     SIGSVGD_PAIR_MODE=serial|bands pins the schedule of the paired launches (sigsvgd_pair_*): one wavefront per pair, or a
+ *     workgroup per pair with the pair's 64-row bands dealt to its wavefronts, wherever that plan has two or more
+ *     (sigsvgd_pair_schedule tells which one a launch would run; any other value is ignored);
  *     SIGSVGD_SWEEP_WINDOWS=table keeps Gram + gradient launches of 64-point paths on the register-resident kernel
  *     whose PDE sweeps read their lane windows from the constant table (what every other path length runs) instead
  *     of its twin with the windows as immediates, so that the two can be compared on one build;
@@ -357,9 +360,19 @@ int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX
  * gradient outputs NULL, bad shapes, kinds, orders, dtypes, inv_h <= 0 with RBF or null pointers are SIGSVGD_E_BADARG.
  * One pair per wavefront, each gradient entry written by one lane in a fixed order: bit-reproducible, no floating-point
  * atomics.  Workspace: per-wave scratch of 2 x P x (Q + 63) floats for min(resident wavefronts, A) waves (at most 1 GiB,
- * fewer waves beyond); forward-only launches need none and report 0 bytes. */
+ * fewer waves beyond); forward-only launches need none and report 0 bytes.
+ *
+ * Schedule (third revision of ABI 10, additive): where a pair has enough 64-row bands for it to pay
+ * (the rule counts both schedules' dependent steps over the rounds the launch takes), each pair gets a workgroup of up to 8
+ * wavefronts that sweep the pair's bands as a pipeline (pair_bands.hip).  Same arithmetic per cell in the same order: K and both gradients are
+ * bit-identical to the one-wavefront schedule, and the workspace is the same (fewer of its per-pair slots are used).
+ * sigsvgd_pair_schedule (host only; the argument checks and refusals of sigsvgd_pair_workspace_bytes) reports what a launch
+ * with these arguments would run now, SIGSVGD_PAIR_MODE included: wavefronts per pair (1: the one-wavefront kernel), the
+ * grid, and the LDS bytes of a workgroup. */
 int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
                                  unsigned flags, size_t *bytes);
+int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad, unsigned flags,
+                          int *waves_per_pair, int *grid, size_t *lds_bytes);
 int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
                      int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
                      size_t workspace_bytes, void *stream);

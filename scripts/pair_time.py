@@ -2,6 +2,7 @@
 replaces for the built-in static kernels, the diagonal of a Gram launch.
 
     python scripts/pair_time.py [--reps 10]
+    python scripts/pair_time.py --modes [--only A,T,d,order]
 
 Prints one JSON line per shape and route: milliseconds per call (median of `reps` timed with device events after warm-up) of
   fwd        the forward alone (no input requires grad);
@@ -13,6 +14,12 @@ Shapes: A = 1024, T = 64, d = 7, order 0 in fp32 and fp64 (SVGD's C4 batch); A =
 A = 6, T = 100, d = 3, order 3 (the reference's arm-spline example) and A = 16 (the edge of compute_kernel's rule for small
 forward-only calls); A = 32, T = 1024, d = 4, order 0 (long).  The "pair" line also gives
 "pair_fwd_op": `ops.pair_fwd` itself, which compute_kernel's forward passes over where that rule sends it to the diagonal.
+
+--modes times the two schedules of the paired launch instead: `ops.pair_fwd` and `ops.pair_fwd_bwd`
+under SIGSVGD_PAIR_MODE=serial (one wavefront per pair) and =bands (a workgroup per pair) in one process, the two modes
+alternating call by call, median and min - max of `reps` calls each after warm-up, one JSON line per shape with the waves
+per pair of the bands plan and what the default rule picks.  --only A,T,d,order: that shape alone, with whatever schedule the
+environment gives (for runs of two builds side by side, SIGSVGD_LIB_PATH).
 """
 import argparse
 import json
@@ -46,13 +53,73 @@ def timed(fn, reps, warmup=2):
     return ts[len(ts) // 2], ts[0], ts[-1]
 
 
+# (A, T, d, order) of --modes: few long pairs, the reference's refined shapes, and many short pairs (one band: serial always)
+MODE_SHAPES = [(1, 4096, 4, 0), (2, 1024, 4, 0), (6, 1024, 4, 0), (32, 1024, 4, 0), (128, 1024, 4, 0), (512, 1024, 4, 0),
+               (6, 100, 3, 3), (16, 100, 3, 3), (64, 200, 3, 2), (1024, 64, 7, 0)]
+# shapes on both sides of the default rule, timed after them: more pairs than the device holds
+# workgroups, few bands per pair, many short pairs of two bands
+EDGE_SHAPES = [(700, 1024, 4, 0), (2048, 1024, 4, 0), (2, 700, 2, 0), (2, 450, 3, 0), (2, 386, 3, 0), (2, 322, 3, 0),
+               (300, 322, 3, 0), (3, 130, 2, 0), (2000, 100, 3, 0)]
+
+
+def timed_alternating(fns, reps, warmup=2):
+    """{name: (median, min, max)} ms of the calls `fns[name]()`, the names taking turns call by call"""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {name: [] for name in fns}
+    for _ in range(reps):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[name].append(a.elapsed_time(b))
+    return {name: (sorted(v)[len(v) // 2], min(v), max(v)) for name, v in ts.items()}
+
+
+def modes(a, dev, g):
+    shapes = [tuple(int(v) for v in a.only.split(","))] if a.only else MODE_SHAPES + EDGE_SHAPES
+    fixed = ["env"] if a.only else ["serial", "bands"]
+    for (A, T, d, order) in shapes:
+        X = (torch.randn(A, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).to(dev, torch.float32)
+        Y = (torch.randn(A, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).to(dev, torch.float32)
+
+        def under(mode, fn):
+            def call():
+                if mode != "env":
+                    os.environ["SIGSVGD_PAIR_MODE"] = mode
+                return fn()
+            return call
+
+        res = {"shape": [A, T, d], "order": order}
+        if not a.only:
+            os.environ["SIGSVGD_PAIR_MODE"] = "bands"
+            res["waves_per_pair"], res["grid"], res["lds"] = ops.pair_schedule(A, T, T, d, order)
+            del os.environ["SIGSVGD_PAIR_MODE"]
+            res["default_waves"] = ops.pair_schedule(A, T, T, d, order)[0]
+        fwd = timed_alternating({m: under(m, lambda: ops.pair_fwd(X, Y, 1.0 / a.sigma, order)) for m in fixed}, a.reps)
+        bwd = timed_alternating({m: under(m, lambda: ops.pair_fwd_bwd(X, Y, 1.0 / a.sigma, order)) for m in fixed}, a.reps)
+        if not a.only:
+            os.environ.pop("SIGSVGD_PAIR_MODE", None)
+        for m in fixed:
+            res[m] = {"fwd": [round(v, 4) for v in fwd[m]], "fwd_bwd": [round(v, 4) for v in bwd[m]]}
+        print(json.dumps(res), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--sigma", type=float, default=1.0)
+    ap.add_argument("--modes", action="store_true")
+    ap.add_argument("--only", default="")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
+    if a.modes or a.only:
+        return modes(a, dev, g)
     k = sk.SigKernel(sk.RBFKernel(a.sigma), 0)
     for (A, T, d, order, dtype) in SHAPES:
         k.dyadic_order = order

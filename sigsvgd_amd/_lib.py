@@ -16,8 +16,10 @@ _CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
            "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
-           "sig_pde.hip", "gram_long.hip", "sqdist_select.hip"]
+           "sig_pde.hip", "gram_long.hip", "pair_bands.hip", "pair_bands_f32.hip",
+           "sqdist_select.hip"]
 HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"), os.path.join(_CSRC, "ring_sweep.h"),
+           os.path.join(_CSRC, "long_static.h"), os.path.join(_CSRC, "pair_bands.h"),  # (pair_bands_f32.hip includes pair_bands.hip: both are in SOURCES)
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
 # mirror of include/sigsvgd_hip.h
@@ -61,6 +63,7 @@ ARGTYPES = {
     "sigsvgd_pair_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
     "sigsvgd_pair_fwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _sz, _vp],
     "sigsvgd_pair_fwd_bwd": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+    "sigsvgd_pair_schedule": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_ci), _out(_ci), _out(_sz)],
     "sigsvgd_gram_long2_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
     "sigsvgd_gram_long_fwd_bwd2": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _sz,
                                    _vp],
@@ -102,7 +105,8 @@ def build(force: bool = False, verbose: bool = False, out_path: str = None, objd
 
 
 def _build_to(lib_path: str, objdir: str, verbose: bool, defines=()) -> str:
-    # one hipcc per source, side by side (the four pair-solver files take 30-50 s each: 3 min in a row, 1 min in parallel),
+    # one hipcc per source, side by side (the four pair-solver files take 30-50 s each, the two
+    # of pair_bands about 2 min each: 7 min in a row, 2 min in parallel),
     # then one link; objects under sigsvgd_amd/_obj/ (git-ignored)
     from concurrent.futures import ThreadPoolExecutor
 

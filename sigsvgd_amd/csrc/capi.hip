@@ -68,6 +68,7 @@ int long_workspace(const LongProblem &p, int want_grad, size_t *bytes);
 int long_launch(const LongProblem &p);
 int pair_workspace(const LongProblem &p, int want_grad, size_t *bytes);
 int pair_launch(const LongProblem &p);
+int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int *grid, size_t *lds_bytes);
 int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes);
 int long2_launch(const LongProblem &p);
 int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC);
@@ -641,6 +642,16 @@ int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order,
     const int rc = check_pair(p, false);
     if (rc) return rc;
     return pair_workspace(p, want_grad ? 1 : 0, bytes);
+}
+
+int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad, unsigned flags,
+                          int *waves_per_pair, int *grid, size_t *lds_bytes)
+{
+    if (!waves_per_pair || !grid || !lds_bytes) return bad_arg("pair: schedule query without a place for its answer");
+    const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    const int rc = check_pair(p, false);
+    if (rc) return rc;
+    return pair_schedule(p, want_grad ? 1 : 0, waves_per_pair, grid, lds_bytes);
 }
 
 int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,

@@ -21,6 +21,9 @@
 // same fill and sweeps.  From the pair's one S the gradient pass writes gX_i straight into the caller's buffer, and the same
 // pass with lanes owning points n of Y_i and walking m chains S through dk/dy into gY_i[n] = w_i sum_m dG[m][n] dk(x_m, y_n)/dy_n
 // (dk/dy = 2 inv_h (x - y) k for RBF, x for linear).  Either output may be skipped; no slabs and no reduce kernel.
+// Where a pair has bands enough for it to pay (pair_use_bands), pair_launch hands the launch to pair_bands.hip (a workgroup per
+// pair, its bands dealt to the wavefronts): same bits, same workspace.  The static kernels' device
+// helpers both files use are in long_static.h.
 //
 // Two-sided Gram mode (gram_long2_kernel): a work item is a tile of IC rows x JC columns whose pairs
 // are walked row by row.  After a pair's one reverse sweep the row-side pass adds w_row dk/dx into the tile's fp64 slab of
@@ -39,12 +42,16 @@
 // MI355X: forward-only launches by 1.5-4 %, the partial kernel by 1-1.4 %, ranges of run-medians apart
 // (profiles/long_shared_solve_ab.txt).  So the copies stay.
 #include <algorithm>
+#include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <tuple>
 #include <type_traits>
 #include <vector>
 
+#include "long_static.h"
+#include "pair_bands.h"
 #include "ring_sweep.h"
 
 namespace sigsvgd {
@@ -81,142 +88,6 @@ struct PartArgs : LongArgs {
     long long nfull; // items of the first pass (the chunks strictly between a tile's first and last)
 };
 
-namespace {
-// The radial kinds beside RBF: k = phi(s), s = |x - y|^2 inv_h.  radial_phi: phi(s); radial_slope:
-// -phi'(s), which takes the place of RBF's exp(-s) in the gradient contraction (IMQ: k^3 / 2, rational quadratic: k^2).
-template <int KIND>
-inline constexpr bool kRadialKind = KIND == SIGSVGD_STATIC_IMQ || KIND == SIGSVGD_STATIC_RQ;
-template <int KIND>
-__device__ __forceinline__ double radial_phi(double s)
-{
-    return KIND == SIGSVGD_STATIC_IMQ ? rsqrt(1.0 + s) : 1.0 / (1.0 + s);
-}
-template <int KIND>
-__device__ __forceinline__ double radial_slope(double s)
-{
-    const double k = radial_phi<KIND>(s);
-    return KIND == SIGSVGD_STATIC_IMQ ? 0.5 * (k * k * k) : k * k;
-}
-
-// the static kernel of x (LDS, fp64) and y (global, the caller's dtype)
-template <int KIND, typename IO>
-__device__ __forceinline__ double static_k(const double *x, const IO *y, int d, double inv_h)
-{
-    double s = 0.0;
-    if constexpr (kRadialKind<KIND>) {
-        for (int c = 0; c < d; ++c) {
-            const double t = x[c] - (double)y[c];
-            s = __builtin_fma(t, t, s);
-        }
-        return radial_phi<KIND>(s * inv_h);
-    }
-    if (KIND == SIGSVGD_STATIC_RBF) {
-        for (int c = 0; c < d; ++c) {
-            const double t = x[c] - (double)y[c];
-            s = __builtin_fma(t, t, s);
-        }
-        return exp64(-s * inv_h);
-    }
-    for (int c = 0; c < d; ++c) s = __builtin_fma(x[c], (double)y[c], s);
-    return s;
-}
-// the same with y's first min(d, 16) coordinates in registers (d <= 16; the branches on d are wave-uniform)
-template <int KIND>
-__device__ __forceinline__ double static_k16(const double *x, const double (&y)[16], int d, double inv_h)
-{
-    double s = 0.0;
-    if constexpr (kRadialKind<KIND>) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            if (c < d) {
-                const double t = x[c] - y[c];
-                s = __builtin_fma(t, t, s);
-            }
-        }
-        return radial_phi<KIND>(s * inv_h);
-    }
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        if (c < d) {
-            if (KIND == SIGSVGD_STATIC_RBF) {
-                const double t = x[c] - y[c];
-                s = __builtin_fma(t, t, s);
-            } else {
-                s = __builtin_fma(x[c], y[c], s);
-            }
-        }
-    }
-    return KIND == SIGSVGD_STATIC_RBF ? exp64(-s * inv_h) : s;
-}
-
-// The pair's coarse S chained through the static kernel's derivative into the gradient of the points of one of its paths.
-// Lanes own points o of that path, 63 per pass (lane l holds o = o0 - 1 + l and, from lane 1 on, its gradient; S at o - 1
-// arrives from the lane below), and walk the points t of the other path in order.  dG[m][n] / w = (S[m-1][n-1] + S[m][n]) -
-// (S[m-1][n] + S[m][n-1]), S = 0 outside the coarse grid; store(o, c, g) takes coordinate c of own point o's gradient.
-// OWN_X: the points are X's, dk/dx = -2 inv_h (x - y) k (RBF) or y (linear); else Y's, dk/dy = 2 inv_h (x - y) k or x.
-// The radial kinds: RBF's with -phi'(s) for k.
-template <int KIND, bool OWN_X, typename IO, typename Store>
-__device__ __forceinline__ void static_grad_pass(const RingWave &rw, const IO *own, int To, const IO *oth, int Tt, int d,
-                                                 double inv_h, Store &&store)
-{
-    const int lane = threadIdx.x;
-    for (int o0 = 0; o0 < To; o0 += kWave - 1) {
-        const int o = o0 - 1 + lane;
-        const bool valid = lane >= 1 && o < To;
-        const IO *po = own + (size_t)min(max(o, 0), To - 1) * d;
-        for (int c0 = 0; c0 < d; c0 += 16) {
-            double accv[16];
-#pragma unroll
-            for (int c = 0; c < 16; ++c) accv[c] = 0.0;
-            double s_prev = 0.0, nb_prev = 0.0; // S at (o, t - 1), (o - 1, t - 1)
-            for (int t = 0; t < Tt; ++t) {
-                const int oc = min(max(o, 0), To - 2), tc = min(t, Tt - 2); // (read at a clamped block, then dropped)
-                const double s = OWN_X ? ring_S(rw, oc, tc) : ring_S(rw, tc, oc);
-                const double s_cur = o >= 0 && o < To - 1 && t < Tt - 1 ? s : 0.0;
-                const double nb = shfl_up_f64(s_cur); // S at (o - 1, t)
-                const double R = (nb_prev + s_cur) - (nb + s_prev); // dG / w
-                s_prev = s_cur;
-                nb_prev = nb;
-                const IO *pt = oth + (size_t)t * d;
-                const IO *xm = OWN_X ? po : pt, *yn = OWN_X ? pt : po;
-                if constexpr (kRadialKind<KIND>) { // RBF's contraction with -phi'(s) in place of exp(-s)
-                    double dist = 0.0;
-                    for (int c = 0; c < d; ++c) {
-                        const double u = (double)xm[c] - (double)yn[c];
-                        dist = __builtin_fma(u, u, dist);
-                    }
-                    const double rk = R * radial_slope<KIND>(dist * inv_h);
-#pragma unroll
-                    for (int c = 0; c < 16; ++c)
-                        if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
-                } else if (KIND == SIGSVGD_STATIC_RBF) {
-                    double dist = 0.0;
-                    for (int c = 0; c < d; ++c) {
-                        const double u = (double)xm[c] - (double)yn[c];
-                        dist = __builtin_fma(u, u, dist);
-                    }
-                    const double rk = R * exp64(-dist * inv_h);
-#pragma unroll
-                    for (int c = 0; c < 16; ++c)
-                        if (c0 + c < d) accv[c] = __builtin_fma(rk, (double)xm[c0 + c] - (double)yn[c0 + c], accv[c]);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 16; ++c)
-                        if (c0 + c < d) accv[c] = __builtin_fma(R, (double)pt[c0 + c], accv[c]);
-                }
-            }
-            if (valid) {
-#pragma unroll
-                for (int c = 0; c < 16; ++c)
-                    if (c0 + c < d)
-                        store(o, c0 + c, KIND == SIGSVGD_STATIC_RBF || kRadialKind<KIND>
-                                             ? ((OWN_X ? -2.0 : 2.0) * inv_h) * accv[c]
-                                             : accv[c]);
-            }
-        }
-    }
-}
-} // namespace
 
 template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false>
 __global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED, PairArgs, LongArgs> a)
@@ -927,6 +798,45 @@ int long_launch(const LongProblem &p)
     return rc;
 }
 
+// ---- the paired mode's schedule: one wavefront per pair (gram_long_kernel) or a workgroup per pair (pair_bands.hip) --------
+namespace {
+PairGeom pair_geom(const LongPlan &pl)
+{
+    return PairGeom{pl.r, pl.P, pl.Q, pl.nbands, pl.nsteps, pl.nrow, pl.grid, pl.per_wave / sizeof(float)};
+}
+// Whether a paired launch runs the band-parallel kernel under plan bp.  SIGSVGD_PAIR_MODE=serial|bands (read per launch; tests
+// and measurements only, the results have the same bits; any other value is ignored) pins it wherever the plan has two waves
+// or more.  Default rule: bands where its dependent steps, over the rounds the launch takes, are
+// fewer than a third of the serial schedule's,
+//   3 * rounds_bands * phases * 16  <  rounds_serial * nbands * nsteps,      rounds = ceil(A / workgroups or waves in flight).
+// The 3 is the measured cost of a band-parallel step against a serial one (2.2 - 2.6: two waves share a SIMD, and a barrier
+// every 16 steps), rounded up.  Few bands per pair, or pairs enough to fill the device in both schedules, stay serial.
+bool pair_use_bands(int A, const LongPlan &pl, const PairBandsPlan &bp)
+{
+    if (bp.NB < 2) return false;
+    const char *e = getenv("SIGSVGD_PAIR_MODE");
+    if (e && !strcmp(e, "serial")) return false;
+    if (e && !strcmp(e, "bands")) return true;
+    const long long rounds_b = (A + bp.grid - 1) / bp.grid, rounds_s = (A + pl.grid - 1) / pl.grid;
+    return 3 * rounds_b * bp.phases * 16 < rounds_s * (long long)pl.nbands * pl.nsteps;
+}
+} // namespace
+
+// what a paired launch would run now (host only): waves per pair, workgroups, LDS bytes per workgroup
+int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int *grid, size_t *lds_bytes)
+{
+    LongPlan pl;
+    const int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
+    if (rc) return rc;
+    PairBandsPlan bp;
+    pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
+    const bool bands = pair_use_bands(p.A, pl, bp);
+    *waves_per_pair = bands ? bp.NB : 1;
+    *grid = bands ? bp.grid : pl.grid;
+    *lds_bytes = bands ? bp.lds : pl.lds;
+    return SIGSVGD_OK;
+}
+
 // gradX_out and gradY_out both NULL: forward only
 int pair_launch(const LongProblem &p)
 {
@@ -936,6 +846,9 @@ int pair_launch(const LongProblem &p)
     int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
+    PairBandsPlan bp;
+    pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
+    if (pair_use_bands(p.A, pl, bp)) return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
     return ring_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
 }

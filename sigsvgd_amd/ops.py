@@ -307,6 +307,17 @@ def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_k
                                            1 if want_grad else 0, 0), (ctypes.c_size_t(0),), may_refuse=True)
 
 
+def pair_schedule(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                  want_grad: bool = True) -> Tuple[int, int, int]:
+    """(waves_per_pair, grid, lds_bytes) of the paired launch these arguments would run now (`sigsvgd_pair_schedule`, host
+    only, SIGSVGD_PAIR_MODE included): 1 wave per pair is the serial kernel of csrc/gram_long.hip, more the band-parallel one
+    of csrc/pair_bands.hip.  The results do not depend on it, bit for bit."""
+    waves, grid, lds = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
+    _query("pair_schedule", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind), 1 if want_grad else 0, 0),
+           (waves, grid, lds))
+    return waves.value, grid.value, lds.value
+
+
 def _prep_pair(X, Y):
     if X.dim() != 3 or Y.dim() != 3 or X.shape[0] != Y.shape[0]:
         raise ValueError(f"pairs need X [A, TX, d] and Y [A, TY, d]; got {tuple(X.shape)} and {tuple(Y.shape)}")
