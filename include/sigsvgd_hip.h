@@ -403,6 +403,42 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
                                void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---- long-path route, derivative in the static kernel's bandwidth (ABI 10, additive) --------------
+ * sigsvgd_gram_long_fwd_bwd2 and sigsvgd_pair_fwd_bwd with one more output: for the static kernels k = phi(|x - y|^2 inv_h)
+ * (SIGSVGD_STATIC_RBF, _IMQ, _RQ) every pair's derivative of K in inv_h, from the pair's one reverse sweep,
+ *   dK_dinvh_out[i][j] = - sum_{m,n} R_ij[m][n] slope(dist inv_h) dist,     dist = |x_im - y_jn|^2,
+ * with R = dG / w the 4-corner scatter of the pair's S and slope = -phi' (exp(-s) for RBF, k^3 / 2 for IMQ, k^2 for the
+ * rational quadratic kernel): the contraction of the coordinate gradients with the scalar dist in place of (x - y).  It is the
+ * reference's GG convention chained exactly through the static kernel (the exact derivative of K for the first-order stencil;
+ * for the default stencil GG is not the exact adjoint, and the value differs from a finite difference of K by per cents, as
+ * the coordinate gradients do).  dK / d sigma = -inv_h^2 dK / d inv_h for k(x, y) = phi(|x - y|^2 / sigma).
+ * dK_dinvh_out is required, [A][B] (sigsvgd_gram_long_fwd_bwd_h) or [A] (sigsvgd_pair_fwd_bwd_h) in the I/O dtype, and is
+ * unweighted: grad_out and SIGSVGD_FLAG_SYM weight the coordinate gradients only.  With SIGSVGD_FLAG_Y_IS_X the pair (i, j),
+ * i <= j, stores its value at [i][j] and [j][i], as K's mirror does.  gradX_out and gradY_out may both be NULL: the launch
+ * still runs the reverse sweep and needs the per-wave scratch, and no slabs.  K_out and the gradients returned are
+ * bit-identical to those of sigsvgd_gram_long_fwd_bwd2 / sigsvgd_pair_fwd_bwd on the same arguments.  The paired launch always
+ * runs the one-wavefront schedule.  Lanes own points of X and add their terms in fp64; a fixed-shape reduction over the
+ * wavefront and a fixed order over the passes of 63 points follow, and one lane stores the pair's value: bit-reproducible, no
+ * floating-point atomics.
+ * SIGSVGD_E_BADARG: SIGSVGD_STATIC_LINEAR (it has no bandwidth), dK_dinvh_out == NULL, inv_h <= 0, unknown flag bits, and what
+ * the launches without the output refuse; limits and SIGSVGD_E_UNSUPPORTED are theirs too (SIGSVGD_FLAG_NAIVE_SOLVER: RBF
+ * only).  Workspace: sigsvgd_gram_long_h_workspace_bytes = the scratch plus the slabs of the gradients wanted (what
+ * sigsvgd_gram_long2_workspace_bytes reports where one is wanted; the scratch alone where neither is);
+ * sigsvgd_pair_h_workspace_bytes = sigsvgd_pair_workspace_bytes with the gradient. */
+int sigsvgd_gram_long_h_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
+                                        int want_gradX, int want_gradY, unsigned flags, size_t *bytes);
+int sigsvgd_gram_long_fwd_bwd_h(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                                int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                                void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */,
+                                void *dK_dinvh_out /* [A][B], required */, void *workspace, size_t workspace_bytes,
+                                void *stream);
+int sigsvgd_pair_h_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, unsigned flags,
+                                   size_t *bytes);
+int sigsvgd_pair_fwd_bwd_h(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                           int dyadic_order, int static_kind, unsigned flags, const void *grad_out /* [A] or NULL = ones */,
+                           void *K_out, void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */,
+                           void *dK_dinvh_out /* [A], required */, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- long-path Gram, one rank's share of the Y = X solve (ABI 10, additive) -----------------------
  * The partial mode of the two-sided Y-is-X launch, for the sharded SVGD step: the launch of rank tile_offset of tile_stride
  * owns the row tiles tile_offset + k tile_stride of tile_rows rows each -- with SIGSVGD_FLAG_FOLD_TILES also their mirror

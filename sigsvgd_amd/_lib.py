@@ -67,6 +67,11 @@ ARGTYPES = {
     "sigsvgd_gram_long2_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
     "sigsvgd_gram_long_fwd_bwd2": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _sz,
                                    _vp],
+    "sigsvgd_gram_long_h_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_gram_long_fwd_bwd_h": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _sz, _vp],
+    "sigsvgd_pair_h_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _ci, _cu, _out(_sz)],
+    "sigsvgd_pair_fwd_bwd_h": [_vp, _vp, _ci, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
     "sigsvgd_gram_long_partial_plan": [_ci, _ci, _ci, _ci, _ci, _cu, _ci, _out(_ci), _out(_ci)],
     "sigsvgd_gram_long_partial_workspace_bytes": [_ci, _ci, _ci, _ci, _ci, _cu, _ci, _ci, _out(_sz)],
     "sigsvgd_gram_long_sym_partial": [_vp, _ci, _ci, _ci, _ci, _cd, _ci, _ci, _cu, _ci, _ci, _vp, _vp, _vp, _vp, _sz, _vp],

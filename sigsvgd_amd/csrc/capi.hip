@@ -71,6 +71,9 @@ int pair_launch(const LongProblem &p);
 int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int *grid, size_t *lds_bytes);
 int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes);
 int long2_launch(const LongProblem &p);
+int pair_h_launch(const LongProblem &p, void *dk_out);
+int long2_h_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes);
+int long2_h_launch(const LongProblem &p, void *dk_out);
 int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC);
 int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes);
 int long_part_launch(const LongProblem &p, int off, int stride);
@@ -187,6 +190,16 @@ static int check_pair(const LongProblem &p, bool launch)
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
     return check_long(p, launch);
+}
+
+// the bandwidth entry points, after their mode's own checks: a static kernel that has a bandwidth,
+// and with `launch` a place for the derivative
+static int check_bandwidth(const char *who, const LongProblem &p, bool launch, const void *dK_dinvh_out)
+{
+    if (!static_kind_radial(p.kind))
+        return bad_arg("%s: the linear static kernel has no bandwidth (SIGSVGD_STATIC_RBF, _IMQ or _RQ)", who);
+    if (launch && !dK_dinvh_out) return bad_arg("%s: dK_dinvh_out == NULL", who);
+    return SIGSVGD_OK;
 }
 
 // the distance select's (sqdist_select.hip): the shape, the one flag it takes (SIGSVGD_FLAG_Y_IS_X: one batch in both slots)
@@ -700,6 +713,56 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
     return long2_launch(p);
+}
+
+int sigsvgd_gram_long_h_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
+                                        int want_gradX, int want_gradY, unsigned flags, size_t *bytes)
+{
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    int rc = check_long2(p, false, want_gradY != 0);
+    if (!rc) rc = check_bandwidth("gram_long_h", p, false, nullptr);
+    if (rc) return rc;
+    return long2_h_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
+}
+
+int sigsvgd_gram_long_fwd_bwd_h(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
+                                int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                                void *gradX_out, void *gradY_out, void *dK_dinvh_out, void *workspace, size_t workspace_bytes,
+                                void *stream)
+{
+    const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
+                        gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    int rc = check_long2(p, true, gradY_out != nullptr);
+    if (!rc) rc = check_bandwidth("gram_long_h", p, true, dK_dinvh_out);
+    if (rc) return rc;
+    Range range("sigsvgd_gram_long_fwd_bwd_h");
+    return long2_h_launch(p, dK_dinvh_out);
+}
+
+int sigsvgd_pair_h_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, unsigned flags,
+                                   size_t *bytes)
+{
+    if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
+    const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
+    int rc = check_pair(p, false);
+    if (!rc) rc = check_bandwidth("pair_h", p, false, nullptr);
+    if (rc) return rc;
+    return pair_workspace(p, 1, bytes); // (the launch always runs the reverse sweep)
+}
+
+int sigsvgd_pair_fwd_bwd_h(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
+                           int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
+                           void *gradX_out, void *gradY_out, void *dK_dinvh_out, void *workspace, size_t workspace_bytes,
+                           void *stream)
+{
+    const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
+                        gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    int rc = check_pair(p, true);
+    if (!rc) rc = check_bandwidth("pair_h", p, true, dK_dinvh_out);
+    if (rc) return rc;
+    Range range("sigsvgd_pair_fwd_bwd_h");
+    return pair_h_launch(p, dK_dinvh_out);
 }
 
 int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags, int tile_stride,

@@ -36,6 +36,10 @@
 // tile from its first row on, the slabs cover the owned tiles only, and long_part_reduce_kernel writes the fp64 partial
 // gradient of every row (zero where nothing arrived).  The host picks (R, JC) by search (part_pick).
 //
+// Bandwidth launches (BW): the paired and the two-sided kernel with one more pass per pair behind the
+// gradient passes, static_bw_pass (long_static.h), which contracts the same S with the static kernel's derivative in inv_h and
+// stores the pair's dK / d inv_h, unweighted.  A compile-time flag: the instantiations without it are the code they were.
+//
 // The per-pair solve (staging, fill, forward sweep, K store, reverse sweep) is written out in each of the three kernels, and K's
 // bit-identity across the modes rests on the copies staying equal.  One shared function (long_solve_pair over a PairSource, with
 // one two_sided_grad block) gave the same bits and the same registers, scratch and occupancy, but was measured slower on the
@@ -81,6 +85,14 @@ struct Long2Args : LongArgs {
 // the partial mode's arguments: LongArgs (A = B paths of M = N points; JC: the columns of an item;
 // partials: the row-side slabs, one [TX * d] per (row of an owned tile, column chunk), owned tiles in the order of `tm`) and
 // the column-side slabs, one per (owned tile, row j from the tile's first row on): TileMap::start gives a tile's first.
+// The bandwidth launches' arguments: the paired mode's and the two-sided mode's with the output of the
+// per-pair dK / d inv_h (caller's dtype).  Types of their own once more: the launches without it keep their argument layout.
+struct PairHArgs : PairArgs {
+    void *dK_dinvh; // [A]
+};
+struct Long2HArgs : Long2Args {
+    void *dK_dinvh; // [A][B]
+};
 struct PartArgs : LongArgs {
     double *colpart;
     TileMap tm;      // the row tiles this launch owns, R rows each
@@ -89,9 +101,14 @@ struct PartArgs : LongArgs {
 };
 
 
-template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false>
-__global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED, PairArgs, LongArgs> a)
+// BW (paired mode only): after the pair's gradient passes one more pass chains the same S through the
+// static kernel's derivative in the bandwidth and stores the pair's dK / d inv_h; a compile-time branch, so the instantiations
+// without it keep their code.
+template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false, bool BW = false>
+__global__ __launch_bounds__(64) void gram_long_kernel(
+    std::conditional_t<BW, PairHArgs, std::conditional_t<PAIRED, PairArgs, LongArgs>> a)
 {
+    static_assert(!BW || (PAIRED && GRAD), "the bandwidth pass needs the paired mode's reverse sweep");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -165,6 +182,10 @@ __global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED
                     static_grad_pass<KIND, false>(rw, yj, N, xi, M, d, a.inv_h, [&](int nn, int c, double g) {
                         gY[((size_t)i * N + nn) * d + c] = (IO)(w * g);
                     });
+                if constexpr (BW) { // (unweighted: K's own derivative)
+                    const double dk = static_bw_pass<KIND>(rw, xi, M, yj, N, d, a.inv_h);
+                    if (lane == 0) static_cast<IO *>(a.dK_dinvh)[i] = (IO)dk;
+                }
             } else { // into the item's slab, in j order
                 static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
                     double *o = slab + (size_t)m * d + c;
@@ -178,9 +199,12 @@ __global__ __launch_bounds__(64) void gram_long_kernel(std::conditional_t<PAIRED
 
 // The two-sided Gram mode, a kernel of its own so that gram_long_kernel's instantiations keep
 // their code: the same staging, fill and sweeps per pair (K has the same bits), the items and the gradient passes differ.
-template <typename IO, bool NAIVE, bool GRAD, int KIND>
-__global__ __launch_bounds__(64) void gram_long2_kernel(Long2Args a)
+// BW: the bandwidth pass behind the pair's gradient passes, as in gram_long_kernel; with yx the pair
+// (i, j) stores its derivative at [i][j] and [j][i], as K's mirror does.
+template <typename IO, bool NAIVE, bool GRAD, int KIND, bool BW = false>
+__global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, Long2HArgs, Long2Args> a)
 {
+    static_assert(!BW || GRAD, "the bandwidth pass needs the reverse sweep");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -279,6 +303,13 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(Long2Args a)
                         double *o = cs + (size_t)nn * d + c;
                         *o = i == i0 ? wc * g : __builtin_fma(wc, g, *o);
                     });
+                if constexpr (BW) { // (unweighted: K's own derivative)
+                    const double dk = static_bw_pass<KIND>(rw, xi, M, yj, N, d, a.inv_h);
+                    if (lane == 0) {
+                        static_cast<IO *>(a.dK_dinvh)[(size_t)i * a.B + j] = (IO)dk;
+                        if (a.yx) static_cast<IO *>(a.dK_dinvh)[(size_t)j * a.B + i] = (IO)dk; // the mirror: same bits
+                    }
+                }
                 __syncthreads(); // (the next pair's forward sweep overwrites the scratch and the ring)
             }
         }
@@ -517,10 +548,12 @@ struct Long2Plan : LongPlan {
     int IC, nti;
 };
 
-int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, bool want_col, bool yx, Long2Plan &pl)
+// want_bw (the bandwidth launch): the per-wave scratch of a reverse sweep whatever gradients are wanted, and nothing else.
+int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, bool want_col, bool yx, Long2Plan &pl,
+                    bool want_bw = false)
 {
     const int want_grad = want_row || want_col;
-    const int rc = ring_make_plan(M, N, n, want_grad, d, "gram_long", pl);
+    const int rc = ring_make_plan(M, N, n, want_grad || want_bw, d, "gram_long", pl);
     if (rc) return rc;
     auto tiles = [](int rows, int chunk) { return (rows + chunk - 1) / chunk; };
     int IC = 32, JC = 32;
@@ -719,6 +752,21 @@ struct Long2Family {
     template <typename IO, bool NAIVE, bool GRAD, int KIND>
     static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, GRAD, KIND>; }
 };
+// the bandwidth launches (always with the reverse sweep; RBF and the radial kinds: bw_launch below names their instantiations)
+struct PairHFamily {
+    using Args = PairHArgs;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long paired, bandwidth)",
+                                *launch_failed = "launch gram_long_kernel (paired, bandwidth)";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, true, KIND, true, true>; }
+};
+struct Long2HFamily {
+    using Args = Long2HArgs;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2, bandwidth)",
+                                *launch_failed = "launch gram_long2_kernel (bandwidth)";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, true, KIND, true>; }
+};
 struct PartFamily { // (always with the gradient)
     using Args = PartArgs;
     static constexpr bool has_kind = true, has_fwd_only = false;
@@ -747,6 +795,30 @@ int long2_reduce(const LongProblem &p, const double *partials, void *out, int ro
     const hipError_t e = hipGetLastError();
     return e != hipSuccess ? hip_fail(e, what) : SIGSVGD_OK;
 }
+
+// ring_launch for the bandwidth families: the kinds that have a bandwidth, the first-order stencil where the route has it (RBF)
+template <typename F, typename IO, typename Plan>
+hipError_t bw_launch_kind(int kind, bool naive, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if (kind == SIGSVGD_STATIC_IMQ || kind == SIGSVGD_STATIC_RQ) {
+        if (naive) return hipErrorInvalidValue; // (the entry points refuse it before this)
+        return kind == SIGSVGD_STATIC_IMQ ? ring_launch_one<F, IO, false, true, SIGSVGD_STATIC_IMQ>(pl, stream, a)
+                                          : ring_launch_one<F, IO, false, true, SIGSVGD_STATIC_RQ>(pl, stream, a);
+    }
+    if (kind != SIGSVGD_STATIC_RBF) return hipErrorInvalidValue;
+    return naive ? ring_launch_one<F, IO, true, true, SIGSVGD_STATIC_RBF>(pl, stream, a)
+                 : ring_launch_one<F, IO, false, true, SIGSVGD_STATIC_RBF>(pl, stream, a);
+}
+template <typename F, typename Plan>
+int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    hipError_t e = dtype == SIGSVGD_F64 ? bw_launch_kind<F, double>(kind, naive, pl, stream, a)
+                                        : bw_launch_kind<F, float>(kind, naive, pl, stream, a);
+    if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+    return SIGSVGD_OK;
+}
 } // namespace
 
 // ---- workspace queries and launches; the argument checks are the entry points' (capi.hip) ----------------------------------
@@ -766,6 +838,14 @@ int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t
 {
     return ring_plan_total<Long2Plan>(bytes, [&](Long2Plan &pl) {
         return long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl);
+    });
+}
+// the two-sided bandwidth launch: the scratch also where neither coordinate gradient is wanted (the paired one's workspace is
+// pair_workspace's with the gradient: the scratch alone)
+int long2_h_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes)
+{
+    return ring_plan_total<Long2Plan>(bytes, [&](Long2Plan &pl) {
+        return long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl, true);
     });
 }
 int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes)
@@ -853,19 +933,42 @@ int pair_launch(const LongProblem &p)
     return ring_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
 }
 
+// The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
+// schedule (pair_bands.hip has no bandwidth pass) with the reverse sweep; gradX_out and gradY_out may both be NULL.
+int pair_h_launch(const LongProblem &p, void *dk_out)
+{
+    LongPlan pl;
+    PairHArgs a;
+    int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, 1, pl);
+    if (!rc) rc = long_args("pair", pl, p, 1, a);
+    if (rc) return rc;
+    a.gradX = p.gradX_out; a.gradY = p.gradY_out; a.dK_dinvh = dk_out;
+    return bw_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), pl, p.stream, a);
+}
+
+// The two-sided launch, with the bandwidth derivative where dk_out is given (dk_out[A][B] =
+// dK_ij / d inv_h; the reverse sweep then runs whatever gradients are wanted, and the plan of the gradients' slabs and tiles is
+// the one the launch without dk_out makes).
 // gradX_out and gradY_out both NULL: forward only.  Y_IS_X: A == B, TX == TY, no gradY_out; gradX_out then gets both sides of
 // every unordered pair.
-int long2_launch(const LongProblem &p)
+namespace {
+template <bool BW>
+int long2_launch_any(const LongProblem &p, void *dk_out)
 {
     const bool yx = long_yx(p), want_row = p.gradX_out != nullptr, want_col = p.gradY_out != nullptr || (yx && want_row);
     Long2Plan pl;
-    Long2Args a;
-    int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_row, p.gradY_out != nullptr, yx, pl);
+    std::conditional_t<BW, Long2HArgs, Long2Args> a;
+    int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_row, p.gradY_out != nullptr, yx, pl, BW);
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
     if (rc) return rc;
     a.colpart = long_colpart(pl, a);
     a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
-    rc = ring_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
+    if constexpr (BW) {
+        a.dK_dinvh = dk_out;
+        rc = bw_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), pl, p.stream, a);
+    } else {
+        rc = ring_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
+    }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,
                           "launch long2_reduce_kernel (rows)");
@@ -873,6 +976,9 @@ int long2_launch(const LongProblem &p)
         rc = long2_reduce(p, a.colpart, p.gradY_out, p.B, pl.nti, p.TY * p.d, 0, "launch long2_reduce_kernel (columns)");
     return rc;
 }
+} // namespace
+int long2_launch(const LongProblem &p) { return long2_launch_any<false>(p, nullptr); }
+int long2_h_launch(const LongProblem &p, void *dk_out) { return long2_launch_any<true>(p, dk_out); }
 
 // The share of rank `off` of `stride` (Y = X: B = A, TY = TX).  K_out gets the owned pairs and their mirror images, gradX_out
 // (fp64 whatever the dtype) is overwritten whole; a rank that owns no tile launches the reduction alone, which writes zeros.

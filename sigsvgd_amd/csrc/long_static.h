@@ -1,6 +1,7 @@
 // The built-in static kernels of the long-path route (DESIGN.md sections 5.10, 5.15), shared by the kernels of gram_long.hip
-// and pair_bands.hip: the kernel's value at a point of X (LDS, fp64) and a point of Y, and the gradient pass that chains a
-// pair's coarse S through the static kernel's derivative.
+// and pair_bands.hip: the kernel's value at a point of X (LDS, fp64) and a point of Y, the gradient pass that chains a
+// pair's coarse S through the static kernel's derivative, and the pass that chains it through the kernel's derivative in the
+// bandwidth (gram_long.hip only).
 #pragma once
 
 #include "ring_sweep.h"
@@ -203,6 +204,60 @@ __device__ __forceinline__ void static_grad_pass_one(const RingWave &rw, const I
                                          : accv[c]);
         }
     }
+}
+
+// The sum of v over the wavefront, the same bits in every lane: a butterfly whose adds have a fixed shape (lane l adds its
+// partner l ^ 32, then l ^ 16, ... l ^ 1; the two lanes of an exchange form the same sum, a + b and b + a).
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int m = kWave / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
+    return v;
+}
+
+// The pair's coarse S chained through the static kernel's derivative in the bandwidth: returns
+//   dK / d inv_h = - sum_{m,n} R[m][n] slope(dist inv_h) dist,   dist = |x_m - y_n|^2,
+// R = dG / w as in static_grad_pass and slope = exp(-s) (RBF) or radial_slope (the radial kinds): the contraction of
+// static_grad_pass<KIND, true> with the scalar dist in place of (x_m - y_n) -2 inv_h.  Lanes own points m of X, 63 per pass,
+// and walk the points n of Y; the 63 sums of a pass are added by wave_sum_f64 and the passes in order, so the bits depend on
+// the inputs alone.  Every lane returns the value.  The radial kinds and RBF only: the linear kernel has no bandwidth.
+template <int KIND, typename IO>
+__device__ __forceinline__ double static_bw_pass(const RingWave &rw, const IO *X, int M, const IO *Y, int N, int d,
+                                                 double inv_h)
+{
+    static_assert(KIND == SIGSVGD_STATIC_RBF || kRadialKind<KIND>, "the bandwidth pass is for the kernels of |x - y|^2 inv_h");
+    const int lane = threadIdx.x;
+    double total = 0.0;
+    for (int o0 = 0; o0 < M; o0 += kWave - 1) {
+        const int o = o0 - 1 + lane;
+        const bool valid = lane >= 1 && o < M;
+        const IO *xm = X + (size_t)min(max(o, 0), M - 1) * d;
+        double acc = 0.0;
+        double s_prev = 0.0, nb_prev = 0.0; // S at (o, t - 1), (o - 1, t - 1)
+        for (int t = 0; t < N; ++t) {
+            const int oc = min(max(o, 0), M - 2), tc = min(t, N - 2); // (read at a clamped block, then dropped)
+            const double s = ring_S(rw, oc, tc);
+            const double s_cur = o >= 0 && o < M - 1 && t < N - 1 ? s : 0.0;
+            const double nb = shfl_up_f64(s_cur); // S at (o - 1, t)
+            const double R = (nb_prev + s_cur) - (nb + s_prev); // dG / w
+            s_prev = s_cur;
+            nb_prev = nb;
+            const IO *yn = Y + (size_t)t * d;
+            double dist = 0.0;
+            for (int c = 0; c < d; ++c) {
+                const double u = (double)xm[c] - (double)yn[c];
+                dist = __builtin_fma(u, u, dist);
+            }
+            double rk;
+            if constexpr (kRadialKind<KIND>)
+                rk = R * radial_slope<KIND>(dist * inv_h);
+            else
+                rk = R * exp64(-dist * inv_h);
+            acc = __builtin_fma(rk, dist, acc);
+        }
+        total += wave_sum_f64(valid ? acc : 0.0);
+    }
+    return -total;
 }
 } // namespace
 } // namespace sigsvgd

@@ -362,6 +362,74 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     return K, gX, gY
 
 
+def gram_long_h_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                      want_gradX: bool = True, want_gradY: bool = True, naive: bool = False, y_is_x: bool = False) -> bool:
+    """Whether `gram_long_fwd_bwd_h` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
+    query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, per-wave
+    state beyond the LDS, or the first-order stencil with IMQ / rational quadratic); any other error raises."""
+    return _query("gram_long_h_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                                  1 if want_gradX else 0, 1 if want_gradY else 0,
+                                                  _flags(naive, False, y_is_x, False)), (ctypes.c_size_t(0),), may_refuse=True)
+
+
+def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                        grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
+                        y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True):
+    """(K[A,B], gX or None, gY or None, dK_dinvh[A,B]): `gram_long_fwd_bwd2` with every pair's derivative of K in the
+    static kernel's inverse bandwidth from the same reverse sweep (`sigsvgd_gram_long_fwd_bwd_h`, DESIGN.md section 5.16;
+    RBF, IMQ and rational quadratic).  dK_dinvh is unweighted -- grad_out and sym weight gX and gY only -- and with y_is_x
+    exactly symmetric; dK/dsigma = -inv_h^2 dK_dinvh.  K, gX and gY have the bits `gram_long_fwd_bwd2` returns.  Neither
+    gradient wanted: the reverse sweep still runs.  Bit-reproducible."""
+    dev = _require_gpu(X, Y, grad_out)
+    Xc, Yc = _prep_long(X, Y)
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    if (sym or y_is_x) and (A != B or TX != TY):
+        raise ValueError("sym and y_is_x need X and Y of one shape")
+    want_gradY = bool(want_gradY) and not (sym or y_is_x)
+    go = _weights(grad_out, (A, B), Xc.dtype)
+    flags = _flags(naive, sym, y_is_x, False)
+    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
+    dK = torch.empty((A, B), dtype=Xc.dtype, device=dev)
+    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
+    gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
+    _launch(dev, "gram_long_fwd_bwd_h", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                         int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX),
+                                         _ptr(gY), dK.data_ptr()),
+            "gram_long_h_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1 if want_gradX else 0,
+                                            1 if want_gradY else 0, flags))
+    return K, gX, gY, dK
+
+
+def pair_h_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                 naive: bool = False) -> bool:
+    """Whether `pair_fwd_bwd_h` takes pairs X [A, TX, d], Y [A, TY, d]: the library's workspace query, host only.  False
+    exactly where it reports SIGSVGD_E_UNSUPPORTED (as `gram_long_h_takes`); any other error raises."""
+    return _query("pair_h_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
+                                             _flags(naive, False, False, False)), (ctypes.c_size_t(0),), may_refuse=True)
+
+
+def pair_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
+                   grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True, want_y: bool = True):
+    """(K[A], gX or None, gY or None, dK_dinvh[A]): `pair_fwd_bwd` with each pair's derivative of K in the static kernel's
+    inverse bandwidth (`sigsvgd_pair_fwd_bwd_h`), unweighted; equal, bit for bit, to the diagonal of
+    `gram_long_fwd_bwd_h`'s.  K, gX and gY have the bits `pair_fwd_bwd` returns; neither gradient wanted is allowed.  Always
+    the one-wavefront schedule."""
+    dev = _require_gpu(X, Y, grad_out)
+    Xc, Yc = _prep_pair(X, Y)
+    (A, TX, d), TY = Xc.shape, Yc.shape[1]
+    go = _weights(grad_out, (A,), Xc.dtype)
+    flags = _flags(naive, False, False, False)
+    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
+    dK = torch.empty((A,), dtype=Xc.dtype, device=dev)
+    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
+    gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
+    _launch(dev, "pair_fwd_bwd_h", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
+                                    int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX), _ptr(gY),
+                                    dK.data_ptr()),
+            "pair_h_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), flags))
+    return K, gX, gY, dK
+
+
 def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] = None) -> torch.Tensor:
     """The element of rank `rank` (zero-based, ascending; default the lower median (n - 1) // 2, what `torch.median` returns)
     of the n = A B TX TY squared distances |X_ip - Y_jq|^2 between the points of X [A,TX,d] and Y [B,TY,d], as a 0-dim fp64

@@ -26,6 +26,16 @@ heuristic) takes its median from an exact select on the device (`ops.path_sqdist
 the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
 `Gram_matrix` and to the static kernel's own parameters.  The grid costs A*B*M*N elements of memory: large batches
 belong on the built-in kernels.  Objects without `Gram_matrix` raise NotImplementedError.
+
+Learning sigma.  Where the `sigma` of `RBFKernel`, `IMQStaticKernel` or `RationalQuadraticKernel` is a
+one-element tensor that requires grad (on any device) and grad mode is on, `compute_Gram` and `compute_kernel` -- and
+`compute_distance` / `compute_mmd` through them -- are autograd nodes that take sigma as an input: they run on the long route's
+bandwidth launches (`ops.gram_long_fwd_bwd_h`, `ops.pair_fwd_bwd_h`) whatever the shape, save every pair's dK/d(1/sigma) in
+forward and return grad_sigma = -(1/sigma)^2 sum(grad_output * dK/d(1/sigma)) without another launch, in the reference's GG
+convention (what upstream's autograd through its torch static kernels gives).  X and Y keep the rules above.  Shapes the long
+route refuses, and IMQ / rational quadratic with `_naive_solver=True`, raise NotImplementedError.  A float sigma, a tensor
+that does not require grad and `torch.no_grad()` take exactly the launches described above.  Data-dependent bandwidths (the
+median) stay detached, as in the reference.
 """
 from __future__ import annotations
 
@@ -56,6 +66,12 @@ class LinearKernel:
         return torch.einsum("ipk,jqk->ijpq", X, Y)
 
 
+def _sigma_value(sigma) -> float:
+    """sigma as a float; a tensor (also one that requires grad: SigKernel differentiates it) is read
+    detached"""
+    return float(sigma.detach()) if isinstance(sigma, torch.Tensor) else float(sigma)
+
+
 class RBFKernel:
     """k(x, y) = exp(-|x-y|^2 / sigma)   (sigkernel's convention: divide by sigma, not 2 sigma^2)."""
 
@@ -65,7 +81,7 @@ class RBFKernel:
         self.sigma = sigma
 
     def inv_bandwidth(self, X, Y) -> float:
-        return 1.0 / float(self.sigma)
+        return 1.0 / _sigma_value(self.sigma)
 
     def batch_kernel(self, X, Y):
         Xs = torch.sum(X**2, dim=2)
@@ -106,7 +122,7 @@ class IMQStaticKernel:
         self.sigma = sigma
 
     def inv_bandwidth(self, X, Y) -> float:
-        return 1.0 / float(self.sigma)
+        return 1.0 / _sigma_value(self.sigma)
 
     def batch_kernel(self, X, Y):
         return radial_power(batch_sqdist(X, Y), self.sigma, self.power)
@@ -314,6 +330,19 @@ def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
     return K, gX, gY
 
 
+def _scaled_ones(g_ones, gy_ones, grad_output):
+    """-> (gX, gY) from the unit-weight gradients speculated in forward where grad_output is uniform (an expanded scalar, or
+    equal entries: one host sync), each None where it was not speculated; (None, None) for any other grad_output"""
+    if g_ones is None and gy_ones is None:
+        return None, None
+    scalar = grad_output.reshape(-1)[:1]
+    # an expanded scalar (e.g. from K.sum().backward()) is uniform as it stands; anything else costs one host sync
+    if grad_output.stride() != (0, 0) and not bool((grad_output == scalar).all()):
+        return None, None
+    return (None if g_ones is None else g_ones * scalar.to(g_ones.dtype),
+            None if gy_ones is None else gy_ones * scalar.to(gy_ones.dtype))
+
+
 # ------------------------------------------------------------------------------------------------
 # autograd node
 # ------------------------------------------------------------------------------------------------
@@ -345,18 +374,7 @@ class _SigKernelGram(torch.autograd.Function):
     def backward(ctx, grad_output):
         X, Y = ctx.saved_tensors
         want_x, want_y = ctx.want
-        gX = gY = None
-        if ctx.g_ones is not None or ctx.gy_ones is not None:
-            scalar = None
-            if grad_output.stride() == (0, 0):  # expanded scalar, e.g. from K.sum().backward()
-                scalar = grad_output.reshape(-1)[:1]
-            else:
-                first = grad_output.reshape(-1)[:1]
-                if bool((grad_output == first).all()):  # one host sync; uniform weights => scale
-                    scalar = first
-            if scalar is not None:
-                gX = None if ctx.g_ones is None else ctx.g_ones * scalar.to(ctx.g_ones.dtype)
-                gY = None if ctx.gy_ones is None else ctx.gy_ones * scalar.to(ctx.gy_ones.dtype)
+        gX, gY = _scaled_ones(ctx.g_ones, ctx.gy_ones, grad_output)
         if gX is None and gY is None and (want_x or want_y):
             _, gX, gY = _solve_gram(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
         if gY is not None:
@@ -395,6 +413,99 @@ class _SigKernelPair(torch.autograd.Function):
         return gX, gY, None, None, None, None
 
 
+# ------------------------------------------------------------------------------------------------
+# a static-kernel sigma that requires grad
+# ------------------------------------------------------------------------------------------------
+def _learned_sigma(static_kernel):
+    """-> the static kernel's `sigma` where it is to be differentiated: one of this module's RBF / IMQ / rational-quadratic
+    kernels whose sigma is a one-element tensor that requires grad, with grad mode on.  None otherwise (a float, a plain
+    tensor, `torch.no_grad()`, any other static kernel): those calls take the launches they always took."""
+    if not isinstance(static_kernel, (RBFKernel, IMQStaticKernel)) or not torch.is_grad_enabled():
+        return None
+    sigma = getattr(static_kernel, "sigma", None)
+    if not isinstance(sigma, torch.Tensor) or not sigma.requires_grad:
+        return None
+    if sigma.numel() != 1:
+        raise ValueError(f"a static-kernel sigma that requires grad must have one element, got {tuple(sigma.shape)}")
+    return sigma
+
+
+def _sigma_grad(sigma_like, inv_h, grad_output, dK_dinvh):
+    """d sum(grad_output K) / d sigma from the saved per-pair dK / d inv_h (inv_h = 1 / sigma): no launch"""
+    g = -(inv_h * inv_h) * (grad_output.double() * dK_dinvh.double()).sum()
+    return g.to(device=sigma_like.device, dtype=sigma_like.dtype).reshape(sigma_like.shape)
+
+
+def _refused(what, X, Y, dyadic_order):
+    return NotImplementedError(
+        f"{what}: the gradient of a static-kernel sigma runs on the long route only (csrc/gram_long.hip), which refuses "
+        f"paths {tuple(X.shape)} x {tuple(Y.shape)} at dyadic order {dyadic_order}: {_lib.last_error()}")
+
+
+class _SigKernelGramSigma(torch.autograd.Function):
+    """`_SigKernelGram` with the static kernel's sigma as an input: every launch is the long route's bandwidth launch
+    (`ops.gram_long_fwd_bwd_h`), whose per-pair dK / d inv_h is saved in forward; backward returns
+    grad_sigma = -inv_h^2 sum(grad_output dK_dinvh) without a launch.  X and Y keep `_SigKernelGram`'s rules: the unit-weight
+    gradients are speculated in forward, a non-uniform grad_output takes one `ops.gram_long_fwd_bwd2` launch with the real
+    weights (the same bits as the bandwidth launch returns)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y):
+        ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
+        ctx.yx = y_is_x and not ctx.want[1]  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
+        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym)
+        ctx.y_dtype = Y.dtype
+        ctx.sigma_like = sigma.detach()
+        Xd, Yd = X.detach(), Y.detach()
+        spec = speculate and any(ctx.want)
+        K, ctx.g_ones, ctx.gy_ones, dK = ops.gram_long_fwd_bwd_h(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym,
+                                                                 ctx.yx, spec and ctx.want[0], spec and ctx.want[1])
+        ctx.save_for_backward(Xd, Yd, dK)
+        return K
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y, dK = ctx.saved_tensors
+        static_kind, inv_h, dyadic_order, naive, sym = ctx.cfg
+        want_x, want_y = ctx.want
+        gS = _sigma_grad(ctx.sigma_like, inv_h, grad_output, dK) if ctx.needs_input_grad[2] else None
+        gX, gY = _scaled_ones(ctx.g_ones, ctx.gy_ones, grad_output)
+        if gX is None and gY is None and (want_x or want_y):
+            _, gX, gY = ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym, ctx.yx,
+                                               want_x, want_y)
+        if gY is not None:
+            gY = gY.to(ctx.y_dtype)
+        return gX, gY, gS, None, None, None, None, None, None, None, None
+
+
+class _SigKernelPairSigma(torch.autograd.Function):
+    """`_SigKernelPair` with the static kernel's sigma as an input: one `ops.pair_fwd_bwd_h` launch in forward (unit weights,
+    the coordinate gradients needed, the per-pair dK / d inv_h), and a backward without launches."""
+
+    @staticmethod
+    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive):
+        want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.dtypes = (X.dtype, Y.dtype)
+        ctx.inv_h = inv_h
+        ctx.sigma_like = sigma.detach()
+        K, gX, gY, dK = ops.pair_fwd_bwd_h(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
+                                           want_y)
+        ctx.save_for_backward(gX, gY, dK)
+        return K
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gX1, gY1, dK = ctx.saved_tensors
+        gX = gY = gS = None
+        if gX1 is not None:
+            gX = (gX1 * grad_output.to(gX1.dtype)[:, None, None]).to(ctx.dtypes[0])
+        if gY1 is not None:
+            gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
+        if ctx.needs_input_grad[2]:
+            gS = _sigma_grad(ctx.sigma_like, ctx.inv_h, grad_output, dK)
+        return gX, gY, gS, None, None, None, None
+
+
 class SigKernel:
     """Signature kernel with a static kernel and a dyadic refinement order (PDE solver)."""
 
@@ -426,6 +537,14 @@ class SigKernel:
             # One device compare + scalar read-back (tens of microseconds) buys the symmetric solve: each
             # unordered pair once instead of every ordered pair, i.e. half the launch at these batch sizes.
             y_is_x = True
+        sigma = _learned_sigma(self.static_kernel)
+        if sigma is not None:  # the long route's bandwidth launch, whatever the shape
+            want_y = bool(grad_Y) and Y.requires_grad
+            if not ops.gram_long_h_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order,
+                                         static_kind, X.requires_grad, want_y, self._naive_solver, y_is_x and not want_y):
+                raise _refused("compute_Gram", X, Y, self.dyadic_order)
+            return _SigKernelGramSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver,
+                                             bool(sym), y_is_x, self.speculate_ones, bool(grad_Y))
         return _SigKernelGram.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver, bool(sym),
                                     y_is_x, self.speculate_ones, bool(grad_Y))
 
@@ -444,6 +563,12 @@ class SigKernel:
         if static_kind is None and hasattr(self.static_kernel, "batch_kernel"):
             G = self.static_kernel.batch_kernel(X, Y)
             return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
+        sigma = None if static_kind is None else _learned_sigma(self.static_kernel)
+        if sigma is not None:  # the paired bandwidth launch, whatever the shape
+            if not ops.pair_h_takes(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind,
+                                    self._naive_solver):
+                raise _refused("compute_kernel", X, Y, self.dyadic_order)
+            return _SigKernelPairSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver)
         if static_kind is not None:
             want_grad = torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)
             if _pair_route(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], static_kind, self.dyadic_order, want_grad,
