@@ -114,6 +114,13 @@ extern "C" {
  * SIGSVGD_FLAG_NAIVE_SOLVER with them is SIGSVGD_E_UNSUPPORTED there.  sigsvgd_gram_sym_partial stays RBF-only. */
 #define SIGSVGD_STATIC_IMQ 2    /* k(x,y) = (1 + s)^(-1/2)          (inverse multiquadric)     */
 #define SIGSVGD_STATIC_RQ 3     /* k(x,y) = (1 + s)^(-1)            (rational quadratic)       */
+/* The Matern kinds, accepted by a later revision of ABI 10 (again no new symbol and no changed
+ * signature: an earlier library answers SIGSVGD_E_BADARG).  Same s and the same routes, refusals and workspace figures as IMQ / RQ above; a Matern kernel of lengthscale l
+ * is inv_h = 1 / l^2.  s is clamped at 0 before the square root, and -dk/ds is finite at s = 0 (3/2 and 5/6), so coincident
+ * points contribute a zero gradient term.  Kinds 4 and 5 are reserved and stay SIGSVGD_E_BADARG.  Matern-1/2 (exp(-sqrt(s)),
+ * whose slope is unbounded at 0) is not provided.  The sigsvgd_*_h entry points take both kinds. */
+#define SIGSVGD_STATIC_MATERN32 6 /* k(x,y) = (1 + u) exp(-u),           u = sqrt(3 s);  -dk/ds = (3/2) exp(-u)         */
+#define SIGSVGD_STATIC_MATERN52 7 /* k(x,y) = (1 + u + u^2/3) exp(-u),   u = sqrt(5 s);  -dk/ds = (5/6) (1 + u) exp(-u) */
 
 /* vector kernels (sigsvgd_vec_kernel) */
 #define SIGSVGD_VEC_GAUSSIAN 0 /* k = exp(-sq / (2 h^2))          src/kernels/_kernels.py:106 */

@@ -1,11 +1,12 @@
 """A/B of the coverage kernel's RBF launch between two builds of libsigsvgd_hip.so, interleaved on one device as scripts/ab.py
-does, with a bit comparison of what the RBF and linear kernels return on every entry point that takes a static kernel.
+does, with a bit comparison of what the RBF, linear, IMQ and rational-quadratic kernels return on every entry point that takes a
+static kernel (the kinds both builds have; IMQ and RQ without the first-order stencil on the long route, which has none for them).
 
     python scripts/static_kinds_ab.py parent.so branch.so [rounds=6]
 
 Every run is a process of its own under SIGSVGD_LIB_PATH.  It times ops.gram_fwd_bwd(X, X, 1.0, 0, y_is_x=True,
 force_generic=True) at N = 256, T = 64, d = 7 (median of 10 launches with device events after warm-up) and saves the RBF and
-linear outputs of the fused, long, two-sided, paired and partial launches.  Prints the series, range and median per library,
+other kinds' outputs of the fused, long, two-sided, paired, partial and bandwidth launches.  Prints the series, range and median per library,
 and whether every saved tensor of the last library equals the first's bit for bit."""
 import os
 import statistics
@@ -32,7 +33,7 @@ def child(out_path):
     S = O.synthetic_inputs(24, 64, 7)[0].to(dev)
     out["smoke_shape"] = ops.gram_fwd_bwd(S, S, 1.0, 0, y_is_x=True)
     W = torch.as_tensor(O.synthetic_inputs(6, 6, 1, seed_x=3)[0][..., 0], dtype=torch.float64, device=dev)
-    for kind in (0, 1):
+    for kind in (0, 1, 2, 3):
         for (T, d, n) in [(20, 3, 2), (70, 17, 0), (128, 14, 0)]:
             A, B = O.synthetic_inputs(6, T, d)[0].double().to(dev), O.synthetic_inputs(6, T, d, seed_x=5)[0].double().to(dev)
             out[f"generic k{kind} {T} {d} {n}"] = ops.gram_fwd_bwd(A, B, 1.0, n, kind, W, force_generic=True)
@@ -42,7 +43,7 @@ def child(out_path):
         out[f"generic yx k{kind}"] = ops.gram_fwd_bwd(big, big, 1.0, 0, kind, y_is_x=True, force_generic=True)
         for (TX, TY, d, n) in [(70, 66, 3, 0), (9, 12, 17, 2), (300, 300, 2, 0)]:
             A, B = O.synthetic_inputs(6, TX, d)[0].double().to(dev), O.synthetic_inputs(6, TY, d, seed_x=5)[0].double().to(dev)
-            for naive in (False, True):
+            for naive in ((False, True) if kind < 2 else (False,)):
                 out[f"long k{kind} {TX} {d} {n} {naive}"] = ops.gram_long_fwd_bwd(A, B, 1.0, n, kind, W, naive)
                 out[f"long2 k{kind} {TX} {d} {n} {naive}"] = ops.gram_long_fwd_bwd2(A, B, 1.0, n, kind, W, naive)
                 out[f"pair k{kind} {TX} {d} {n} {naive}"] = ops.pair_fwd_bwd(A, B, 1.0, n, kind, W[0].contiguous(), naive)
@@ -50,6 +51,9 @@ def child(out_path):
             if TX == TY:
                 out[f"long2 yx k{kind} {TX}"] = ops.gram_long_fwd_bwd2(A, A, 1.0, n, kind, W, y_is_x=True)[:2]
                 out[f"partial k{kind} {TX}"] = ops.gram_long_sym_partial(A, 1.0, 1, 2, n, kind, W, fold=True)
+            if kind != 1:  # (the linear kernel has no bandwidth)
+                out[f"long h k{kind} {TX} {d} {n}"] = ops.gram_long_fwd_bwd_h(A, B, 1.0, n, kind, W)
+                out[f"pair h k{kind} {TX} {d} {n}"] = ops.pair_fwd_bwd_h(A, B, 1.0, n, kind, W[0].contiguous())
     torch.cuda.synchronize()
     torch.save({k: tuple(t.cpu() for t in v) for k, v in out.items()}, out_path)
     print(f"MS {ms:.4f}")
@@ -77,7 +81,7 @@ def main():
             print(f"{lib}: {min(v):.4f} .. {max(v):.4f} (range {max(v) - min(v):.4f}), median {statistics.median(v):.4f}")
         first, last = torch.load(os.path.join(tmp, "0.pt")), torch.load(os.path.join(tmp, f"{len(libs) - 1}.pt"))
         bad = [k for k in first if not all(torch.equal(a, b) for a, b in zip(first[k], last[k]))]
-        print(f"bit comparison of {len(first)} RBF / linear launches, {libs[0]} against {libs[-1]}: "
+        print(f"bit comparison of {len(first)} RBF / linear / IMQ / RQ launches, {libs[0]} against {libs[-1]}: "
               + ("all equal" if not bad and first.keys() == last.keys() else f"DIFFERENT: {bad}"))
         sys.exit(1 if bad else 0)
 

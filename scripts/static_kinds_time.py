@@ -4,7 +4,7 @@
 
 Prints one JSON line per shape: milliseconds per Gram + gradient launch, [median, min, max] of `reps` timed with device
 events after warm-up, for RBF (the yardstick; on the coverage kernel with force_generic=True, since RBF alone has the
-fp32-sweep kernels), IMQ and the rational quadratic kernel:
+fp32-sweep kernels), IMQ, the rational quadratic kernel and the two Matern kernels:
   coverage kernel  N = 100, T = 10, d = 2, order 4 and N = 256, T = 64, d = 7, order 0: ops.gram_fwd_bwd(X, X, y_is_x=True);
   long route       A = B = 32, T = 512, d = 4, order 0: ops.gram_long_fwd_bwd(X, X).
 Next to the first shape: the user route of the same IMQ kernel (torch builds the [N, N, T, T] grid, sig_pde.hip solves it,
@@ -22,7 +22,8 @@ from sigsvgd_amd import _lib, ops  # noqa: E402
 import sigsvgd_amd.sigkernel as sk  # noqa: E402
 from long_time import timed  # noqa: E402
 
-KINDS = {"rbf": _lib.STATIC_RBF, "imq": _lib.STATIC_IMQ, "rq": _lib.STATIC_RQ}
+KINDS = {"rbf": _lib.STATIC_RBF, "imq": _lib.STATIC_IMQ, "rq": _lib.STATIC_RQ, "matern32": _lib.STATIC_MATERN32,
+         "matern52": _lib.STATIC_MATERN52}
 
 
 class _GramOnlyIMQ:

@@ -90,11 +90,31 @@ static bool no_bytes(const size_t *bytes)
 }
 
 // the static kernels the library evaluates itself, and those of them that are functions of |x - y|^2 inv_h (inv_h > 0)
-static bool static_kind_known(int kind) { return kind >= SIGSVGD_STATIC_RBF && kind <= SIGSVGD_STATIC_RQ; }
+// (an explicit set: the values 4 and 5 between the rational quadratic and the Matern kinds are reserved and refused)
+static bool static_kind_known(int kind)
+{
+    switch (kind) {
+    case SIGSVGD_STATIC_RBF:
+    case SIGSVGD_STATIC_LINEAR:
+    case SIGSVGD_STATIC_IMQ:
+    case SIGSVGD_STATIC_RQ:
+    case SIGSVGD_STATIC_MATERN32:
+    case SIGSVGD_STATIC_MATERN52: return true;
+    default: return false;
+    }
+}
 static bool static_kind_radial(int kind) { return static_kind_known(kind) && kind != SIGSVGD_STATIC_LINEAR; }
+// the kinds that have fp64 kernels only, with the default stencil only on the long-path route (DESIGN.md sections 5.15, 5.17)
+static bool static_kind_fp64_only(int kind) { return static_kind_radial(kind) && kind != SIGSVGD_STATIC_RBF; }
 static const char *static_kind_name(int kind)
 {
-    return kind == SIGSVGD_STATIC_RBF ? "RBF" : kind == SIGSVGD_STATIC_IMQ ? "IMQ" : "rational-quadratic";
+    switch (kind) {
+    case SIGSVGD_STATIC_RBF: return "RBF";
+    case SIGSVGD_STATIC_IMQ: return "IMQ";
+    case SIGSVGD_STATIC_MATERN32: return "Matern-3/2";
+    case SIGSVGD_STATIC_MATERN52: return "Matern-5/2";
+    default: return "rational-quadratic";
+    }
 }
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
@@ -127,7 +147,7 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
 
 // The checks of the long-path entry points (gram_long.hip), each condition in one place.  check_long: the Gram mode's, which
 // every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
-// know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ and rational quadratic), SIGSVGD_FLAG_SYM
+// know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_SYM
 // (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, every other bit is refused.
 static int check_long(const LongProblem &p, bool launch)
 {
@@ -145,8 +165,8 @@ static int check_long(const LongProblem &p, bool launch)
     if (launch && p.dtype != SIGSVGD_F32 && p.dtype != SIGSVGD_F64) return bad_arg("gram_long: bad dtype %d", p.dtype);
     if (launch && static_kind_radial(p.kind) && !(p.inv_h > 0.0))
         return bad_arg("gram_long: %s static kernel needs inv_h > 0 (got %g)", static_kind_name(p.kind), p.inv_h);
-    // (the long-path kernels are built with the default stencil only for the two newer kinds: DESIGN.md section 5.15)
-    if ((p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) && (p.kind == SIGSVGD_STATIC_IMQ || p.kind == SIGSVGD_STATIC_RQ)) {
+    // (the long-path kernels are built with the default stencil only for the newer kinds: DESIGN.md sections 5.15, 5.17)
+    if ((p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) && static_kind_fp64_only(p.kind)) {
         set_error("gram_long: SIGSVGD_FLAG_NAIVE_SOLVER is not built for the %s static kernel on the long-path route "
                   "(default stencil only)", static_kind_name(p.kind));
         return SIGSVGD_E_UNSUPPORTED;
@@ -197,7 +217,7 @@ static int check_pair(const LongProblem &p, bool launch)
 static int check_bandwidth(const char *who, const LongProblem &p, bool launch, const void *dK_dinvh_out)
 {
     if (!static_kind_radial(p.kind))
-        return bad_arg("%s: the linear static kernel has no bandwidth (SIGSVGD_STATIC_RBF, _IMQ or _RQ)", who);
+        return bad_arg("%s: the linear static kernel has no bandwidth (SIGSVGD_STATIC_RBF, _IMQ, _RQ, _MATERN32 or _MATERN52)", who);
     if (launch && !dK_dinvh_out) return bad_arg("%s: dK_dinvh_out == NULL", who);
     return SIGSVGD_OK;
 }
@@ -298,9 +318,10 @@ static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigne
 {
     const bool fp32 = kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
     if (flags & SIGSVGD_FLAG_FORCE_GENERIC) return GramRoute::GenericPrecise;
-    // IMQ and the rational quadratic kernel have fp64 kernels only and are held to fp64 results: the plan that keeps the
-    // increments in fp64 wherever their table (or the per-band layout) fits, what FORCE_GENERIC selects
-    if (!partial && (kind == SIGSVGD_STATIC_IMQ || kind == SIGSVGD_STATIC_RQ)) return GramRoute::GenericPrecise;
+    // IMQ, the rational quadratic and the Matern kernels have fp64 kernels only and are held to fp64 results: the plan that keeps
+    // the increments in fp64 wherever their table (or the per-band layout) fits, what FORCE_GENERIC selects (DESIGN.md sections
+    // 5.15, 5.17)
+    if (!partial && static_kind_fp64_only(kind)) return GramRoute::GenericPrecise;
     if (!partial && fp32 && want_grad && d == 1 && n == 0 && T >= 3 && T <= 128) return GramRoute::GenericOneChannel;
     if (fp32 && fast_supported(T, d, n)) return GramRoute::Fast;
     if (fp32 && quad_supported(T, d, n)) return GramRoute::Quad;

@@ -45,19 +45,25 @@ struct GenericArgs {
 };
 
 // The radial static kernels k = phi(s), s = |x - y|^2 inv_h, from the argument t = -s the kernel forms for RBF's exponential
-// (DESIGN.md section 5.15).  NEWKIND is gram_generic_kernel's compile-time parameter: false is RBF (and the linear kernel, which
-// never gets here) with the code it always had, true is IMQ or the rational quadratic kernel, told apart by the wave-uniform
-// `kind`.  radial_k: phi; radial_slope: -phi'(s), RBF's exp(-s) in the gradient contraction (IMQ: k^3 / 2, RQ: k^2).
-template <bool NEWKIND>
+// (DESIGN.md sections 5.15, 5.17).  NEWKIND is gram_generic_kernel's compile-time parameter: 0 is RBF (and the linear kernel,
+// which never gets here) with the code it always had, 1 is IMQ or the rational quadratic kernel and 2 is Matern-3/2 or -5/2, the
+// two of a value told apart by the wave-uniform `kind`.  radial_k: phi; radial_slope: -phi'(s), RBF's exp(-s) in the gradient
+// contraction (IMQ: k^3 / 2, RQ: k^2).  The Matern kinds take the square root of -t clamped at 0 (matern_u): t is
+// (2 dot - xn - yn) inv_h, which rounding leaves a few ulp above 0 for coincident points.
+template <int NEWKIND>
 __device__ __forceinline__ double radial_k(int kind, double t)
 {
     if constexpr (!NEWKIND) return exp64(t);
+    if constexpr (NEWKIND == 2)
+        return matern_phi(kind == SIGSVGD_STATIC_MATERN32, matern_u(kind == SIGSVGD_STATIC_MATERN32, -t));
     return kind == SIGSVGD_STATIC_IMQ ? rsqrt(1.0 - t) : 1.0 / (1.0 - t);
 }
-template <bool NEWKIND>
+template <int NEWKIND>
 __device__ __forceinline__ double radial_slope(int kind, double t)
 {
     if constexpr (!NEWKIND) return exp64(t);
+    if constexpr (NEWKIND == 2)
+        return matern_slope(kind == SIGSVGD_STATIC_MATERN32, matern_u(kind == SIGSVGD_STATIC_MATERN32, -t));
     const double k = radial_k<NEWKIND>(kind, t);
     return kind == SIGSVGD_STATIC_IMQ ? 0.5 * (k * k * k) : k * k;
 }
@@ -88,9 +94,9 @@ __host__ __device__ inline size_t generic_lds_bytes(int T, int d, int n, int wan
 // a small remainder of much larger values and inherits ~3e-7 .. 3e-6 (T = 64 .. 128) of their ratio to it from the rounded
 // increments, whatever the precision of the sweeps.  double wherever the table fits next to the rest (always for the
 // reference's own shapes; the fp64 pass over flagged pairs and force_generic whenever 160 KB allow).
-// NEWKIND: the static kernel is IMQ or the rational quadratic (a.kind says which); false: RBF or linear, the instantiations
-// the kernel had before those kinds, instruction for instruction.
-template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, bool NEWKIND = false>
+// NEWKIND: 1: the static kernel is IMQ or the rational quadratic, 2: Matern-3/2 or -5/2 (a.kind says which of the two); 0: RBF
+// or linear, the instantiations the kernel had before those kinds, instruction for instruction.
+template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, int NEWKIND = 0>
 __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
     const int T = a.T, d = a.d, dp = a.dp, Tm = a.Tm, TmS = a.TmS, P = a.P, n = a.n, r = a.r;
     constexpr bool naive = NAIVE;
     const int kind = a.kind;
-    const bool radial = NEWKIND || a.kind == SIGSVGD_STATIC_RBF; // RBF, IMQ, rational quadratic: functions of |x - y|^2 inv_h
+    const bool radial = NEWKIND != 0 || a.kind == SIGSVGD_STATIC_RBF; // RBF, IMQ, RQ, Matern: functions of |x - y|^2 inv_h
 
     double *xs = reinterpret_cast<double *>(smem_raw);
     double *ys = xs + (size_t)T * dp;
@@ -601,7 +607,7 @@ int generic_plan(int A, int B, int T, int d, int n, int want_grad, bool sym, boo
 }
 
 namespace {
-template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, bool NEWKIND>
+template <typename IO, bool NAIVE, bool GRAD, bool BIG, typename DT, int NEWKIND>
 hipError_t generic_launch_one(const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     // (the largest size any plan can ask for)
@@ -610,7 +616,7 @@ hipError_t generic_launch_one(const GenericPlan &pl, hipStream_t stream, const G
     hipLaunchKernelGGL((gram_generic_kernel<IO, NAIVE, GRAD, BIG, DT, NEWKIND>), dim3(pl.grid), dim3(kWave), pl.lds, stream, a);
     return hipSuccess;
 }
-template <typename IO, bool NAIVE, typename DT, bool NEWKIND>
+template <typename IO, bool NAIVE, typename DT, int NEWKIND>
 hipError_t generic_dispatch2(bool grad, bool big, const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     if constexpr (sizeof(DT) == 8) { // (the long-path layout is fp64 only: make_plan)
@@ -618,7 +624,7 @@ hipError_t generic_dispatch2(bool grad, bool big, const GenericPlan &pl, hipStre
     }
     return grad ? generic_launch_one<IO, NAIVE, true, false, DT, NEWKIND>(pl, stream, a) : generic_launch_one<IO, NAIVE, false, false, DT, NEWKIND>(pl, stream, a);
 }
-template <typename IO, bool NEWKIND>
+template <typename IO, int NEWKIND>
 hipError_t generic_dispatch1(bool naive, bool grad, bool big, const GenericPlan &pl, hipStream_t stream, const GenericArgs &a)
 {
     if (pl.dd)
@@ -628,9 +634,11 @@ hipError_t generic_dispatch1(bool naive, bool grad, bool big, const GenericPlan 
 hipError_t generic_dispatch(bool f64, bool naive, bool grad, bool big, const GenericPlan &pl, hipStream_t stream,
                             const GenericArgs &a)
 {
+    if (a.kind == SIGSVGD_STATIC_MATERN32 || a.kind == SIGSVGD_STATIC_MATERN52)
+        return f64 ? generic_dispatch1<double, 2>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, 2>(naive, grad, big, pl, stream, a);
     if (a.kind == SIGSVGD_STATIC_IMQ || a.kind == SIGSVGD_STATIC_RQ)
-        return f64 ? generic_dispatch1<double, true>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, true>(naive, grad, big, pl, stream, a);
-    return f64 ? generic_dispatch1<double, false>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, false>(naive, grad, big, pl, stream, a);
+        return f64 ? generic_dispatch1<double, 1>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, 1>(naive, grad, big, pl, stream, a);
+    return f64 ? generic_dispatch1<double, 0>(naive, grad, big, pl, stream, a) : generic_dispatch1<float, 0>(naive, grad, big, pl, stream, a);
 }
 } // namespace
 

@@ -40,6 +40,9 @@
 // gradient passes, static_bw_pass (long_static.h), which contracts the same S with the static kernel's derivative in inv_h and
 // stores the pair's dK / d inv_h, unweighted.  A compile-time flag: the instantiations without it are the code they were.
 //
+// The Matern kinds are instantiated in gram_long_matern.hip, which includes this file for its kernels
+// and families (long_matern_launch below); family_launch sends their launches there.
+//
 // The per-pair solve (staging, fill, forward sweep, K store, reverse sweep) is written out in each of the three kernels, and K's
 // bit-identity across the modes rests on the copies staying equal.  One shared function (long_solve_pair over a PairSource, with
 // one two_sided_grad block) gave the same bits and the same registers, scratch and occupancy, but was measured slower on the
@@ -450,6 +453,109 @@ __global__ __launch_bounds__(64) void gram_long_part_kernel(PartArgs a)
     }
 }
 
+namespace {
+// the kernel families of this file for ring_launch (ring_sweep.h); id: the family's number in long_matern_launch, bandwidth: a
+// family of the bandwidth launches (always the reverse sweep, kinds that have a bandwidth)
+template <bool PAIRED>
+struct LongFamily {
+    using Args = std::conditional_t<PAIRED, PairArgs, LongArgs>;
+    static constexpr bool has_kind = true, has_fwd_only = true, bandwidth = false;
+    static constexpr int id = PAIRED ? 1 : 0;
+    static constexpr const char *attr_failed = PAIRED ? "hipFuncSetAttribute(gram_long paired)"
+                                                      : "hipFuncSetAttribute(gram_long)";
+    static constexpr const char *launch_failed = PAIRED ? "launch gram_long_kernel (paired)" : "launch gram_long_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>; }
+};
+struct Long2Family {
+    using Args = Long2Args;
+    static constexpr bool has_kind = true, has_fwd_only = true, bandwidth = false;
+    static constexpr int id = 2;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2)", *launch_failed = "launch gram_long2_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, GRAD, KIND>; }
+};
+// the bandwidth launches (always with the reverse sweep; RBF and the radial kinds: bw_launch below names their instantiations)
+struct PairHFamily {
+    using Args = PairHArgs;
+    static constexpr bool bandwidth = true;
+    static constexpr int id = 3;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long paired, bandwidth)",
+                                *launch_failed = "launch gram_long_kernel (paired, bandwidth)";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, true, KIND, true, true>; }
+};
+struct Long2HFamily {
+    using Args = Long2HArgs;
+    static constexpr bool bandwidth = true;
+    static constexpr int id = 4;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2, bandwidth)",
+                                *launch_failed = "launch gram_long2_kernel (bandwidth)";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, true, KIND, true>; }
+};
+struct PartFamily { // (always with the gradient)
+    using Args = PartArgs;
+    static constexpr bool has_kind = true, has_fwd_only = false, bandwidth = false;
+    static constexpr int id = 5;
+    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long_part)",
+                                *launch_failed = "launch gram_long_part_kernel";
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel()
+    {
+        static_assert(GRAD, "gram_long_part_kernel has no forward-only form");
+        return &gram_long_part_kernel<IO, NAIVE, KIND>;
+    }
+};
+} // namespace
+
+// The Matern kinds' instantiations of every family above compile in a translation unit of their own,
+// gram_long_matern.hip, which includes this file with SIGSVGD_GRAM_LONG_MATERN defined and builds the kernels, the families and
+// this one function: the launch of family `family` (F::id) at the plan's grid and LDS bytes, default stencil only; args: the
+// family's F::Args.  Everything else of this file is the other translation unit's.
+hipError_t long_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                              const void *args);
+#ifdef SIGSVGD_GRAM_LONG_MATERN
+namespace {
+struct MaternPlan {
+    int grid;
+    size_t lds;
+};
+template <typename F, typename IO>
+hipError_t matern_launch_io(int kind, bool grad, const MaternPlan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if constexpr (F::bandwidth)
+        return kind == SIGSVGD_STATIC_MATERN32 ? ring_launch_one<F, IO, false, true, SIGSVGD_STATIC_MATERN32>(pl, stream, a)
+                                               : ring_launch_one<F, IO, false, true, SIGSVGD_STATIC_MATERN52>(pl, stream, a);
+    else
+        return kind == SIGSVGD_STATIC_MATERN32 ? ring_launch_solver<F, IO, SIGSVGD_STATIC_MATERN32>(false, grad, pl, stream, a)
+                                               : ring_launch_solver<F, IO, SIGSVGD_STATIC_MATERN52>(false, grad, pl, stream, a);
+}
+template <typename F>
+hipError_t matern_launch_family(int dtype, int kind, bool grad, const MaternPlan &pl, hipStream_t stream, const void *args)
+{
+    const typename F::Args &a = *static_cast<const typename F::Args *>(args);
+    return dtype == SIGSVGD_F64 ? matern_launch_io<F, double>(kind, grad, pl, stream, a)
+                                : matern_launch_io<F, float>(kind, grad, pl, stream, a);
+}
+} // namespace
+hipError_t long_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                              const void *args)
+{
+    if (kind != SIGSVGD_STATIC_MATERN32 && kind != SIGSVGD_STATIC_MATERN52) return hipErrorInvalidValue;
+    const MaternPlan pl{grid, lds};
+    switch (family) {
+    case LongFamily<false>::id: return matern_launch_family<LongFamily<false>>(dtype, kind, grad, pl, stream, args);
+    case LongFamily<true>::id: return matern_launch_family<LongFamily<true>>(dtype, kind, grad, pl, stream, args);
+    case Long2Family::id: return matern_launch_family<Long2Family>(dtype, kind, grad, pl, stream, args);
+    case PairHFamily::id: return matern_launch_family<PairHFamily>(dtype, kind, grad, pl, stream, args);
+    case Long2HFamily::id: return matern_launch_family<Long2HFamily>(dtype, kind, grad, pl, stream, args);
+    case PartFamily::id: return matern_launch_family<PartFamily>(dtype, kind, grad, pl, stream, args);
+    }
+    return hipErrorInvalidValue;
+}
+#else
+
 // grad_partial[k][e] (fp64, whatever the I/O dtype) = row k's column-side slabs in the order of the owned tiles, then, where
 // the launch owns k's tile, its row-side slabs in chunk order; slabs no pair wrote are skipped (the column side of a tile's
 // first row; chunks that end at or before the diagonal), and a row that received nothing gets zero.  One block per row.
@@ -734,52 +840,6 @@ bool long_naive(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAIVE_SOL
 bool long_yx(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_Y_IS_X) != 0; }
 bool long_fold(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_FOLD_TILES) != 0; }
 
-// the kernel families of this file for ring_launch (ring_sweep.h)
-template <bool PAIRED>
-struct LongFamily {
-    using Args = std::conditional_t<PAIRED, PairArgs, LongArgs>;
-    static constexpr bool has_kind = true, has_fwd_only = true;
-    static constexpr const char *attr_failed = PAIRED ? "hipFuncSetAttribute(gram_long paired)"
-                                                      : "hipFuncSetAttribute(gram_long)";
-    static constexpr const char *launch_failed = PAIRED ? "launch gram_long_kernel (paired)" : "launch gram_long_kernel";
-    template <typename IO, bool NAIVE, bool GRAD, int KIND>
-    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, GRAD, KIND, PAIRED>; }
-};
-struct Long2Family {
-    using Args = Long2Args;
-    static constexpr bool has_kind = true, has_fwd_only = true;
-    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2)", *launch_failed = "launch gram_long2_kernel";
-    template <typename IO, bool NAIVE, bool GRAD, int KIND>
-    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, GRAD, KIND>; }
-};
-// the bandwidth launches (always with the reverse sweep; RBF and the radial kinds: bw_launch below names their instantiations)
-struct PairHFamily {
-    using Args = PairHArgs;
-    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long paired, bandwidth)",
-                                *launch_failed = "launch gram_long_kernel (paired, bandwidth)";
-    template <typename IO, bool NAIVE, bool GRAD, int KIND>
-    static constexpr auto kernel() { return &gram_long_kernel<IO, NAIVE, true, KIND, true, true>; }
-};
-struct Long2HFamily {
-    using Args = Long2HArgs;
-    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long2, bandwidth)",
-                                *launch_failed = "launch gram_long2_kernel (bandwidth)";
-    template <typename IO, bool NAIVE, bool GRAD, int KIND>
-    static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, true, KIND, true>; }
-};
-struct PartFamily { // (always with the gradient)
-    using Args = PartArgs;
-    static constexpr bool has_kind = true, has_fwd_only = false;
-    static constexpr const char *attr_failed = "hipFuncSetAttribute(gram_long_part)",
-                                *launch_failed = "launch gram_long_part_kernel";
-    template <typename IO, bool NAIVE, bool GRAD, int KIND>
-    static constexpr auto kernel()
-    {
-        static_assert(GRAD, "gram_long_part_kernel has no forward-only form");
-        return &gram_long_part_kernel<IO, NAIVE, KIND>;
-    }
-};
-
 // out (the launch's dtype) = the sums of `rows` rows' slabs, long2_reduce_kernel
 int long2_reduce(const LongProblem &p, const double *partials, void *out, int rows, int nslabs, int TD, int skip,
                  const char *what)
@@ -814,6 +874,23 @@ int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t strea
 {
     hipError_t e = dtype == SIGSVGD_F64 ? bw_launch_kind<F, double>(kind, naive, pl, stream, a)
                                         : bw_launch_kind<F, float>(kind, naive, pl, stream, a);
+    if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+    e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+    return SIGSVGD_OK;
+}
+// the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations
+template <typename F, typename Plan>
+int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if (kind != SIGSVGD_STATIC_MATERN32 && kind != SIGSVGD_STATIC_MATERN52) {
+        if constexpr (F::bandwidth)
+            return bw_launch<F>(dtype, kind, naive, pl, stream, a);
+        else
+            return ring_launch<F>(dtype, kind, naive, grad, pl, stream, a);
+    }
+    // (the entry points refuse NAIVE_SOLVER with these kinds before this)
+    hipError_t e = naive ? hipErrorInvalidValue : long_matern_launch(F::id, dtype, kind, grad, pl.grid, pl.lds, stream, &a);
     if (e != hipSuccess) return hip_fail(e, F::attr_failed);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, F::launch_failed);
@@ -872,7 +949,7 @@ int long_launch(const LongProblem &p)
     LongArgs a;
     int rc = long_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
-    if (!rc) rc = ring_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
+    if (!rc) rc = family_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
     if (!rc && want_grad) // a row's slabs in chunk order
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, pl.nchunks, p.TX * p.d, 0, "launch long2_reduce_kernel (rows)");
     return rc;
@@ -930,7 +1007,7 @@ int pair_launch(const LongProblem &p)
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
     if (pair_use_bands(p.A, pl, bp)) return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
-    return ring_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
 }
 
 // The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
@@ -943,7 +1020,7 @@ int pair_h_launch(const LongProblem &p, void *dk_out)
     if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
     a.gradX = p.gradX_out; a.gradY = p.gradY_out; a.dK_dinvh = dk_out;
-    return bw_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), pl, p.stream, a);
+    return family_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
 }
 
 // The two-sided launch, with the bandwidth derivative where dk_out is given (dk_out[A][B] =
@@ -965,9 +1042,9 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
     a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
     if constexpr (BW) {
         a.dK_dinvh = dk_out;
-        rc = bw_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), pl, p.stream, a);
+        rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
     } else {
-        rc = ring_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
+        rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
     }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,
@@ -991,7 +1068,7 @@ int long_part_launch(const LongProblem &p, int off, int stride)
     if (rc) return rc;
     a.colpart = long_colpart(pl, a);
     a.tm = pl.tm; a.R = pl.R; a.nfull = pl.nfull;
-    if (pl.items > 0) rc = ring_launch<PartFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
+    if (pl.items > 0) rc = family_launch<PartFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
     if (rc) return rc;
     hipLaunchKernelGGL(long_part_reduce_kernel, dim3(p.A), dim3(256), 0, p.stream, a.partials, a.colpart,
                        static_cast<double *>(p.gradX_out), p.A, p.TX * p.d, pl.R, pl.JC, pl.tm);
@@ -1000,4 +1077,5 @@ int long_part_launch(const LongProblem &p, int off, int stride)
     return SIGSVGD_OK;
 }
 
+#endif // SIGSVGD_GRAM_LONG_MATERN
 } // namespace sigsvgd

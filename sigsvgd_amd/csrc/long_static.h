@@ -1,4 +1,4 @@
-// The built-in static kernels of the long-path route (DESIGN.md sections 5.10, 5.15), shared by the kernels of gram_long.hip
+// The built-in static kernels of the long-path route (DESIGN.md sections 5.10, 5.15, 5.17), shared by the kernels of gram_long.hip
 // and pair_bands.hip: the kernel's value at a point of X (LDS, fp64) and a point of Y, the gradient pass that chains a
 // pair's coarse S through the static kernel's derivative, and the pass that chains it through the kernel's derivative in the
 // bandwidth (gram_long.hip only).
@@ -10,16 +10,19 @@ namespace sigsvgd {
 namespace {
 // The radial kinds beside RBF: k = phi(s), s = |x - y|^2 inv_h.  radial_phi: phi(s); radial_slope:
 // -phi'(s), which takes the place of RBF's exp(-s) in the gradient contraction (IMQ: k^3 / 2, rational quadratic: k^2).
+// (the Matern kinds, DESIGN.md section 5.17: kMaternKind, matern_u, matern_phi and matern_slope of sig_common.h)
 template <int KIND>
-inline constexpr bool kRadialKind = KIND == SIGSVGD_STATIC_IMQ || KIND == SIGSVGD_STATIC_RQ;
+inline constexpr bool kRadialKind = KIND == SIGSVGD_STATIC_IMQ || KIND == SIGSVGD_STATIC_RQ || kMaternKind<KIND>;
 template <int KIND>
 __device__ __forceinline__ double radial_phi(double s)
 {
+    if constexpr (kMaternKind<KIND>) return matern_phi(KIND == SIGSVGD_STATIC_MATERN32, matern_u(KIND == SIGSVGD_STATIC_MATERN32, s));
     return KIND == SIGSVGD_STATIC_IMQ ? rsqrt(1.0 + s) : 1.0 / (1.0 + s);
 }
 template <int KIND>
 __device__ __forceinline__ double radial_slope(double s)
 {
+    if constexpr (kMaternKind<KIND>) return matern_slope(KIND == SIGSVGD_STATIC_MATERN32, matern_u(KIND == SIGSVGD_STATIC_MATERN32, s));
     const double k = radial_phi<KIND>(s);
     return KIND == SIGSVGD_STATIC_IMQ ? 0.5 * (k * k * k) : k * k;
 }

@@ -394,7 +394,7 @@ hipError_t bands_launch_one(const PairBandsPlan &bp, hipStream_t stream, const B
 template <typename IO, int KIND>
 hipError_t bands_launch_solver(bool naive, bool grad, const PairBandsPlan &bp, hipStream_t stream, const BandsArgs &a)
 {
-    // (IMQ and rational quadratic have the default stencil only, as in the serial kernel)
+    // (IMQ, rational quadratic and Matern have the default stencil only, as in the serial kernel)
     constexpr bool has_naive = KIND == SIGSVGD_STATIC_RBF || KIND == SIGSVGD_STATIC_LINEAR;
     if constexpr (has_naive) {
         if (naive)
@@ -420,7 +420,22 @@ hipError_t bands_launch_kind(int kind, bool naive, bool grad, const PairBandsPla
 // The fp32-I/O instantiations compile in a translation unit of their own (pair_bands_f32.hip includes this file with
 // SIGSVGD_PAIR_BANDS_F32 defined), side by side with the fp64-I/O ones: half the build time of the slowest source.
 hipError_t pair_bands_launch_f32(int kind, bool naive, bool grad, const PairBandsPlan &bp, hipStream_t stream, const BandsArgs &a);
-#ifdef SIGSVGD_PAIR_BANDS_F32
+// The Matern kinds' instantiations (both I/O types, default stencil only) compile in a third one,
+// pair_bands_matern.hip, with SIGSVGD_PAIR_BANDS_MATERN defined.
+hipError_t pair_bands_launch_matern(int dtype, int kind, bool grad, const PairBandsPlan &bp, hipStream_t stream,
+                                    const BandsArgs &a);
+#if defined(SIGSVGD_PAIR_BANDS_MATERN)
+hipError_t pair_bands_launch_matern(int dtype, int kind, bool grad, const PairBandsPlan &bp, hipStream_t stream,
+                                    const BandsArgs &a)
+{
+    if (kind != SIGSVGD_STATIC_MATERN32 && kind != SIGSVGD_STATIC_MATERN52) return hipErrorInvalidValue;
+    if (dtype == SIGSVGD_F64)
+        return kind == SIGSVGD_STATIC_MATERN32 ? bands_launch_solver<double, SIGSVGD_STATIC_MATERN32>(false, grad, bp, stream, a)
+                                               : bands_launch_solver<double, SIGSVGD_STATIC_MATERN52>(false, grad, bp, stream, a);
+    return kind == SIGSVGD_STATIC_MATERN32 ? bands_launch_solver<float, SIGSVGD_STATIC_MATERN32>(false, grad, bp, stream, a)
+                                           : bands_launch_solver<float, SIGSVGD_STATIC_MATERN52>(false, grad, bp, stream, a);
+}
+#elif defined(SIGSVGD_PAIR_BANDS_F32)
 hipError_t pair_bands_launch_f32(int kind, bool naive, bool grad, const PairBandsPlan &bp, hipStream_t stream, const BandsArgs &a)
 {
     return bands_launch_kind<float>(kind, naive, grad, bp, stream, a);
@@ -484,8 +499,11 @@ int pair_bands_launch(const LongProblem &p, const PairGeom &g, const PairBandsPl
     a.wave_doubles = (unsigned)bp.wave_doubles; a.seam_doubles = (unsigned)bp.seam_doubles;
     a.inv_h = p.inv_h; a.inv_r2 = 1.0 / ((double)g.r * (double)g.r);
     const bool naive = (p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0;
-    hipError_t e = p.dtype == SIGSVGD_F64 ? bands_launch_kind<double>(p.kind, naive, grad, bp, p.stream, a)
-                                          : pair_bands_launch_f32(p.kind, naive, grad, bp, p.stream, a);
+    const bool matern = p.kind == SIGSVGD_STATIC_MATERN32 || p.kind == SIGSVGD_STATIC_MATERN52;
+    hipError_t e = matern ? (naive ? hipErrorInvalidValue // (the entry points refuse it before this)
+                                   : pair_bands_launch_matern(p.dtype, p.kind, grad, bp, p.stream, a))
+                   : p.dtype == SIGSVGD_F64 ? bands_launch_kind<double>(p.kind, naive, grad, bp, p.stream, a)
+                                            : pair_bands_launch_f32(p.kind, naive, grad, bp, p.stream, a);
     if (e != hipSuccess) return hip_fail(e, "hipFuncSetAttribute(pair_bands)");
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch pair_bands_kernel");

@@ -90,7 +90,9 @@ int ring_plan_total(size_t *bytes, Make &&make)
 // address), F::has_kind (false: one kernel for every static kernel, KIND = 0), F::has_fwd_only (false: GRAD = true only) and
 // the two texts of a failure.  ring_launch maps the runtime (dtype, kind, naive, grad) to the instantiation, raises its LDS
 // limit and launches pl.grid wavefronts with pl.lds bytes of LDS each; only instantiations the family has are named.  The
-// kinds SIGSVGD_STATIC_IMQ and _RQ are instantiated with the default stencil only.
+// kinds SIGSVGD_STATIC_IMQ and _RQ are instantiated with the default stencil only, and so are the
+// Matern kinds, which ring_launch_solver serves but ring_launch_kind does not name: gram_long.hip launches them from a
+// translation unit of their own.
 template <typename F, typename IO, bool NAIVE, bool GRAD, int KIND, typename Plan>
 hipError_t ring_launch_one(const Plan &pl, hipStream_t stream, const typename F::Args &a)
 {
@@ -103,7 +105,7 @@ hipError_t ring_launch_one(const Plan &pl, hipStream_t stream, const typename F:
 template <typename F, typename IO, int KIND, typename Plan>
 hipError_t ring_launch_solver(bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
 {
-    // (IMQ and rational quadratic have the default stencil only: the entry points refuse NAIVE_SOLVER before this)
+    // (IMQ, rational quadratic and Matern have the default stencil only: the entry points refuse NAIVE_SOLVER before this)
     constexpr bool has_naive = KIND == SIGSVGD_STATIC_RBF || KIND == SIGSVGD_STATIC_LINEAR;
     if constexpr (!has_naive) {
         if (naive) return hipErrorInvalidValue;

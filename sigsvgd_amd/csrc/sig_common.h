@@ -45,6 +45,32 @@ __device__ __forceinline__ double exp64(double a0)
     return (a0 != a0) ? a0 : e; // a NaN in a path poisons its own row / column of K, as in the reference
 }
 
+// The Matern static kernels of the fp64 routes, k = phi(s) with s = |x - y|^2 inv_h: u = sqrt(3 s) and
+// phi = (1 + u) e^-u, -phi' = (3/2) e^-u (Matern-3/2); u = sqrt(5 s) and phi = (1 + u + u^2 / 3) e^-u, -phi' = (5/6) (1 + u) e^-u
+// (Matern-5/2).  One sqrt and one exp64 each; -phi'(0) is finite, so coincident points have a zero gradient term.
+template <int KIND>
+inline constexpr bool kMaternKind = KIND == SIGSVGD_STATIC_MATERN32 || KIND == SIGSVGD_STATIC_MATERN52;
+// m32: Matern-3/2, else Matern-5/2 (a constant where the kind is a template parameter, wave-uniform in the coverage kernel).
+// u from s clamped at 0: a distance formed as xn + yn - 2 dot can round a few ulp below 0 for coincident points (a NaN stays
+// one: it poisons its row / column of K as for the other kinds)
+__device__ __forceinline__ double matern_u(bool m32, double s)
+{
+    return sqrt((m32 ? 3.0 : 5.0) * (s < 0.0 ? 0.0 : s));
+}
+// (Both values end in an explicit fma, e + (u e) (1 + u / 3) for Matern-5/2: a product as the last operation could be
+// contracted with the subtraction that follows it in one kernel's increments and not in another's, and the schedules and modes
+// of the long route must agree bit for bit.)
+__device__ __forceinline__ double matern_phi(bool m32, double u)
+{
+    const double e = exp64(-u);
+    return m32 ? __builtin_fma(u, e, e) : __builtin_fma(u * e, __builtin_fma(u, 1.0 / 3.0, 1.0), e);
+}
+__device__ __forceinline__ double matern_slope(bool m32, double u) // -phi'(s)
+{
+    const double e = exp64(-u);
+    return m32 ? 1.5 * e : (5.0 / 6.0) * __builtin_fma(u, e, e);
+}
+
 // 2^t for the register-resident kernels: t arrives already scaled by log2(e) (the scale is folded into the particle
 // coordinates), so the reduction is exact: k = rint(t), f = t - k in [-1/2, 1/2], and 2^f is a degree-7 polynomial (max
 // relative error 5.5e-11 on [-1/2, 1/2]; the kernels' increments are rounded to fp32, 6e-8 relative, right after).

@@ -132,8 +132,9 @@ class ShardedSigSVGD:
     d <= 16); the row-wise solve where the fused kernels take the launch, and always with a caller's rows_fn (unless a
     long_partial_fn is given too: a caller's row solver keeps the launches it got before); else the long partial solve
     long_partial_fn(X_full, inv_h, tile_offset, tile_stride, dyadic_order=, static_kind=, out=, fold=) -> (K_partial,
-    grad_partial), by default `ops.gram_long_sym_partial`; else the row-wise call's own error.  static_kind 2 and 3 (IMQ,
-    rational quadratic: the fp64 coverage kernel and the long route, never the fused partial solve): their row-wise step
+    grad_partial), by default `ops.gram_long_sym_partial`; else the row-wise call's own error.  static_kind 2, 3, 6 and 7 (IMQ,
+    rational quadratic, Matern-3/2 and -5/2: the fp64 coverage kernel and the long route, never the fused partial solve): their
+    row-wise step
     takes `ops.gram_long_fwd_bwd` at a shape only the long route takes.  long_partial=True sends every
     shape the long partial takes to it (each pair once also at 129 <= T <= 190), long_partial=False never uses it.
     `last_route` names the last step's route ("partial", "rowwise" or "long_partial").
@@ -193,7 +194,7 @@ class ShardedSigSVGD:
         # the long route is taken by itself only in place of the library's own row-wise solve: a caller's rows_fn keeps the
         # launches it got before, unless the caller asks for the long partial (long_partial=True or a long_partial_fn)
         self._auto_long = rows_fn is None or long_partial_fn is not None
-        if rows_fn is None and self.static_kind in (_lib.STATIC_IMQ, _lib.STATIC_RQ):
+        if rows_fn is None and self.static_kind in (_lib.STATIC_IMQ, _lib.STATIC_RQ, _lib.STATIC_MATERN32, _lib.STATIC_MATERN52):
             rows_fn = self._rows_fused_or_long
         elif rows_fn is None and (self.dyadic_order != 0 or self.static_kind != _lib.STATIC_RBF):
             rows_fn = lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind)
@@ -368,7 +369,7 @@ class ShardedSigSVGD:
         return "rowwise"
 
     def _rows_fused_or_long(self, Xs, Xf, inv_h):
-        """The library's row solver of the IMQ and rational-quadratic kernels: the fused launch where the coverage kernel
+        """The library's row solver of the IMQ, rational-quadratic and Matern kernels: the fused launch where the coverage kernel
         takes the rows' shape, else the long route's ordered launch (a row-wise step at a shape only the long route takes:
         rowwise=True, long_partial=False)."""
         n, T, d = Xs.shape

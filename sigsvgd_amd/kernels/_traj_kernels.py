@@ -1,5 +1,6 @@
 """Trajectory kernels: `BatchGaussianKernel` (static RBF on path points; `BatchIMQKernel` and
-`BatchRationalQuadraticKernel` are its heavy-tailed siblings) and `SignatureKernel` (signature
+`BatchRationalQuadraticKernel` are its heavy-tailed siblings, `BatchMatern32Kernel` and `BatchMatern52Kernel` its rougher
+ones) and `SignatureKernel` (signature
 kernel via the Goursat PDE) -- reference src/kernels/_traj_kernels.py:147-206 -- backed by the HIP library
 instead of `sigkernel`; `PathSigKernel` (static kernel on truncated signatures, :72-144) backed by the HIP
 signature kernel instead of `signatory`; `TrajectoryKernel` (:14-69)."""
@@ -8,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from .. import _lib
-from ..sigkernel import SigKernel, batch_sqdist, gram_sqdist, inv_bandwidth_from_fn, radial_power
+from ..sigkernel import SigKernel, batch_sqdist, gram_sqdist, inv_bandwidth_from_fn, matern_radial, radial_power
 from ._kernels import BaseKernel, GaussianKernel, _SqDist, kernel_output, scalar_function
 
 class TrajectoryKernel(BaseKernel):
@@ -124,12 +125,32 @@ class BatchRationalQuadraticKernel(BatchIMQKernel):
     power = -1.0
 
 
-_STATIC_BY_NAME = {"rbf": BatchGaussianKernel, "imq": BatchIMQKernel, "rq": BatchRationalQuadraticKernel}
+class BatchMatern32Kernel(BatchIMQKernel):
+    """Matern-3/2 kernel on path points, k = (1 + u) exp(-u), u = sqrt(3 |x-y|^2 / h), h = bandwidth_fn(dist): a Matern kernel
+    of lengthscale l is h = l^2.  Bandwidths resolve as BatchGaussianKernel's do."""
+
+    static_kind = _lib.STATIC_MATERN32
+    power = None  # (not a power of 1 + dist / h)
+    order = 3
+
+    def _of(self, dist, h):
+        return matern_radial(dist, self.get_bandwidth(dist) if h is None else float(h), self.order)
+
+
+class BatchMatern52Kernel(BatchMatern32Kernel):
+    """Matern-5/2 kernel on path points, k = (1 + u + u^2 / 3) exp(-u), u = sqrt(5 |x-y|^2 / h), h = bandwidth_fn(dist)."""
+
+    static_kind = _lib.STATIC_MATERN52
+    order = 5
+
+
+_STATIC_BY_NAME = {"rbf": BatchGaussianKernel, "imq": BatchIMQKernel, "rq": BatchRationalQuadraticKernel,
+                   "matern32": BatchMatern32Kernel, "matern52": BatchMatern52Kernel}
 
 
 class SignatureKernel:
     """Signature kernel with a static kernel on path points; `depth` is the DYADIC ORDER of the PDE solver
-    (not a truncation level).  static_kernel: None or "rbf" (the reference's RBF), "imq", "rq" (each built on
+    (not a truncation level).  static_kernel: None or "rbf" (the reference's RBF), "imq", "rq", "matern32", "matern52" (each built on
     `bandwidth_fn`), or a static-kernel instance, used as it is.  Unknown keyword arguments are accepted and ignored, as in
     the reference (examples/script_planning_robot.py:391 passes `bandwidth=`)."""
 

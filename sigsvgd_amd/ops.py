@@ -366,7 +366,7 @@ def gram_long_h_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: in
                       want_gradX: bool = True, want_gradY: bool = True, naive: bool = False, y_is_x: bool = False) -> bool:
     """Whether `gram_long_fwd_bwd_h` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, per-wave
-    state beyond the LDS, or the first-order stencil with IMQ / rational quadratic); any other error raises."""
+    state beyond the LDS, or the first-order stencil with IMQ / rational quadratic / Matern); any other error raises."""
     return _query("gram_long_h_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                                   1 if want_gradX else 0, 1 if want_gradY else 0,
                                                   _flags(naive, False, y_is_x, False)), (ctypes.c_size_t(0),), may_refuse=True)
@@ -377,7 +377,7 @@ def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: 
                         y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True):
     """(K[A,B], gX or None, gY or None, dK_dinvh[A,B]): `gram_long_fwd_bwd2` with every pair's derivative of K in the
     static kernel's inverse bandwidth from the same reverse sweep (`sigsvgd_gram_long_fwd_bwd_h`, DESIGN.md section 5.16;
-    RBF, IMQ and rational quadratic).  dK_dinvh is unweighted -- grad_out and sym weight gX and gY only -- and with y_is_x
+    RBF, IMQ, rational quadratic and Matern).  dK_dinvh is unweighted -- grad_out and sym weight gX and gY only -- and with y_is_x
     exactly symmetric; dK/dsigma = -inv_h^2 dK_dinvh.  K, gX and gY have the bits `gram_long_fwd_bwd2` returns.  Neither
     gradient wanted: the reverse sweep still runs.  Bit-reproducible."""
     dev = _require_gpu(X, Y, grad_out)

@@ -15,25 +15,28 @@ sigsvgd_amd.sigkernel` makes the reference's own code run o
 for X only (None for everything else), like upstream; `grad_Y=True` adds the second-slot gradient for Y.  `compute_kernel` (and `compute_distance` on it) solves each pair
 (X_i, Y_i) once and differentiates both paths, each in its own slot.
 
-Static kernels.  `RBFKernel`, `LinearKernel`, the heavy-tailed `IMQStaticKernel` and `RationalQuadraticKernel`, anything with
-`static_kind` + `inv_bandwidth` (`sigsvgd_amd.kernels.BatchGaussianKernel`, `BatchIMQKernel`, `BatchRationalQuadraticKernel`)
+Static kernels.  `RBFKernel`, `LinearKernel`, the heavy-tailed `IMQStaticKernel` and `RationalQuadraticKernel`, the rougher
+`Matern32StaticKernel` and `Matern52StaticKernel`, anything with
+`static_kind` + `inv_bandwidth` (`sigsvgd_amd.kernels.BatchGaussianKernel`, `BatchIMQKernel`, `BatchRationalQuadraticKernel`,
+`BatchMatern32Kernel`, `BatchMatern52Kernel`)
 and the reference's own `BatchGaussianKernel` are evaluated inside the fused HIP kernels (nothing of size [A,B,T,T] is formed); paths too long for
 the fused kernels' LDS take the long route (csrc/gram_long.hip), which evaluates the static kernel inside its PDE sweep
-(P, Q <= 8192 refined cells).  RBF alone has the fp32-sweep kernels; the linear, IMQ and rational-quadratic kernels run
-on the fp64 coverage kernel and the long route (there with the default stencil only: DESIGN.md section 5.15).  A `BatchGaussianKernel` without a `bandwidth_fn` (the reference's default, the median
+(P, Q <= 8192 refined cells).  RBF alone has the fp32-sweep kernels; the linear, IMQ, rational-quadratic and Matern kernels run
+on the fp64 coverage kernel and the long route (there, but for the linear kernel, with the default stencil only: DESIGN.md
+sections 5.15, 5.17).  A `BatchGaussianKernel` without a `bandwidth_fn` (the reference's default, the median
 heuristic) takes its median from an exact select on the device (`ops.path_sqdist_select`), at any batch size.  Any other object with upstream's `Gram_matrix(X, Y) -> [A,B,M,N]` (and, optionally,
 `batch_kernel(X, Y) -> [A,M,N]`) is a USER static kernel: its grid is materialised by the user's own torch code, as upstream does, and the signature PDE on it runs on
 the device (`ops.PDESolve`, csrc/sig_pde.hip).  Gradients then flow through torch autograd -- to X through the user's
 `Gram_matrix` and to the static kernel's own parameters.  The grid costs A*B*M*N elements of memory: large batches
 belong on the built-in kernels.  Objects without `Gram_matrix` raise NotImplementedError.
 
-Learning sigma.  Where the `sigma` of `RBFKernel`, `IMQStaticKernel` or `RationalQuadraticKernel` is a
-one-element tensor that requires grad (on any device) and grad mode is on, `compute_Gram` and `compute_kernel` -- and
+Learning sigma.  Where the `sigma` of `RBFKernel`, `IMQStaticKernel`, `RationalQuadraticKernel`,
+`Matern32StaticKernel` or `Matern52StaticKernel` is a one-element tensor that requires grad (on any device) and grad mode is on, `compute_Gram` and `compute_kernel` -- and
 `compute_distance` / `compute_mmd` through them -- are autograd nodes that take sigma as an input: they run on the long route's
 bandwidth launches (`ops.gram_long_fwd_bwd_h`, `ops.pair_fwd_bwd_h`) whatever the shape, save every pair's dK/d(1/sigma) in
 forward and return grad_sigma = -(1/sigma)^2 sum(grad_output * dK/d(1/sigma)) without another launch, in the reference's GG
 convention (what upstream's autograd through its torch static kernels gives).  X and Y keep the rules above.  Shapes the long
-route refuses, and IMQ / rational quadratic with `_naive_solver=True`, raise NotImplementedError.  A float sigma, a tensor
+route refuses, and IMQ / rational quadratic / Matern with `_naive_solver=True`, raise NotImplementedError.  A float sigma, a tensor
 that does not require grad and `torch.no_grad()` take exactly the launches described above.  Data-dependent bandwidths (the
 median) stay detached, as in the reference.
 """
@@ -45,7 +48,8 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["SigKernel", "RBFKernel", "LinearKernel", "IMQStaticKernel", "RationalQuadraticKernel", "gram_and_grad"]
+__all__ = ["SigKernel", "RBFKernel", "LinearKernel", "IMQStaticKernel", "RationalQuadraticKernel", "Matern32StaticKernel",
+           "Matern52StaticKernel", "gram_and_grad"]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -136,6 +140,46 @@ class RationalQuadraticKernel(IMQStaticKernel):
 
     static_kind = _lib.STATIC_RQ
     power = -1.0
+
+
+def matern_radial(dist, h, order):
+    """The Matern kernel of a squared distance: order 3 is (1 + u) e^-u with u = sqrt(3 dist / h), order 5 is
+    (1 + u + u^2 / 3) e^-u with u = sqrt(5 dist / h).  dist / h is clamped at 0 (a distance formed from dot products can round
+    below it), and the square root is taken where it is positive only, so autograd through coincident points gives the zero
+    gradient term they have instead of sqrt's inf * 0."""
+    s = dist / h
+    pos = s > 0
+    u = torch.where(pos, torch.sqrt(float(order) * torch.where(pos, s, torch.ones_like(s))), torch.zeros_like(s))
+    poly = 1.0 + u if order == 3 else 1.0 + u + u * u / 3.0
+    return poly * torch.exp(-u)
+
+
+class Matern32StaticKernel:
+    """k(x, y) = (1 + u) exp(-u), u = sqrt(3 |x-y|^2 / sigma): the Matern kernel of smoothness 3/2 (once differentiable sample
+    paths).  sigma divides the squared distance, as RBFKernel's does: a lengthscale l is sigma = l^2."""
+
+    static_kind = _lib.STATIC_MATERN32
+    order = 3
+
+    def __init__(self, sigma):
+        self.sigma = sigma
+
+    def inv_bandwidth(self, X, Y) -> float:
+        return 1.0 / _sigma_value(self.sigma)
+
+    def batch_kernel(self, X, Y):
+        return matern_radial(batch_sqdist(X, Y), self.sigma, self.order)
+
+    def Gram_matrix(self, X, Y):
+        return matern_radial(gram_sqdist(X, Y), self.sigma, self.order)
+
+
+class Matern52StaticKernel(Matern32StaticKernel):
+    """k(x, y) = (1 + u + u^2 / 3) exp(-u), u = sqrt(5 |x-y|^2 / sigma): the Matern kernel of smoothness 5/2 (twice
+    differentiable sample paths)."""
+
+    static_kind = _lib.STATIC_MATERN52
+    order = 5
 
 
 # refuse to materialise distance tensors larger than this for data-dependent bandwidths
@@ -252,8 +296,9 @@ def _resolve_static(static_kernel, X, Y):
         return None, None
     raise NotImplementedError(
         f"static kernel {type(static_kernel).__name__} is not supported by the HIP path: it needs upstream's "
-        "Gram_matrix(X, Y) (fused: RBFKernel, LinearKernel, IMQStaticKernel, RationalQuadraticKernel, BatchGaussianKernel, "
-        "BatchIMQKernel, BatchRationalQuadraticKernel)"
+        "Gram_matrix(X, Y) (fused: RBFKernel, LinearKernel, IMQStaticKernel, RationalQuadraticKernel, Matern32StaticKernel, "
+        "Matern52StaticKernel, BatchGaussianKernel, BatchIMQKernel, BatchRationalQuadraticKernel, BatchMatern32Kernel, "
+        "BatchMatern52Kernel)"
     )
 
 
@@ -417,10 +462,10 @@ class _SigKernelPair(torch.autograd.Function):
 # a static-kernel sigma that requires grad
 # ------------------------------------------------------------------------------------------------
 def _learned_sigma(static_kernel):
-    """-> the static kernel's `sigma` where it is to be differentiated: one of this module's RBF / IMQ / rational-quadratic
-    kernels whose sigma is a one-element tensor that requires grad, with grad mode on.  None otherwise (a float, a plain
+    """-> the static kernel's `sigma` where it is to be differentiated: one of this module's RBF / IMQ / rational-quadratic /
+    Matern kernels whose sigma is a one-element tensor that requires grad, with grad mode on.  None otherwise (a float, a plain
     tensor, `torch.no_grad()`, any other static kernel): those calls take the launches they always took."""
-    if not isinstance(static_kernel, (RBFKernel, IMQStaticKernel)) or not torch.is_grad_enabled():
+    if not isinstance(static_kernel, (RBFKernel, IMQStaticKernel, Matern32StaticKernel)) or not torch.is_grad_enabled():
         return None
     sigma = getattr(static_kernel, "sigma", None)
     if not isinstance(sigma, torch.Tensor) or not sigma.requires_grad:
