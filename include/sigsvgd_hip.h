@@ -157,6 +157,16 @@ extern "C" {
 int sigsvgd_abi_version(void);
 const char *sigsvgd_last_error(void);
 
+/* The workspace contract of every entry point below that takes `workspace, workspace_bytes`:
+ *   1. a buffer of exactly the bytes the entry point's *_workspace_bytes query reports is enough;
+ *   2. the pointer may have any alignment: every reported total includes 256 B of slack, and the launcher aligns the pointer
+ *      up to 256 B itself;
+ *   3. the contents do not matter: no launch needs a zeroed (or otherwise prepared) workspace, and the results have the same
+ *      bits whatever it held.
+ * A size below the query's is refused with SIGSVGD_E_WORKSPACE (sigsvgd_last_error names the required bytes) before any
+ * device work: nothing is enqueued and no output is written.  A query of 0 bytes: the launch takes workspace = NULL.
+ * tests/test_gpu_workspace.py holds this for every launch form (exact size, misaligned, poisoned, between guard areas). */
+
 /* Bytes of scratch the two Gram entry points need for this problem.  Forward-only launches need some too
  * (accumulation buffers, scratch of the persistent grids), so always query.  The size is the largest of the launches the
  * arguments can reach: with SIGSVGD_FLAG_Y_IS_X and A == B the symmetric launch and (want_grad = 1) the symmetric partial
@@ -277,7 +287,8 @@ int sigsvgd_vec_kernel_fused(const void *X, const void *Y, const void *XM, const
 /* Scratch for the reproducible route of sigsvgd_vec_kernel_fused (ABI 9): the launch splits the columns over the grid, and
  * with a workspace of this size every split stores its partial dK in a block of its own, added in split order by a second
  * small launch -- bits that depend on the launch geometry only.  workspace = NULL keeps the one-launch route whose splits
- * meet in fp32 atomics (last bits of dK_out may differ between calls).  0 bytes: a single split, nothing to join. */
+ * meet in fp32 atomics (last bits of dK_out may differ between calls).  0 bytes: a single split, nothing to join.
+ * Otherwise splits * A * D * 4 bytes and the 256 B of alignment slack (the launcher aligns the pointer up, as everywhere). */
 int sigsvgd_vec_fused_workspace_bytes(int A, int B, int D, size_t *bytes);
 
 /* ---- trajectory cost in front of the path -----------------------------------------------

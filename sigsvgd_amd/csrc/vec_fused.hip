@@ -306,12 +306,13 @@ int fused_launch_nt(const float *X, const float *Y, const float *XM, const float
     float *part = nullptr;
     if (dK && splits == 1) {
         part = dK;
-    } else if (dK && ws) {
-        if (ws_bytes < (size_t)splits * A * D * sizeof(float)) {
-            set_error("vec_kernel_fused: workspace %zu B < required %zu B", ws_bytes, (size_t)splits * A * D * sizeof(float));
+    } else if (dK && ws) { // the blocks start at the caller's pointer aligned up to 256 B: the query's total carries that slack
+        const size_t need = (size_t)splits * A * D * sizeof(float) + 256;
+        if (ws_bytes < need) {
+            set_error("vec_kernel_fused: workspace %zu B < required %zu B", ws_bytes, need);
             return SIGSVGD_E_WORKSPACE;
         }
-        part = ws;
+        part = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
     } else if (dK) {
         hipError_t e = hipMemsetAsync(dK, 0, (size_t)A * D * sizeof(float), stream);
         if (e != hipSuccess) return hip_fail(e, "hipMemsetAsync(dK)");
@@ -347,7 +348,7 @@ size_t vec_fused_workspace_bytes(int A, int B, int D)
 {
     int splits, per;
     fused_splits(A, B, true, splits, per);
-    return splits > 1 ? (size_t)splits * A * D * sizeof(float) : 0;
+    return splits > 1 ? (size_t)splits * A * D * sizeof(float) + 256 : 0; // (+ the slack of aligning the caller's pointer)
 }
 
 bool vec_fused_supported(int D, int dtype) { return dtype == SIGSVGD_F32 && D >= 1 && D <= 512; }

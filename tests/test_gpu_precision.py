@@ -132,9 +132,12 @@ def test_exact_pass_long_paths(gpu, A, B, T, d, h, scale, dtype):
 def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
     """the workspace query sized refined shapes for the refined-grid / band kernels whatever the static
     kernel, while the linear kernel runs them on the coverage kernel (far more scratch).  The query takes the static kind
-    since ABI 9; a launch on a workspace of exactly the queried size must pass."""
+    since ABI 9; a launch on a workspace of exactly the queried size must pass -- here between the guards of
+    tests/guarded_workspace.py, every byte 0xFF, at the worst alignment (tests/test_gpu_workspace.py does that for every
+    launch form)."""
     import ctypes
 
+    from guarded_workspace import GuardedWorkspace
     from oracle import sigkernel_oracle as O
     from sigsvgd_amd import _lib, ops
 
@@ -145,13 +148,16 @@ def test_linear_kernel_on_refined_shapes_fresh_workspace(gpu):
         Xg, Yg = torch.as_tensor(X, device=gpu), torch.as_tensor(Y, device=gpu)
         nb = ctypes.c_size_t(0)
         assert L.sigsvgd_gram_workspace_bytes(A, B, T, d, n, _lib.STATIC_LINEAR, 1, 0, ctypes.byref(nb)) == 0
-        ws = torch.empty(nb.value, dtype=torch.uint8, device=gpu)
+        guarded = GuardedWorkspace("ones", 1)
+        ws, nws = guarded(gpu, nb.value)
+        assert nws == nb.value and ws.numel() == nb.value
         K = torch.empty(A, B, device=gpu)
         g = torch.empty(A, T, d, device=gpu)
         rc = L.sigsvgd_gram_fwd_bwd(Xg.data_ptr(), Yg.data_ptr(), A, B, T, d, _lib.F32, 1.0, n, _lib.STATIC_LINEAR, 0, None,
-                                    K.data_ptr(), g.data_ptr(), ws.data_ptr(), nb.value, None)
+                                    K.data_ptr(), g.data_ptr(), ws.data_ptr(), nws, None)
         assert rc == 0, _lib.last_error()
         torch.cuda.synchronize()
+        guarded.check()
         assert rel_entry(K.cpu().numpy(), Kref, 1e-6) < TOL and rel_max(g.cpu().numpy(), gref) < TOL
         K2, g2 = ops.gram_fwd_bwd(Xg, Yg, 1.0, n, static_kind=_lib.STATIC_LINEAR)
         assert torch.equal(K, K2) and torch.equal(g, g2)
