@@ -508,9 +508,13 @@ def svgd_phi(K, score, grad_k, mask=None, X=None, lr: Optional[float] = None, ad
     Kc = K.detach().to(torch.float32).contiguous()
     s, gk = _flat32(score, N), _flat32(grad_k, N)
     D = s.shape[1]
+    if score.shape[0] != N:
+        raise ValueError(f"score must have K's {N} rows, got {tuple(score.shape)}")
     if gk.shape != s.shape:
         raise ValueError(f"grad_k shape {tuple(grad_k.shape)} does not match score {tuple(score.shape)}")
     Xc, m = _update_operands(dev, shape, D, X, mask, inplace, adagrad_state, "score")
+    if Xc is not None and Xc.shape != s.shape:  # (the kernel indexes X_in and X_out by the launch's N and D)
+        raise ValueError(f"X shape {tuple(X.shape)} does not match score {tuple(score.shape)}")
     v = torch.empty_like(s)
     Xn = Xc if inplace or Xc is None else torch.empty_like(Xc)
     _launch(dev, "svgd_step", (Kc.data_ptr(), s.data_ptr(), gk.data_ptr(), _ptr(m), N, D, v.data_ptr(), _ptr(Xc), _ptr(Xn),
@@ -546,8 +550,11 @@ def svgd_adam(K, score, grad_k, X, lr: float, state: AdamState, mask=None, inpla
     Kc = K.detach().to(torch.float32).contiguous()
     s, gk = _flat32(score, N), _flat32(grad_k, N)
     D = s.shape[1]
+    if score.shape[0] != N:
+        raise ValueError(f"score must have K's {N} rows, got {tuple(score.shape)}")
     Xc, m = _update_operands(dev, shape, D, X, mask, inplace, None, "score")
-    if gk.shape != s.shape or Xc.shape != s.shape or tuple(state.exp_avg.shape) != (N, D):
+    if gk.shape != s.shape or Xc.shape != s.shape or tuple(state.exp_avg.shape) != (N, D) \
+            or tuple(state.exp_avg_sq.shape) != (N, D):
         raise ValueError("score, grad_k, X and the Adam state must share the shape [N, D]")
     v = torch.empty_like(s)
     Xn = Xc if inplace else torch.empty_like(Xc)

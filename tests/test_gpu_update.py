@@ -6,6 +6,10 @@ So for manual, Adagrad and Adam, with and without a mask, over three consecutive
 the fused `ops.svgd_phi` / `ops.svgd_adam`, each on its own copy of the state, must agree in v_out, X_out, the Adagrad sum,
 exp_avg, exp_avg_sq and the step counter under torch.equal.
 
+Equality says that the two kernels agree, not that either is right.  That evidence is in tests/test_gpu_phi.py: the fused
+kernel's product per entry against the fp64 reference at these partial-tile shapes and two dozen more, and both kernels'
+update rules per entry against `update_reference.check_update` at (5, 3), (33, 70), (68, 132) and (129, 63).
+
 Shapes (N, D): (5, 3) the scalar path; (33, 70) partial 32 x 64 tiles of the fused kernel, and for the update kernel a D
 that is no multiple of 4 with rows off the 16-byte grid; (64, 448) the 16-byte path over several grid-stride rounds (7168
 accesses on 7 workgroups of 256 threads)."""

@@ -1,5 +1,6 @@
-"""What the tests of the sharded step's update rules share (tests/test_distributed_update_cpu.py under gloo,
-tests/test_gpu_distributed_update.py under RCCL): a torch restatement of `ops.svgd_update` for CPU tensors, the fp64
+"""What the tests of the update rules share (the sharded step's: tests/test_distributed_update_cpu.py under gloo,
+tests/test_gpu_distributed_update.py under RCCL; the fused launches' and `ops.svgd_update`'s at partial-tile shapes:
+tests/test_gpu_phi.py): a torch restatement of `ops.svgd_update` for CPU tensors, the fp64
 reference of one update (torch.optim.Adam itself; the reference's two Adagrad lines), and the rounding bounds of the fp32
 arithmetic.  Not a test module.
 
@@ -86,9 +87,11 @@ def reference_update(mode, v, x, lr, mask, state, t, betas=(0.9, 0.999), eps=1e-
     return p.detach().numpy(), v, {"exp_avg": st["exp_avg"].numpy(), "exp_avg_sq": st["exp_avg_sq"].numpy()}
 
 
-def check_update(mode, got_x, got_state, v, x, lr, mask, state, t, betas=(0.9, 0.999), eps=1e-8, where=""):
+def check_update(mode, got_x, got_state, v, x, lr, mask, state, t, betas=(0.9, 0.999), eps=1e-8, where="", got_v=None):
     """Asserts one step's new particles and state against `reference_update` within the rounding bounds of the module
-    docstring; prints each figure (largest error over its bound) before it asserts."""
+    docstring; prints each figure (largest error over its bound) before it asserts.  `got_v`: the velocity the launch
+    stored (after mask and Adagrad), asserted too where given: COUNT["adagrad_v"] roundings of |v_applied| under Adagrad,
+    the one rounding of v * mask otherwise."""
     x_ref, va, st_ref = reference_update(mode, v, x, lr, mask, state, t, betas, eps)
     f = lambda a, like: np.asarray(a, np.float64).reshape(np.shape(like))
     checks = []
@@ -107,6 +110,8 @@ def check_update(mode, got_x, got_state, v, x, lr, mask, state, t, betas=(0.9, 0
         checks.append(("exp_avg", f(got_state["exp_avg"], m), m, COUNT["adam_m"] * U * (np.abs(m_old) + np.abs(va))))
         checks.append(("exp_avg_sq", f(got_state["exp_avg_sq"], q), q, COUNT["adam_q"] * U * q))
         checks.append(("X", f(got_x, x_ref), x_ref, COUNT["adam_X"] * U * (np.abs(np.asarray(x, np.float64)) + term)))
+    if got_v is not None:
+        checks.append(("v_applied", f(got_v, va), va, (COUNT["adagrad_v"] if mode == "adagrad" else 1) * U * np.abs(va)))
     for name, got, ref, bound in checks:
         err = np.abs(got - ref)
         worst = float((err / np.maximum(bound, 1e-300)).max()) if err.max() > 0 else 0.0
