@@ -111,7 +111,8 @@ extern "C" {
  * second revision of ABI 10 on (no new symbol, no changed signature: a library of the first revision answers
  * SIGSVGD_E_BADARG).  They run on the fp64 kernels: sigsvgd_gram_fwd / _fwd_bwd wherever the coverage kernel's plan fits,
  * and the long-path entry points (sigsvgd_gram_long_*, sigsvgd_pair_*) with the default stencil only --
- * SIGSVGD_FLAG_NAIVE_SOLVER with them is SIGSVGD_E_UNSUPPORTED there.  sigsvgd_gram_sym_partial stays RBF-only. */
+ * SIGSVGD_FLAG_NAIVE_SOLVER with them is SIGSVGD_E_UNSUPPORTED there.  sigsvgd_gram_sym_partial refuses them unless
+ * SIGSVGD_FLAG_FP32_SWEEPS sends them to the register-resident kernel (3 <= T <= 64; see the flag). */
 #define SIGSVGD_STATIC_IMQ 2    /* k(x,y) = (1 + s)^(-1/2)          (inverse multiquadric)     */
 #define SIGSVGD_STATIC_RQ 3     /* k(x,y) = (1 + s)^(-1)            (rational quadratic)       */
 /* The Matern kinds, accepted by a later revision of ABI 10 (again no new symbol and no changed
@@ -142,6 +143,16 @@ extern "C" {
                                       /* their mirror images ntile-1 - (tile_offset + k*tile_stride): a tile and its mirror image  */
                                       /* together always hold the same number of pairs of the upper triangle, so every rank of   */
                                       /* the sharded step gets the same share (cyclic ownership alone: +5.4 % on the first rank)    */
+#define SIGSVGD_FLAG_FP32_SWEEPS 128u  /* IMQ / rational-quadratic static kernel (SIGSVGD_STATIC_IMQ, _RQ) at dyadic order 0, 3 <= T <= 64,   */
+                                      /* d <= 16, default stencil: run the register-resident fp32-sweep kernel RBF runs there instead of  */
+                                      /* the fp64 coverage kernel.  Opt-in because it selects that kernel's        */
+                                      /* accuracy contract (above: every entry of K within 1e-5 relative, the gradient within 1e-5 of its  */
+                                      /* largest entry; the per-pair checks and the fp64 repair of K apply) where the default holds these  */
+                                      /* kinds to fp64 results.  sigsvgd_gram_fwd / _fwd_bwd / _workspace_bytes and                         */
+                                      /* sigsvgd_gram_sym_partial take it.  One-channel Gram + gradient launches stay on the coverage      */
+                                      /* kernel as for RBF; with any other kind, shape, order, SIGSVGD_FLAG_NAIVE_SOLVER or                */
+                                      /* SIGSVGD_FLAG_FORCE_GENERIC the bit is accepted and ignored (as it was before this revision of     */
+                                      /* ABI 10, which adds no symbol and changes no signature)                                             */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */

@@ -26,11 +26,11 @@ elif sys.argv[1] == "run":
     import pytest
 
     files = ["tests/test_gpu_fast.py", "tests/test_gpu_longpaths.py", "tests/test_gpu_dyadic.py", "tests/test_gpu_precision.py",
-             "tests/test_gpu_partition.py"]
+             "tests/test_gpu_partition.py", "tests/test_gpu_fast_static.py"]
     rc = pytest.main(["-q", "-m", "gpu", "-x"] + [os.path.join(ROOT, f) for f in files])
     L = ctypes.CDLL(LIB)
     words = {}
-    for unit in ("fast", "quad", "dyad"):
+    for unit in ("fast", "fast_radial", "quad", "dyad"):
         fn = getattr(L, f"sigsvgd_debug_exec_violations_{unit}")
         fn.restype = ctypes.c_uint
         words[unit] = fn()

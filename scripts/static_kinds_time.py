@@ -1,6 +1,6 @@
 """Time the built-in static kernels next to each other on the routes that take all of them.
 
-    python scripts/static_kinds_time.py [--reps 10]
+    python scripts/static_kinds_time.py [--reps 10] [--fp32-sweeps]
 
 Prints one JSON line per shape: milliseconds per Gram + gradient launch, [median, min, max] of `reps` timed with device
 events after warm-up, for RBF (the yardstick; on the coverage kernel with force_generic=True, since RBF alone has the
@@ -8,7 +8,10 @@ fp32-sweep kernels), IMQ, the rational quadratic kernel and the two Matern kerne
   coverage kernel  N = 100, T = 10, d = 2, order 4 and N = 256, T = 64, d = 7, order 0: ops.gram_fwd_bwd(X, X, y_is_x=True);
   long route       A = B = 32, T = 512, d = 4, order 0: ops.gram_long_fwd_bwd(X, X).
 Next to the first shape: the user route of the same IMQ kernel (torch builds the [N, N, T, T] grid, sig_pde.hip solves it,
-autograd chains dG to X) and the peak device memory of both routes."""
+autograd chains dG to X) and the peak device memory of both routes.
+--fp32-sweeps prints instead, for N = 256 and N = 1024 at T = 64, d = 7, order 0, Y = X, one line with
+RBF on the register-resident kernel (the default route), IMQ and the rational quadratic kernel on it (`fp32_sweeps=True`) and
+both on the coverage kernel (their default route), all in this one process."""
 import argparse
 import json
 import os
@@ -43,9 +46,22 @@ def peak_mb(fn):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--fp32-sweeps", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
+    if a.fp32_sweeps:
+        for N in (256, 1024):
+            T, d = 64, 7
+            X = (torch.randn(N, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).float().to(dev)
+            res = {"route": "fast against coverage", "shape": [N, T, d], "order": 0}
+            res["rbf_fast"] = timed(lambda: ops.gram_fwd_bwd(X, X, 1.0, 0, KINDS["rbf"], y_is_x=True), a.reps)
+            for name in ("imq", "rq"):
+                res[name + "_fast"] = timed(lambda: ops.gram_fwd_bwd(X, X, 1.0, 0, KINDS[name], y_is_x=True, fp32_sweeps=True), a.reps)
+            for name in ("imq", "rq"):
+                res[name + "_coverage"] = timed(lambda: ops.gram_fwd_bwd(X, X, 1.0, 0, KINDS[name], y_is_x=True), a.reps)
+            print(json.dumps(res), flush=True)
+        return
     for (N, T, d, order) in [(100, 10, 2, 4), (256, 64, 7, 0)]:
         X = (torch.randn(N, T, d, generator=g, dtype=torch.float64) / T**0.5).cumsum(1).float().to(dev)
         res = {"route": "coverage", "shape": [N, T, d], "order": order}

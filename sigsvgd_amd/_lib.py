@@ -14,12 +14,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 # SIGSVGD_LIB_PATH: A/B benchmarking of two builds on the same GPU box (scripts/ab.py); never set in tests
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
-SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_quad.hip", "svgd_phi.hip",
+SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "gram_quad.hip", "svgd_phi.hip",
            "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
            "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
            "pair_bands_matern.hip", "sqdist_select.hip"]
 HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"), os.path.join(_CSRC, "ring_sweep.h"),
-           os.path.join(_CSRC, "long_static.h"), os.path.join(_CSRC, "pair_bands.h"),  # (pair_bands_f32.hip and pair_bands_matern.hip include pair_bands.hip, gram_long_matern.hip includes gram_long.hip: all in SOURCES)
+           os.path.join(_CSRC, "long_static.h"), os.path.join(_CSRC, "pair_bands.h"),  # (pair_bands_f32.hip and pair_bands_matern.hip include pair_bands.hip, gram_long_matern.hip includes gram_long.hip, gram_fast_radial.hip includes gram_fast.hip: all in SOURCES)
            os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
 # mirror of include/sigsvgd_hip.h
@@ -28,6 +28,7 @@ STATIC_RBF, STATIC_LINEAR, STATIC_IMQ, STATIC_RQ = 0, 1, 2, 3
 STATIC_MATERN32, STATIC_MATERN52 = 6, 7  # (4 and 5 are reserved: the library refuses them)
 FLAG_NAIVE_SOLVER, FLAG_SYM, FLAG_Y_IS_X, FLAG_FORCE_GENERIC, FLAG_WS_CLEAN, FLAG_STORED_FORWARD = 1, 2, 4, 8, 16, 32
 FLAG_FOLD_TILES = 64
+FLAG_FP32_SWEEPS = 128
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 ABI_VERSION = 10

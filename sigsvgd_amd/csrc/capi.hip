@@ -314,10 +314,16 @@ static bool band_parallel(int A, int B, int T, int d, int n, bool sym)
 // more, r >= 4) and, for one-channel paths, at 64 cells too: their very smooth regime wants the two-float add in both sweeps.
 // `partial`: the symmetric partial solve, which has the register-resident and quadrant kernels only (any other route: it does
 // not take the launch) and keeps them for one-channel paths.
+// SIGSVGD_FLAG_FP32_SWEEPS is the caller's opt-in to the register-resident kernel for the IMQ and
+// rational-quadratic kernels with the default stencil at that kernel's shapes -- the one-channel gradient rule first, as for RBF.
+// In every other case the bit changes nothing: without it every route is what it was.
 static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigned flags, int want_grad, bool partial = false)
 {
     const bool fp32 = kind == SIGSVGD_STATIC_RBF && !(flags & SIGSVGD_FLAG_NAIVE_SOLVER);
     if (flags & SIGSVGD_FLAG_FORCE_GENERIC) return GramRoute::GenericPrecise;
+    if ((flags & SIGSVGD_FLAG_FP32_SWEEPS) && (kind == SIGSVGD_STATIC_IMQ || kind == SIGSVGD_STATIC_RQ) &&
+        !(flags & SIGSVGD_FLAG_NAIVE_SOLVER) && fast_supported(T, d, n) && (partial || !(want_grad && d == 1)))
+        return GramRoute::Fast;
     // IMQ, the rational quadratic and the Matern kernels have fp64 kernels only and are held to fp64 results: the plan that keeps
     // the increments in fp64 wherever their table (or the per-band layout) fits, what FORCE_GENERIC selects (DESIGN.md sections
     // 5.15, 5.17)
@@ -340,10 +346,10 @@ static GramRoute gram_route(const GramProblem &p, bool partial = false)
 }
 
 // the workspace plan of a launch on route r; sym: the Y_IS_X orientation
-static int route_plan(GramRoute r, int A, int B, int T, int d, int n, int want_grad, bool sym, WsPlan &w)
+static int route_plan(GramRoute r, int A, int B, int T, int d, int n, int kind, int want_grad, bool sym, WsPlan &w)
 {
     switch (r) {
-    case GramRoute::Fast: w = fast_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
+    case GramRoute::Fast: w = fast_plan(A, B, T, d, want_grad, sym, 0, 1, false, kind); return SIGSVGD_OK;
     case GramRoute::Quad: w = quad_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
     case GramRoute::Dyad: w = dyad_plan(A, B, T, d, want_grad, sym); return SIGSVGD_OK;
     case GramRoute::BandParallel: w = band_plan(A, B, T, d, n, want_grad, sym, false); return SIGSVGD_OK;
@@ -394,7 +400,7 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
         const GramRoute r = gram_route(A, B, T, d, dyadic_order, static_kind, f, want_grad, partial);
         if (partial && r != GramRoute::Fast && r != GramRoute::Quad) return (int)SIGSVGD_OK; // (not a partial-solve shape)
         WsPlan w;
-        const int rc = route_plan(r, A, B, T, d, dyadic_order, want_grad, sym, w);
+        const int rc = route_plan(r, A, B, T, d, dyadic_order, static_kind, want_grad, sym, w);
         if (w.total() > most) most = w.total();
         return rc;
     };
@@ -445,7 +451,8 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     const GramRoute r = gram_route(p, true);
     if (r != GramRoute::Fast && r != GramRoute::Quad) {
-        set_error("sym_partial: shape/kernel outside the register-resident and quadrant kernels (need 3<=T<=128, d<=16, RBF)");
+        set_error("sym_partial: shape/kernel outside the register-resident and quadrant kernels (need 3<=T<=128, d<=16 and RBF, or "
+                  "3<=T<=64, d<=16 and IMQ / rational quadratic with SIGSVGD_FLAG_FP32_SWEEPS)");
         return SIGSVGD_E_UNSUPPORTED;
     }
     if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride)

@@ -37,6 +37,7 @@
 // static kernel src/kernels/_traj_kernels.py:176-195; callers src/inference/score.py:68-69.
 #include <atomic>
 #include <cstdlib>
+#include <type_traits>
 
 #include "sig_common.h"
 
@@ -102,6 +103,13 @@ struct FastArgs {
                                 // waves of the older and of the younger half of every workgroup
 #endif
 };
+// The arguments of the RADIAL instantiations: FastArgs and the static kernel's kind, SIGSVGD_STATIC_IMQ or _RQ
+// (wave-uniform).  A struct of its own, so that the RBF kernels keep their argument layout and with it their code.
+struct FastRadialArgs : FastArgs {
+    int kind;
+};
+template <int RADIAL>
+using FastArgsOf = std::conditional_t<RADIAL != 0, FastRadialArgs, FastArgs>;
 
 // ---- wave-wide shifts on the DPP path ----------------------------------------------------------
 // wave_shr:1 (0x138): lane l reads lane l-1; wave_shl:1 (0x130): lane l reads lane l+1.
@@ -498,6 +506,17 @@ __device__ __forceinline__ double resweep_fwd_fp64(const float (&Dsl)[RING], int
     return cur;
 }
 
+// ---- the heavy-tailed static kernels of the RADIAL instantiations --------------------------------------------
+// 1 / sqrt(x) for x = 1 + s >= 1: the hardware estimate and one step of third order (e = 1 - x y^2; y (1 + e/2 + 3 e^2/8)),
+// which is what the math library's rsqrt does after its range and special-value handling -- none of which 1 + s needs (a NaN
+// stays a NaN and poisons its row / column of K, as RBF's does).  The increments are rounded to fp32 right after.
+__device__ __forceinline__ double rsqrt_ge1(double x)
+{
+    const double y = __builtin_amdgcn_rsq(x);
+    const double e = __builtin_fma(-(x * y), y, 1.0);
+    return __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
+}
+
 // [slot][lane] image of G (then R*G) with row stride 65 floats: every in-sweep access is
 // lane*4 + constant (one ds instruction with an immediate offset, nothing to keep in registers),
 // and the transposed read of the symmetric pass ((m+n)&63)*65 + m hits 32 distinct banks.
@@ -521,16 +540,21 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // PFIX: 0, or the launch's P = T - 1 as a compile-time constant: the sweeps then build their EXEC windows from immediates (see
 // "fixed windows" above; gradient kernels of the 64-slot ring at T = 64).  Nothing else of the kernel depends on it.
 // BAL: 0, or the wave-balance schedule of the pair (see bal_top above); it adds the s_setprio and their branches, nothing else.
-template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0>
+// RADIAL: 0 the RBF static kernel; 1 the inverse multiquadric or the rational quadratic, told apart by the wave-uniform a.kind
+// (DESIGN.md 5.18).  Phase 1 then evaluates k = phi(s), s = |x~ - y~|^2 inv_h clamped at 0, in place of the exponential, and the
+// G image holds -phi'(s) where RBF's holds k (for RBF the two are the same number); nothing after `rd = g - gprev` depends on it.
+// General windows only (no PFIX, no BAL); instantiated in gram_fast_radial.hip.
+template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0, int RADIAL = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : 2),
-    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgs a)
+    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgsOf<RADIAL> a)
 {
     constexpr int DC = LP ? DPAD - 1 : DPAD; // channels that can be non-zero
     constexpr int NT = NW * 64;
     constexpr int RM = RING - 1;
     constexpr int RPW = (RING == 32) ? 2 : 1; // rows (trajectories i) per wavefront
     constexpr int NWR = NW * RPW;             // rows per tile
+    static_assert(RADIAL == 0 || (PFIX == 0 && BAL == 0), "the radial kinds: general windows, no wave balance");
     static_assert(BAL == 0 || (GRAD && SYM && RING == 64 && NW == 8 && PFIX != 0 && (BAL & 3) != 0 && BAL < 8),
                   "wave balance: the symmetric gradient kernels with fixed windows on 8-wave workgroups (the ones SIG_PRIO leaves alone)");
     // y rows are stored twice (row r and r + 64) so that the skewed row (t - lane) & 63 becomes
@@ -624,7 +648,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             }
         }
     };
-    const double nscale = -inv_h * 1.4426950408889634074; // exponent scale: exp(-d/h) = 2^(nscale*d)
+    // (RADIAL: the plain scale of s = |x~ - y~|^2 inv_h -- no log2 e, positive)
+    const double nscale = RADIAL ? inv_h : -inv_h * 1.4426950408889634074; // exponent scale: exp(-d/h) = 2^(nscale*d)
     auto stage_store = [&]() {
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
@@ -732,6 +757,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             }
             // everything downstream of the static kernel works with G / sqrt(12): the increments become
             // gamma = D / sqrt(12) (stencil below), and the gradient pass multiplies the scale back (m2h)
+            if constexpr (RADIAL) xn = xn * nscale; // (the 1 / sqrt(12) is a factor of k, below)
+            else
             xn = __builtin_fma(xn, nscale, -1.79248125036057809); // - log2(sqrt(12))
 
             // ---- phase 1: G rows (skewed: column (t - lane) & 63 on iteration t) -> D slots --------
@@ -761,8 +788,17 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                         }
 #pragma unroll
                         for (int c = 0; c < DC; ++c) e2 = __builtin_fma(xs[c], ycu[c], e2);
+                        if constexpr (RADIAL) {
+                            // e2 is s (rounding leaves it a few ulp below 0 for coincident points; a NaN stays one).  k_imq =
+                            // (1 + s)^-1/2 and k_rq = k_imq^2; -phi' = k_imq^3 / 2 and k_imq^4; both carry the 1 / sqrt(12)
+                            const double ki = rsqrt_ge1(1.0 + (e2 < 0.0 ? 0.0 : e2)), ki2 = ki * ki;
+                            const bool rq = a.kind == SIGSVGD_STATIC_RQ;
+                            g = (rq ? ki2 : ki) * 0.28867513459481288225;
+                            if (GRAD) Gs[gs_index(t, lane)] = (float)((rq ? ki2 : 0.5 * ki) * (ki2 * 0.28867513459481288225));
+                        } else {
                         g = exp2_p7(e2);
                         if (GRAD) Gs[gs_index(t, lane)] = (float)g;
+                        }
                         if (t == 0) g0 = g;
                         if (t == 1) g1 = g;
                     } else {
@@ -1138,6 +1174,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #endif
 }
 
+#ifndef SIGSVGD_GRAM_FAST_RADIAL // (everything from here to the launchers is gram_fast.hip's own translation unit's)
 // ---- fixed-order reduction of the gradient partials -----------------------------------------------------------------
 // One thread per output element (i, t, c).  Row side: the segments of row i's tile, one per workgroup whose item range
 // met the tile, in workgroup order.  Column side (symmetric launches): the items (tile, column i) of every owned tile
@@ -1378,6 +1415,7 @@ static bool fixed_windows(int T, int want_grad)
     const char *e = getenv("SIGSVGD_SWEEP_WINDOWS");
     return !(e && e[0] == 't');
 }
+#endif // SIGSVGD_GRAM_FAST_RADIAL
 
 // The symmetric 4- and 8-channel gradient kernels with fixed windows have a twin with the wave-balance schedule (BAL, see bal_top);
 // launches that reach them run the twin.  SIGSVGD_WAVE_BALANCE=off, read per launch next to SIGSVGD_SWEEP_WINDOWS, keeps them
@@ -1393,6 +1431,7 @@ constexpr int FAST_BAL = SIG_EXPERIMENT_BALANCE;
 // ordered 8-channel kernel was built with it in place of SIG_PRIO and lost 0.6-1.3 %: it keeps SIG_PRIO.
 template <int DPAD, bool SYM>
 constexpr bool fast_has_balance() { return FAST_BAL != 0 && SYM && DPAD <= 8; }
+#ifndef SIGSVGD_GRAM_FAST_RADIAL
 static bool wave_balance(int T, int d, int want_grad, bool sym)
 {
     if (!sym || d > 8 || !fast_has_balance<8, true>() || !fixed_windows(T, want_grad)) return false;
@@ -1401,11 +1440,13 @@ static bool wave_balance(int T, int d, int want_grad, bool sym)
 }
 
 // [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
-WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold)
+// (kind: the IMQ and rational-quadratic launches have the general-window kernels only; the areas are kind-independent)
+WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold, int kind)
 {
     WsPlan w;
-    w.fixed_windows = fixed_windows(T, want_grad) ? 1 : 0;
-    w.wave_balance = wave_balance(T, d, want_grad, sym) ? 1 : 0;
+    const bool rbf = kind == SIGSVGD_STATIC_RBF;
+    w.fixed_windows = rbf && fixed_windows(T, want_grad) ? 1 : 0;
+    w.wave_balance = rbf && wave_balance(T, d, want_grad, sym) ? 1 : 0;
     if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
     if (want_grad) {
         w.g = fast_geometry(A, B, T, d, sym, off, stride, fold);
@@ -1414,14 +1455,20 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
     }
     return w;
 }
+#endif // SIGSVGD_GRAM_FAST_RADIAL
+
+// The launch of the RADIAL = 1 instantiations (kinds IMQ and rational quadratic, a.kind), which compile in a translation unit of
+// their own, gram_fast_radial.hip: it includes this file with SIGSVGD_GRAM_FAST_RADIAL defined and builds the kernel, the
+// launchers below for RADIAL = 1 and this one function; everything else of this file is the other translation unit's.
+int fast_radial_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows);
 
 namespace {
 // a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths, or
-// (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule
-template <int DPAD, int NW, bool SYM, bool LP, int RING>
-void launch_grad(bool fix, bool bal, dim3 grid, dim3 block, hipStream_t stream, const FastArgs &a)
+// (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule; RADIAL has neither twin
+template <int DPAD, int NW, bool SYM, bool LP, int RING, int RADIAL>
+void launch_grad(bool fix, bool bal, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
 {
-    if constexpr (RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
+    if constexpr (RADIAL == 0 && RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
         if constexpr (fast_has_balance<DPAD, SYM>()) {
             if (fix && bal) {
                 hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, FAST_BAL>), grid, block, 0, stream, a);
@@ -1433,10 +1480,10 @@ void launch_grad(bool fix, bool bal, dim3 grid, dim3 block, hipStream_t stream, 
             return;
         }
     }
-    hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING>), grid, block, 0, stream, a);
+    hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 0, 0, RADIAL>), grid, block, 0, stream, a);
 }
 
-template <int DPAD, int NW, int RING = 64>
+template <int RADIAL, int DPAD, int NW, int RING = 64>
 int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
 {
     // items of this launch: (owned row tile, column); symmetric launches only the columns from the tile's first row on
@@ -1465,20 +1512,23 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     }
     constexpr bool HAS_LP = DPAD <= 8; // the d == DPAD - 1 instantiations exist for the 4- and 8-channel layouts
     const bool lp = HAS_LP && grad && p.d == DPAD - 1;
+    FastArgsOf<RADIAL> ka{}; // the kernel's arguments: `a`, and for the radial kinds the kind
+    static_cast<FastArgs &>(ka) = a;
+    if constexpr (RADIAL != 0) ka.kind = p.kind;
     const bool fix = grad && w.fixed_windows && p.T == 64; // (the kernel's PFIX must be the launch's T - 1)
     const bool bal = fix && w.wave_balance;
     if (!grad && sym)
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING>), grid, block, 0, p.stream, a);
+        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (!grad)
-        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING>), grid, block, 0, p.stream, a);
+        hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (sym && lp)
-        launch_grad<DPAD, NW, true, HAS_LP, RING>(fix, bal, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, true, HAS_LP, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
     else if (sym)
-        launch_grad<DPAD, NW, true, false, RING>(fix, bal, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, true, false, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
     else if (lp)
-        launch_grad<DPAD, NW, false, HAS_LP, RING>(fix, bal, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, false, HAS_LP, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
     else
-        launch_grad<DPAD, NW, false, false, RING>(fix, bal, grid, block, p.stream, a);
+        launch_grad<DPAD, NW, false, false, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS
@@ -1492,19 +1542,21 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     return SIGSVGD_OK;
 }
 
+template <int RADIAL>
 int dispatch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
 {
     if (!grad && p.d <= 4) // forward only: no G image, <=168 VGPRs -> 4-wave workgroups pack 3 waves per SIMD
-        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<4, 4>(p, a, w, false, sym, tile_rows);
+        return p.T <= 32 ? launch_variant<RADIAL, 4, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<RADIAL, 4, 4>(p, a, w, false, sym, tile_rows);
     if (!grad && p.d <= 8)
-        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<8, 4>(p, a, w, false, sym, tile_rows);
+        return p.T <= 32 ? launch_variant<RADIAL, 8, 4, 32>(p, a, w, false, sym, tile_rows) : launch_variant<RADIAL, 8, 4>(p, a, w, false, sym, tile_rows);
     if (p.d <= 4) // (paths of <= 32 points: the 32-slot ring on 4-wave workgroups, three per CU = 3 waves per SIMD)
-        return p.T <= 32 ? launch_variant<4, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<4, 8>(p, a, w, grad, sym, tile_rows);
+        return p.T <= 32 ? launch_variant<RADIAL, 4, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<RADIAL, 4, 8>(p, a, w, grad, sym, tile_rows);
     if (p.d <= 8)
-        return p.T <= 32 ? launch_variant<8, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<8, 8>(p, a, w, grad, sym, tile_rows);
-    return launch_variant<16, 4>(p, a, w, grad, sym, tile_rows); // 1 wave per SIMD: 512-VGPR budget, no spills
+        return p.T <= 32 ? launch_variant<RADIAL, 8, 4, 32>(p, a, w, grad, sym, tile_rows) : launch_variant<RADIAL, 8, 8>(p, a, w, grad, sym, tile_rows);
+    return launch_variant<RADIAL, 16, 4>(p, a, w, grad, sym, tile_rows); // 1 wave per SIMD: 512-VGPR budget, no spills
 }
 
+#ifndef SIGSVGD_GRAM_FAST_RADIAL
 // cut the workspace from the plan, enqueue the kernel over the row tiles `own` says (off / stride / fold: the tile count is the
 // kernel's), the fp64 pass and (gradient) the reduction into `out`
 int run(const GramProblem &p, const WsPlan &w, bool sym, const TileMap &own, void *out, int out64)
@@ -1516,16 +1568,25 @@ int run(const GramProblem &p, const WsPlan &w, bool sym, const TileMap &own, voi
     fill_sweep_args(a, p, w, base);
     a.tm = own;
     int tile_rows = 0;
-    rc = dispatch_variant(p, a, w, out != nullptr, sym, tile_rows);
+    rc = p.kind == SIGSVGD_STATIC_RBF ? dispatch_variant<0>(p, a, w, out != nullptr, sym, tile_rows)
+                                      : fast_radial_dispatch(p, a, w, out != nullptr, sym, tile_rows);
     if (rc) return rc;
     return finish_launch(p, w, base, sym, a.tm, tile_rows, out, out64);
 }
+#endif // SIGSVGD_GRAM_FAST_RADIAL
 } // namespace
+
+#ifdef SIGSVGD_GRAM_FAST_RADIAL
+int fast_radial_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows)
+{
+    return dispatch_variant<1>(p, a, w, grad, sym, tile_rows);
+}
+#else
 
 int fast_launch(const GramProblem &p)
 {
     const bool sym = (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B; // Y is X: each unordered pair once, K mirrored
-    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym);
+    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, p.gradX_out != nullptr, sym, 0, 1, false, p.kind);
     return run(p, w, sym, make_tilemap(1, 0, 1, false), p.gradX_out, p.dtype == SIGSVGD_F64);
 }
 
@@ -1534,11 +1595,16 @@ int fast_launch(const GramProblem &p)
 // grad_partial[N,T,d] (fp64) is OVERWRITTEN with this launch's share of the gradient (rows it does not touch get 0).
 int fast_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial)
 {
-    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold);
+    const WsPlan w = fast_plan(p.A, p.B, p.T, p.d, 1, true, tile_offset, tile_stride, fold, p.kind);
     return run(p, w, true, make_tilemap((p.A + grad_nw(p.T, p.d) - 1) / grad_nw(p.T, p.d), tile_offset, tile_stride, fold),
                grad_partial, 1);
 }
 
+#endif // SIGSVGD_GRAM_FAST_RADIAL
 } // namespace sigsvgd
 
+#ifdef SIGSVGD_GRAM_FAST_RADIAL
+SIG_EXEC_DEBUG_GETTER(fast_radial)
+#else
 SIG_EXEC_DEBUG_GETTER(fast)
+#endif

@@ -431,7 +431,8 @@ int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool
 
 // register-resident fast path (n == 0, T <= 64) -- gram_fast.hip; off / stride / fold: the row tiles a partial solve owns
 bool fast_supported(int T, int d, int n);
-WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false);
+WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false,
+                 int kind = SIGSVGD_STATIC_RBF); // (IMQ / rational quadratic with SIGSVGD_FLAG_FP32_SWEEPS: general windows only)
 int fast_launch(const GramProblem &p);
 int fast_sym_partial(const GramProblem &p, int tile_offset, int tile_stride, bool fold, double *grad_partial);
 int sym_tile_rows_fast(int T, int d); // rows per tile of the gradient launches (ownership unit of the partial solve)

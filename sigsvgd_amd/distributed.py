@@ -137,7 +137,11 @@ class ShardedSigSVGD:
     row-wise step
     takes `ops.gram_long_fwd_bwd` at a shape only the long route takes.  long_partial=True sends every
     shape the long partial takes to it (each pair once also at 129 <= T <= 190), long_partial=False never uses it.
-    `last_route` names the last step's route ("partial", "rowwise" or "long_partial").
+    `last_route` names the last step's route ("partial", "rowwise" or "long_partial"); `route(X_shard)` answers it without a step.
+    fp32_sweeps=True with static_kind 2 or 3 at order 0: the fused partial solve takes the step at
+    3 <= T <= 64, d <= 16 (`ops.gram_sym_partial(..., static_kind=, fp32_sweeps=True)`: the register-resident kernel, each
+    unordered pair once, K within 1e-5 per entry instead of fp64 results), and the row-wise solve passes the flag too; with
+    any other kind it changes nothing.
 
     update: "manual" (X - lr * v, the reference's optimizer=None), "adagrad" (its adaptive_gradient=True) or "adam"
     (torch.optim.Adam with `betas`, `eps`; lr is its learning rate); mask: multiplies the velocity, broadcastable to the
@@ -155,7 +159,7 @@ class ShardedSigSVGD:
                  fold: bool = True, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                  long_partial: Optional[bool] = None, long_partial_fn: Optional[Callable] = None,
                  update: str = "manual", betas=(0.9, 0.999), eps: float = 1e-8, mask=None,
-                 update_fn: Optional[Callable] = None):
+                 update_fn: Optional[Callable] = None, fp32_sweeps: bool = False):
         if update not in ("manual", "adagrad", "adam"):
             raise ValueError(f'update must be "manual", "adagrad" or "adam", got {update!r}')
         self.update = update
@@ -172,11 +176,18 @@ class ShardedSigSVGD:
         self.fold = bool(fold)
         self.dyadic_order = int(dyadic_order)
         self.static_kind = int(static_kind)
+        self.fp32_sweeps = bool(fp32_sweeps)
+        # the IMQ / rational-quadratic step on the fp32-sweep kernels: the keyword goes to `ops` only where it is set
+        self._fast_radial = self.fp32_sweeps and self.dyadic_order == 0 and self.static_kind in (_lib.STATIC_IMQ, _lib.STATIC_RQ)
+        self._fp32_kw = {"fp32_sweeps": True} if self.fp32_sweeps else {}
         self.long_partial = None if long_partial is None else bool(long_partial)
         self.long_partial_fn = long_partial_fn or ops.gram_long_sym_partial
         self._long_fold = bool(fold)  # (the 4-argument fallback below concerns partial_fn only)
         self.last_route = None
         self._routes = {}
+        if partial_fn is None and self._fast_radial:
+            partial_fn = lambda X, inv_h, off, stride, out=None, fold=False: ops.gram_sym_partial(
+                X, inv_h, off, stride, static_kind=self.static_kind, out=out, fold=fold, fp32_sweeps=True)
         self.partial_fn = partial_fn or ops.gram_sym_partial
         # `out=` / `fold=` are passed only to callables that take them (the 4-argument contract of rounds 1-2 still works;
         # such a callable owns cyclic tiles and allocates its results)
@@ -197,7 +208,7 @@ class ShardedSigSVGD:
         if rows_fn is None and self.static_kind in (_lib.STATIC_IMQ, _lib.STATIC_RQ, _lib.STATIC_MATERN32, _lib.STATIC_MATERN52):
             rows_fn = self._rows_fused_or_long
         elif rows_fn is None and (self.dyadic_order != 0 or self.static_kind != _lib.STATIC_RBF):
-            rows_fn = lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind)
+            rows_fn = lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind, **self._fp32_kw)
         self.rows_fn = rows_fn or (lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h))
         self.rowwise = bool(rowwise)
         self.last_K_partial = None  # ALIASES the step's preallocated buffer: the next step() overwrites it (clone to keep it)
@@ -346,6 +357,14 @@ class ShardedSigSVGD:
             self.phase_ms = mark.result()
         return out
 
+    def route(self, X_shard: torch.Tensor, world: Optional[int] = None) -> str:
+        """The route `step` takes for a shard of this shape ("partial", "rowwise" or "long_partial"), from host-only queries of
+        the library; world: the number of ranks (default: the group's)."""
+        if world is None:
+            world = _world(self.group)[1]
+        n, T, d = X_shard.shape
+        return self._route(n, torch.empty((n * world, T, d), dtype=X_shard.dtype, device="meta"), world)
+
     def _route(self, n_own: int, X_full, world: int) -> str:
         """"partial" (fused), "rowwise" or "long_partial" for this step's shape; see the class docstring for the order"""
         N, T, d = X_full.shape
@@ -363,8 +382,11 @@ class ShardedSigSVGD:
             return "long_partial"
         if self.dyadic_order == 0 and self.static_kind == _lib.STATIC_RBF and self._partial_supported(X_full):
             return "partial"
+        # (IMQ / rational quadratic with fp32_sweeps: the register-resident kernel's lengths only, the quadrant kernel is RBF's)
+        if self._fast_radial and 3 <= T <= 64 and self._partial_supported(X_full):
+            return "partial"
         if self.long_partial is None and self._auto_long \
-                and not ops.gram_takes(n_own, N, T, d, self.dyadic_order, self.static_kind) and takes_long():
+                and not ops.gram_takes(n_own, N, T, d, self.dyadic_order, self.static_kind, **self._fp32_kw) and takes_long():
             return "long_partial"
         return "rowwise"
 
@@ -373,8 +395,8 @@ class ShardedSigSVGD:
         takes the rows' shape, else the long route's ordered launch (a row-wise step at a shape only the long route takes:
         rowwise=True, long_partial=False)."""
         n, T, d = Xs.shape
-        if ops.gram_takes(n, Xf.shape[0], T, d, self.dyadic_order, self.static_kind):
-            return ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind)
+        if ops.gram_takes(n, Xf.shape[0], T, d, self.dyadic_order, self.static_kind, **self._fp32_kw):
+            return ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind, **self._fp32_kw)
         return ops.gram_long_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind)
 
     @staticmethod

@@ -132,7 +132,8 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
     return pad_to_length(X.detach(), T).contiguous(), pad_to_length(Y.detach(), T).contiguous()
 
 
-def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False) -> int:
+def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
+           fp32_sweeps: bool = False) -> int:
     f = 0
     if naive:
         f |= _lib.FLAG_NAIVE_SOLVER
@@ -144,21 +145,23 @@ def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_for
         f |= _lib.FLAG_FORCE_GENERIC
     if stored_forward:
         f |= _lib.FLAG_STORED_FORWARD
+    if fp32_sweeps:
+        f |= _lib.FLAG_FP32_SWEEPS
     return f
 
 
 def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
              naive: bool = False, force_generic: bool = False, y_is_x: bool = False,
-             stored_forward: bool = False) -> torch.Tensor:
+             stored_forward: bool = False, fp32_sweeps: bool = False) -> torch.Tensor:
     """K[A,B] = signature-kernel Gram matrix (forward only).  y_is_x: the caller states that Y holds the
-    same values as X, so each unordered pair is solved once and K is mirrored."""
+    same values as X, so each unordered pair is solved once and K is mirrored.  fp32_sweeps: see `gram_fwd_bwd`."""
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_paths(X, Y)
     A, T, d = Xc.shape
     B = Yc.shape[0]
     if y_is_x and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x needs X and Y of one shape")
-    flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward)
+    flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward, fp32_sweeps)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
                               int(static_kind), flags, K.data_ptr()),
@@ -169,7 +172,8 @@ def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
 def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                  grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
                  y_is_x: bool = False, force_generic: bool = False,
-                 check_regime: bool = True, stored_forward: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                 check_regime: bool = True, stored_forward: bool = False,
+                 fp32_sweeps: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(K[A,B], gradX[A,T,d]) with gradX = d sum(grad_out*K)/dX (first slot); grad_out None = ones.
 
     Bit-reproducible: every reduction over pairs runs in an order fixed by the launch geometry (no floating-point
@@ -179,6 +183,11 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     the fp32-sweep kernels check every pair for cancellation and for its conditioning in the increments and hand the pairs
     that fail to an exact fp64 pass inside the same call; the gradient of such a pair keeps the fp32 solution (its error is
     relative to the largest gradient entry of the launch).  `force_generic=True`: fp64 sweeps for K and the gradient alike.
+    `fp32_sweeps=True` (SIGSVGD_FLAG_FP32_SWEEPS): the IMQ and rational-quadratic static kernels
+    (`static_kind` 2, 3), which by default run on the fp64 coverage kernel and are held to fp64 results, take the
+    register-resident fp32-sweep kernel RBF runs at dyadic order 0, 3 <= T <= 64, d <= 16 -- and with it the accuracy above
+    (K per entry within 1e-5, the gradient within 1e-5 of its largest entry).  One-channel gradient launches stay on the
+    coverage kernel as for RBF; for every other kind, shape, order or solver the argument changes nothing.
     `check_regime` and `stored_forward` are accepted for callers written against earlier versions (when long paths
     could run on a kernel that regenerated the forward solution and declined rough pairs) and have no effect."""
     dev = _require_gpu(X, Y, grad_out)
@@ -188,7 +197,7 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     go = _weights(grad_out, (A, B), Xc.dtype)
     if (y_is_x or sym) and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x / sym need X and Y of one shape")
-    flags = _flags(naive, sym, y_is_x, force_generic, stored_forward)
+    flags = _flags(naive, sym, y_is_x, force_generic, stored_forward, fp32_sweeps)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, T, d), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
@@ -198,11 +207,12 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
 
 
 def gram_takes(A: int, B: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-               want_grad: bool = True, naive: bool = False, sym: bool = False, y_is_x: bool = False) -> bool:
+               want_grad: bool = True, naive: bool = False, sym: bool = False, y_is_x: bool = False,
+               fp32_sweeps: bool = False) -> bool:
     """Whether `gram_fwd` (want_grad False) / `gram_fwd_bwd` take paths [A, T, d] x [B, T, d] with these settings: the
     library's workspace query for the call's flags, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (the
     per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those); any other error raises."""
-    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False)
+    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False, False, fp32_sweeps)
     return _query("gram_workspace_bytes", (int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
                                            1 if want_grad else 0, flags), (ctypes.c_size_t(0),), may_refuse=True)
 
@@ -615,19 +625,21 @@ def _partial_out(out, Xc: torch.Tensor, dev: torch.device) -> Tuple[torch.Tensor
 
 
 def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static_kind: int = _lib.STATIC_RBF,
-                     grad_out: Optional[torch.Tensor] = None, sym: bool = False, out=None, fold: bool = False):
+                     grad_out: Optional[torch.Tensor] = None, sym: bool = False, out=None, fold: bool = False,
+                     fp32_sweeps: bool = False):
     """This rank's share of the symmetric Gram + gradient on the gathered particles X [N,T,d]:
     returns (K_partial [N,N] X.dtype, grad_partial [N,T,d] fp64), zero outside the owned pairs.
     Summed over tile_offset = 0..tile_stride-1 they equal gram_fwd_bwd(X, X, y_is_x=True).
     The launch owns the row tiles (`sym_tile_rows(T, d)` rows each) tile_offset + k*tile_stride; with fold=True also
     their mirror images, which gives every rank the same number of pairs (SIGSVGD_FLAG_FOLD_TILES).
-    `out=(K_partial, grad_partial)` reuses the caller's buffers (K_partial is re-zeroed, grad_partial overwritten)."""
+    `out=(K_partial, grad_partial)` reuses the caller's buffers (K_partial is re-zeroed, grad_partial overwritten).
+    RBF, or with `fp32_sweeps=True` (see `gram_fwd_bwd`) the IMQ and rational-quadratic kernels at T <= 64."""
     dev = _require_gpu(X, grad_out)
     Xc, _ = _prep_paths(X, X)
     N, T, d = Xc.shape
     go = _weights(grad_out, (N, N), Xc.dtype)
     Kp, gp = _partial_out(out, Xc, dev)
-    flags = _flags(False, sym, True, False) | (_lib.FLAG_FOLD_TILES if fold else 0)
+    flags = _flags(False, sym, True, False, False, fp32_sweeps) | (_lib.FLAG_FOLD_TILES if fold else 0)
     _launch(dev, "gram_sym_partial", (Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(static_kind), flags,
                                       int(tile_offset), int(tile_stride), _ptr(go), Kp.data_ptr(), gp.data_ptr()),
             "gram_workspace_bytes", (N, N, T, d, 0, int(static_kind), 1, flags))

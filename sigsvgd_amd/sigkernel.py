@@ -302,12 +302,19 @@ def _resolve_static(static_kernel, X, Y):
     )
 
 
-def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x) -> bool:
+def _fp32_kw(fp32_sweeps) -> dict:
+    """the `fp32_sweeps` keyword of the fused launches and queries, handed over only where it is set (a default SigKernel
+    calls `ops` exactly as it did before the keyword existed)"""
+    return {"fp32_sweeps": True} if fp32_sweeps else {}
+
+
+def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x, fp32_sweeps=False) -> bool:
     """True where the fused Gram kernels refuse the launch (`ops.gram_takes`: their per-pair state outgrows the LDS); the
     built-in static kernels then run on the long route (`ops.gram_long_fwd*`, csrc/gram_long.hip).  Every launch the
     fused kernels take stays on them."""
     T = max(X.shape[1], Y.shape[1])  # (the fused route pads the shorter batch to this length)
-    return not ops.gram_takes(X.shape[0], Y.shape[0], T, X.shape[2], dyadic_order, static_kind, want_grad, naive, sym, y_is_x)
+    return not ops.gram_takes(X.shape[0], Y.shape[0], T, X.shape[2], dyadic_order, static_kind, want_grad, naive, sym, y_is_x,
+                              **_fp32_kw(fp32_sweeps))
 
 
 def _long_yx_route(y_is_x: bool, A: int, want_grad: bool, cus: int) -> bool:
@@ -330,7 +337,7 @@ def _device_cus(X) -> int:
     return torch.cuda.get_device_properties(X.device).multi_processor_count if X.is_cuda else 256
 
 
-def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus) -> bool:
+def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus, fp32_sweeps=False) -> bool:
     """True where `compute_kernel` with a built-in static kernel solves its pairs on the paired route (`ops.pair_fwd*`): every
     shape `ops.pair_takes` takes, except forward-only calls of A^2 <= cus pairs that the fused Gram kernels take.  Such a Gram
     launch is one round of the device, latency-bound like the paired launch but on the fused kernels' fp32 sweeps, so its
@@ -339,38 +346,40 @@ def _pair_route(A, TX, TY, d, static_kind, dyadic_order, want_grad, naive, cus) 
         return False
     if want_grad or A * A > cus:
         return True
-    return not ops.gram_takes(A, A, max(TX, TY), d, dyadic_order, static_kind, False, naive)
+    return not ops.gram_takes(A, A, max(TX, TY), d, dyadic_order, static_kind, False, naive, **_fp32_kw(fp32_sweeps))
 
 
 def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
     """-> (K, gX or None, gY or None): the one place that chooses the launch of a Gram request with a built-in static kernel.
-    cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x); want_x / want_y: the gradients wanted (neither: forward
+    cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps); want_x / want_y: the gradients wanted (neither: forward
     only, grad_out unused); fused_yx: whether a gradient launch of the fused kernels with Y = X is told so (the speculated
     unit-weight launch and `gram_and_grad` are, a backward with real weights is not).
 
     The fused kernels take every launch `ops.gram_takes` grants; the long route takes the rest, each unordered pair once
     where `_long_yx_route` says so.  The long route gets K and both gradients from one `ops.gram_long_fwd_bwd2` launch (one
     solve per pair).  The fused route has no second-slot kernel: gY is the first slot of the swapped launch
-    `ops.gram_fwd_bwd(Y, X, grad_out^T)`, a second launch."""
-    static_kind, inv_h, dyadic_order, naive, sym, y_is_x = cfg
+    `ops.gram_fwd_bwd(Y, X, grad_out^T)`, a second launch.  fp32_sweeps (`SigKernel(..., fp32_sweeps=True)`) goes to the
+    fused launches and their queries; the long route has no such kernels and does not see it."""
+    static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps = cfg
+    fkw = _fp32_kw(fp32_sweeps)
     if not (want_x or want_y):
-        if not _long_route(X, Y, static_kind, dyadic_order, False, naive, False, y_is_x):
-            return ops.gram_fwd(X, Y, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x), None, None
+        if not _long_route(X, Y, static_kind, dyadic_order, False, naive, False, y_is_x, fp32_sweeps):
+            return ops.gram_fwd(X, Y, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x, **fkw), None, None
         if _long_yx_route(y_is_x, X.shape[0], False, _device_cus(X)):
             return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, None, naive, y_is_x=True,
                                           want_gradX=False, want_gradY=False)
         return ops.gram_long_fwd(X, Y, inv_h, dyadic_order, static_kind, naive), None, None
     yx = y_is_x and not want_y  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
-    if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx):
+    if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx, fp32_sweeps):
         if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
             return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x, want_y)
         return (*ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym), None)
     K = gX = gY = None
     if want_x:
-        K, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx and fused_yx)
+        K, gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx and fused_yx, **fkw)
     if want_y:  # the second slot is the first slot of the swapped launch
         Kt, gY = ops.gram_fwd_bwd(Y, X, inv_h, dyadic_order, static_kind, None if grad_out is None else grad_out.T, naive,
-                                  False, False)
+                                  False, False, **fkw)
         K = Kt.T.contiguous() if K is None else K
     return K, gX, gY
 
@@ -401,8 +410,8 @@ class _SigKernelGram(torch.autograd.Function):
     Any other grad_output triggers one more launch with the real weights.  `_solve_gram` chooses every launch."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y):
-        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x)
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y, fp32_sweeps=False):
+        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps)
         ctx.g_ones = ctx.gy_ones = None
         ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
         ctx.y_dtype = Y.dtype
@@ -424,7 +433,7 @@ class _SigKernelGram(torch.autograd.Function):
             _, gX, gY = _solve_gram(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
         if gY is not None:
             gY = gY.to(ctx.y_dtype)
-        return gX, gY, None, None, None, None, None, None, None, None
+        return gX, gY, None, None, None, None, None, None, None, None, None
 
 
 class _SigKernelPair(torch.autograd.Function):
@@ -552,12 +561,19 @@ class _SigKernelPairSigma(torch.autograd.Function):
 
 
 class SigKernel:
-    """Signature kernel with a static kernel and a dyadic refinement order (PDE solver)."""
+    """Signature kernel with a static kernel and a dyadic refinement order (PDE solver).
 
-    def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False):
+    fp32_sweeps=True: `IMQStaticKernel` and `RationalQuadraticKernel` Gram launches at dyadic order 0,
+    3 <= T <= 64, d <= 16 run on the register-resident fp32-sweep kernel RBF runs there (K per entry within 1e-5, the gradient
+    within 1e-5 of its largest entry) instead of the fp64 coverage kernel; everything else is unchanged.  It reaches the fused
+    Gram launches only: the long route, the paired route of `compute_kernel` and a learned sigma (a `sigma` tensor that requires
+    grad takes the long route's bandwidth launch, section 5.16) ignore it."""
+
+    def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False):
         self.static_kernel = static_kernel
         self.dyadic_order = int(dyadic_order)
         self._naive_solver = bool(_naive_solver)
+        self.fp32_sweeps = bool(fp32_sweeps)
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
@@ -591,7 +607,7 @@ class SigKernel:
             return _SigKernelGramSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver,
                                              bool(sym), y_is_x, self.speculate_ones, bool(grad_Y))
         return _SigKernelGram.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver, bool(sym),
-                                    y_is_x, self.speculate_ones, bool(grad_Y))
+                                    y_is_x, self.speculate_ones, bool(grad_Y), self.fp32_sweeps)
 
     # -- the rest of the upstream `sigkernel.SigKernel` surface [RECALLED from the public package; the
     #    reference tree never calls these].  compute_kernel / compute_distance differentiate both arguments (each its
@@ -617,7 +633,7 @@ class SigKernel:
         if static_kind is not None:
             want_grad = torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)
             if _pair_route(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], static_kind, self.dyadic_order, want_grad,
-                           self._naive_solver, _device_cus(X)):
+                           self._naive_solver, _device_cus(X), self.fp32_sweeps):
                 return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver)
         return self.compute_Gram(X, Y).diagonal()
 
@@ -641,7 +657,7 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
-        cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None)
+        cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None, self.fp32_sweeps)
         return _solve_gram(X, Yv, cfg, grad_out, True, False, True)[:2]
 
     def _user_gram_and_grad(self, X, Y, grad_out, sym):
