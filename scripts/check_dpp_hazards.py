@@ -93,7 +93,7 @@ def check_disassembly(text: str):
 
 
 # ---- second check: the sweep statements' EXEC discipline ----------------------------------------------------------------
-# The hand-written sweep statements (csrc/gram_fast.hip, csrc/quad_sweeps.h) move lane windows into EXEC and leave it at all
+# The hand-written sweep statements (csrc/gram_fast_kernel.h, csrc/quad_sweeps.h) move lane windows into EXEC and leave it at all
 # ones.  EXEC is a reserved register for hipcc (a clobber on it is ignored with a warning), so the statements are only correct
 # where the compiler's own EXEC is all ones: in wave-uniform control flow.  On the disassembly that reads: no statement -- an
 # `s_mov_b64 exec, -1` directly followed by a wave_shr / wave_shl DPP move -- may lie

@@ -14,13 +14,14 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 # SIGSVGD_LIB_PATH: A/B benchmarking of two builds on the same GPU box (scripts/ab.py); never set in tests
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
-SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "gram_quad.hip", "svgd_phi.hip",
-           "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip", "gram_band.hip",
-           "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
+SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "sweep_host.hip", "gram_quad.hip",
+           "svgd_phi.hip", "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip",
+           "gram_band.hip", "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
            "pair_bands_matern.hip", "sqdist_select.hip"]
-HEADERS = [os.path.join(_CSRC, "sig_common.h"), os.path.join(_CSRC, "quad_sweeps.h"), os.path.join(_CSRC, "ring_sweep.h"),
-           os.path.join(_CSRC, "long_static.h"), os.path.join(_CSRC, "pair_bands.h"),  # (pair_bands_f32.hip and pair_bands_matern.hip include pair_bands.hip, gram_long_matern.hip includes gram_long.hip, gram_fast_radial.hip includes gram_fast.hip: all in SOURCES)
-           os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
+# every header of csrc/ (a source includes headers only), then the public header, which stays the last element
+HEADERS = [os.path.join(_CSRC, h) for h in ("sig_common.h", "quad_sweeps.h", "ring_sweep.h", "long_static.h", "pair_bands.h",
+                                            "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h")] + \
+          [os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
 # mirror of include/sigsvgd_hip.h
 F32, F64 = 0, 1
@@ -142,7 +143,7 @@ def _build_to(lib_path: str, objdir: str, verbose: bool, defines=()) -> str:
 
 def _check_dpp_hazards(lib_path: str) -> None:
     """The kernels' inline-asm DPP moves/adds rely on hipcc's schedule for the 2 wait states after a VALU
-    write of their source (csrc/gram_fast.hip); verify that on the disassembly of what was just built and
+    write of their source (csrc/gram_fast_kernel.h); verify that on the disassembly of what was just built and
     refuse the library otherwise (scripts/check_dpp_hazards.py)."""
     import importlib.util
 

@@ -156,7 +156,7 @@ __device__ __forceinline__ float shfl_up_zero(float v) // lane l <- lane l-1, la
 }
 
 // Sum over the lanes in DPP adds (no LDS round trip).  Lane 31 ends with the total of lanes 0 .. 31; lane 63 with the
-// total of ALL 64 lanes if `WHOLE`, else of lanes 32 .. 63 (two pairs per wavefront in gram_fast.hip).
+// total of ALL 64 lanes if `WHOLE`, else of lanes 32 .. 63 (two pairs per wavefront in gram_fast_kernel.h).
 template <bool WHOLE>
 __device__ __forceinline__ float wave_sum_dpp(float v)
 {
@@ -185,7 +185,7 @@ __device__ __forceinline__ float max3_abs(float m, float a, float b)
         ph_[i] += now_ - tlast_;                                             \
         tlast_ = now_;                                                       \
     }
-constexpr int kMaxPhases = 32; // (gram_fast.hip keeps two sets of its 9: one per half of the workgroup)
+constexpr int kMaxPhases = 32; // (gram_fast_kernel.h keeps two sets of its 9: one per half of the workgroup)
 // the per-phase totals of the next launch on `stream`, zeroed (one buffer: every report below synchronises)
 inline unsigned long long *phase_stamps_begin(hipStream_t stream)
 {
@@ -244,7 +244,7 @@ void phase_stamps_report_halves(hipStream_t stream, const unsigned long long *bu
 #endif
 
 // ---- EXEC discipline of the hand-written sweep statements ----------------------------------------------------------------
-// The sweep statements (gram_fast.hip sweep_fwd8 / sweep_rev8, quad_sweeps.h) move lane windows into EXEC and leave it at
+// The sweep statements (gram_fast_kernel.h sweep_fwd8 / sweep_rev8, quad_sweeps.h) move lane windows into EXEC and leave it at
 // all ones.  EXEC is a reserved register for hipcc: a clobber on it is ignored with a warning ("inline asm clobber list
 // contains reserved registers"), so the compiler cannot be told.  The statements are therefore only correct where the
 // compiler's own EXEC is all ones too, i.e. in wave-uniform control flow -- which every call site is by construction (the
@@ -304,7 +304,7 @@ struct LongProblem {
     hipStream_t stream;
 };
 
-// fixed-order reduction of the gradient partial sums shared by the register-resident and the quadrant kernel -- gram_fast.hip
+// fixed-order reduction of the gradient partial sums shared by the register-resident and the quadrant kernel -- sweep_host.hip
 // Which row tiles a launch owns and the order it enumerates them in (kq = 0 .. owned-1).  A full launch owns all of
 // them (off 0, stride 1).  The sharded partial solve of rank `off` of `stride` owns the tiles off + k*stride (cyclic), or
 // -- SIGSVGD_FLAG_FOLD_TILES -- those AND their mirror images ntile-1 - (off + k*stride): in the upper triangle tile t
@@ -380,7 +380,7 @@ inline T *ws_at(unsigned char *base, const WsArea &a)
     return a.bytes ? reinterpret_cast<T *>(base + a.off) : nullptr;
 }
 // `base` = p.ws aligned to 256 B; SIGSVGD_E_WORKSPACE (message "<family>: workspace ... required N B") when the caller's
-// buffer is smaller than w.total() -- a plan without areas takes any buffer, NULL included
+// buffer is smaller than w.total() -- a plan without areas takes any buffer, NULL included -- sweep_host.hip, as finish_launch
 int ws_base(const GramProblem &p, const WsPlan &w, const char *family, unsigned char *&base);
 // the tail of the fp32-sweep launches: the fp64 pass over the flagged pairs of the rows of the tiles `tm` owns (tile_rows rows
 // each), then the fixed-order gradient reduction into `out` (fp64 when out64; NULL: a forward-only launch)
@@ -429,7 +429,7 @@ int generic_launch(const GramProblem &p, bool precise, bool any_size);
 // K mirrored; rows of the tiles `tm` owns, `tile_rows` rows each) -- gram_generic.hip
 int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool sym, const TileMap &tm, int tile_rows);
 
-// register-resident fast path (n == 0, T <= 64) -- gram_fast.hip; off / stride / fold: the row tiles a partial solve owns
+// register-resident fast path (n == 0, T <= 64) -- gram_fast.hip (kernel: gram_fast_kernel.h); off / stride / fold: the row tiles a partial solve owns
 bool fast_supported(int T, int d, int n);
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false,
                  int kind = SIGSVGD_STATIC_RBF); // (IMQ / rational quadratic with SIGSVGD_FLAG_FP32_SWEEPS: general windows only)

@@ -317,7 +317,7 @@ def gram_geometry(A, B, T, d, n, want_grad, sym, cus=256, band_mode=None):
     """The work split of a Gram launch (RBF, second-order solver) of X [A, T, d] x Y [B, T, d] at dyadic order n on `cus`
     compute units, as a dict (family, rows_per_tile, resident, items, grid); None where the launch leaves the four fp32-sweep
     families for the coverage kernel.  `sym`: the Y_IS_X orientation (A == B, each unordered pair once).  Restates
-    `gram_route` (csrc/capi.hip), `dispatch_variant` / `launch_variant` / `grad_nw` / `grad_wg_per_cu` (gram_fast.hip),
+    `gram_route` (csrc/capi.hip), `dispatch_variant` / `launch_variant` (gram_fast_kernel.h), `grad_nw` / `grad_wg_per_cu` (gram_fast.hip),
     `quad_plan`, `dyad_plan` and `band_geometry`; a launch is `items` (row tile, column) pairs over
     grid = min(items, resident) workgroups, workgroup w taking the items [items*w/grid, items*(w+1)/grid).
     `band_mode`: SIGSVGD_BAND_MODE ("serial" / "parallel"; None: the environment's).

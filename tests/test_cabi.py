@@ -175,6 +175,22 @@ def test_argument_errors_are_status_codes(lib):
     assert rc == -1
 
 
+def test_csrc_layout_is_sources_and_headers():
+    """Every .hip of csrc/ is one translation unit of the build, every .h is a dependency needs_build() sees, and a source is
+    never compiled a second time through an #include of it (a file is one program, not several under macros)."""
+    from sigsvgd_amd import _lib
+
+    csrc = os.path.join(ROOT, "sigsvgd_amd", "csrc")
+    files = sorted(os.listdir(csrc))
+    assert sorted(f for f in files if f.endswith(".hip")) == sorted(_lib.SOURCES)
+    listed = {os.path.basename(h) for h in _lib.HEADERS if os.path.samefile(os.path.dirname(h), csrc)}
+    assert sorted(f for f in files if f.endswith(".h")) == sorted(listed)
+    assert os.path.basename(_lib.HEADERS[-1]) == "sigsvgd_hip.h"  # (the C-ABI tests open HEADERS[-1])
+    for f in files:
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, f)).read(), flags=re.M):
+            assert inc.endswith(".h"), f"{f} includes {inc}"
+
+
 def test_build_from_a_clean_tree(tmp_path):
     """`build()` proves itself: the sources alone, compiled into an empty directory (no object or library of an earlier
     build is touched), give a library that exports exactly the header's entry points, reports the header's ABI version and

@@ -1,5 +1,5 @@
 """The IMQ and rational-quadratic static kernels on the register-resident fp32-sweep kernel (`fp32_sweeps=True`,
-SIGSVGD_FLAG_FP32_SWEEPS; csrc/gram_fast.hip RADIAL = 1, csrc/gram_fast_radial.hip) against the fp64
+SIGSVGD_FLAG_FP32_SWEEPS; csrc/gram_fast_kernel.h RADIAL = 1, csrc/gram_fast_radial.hip) against the fp64
 numpy reference of tests/radial_reference.py, on inputs of `oracle.sigkernel_oracle.synthetic_inputs` with h = 1.
 
 Tolerance: the fp32-sweep contract of include/sigsvgd_hip.h, K per entry `rel_entry(K, Kr, 0.0, min_ref=0.5) < 1e-5` and the

@@ -1,4 +1,4 @@
-"""The column staging of gram_fast_kernel in the multi-item regime (csrc/gram_fast.hip, "staging").
+"""The column staging of gram_fast_kernel in the multi-item regime (csrc/gram_fast_kernel.h, "staging").
 
 A workgroup of the register-resident kernel walks a range of (row tile, column) items.  The next column trajectory is
 loaded at the top of the current pair and stays in flight, as raw bits, through the pair; after the pair's closing

@@ -1,5 +1,5 @@
 """The gradient reduction with four elements per thread, and the window of gram_fast_kernel's RAW_STAGE instantiations
-(csrc/gram_fast.hip: `grad_reduce_kernel<V>`, "the window between two pairs").
+(csrc/sweep_host.hip: `grad_reduce_kernel<V>`; csrc/gram_fast_kernel.h: "the window between two pairs").
 
 grad_reduce_kernel<4> serves launches whose T*d is a multiple of 4 with 16-byte loads (a thread owns 4 consecutive
 elements of a column block); every other T*d runs grad_reduce_kernel<1>.  Either adds the same fp64 terms per element in
