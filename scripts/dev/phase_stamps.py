@@ -6,7 +6,8 @@ barrier and the next pair comes as three parts: "block sum + stage store", "seco
 of the next pair: flags, addresses and issue of the next column's loads).  After that line gram_fast_kernel prints a second one with
 the older half of the workgroups (waves 0 .. NW/2 - 1) and the younger half side by side, "older % | younger %" per phase, each of its
 own half's total: the half that waits longer at "barrier after the pair" is the one that arrives first.
-SIGSVGD_WAVE_BALANCE=off in the environment shows the kernel without the wave-balance schedule.
+SIGSVGD_WAVE_BALANCE=off in the environment shows the kernel without the wave-balance schedule, SIGSVGD_HALF_OFFSET=off the
+wave-balance twin in place of the half-offset one (there the younger half's sync falls between its "phase 2" and "phase 3" stamps).
 usage (on the GPU box): python scripts/dev/phase_stamps.py [N T d [sym|ordered|fwd|fwdsym|dyadic<k>]]      (build only: --build)"""
 import os
 import subprocess

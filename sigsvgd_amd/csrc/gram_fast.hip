@@ -40,6 +40,14 @@ static bool wave_balance(int T, int d, int want_grad, bool sym)
     return !(e && e[0] == 'o' && e[1] == 'f');
 }
 
+// ... or, for d = 7 (fast_has_half), the half-offset twin, unless SIGSVGD_HALF_OFFSET=off (read per launch, like the two above)
+static bool half_offset(int T, int d, int want_grad, bool sym)
+{
+    if (!sym || d != 7 || !fast_has_half<8, true, true>() || !fixed_windows(T, want_grad)) return false;
+    const char *e = getenv("SIGSVGD_HALF_OFFSET");
+    return !(e && e[0] == 'o' && e[1] == 'f');
+}
+
 // [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
 // (kind: the IMQ and rational-quadratic launches have the general-window kernels only; the areas are kind-independent)
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold, int kind)
@@ -48,6 +56,7 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
     const bool rbf = kind == SIGSVGD_STATIC_RBF;
     w.fixed_windows = rbf && fixed_windows(T, want_grad) ? 1 : 0;
     w.wave_balance = rbf && wave_balance(T, d, want_grad, sym) ? 1 : 0;
+    w.half_offset = rbf && half_offset(T, d, want_grad, sym) ? 1 : 0;
     if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
     if (want_grad) {
         w.g = fast_geometry(A, B, T, d, sym, off, stride, fold);

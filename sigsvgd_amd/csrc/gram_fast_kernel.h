@@ -544,11 +544,13 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // PFIX: 0, or the launch's P = T - 1 as a compile-time constant: the sweeps then build their EXEC windows from immediates (see
 // "fixed windows" above; gradient kernels of the 64-slot ring at T = 64).  Nothing else of the kernel depends on it.
 // BAL: 0, or the wave-balance schedule of the pair (see bal_top above); it adds the s_setprio and their branches, nothing else.
+// HALF: 0, or 1: the younger half of the workgroup runs half a pair behind the older one (see half_younger in the kernel; DESIGN.md
+// 5.1.2).  The symmetric 7-of-8-channel gradient kernel with fixed windows only; it has its own priority schedule (BAL = 0).
 // RADIAL: 0 the RBF static kernel; 1 the inverse multiquadric or the rational quadratic, told apart by the wave-uniform a.kind
 // (DESIGN.md 5.18).  Phase 1 then evaluates k = phi(s), s = |x~ - y~|^2 inv_h clamped at 0, in place of the exponential, and the
 // G image holds -phi'(s) where RBF's holds k (for RBF the two are the same number); nothing after `rd = g - gprev` depends on it.
 // General windows only (no PFIX, no BAL); instantiated in gram_fast_radial.hip.
-template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0, int RADIAL = 0>
+template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0, int RADIAL = 0, int HALF = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : 2),
     GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgsOf<RADIAL> a)
@@ -561,6 +563,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     static_assert(RADIAL == 0 || (PFIX == 0 && BAL == 0), "the radial kinds: general windows, no wave balance");
     static_assert(BAL == 0 || (GRAD && SYM && RING == 64 && NW == 8 && PFIX != 0 && (BAL & 3) != 0 && BAL < 8),
                   "wave balance: the symmetric gradient kernels with fixed windows on 8-wave workgroups (the ones SIG_PRIO leaves alone)");
+    static_assert(HALF == 0 || (GRAD && SYM && LP && DPAD == 8 && RING == 64 && NW == 8 && PFIX != 0 && BAL == 0 && RADIAL == 0),
+                  "half offset: the symmetric 7-of-8-channel gradient kernel with fixed windows on 8-wave workgroups; a schedule of its own");
     // y rows are stored twice (row r and r + 64) so that the skewed row (t - lane) & 63 becomes
     // (64 - lane) + t: a per-lane base plus a compile-time offset.
     // Row strides are padded (YDS doubles / YFS floats) so that the 16 lanes a ds_read_b128 services per
@@ -570,12 +574,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     constexpr int YDS = DPAD + 2; // doubles per fp64 row: 80 B at DPAD=8 -> 80*l mod 256 distinct for 16 l
     constexpr int YFS = (DPAD == 4) ? 12 : DPAD + 4; // floats per fp32 row: 48 B at DPAD<=8, 80 B at 16
     // (sized by the ring: with 32 slots a 4-wave workgroup needs 47 KB instead of 84, three of them fit a CU)
-    constexpr int GSW = RING * GS_STRIDE; // floats of a wavefront's [slot][lane] image
+    constexpr int GSS = HALF ? 64 : GS_STRIDE; // (HALF: no padding word per slot -- every access is [slot][lane], and the LDS is needed)
+    constexpr int GSW = RING * GSS; // floats of a wavefront's [slot][lane] image
     __shared__ float Gs_all[GRAD ? NW * GSW : 1];
     __shared__ __align__(16) double yd[2 * RING * YDS];
-    __shared__ double ynd[2 * RING];
-    __shared__ double yref[DPAD];
-    __shared__ __align__(16) float yf[GRAD ? 2 * RING * YFS : 1];
+    __shared__ double ynd[HALF ? 1 : 2 * RING]; // (HALF is LP: the norm rides in the padded channel of yd, nobody reads ynd)
+    // HALF: the younger half of the workgroup runs its phases 3-4 on column j while the older half runs them on column j + 1, so
+    // what those phases read of a column -- yf and yref -- exists twice, [pb] = the pair's parity in the workgroup's range
+    constexpr int YFB = 2 * RING * YFS; // floats of one yf buffer
+    __shared__ double yref[HALF ? 2 * DPAD : DPAD];
+    __shared__ __align__(16) float yf[GRAD ? (HALF ? 2 : 1) * YFB : 1];
+    // HALF: the younger half's parked column sums [wave - NW/2][column][c] (its G image is rewritten by its next phase 1 before
+    // the sync that adds them up), and the older half's partial block sum of an item, kept until that sync
+    __shared__ float ypark[HALF ? (NW / 2) * RING * DC : 1];
+    __shared__ float ycarry[HALF ? RING * DC : 1];
 
     const int tid = threadIdx.x, lane = tid & 63;
     // (scalar: row index, row pointers and the per-wave LDS bases then live in SGPRs; as a vector value hipcc hoists the
@@ -583,6 +595,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lrow = lane & RM; // the row this lane owns
     const bool bal_first = (BAL & 4) ? wave < NW / 2 : wave >= NW / 2; // (BAL: this wave's half holds the priority first; scalar)
+    // Half offset (the kernel's HALF): the younger half of the workgroup (waves NW/2 .. NW-1) passes the pair's
+    // sync block between phase 2 and phase 3 instead of after phase 4.  Between two syncs it then runs [phases 3-4 of pair j,
+    // phases 0-2 of pair j + 1] beside the older half's [phases 0-2, phases 3-4 of pair j + 1]: each SIMD holds one wave in the
+    // fp64 static kernel or the forward sweep and one in the reverse sweep or the gradient pass.  One copy of the phases; the two
+    // sync sites are the same barrier events, each under a scalar branch on the wave index.
+    const bool half_younger = HALF != 0 && wave >= NW / 2; // (scalar)
+    int pb = 0; // HALF: which yf / yref buffer holds the column of the pair in work (flips with every pair of the range; scalar)
     const int T = a.T, d = a.d, P = T - 1, io64 = a.io64;
     // Work distribution: the items of a launch -- (owned row tile, column), tile-major; symmetric launches only the
     // columns from the tile's first row on -- all cost the same (the NW waves of a workgroup meet at a barrier per
@@ -654,7 +673,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     };
     // (RADIAL: the plain scale of s = |x~ - y~|^2 inv_h -- no log2 e, positive)
     const double nscale = RADIAL ? inv_h : -inv_h * 1.4426950408889634074; // exponent scale: exp(-d/h) = 2^(nscale*d)
-    auto stage_store = [&]() {
+    auto stage_store = [&](int buf) { // (buf: HALF only, the yf / yref buffer of the column; 0 otherwise)
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const int e = tid + k * NT;
@@ -670,16 +689,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     yd[(t + RING) * YDS + c] = v;
                 }
                 if (GRAD) {
-                    yf[t * YFS + c] = (float)v;
-                    yf[(t + RING) * YFS + c] = (float)v;
+                    float *yfb = yf + (HALF ? buf * YFB : 0);
+                    yfb[t * YFS + c] = (float)v;
+                    yfb[(t + RING) * YFS + c] = (float)v;
                 }
-                if (t == 0) yref[c] = stage_r[k];
+                if (t == 0) yref[(HALF ? buf * DPAD : 0) + c] = stage_r[k];
                 double s = v * v * nscale; // -log2(e)/h * |y~_t|^2 via xor-reduction over the DPAD lanes of a row
 #pragma unroll
                 for (int off = 1; off < DPAD; off <<= 1) s += __shfl_xor(s, off, 64);
                 if (c == 0) {
-                    ynd[t] = s;
-                    ynd[t + RING] = s;
+                    if constexpr (!HALF) {
+                        ynd[t] = s;
+                        ynd[t + RING] = s;
+                    }
                     if (LP) { // the padded channel of the fp64 row carries the norm: phase 1 needs no separate read
                         yd[t * YDS + DPAD - 1] = s;
                         yd[(t + RING) * YDS + DPAD - 1] = s;
@@ -729,7 +751,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     if (!staged) { // the range's first column: the only exposed load round trip
         staged = true;
         stage_load(j0);
-        stage_store();
+        stage_store(pb);
         __syncthreads();
     }
 
@@ -743,6 +765,70 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         if (more) stage_load(last ? jnext_tile : j + 1); // in flight during the pair
 
         float Dsl[RING]; // increments / sqrt(12) (the scale the difference-form stencil wants), one slot per anti-diagonal
+        const double *yrefp = yref + (HALF ? pb * DPAD : 0); // first point of y_j
+        // the pair's sync block: barrier, block sum + stage_store, barrier.  One call site, at the end of the pair; HALF: the older
+        // half's, the younger half passes it after phase 2 (waves without a pair included: the same barrier events).
+        auto pair_sync = [&]() __attribute__((always_inline)) {
+            SIG_STAMP(5)
+#ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER // timing experiment only (results are garbage without it)
+            __syncthreads(); // every wave is done with y_j (and has parked its column-side result)
+#endif
+            SIG_STAMP(6)
+            if constexpr (HALF != 0) {
+                // At this sync the older half has parked the column sums of item j (its G regions) and the younger half those of
+                // item j - 1 (ypark).  The item's block sum s = 0; s += w0; ... s += w7 is therefore split: waves 0..3 of item j
+                // into ycarry now, ycarry + w4 + ... + w7 to the slab row at the next sync (or the tile's closing one, below) --
+                // the same operands in the same order, the same bits.  Element e is read and written by thread e alone.
+                const float inv_d = 1.0f / (float)d;
+                const bool pend = j > j0; // item j - 1 of this tile waits in ycarry / ypark
+                float *dstp = a.cslab + (size_t)(item - 1) * (T * d);
+                for (int e = tid; e < T * d; e += NT) {
+                    const int n = (int)(((float)e + 0.5f) * inv_d), c = e - n * d; // exact for e < 2^20
+                    if (pend) {
+                        float s = ycarry[e];
+#pragma unroll
+                        for (int w = 0; w < NW / 2; ++w) s += ypark[w * RING * DC + e]; // (d == DC, T == RING: [column][c] is e)
+                        dstp[e] = s;
+                    }
+                    float s = 0.f;
+#pragma unroll
+                    for (int w = 0; w < NW / 2; ++w) s += Gs_all[w * GSW + n * DPAD + c];
+                    ycarry[e] = s;
+                }
+            } else if (GRAD && SYM) {
+                // thread e takes element e of the column's [T][d] block: the NW waves' sums are added in wave order and the
+                // item's partial goes to its own row of the slab with one coalesced store per element (grad_reduce_kernel
+                // adds the rows of a column in tile order).  Rounds 1-2 sent it with one atomic per element into a shared
+                // accumulator: 29.6 M memory-side atomics per C4 launch, and a result that depended on their order.
+                const float inv_d = 1.0f / (float)d;
+                float *dst = a.cslab + (size_t)item * (T * d);
+                for (int e = tid; e < T * d; e += NT) {
+                    const int n = (int)(((float)e + 0.5f) * inv_d), c = e - n * d; // exact for e < 2^20
+                    float s = 0.f;
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) {
+                        s += Gs_all[w * GSW + n * DPAD + c];
+                        if (RING == 32) s += Gs_all[w * GSW + (RING + n) * DPAD + c]; // the wavefront's second row
+                    }
+                    dst[e] = s;
+                }
+            }
+            ++item;
+            if (more) stage_store(HALF ? pb ^ 1 : 0); // (HALF: the next pair's buffer)
+            SIG_STAMP(7)
+#ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER
+            __syncthreads();
+#endif
+            SIG_STAMP(8)
+        };
+        auto younger_sync = [&]() __attribute__((always_inline)) { // (RAW_STAGE: the next column has arrived, as at the end of the pair)
+            if constexpr (RAW_STAGE) {
+#pragma unroll
+                for (int k = 0; k < EPT; ++k)
+                    asm volatile("" : "+v"(raw_v[k].lo), "+v"(raw_v[k].hi), "+v"(raw_r[k].lo), "+v"(raw_r[k].hi));
+            }
+            pair_sync();
+        };
 
         SIG_STAMP(0)
         SIG_PRIO(3)
@@ -755,7 +841,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             double xn = 0.0;
 #pragma unroll
             for (int c = 0; c < DPAD; ++c) {
-                const double xc = (lrow < T && c < d) ? xraw[c] - yref[c] : 0.0;
+                const double xc = (lrow < T && c < d) ? xraw[c] - yrefp[c] : 0.0;
                 xn = __builtin_fma(xc, xc, xn);
                 xs[c] = xc * (-2.0 * nscale);
             }
@@ -798,10 +884,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                             const double ki = rsqrt_ge1(1.0 + (e2 < 0.0 ? 0.0 : e2)), ki2 = ki * ki;
                             const bool rq = a.kind == SIGSVGD_STATIC_RQ;
                             g = (rq ? ki2 : ki) * 0.28867513459481288225;
-                            if (GRAD) Gs[gs_index(t, lane)] = (float)((rq ? ki2 : 0.5 * ki) * (ki2 * 0.28867513459481288225));
+                            if (GRAD) Gs[t * GSS + lane] = (float)((rq ? ki2 : 0.5 * ki) * (ki2 * 0.28867513459481288225));
                         } else {
                         g = exp2_p7(e2);
-                        if (GRAD) Gs[gs_index(t, lane)] = (float)g;
+                        if (GRAD) Gs[t * GSS + lane] = (float)g;
                         }
                         if (t == 0) g0 = g;
                         if (t == 1) g1 = g;
@@ -936,6 +1022,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
             SIG_STAMP(2)
             SIG_PRIO(1)
             bal_switch<BAL, 2>(bal_first);
+            if constexpr (HALF != 0) {
+                // the younger half's sync site: it keeps its increments and K_fwd slots across it (the sync code touches neither).
+                // Then every wave holds `s_setprio 1` through its phases 3-4: without it the younger half loses the arbitration
+                // there and the older half waits a third of its time at the sync (profiles/half_offset_bound.txt).
+                if (half_younger) younger_sync();
+                __builtin_amdgcn_s_setprio(1);
+            }
             if (GRAD) {
                 // weights of this lane's pair: row side w_ij, column side w_ji (per lane with two rows per wavefront,
                 // uniform otherwise; fetched here so that the loads are long back when the gradient pass needs them)
@@ -963,8 +1056,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                 for (int c = 0; c < DPAD / 2; ++c) {
                     const bool ok0 = lrow < T && 2 * c < d, ok1 = lrow < T && 2 * c + 1 < d;
-                    xc2[c] = f32x2{ok0 ? (float)(xraw[2 * c] - yref[2 * c]) : 0.f,
-                                   ok1 ? (float)(xraw[2 * c + 1] - yref[2 * c + 1]) : 0.f};
+                    xc2[c] = f32x2{ok0 ? (float)(xraw[2 * c] - yrefp[2 * c]) : 0.f,
+                                   ok1 ? (float)(xraw[2 * c + 1] - yrefp[2 * c + 1]) : 0.f};
                 }
                 // column-side (SYM): accumulators that TRAVEL one lane down per step.  On step sigma lane m
                 // holds R*G[m, n] with n = sigma+2-m; on the next step lane m-1 holds the same column n, so
@@ -975,7 +1068,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                 for (int c = 0; c < DPAD; ++c) tacc[c] = 0.f;
 
-                int yfrow = RING - lrow;                        // row (sigma + 2 - lrow) & RM == yfrow + k2
+                int yfrow = RING - lrow + (HALF ? pb * 2 * RING : 0); // row (sigma + 2 - lrow) & RM == yfrow + k2 (HALF: of this pair's buffer)
                 int gsoff = (GRAD ? wave * GSW : 0) + lane; // this wave's [slot][lane] image
                 // one iteration of the phase-4 pass (below); `gcu`, `ycu`: G[l][n] and the y~_n row, fetched one
                 // iteration ahead so that the LDS latency is off the chain and one s_waitcnt serves the iteration
@@ -1088,7 +1181,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                         Svn = Ksl[(RING - 2 - it) & RM];
                         if (it + 1 >= 2) {
                             const int k2n = (RING - it) & RM;
-                            gnx = Gs_all[gsoff + k2n * GS_STRIDE];
+                            gnx = Gs_all[gsoff + k2n * GSS];
                             const f32x2 *yr = reinterpret_cast<const f32x2 *>(yf + (yfrow + k2n) * YFS);
 #pragma unroll
                             for (int c = 0; c < DPAD / 2; ++c) ynx[c] = yr[c];
@@ -1110,14 +1203,26 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     // diagonal pair has no column side, a half without a pair contributes nothing
                     const int ncol = (RING - lrow) & RM; // the column whose finished sums this lane ended up with
                     const float wpark = (ncol <= P) ? ((RING == 32) ? -m2h : -(wcol * m2h)) : 0.f;
+                    if (HALF != 0 && half_younger) { // (its G image belongs to its next phase 1 before the sums are added up)
+                        float *pk = ypark + ((wave - NW / 2) * RING + ncol) * DC;
+#pragma unroll
+                        for (int c = 0; c < DC; ++c) pk[c] = wpark * tacc[c];
+                    } else {
                     float *pk = Gs + ((RING == 32 ? (lane >> 5) * RING : 0) + ncol) * DPAD;
 #pragma unroll
                     for (int c = 0; c < DPAD; ++c) pk[c] = wpark * tacc[c];
+                    }
                 }
             }
         } else if (GRAD && SYM) {
+            if (HALF != 0 && half_younger) {
+                younger_sync();
+#pragma unroll
+                for (int c = 0; c < DC; ++c) ypark[((wave - NW / 2) * RING + lane) * DC + c] = 0.f;
+            } else {
 #pragma unroll
             for (int c = 0; c < DPAD; ++c) Gs[lane * DPAD + c] = 0.f; // idle wave contributes nothing
+            }
         }
         // (RAW_STAGE: the next column arrived long ago; saying so HERE, on every path, keeps that wait out of the window
         //  after the barrier: the compiler cannot see that the loads at the loop top and the store that consumes them run
@@ -1128,36 +1233,22 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 asm volatile("" : "+v"(raw_v[k].lo), "+v"(raw_v[k].hi), "+v"(raw_r[k].lo), "+v"(raw_r[k].hi));
         }
         bal_end<BAL>(bal_first); // (a wave without a pair never raised it: then this changes nothing)
-        SIG_STAMP(5)
-#ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER // timing experiment only (results are garbage without it)
-        __syncthreads(); // every wave is done with y_j (and has parked its column-side result)
-#endif
-        SIG_STAMP(6)
-        if (GRAD && SYM) {
-            // thread e takes element e of the column's [T][d] block: the NW waves' sums are added in wave order and the
-            // item's partial goes to its own row of the slab with one coalesced store per element (grad_reduce_kernel
-            // adds the rows of a column in tile order).  Rounds 1-2 sent it with one atomic per element into a shared
-            // accumulator: 29.6 M memory-side atomics per C4 launch, and a result that depended on their order.
-            const float inv_d = 1.0f / (float)d;
-            float *dst = a.cslab + (size_t)item * (T * d);
-            for (int e = tid; e < T * d; e += NT) {
-                const int n = (int)(((float)e + 0.5f) * inv_d), c = e - n * d; // exact for e < 2^20
-                float s = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) {
-                    s += Gs_all[w * GSW + n * DPAD + c];
-                    if (RING == 32) s += Gs_all[w * GSW + (RING + n) * DPAD + c]; // the wavefront's second row
-                }
-                dst[e] = s;
-            }
-        }
-        ++item;
-        if (more) stage_store();
-        SIG_STAMP(7)
-#ifndef SIG_EXPERIMENT_NO_PAIR_BARRIER
+        if constexpr (HALF != 0) __builtin_amdgcn_s_setprio(0);
+        if (!half_younger) pair_sync(); // (HALF: the younger half has passed it after phase 2)
+        if constexpr (HALF != 0) pb ^= 1; // (after the sync: it stages the next column into the other buffer)
+    }
+    if constexpr (HALF != 0) {
+        // the tile's closing sync: the younger half has just finished phases 3-4 of the last item (the older half waits here
+        // meanwhile: half an interval per workgroup and tile; the first interval of a tile mirrors it); the item's block sum
+        // leaves as above.  One barrier: the next writes of ycarry / ypark come after the next sync's first one.
         __syncthreads();
-#endif
-        SIG_STAMP(8)
+        float *dstp = a.cslab + (size_t)(item - 1) * (T * d);
+        for (int e = tid; e < T * d; e += NT) {
+            float s = ycarry[e];
+#pragma unroll
+            for (int w = 0; w < NW / 2; ++w) s += ypark[w * RING * DC + e];
+            dstp[e] = s;
+        }
     }
 
     if (GRAD && row_ok && lrow < T) { // this (workgroup, row tile) segment's own slot: segments are numbered kq + workgroup
@@ -1194,16 +1285,29 @@ constexpr int FAST_BAL = SIG_EXPERIMENT_BALANCE;
 template <int DPAD, bool SYM>
 constexpr bool fast_has_balance() { return FAST_BAL != 0 && SYM && DPAD <= 8; }
 
+// The half-offset twin (the kernel's HALF): the symmetric 7-of-8-channel kernel, the headline's.  d = 8 has no LDS left for it (the
+// norm array cannot go), the 4-channel kernels keep the wave-balance twin.  SIGSVGD_HALF_OFFSET=off, read per launch next to
+// SIGSVGD_WAVE_BALANCE (gram_fast.hip's half_offset), keeps a launch on the wave-balance twin.
+template <int DPAD, bool SYM, bool LP>
+constexpr bool fast_has_half() { return SYM && LP && DPAD == 8; }
+
 // gram_fast_radial.hip: dispatch_variant<1> below (RADIAL = 1: IMQ and rational quadratic, a.kind), called from gram_fast.hip's `run`
 int fast_radial_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows);
 
 namespace {
 // a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths, or
-// (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule; RADIAL has neither twin
+// (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule, or (`half`: the plan's half_offset) its twin with
+// the halves of the workgroup half a pair apart; RADIAL has none of them
 template <int DPAD, int NW, bool SYM, bool LP, int RING, int RADIAL>
-void launch_grad(bool fix, bool bal, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
+void launch_grad(bool fix, bool bal, bool half, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
 {
     if constexpr (RADIAL == 0 && RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
+        if constexpr (fast_has_half<DPAD, SYM, LP>()) {
+            if (fix && half) {
+                hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, 0, 0, 1>), grid, block, 0, stream, a);
+                return;
+            }
+        }
         if constexpr (fast_has_balance<DPAD, SYM>()) {
             if (fix && bal) {
                 hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, FAST_BAL>), grid, block, 0, stream, a);
@@ -1252,18 +1356,19 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     if constexpr (RADIAL != 0) ka.kind = p.kind;
     const bool fix = grad && w.fixed_windows && p.T == 64; // (the kernel's PFIX must be the launch's T - 1)
     const bool bal = fix && w.wave_balance;
+    const bool half = fix && w.half_offset;
     if (!grad && sym)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (!grad)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (sym && lp)
-        launch_grad<DPAD, NW, true, HAS_LP, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, true, HAS_LP, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
     else if (sym)
-        launch_grad<DPAD, NW, true, false, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, true, false, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
     else if (lp)
-        launch_grad<DPAD, NW, false, HAS_LP, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, false, HAS_LP, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
     else
-        launch_grad<DPAD, NW, false, false, RING, RADIAL>(fix, bal, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, false, false, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS

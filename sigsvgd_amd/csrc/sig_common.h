@@ -364,6 +364,7 @@ struct WsPlan {
     WsArea counter, partials, colslab; // gram_generic.hip: work counter, gradient partials, column-side slab
     int fixed_windows = 0; // gram_fast.hip: the launch runs the kernel whose sweeps have their EXEC windows as immediates
     int wave_balance = 0;  // gram_fast.hip: ... and, where that kernel has a wave-balance twin, the twin
+    int half_offset = 0;   // gram_fast.hip: ... or, where it has one, the twin that runs the halves of a workgroup half a pair apart
     size_t end = 0; // bytes of the areas
     WsArea take(size_t bytes) // the next area, behind the ones taken so far
     {
