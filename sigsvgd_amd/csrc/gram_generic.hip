@@ -6,7 +6,8 @@
 // forward solution is parked in a per-workgroup HBM scratch in [step][lane] order (coalesced
 // 256-B rows, written and re-read by the same wavefront, so it stays in L2).
 //
-// With Y == X and enough pairs to fill the chip (>= 4096) each unordered pair is solved once: K is mirrored and
+// With Y == X and enough pairs to fill the chip (>= 4096) each unordered pair is solved once (below that count every ordered pair is solved, and
+// K[j][i], j > i, is still the stored K[i][j]: GenericArgs::mirror): K is mirrored and
 // the pair's gradient with respect to x_j comes from a second contraction of the same coarse scatter, added
 // in fixed order by the reduction kernel from a per-pair slab; work items are then pulled from a counter.
 //
@@ -27,6 +28,8 @@ struct GenericArgs {
                       // reduce_partials_kernel adds the blocks of a column in row order (no atomics: reproducible bits)
     float *wsk;       // [grid][nbands*nsteps*64]
     int yx;           // Y is X: solve the pairs j >= i only, mirror K, add d k(x_j, x_i)/d x_j through colacc
+    int mirror;       // Y is X solved as ordered pairs (too few of them for yx): K[j][i], j > i, is the stored K[i][j] all the same --
+                      // the two solves of a pair agree to fp64 rounding only, and K of a Y_IS_X launch is symmetric bit for bit
     unsigned long long *next_item; // work counter (zeroed by the launcher): items are pulled, not assigned, because
                                    // with yx their cost varies from nothing to JC pairs
     int A, B, T, d, dp, n, r, P, Tm, TmS, nbands, nsteps, JC, nchunks, kind, naive, sym, want_grad;
@@ -300,8 +303,8 @@ __global__ __launch_bounds__(64) void gram_generic_kernel(GenericArgs a)
                 if (p == P - 1) Kval = cur;
             }
             if (((P - 1) & (kWave - 1)) == lane) {
-                Kout[(size_t)i * a.B + j] = (IO)Kval;
-                if (a.yx && j != i) Kout[(size_t)j * a.B + i] = (IO)Kval;
+                if (!a.mirror || j >= i) Kout[(size_t)i * a.B + j] = (IO)Kval;
+                if ((a.yx || a.mirror) && j > i) Kout[(size_t)j * a.B + i] = (IO)Kval;
             }
 
             SIG_STAMP(2)
@@ -663,6 +666,7 @@ int generic_launch(const GramProblem &p, bool precise, bool any_size)
     }
     a.partials = ws_at<double>(base, w.partials);
     a.yx = yx ? 1 : 0;
+    a.mirror = (!yx && (p.flags & SIGSVGD_FLAG_Y_IS_X) && p.A == p.B) ? 1 : 0;
     a.colslab = ws_at<double>(base, w.colslab);
     a.wsk = ws_at<float>(base, w.wsk);
     a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.dp = pl.dp; a.n = p.n; a.r = pl.r; a.P = pl.P;
@@ -719,6 +723,7 @@ int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool
     a.X = p.X; a.Y = p.Y; a.grad_out = nullptr; a.K_out = p.K_out;
     a.next_item = nullptr; a.partials = nullptr; a.colslab = nullptr; a.wsk = nullptr;
     a.yx = sym ? 1 : 0;
+    a.mirror = 0;
     a.A = p.A; a.B = p.B; a.T = p.T; a.d = p.d; a.dp = pl.dp; a.n = p.n; a.r = pl.r; a.P = pl.P;
     a.Tm = pl.Tm; a.TmS = pl.TmS; a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.JC = pl.JC;
     a.nchunks = pl.nchunks; a.kind = p.kind; a.naive = 0; a.sym = 0; a.want_grad = 0; a.inv_h = p.inv_h;

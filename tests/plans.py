@@ -1,7 +1,7 @@
 """Python restatements of the library's launch plans, and the case tables that are read off them.  Each function names the
 C++ function it mirrors; the host-only C-ABI tests pin every one of them to the library's own workspace and plan queries
-(test_pde_cabi, test_long_cabi, test_long2_cabi, test_long_partial_cabi, test_pair_cabi, test_gram_geometry), so the GPU
-tests can assert from them which branch of a plan a shape reaches."""
+(test_pde_cabi, test_long_cabi, test_long2_cabi, test_long_partial_cabi, test_pair_cabi, test_gram_geometry,
+test_generic_plan_cabi), so the GPU tests can assert from them which branch of a plan a shape reaches."""
 import os
 from collections import namedtuple
 from functools import lru_cache
@@ -361,6 +361,82 @@ def gram_geometry(A, B, T, d, n, want_grad, sym, cus=256, band_mode=None):
     items = sum(B - t * rows for t in range(ntile)) if sym else ntile * B
     resident = cus * per_cu
     return dict(family=family, rows_per_tile=rows, resident=resident, items=items, grid=min(items, resident))
+
+
+# ---- the coverage kernel (gram_generic.hip) ---------------------------------------------------------------------------------
+def generic_lds_bytes(T, d, n, want_grad, big, dd=False):
+    """`generic_lds_bytes`: the per-pair LDS of the coverage kernel.  big: the per-band layout; dd: fp64 increment table"""
+    dp = d + 1 if d % 2 == 0 else d
+    Tm = T - 1
+    TmS, P = Tm | 1, (1 << n) * Tm
+    dbl = 2 * T * dp + 2 * T + (P + 2) + 64
+    if big:
+        return (dbl + 64 * TmS + T) * 8
+    flt = Tm * TmS
+    if want_grad:
+        dbl += Tm * Tm + T * dp
+    if dd:
+        dbl, flt = dbl + Tm * TmS, 0
+    return dbl * 8 + flt * 4
+
+
+def generic_plan(A, B, T, d, n, want_grad, sym, precise, any_size, cus=256):
+    """The launch plan of csrc/gram_generic.hip (`generic_solves_unordered`, `make_plan` and the workspace layout of
+    `generic_plan`) for X [A, T, d] x Y [B, T, d] at dyadic order n on `cus` compute units, as a dict: table ("f64": the
+    whole-grid increment table in fp64, "f32": in fp32, "big": fp64 increments per band of 64 rows, S in the scratch), lds,
+    P, nbands, nsteps, JC, nchunks, items, grid, yx (each unordered pair once), bytes (what sigsvgd_gram_workspace_bytes
+    reports for a query that covers this one launch); None where the library refuses the launch (E_UNSUPPORTED).
+    `sym`: the Y_IS_X orientation with A == B; `precise`, `any_size`: what the route passes (`generic_route`).
+    tests/test_generic_plan_cabi.py pins it to the library."""
+    assert A >= 1 and B >= 1 and T >= 2 and d >= 1 and 0 <= n <= 10
+    yx = bool(sym) and (any_size or A * B >= 4096)
+    if yx and want_grad and A * B * T * d * 8 > (1 << 30):
+        yx = False  # the column slab would pass 1 GiB: ordered pairs
+    P = (1 << n) * (T - 1)
+    if P > 16384:
+        return None
+    table, lds = "f32", generic_lds_bytes(T, d, n, want_grad, False)
+    l2 = generic_lds_bytes(T, d, n, want_grad, False, True)
+    if l2 <= (160 if precise else 20) * 1024:
+        table, lds = "f64", l2
+    elif n == 0 and (precise or lds > 160 * 1024):
+        table, lds = "big", generic_lds_bytes(T, d, n, want_grad, True)
+    if lds > 160 * 1024:
+        return None
+    JC = 32
+    while JC > 1 and A * -(-B // JC) < (16384 if yx else 2048):
+        JC >>= 1
+    nchunks = -(-B // JC)
+    items = A * nchunks
+    grid = min(cus * max(1, min(8, 160 * 1024 // lds)), items)
+    nbands, nsteps = -(-P // 64), P + 63
+    partial_bytes = A * nchunks * T * d * 8 if want_grad else 0
+    col_bytes = (A * B * T * d * 8 + 255) & ~255 if want_grad and yx else 0
+    big = table == "big"
+    wsk_per_block = nbands * nsteps * 64 * (2 if big else 1) + (64 if big else 0) if want_grad else 0
+    return dict(table=table, lds=lds, P=P, nbands=nbands, nsteps=nsteps, JC=JC, nchunks=nchunks, items=items, grid=grid, yx=yx,
+                bytes=256 + partial_bytes + col_bytes + wsk_per_block * 4 * grid + 256)
+
+
+def generic_route(A, B, T, d, n, kind, want_grad, naive=False, force_generic=False, sym=False, cus=256, band_mode=None):
+    """`gram_route`'s three ways into the coverage kernel: "Generic", "GenericPrecise", "GenericOneChannel"; None where the
+    launch stays on an fp32-sweep family.  kind: the static kernel (0 RBF, 1 linear, 2 IMQ, 3 RQ, 6 / 7 Matern); without
+    SIGSVGD_FLAG_FP32_SWEEPS.  -> (route, precise, any_size): the last two are what `generic_plan` takes."""
+    if force_generic or kind not in (0, 1):  # (IMQ, RQ, Matern: fp64 kernels only, held to fp64 results)
+        return "GenericPrecise", True, False
+    fp32 = kind == 0 and not naive
+    if fp32 and want_grad and d == 1 and n == 0 and 3 <= T <= 128:
+        return "GenericOneChannel", True, True
+    if fp32 and gram_geometry(A, B, T, d, n, want_grad, sym, cus, band_mode) is not None:
+        return None
+    return "Generic", False, False
+
+
+def routed_generic_plan(A, B, T, d, n, kind, want_grad, naive=False, force_generic=False, sym=False, cus=256):
+    """(route, plan) of a Gram call that reaches the coverage kernel (asserted)"""
+    r = generic_route(A, B, T, d, n, kind, want_grad, naive, force_generic, sym, cus)
+    assert r is not None, "not a launch of the coverage kernel"
+    return r[0], generic_plan(A, B, T, d, n, want_grad, sym and A == B, r[1], r[2], cus)
 
 
 def gram_item_ranges(A, B, geom, sym, tiles=None):

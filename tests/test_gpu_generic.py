@@ -56,24 +56,6 @@ def test_generic_fwd_bwd(gpu, A, B, T, d, n, kind, naive, dtype):
     assert rel_max(g3.cpu().numpy(), O.gram_backward(X, Y, None, kind, h, n, naive)[1]) < TOL
 
 
-def test_phi(gpu):
-    from sigsvgd_amd import ops
-
-    rng = np.random.default_rng(0)
-    for N, D in [(16, 40), (100, 20), (128, 224), (257, 65)]:
-        K = rng.standard_normal((N, N)).astype(np.float32)
-        s = rng.standard_normal((N, D)).astype(np.float32)
-        gk = rng.standard_normal((N, D)).astype(np.float32)
-        m = (rng.random((N, D)) > 0.3).astype(np.float32)
-        X = rng.standard_normal((N, D)).astype(np.float32)
-        vref = O.svgd_velocity(K, s, gk, m)
-        v, Xn = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk, m)), X=torch.as_tensor(X, device=gpu), lr=0.1)
-        assert rel_max(v.cpu().numpy(), vref) < TOL
-        assert rel_max(Xn.cpu().numpy(), X - 0.1 * vref) < TOL
-        v2 = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk)))
-        assert rel_max(v2.cpu().numpy(), O.svgd_velocity(K, s, gk)) < TOL
-
-
 @pytest.mark.parametrize("N,T,d,n,kind", [(70, 10, 2, 4, 0), (66, 20, 2, 2, 0), (64, 5, 3, 5, 0), (65, 30, 2, 2, 0), (67, 12, 3, 1, 1),
                                           (64, 128, 14, 0, 0), (9, 10, 2, 3, 0)])
 @pytest.mark.parametrize("weights", ["ones", "random", "sym"])

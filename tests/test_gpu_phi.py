@@ -51,6 +51,8 @@ import torch
 
 import phi_reference as P
 import update_reference as R
+from oracle import sigkernel_oracle as O
+from parity import rel_max
 from phi_reference import BENCH_SHAPE, SEED, SHAPES
 
 pytestmark = pytest.mark.gpu
@@ -329,3 +331,25 @@ def test_update_kernel_per_entry(gpu, N, D, mode, masked):
                        where=f"update ({N}, {D}) step {k}", got_v=host(vu))
     if masked:
         assert torch.equal(Xu[mg == 0], Xg0[mg == 0])
+
+
+# ---- the round-1 smoke comparison of the velocity kernel, moved here unchanged from tests/test_gpu_generic.py -----------------
+TOL = 1e-5  # north_star: within 1e-5 relative fp32
+
+
+def test_phi(gpu):
+    from sigsvgd_amd import ops
+
+    rng = np.random.default_rng(0)
+    for N, D in [(16, 40), (100, 20), (128, 224), (257, 65)]:
+        K = rng.standard_normal((N, N)).astype(np.float32)
+        s = rng.standard_normal((N, D)).astype(np.float32)
+        gk = rng.standard_normal((N, D)).astype(np.float32)
+        m = (rng.random((N, D)) > 0.3).astype(np.float32)
+        X = rng.standard_normal((N, D)).astype(np.float32)
+        vref = O.svgd_velocity(K, s, gk, m)
+        v, Xn = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk, m)), X=torch.as_tensor(X, device=gpu), lr=0.1)
+        assert rel_max(v.cpu().numpy(), vref) < TOL
+        assert rel_max(Xn.cpu().numpy(), X - 0.1 * vref) < TOL
+        v2 = ops.svgd_phi(*(torch.as_tensor(t, device=gpu) for t in (K, s, gk)))
+        assert rel_max(v2.cpu().numpy(), O.svgd_velocity(K, s, gk)) < TOL
