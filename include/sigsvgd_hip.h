@@ -153,6 +153,19 @@ extern "C" {
                                       /* kernel as for RBF; with any other kind, shape, order, SIGSVGD_FLAG_NAIVE_SOLVER or                */
                                       /* SIGSVGD_FLAG_FORCE_GENERIC the bit is accepted and ignored (as it was before this revision of     */
                                       /* ABI 10, which adds no symbol and changes no signature)                                             */
+#define SIGSVGD_FLAG_EXACT_ADJOINT 256u /* gradient launches of the long route (sigsvgd_pde_fwd_bwd, sigsvgd_gram_long_fwd_bwd, _fwd_bwd2,     */
+                                      /* _fwd_bwd_h, sigsvgd_pair_fwd_bwd, _fwd_bwd_h): every gradient -- dG_out,      */
+                                      /* gradX_out, gradY_out, dK_dinvh_out -- is the exact derivative of the discrete K the launch returns, */
+                                      /* the adjoint of the default (second-order) stencil itself, instead of the reference's GG convention  */
+                                      /* K_fwd[p][q] K_rev[p+1][q+1], which is that derivative for the first-order stencil only and differs  */
+                                      /* from it by per cents otherwise.  K_out is bit-identical to the unflagged launch, the workspace is   */
+                                      /* the same bytes, the cost is the same sweeps.  With SIGSVGD_FLAG_NAIVE_SOLVER the bit is accepted    */
+                                      /* and the launch is the unflagged one (GG is exact there).  Paired launches run one wavefront per     */
+                                      /* pair with it (sigsvgd_pair_schedule says so).  Forward-only launches and their queries refuse it    */
+                                      /* as an unknown bit (SIGSVGD_E_BADARG); sigsvgd_gram_long_sym_partial with its plan and workspace     */
+                                      /* queries, sigsvgd_gram_fwd_bwd, sigsvgd_gram_sym_partial and sigsvgd_gram_workspace_bytes, whose     */
+                                      /* routes have GG kernels only, return SIGSVGD_E_UNSUPPORTED.  A later revision of ABI 10: no new      */
+                                      /* symbol, no changed signature; an earlier library answers SIGSVGD_E_BADARG                           */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */
@@ -186,6 +199,7 @@ const char *sigsvgd_last_error(void);
  * (ABI 9: the static kernel decides which solver runs -- the linear kernel always takes the coverage kernel --, so the
  * query needs it; ABI <= 8 sized for RBF whatever the launch asked for).
  * want_grad = 0 for sigsvgd_gram_fwd, 1 for sigsvgd_gram_fwd_bwd.  Returns 0 and sets *bytes. */
+/* (flags with SIGSVGD_FLAG_EXACT_ADJOINT: SIGSVGD_E_UNSUPPORTED -- the fused kernels have the GG gradient only; see the flag.) */
 int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, int static_kind, int want_grad,
                                  unsigned flags, size_t *bytes);
 
@@ -197,6 +211,8 @@ int sigsvgd_gram_fwd(const void *X, const void *Y, int A, int B, int T, int d, i
 /* As above, plus gradX_out[A,T,d] = d( sum_ij grad_out[i,j] K[i,j] ) / dX  (first slot only;
  * Y receives no gradient, as in the reference).  grad_out == NULL means all ones (the only case
  * the reference produces: callers differentiate K.sum()). */
+/* SIGSVGD_FLAG_EXACT_ADJOINT: SIGSVGD_E_UNSUPPORTED before any device work (GG kernels only on this route; the long-path entry
+ * points below take it). */
 int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int d, int dtype,
                          double inv_h, int dyadic_order, int static_kind, unsigned flags,
                          const void *grad_out, void *K_out, void *gradX_out, void *workspace,
@@ -214,6 +230,7 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
  * gradient up to the fp64 rounding of the sum).  Shapes of the register-resident and quadrant kernels
  * (dyadic_order 0, 3 <= T <= 128, d <= 16, RBF, no SIGSVGD_FLAG_NAIVE_SOLVER / SIGSVGD_FLAG_FORCE_GENERIC).
  * `workspace` as sized by sigsvgd_gram_workspace_bytes(N, N, T, d, 0, static_kind, 1, SIGSVGD_FLAG_Y_IS_X). */
+/* SIGSVGD_FLAG_EXACT_ADJOINT: SIGSVGD_E_UNSUPPORTED before any device work (GG kernels only). */
 int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h,
                              int static_kind, unsigned flags, int tile_offset, int tile_stride,
                              const void *grad_out, void *K_partial, double *grad_partial,
@@ -346,6 +363,10 @@ int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L
  * P + 1, Q + 1 <= 1023); beyond that SIGSVGD_E_UNSUPPORTED.  Bit-reproducible (no floating-point atomics).
  * The workspace is sized by the resident wavefronts, not by npairs (one pair per wavefront; forward-only launches need
  * none and report 0 bytes); want_grad = 1 for sigsvgd_pde_fwd_bwd. */
+/* flags: SIGSVGD_FLAG_NAIVE_SOLVER, and for sigsvgd_pde_fwd_bwd and its query (want_grad = 1) SIGSVGD_FLAG_EXACT_ADJOINT: dG_out
+ * is then the exact derivative of the discrete K_out in G for the default stencil too.  K_out is
+ * bit-identical to the unflagged launch and the workspace the same bytes; together with SIGSVGD_FLAG_NAIVE_SOLVER the launch is
+ * the unflagged one.  sigsvgd_pde_fwd and the query with want_grad = 0 refuse the bit like any unknown one (SIGSVGD_E_BADARG). */
 int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes);
 int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags, void *K_out,
                     void *workspace, size_t workspace_bytes, void *stream);
@@ -373,6 +394,10 @@ int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int d
 int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                           int dyadic_order, int static_kind, unsigned flags, void *K_out, void *workspace,
                           size_t workspace_bytes, void *stream);
+/* sigsvgd_gram_long_fwd_bwd (and the query with want_grad = 1) takes SIGSVGD_FLAG_EXACT_ADJOINT: gradX_out is the exact
+ * derivative of the discrete K_out (every static kernel); K_out is bit-identical to the unflagged launch,
+ * the workspace the same bytes, and with SIGSVGD_FLAG_NAIVE_SOLVER the launch is the unflagged one.  sigsvgd_gram_long_fwd and the
+ * query with want_grad = 0: SIGSVGD_E_BADARG, as for any unknown bit. */
 int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                               int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                               void *gradX_out, void *workspace, size_t workspace_bytes, void *stream);
@@ -400,6 +425,11 @@ int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX
  * grid, and the LDS bytes of a workgroup. */
 int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad,
                                  unsigned flags, size_t *bytes);
+/* SIGSVGD_FLAG_EXACT_ADJOINT (sigsvgd_pair_fwd_bwd, and the queries with want_grad = 1): gradX_out and gradY_out are the exact
+ * derivatives of the discrete K_out; K_out is bit-identical to the unflagged launch and the workspace the same bytes.  The
+ * launch runs one wavefront per pair whatever the shape (the band-parallel kernel has the GG sweep only), and
+ * sigsvgd_pair_schedule reports waves_per_pair = 1 with the bit.  With SIGSVGD_FLAG_NAIVE_SOLVER the launch -- and the schedule
+ * reported -- is the unflagged one.  sigsvgd_pair_fwd and the queries with want_grad = 0: SIGSVGD_E_BADARG. */
 int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int static_kind, int want_grad, unsigned flags,
                           int *waves_per_pair, int *grid, size_t *lds_bytes);
 int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d, int dtype, double inv_h,
@@ -427,6 +457,10 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
  * (A ceil(B / JC) TX + B ceil(A / IC) TY) d doubles of slabs; forward-only launches need none and report 0 bytes. */
 int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
                                        int want_gradX, int want_gradY, unsigned flags, size_t *bytes);
+/* SIGSVGD_FLAG_EXACT_ADJOINT (with a gradient output, and the query with want_gradX or want_gradY): gradX_out and gradY_out are
+ * the exact derivatives of the discrete K_out, with SIGSVGD_FLAG_Y_IS_X, SIGSVGD_FLAG_SYM and weights as without it; K_out is
+ * bit-identical to the unflagged launch, the workspace the same bytes; with SIGSVGD_FLAG_NAIVE_SOLVER the launch is the
+ * unflagged one.  Forward only (both outputs NULL / neither wanted): SIGSVGD_E_BADARG. */
 int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
                                int dyadic_order, int static_kind, unsigned flags, const void *grad_out, void *K_out,
                                void *gradX_out /* may be NULL */, void *gradY_out /* may be NULL */, void *workspace,
@@ -454,6 +488,10 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
  * only).  Workspace: sigsvgd_gram_long_h_workspace_bytes = the scratch plus the slabs of the gradients wanted (what
  * sigsvgd_gram_long2_workspace_bytes reports where one is wanted; the scratch alone where neither is);
  * sigsvgd_pair_h_workspace_bytes = sigsvgd_pair_workspace_bytes with the gradient. */
+/* SIGSVGD_FLAG_EXACT_ADJOINT (both launches and both queries): gradX_out, gradY_out and dK_dinvh_out are the exact derivatives of
+ * the discrete K_out -- dK_dinvh_out then agrees with a finite difference of K_out in inv_h, which the GG value misses by per
+ * cents; K_out is bit-identical to the unflagged launch, the workspace the same bytes; with SIGSVGD_FLAG_NAIVE_SOLVER the launch
+ * is the unflagged one. */
 int sigsvgd_gram_long_h_workspace_bytes(int A, int B, int TX, int TY, int d, int dyadic_order, int static_kind,
                                         int want_gradX, int want_gradY, unsigned flags, size_t *bytes);
 int sigsvgd_gram_long_fwd_bwd_h(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, double inv_h,
@@ -494,6 +532,8 @@ int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int st
                                    int *tile_rows, int *tile_cols);
 int sigsvgd_gram_long_partial_workspace_bytes(int N, int T, int d, int dyadic_order, int static_kind, unsigned flags,
                                               int tile_offset, int tile_stride, size_t *bytes);
+/* SIGSVGD_FLAG_EXACT_ADJOINT: SIGSVGD_E_UNSUPPORTED from the launch and from both queries above, before any device work (the
+ * partial mode has the GG sweep only; the message names the flag). */
 int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype, double inv_h, int dyadic_order,
                                   int static_kind, unsigned flags, int tile_offset, int tile_stride,
                                   const void *grad_out /* [N,N] or NULL = ones */, void *K_partial, double *grad_partial,

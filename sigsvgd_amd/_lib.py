@@ -17,10 +17,12 @@ LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_
 SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "sweep_host.hip", "gram_quad.hip",
            "svgd_phi.hip", "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip",
            "gram_band.hip", "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
-           "pair_bands_matern.hip", "sqdist_select.hip"]
+           "pair_bands_matern.hip", "sqdist_select.hip", "sig_pde_exact.hip", "gram_long_exact.hip",
+           "gram_long_exact_matern.hip"]
 # every header of csrc/ (a source includes headers only), then the public header, which stays the last element
 HEADERS = [os.path.join(_CSRC, h) for h in ("sig_common.h", "quad_sweeps.h", "ring_sweep.h", "long_static.h", "pair_bands.h",
-                                            "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h")] + \
+                                            "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h",
+                                            "sig_pde_kernel.h")] + \
           [os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 
 # mirror of include/sigsvgd_hip.h
@@ -30,6 +32,7 @@ STATIC_MATERN32, STATIC_MATERN52 = 6, 7  # (4 and 5 are reserved: the library re
 FLAG_NAIVE_SOLVER, FLAG_SYM, FLAG_Y_IS_X, FLAG_FORCE_GENERIC, FLAG_WS_CLEAN, FLAG_STORED_FORWARD = 1, 2, 4, 8, 16, 32
 FLAG_FOLD_TILES = 64
 FLAG_FP32_SWEEPS = 128
+FLAG_EXACT_ADJOINT = 256
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 ABI_VERSION = 10

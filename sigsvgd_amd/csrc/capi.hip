@@ -61,8 +61,8 @@ int signature_launch(const void *X, int N, int L, int C, int depth, int basepoin
 int signature_bwd_launch(const void *X, const void *gsig, int N, int L, int C, int depth, int basepoint, int dtype, void *gX,
                          long long sigdim, hipStream_t stream);
 int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes);
-int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, const void *grad_out, void *K_out,
-               void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream);
+int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, bool exact, const void *grad_out,
+               void *K_out, void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream);
 // the long-path route (gram_long.hip); the queries read the problem's shape, order and flags only
 int long_workspace(const LongProblem &p, int want_grad, size_t *bytes);
 int long_launch(const LongProblem &p);
@@ -117,6 +117,15 @@ static const char *static_kind_name(int kind)
     }
 }
 
+// SIGSVGD_FLAG_EXACT_ADJOINT on a route that has the GG kernels only: refused before any device work
+static int no_exact_adjoint(const char *who, unsigned flags)
+{
+    if (!(flags & SIGSVGD_FLAG_EXACT_ADJOINT)) return SIGSVGD_OK;
+    set_error("%s: SIGSVGD_FLAG_EXACT_ADJOINT is not built for this route (the gradient launches of sigsvgd_pde_fwd_bwd, "
+              "sigsvgd_gram_long_fwd_bwd / _fwd_bwd2 / _fwd_bwd_h and sigsvgd_pair_fwd_bwd / _fwd_bwd_h take it)", who);
+    return SIGSVGD_E_UNSUPPORTED;
+}
+
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
@@ -133,9 +142,10 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
 }
 
 // the shape, dtype, order and flag checks of the PDE entry points (sig_pde.hip): only SIGSVGD_FLAG_NAIVE_SOLVER means
-// anything there, every other bit is refused
-static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
+// anything there, and for a gradient launch (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; every other bit is refused
+static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags, bool grad = false)
 {
+    if (grad) flags &= ~SIGSVGD_FLAG_EXACT_ADJOINT;
     if (npairs < 1 || M < 2 || N < 2)
         return bad_arg("pde: bad shape npairs=%d M=%d N=%d (need npairs >= 1, M, N >= 2)", npairs, M, N);
     if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("pde: bad dtype %d", dtype);
@@ -148,8 +158,9 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags)
 // The checks of the long-path entry points (gram_long.hip), each condition in one place.  check_long: the Gram mode's, which
 // every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
 // know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_SYM
-// (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, every other bit is refused.
-static int check_long(const LongProblem &p, bool launch)
+// (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, and for a launch with the reverse
+// sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; every other bit is refused.
+static int check_long(const LongProblem &p, bool launch, bool grad = false)
 {
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
@@ -157,7 +168,8 @@ static int check_long(const LongProblem &p, bool launch)
                        p.TY, p.d);
     if (!static_kind_known(p.kind)) return bad_arg("gram_long: bad static kernel kind %d", p.kind);
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
-    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X;
+    const unsigned known =
+        SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u);
     if (p.flags & ~known)
         return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
@@ -176,9 +188,9 @@ static int check_long(const LongProblem &p, bool launch)
 
 // the two-sided entry points: check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says: one batch in both slots
 // (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
-static int check_long2(const LongProblem &p, bool launch, bool want_gradY)
+static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false)
 {
-    const int rc = check_long(p, launch);
+    const int rc = check_long(p, launch, grad);
     if (rc) return rc;
     if ((p.flags & SIGSVGD_FLAG_Y_IS_X) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
@@ -188,9 +200,10 @@ static int check_long2(const LongProblem &p, bool launch, bool want_gradY)
 }
 
 // the partial entry points: check_long's for one batch in both slots with SIGSVGD_FLAG_FOLD_TILES taken too, and the rank's
-// tiles: tile_offset in [0, tile_stride)
+// tiles: tile_offset in [0, tile_stride).  SIGSVGD_FLAG_EXACT_ADJOINT: UNSUPPORTED (gram_long_part_kernel has the GG sweep only)
 static int check_long_partial(const LongProblem &p, bool launch, int tile_offset, int tile_stride)
 {
+    if (no_exact_adjoint("gram_long_sym_partial", p.flags)) return SIGSVGD_E_UNSUPPORTED;
     LongProblem q = p;
     q.flags &= ~(unsigned)SIGSVGD_FLAG_FOLD_TILES;
     const int rc = check_long(q, launch);
@@ -201,15 +214,17 @@ static int check_long_partial(const LongProblem &p, bool launch, int tile_offset
 }
 
 // the paired entry points (B = 1: one column of pairs): the pointers, flags (SIGSVGD_FLAG_NAIVE_SOLVER only) and shape under
-// the mode's own name, then check_long's remaining conditions
-static int check_pair(const LongProblem &p, bool launch)
+// the mode's own name, then check_long's remaining conditions; `grad`: a launch with the reverse sweep, which takes
+// SIGSVGD_FLAG_EXACT_ADJOINT too
+static int check_pair(const LongProblem &p, bool launch, bool grad = false)
 {
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
-    if (p.flags & ~SIGSVGD_FLAG_NAIVE_SOLVER)
-        return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
+    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u);
+    if (p.flags & ~known)
+        return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~known);
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
-    return check_long(p, launch);
+    return check_long(p, launch, grad);
 }
 
 // the bandwidth entry points, after their mode's own checks: a static kernel that has a bandwidth,
@@ -391,6 +406,7 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     if (!static_kind_known(static_kind)) return bad_arg("bad static kernel kind %d", static_kind);
+    if (no_exact_adjoint("gram_workspace_bytes", flags)) return SIGSVGD_E_UNSUPPORTED;
     // The largest plan of the launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B
     // the symmetric launch and -- gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch
     // and, when A == B, the symmetric one.
@@ -433,6 +449,7 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
     if (rc) return rc;
     if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_fwd for forward only)");
     if ((flags & SIGSVGD_FLAG_Y_IS_X) && A != B) return bad_arg("Y_IS_X needs A == B");
+    if (no_exact_adjoint("gram_fwd_bwd", flags)) return SIGSVGD_E_UNSUPPORTED;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out,
                   K_out, gradX_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     Range range("sigsvgd_gram_fwd_bwd");
@@ -447,6 +464,7 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
     int rc = check_common(X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags, K_partial);
     if (rc) return rc;
     if (!grad_partial) return bad_arg("grad_partial == NULL");
+    if (no_exact_adjoint("sym_partial", flags)) return SIGSVGD_E_UNSUPPORTED;
     GramProblem p{X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags | SIGSVGD_FLAG_Y_IS_X, grad_out,
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     const GramRoute r = gram_route(p, true);
@@ -611,7 +629,7 @@ int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L
 int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes)
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
-    const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags);
+    const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags, want_grad != 0);
     if (rc) return rc;
     return pde_workspace(npairs, M, N, dyadic_order, want_grad ? 1 : 0, bytes);
 }
@@ -623,19 +641,20 @@ int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyad
     const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd");
-    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, nullptr, K_out, nullptr,
-                      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, false, nullptr, K_out,
+                      nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int dyadic_order, unsigned flags,
                         const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!G || !K_out || !dG_out) return bad_arg("pde_fwd_bwd: null pointer argument");
-    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
+    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags, true);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd_bwd");
-    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, grad_out, K_out, dG_out,
-                      workspace, workspace_bytes, static_cast<hipStream_t>(stream));
+    return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
+                      (flags & SIGSVGD_FLAG_EXACT_ADJOINT) != 0, grad_out, K_out, dG_out, workspace, workspace_bytes,
+                      static_cast<hipStream_t>(stream));
 }
 
 // ---- the long-path route (gram_long.hip): each entry point fills one LongProblem, checks it and hands it on ----------------
@@ -645,7 +664,7 @@ int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int d
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long(p, false);
+    const int rc = check_long(p, false, want_grad != 0);
     if (rc) return rc;
     return long_workspace(p, want_grad ? 1 : 0, bytes);
 }
@@ -668,7 +687,7 @@ int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long(p, true);
+    const int rc = check_long(p, true, true);
     if (rc) return rc;
     if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_long_fwd for forward only)");
     Range range("sigsvgd_gram_long_fwd_bwd");
@@ -680,7 +699,7 @@ int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order,
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false);
+    const int rc = check_pair(p, false, want_grad != 0);
     if (rc) return rc;
     return pair_workspace(p, want_grad ? 1 : 0, bytes);
 }
@@ -690,7 +709,7 @@ int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int st
 {
     if (!waves_per_pair || !grid || !lds_bytes) return bad_arg("pair: schedule query without a place for its answer");
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false);
+    const int rc = check_pair(p, false, want_grad != 0);
     if (rc) return rc;
     return pair_schedule(p, want_grad ? 1 : 0, waves_per_pair, grid, lds_bytes);
 }
@@ -713,7 +732,7 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_pair(p, true);
+    const int rc = check_pair(p, true, true);
     if (rc) return rc;
     if (!gradX_out && !gradY_out)
         return bad_arg("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
@@ -726,7 +745,7 @@ int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int 
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long2(p, false, want_gradY != 0);
+    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY);
     if (rc) return rc;
     return long2_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
@@ -737,7 +756,7 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long2(p, true, gradY_out != nullptr);
+    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out); // (neither: forward only)
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
     return long2_launch(p);
@@ -748,7 +767,7 @@ int sigsvgd_gram_long_h_workspace_bytes(int A, int B, int TX, int TY, int d, int
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    int rc = check_long2(p, false, want_gradY != 0);
+    int rc = check_long2(p, false, want_gradY != 0, true); // (the launch always runs the reverse sweep)
     if (!rc) rc = check_bandwidth("gram_long_h", p, false, nullptr);
     if (rc) return rc;
     return long2_h_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
@@ -761,7 +780,7 @@ int sigsvgd_gram_long_fwd_bwd_h(const void *X, const void *Y, int A, int B, int 
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    int rc = check_long2(p, true, gradY_out != nullptr);
+    int rc = check_long2(p, true, gradY_out != nullptr, true);
     if (!rc) rc = check_bandwidth("gram_long_h", p, true, dK_dinvh_out);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd_h");
@@ -773,7 +792,7 @@ int sigsvgd_pair_h_workspace_bytes(int A, int TX, int TY, int d, int dyadic_orde
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    int rc = check_pair(p, false);
+    int rc = check_pair(p, false, true);
     if (!rc) rc = check_bandwidth("pair_h", p, false, nullptr);
     if (rc) return rc;
     return pair_workspace(p, 1, bytes); // (the launch always runs the reverse sweep)
@@ -786,7 +805,7 @@ int sigsvgd_pair_fwd_bwd_h(const void *X, const void *Y, int A, int TX, int TY, 
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    int rc = check_pair(p, true);
+    int rc = check_pair(p, true, true);
     if (!rc) rc = check_bandwidth("pair_h", p, true, dK_dinvh_out);
     if (rc) return rc;
     Range range("sigsvgd_pair_fwd_bwd_h");

@@ -1,6 +1,7 @@
 // Host side of the long-path route (DESIGN.md sections 5.10 - 5.16): the slab reduce kernels, the plans of the four modes,
 // the workspace queries and the launchers.  The kernels and their families are in gram_long_kernels.h; this unit builds every
-// kind but the Matern ones, which family_launch sends to gram_long_matern.hip.
+// kind but the Matern ones, which family_launch sends to gram_long_matern.hip, and launches with SIGSVGD_FLAG_EXACT_ADJOINT
+//  go to gram_long_exact.hip: the plans, the workspace and everything behind the kernel are the same.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -298,6 +299,9 @@ double *long_colpart(const LongPlan &pl, const LongArgs &a)
 bool long_naive(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0; }
 bool long_yx(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_Y_IS_X) != 0; }
 bool long_fold(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_FOLD_TILES) != 0; }
+// SIGSVGD_FLAG_EXACT_ADJOINT where it changes the launch: with the first-order stencil GG is the exact
+// adjoint already, and the launch is the unflagged one
+bool long_exact(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_EXACT_ADJOINT) != 0 && !long_naive(p); }
 
 // out (the launch's dtype) = the sums of `rows` rows' slabs, long2_reduce_kernel
 int long2_reduce(const LongProblem &p, const double *partials, void *out, int rows, int nslabs, int TD, int skip,
@@ -338,10 +342,19 @@ int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t strea
     if (e != hipSuccess) return hip_fail(e, F::launch_failed);
     return SIGSVGD_OK;
 }
-// the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations
+// the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations; `exact`
+// (long_exact below: a gradient launch with the default stencil): gram_long_exact.hip's, for every kind
 template <typename F, typename Plan>
-int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a)
+int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a,
+                  bool exact = false)
 {
+    if (exact && grad && !naive) {
+        hipError_t e = long_exact_launch(F::id, dtype, kind, pl.grid, pl.lds, stream, &a);
+        if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+        return SIGSVGD_OK;
+    }
     if (kind != SIGSVGD_STATIC_MATERN32 && kind != SIGSVGD_STATIC_MATERN52) {
         if constexpr (F::bandwidth)
             return bw_launch<F>(dtype, kind, naive, pl, stream, a);
@@ -408,7 +421,7 @@ int long_launch(const LongProblem &p)
     LongArgs a;
     int rc = long_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
-    if (!rc) rc = family_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
+    if (!rc) rc = family_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, long_exact(p));
     if (!rc && want_grad) // a row's slabs in chunk order
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, pl.nchunks, p.TX * p.d, 0, "launch long2_reduce_kernel (rows)");
     return rc;
@@ -446,7 +459,8 @@ int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int 
     if (rc) return rc;
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
-    const bool bands = pair_use_bands(p.A, pl, bp);
+    // (the exact adjoint has the one-wavefront kernel only: pair_bands.hip has its own sweep)
+    const bool bands = !(want_grad && long_exact(p)) && pair_use_bands(p.A, pl, bp);
     *waves_per_pair = bands ? bp.NB : 1;
     *grid = bands ? bp.grid : pl.grid;
     *lds_bytes = bands ? bp.lds : pl.lds;
@@ -464,9 +478,11 @@ int pair_launch(const LongProblem &p)
     if (rc) return rc;
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
-    if (pair_use_bands(p.A, pl, bp)) return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
+    const bool exact = want_grad && long_exact(p); // (the one-wavefront schedule, as the bandwidth launch)
+    if (!exact && pair_use_bands(p.A, pl, bp))
+        return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
-    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a);
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact);
 }
 
 // The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
@@ -479,7 +495,7 @@ int pair_h_launch(const LongProblem &p, void *dk_out)
     if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
     a.gradX = p.gradX_out; a.gradY = p.gradY_out; a.dK_dinvh = dk_out;
-    return family_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
+    return family_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_exact(p));
 }
 
 // The two-sided launch, with the bandwidth derivative where dk_out is given (dk_out[A][B] =
@@ -501,9 +517,9 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
     a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
     if constexpr (BW) {
         a.dK_dinvh = dk_out;
-        rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a);
+        rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_exact(p));
     } else {
-        rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a);
+        rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_exact(p));
     }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,

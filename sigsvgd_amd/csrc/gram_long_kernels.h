@@ -1,6 +1,7 @@
 // The long-path kernels (gram_long_kernel, gram_long2_kernel, gram_long_part_kernel), their argument structs and their
-// families for ring_launch (ring_sweep.h).  Included by gram_long.hip (plans, reduce kernels, launchers; every kind but Matern)
-// and by gram_long_matern.hip (the Matern kinds' instantiations).
+// families for ring_launch (ring_sweep.h).  Included by gram_long.hip (plans, reduce kernels, launchers; every kind but Matern),
+// by gram_long_matern.hip (the Matern kinds' instantiations) and by gram_long_exact.hip and gram_long_exact_matern.hip (the
+// exact adjoint's instantiations).
 //
 // Signature-kernel Gram matrix and gradient for the built-in static kernels on long paths.
 //
@@ -102,10 +103,15 @@ struct PartArgs : LongArgs {
 // BW (paired mode only): after the pair's gradient passes one more pass chains the same S through the
 // static kernel's derivative in the bandwidth and stores the pair's dK / d inv_h; a compile-time branch, so the instantiations
 // without it keep their code.
-template <typename IO, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false, bool BW = false>
+// IOX: float, double, or ExactIO<float>, ExactIO<double> (ring_sweep.h): the sweeps of the exact adjoint
+// (default stencil, gradient launches); everything behind S is the same code.  Instantiated in gram_long_exact.hip and
+// gram_long_exact_matern.hip.
+template <typename IOX, bool NAIVE, bool GRAD, int KIND, bool PAIRED = false, bool BW = false>
 __global__ __launch_bounds__(64) void gram_long_kernel(
     std::conditional_t<BW, PairHArgs, std::conditional_t<PAIRED, PairArgs, LongArgs>> a)
 {
+    using IO = typename RingIO<IOX>::type;
+    constexpr bool EXACT = RingIO<IOX>::exact;
     static_assert(!BW || (PAIRED && GRAD), "the bandwidth pass needs the paired mode's reverse sweep");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
                 __syncthreads();
             };
 
-            const double Kval = ring_forward<NAIVE, GRAD>(rw, fill, stage_x);
+            const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rw, fill, stage_x);
             if (((rw.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
@@ -163,7 +169,7 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
             __syncthreads();
-            ring_reverse<NAIVE>(rw, fill, stage_x);
+            ring_reverse<NAIVE, EXACT>(rw, fill, stage_x);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
             __syncthreads();
 
@@ -199,9 +205,12 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
 // their code: the same staging, fill and sweeps per pair (K has the same bits), the items and the gradient passes differ.
 // BW: the bandwidth pass behind the pair's gradient passes, as in gram_long_kernel; with yx the pair
 // (i, j) stores its derivative at [i][j] and [j][i], as K's mirror does.
-template <typename IO, bool NAIVE, bool GRAD, int KIND, bool BW = false>
+// IOX: as in gram_long_kernel.
+template <typename IOX, bool NAIVE, bool GRAD, int KIND, bool BW = false>
 __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, Long2HArgs, Long2Args> a)
 {
+    using IO = typename RingIO<IOX>::type;
+    constexpr bool EXACT = RingIO<IOX>::exact;
     static_assert(!BW || GRAD, "the bandwidth pass needs the reverse sweep");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
@@ -262,7 +271,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                     __syncthreads();
                 };
 
-                const double Kval = ring_forward<NAIVE, GRAD>(rw, fill, stage_x);
+                const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rw, fill, stage_x);
                 if (((rw.P - 1) & (kWave - 1)) == lane) {
                     static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)Kval;
                     if (a.yx) static_cast<IO *>(a.K_out)[(size_t)j * a.B + i] = (IO)Kval; // the mirror: same bits
@@ -273,7 +282,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
                 __syncthreads();
-                ring_reverse<NAIVE>(rw, fill, stage_x);
+                ring_reverse<NAIVE, EXACT>(rw, fill, stage_x);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
                 __syncthreads();
 
@@ -489,6 +498,65 @@ struct Long2HFamily {
     template <typename IO, bool NAIVE, bool GRAD, int KIND>
     static constexpr auto kernel() { return &gram_long2_kernel<IO, NAIVE, true, KIND, true>; }
 };
+// the exact adjoint's families: their base's arguments, ids and texts, the exact kernels (default
+// stencil, always the reverse sweep)
+template <bool PAIRED>
+struct LongExactFamily : LongFamily<PAIRED> {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<ExactIO<IO>, false, true, KIND, PAIRED>; }
+};
+struct Long2ExactFamily : Long2Family {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<ExactIO<IO>, false, true, KIND>; }
+};
+struct PairHExactFamily : PairHFamily {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<ExactIO<IO>, false, true, KIND, true, true>; }
+};
+struct Long2HExactFamily : Long2HFamily {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<ExactIO<IO>, false, true, KIND, true>; }
+};
+// the launch of family `family` (F::id; not the partial mode's) with the exact kernel of `kind`, for the two units that build
+// them: the unit names its kinds, K0 .. (a kind of another unit: hipErrorInvalidValue)
+struct ExactPlan {
+    int grid;
+    size_t lds;
+};
+template <typename F, typename IO, int K0, int... KS>
+hipError_t exact_launch_kind(int kind, const ExactPlan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if (kind == K0) {
+        if constexpr (F::bandwidth && K0 == SIGSVGD_STATIC_LINEAR)
+            return hipErrorInvalidValue; // (no bandwidth: the entry points refuse it before this)
+        else
+            return ring_launch_one<F, IO, false, true, K0>(pl, stream, a);
+    }
+    if constexpr (sizeof...(KS) > 0)
+        return exact_launch_kind<F, IO, KS...>(kind, pl, stream, a);
+    else
+        return hipErrorInvalidValue;
+}
+template <typename F, int... KS>
+hipError_t exact_launch_family(int dtype, int kind, const ExactPlan &pl, hipStream_t stream, const void *args)
+{
+    const typename F::Args &a = *static_cast<const typename F::Args *>(args);
+    return dtype == SIGSVGD_F64 ? exact_launch_kind<F, double, KS...>(kind, pl, stream, a)
+                                : exact_launch_kind<F, float, KS...>(kind, pl, stream, a);
+}
+template <int... KS>
+hipError_t exact_launch_any(int family, int dtype, int kind, int grid, size_t lds, hipStream_t stream, const void *args)
+{
+    const ExactPlan pl{grid, lds};
+    switch (family) {
+    case LongFamily<false>::id: return exact_launch_family<LongExactFamily<false>, KS...>(dtype, kind, pl, stream, args);
+    case LongFamily<true>::id: return exact_launch_family<LongExactFamily<true>, KS...>(dtype, kind, pl, stream, args);
+    case Long2Family::id: return exact_launch_family<Long2ExactFamily, KS...>(dtype, kind, pl, stream, args);
+    case PairHFamily::id: return exact_launch_family<PairHExactFamily, KS...>(dtype, kind, pl, stream, args);
+    case Long2HFamily::id: return exact_launch_family<Long2HExactFamily, KS...>(dtype, kind, pl, stream, args);
+    }
+    return hipErrorInvalidValue;
+}
 struct PartFamily { // (always with the gradient)
     using Args = PartArgs;
     static constexpr bool has_kind = true, has_fwd_only = false, bandwidth = false;
@@ -508,5 +576,10 @@ struct PartFamily { // (always with the gradient)
 // plan's grid and LDS bytes, default stencil only; args: the family's F::Args.  gram_long.hip's family_launch calls it.
 hipError_t long_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
                               const void *args);
+// gram_long_exact.hip: the launch of family `family`'s exact-adjoint instantiation for `kind` (default
+// stencil, gradient launches; the Matern kinds from gram_long_exact_matern.hip).  gram_long.hip's family_launch calls it.
+hipError_t long_exact_launch(int family, int dtype, int kind, int grid, size_t lds, hipStream_t stream, const void *args);
+hipError_t long_exact_matern_launch(int family, int dtype, int kind, int grid, size_t lds, hipStream_t stream,
+                                    const void *args);
 
 } // namespace sigsvgd

@@ -14,6 +14,22 @@
 #include "sig_common.h"
 
 namespace sigsvgd {
+// The exact adjoint is a compile-time variant of the kernels on this sweep, named through their I/O
+// type: ExactIO<float> / ExactIO<double> in the place of float / double.  A flag of its own among the template parameters would
+// rename every instantiation the kernels already have; this way those keep their names and, statement for statement, their code.
+template <typename T>
+struct ExactIO {};
+template <typename T>
+struct RingIO {
+    using type = T;
+    static constexpr bool exact = false;
+};
+template <typename T>
+struct RingIO<ExactIO<T>> {
+    using type = T;
+    static constexpr bool exact = true;
+};
+
 namespace {
 constexpr int kRingMaxCells = 8192;                 // P and Q
 constexpr size_t kRingDoubles = 8192;               // 64 KB of increments per wave
@@ -175,9 +191,13 @@ __device__ __forceinline__ RingWave ring_wave(const Args &a, unsigned char *smem
 // fill(a0, b_lo, b_hi): coarse columns b_lo .. b_hi of the increment rows a0 .. a0 + nrow - 1 into the ring, between barriers;
 // band(a0): called as each band starts, before its first fill.  (The step of gram_generic_kernel: branch-free, results of
 // lanes outside the grid dropped by selects, the operands of step s + 1 fetched during step s.)
-template <bool NAIVE, bool GRAD, typename Fill, typename Band>
+// EXACT (default stencil with GRAD only): what the sweep keeps for the reverse sweep is not K00 =
+// K_fwd[p][q] but the cell's derivative of the step in its increment, c = (K10 + K01) (1/2 + g/6) + K00 g/6, in the same slot;
+// the arithmetic that produces K is the same.
+template <bool NAIVE, bool GRAD, bool EXACT = false, typename Fill, typename Band>
 __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, Band &&band)
 {
+    static_assert(!EXACT || (GRAD && !NAIVE), "the exact adjoint is the default stencil's, and a gradient launch's");
     const int lane = threadIdx.x;
     const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
     double *rowbuf = w.rowbuf;
@@ -211,7 +231,11 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
                 double up_in = shfl_up_f64(cur);
                 up_in = (lane == 0) ? rb : up_in;
                 const double nw = stencil(cur, up_in, upprev, gf * w.inv_r2, NAIVE);
-                if (GRAD) { // K_fwd[p][q] at [step][lane] (issued from inline asm: no wait for the previous step's store)
+                if constexpr (EXACT) { // c[p][q] at [step][lane], where K_fwd[p][q] goes otherwise
+                    const double g6 = gf * w.inv_r2 * (1.0 / 6.0);
+                    const float kst = (float)__builtin_fma(cur + up_in, 0.5 + g6, upprev * g6);
+                    asm volatile("global_store_dword %0, %1, off" ::"v"(wp + (size_t)s * kWave), "v"(kst));
+                } else if (GRAD) { // K_fwd[p][q] at [step][lane] (issued from inline asm: no wait for the previous step's store)
                     const float kst = (float)upprev;
                     asm volatile("global_store_dword %0, %1, off" ::"v"(wp + (size_t)s * kWave), "v"(kst));
                 }
@@ -229,9 +253,16 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
 
 // ---- reverse sweep: GG = K_fwd[p][q] K_rev[p+1][q+1], summed over the r columns of a block per lane, into w.wss -------------
 // (fill and band as in ring_forward; the caller makes the forward solution visible first)
-template <bool NAIVE, typename Fill, typename Band>
+// EXACT: the adjoint of the default stencil itself.  With lambda(p, q) = dK[P][Q] / dK[p+1][q+1],
+// alpha = A(g) lambda and beta = B(g) lambda of the lane's own cell (A = 1 + g/2 + g^2/12, B = 1 - g^2/12),
+//   lambda(p, q) = alpha(p, q+1) + h(p+1, q),   h(p+1, q) = alpha(p+1, q) - beta(p+1, q+1),   lambda(P-1, Q-1) = 1,
+// alpha = beta = 0 outside the grid.  Lane p + 1 is one column ahead, so h is the one number it formed on the step before
+// (its newest alpha less the beta of the step before that): the one shfl_down_f64 of the step moves it, and the band below
+// hands its row of h over in rowbuf.  The sum filed in w.wss is lambda c, c from ring_forward<.., EXACT>.
+template <bool NAIVE, bool EXACT = false, typename Fill, typename Band>
 __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Band &&band)
 {
+    static_assert(!EXACT || !NAIVE, "the exact adjoint is the default stencil's");
     const int lane = threadIdx.x;
     const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
     double *rowbuf = w.rowbuf;
@@ -247,6 +278,8 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
         const bool lastband = kb == w.nbands - 1;
         const bool hands_over = lane == 0 && kb > 0;
         double cur = 1.0, dprev = 1.0, sb = 0.0;
+        [[maybe_unused]] double bprev = 0.0; // EXACT: cur = h, dprev = the lane's newest alpha, bprev = its newest beta
+        if constexpr (EXACT) cur = dprev = 0.0;
         const int nsp = Q + L - 1;
         int q = Q - 1 + (L - 1 - lane);
         int R = Q - 1 + L - 1; // row of the stored forward solution on reverse step 0
@@ -267,6 +300,7 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
             double gf = Drow[(min(max(q, 0), Q - 1) >> n) & (W - 1)];
             double rbk = rowbuf[max(Q - 1 - sp0, 0)];
             rb = lastband ? 1.0 : rbk;
+            if constexpr (EXACT) rb = lastband ? (sp0 == 0 ? 1.0 : 0.0) : rbk; // (below the grid 0; the 1 is lambda(P-1, Q-1))
             // (the groups past nsp have no lane inside the grid and change nothing; their S stores go to the spare row)
             for (int sp1 = sp0; sp1 < sp0 + kWave; sp1 += KPF) {
 #pragma unroll
@@ -275,20 +309,38 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
                     const bool active = rowvalid && q >= 0 && q < Q;
                     const double gfn = Drow[(min(max(q - 1, 0), Q - 1) >> n) & (W - 1)];
                     const double rbr = rowbuf[max(Q - 2 - sp, 0)];
-                    const double rbn = lastband ? 1.0 : rbr;
+                    double rbn = lastband ? 1.0 : rbr;
+                    if constexpr (EXACT) rbn = lastband ? 0.0 : rbr;
                     const double kf = (double)kfr[u];
                     kfr[u] = wrow[(size_t)max(R - KPF, 0) * kWave];
                     double down_in = shfl_down_f64(cur);
                     down_in = (lane == L - 1) ? rb : down_in;
-                    sb = active ? __builtin_fma(kf, dprev, sb) : sb;
-                    const bool done = active && (q & (w.r - 1)) == 0; // the block's last (lowest) column
-                    const float sst = done ? (float)(sb * w.inv_r2) : 0.f;
-                    asm volatile("global_store_dword %0, %1, off" ::"v"(R >= 0 ? wsrow + (size_t)R * kWave : w.spare), "v"(sst));
-                    sb = done ? 0.0 : sb;
-                    const double nw = stencil(cur, down_in, dprev, gf * w.inv_r2, NAIVE);
-                    *((hands_over && active) ? rowbuf + q : w.dump + lane) = nw;
-                    cur = active ? nw : cur;
-                    dprev = active ? down_in : dprev;
+                    if constexpr (EXACT) {
+                        const double g = gf * w.inv_r2, b12 = g * g * (1.0 / 12.0);
+                        const double lam = dprev + down_in;
+                        const double al = __builtin_fma(lam, __builtin_fma(g, 0.5, b12), lam); // alpha
+                        const double be = __builtin_fma(-lam, b12, lam);                       // beta
+                        const double h = al - bprev;
+                        sb = active ? __builtin_fma(kf, lam, sb) : sb;
+                        const bool done = active && (q & (w.r - 1)) == 0; // the block's last (lowest) column
+                        const float sst = done ? (float)(sb * w.inv_r2) : 0.f;
+                        asm volatile("global_store_dword %0, %1, off" ::"v"(R >= 0 ? wsrow + (size_t)R * kWave : w.spare), "v"(sst));
+                        sb = done ? 0.0 : sb;
+                        *((hands_over && active) ? rowbuf + q : w.dump + lane) = h;
+                        cur = active ? h : cur;
+                        dprev = active ? al : dprev;
+                        bprev = active ? be : bprev;
+                    } else {
+                        sb = active ? __builtin_fma(kf, dprev, sb) : sb;
+                        const bool done = active && (q & (w.r - 1)) == 0; // the block's last (lowest) column
+                        const float sst = done ? (float)(sb * w.inv_r2) : 0.f;
+                        asm volatile("global_store_dword %0, %1, off" ::"v"(R >= 0 ? wsrow + (size_t)R * kWave : w.spare), "v"(sst));
+                        sb = done ? 0.0 : sb;
+                        const double nw = stencil(cur, down_in, dprev, gf * w.inv_r2, NAIVE);
+                        *((hands_over && active) ? rowbuf + q : w.dump + lane) = nw;
+                        cur = active ? nw : cur;
+                        dprev = active ? down_in : dprev;
+                    }
                     gf = gfn;
                     rb = rbn;
                 }

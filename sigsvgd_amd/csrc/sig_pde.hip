@@ -8,78 +8,11 @@
 // S[m][n] - S[m-1][n] - S[m][n-1]) with S = 0 outside the grid.
 //
 // Layout: the ring sweep of ring_sweep.h (the long-path mode of gram_generic_kernel), its ring filled from G in global
-// memory; the assembly reads S with ring_S.
-#include "ring_sweep.h"
+// memory; the assembly reads S with ring_S.  The kernel is in sig_pde_kernel.h.  With SIGSVGD_FLAG_EXACT_ADJOINT (default
+// stencil, gradient launches) S is the exact derivative of the discrete K in the increments.
+#include "sig_pde_kernel.h"
 
 namespace sigsvgd {
-
-struct PdeArgs {
-    const void *G, *grad_out;
-    void *K_out, *dG_out;
-    float *wsk;           // [grid][wsk_per_block]: forward solution, then S partials (+ one spare row)
-    size_t wsk_per_block; // floats
-    int npairs, M, N, n, r, P, Q, nbands, nsteps, nrow, W;
-    double inv_r2;
-};
-
-template <typename IO, bool NAIVE, bool GRAD>
-__global__ __launch_bounds__(64) void sig_pde_kernel(PdeArgs a)
-{
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    const int lane = threadIdx.x;
-    const int M = a.M, N = a.N, W = a.W, nrow = a.nrow;
-    const RingWave rw = ring_wave<GRAD>(a, smem_raw);
-    double *ring = rw.ring;
-    const IO *GO = static_cast<const IO *>(a.grad_out);
-    const auto no_band = [](int) {};
-
-    for (int pair = blockIdx.x; pair < a.npairs; pair += gridDim.x) {
-        const IO *G = static_cast<const IO *>(a.G) + (size_t)pair * M * N;
-        // coarse columns b_lo .. b_hi of the increment rows a0 .. a0 + nrow - 1 into the ring: lane = column, down the G rows
-        // (every load unconditional at a clamped address, so the compiler can issue them back to back)
-        auto fill = [&](int a0, int b_lo, int b_hi) {
-            __syncthreads(); // (the sweep's reads of the slots this overwrites are done)
-            for (int b0 = b_lo; b0 <= b_hi; b0 += kWave) {
-                const int b = b0 + lane;
-                const bool ok = b <= b_hi;
-                const IO *gc = G + min(b, N - 2);
-                double rd_prev = 0.0;
-#pragma unroll 4
-                for (int k = 0; k <= nrow; ++k) {
-                    const int ga = min(a0 + k, M - 1);
-                    const double rd = (double)gc[(size_t)ga * N + 1] - (double)gc[(size_t)ga * N];
-                    if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < M) ? rd - rd_prev : 0.0;
-                    rd_prev = rd;
-                }
-            }
-            __syncthreads();
-        };
-
-        const double Kval = ring_forward<NAIVE, GRAD>(rw, fill, no_band);
-        if (((rw.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[pair] = (IO)Kval;
-        if (!GRAD) continue;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
-        __syncthreads();
-        ring_reverse<NAIVE>(rw, fill, no_band);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before the assembly reads it
-        __syncthreads();
-
-        // ---- assembly: dG = grad_out * 4-corner scatter of S ------------------------------------------------------------
-        const int Mm = M - 1, Nm = N - 1;
-        const double w = GO ? (double)GO[pair] : 1.0;
-        IO *dG = static_cast<IO *>(a.dG_out) + (size_t)pair * M * N;
-        for (int e = lane; e < M * N; e += kWave) {
-            const int m = e / N, nn = e - m * N;
-            double Rv = 0.0;
-            if (m >= 1 && nn >= 1) Rv += ring_S(rw, m - 1, nn - 1);
-            if (m < Mm && nn < Nm) Rv += ring_S(rw, m, nn);
-            if (m >= 1 && nn < Nm) Rv -= ring_S(rw, m - 1, nn);
-            if (m < Mm && nn >= 1) Rv -= ring_S(rw, m, nn - 1);
-            dG[e] = (IO)(w * Rv);
-        }
-        __syncthreads(); // (the next pair's forward sweep overwrites the scratch and the ring)
-    }
-}
 
 namespace {
 struct PdePlan : RingPlan {
@@ -125,8 +58,8 @@ int pde_workspace(int npairs, int M, int N, int n, int want_grad, size_t *bytes)
 }
 
 // the argument checks are the entry points' (capi.hip); dG_out == NULL: forward only
-int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, const void *grad_out, void *K_out,
-               void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream)
+int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool naive, bool exact, const void *grad_out,
+               void *K_out, void *dG_out, void *ws, size_t ws_bytes, hipStream_t stream)
 {
     const int want_grad = dG_out != nullptr;
     PdePlan pl;
@@ -141,6 +74,12 @@ int pde_launch(const void *G, int npairs, int M, int N, int dtype, int n, bool n
     a.npairs = npairs; a.M = M; a.N = N; a.n = n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
     a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W;
     a.inv_r2 = 1.0 / ((double)pl.r * (double)pl.r);
+    if (exact && want_grad && !naive) { // (with the first-order stencil GG is the exact adjoint: the launch below)
+        hipError_t e = pde_exact_launch(dtype, pl.grid, pl.lds, stream, a);
+        if (e != hipSuccess) return hip_fail(e, PdeFamily::attr_failed);
+        e = hipGetLastError();
+        return e != hipSuccess ? hip_fail(e, PdeFamily::launch_failed) : SIGSVGD_OK;
+    }
     return ring_launch<PdeFamily>(dtype, SIGSVGD_STATIC_RBF, naive, want_grad != 0, pl, stream, a);
 }
 

@@ -133,7 +133,7 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
 
 
 def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
-           fp32_sweeps: bool = False) -> int:
+           fp32_sweeps: bool = False, exact_adjoint: bool = False) -> int:
     f = 0
     if naive:
         f |= _lib.FLAG_NAIVE_SOLVER
@@ -147,6 +147,8 @@ def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_for
         f |= _lib.FLAG_STORED_FORWARD
     if fp32_sweeps:
         f |= _lib.FLAG_FP32_SWEEPS
+    if exact_adjoint:
+        f |= _lib.FLAG_EXACT_ADJOINT
     return f
 
 
@@ -249,18 +251,21 @@ def gram_long_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = 
 
 def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                       grad_out: Optional[torch.Tensor] = None, naive: bool = False,
-                      sym: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                      sym: bool = False, exact_adjoint: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(K[A,B], gradX[A,TX,d]) with gradX = d sum(grad_out*K)/dX (first slot; grad_out None = ones; sym: grad_out +
     grad_out^T) on the long route (`sigsvgd_gram_long_fwd_bwd`).  Bit-reproducible.  Every ordered pair is solved, also
     when Y holds X's values, and Y gets no gradient: `gram_long_fwd_bwd2` solves Y = X once per unordered pair and returns
-    the gradients of both slots."""
+    the gradients of both slots.  exact_adjoint (SIGSVGD_FLAG_EXACT_ADJOINT; here and on every
+    gradient launch of the long route below): gX is the exact derivative of the discrete K returned -- the adjoint of the
+    default stencil itself -- instead of the reference's GG convention, which differs from it by per cents; K has the
+    same bits, the workspace the same bytes.  With naive=True (where GG is exact) it changes nothing."""
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
     go = _weights(grad_out, (A, B), Xc.dtype)
     if sym and (A != B or TX != TY):
         raise ValueError("sym needs X and Y of one shape")
-    flags = _flags(naive, sym, False, False)
+    flags = _flags(naive, sym, False, False, exact_adjoint=exact_adjoint)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_long_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
@@ -270,19 +275,21 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
 
 
 def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                     want_gradX: bool = True, want_gradY: bool = True, y_is_x: bool = False) -> bool:
+                     want_gradX: bool = True, want_gradY: bool = True, y_is_x: bool = False,
+                     exact_adjoint: bool = False) -> bool:
     """Whether `gram_long_fwd_bwd2` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS); any other error raises."""
     return _query("gram_long2_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                                  1 if want_gradX else 0, 1 if want_gradY else 0,
-                                                 _lib.FLAG_Y_IS_X if y_is_x else 0), (ctypes.c_size_t(0),), may_refuse=True)
+                                                 _flags(False, False, y_is_x, False, exact_adjoint=exact_adjoint)),
+                  (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                        grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
-                       y_is_x: bool = False, want_gradX: bool = True,
-                       want_gradY: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True,
+                       exact_adjoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(K[A,B], gX[A,TX,d] or None, gY[B,TY,d] or None) on the long route from one solve per pair
     (`sigsvgd_gram_long_fwd_bwd2`): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each its own slot (grad_out
     None = ones), K bit-identical to `gram_long_fwd`.  y_is_x (Y holds X's values; A == B, TX == TY): each unordered pair is
@@ -296,7 +303,7 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
         raise ValueError("sym and y_is_x need X and Y of one shape")
     want_gradY = bool(want_gradY) and not (sym or y_is_x)
     go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False)
+    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
     gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
@@ -309,22 +316,24 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
 
 
 def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-               want_grad: bool = True) -> bool:
+               want_grad: bool = True, exact_adjoint: bool = False) -> bool:
     """Whether `pair_fwd` (want_grad False) / `pair_fwd_bwd` take pairs X [A, TX, d], Y [A, TY, d]: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS); any other error raises."""
     return _query("pair_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                           1 if want_grad else 0, 0), (ctypes.c_size_t(0),), may_refuse=True)
+                                           1 if want_grad else 0, _flags(False, False, False, False, exact_adjoint=exact_adjoint)),
+                  (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def pair_schedule(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                  want_grad: bool = True) -> Tuple[int, int, int]:
+                  want_grad: bool = True, exact_adjoint: bool = False) -> Tuple[int, int, int]:
     """(waves_per_pair, grid, lds_bytes) of the paired launch these arguments would run now (`sigsvgd_pair_schedule`, host
     only, SIGSVGD_PAIR_MODE included): 1 wave per pair is the serial kernel of csrc/gram_long.hip, more the band-parallel one
-    of csrc/pair_bands.hip.  The results do not depend on it, bit for bit."""
+    of csrc/pair_bands.hip.  The results do not depend on it, bit for bit.  exact_adjoint: gradient launches with it always
+    run 1 wave per pair."""
     waves, grid, lds = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
-    _query("pair_schedule", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind), 1 if want_grad else 0, 0),
-           (waves, grid, lds))
+    _query("pair_schedule", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind), 1 if want_grad else 0,
+                             _flags(False, False, False, False, exact_adjoint=exact_adjoint)), (waves, grid, lds))
     return waves.value, grid.value, lds.value
 
 
@@ -351,8 +360,8 @@ def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
 
 
 def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                 grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True,
-                 want_y: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+                 grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True, want_y: bool = True,
+                 exact_adjoint: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(K[A], gX[A,TX,d] or None, gY[A,TY,d] or None): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each path's
     own slot (grad_out None = ones), from one forward and one reverse sweep per pair (`sigsvgd_pair_fwd_bwd`).  Computed
     and returned in X's dtype; bit-reproducible."""
@@ -362,7 +371,7 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
     go = _weights(grad_out, (A,), Xc.dtype)
-    flags = _flags(naive, False, False, False)
+    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
     gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
@@ -373,18 +382,20 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
 
 
 def gram_long_h_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                      want_gradX: bool = True, want_gradY: bool = True, naive: bool = False, y_is_x: bool = False) -> bool:
+                      want_gradX: bool = True, want_gradY: bool = True, naive: bool = False, y_is_x: bool = False,
+                      exact_adjoint: bool = False) -> bool:
     """Whether `gram_long_fwd_bwd_h` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, per-wave
     state beyond the LDS, or the first-order stencil with IMQ / rational quadratic / Matern); any other error raises."""
     return _query("gram_long_h_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                                   1 if want_gradX else 0, 1 if want_gradY else 0,
-                                                  _flags(naive, False, y_is_x, False)), (ctypes.c_size_t(0),), may_refuse=True)
+                                                  _flags(naive, False, y_is_x, False, exact_adjoint=exact_adjoint)),
+                  (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                         grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
-                        y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True):
+                        y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True, exact_adjoint: bool = False):
     """(K[A,B], gX or None, gY or None, dK_dinvh[A,B]): `gram_long_fwd_bwd2` with every pair's derivative of K in the
     static kernel's inverse bandwidth from the same reverse sweep (`sigsvgd_gram_long_fwd_bwd_h`, DESIGN.md section 5.16;
     RBF, IMQ, rational quadratic and Matern).  dK_dinvh is unweighted -- grad_out and sym weight gX and gY only -- and with y_is_x
@@ -397,7 +408,7 @@ def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: 
         raise ValueError("sym and y_is_x need X and Y of one shape")
     want_gradY = bool(want_gradY) and not (sym or y_is_x)
     go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False)
+    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     dK = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
@@ -411,15 +422,17 @@ def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: 
 
 
 def pair_h_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                 naive: bool = False) -> bool:
+                 naive: bool = False, exact_adjoint: bool = False) -> bool:
     """Whether `pair_fwd_bwd_h` takes pairs X [A, TX, d], Y [A, TY, d]: the library's workspace query, host only.  False
     exactly where it reports SIGSVGD_E_UNSUPPORTED (as `gram_long_h_takes`); any other error raises."""
     return _query("pair_h_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                             _flags(naive, False, False, False)), (ctypes.c_size_t(0),), may_refuse=True)
+                                             _flags(naive, False, False, False, exact_adjoint=exact_adjoint)),
+                  (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def pair_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                   grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True, want_y: bool = True):
+                   grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True, want_y: bool = True,
+                   exact_adjoint: bool = False):
     """(K[A], gX or None, gY or None, dK_dinvh[A]): `pair_fwd_bwd` with each pair's derivative of K in the static kernel's
     inverse bandwidth (`sigsvgd_pair_fwd_bwd_h`), unweighted; equal, bit for bit, to the diagonal of
     `gram_long_fwd_bwd_h`'s.  K, gX and gY have the bits `pair_fwd_bwd` returns; neither gradient wanted is allowed.  Always
@@ -428,7 +441,7 @@ def pair_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int =
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
     go = _weights(grad_out, (A,), Xc.dtype)
-    flags = _flags(naive, False, False, False)
+    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
     dK = torch.empty((A,), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
@@ -939,10 +952,11 @@ def pde_fwd(G, dyadic_order: int = 0, naive: bool = False) -> torch.Tensor:
 
 
 def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = None,
-                naive: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                naive: bool = False, exact_adjoint: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(K[npairs], dG[npairs, M, N]) with dG = d sum(grad_out * K) / dG (`sigsvgd_pde_fwd_bwd`; grad_out None = ones), in
     the reference's convention GG = K_fwd * K_rev (the exact adjoint for the naive stencil; what the built-in kernels
-    return).  Bit-reproducible."""
+    return), or with exact_adjoint (SIGSVGD_FLAG_EXACT_ADJOINT) the exact derivative of the discrete
+    K for the default stencil too; K has the same bits either way.  Bit-reproducible."""
     dev = _require_gpu(G, grad_out)
     Gc = _prep_grid(G)
     npairs, M, N = Gc.shape
@@ -951,7 +965,7 @@ def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = Non
         if grad_out.numel() != npairs:
             raise ValueError(f"grad_out must have {npairs} entries, got {tuple(grad_out.shape)}")
         go = grad_out.detach().reshape(npairs).to(Gc.dtype).contiguous()
-    flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
+    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint)
     K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
     dG = torch.empty_like(Gc)
     _launch(dev, "pde_fwd_bwd", (Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, _ptr(go),
@@ -963,13 +977,14 @@ def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = Non
 class PDESolve(torch.autograd.Function):
     """K[...] = signature kernel of every static-kernel grid G[..., M, N] (any leading shape).  Backward: dG from one
     `pde_fwd_bwd` launch with the incoming weights, so gradients reach whatever produced G -- the paths through a user's
-    `Gram_matrix`, and that static kernel's own parameters."""
+    `Gram_matrix`, and that static kernel's own parameters.  exact_adjoint: as `pde_fwd_bwd`'s."""
 
     @staticmethod
-    def forward(ctx, G, dyadic_order, naive):
+    def forward(ctx, G, dyadic_order, naive, exact_adjoint=False):
         lead, (M, N) = tuple(G.shape[:-2]), tuple(G.shape[-2:])
         Gf = G.detach().reshape(-1, M, N)
         ctx.cfg = (lead, int(dyadic_order), bool(naive))
+        ctx.exact_kw = {"exact_adjoint": True} if exact_adjoint else {}
         ctx.save_for_backward(Gf)
         return pde_fwd(Gf, dyadic_order, naive).reshape(lead)
 
@@ -977,5 +992,5 @@ class PDESolve(torch.autograd.Function):
     def backward(ctx, grad_output):
         (Gf,) = ctx.saved_tensors
         lead, dyadic_order, naive = ctx.cfg
-        _, dG = pde_fwd_bwd(Gf, dyadic_order, grad_output.reshape(-1), naive)
-        return dG.reshape(lead + tuple(Gf.shape[-2:])), None, None
+        _, dG = pde_fwd_bwd(Gf, dyadic_order, grad_output.reshape(-1), naive, **ctx.exact_kw)
+        return dG.reshape(lead + tuple(Gf.shape[-2:])), None, None, None

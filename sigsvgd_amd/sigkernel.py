@@ -308,6 +308,12 @@ def _fp32_kw(fp32_sweeps) -> dict:
     return {"fp32_sweeps": True} if fp32_sweeps else {}
 
 
+def _exact_kw(exact_grad) -> dict:
+    """the `exact_adjoint` keyword of the long route's gradient launches and queries (and `ops.PDESolve`'s trailing argument),
+    handed over only where it is set, as `_fp32_kw`"""
+    return {"exact_adjoint": True} if exact_grad else {}
+
+
 def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x, fp32_sweeps=False) -> bool:
     """True where the fused Gram kernels refuse the launch (`ops.gram_takes`: their per-pair state outgrows the LDS); the
     built-in static kernels then run on the long route (`ops.gram_long_fwd*`, csrc/gram_long.hip).  Every launch the
@@ -359,8 +365,12 @@ def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
     where `_long_yx_route` says so.  The long route gets K and both gradients from one `ops.gram_long_fwd_bwd2` launch (one
     solve per pair).  The fused route has no second-slot kernel: gY is the first slot of the swapped launch
     `ops.gram_fwd_bwd(Y, X, grad_out^T)`, a second launch.  fp32_sweeps (`SigKernel(..., fp32_sweeps=True)`) goes to the
-    fused launches and their queries; the long route has no such kernels and does not see it."""
-    static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps = cfg
+    fused launches and their queries; the long route has no such kernels and does not see it.  An eighth element of cfg,
+    exact_grad (`SigKernel(..., exact_grad=True)`): every gradient launch is the long route's with
+    `exact_adjoint=True`, whatever the shape (the fused kernels have the GG convention only); forward-only launches are
+    untouched."""
+    static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps, *rest = cfg
+    exact = bool(rest and rest[0])
     fkw = _fp32_kw(fp32_sweeps)
     if not (want_x or want_y):
         if not _long_route(X, Y, static_kind, dyadic_order, False, naive, False, y_is_x, fp32_sweeps):
@@ -370,6 +380,14 @@ def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
                                           want_gradX=False, want_gradY=False)
         return ops.gram_long_fwd(X, Y, inv_h, dyadic_order, static_kind, naive), None, None
     yx = y_is_x and not want_y  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
+    if exact:
+        if not ops.gram_long2_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], dyadic_order, static_kind,
+                                    want_x, want_y, yx, exact_adjoint=True):
+            raise _refused("compute_Gram", X, Y, dyadic_order, "the exact gradient (exact_grad=True)")
+        if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
+            return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x, want_y,
+                                          exact_adjoint=True)
+        return (*ops.gram_long_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, exact_adjoint=True), None)
     if _long_route(X, Y, static_kind, dyadic_order, True, naive, sym, yx and fused_yx, fp32_sweeps):
         if want_y or _long_yx_route(yx, X.shape[0], True, _device_cus(X)):
             return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x, want_y)
@@ -410,8 +428,9 @@ class _SigKernelGram(torch.autograd.Function):
     Any other grad_output triggers one more launch with the real weights.  `_solve_gram` chooses every launch."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y, fp32_sweeps=False):
-        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps)
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y, fp32_sweeps=False,
+                exact_grad=False):
+        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps, exact_grad)
         ctx.g_ones = ctx.gy_ones = None
         ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
         ctx.y_dtype = Y.dtype
@@ -433,7 +452,7 @@ class _SigKernelGram(torch.autograd.Function):
             _, gX, gY = _solve_gram(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
         if gY is not None:
             gY = gY.to(ctx.y_dtype)
-        return gX, gY, None, None, None, None, None, None, None, None, None
+        return gX, gY, None, None, None, None, None, None, None, None, None, None
 
 
 class _SigKernelPair(torch.autograd.Function):
@@ -445,12 +464,12 @@ class _SigKernelPair(torch.autograd.Function):
     there is one launch per call.  The launch computes in X's dtype; each gradient returns in its own input's dtype."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive):
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, exact_grad=False):
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ctx.dtypes = (X.dtype, Y.dtype)
         if want_x or want_y:
             K, gX, gY = ops.pair_fwd_bwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
-                                         want_y)
+                                         want_y, **_exact_kw(exact_grad))
             ctx.save_for_backward(gX, gY)
         else:
             K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive)
@@ -464,7 +483,7 @@ class _SigKernelPair(torch.autograd.Function):
             gX = (gX1 * grad_output.to(gX1.dtype)[:, None, None]).to(ctx.dtypes[0])
         if gY1 is not None:
             gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
-        return gX, gY, None, None, None, None
+        return gX, gY, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -490,9 +509,9 @@ def _sigma_grad(sigma_like, inv_h, grad_output, dK_dinvh):
     return g.to(device=sigma_like.device, dtype=sigma_like.dtype).reshape(sigma_like.shape)
 
 
-def _refused(what, X, Y, dyadic_order):
+def _refused(what, X, Y, dyadic_order, whose="the gradient of a static-kernel sigma"):
     return NotImplementedError(
-        f"{what}: the gradient of a static-kernel sigma runs on the long route only (csrc/gram_long.hip), which refuses "
+        f"{what}: {whose} runs on the long route only (csrc/gram_long.hip), which refuses "
         f"paths {tuple(X.shape)} x {tuple(Y.shape)} at dyadic order {dyadic_order}: {_lib.last_error()}")
 
 
@@ -504,7 +523,8 @@ class _SigKernelGramSigma(torch.autograd.Function):
     weights (the same bits as the bandwidth launch returns)."""
 
     @staticmethod
-    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y):
+    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y, exact_grad=False):
+        ctx.exact_kw = _exact_kw(exact_grad)
         ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
         ctx.yx = y_is_x and not ctx.want[1]  # (one tensor in both slots with grad_Y: both slots of every ordered pair)
         ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym)
@@ -513,7 +533,8 @@ class _SigKernelGramSigma(torch.autograd.Function):
         Xd, Yd = X.detach(), Y.detach()
         spec = speculate and any(ctx.want)
         K, ctx.g_ones, ctx.gy_ones, dK = ops.gram_long_fwd_bwd_h(Xd, Yd, inv_h, dyadic_order, static_kind, None, naive, sym,
-                                                                 ctx.yx, spec and ctx.want[0], spec and ctx.want[1])
+                                                                 ctx.yx, spec and ctx.want[0], spec and ctx.want[1],
+                                                                 **ctx.exact_kw)
         ctx.save_for_backward(Xd, Yd, dK)
         return K
 
@@ -526,10 +547,10 @@ class _SigKernelGramSigma(torch.autograd.Function):
         gX, gY = _scaled_ones(ctx.g_ones, ctx.gy_ones, grad_output)
         if gX is None and gY is None and (want_x or want_y):
             _, gX, gY = ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_output, naive, sym, ctx.yx,
-                                               want_x, want_y)
+                                               want_x, want_y, **ctx.exact_kw)
         if gY is not None:
             gY = gY.to(ctx.y_dtype)
-        return gX, gY, gS, None, None, None, None, None, None, None, None
+        return gX, gY, gS, None, None, None, None, None, None, None, None, None
 
 
 class _SigKernelPairSigma(torch.autograd.Function):
@@ -537,13 +558,13 @@ class _SigKernelPairSigma(torch.autograd.Function):
     the coordinate gradients needed, the per-pair dK / d inv_h), and a backward without launches."""
 
     @staticmethod
-    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive):
+    def forward(ctx, X, Y, sigma, static_kind, inv_h, dyadic_order, naive, exact_grad=False):
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ctx.dtypes = (X.dtype, Y.dtype)
         ctx.inv_h = inv_h
         ctx.sigma_like = sigma.detach()
         K, gX, gY, dK = ops.pair_fwd_bwd_h(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
-                                           want_y)
+                                           want_y, **_exact_kw(exact_grad))
         ctx.save_for_backward(gX, gY, dK)
         return K
 
@@ -557,7 +578,7 @@ class _SigKernelPairSigma(torch.autograd.Function):
             gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
         if ctx.needs_input_grad[2]:
             gS = _sigma_grad(ctx.sigma_like, ctx.inv_h, grad_output, dK)
-        return gX, gY, gS, None, None, None, None
+        return gX, gY, gS, None, None, None, None, None
 
 
 class SigKernel:
@@ -567,13 +588,27 @@ class SigKernel:
     3 <= T <= 64, d <= 16 run on the register-resident fp32-sweep kernel RBF runs there (K per entry within 1e-5, the gradient
     within 1e-5 of its largest entry) instead of the fp64 coverage kernel; everything else is unchanged.  It reaches the fused
     Gram launches only: the long route, the paired route of `compute_kernel` and a learned sigma (a `sigma` tensor that requires
-    grad takes the long route's bandwidth launch, section 5.16) ignore it."""
+    grad takes the long route's bandwidth launch, section 5.16) ignore it.
 
-    def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False):
+    exact_grad=True: every gradient -- of X, of Y, of a learned sigma, of a user static kernel's grid --
+    is the exact derivative of the discrete K the call returns (the adjoint of the default second-order stencil itself), where
+    the default is the reference's GG convention, which differs from it by per cents and is the gradient of no function: what
+    `compute_mmd(grad_Y=True)` training, a learned sigma, line-search optimisers and `torch.autograd.gradcheck` need.  Every
+    gradient-bearing launch of `compute_Gram`, `compute_kernel`, `compute_distance`, `compute_mmd` and `gram_and_grad` then
+    takes the long route with SIGSVGD_FLAG_EXACT_ADJOINT whatever the shape (fp64 sweeps; K keeps the long route's bits);
+    shapes the long route refuses raise NotImplementedError.  Forward-only calls are untouched, and so is `_naive_solver=True`,
+    whose GG is exact already.  Not together with fp32_sweeps (ValueError)."""
+
+    def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False,
+                 exact_grad: bool = False):
+        if exact_grad and fp32_sweeps:
+            raise ValueError("SigKernel: exact_grad=True runs every gradient launch on the long route's fp64 sweeps; "
+                             "fp32_sweeps=True selects an fp32-sweep kernel.  Use one of them")
         self.static_kernel = static_kernel
         self.dyadic_order = int(dyadic_order)
         self._naive_solver = bool(_naive_solver)
         self.fp32_sweeps = bool(fp32_sweeps)
+        self.exact_grad = bool(exact_grad)
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
@@ -589,7 +624,7 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
         if static_kind is None:  # user static kernel: its grid, the PDE on the device, autograd through both
             G = self.static_kernel.Gram_matrix(X, Y if sym or grad_Y else Y.detach())
-            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
+            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver, *_exact_kw(self.exact_grad).values())
         y_is_x = _same_storage(X, Y)
         if (not y_is_x and Y.shape == X.shape and Y.dtype == X.dtype and X.shape[0] >= self.value_check_min_batch
                 and bool(torch.equal(X.detach(), Y.detach()))):
@@ -602,12 +637,15 @@ class SigKernel:
         if sigma is not None:  # the long route's bandwidth launch, whatever the shape
             want_y = bool(grad_Y) and Y.requires_grad
             if not ops.gram_long_h_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order,
-                                         static_kind, X.requires_grad, want_y, self._naive_solver, y_is_x and not want_y):
+                                         static_kind, X.requires_grad, want_y, self._naive_solver, y_is_x and not want_y,
+                                         **_exact_kw(self.exact_grad)):
                 raise _refused("compute_Gram", X, Y, self.dyadic_order)
             return _SigKernelGramSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver,
-                                             bool(sym), y_is_x, self.speculate_ones, bool(grad_Y))
+                                             bool(sym), y_is_x, self.speculate_ones, bool(grad_Y),
+                                             *_exact_kw(self.exact_grad).values())
         return _SigKernelGram.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver, bool(sym),
-                                    y_is_x, self.speculate_ones, bool(grad_Y), self.fp32_sweeps)
+                                    y_is_x, self.speculate_ones, bool(grad_Y), self.fp32_sweeps,
+                                    *_exact_kw(self.exact_grad).values())
 
     # -- the rest of the upstream `sigkernel.SigKernel` surface [RECALLED from the public package; the
     #    reference tree never calls these].  compute_kernel / compute_distance differentiate both arguments (each its
@@ -623,15 +661,21 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
         if static_kind is None and hasattr(self.static_kernel, "batch_kernel"):
             G = self.static_kernel.batch_kernel(X, Y)
-            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver)
+            return ops.PDESolve.apply(G, self.dyadic_order, self._naive_solver, *_exact_kw(self.exact_grad).values())
         sigma = None if static_kind is None else _learned_sigma(self.static_kernel)
         if sigma is not None:  # the paired bandwidth launch, whatever the shape
             if not ops.pair_h_takes(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind,
-                                    self._naive_solver):
+                                    self._naive_solver, **_exact_kw(self.exact_grad)):
                 raise _refused("compute_kernel", X, Y, self.dyadic_order)
-            return _SigKernelPairSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver)
+            return _SigKernelPairSigma.apply(X, Y, sigma, static_kind, inv_h, self.dyadic_order, self._naive_solver,
+                                             *_exact_kw(self.exact_grad).values())
         if static_kind is not None:
             want_grad = torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)
+            if want_grad and self.exact_grad:  # the paired route with the flag, whatever the shape
+                if not ops.pair_takes(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind, True,
+                                      exact_adjoint=True):
+                    raise _refused("compute_kernel", X, Y, self.dyadic_order, "the exact gradient (exact_grad=True)")
+                return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver, True)
             if _pair_route(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], static_kind, self.dyadic_order, want_grad,
                            self._naive_solver, _device_cus(X), self.fp32_sweeps):
                 return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver)
@@ -657,7 +701,7 @@ class SigKernel:
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
-        cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None, self.fp32_sweeps)
+        cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None, self.fp32_sweeps, self.exact_grad)
         return _solve_gram(X, Yv, cfg, grad_out, True, False, True)[:2]
 
     def _user_gram_and_grad(self, X, Y, grad_out, sym):
@@ -671,7 +715,8 @@ class SigKernel:
         go = None if grad_out is None else grad_out.detach().to(G.dtype)
         if sym:
             go = torch.full((A, B), 2.0, dtype=G.dtype, device=G.device) if go is None else go + go.T
-        K, dG = ops.pde_fwd_bwd(G.detach().reshape(A * B, M, N), self.dyadic_order, go, self._naive_solver)
+        K, dG = ops.pde_fwd_bwd(G.detach().reshape(A * B, M, N), self.dyadic_order, go, self._naive_solver,
+                                **_exact_kw(self.exact_grad))
         (gX,) = torch.autograd.grad(G, Xg, dG.reshape(A, B, M, N))
         return K.reshape(A, B), gX
 
