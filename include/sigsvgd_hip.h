@@ -166,6 +166,24 @@ extern "C" {
                                       /* queries, sigsvgd_gram_fwd_bwd, sigsvgd_gram_sym_partial and sigsvgd_gram_workspace_bytes, whose     */
                                       /* routes have GG kernels only, return SIGSVGD_E_UNSUPPORTED.  A later revision of ABI 10: no new      */
                                       /* symbol, no changed signature; an earlier library answers SIGSVGD_E_BADARG                           */
+#define SIGSVGD_FLAG_NAN_TAILS 512u   /* variable-length batches on the long route: a path of X[A][TX][d] or        */
+                                      /* Y[B][TY][d] ends before its first point whose channel 0 is NaN (length L = that index, T where     */
+                                      /* there is none).  The path is its points 0 .. L-1 and pair (i, j) is solved on its own                */
+                                      /* r (L_i - 1) x r (L_j - 1) grid: K and the gradients have the bits of the unflagged 1 x 1 launch on    */
+                                      /* the truncated paths.  Rows m >= L of every gradient output are exact zeros, row L-1 is the end        */
+                                      /* point's whole gradient.  L = 1 is a one-point path: K = 1 exactly, no gradient.  L = 0 (a path that   */
+                                      /* starts with NaN) is the caller's error: it is treated as L = 1, the result is unspecified, nothing     */
+                                      /* is read or written out of bounds.  The lengths are found on the device by a pass of its own ahead of  */
+                                      /* the launch, on its stream (no read-back, no host sync: capturable), into int arrays at the head of    */
+                                      /* the workspace, which grows by them (padded to 256 B) and by nothing else; with SIGSVGD_FLAG_Y_IS_X     */
+                                      /* Y's lengths are X's.  Taken by sigsvgd_gram_long_fwd_bwd2 (every output combination, forward only     */
+                                      /* included) with sigsvgd_gram_long2_workspace_bytes, and by sigsvgd_pair_fwd, sigsvgd_pair_fwd_bwd,      */
+                                      /* sigsvgd_pair_workspace_bytes and sigsvgd_pair_schedule; paired launches run one wavefront per pair    */
+                                      /* with it (sigsvgd_pair_schedule says so).  SIGSVGD_E_UNSUPPORTED before any device work from           */
+                                      /* sigsvgd_gram_long_fwd, _fwd_bwd, _fwd_bwd_h, sigsvgd_pair_fwd_bwd_h, sigsvgd_gram_long_sym_partial     */
+                                      /* and their queries, and from every entry point when SIGSVGD_FLAG_EXACT_ADJOINT is set too.  Every       */
+                                      /* other entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol,     */
+                                      /* no changed signature; an earlier library answers SIGSVGD_E_BADARG                                     */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */

@@ -126,6 +126,24 @@ static int no_exact_adjoint(const char *who, unsigned flags)
     return SIGSVGD_E_UNSUPPORTED;
 }
 
+// SIGSVGD_FLAG_NAN_TAILS on the long route: refused before any device work by the entry points that
+// have no such kernels (`takes` false), and together with SIGSVGD_FLAG_EXACT_ADJOINT by all of them
+static int check_nan_tails(const char *who, unsigned flags, bool takes)
+{
+    if (!(flags & SIGSVGD_FLAG_NAN_TAILS)) return SIGSVGD_OK;
+    if (!takes) {
+        set_error("%s: SIGSVGD_FLAG_NAN_TAILS is not built for this entry point (sigsvgd_gram_long_fwd_bwd2, sigsvgd_pair_fwd, "
+                  "sigsvgd_pair_fwd_bwd, sigsvgd_pair_schedule and their workspace queries take it)", who);
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    if (flags & SIGSVGD_FLAG_EXACT_ADJOINT) {
+        set_error("%s: SIGSVGD_FLAG_NAN_TAILS together with SIGSVGD_FLAG_EXACT_ADJOINT is not built (the exact adjoint's kernels "
+                  "solve every pair on the launch's grid)", who);
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    return SIGSVGD_OK;
+}
+
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
@@ -159,9 +177,11 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags,
 // every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
 // know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_SYM
 // (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, and for a launch with the reverse
-// sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; every other bit is refused.
-static int check_long(const LongProblem &p, bool launch, bool grad = false)
+// sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; `nan_tails`: the entry point takes SIGSVGD_FLAG_NAN_TAILS
+// (the others answer UNSUPPORTED before anything else: check_nan_tails); every other bit is refused.
+static int check_long(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
 {
+    if (check_nan_tails("gram_long", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
@@ -169,7 +189,8 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false)
     if (!static_kind_known(p.kind)) return bad_arg("gram_long: bad static kernel kind %d", p.kind);
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
     const unsigned known =
-        SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u);
+        SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
+        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS : 0u);
     if (p.flags & ~known)
         return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
@@ -188,9 +209,9 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false)
 
 // the two-sided entry points: check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says: one batch in both slots
 // (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
-static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false)
+static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false, bool nan_tails = false)
 {
-    const int rc = check_long(p, launch, grad);
+    const int rc = check_long(p, launch, grad, nan_tails);
     if (rc) return rc;
     if ((p.flags & SIGSVGD_FLAG_Y_IS_X) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
@@ -215,16 +236,18 @@ static int check_long_partial(const LongProblem &p, bool launch, int tile_offset
 
 // the paired entry points (B = 1: one column of pairs): the pointers, flags (SIGSVGD_FLAG_NAIVE_SOLVER only) and shape under
 // the mode's own name, then check_long's remaining conditions; `grad`: a launch with the reverse sweep, which takes
-// SIGSVGD_FLAG_EXACT_ADJOINT too
-static int check_pair(const LongProblem &p, bool launch, bool grad = false)
+// SIGSVGD_FLAG_EXACT_ADJOINT too; `nan_tails`: as in check_long
+static int check_pair(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
 {
+    if (check_nan_tails("pair", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
-    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u);
+    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
+                           (nan_tails ? SIGSVGD_FLAG_NAN_TAILS : 0u);
     if (p.flags & ~known)
         return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~known);
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
-    return check_long(p, launch, grad);
+    return check_long(p, launch, grad, nan_tails);
 }
 
 // the bandwidth entry points, after their mode's own checks: a static kernel that has a bandwidth,
@@ -699,7 +722,7 @@ int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order,
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false, want_grad != 0);
+    const int rc = check_pair(p, false, want_grad != 0, true);
     if (rc) return rc;
     return pair_workspace(p, want_grad ? 1 : 0, bytes);
 }
@@ -709,7 +732,7 @@ int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int st
 {
     if (!waves_per_pair || !grid || !lds_bytes) return bad_arg("pair: schedule query without a place for its answer");
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false, want_grad != 0);
+    const int rc = check_pair(p, false, want_grad != 0, true);
     if (rc) return rc;
     return pair_schedule(p, want_grad ? 1 : 0, waves_per_pair, grid, lds_bytes);
 }
@@ -720,7 +743,7 @@ int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d,
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr, K_out, nullptr, nullptr,
                         workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_pair(p, true);
+    const int rc = check_pair(p, true, false, true);
     if (rc) return rc;
     Range range("sigsvgd_pair_fwd");
     return pair_launch(p);
@@ -732,7 +755,7 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_pair(p, true, true);
+    const int rc = check_pair(p, true, true, true);
     if (rc) return rc;
     if (!gradX_out && !gradY_out)
         return bad_arg("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
@@ -745,7 +768,7 @@ int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int 
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY);
+    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY, true);
     if (rc) return rc;
     return long2_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
@@ -756,7 +779,7 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out); // (neither: forward only)
+    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out, true); // (neither: forward only)
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
     return long2_launch(p);

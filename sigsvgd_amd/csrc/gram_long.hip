@@ -64,7 +64,8 @@ struct LongPlan : RingPlan {
     int JC, nchunks, grid;
     long long items;
     size_t wsk_bytes, partial_bytes, col_bytes = 0; // the forward scratch, the row-side slabs, the column-side slabs
-    size_t total() const { return ring_ws_total(wsk_bytes + partial_bytes + col_bytes); }
+    size_t len_bytes = 0; // SIGSVGD_FLAG_NAN_TAILS: the paths' lengths, ahead of the forward scratch
+    size_t total() const { return ring_ws_total(len_bytes + wsk_bytes + partial_bytes + col_bytes); }
 };
 
 // The grid of a launch of pl.items work items and its forward scratch: one wavefront per item up to what the device holds,
@@ -281,8 +282,8 @@ int long_args(const char *who, const LongPlan &pl, const LongProblem &p, int B, 
     const int rc = ring_ws_base(who, p.ws, p.ws_bytes, pl.total(), base);
     if (rc) return rc;
     a.X = p.X; a.Y = p.Y; a.grad_out = p.grad_out; a.K_out = p.K_out;
-    a.wsk = reinterpret_cast<float *>(base);
-    a.partials = pl.partial_bytes ? reinterpret_cast<double *>(base + pl.wsk_bytes) : nullptr;
+    a.wsk = reinterpret_cast<float *>(base + pl.len_bytes); // (behind the lengths of a launch with NaN-marked tails)
+    a.partials = pl.partial_bytes ? reinterpret_cast<double *>(base + pl.len_bytes + pl.wsk_bytes) : nullptr;
     a.wsk_per_block = pl.per_wave / sizeof(float);
     a.A = p.A; a.B = B; a.M = p.TX; a.N = p.TY; a.d = p.d; a.n = p.n; a.r = pl.r; a.P = pl.P; a.Q = pl.Q;
     a.nbands = pl.nbands; a.nsteps = pl.nsteps; a.nrow = pl.nrow; a.W = pl.W; a.JC = pl.JC; a.nchunks = pl.nchunks;
@@ -302,6 +303,20 @@ bool long_fold(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_FOLD_TILES
 // SIGSVGD_FLAG_EXACT_ADJOINT where it changes the launch: with the first-order stencil GG is the exact
 // adjoint already, and the launch is the unflagged one
 bool long_exact(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_EXACT_ADJOINT) != 0 && !long_naive(p); }
+// SIGSVGD_FLAG_NAN_TAILS: the bytes of the launch's length arrays (nY: Y's paths, 0 where Y is X), and
+// the length pass into them, ahead of the launch on its stream (a: the launch's arguments, whose scratch follows the arrays)
+bool long_nan_tails(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAN_TAILS) != 0; }
+void long_set_lengths(const LongProblem &p, int nY, LongPlan &pl)
+{
+    pl.len_bytes = long_nan_tails(p) ? nan_tail_bytes(p.A, nY) : 0;
+}
+int long_find_lengths(const LongProblem &p, int nY, const LongPlan &pl, const LongArgs &a)
+{
+    if (!long_nan_tails(p)) return SIGSVGD_OK;
+    int *lens = reinterpret_cast<int *>(reinterpret_cast<unsigned char *>(a.wsk) - pl.len_bytes);
+    const hipError_t e = long_nan_tail_lengths(p.dtype, p.X, p.A, p.TX, nY ? p.Y : nullptr, nY, p.TY, p.d, lens, p.stream);
+    return e != hipSuccess ? hip_fail(e, "launch nan_tail_length_kernel") : SIGSVGD_OK;
+}
 
 // out (the launch's dtype) = the sums of `rows` rows' slabs, long2_reduce_kernel
 int long2_reduce(const LongProblem &p, const double *partials, void *out, int rows, int nslabs, int TD, int skip,
@@ -343,11 +358,19 @@ int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t strea
     return SIGSVGD_OK;
 }
 // the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations; `exact`
-// (long_exact below: a gradient launch with the default stencil): gram_long_exact.hip's, for every kind
+// (long_exact below: a gradient launch with the default stencil): gram_long_exact.hip's, for every kind; `nan_tails`
+// (SIGSVGD_FLAG_NAN_TAILS, the paired and the two-sided family): gram_long_nantail.hip's, for every kind and both stencils
 template <typename F, typename Plan>
 int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a,
-                  bool exact = false)
+                  bool exact = false, bool nan_tails = false)
 {
+    if (nan_tails) { // (the entry points refuse it with the exact adjoint and on the families that have no such kernels)
+        hipError_t e = long_nan_tail_launch(F::id, dtype, kind, naive, grad, pl.grid, pl.lds, stream, &a);
+        if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+        return SIGSVGD_OK;
+    }
     if (exact && grad && !naive) {
         hipError_t e = long_exact_launch(F::id, dtype, kind, pl.grid, pl.lds, stream, &a);
         if (e != hipSuccess) return hip_fail(e, F::attr_failed);
@@ -380,12 +403,15 @@ int long_workspace(const LongProblem &p, int want_grad, size_t *bytes)
 }
 int pair_workspace(const LongProblem &p, int want_grad, size_t *bytes)
 {
-    return ring_plan_total<LongPlan>(
-        bytes, [&](LongPlan &pl) { return pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl); });
+    return ring_plan_total<LongPlan>(bytes, [&](LongPlan &pl) {
+        long_set_lengths(p, p.A, pl);
+        return pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
+    });
 }
 int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t *bytes)
 {
     return ring_plan_total<Long2Plan>(bytes, [&](Long2Plan &pl) {
+        long_set_lengths(p, long_yx(p) ? 0 : p.B, pl);
         return long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl);
     });
 }
@@ -460,7 +486,8 @@ int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int 
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
     // (the exact adjoint has the one-wavefront kernel only: pair_bands.hip has its own sweep)
-    const bool bands = !(want_grad && long_exact(p)) && pair_use_bands(p.A, pl, bp);
+    // (and so have launches with NaN-marked tails, whose pairs differ in their bands)
+    const bool bands = !(want_grad && long_exact(p)) && !long_nan_tails(p) && pair_use_bands(p.A, pl, bp);
     *waves_per_pair = bands ? bp.NB : 1;
     *grid = bands ? bp.grid : pl.grid;
     *lds_bytes = bands ? bp.lds : pl.lds;
@@ -473,16 +500,19 @@ int pair_launch(const LongProblem &p)
     const bool want_grad = p.gradX_out != nullptr || p.gradY_out != nullptr;
     LongPlan pl;
     PairArgs a;
+    long_set_lengths(p, p.A, pl);
     int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
     const bool exact = want_grad && long_exact(p); // (the one-wavefront schedule, as the bandwidth launch)
-    if (!exact && pair_use_bands(p.A, pl, bp))
+    if (!exact && !long_nan_tails(p) && pair_use_bands(p.A, pl, bp))
         return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
-    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact);
+    rc = long_find_lengths(p, p.A, pl, a);
+    if (rc) return rc;
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact, long_nan_tails(p));
 }
 
 // The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
@@ -510,6 +540,7 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
     const bool yx = long_yx(p), want_row = p.gradX_out != nullptr, want_col = p.gradY_out != nullptr || (yx && want_row);
     Long2Plan pl;
     std::conditional_t<BW, Long2HArgs, Long2Args> a;
+    long_set_lengths(p, yx ? 0 : p.B, pl); // (BW: the entry points refuse the flag)
     int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_row, p.gradY_out != nullptr, yx, pl, BW);
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
     if (rc) return rc;
@@ -519,7 +550,10 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
         a.dK_dinvh = dk_out;
         rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_exact(p));
     } else {
-        rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_exact(p));
+        rc = long_find_lengths(p, yx ? 0 : p.B, pl, a);
+        if (!rc)
+            rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_exact(p),
+                                            long_nan_tails(p));
     }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,

@@ -1,7 +1,8 @@
 // The long-path kernels (gram_long_kernel, gram_long2_kernel, gram_long_part_kernel), their argument structs and their
 // families for ring_launch (ring_sweep.h).  Included by gram_long.hip (plans, reduce kernels, launchers; every kind but Matern),
-// by gram_long_matern.hip (the Matern kinds' instantiations) and by gram_long_exact.hip and gram_long_exact_matern.hip (the
-// exact adjoint's instantiations).
+// by gram_long_matern.hip (the Matern kinds' instantiations), by gram_long_exact.hip and gram_long_exact_matern.hip (the
+// exact adjoint's instantiations) and by gram_long_nantail.hip and gram_long_nantail_matern.hip (the
+// instantiations for batches of paths of different lengths).
 //
 // Signature-kernel Gram matrix and gradient for the built-in static kernels on long paths.
 //
@@ -100,6 +101,37 @@ struct PartArgs : LongArgs {
 };
 
 
+// NaN-marked tails: the helpers of the NanTailIO instantiations of the two kernels below.
+namespace {
+// the launch's view with the geometry of a pair of Mp x Np points: the plan's LDS and scratch layout, a prefix of each used
+__device__ __forceinline__ RingWave nan_tail_wave(const RingWave &rw, int Mp, int Np)
+{
+    RingWave w = rw;
+    w.N = Np;
+    w.P = rw.r * (Mp - 1);
+    w.Q = rw.r * (Np - 1);
+    w.nbands = (w.P + kWave - 1) / kWave;
+    w.nsteps = w.Q + kWave - 1;
+    return w;
+}
+template <bool NT>
+__device__ __forceinline__ const RingWave &nan_tail_pick(const RingWave &launch, const RingWave &pair)
+{
+    if constexpr (NT)
+        return pair;
+    else
+        return launch;
+}
+// exact zeros into rows from .. to - 1 of the [to][d] block that starts at row `row0` of out (out may be NULL: nothing)
+template <typename T>
+__device__ __forceinline__ void nan_tail_zero_rows(T *out, size_t row0, int from, int to, int d)
+{
+    if (!out) return;
+    T *o = out + row0 * d;
+    for (int e = from * d + (int)threadIdx.x; e < to * d; e += kWave) o[e] = (T)0;
+}
+} // namespace
+
 // BW (paired mode only): after the pair's gradient passes one more pass chains the same S through the
 // static kernel's derivative in the bandwidth and stores the pair's dK / d inv_h; a compile-time branch, so the instantiations
 // without it keep their code.
@@ -112,7 +144,9 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
 {
     using IO = typename RingIO<IOX>::type;
     constexpr bool EXACT = RingIO<IOX>::exact;
+    constexpr bool NT = RingIO<IOX>::nan_tails; // (the paired mode only, no bandwidth pass)
     static_assert(!BW || (PAIRED && GRAD), "the bandwidth pass needs the paired mode's reverse sweep");
+    static_assert(!NT || (PAIRED && !BW), "NaN-marked tails: the paired mode without the bandwidth pass");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -120,6 +154,11 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
     double *ring = rw.ring;
     double *xs = rw.dump + kWave; // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
     const IO *GO = static_cast<const IO *>(a.grad_out);
+    [[maybe_unused]] const int *lenX = nullptr, *lenY = nullptr;
+    if constexpr (NT) {
+        lenX = nan_tail_lengths(a.wsk, a.A, a.A);
+        lenY = lenX + a.A;
+    }
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
         const int i = PAIRED ? (int)item : (int)(item / a.nchunks);
@@ -129,11 +168,30 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
 
         for (int j = j0; j < j1; ++j) {
             const IO *yj = static_cast<const IO *>(a.Y) + (size_t)j * N * d;
+            // NaN-marked tails: the pair's own lengths and grid (Mp = M, Np = N and rp = rw otherwise)
+            int Mp = M, Np = N;
+            [[maybe_unused]] RingWave rwl;
+            if constexpr (NT) {
+                Mp = __builtin_amdgcn_readfirstlane(lenX[i]);
+                Np = __builtin_amdgcn_readfirstlane(lenY[j]);
+                if constexpr (PAIRED) {
+                    if (Mp < 2 || Np < 2) { // a one-point path: K = 1 exactly, no gradient
+                        if (lane == 0) static_cast<IO *>(a.K_out)[i] = (IO)1.0;
+                        if constexpr (GRAD) {
+                            nan_tail_zero_rows(static_cast<IO *>(a.gradX), (size_t)i * M, 0, M, d);
+                            nan_tail_zero_rows(static_cast<IO *>(a.gradY), (size_t)i * N, 0, N, d);
+                        }
+                        continue;
+                    }
+                }
+                rwl = nan_tail_wave(rw, Mp, Np);
+            }
+            const RingWave &rp = nan_tail_pick<NT>(rw, rwl);
             // the band's points of X_i (before the band's first fill, whose barrier publishes them)
             auto stage_x = [&](int a0) {
                 for (int e = lane; e < (nrow + 1) * d; e += kWave) {
                     const int k = e / d;
-                    xs[e] = (double)xi[(size_t)min(a0 + k, M - 1) * d + (e - k * d)];
+                    xs[e] = (double)xi[(size_t)min(a0 + k, Mp - 1) * d + (e - k * d)];
                 }
             };
             // coarse columns b_lo .. b_hi of the increment rows a0 .. a0 + nrow - 1 into the ring: lane l evaluates the static
@@ -144,7 +202,7 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
                 for (int b0 = b_lo; b0 <= b_hi; b0 += kWave - 1) {
                     const int b = b0 + lane;
                     const bool ok = lane < kWave - 1 && b <= b_hi;
-                    const IO *yb = yj + (size_t)min(b, N - 1) * d;
+                    const IO *yb = yj + (size_t)min(b, Np - 1) * d;
                     // (up to 16 channels the lane's point stays in registers for the whole column: one round of loads)
                     double yv[16];
 #pragma unroll
@@ -154,22 +212,22 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
                         const double g = d <= 16 ? static_k16<KIND>(xs + k * d, yv, d, a.inv_h)
                                                  : static_k<KIND>(xs + k * d, yb, d, a.inv_h);
                         const double rd = shfl_down_f64(g) - g; // k(x_{a0+k}, y_{b+1}) - k(x_{a0+k}, y_b)
-                        if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < M) ? rd - rd_prev : 0.0;
+                        if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < Mp) ? rd - rd_prev : 0.0;
                         rd_prev = rd;
                     }
                 }
                 __syncthreads();
             };
 
-            const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rw, fill, stage_x);
-            if (((rw.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
+            const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rp, fill, stage_x);
+            if (((rp.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
                 continue;
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
             __syncthreads();
-            ring_reverse<NAIVE, EXACT>(rw, fill, stage_x);
+            ring_reverse<NAIVE, EXACT>(rp, fill, stage_x);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
             __syncthreads();
 
@@ -179,19 +237,23 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
             if constexpr (PAIRED) { // (either output skipped when NULL)
                 IO *gX = static_cast<IO *>(a.gradX), *gY = static_cast<IO *>(a.gradY);
                 if (gX)
-                    static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
+                    static_grad_pass<KIND, true>(rp, xi, Mp, yj, Np, d, a.inv_h, [&](int m, int c, double g) {
                         gX[((size_t)i * M + m) * d + c] = (IO)(w * g);
                     });
                 if (gY)
-                    static_grad_pass<KIND, false>(rw, yj, N, xi, M, d, a.inv_h, [&](int nn, int c, double g) {
+                    static_grad_pass<KIND, false>(rp, yj, Np, xi, Mp, d, a.inv_h, [&](int nn, int c, double g) {
                         gY[((size_t)i * N + nn) * d + c] = (IO)(w * g);
                     });
+                if constexpr (NT) { // the rows past the path's end: exact zeros
+                    nan_tail_zero_rows(gX, (size_t)i * M, Mp, M, d);
+                    nan_tail_zero_rows(gY, (size_t)i * N, Np, N, d);
+                }
                 if constexpr (BW) { // (unweighted: K's own derivative)
-                    const double dk = static_bw_pass<KIND>(rw, xi, M, yj, N, d, a.inv_h);
+                    const double dk = static_bw_pass<KIND>(rp, xi, Mp, yj, Np, d, a.inv_h);
                     if (lane == 0) static_cast<IO *>(a.dK_dinvh)[i] = (IO)dk;
                 }
             } else { // into the item's slab, in j order
-                static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
+                static_grad_pass<KIND, true>(rp, xi, Mp, yj, Np, d, a.inv_h, [&](int m, int c, double g) {
                     double *o = slab + (size_t)m * d + c;
                     *o = j == j0 ? w * g : __builtin_fma(w, g, *o);
                 });
@@ -211,7 +273,9 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
 {
     using IO = typename RingIO<IOX>::type;
     constexpr bool EXACT = RingIO<IOX>::exact;
+    constexpr bool NT = RingIO<IOX>::nan_tails; // (no bandwidth pass)
     static_assert(!BW || GRAD, "the bandwidth pass needs the reverse sweep");
+    static_assert(!NT || !BW, "NaN-marked tails: no bandwidth pass");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -219,6 +283,11 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
     double *ring = rw.ring;
     double *xs = rw.dump + kWave; // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
     const IO *GO = static_cast<const IO *>(a.grad_out);
+    [[maybe_unused]] const int *lenX = nullptr, *lenY = nullptr;
+    if constexpr (NT) { // (yx: one array serves both slots)
+        lenX = nan_tail_lengths(a.wsk, a.A, a.yx ? 0 : a.B);
+        lenY = a.yx ? lenX : lenX + a.A;
+    }
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
         // the item's tile (ti, tj): rows i0 .. i1 - 1 x columns j0 .. j1 - 1, walked row by row
@@ -241,12 +310,36 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
 
             for (int j = jfirst; j < j1; ++j) {
                 const IO *yj = static_cast<const IO *>(a.Y) + (size_t)j * N * d;
+                // NaN-marked tails: the pair's own lengths and grid (Mp = M, Np = N and rp = rw otherwise)
+                int Mp = M, Np = N;
+                [[maybe_unused]] RingWave rwl;
+                if constexpr (NT) {
+                    Mp = __builtin_amdgcn_readfirstlane(lenX[i]);
+                    Np = __builtin_amdgcn_readfirstlane(lenY[j]);
+                    if (Mp < 2 || Np < 2) { // a one-point path: K = 1 exactly, no gradient; a slab's first pair stores it whole
+                        if (lane == 0) {
+                            static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)1.0;
+                            if (a.yx) static_cast<IO *>(a.K_out)[(size_t)j * a.B + i] = (IO)1.0;
+                        }
+                        if constexpr (GRAD) {
+                            if (a.want_row && j == jfirst)
+                                nan_tail_zero_rows(a.partials, (a.yx ? (size_t)i * (a.nti + 1) + tj + 1 : (size_t)i * a.nchunks + tj) * M,
+                                                   0, M, d);
+                            if (a.want_col && !(a.yx && i == j) && i == i0)
+                                nan_tail_zero_rows(a.yx ? a.partials : a.colpart,
+                                                   (a.yx ? (size_t)j * (a.nti + 1) + ti : (size_t)j * a.nti + ti) * N, 0, N, d);
+                        }
+                        continue;
+                    }
+                    rwl = nan_tail_wave(rw, Mp, Np);
+                }
+                const RingWave &rp = nan_tail_pick<NT>(rw, rwl);
                 // staging and fill: gram_long_kernel's, statement for statement (K must have its bits); a copy because
                 // the shared helper measured slower (profiles/long_shared_solve_ab.txt)
                 auto stage_x = [&](int a0) {
                     for (int e = lane; e < (nrow + 1) * d; e += kWave) {
                         const int k = e / d;
-                        xs[e] = (double)xi[(size_t)min(a0 + k, M - 1) * d + (e - k * d)];
+                        xs[e] = (double)xi[(size_t)min(a0 + k, Mp - 1) * d + (e - k * d)];
                     }
                 };
                 auto fill = [&](int a0, int b_lo, int b_hi) {
@@ -254,7 +347,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                     for (int b0 = b_lo; b0 <= b_hi; b0 += kWave - 1) {
                         const int b = b0 + lane;
                         const bool ok = lane < kWave - 1 && b <= b_hi;
-                        const IO *yb = yj + (size_t)min(b, N - 1) * d;
+                        const IO *yb = yj + (size_t)min(b, Np - 1) * d;
                         // (up to 16 channels the lane's point stays in registers for the whole column: one round of loads)
                         double yv[16];
 #pragma unroll
@@ -264,15 +357,15 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                             const double g = d <= 16 ? static_k16<KIND>(xs + k * d, yv, d, a.inv_h)
                                                      : static_k<KIND>(xs + k * d, yb, d, a.inv_h);
                             const double rd = shfl_down_f64(g) - g; // k(x_{a0+k}, y_{b+1}) - k(x_{a0+k}, y_b)
-                            if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < M) ? rd - rd_prev : 0.0;
+                            if (k >= 1 && ok) ring[(k - 1) * W + (b & (W - 1))] = (a0 + k < Mp) ? rd - rd_prev : 0.0;
                             rd_prev = rd;
                         }
                     }
                     __syncthreads();
                 };
 
-                const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rw, fill, stage_x);
-                if (((rw.P - 1) & (kWave - 1)) == lane) {
+                const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rp, fill, stage_x);
+                if (((rp.P - 1) & (kWave - 1)) == lane) {
                     static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)Kval;
                     if (a.yx) static_cast<IO *>(a.K_out)[(size_t)j * a.B + i] = (IO)Kval; // the mirror: same bits
                 }
@@ -282,7 +375,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
                 __syncthreads();
-                ring_reverse<NAIVE, EXACT>(rw, fill, stage_x);
+                ring_reverse<NAIVE, EXACT>(rp, fill, stage_x);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
                 __syncthreads();
 
@@ -301,17 +394,21 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                 double *cs = a.yx ? a.partials + ((size_t)j * (a.nti + 1) + ti) * TDx
                                   : a.colpart + ((size_t)j * a.nti + ti) * TDy;
                 if (a.want_row)
-                    static_grad_pass<KIND, true>(rw, xi, M, yj, N, d, a.inv_h, [&](int m, int c, double g) {
+                    static_grad_pass<KIND, true>(rp, xi, Mp, yj, Np, d, a.inv_h, [&](int m, int c, double g) {
                         double *o = rs + (size_t)m * d + c;
                         *o = j == jfirst ? w * g : __builtin_fma(w, g, *o);
                     });
                 if (a.want_col && !(a.yx && i == j)) // (a diagonal pair of yx has one slot: the row side took it)
-                    static_grad_pass<KIND, false>(rw, yj, N, xi, M, d, a.inv_h, [&](int nn, int c, double g) {
+                    static_grad_pass<KIND, false>(rp, yj, Np, xi, Mp, d, a.inv_h, [&](int nn, int c, double g) {
                         double *o = cs + (size_t)nn * d + c;
                         *o = i == i0 ? wc * g : __builtin_fma(wc, g, *o);
                     });
+                if constexpr (NT) { // slabs are stored, not accumulated: their first pair stores the zeros past the path's end
+                    if (a.want_row && j == jfirst) nan_tail_zero_rows(rs, 0, Mp, M, d);
+                    if (a.want_col && !(a.yx && i == j) && i == i0) nan_tail_zero_rows(cs, 0, Np, N, d);
+                }
                 if constexpr (BW) { // (unweighted: K's own derivative)
-                    const double dk = static_bw_pass<KIND>(rw, xi, M, yj, N, d, a.inv_h);
+                    const double dk = static_bw_pass<KIND>(rp, xi, Mp, yj, Np, d, a.inv_h);
                     if (lane == 0) {
                         static_cast<IO *>(a.dK_dinvh)[(size_t)i * a.B + j] = (IO)dk;
                         if (a.yx) static_cast<IO *>(a.dK_dinvh)[(size_t)j * a.B + i] = (IO)dk; // the mirror: same bits
@@ -557,6 +654,47 @@ hipError_t exact_launch_any(int family, int dtype, int kind, int grid, size_t ld
     }
     return hipErrorInvalidValue;
 }
+// the families of launches with SIGSVGD_FLAG_NAN_TAILS: their base's arguments, ids and texts, the
+// NanTailIO kernels (forward-only and gradient, both stencils where the kind has both); the Gram mode of gram_long_kernel has none
+struct PairNanTailFamily : LongFamily<true> {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<NanTailIO<IO>, NAIVE, GRAD, KIND, true>; }
+};
+struct Long2NanTailFamily : Long2Family {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<NanTailIO<IO>, NAIVE, GRAD, KIND>; }
+};
+// the launch of family `family` (the paired or the two-sided one) with the NanTailIO kernel of `kind`, for the two units that
+// build them: the unit names its kinds, K0 .. (a kind of another unit: hipErrorInvalidValue)
+template <typename F, typename IO, int K0, int... KS>
+hipError_t nan_tail_launch_kind(int kind, bool naive, bool grad, const ExactPlan &pl, hipStream_t stream,
+                                const typename F::Args &a)
+{
+    if (kind == K0) return ring_launch_solver<F, IO, K0>(naive, grad, pl, stream, a);
+    if constexpr (sizeof...(KS) > 0)
+        return nan_tail_launch_kind<F, IO, KS...>(kind, naive, grad, pl, stream, a);
+    else
+        return hipErrorInvalidValue;
+}
+template <typename F, int... KS>
+hipError_t nan_tail_launch_family(int dtype, int kind, bool naive, bool grad, const ExactPlan &pl, hipStream_t stream,
+                                  const void *args)
+{
+    const typename F::Args &a = *static_cast<const typename F::Args *>(args);
+    return dtype == SIGSVGD_F64 ? nan_tail_launch_kind<F, double, KS...>(kind, naive, grad, pl, stream, a)
+                                : nan_tail_launch_kind<F, float, KS...>(kind, naive, grad, pl, stream, a);
+}
+template <int... KS>
+hipError_t nan_tail_launch_any(int family, int dtype, int kind, bool naive, bool grad, int grid, size_t lds,
+                               hipStream_t stream, const void *args)
+{
+    const ExactPlan pl{grid, lds};
+    switch (family) {
+    case LongFamily<true>::id: return nan_tail_launch_family<PairNanTailFamily, KS...>(dtype, kind, naive, grad, pl, stream, args);
+    case Long2Family::id: return nan_tail_launch_family<Long2NanTailFamily, KS...>(dtype, kind, naive, grad, pl, stream, args);
+    }
+    return hipErrorInvalidValue;
+}
 struct PartFamily { // (always with the gradient)
     using Args = PartArgs;
     static constexpr bool has_kind = true, has_fwd_only = false, bandwidth = false;
@@ -581,5 +719,15 @@ hipError_t long_matern_launch(int family, int dtype, int kind, bool grad, int gr
 hipError_t long_exact_launch(int family, int dtype, int kind, int grid, size_t lds, hipStream_t stream, const void *args);
 hipError_t long_exact_matern_launch(int family, int dtype, int kind, int grid, size_t lds, hipStream_t stream,
                                     const void *args);
+// gram_long_nantail.hip: the launch of the paired or the two-sided family's NanTailIO instantiation for
+// `kind` (the Matern kinds from gram_long_nantail_matern.hip), and the length pass that goes before it: lens[0 .. nX) = the
+// lengths of X's paths, lens[nX .. nX + nY) those of Y's (Y == NULL: none), each the index of the path's first point whose
+// channel 0 is NaN (T where there is none; at least 1).  gram_long.hip calls both.
+hipError_t long_nan_tail_launch(int family, int dtype, int kind, bool naive, bool grad, int grid, size_t lds,
+                                hipStream_t stream, const void *args);
+hipError_t long_nan_tail_matern_launch(int family, int dtype, int kind, bool naive, bool grad, int grid, size_t lds,
+                                       hipStream_t stream, const void *args);
+hipError_t long_nan_tail_lengths(int dtype, const void *X, int nX, int TX, const void *Y, int nY, int TY, int d, int *lens,
+                                 hipStream_t stream);
 
 } // namespace sigsvgd

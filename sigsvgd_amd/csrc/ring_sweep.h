@@ -17,18 +17,39 @@ namespace sigsvgd {
 // The exact adjoint is a compile-time variant of the kernels on this sweep, named through their I/O
 // type: ExactIO<float> / ExactIO<double> in the place of float / double.  A flag of its own among the template parameters would
 // rename every instantiation the kernels already have; this way those keep their names and, statement for statement, their code.
+// NaN-marked tails are named the same way: NanTailIO<float> / NanTailIO<double>.  Their kernels read each
+// path's length (nan_tail_lengths below) and solve each pair on its own grid; the sweeps are the unflagged ones.
 template <typename T>
 struct ExactIO {};
 template <typename T>
+struct NanTailIO {};
+template <typename T>
 struct RingIO {
     using type = T;
-    static constexpr bool exact = false;
+    static constexpr bool exact = false, nan_tails = false;
 };
 template <typename T>
 struct RingIO<ExactIO<T>> {
     using type = T;
-    static constexpr bool exact = true;
+    static constexpr bool exact = true, nan_tails = false;
 };
+template <typename T>
+struct RingIO<NanTailIO<T>> {
+    using type = T;
+    static constexpr bool exact = false, nan_tails = true;
+};
+
+// The lengths of a launch with SIGSVGD_FLAG_NAN_TAILS: int lenX[nX], then int lenY[nY] (nY = 0 where Y is X: one array serves
+// both slots), padded to 256 B, at the head of the workspace right before the forward scratch.  The kernels find them from the
+// scratch pointer they already have, so no argument struct changes.
+__host__ __device__ inline size_t nan_tail_bytes(int nX, int nY)
+{
+    return (((size_t)nX + (size_t)nY) * sizeof(int) + 255) & ~(size_t)255;
+}
+__device__ __forceinline__ const int *nan_tail_lengths(const float *wsk, int nX, int nY)
+{
+    return reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(wsk) - nan_tail_bytes(nX, nY));
+}
 
 namespace {
 constexpr int kRingMaxCells = 8192;                 // P and Q

@@ -39,6 +39,14 @@ convention (what upstream's autograd through its torch static kernels gives).  X
 route refuses, and IMQ / rational quadratic / Matern with `_naive_solver=True`, raise NotImplementedError.  A float sigma, a tensor
 that does not require grad and `torch.no_grad()` take exactly the launches described above.  Data-dependent bandwidths (the
 median) stay detached, as in the reference.
+
+Paths of different lengths in one batch.  `compute_Gram`, `compute_kernel`, `compute_distance` and
+`compute_mmd` take `lengths_X` / `lengths_Y` ([A] / [B] integers in [1, T], a tensor on either device or a sequence): path i is
+its first `lengths_X[i]` points, whatever the rest of its row holds.  The layer replaces the rest by NaN on the device (no
+sync; the padded entries get a zero gradient) and sends every request, forward or gradient, to the long route's launches with
+SIGSVGD_FLAG_NAN_TAILS (`ops.gram_long_fwd_bwd2`, `ops.pair_fwd*` with `nan_tails=True`), which solve every pair on its own
+grid.  Built-in static kernels with an explicit bandwidth only; see `SigKernel.compute_Gram`.  Without lengths every call
+reaches `ops` exactly as described above.
 """
 from __future__ import annotations
 
@@ -314,6 +322,92 @@ def _exact_kw(exact_grad) -> dict:
     return {"exact_adjoint": True} if exact_grad else {}
 
 
+def _nan_kw(nan_tails) -> dict:
+    """the `nan_tails` keyword of the long route's launches and queries, handed over only where it is
+    set, as `_exact_kw`"""
+    return {"nan_tails": True} if nan_tails else {}
+
+
+# ------------------------------------------------------------------------------------------------
+# batches of paths of different lengths (DESIGN.md section 5.20)
+# ------------------------------------------------------------------------------------------------
+def _lengths_tensor(lengths, P, name):
+    """lengths of the paths of P [A, T, d] -> int64 [A] on P's device, or None for None.  A sequence or a CPU tensor is checked
+    here (integers, 1 <= L <= T: ValueError); a device tensor is checked for its shape and dtype alone and clamped to [1, T] on
+    the device, because reading its values would be a host sync."""
+    if lengths is None:
+        return None
+    A, T = P.shape[0], P.shape[1]
+    if isinstance(lengths, torch.Tensor):
+        if lengths.dim() != 1 or lengths.shape[0] != A:
+            raise ValueError(f"{name} must be [{A}] (one length per path), got {tuple(lengths.shape)}")
+        if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool:
+            raise ValueError(f"{name} must hold integers, got {lengths.dtype}")
+        if lengths.device.type != "cpu":
+            return lengths.detach().to(device=P.device, dtype=torch.int64).clamp(1, T)
+        values = lengths.tolist()
+    else:
+        values = list(lengths)
+        if len(values) != A:
+            raise ValueError(f"{name} must hold {A} lengths (one per path), got {len(values)}")
+        if any(isinstance(v, bool) or int(v) != v for v in values):
+            raise ValueError(f"{name} must hold integers, got {values}")
+    if any(not 1 <= int(v) <= T for v in values):
+        raise ValueError(f"{name}: every length must be in [1, {T}] (the paths have {T} points), got {values}")
+    return torch.tensor([int(v) for v in values], dtype=torch.int64).to(P.device, non_blocking=True)
+
+
+def _same_lengths(lengths_X, lengths_Y) -> bool:
+    """whether two `lengths` arguments are known to be equal without reading a device tensor: one object (None included), or
+    equal host values"""
+    if lengths_X is lengths_Y:
+        return True
+    if lengths_X is None or lengths_Y is None:
+        return False
+    on_host = lambda v: not isinstance(v, torch.Tensor) or v.device.type == "cpu"
+    if on_host(lengths_X) and on_host(lengths_Y):
+        return [int(v) for v in lengths_X] == [int(v) for v in lengths_Y]
+    return isinstance(lengths_X, torch.Tensor) and isinstance(lengths_Y, torch.Tensor) and _same_storage(lengths_X, lengths_Y)
+
+
+def _nan_tailed(P, L):
+    """P with the points from each path's length on replaced by NaN: what SIGSVGD_FLAG_NAN_TAILS reads.  Built on P's device
+    without a sync; autograd sends a gradient back to the kept entries only."""
+    if L is None:
+        return P
+    keep = torch.arange(P.shape[1], device=P.device)[None, :] < L[:, None]
+    return torch.where(keep[:, :, None], P, torch.full((), float("nan"), dtype=P.dtype, device=P.device))
+
+
+def _lengths_static(kernel, X, Y):
+    """-> (static_kind, inv_h) of a call with lengths, and its refusals: an explicit bandwidth only (padding would distort one
+    computed from the data), built-in static kernels only, no learned sigma, no exact gradient, no fp32 sweeps"""
+    sk = kernel.static_kernel
+    if kernel.fp32_sweeps:
+        raise ValueError("lengths run on the long route's fp64 sweeps; fp32_sweeps=True selects a fused fp32-sweep kernel")
+    if kernel.exact_grad:
+        raise NotImplementedError("lengths with exact_grad=True: the exact adjoint's kernels solve every pair on the launch's "
+                                  "grid (SIGSVGD_FLAG_NAN_TAILS with SIGSVGD_FLAG_EXACT_ADJOINT is not built)")
+    if _learned_sigma(sk) is not None:
+        raise NotImplementedError("lengths with a static-kernel sigma that requires grad: the bandwidth launches do not take "
+                                  "SIGSVGD_FLAG_NAN_TAILS")
+    builtin = hasattr(sk, "static_kind") and hasattr(sk, "inv_bandwidth")
+    reference_rbf = type(sk).__name__ == "BatchGaussianKernel" and hasattr(sk, "get_bandwidth")
+    if not (builtin or reference_rbf):
+        if hasattr(sk, "Gram_matrix"):
+            raise NotImplementedError(f"lengths with the user static kernel {type(sk).__name__}: its grid is the caller's torch "
+                                      "code; the built-in static kernels take lengths")
+        return _resolve_static(sk, X, Y)  # (raises NotImplementedError)
+    if hasattr(sk, "get_bandwidth"):
+        try:
+            return (int(sk.static_kind) if builtin else _lib.STATIC_RBF), 1.0 / float(sk.get_bandwidth(_ConstantProbe()))
+        except _ConstantProbe.Touched:
+            raise ValueError("lengths need an explicit bandwidth: one computed from the data (the median heuristic, any "
+                             "bandwidth_fn that reads the distances) would see the padding.  Pass a constant bandwidth_fn "
+                             "(lambda _: h) or a static kernel with a sigma") from None
+    return int(sk.static_kind), float(sk.inv_bandwidth(X, Y))
+
+
 def _long_route(X, Y, static_kind, dyadic_order, want_grad, naive, sym, y_is_x, fp32_sweeps=False) -> bool:
     """True where the fused Gram kernels refuse the launch (`ops.gram_takes`: their per-pair state outgrows the LDS); the
     built-in static kernels then run on the long route (`ops.gram_long_fwd*`, csrc/gram_long.hip).  Every launch the
@@ -368,10 +462,18 @@ def _solve_gram(X, Y, cfg, grad_out, want_x, want_y, fused_yx):
     fused launches and their queries; the long route has no such kernels and does not see it.  An eighth element of cfg,
     exact_grad (`SigKernel(..., exact_grad=True)`): every gradient launch is the long route's with
     `exact_adjoint=True`, whatever the shape (the fused kernels have the GG convention only); forward-only launches are
-    untouched."""
+    untouched.  A ninth, nan_tails (a call with lengths): X and Y are NaN-padded and every request,
+    forward or gradient, is one `ops.gram_long_fwd_bwd2` launch with `nan_tails=True`, whatever the shape."""
     static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps, *rest = cfg
     exact = bool(rest and rest[0])
     fkw = _fp32_kw(fp32_sweeps)
+    if len(rest) > 1 and rest[1]:  # nan_tails (a call with lengths, DESIGN.md section 5.20): the flagged two-sided launch alone
+        yx = y_is_x and not want_y
+        if not ops.gram_long2_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], dyadic_order, static_kind,
+                                    want_x, want_y, yx, nan_tails=True):
+            raise _refused("compute_Gram", X, Y, dyadic_order, "a batch with lengths")
+        return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_out, naive, sym, yx, want_x, want_y,
+                                      nan_tails=True)
     if not (want_x or want_y):
         if not _long_route(X, Y, static_kind, dyadic_order, False, naive, False, y_is_x, fp32_sweeps):
             return ops.gram_fwd(X, Y, inv_h, dyadic_order, static_kind, naive, y_is_x=y_is_x, **fkw), None, None
@@ -429,8 +531,8 @@ class _SigKernelGram(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, sym, y_is_x, speculate, grad_Y, fp32_sweeps=False,
-                exact_grad=False):
-        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps, exact_grad)
+                exact_grad=False, nan_tails=False):
+        ctx.cfg = (static_kind, inv_h, dyadic_order, naive, sym, y_is_x, fp32_sweeps, exact_grad, nan_tails)
         ctx.g_ones = ctx.gy_ones = None
         ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
         ctx.y_dtype = Y.dtype
@@ -452,7 +554,7 @@ class _SigKernelGram(torch.autograd.Function):
             _, gX, gY = _solve_gram(X, Y, ctx.cfg, grad_output, want_x, want_y, False)
         if gY is not None:
             gY = gY.to(ctx.y_dtype)
-        return gX, gY, None, None, None, None, None, None, None, None, None, None
+        return gX, gY, None, None, None, None, None, None, None, None, None, None, None
 
 
 class _SigKernelPair(torch.autograd.Function):
@@ -464,15 +566,15 @@ class _SigKernelPair(torch.autograd.Function):
     there is one launch per call.  The launch computes in X's dtype; each gradient returns in its own input's dtype."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, exact_grad=False):
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, exact_grad=False, nan_tails=False):
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ctx.dtypes = (X.dtype, Y.dtype)
         if want_x or want_y:
             K, gX, gY = ops.pair_fwd_bwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
-                                         want_y, **_exact_kw(exact_grad))
+                                         want_y, **_exact_kw(exact_grad), **_nan_kw(nan_tails))
             ctx.save_for_backward(gX, gY)
         else:
-            K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive)
+            K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive, **_nan_kw(nan_tails))
         return K
 
     @staticmethod
@@ -483,7 +585,7 @@ class _SigKernelPair(torch.autograd.Function):
             gX = (gX1 * grad_output.to(gX1.dtype)[:, None, None]).to(ctx.dtypes[0])
         if gY1 is not None:
             gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
-        return gX, gY, None, None, None, None, None
+        return gX, gY, None, None, None, None, None, None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -612,15 +714,22 @@ class SigKernel:
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
-    def compute_Gram(self, X: torch.Tensor, Y: torch.Tensor, sym: bool = False, grad_Y: bool = False) -> torch.Tensor:
+    def compute_Gram(self, X: torch.Tensor, Y: torch.Tensor, sym: bool = False, grad_Y: bool = False, lengths_X=None,
+                     lengths_Y=None) -> torch.Tensor:
         """K[i,j] = k_sig(X_i, Y_j), X [A,Tx,d], Y [B,Ty,d] on a HIP device; same dtype/device as X.  Paths of different
         lengths (upstream sigkernel takes them) are padded with their last point, which is exact (ops.pad_to_length).
         Gradients flow to X (the first slot).  grad_Y=True: a Y that requires grad receives its second-slot gradient too (one
         tensor in both slots then gets the sum of both, which is what sym=True gives; the two together raise ValueError).
-        The default leaves Y without a gradient, as callers that pass one leaf tensor in both slots rely on."""
+        The default leaves Y without a gradient, as callers that pass one leaf tensor in both slots rely on.
+
+        lengths_X [A] / lengths_Y [B] (integers in [1, T], a tensor on either device or a sequence; None: every path is
+        whole): path i of X is its first lengths_X[i] points, whatever the rest of its row holds, and every pair is solved on
+        its own grid (`_lengths_gram`).  The padded entries of X and Y get a zero gradient."""
         if grad_Y and sym:
             raise ValueError("compute_Gram: grad_Y=True differentiates the second slot itself; sym=True folds it into the "
                              "first.  Use one of them")
+        if lengths_X is not None or lengths_Y is not None:
+            return self._lengths_gram(X, Y, bool(sym), bool(grad_Y), lengths_X, lengths_Y)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
         if static_kind is None:  # user static kernel: its grid, the PDE on the device, autograd through both
             G = self.static_kernel.Gram_matrix(X, Y if sym or grad_Y else Y.detach())
@@ -651,13 +760,48 @@ class SigKernel:
     #    reference tree never calls these].  compute_kernel / compute_distance differentiate both arguments (each its
     #    own slot); compute_mmd goes through compute_Gram, so its cross term's gradient flows to the FIRST argument only
     #    unless grad_Y=True, with `sym=True` giving the symmetrised weighting for Gram(X, X).
-    def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+    # -- batches of paths of different lengths -------------------------------------------------------
+    def _lengths_operands(self, X, Y, sym, lengths_X, lengths_Y):
+        """-> (static_kind, inv_h, Xn, Yn, y_is_x): the static kernel of a call with lengths (`_lengths_static`) and the NaN-padded
+        operands, built once where one tensor with one set of lengths is in both slots"""
+        if X.dim() != 3 or Y.dim() != 3:
+            raise ValueError(f"paths must be [batch, length, dim]; got {tuple(X.shape)} and {tuple(Y.shape)}")
+        static_kind, inv_h = _lengths_static(self, X, Y)
+        LX, LY = _lengths_tensor(lengths_X, X, "lengths_X"), _lengths_tensor(lengths_Y, Y, "lengths_Y")
+        same = _same_lengths(lengths_X, lengths_Y)
+        if sym and not same:
+            raise ValueError("sym=True weights K and its transpose alike, which needs one batch in both slots: lengths_X and "
+                             "lengths_Y must be the same")
+        y_is_x = same and _same_storage(X, Y)
+        Xn = _nan_tailed(X, LX)
+        return static_kind, inv_h, Xn, (Xn if y_is_x else _nan_tailed(Y, LY)), y_is_x
+
+    def _lengths_gram(self, X, Y, sym, grad_Y, lengths_X, lengths_Y):
+        """compute_Gram with lengths: the NaN-padded operands through `_SigKernelGram` with nan_tails set, so that every launch,
+        forward or gradient, is `ops.gram_long_fwd_bwd2(..., nan_tails=True)`"""
+        static_kind, inv_h, Xn, Yn, y_is_x = self._lengths_operands(X, Y, sym, lengths_X, lengths_Y)
+        return _SigKernelGram.apply(Xn, Yn, static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, y_is_x,
+                                    self.speculate_ones, grad_Y, False, False, True)
+
+    def _lengths_kernel(self, X, Y, lengths_X, lengths_Y):
+        """compute_kernel with lengths: the NaN-padded operands on the paired route with nan_tails set, whatever the shape"""
+        static_kind, inv_h, Xn, Yn, _ = self._lengths_operands(X, Y, False, lengths_X, lengths_Y)
+        want_grad = torch.is_grad_enabled() and (Xn.requires_grad or Yn.requires_grad)
+        if not ops.pair_takes(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind, want_grad,
+                              nan_tails=True):
+            raise _refused("compute_kernel", X, Y, self.dyadic_order, "a batch with lengths")
+        return _SigKernelPair.apply(Xn, Yn, static_kind, inv_h, self.dyadic_order, self._naive_solver, False, True)
+
+    def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor, lengths_X=None, lengths_Y=None) -> torch.Tensor:
         """Paired kernel k_sig(X_i, Y_i) -> [batch], one solve per pair, differentiable in X and in Y (each its own slot:
         compute_kernel(X, X) differentiates to the sum of both).  Built-in static kernels run on the paired route
         (`ops.pair_fwd*`, csrc/gram_long.hip) wherever `_pair_route` says so, else on the diagonal of compute_Gram (first
         slot only) as before: where `ops.pair_takes` refuses the shape, and for forward-only calls of few pairs; a user static kernel with `batch_kernel` solves the batch pairs through
-        torch autograd; one without it takes the diagonal of its Gram launch."""
+        torch autograd; one without it takes the diagonal of its Gram launch.  lengths_X / lengths_Y: as `compute_Gram`'s; the
+        pairs then run on the paired route whatever the shape."""
         assert X.shape[0] == Y.shape[0], "compute_kernel pairs X_i with Y_i"
+        if lengths_X is not None or lengths_Y is not None:
+            return self._lengths_kernel(X, Y, lengths_X, lengths_Y)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
         if static_kind is None and hasattr(self.static_kernel, "batch_kernel"):
             G = self.static_kernel.batch_kernel(X, Y)
@@ -681,17 +825,27 @@ class SigKernel:
                 return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, self._naive_solver)
         return self.compute_Gram(X, Y).diagonal()
 
-    def compute_distance(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
-        """mean_i k(X_i, X_i) + mean_i k(Y_i, Y_i) - 2 mean_i k(X_i, Y_i)."""
-        return (self.compute_kernel(X, X).mean() + self.compute_kernel(Y, Y).mean()
-                - 2.0 * self.compute_kernel(X, Y).mean())
+    def compute_distance(self, X: torch.Tensor, Y: torch.Tensor, lengths_X=None, lengths_Y=None) -> torch.Tensor:
+        """mean_i k(X_i, X_i) + mean_i k(Y_i, Y_i) - 2 mean_i k(X_i, Y_i).  lengths_X / lengths_Y: as `compute_Gram`'s."""
+        if lengths_X is None and lengths_Y is None:
+            return (self.compute_kernel(X, X).mean() + self.compute_kernel(Y, Y).mean()
+                    - 2.0 * self.compute_kernel(X, Y).mean())
+        return (self.compute_kernel(X, X, lengths_X, lengths_X).mean() + self.compute_kernel(Y, Y, lengths_Y, lengths_Y).mean()
+                - 2.0 * self.compute_kernel(X, Y, lengths_X, lengths_Y).mean())
 
-    def compute_mmd(self, X: torch.Tensor, Y: torch.Tensor, grad_Y: bool = False) -> torch.Tensor:
+    def compute_mmd(self, X: torch.Tensor, Y: torch.Tensor, grad_Y: bool = False, lengths_X=None,
+                    lengths_Y=None) -> torch.Tensor:
         """Biased squared MMD: mean K_XX + mean K_YY - 2 mean K_XY.  grad_Y=True differentiates Y through the cross term
-        too (`compute_Gram(X, Y, grad_Y=True)`); the default gives Y the gradient of mean K_YY alone."""
-        K_XX = self.compute_Gram(X, X, sym=True)
-        K_YY = self.compute_Gram(Y, Y, sym=True)
-        K_XY = self.compute_Gram(X, Y, sym=False, grad_Y=grad_Y)
+        too (`compute_Gram(X, Y, grad_Y=True)`); the default gives Y the gradient of mean K_YY alone.  lengths_X /
+        lengths_Y: as `compute_Gram`'s."""
+        if lengths_X is None and lengths_Y is None:
+            K_XX = self.compute_Gram(X, X, sym=True)
+            K_YY = self.compute_Gram(Y, Y, sym=True)
+            K_XY = self.compute_Gram(X, Y, sym=False, grad_Y=grad_Y)
+        else:
+            K_XX = self.compute_Gram(X, X, sym=True, lengths_X=lengths_X, lengths_Y=lengths_X)
+            K_YY = self.compute_Gram(Y, Y, sym=True, lengths_X=lengths_Y, lengths_Y=lengths_Y)
+            K_XY = self.compute_Gram(X, Y, sym=False, grad_Y=grad_Y, lengths_X=lengths_X, lengths_Y=lengths_Y)
         return K_XX.mean() + K_YY.mean() - 2.0 * K_XY.mean()
 
     def gram_and_grad(self, X: torch.Tensor, Y: Optional[torch.Tensor] = None, grad_out=None, sym: bool = False):
