@@ -184,6 +184,24 @@ extern "C" {
                                       /* and their queries, and from every entry point when SIGSVGD_FLAG_EXACT_ADJOINT is set too.  Every       */
                                       /* other entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol,     */
                                       /* no changed signature; an earlier library answers SIGSVGD_E_BADARG                                     */
+#define SIGSVGD_FLAG_LOG_K 1024u      /* log-domain solve on the long route.  K_out holds the natural logarithm      */
+                                      /* ln K(X_i, Y_j) (same layout, same mirror store with SIGSVGD_FLAG_Y_IS_X) and every gradient output   */
+                                      /* sum_ij w_ij grad ln K_ij = sum_ij w_ij grad K_ij / K_ij in the GG convention; grad_out,              */
+                                      /* SIGSVGD_FLAG_SYM, SIGSVGD_FLAG_Y_IS_X and NULL outputs mean what they mean without the bit.  The     */
+                                      /* sweeps carry a running power-of-two scale (mantissas are those of the unscaled solve), the stored    */
+                                      /* forward solution and the fp32 S partials are scaled too, so nothing overflows while ln K itself is   */
+                                      /* representable: the signature kernel of long rough paths passes fp32 from about T = 300 and fp64      */
+                                      /* from about T = 1600.  A pair whose discrete K is <= 0 gets NaN in K_out and in its gradient          */
+                                      /* contribution.  All six static kinds, both dtypes, any dyadic order, default stencil.  Taken by       */
+                                      /* sigsvgd_gram_long_fwd_bwd2 (every output combination, forward only included) with                    */
+                                      /* sigsvgd_gram_long2_workspace_bytes, and by sigsvgd_pair_fwd, sigsvgd_pair_fwd_bwd,                   */
+                                      /* sigsvgd_pair_workspace_bytes and sigsvgd_pair_schedule; paired launches run one wavefront per pair   */
+                                      /* with it (sigsvgd_pair_schedule says so).  The workspace grows by one int per band and block of 64    */
+                                      /* sweep steps and wave (forward-only launches need that much too), the LDS by one int per block.       */
+                                      /* SIGSVGD_E_UNSUPPORTED before any device work from those entry points when                            */
+                                      /* SIGSVGD_FLAG_NAIVE_SOLVER, SIGSVGD_FLAG_EXACT_ADJOINT or SIGSVGD_FLAG_NAN_TAILS is set too.  Every   */
+                                      /* other entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol,   */
+                                      /* no changed signature; an earlier library answers SIGSVGD_E_BADARG                                    */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */

@@ -144,6 +144,22 @@ static int check_nan_tails(const char *who, unsigned flags, bool takes)
     return SIGSVGD_OK;
 }
 
+// SIGSVGD_FLAG_LOG_K on the entry points that take it (those that take SIGSVGD_FLAG_NAN_TAILS; the
+// others keep their answer for an unknown bit): refused before any device work together with a flag whose kernels have no
+// log-domain form
+static int check_log_k(const char *who, unsigned flags)
+{
+    if (!(flags & SIGSVGD_FLAG_LOG_K)) return SIGSVGD_OK;
+    const char *other = (flags & SIGSVGD_FLAG_NAIVE_SOLVER)    ? "SIGSVGD_FLAG_NAIVE_SOLVER"
+                        : (flags & SIGSVGD_FLAG_EXACT_ADJOINT) ? "SIGSVGD_FLAG_EXACT_ADJOINT"
+                        : (flags & SIGSVGD_FLAG_NAN_TAILS)     ? "SIGSVGD_FLAG_NAN_TAILS"
+                                                               : nullptr;
+    if (!other) return SIGSVGD_OK;
+    set_error("%s: SIGSVGD_FLAG_LOG_K together with %s is not built (the log-domain kernels are the default stencil's GG solve "
+              "on the launch's grid)", who, other);
+    return SIGSVGD_E_UNSUPPORTED;
+}
+
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
@@ -178,10 +194,12 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags,
 // know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_SYM
 // (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, and for a launch with the reverse
 // sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; `nan_tails`: the entry point takes SIGSVGD_FLAG_NAN_TAILS
-// (the others answer UNSUPPORTED before anything else: check_nan_tails); every other bit is refused.
+// (the others answer UNSUPPORTED before anything else: check_nan_tails) and with it SIGSVGD_FLAG_LOG_K (check_log_k: the others
+// refuse that bit as an unknown one); every other bit is refused.
 static int check_long(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
 {
     if (check_nan_tails("gram_long", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
+    if (nan_tails && check_log_k("gram_long", p.flags)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
@@ -190,7 +208,7 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false, bool
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
     const unsigned known =
         SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
-        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS : 0u);
+        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u);
     if (p.flags & ~known)
         return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
@@ -240,9 +258,10 @@ static int check_long_partial(const LongProblem &p, bool launch, int tile_offset
 static int check_pair(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
 {
     if (check_nan_tails("pair", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
+    if (nan_tails && check_log_k("pair", p.flags)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
     const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
-                           (nan_tails ? SIGSVGD_FLAG_NAN_TAILS : 0u);
+                           (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u);
     if (p.flags & ~known)
         return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~known);
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)

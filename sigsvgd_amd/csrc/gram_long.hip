@@ -65,6 +65,7 @@ struct LongPlan : RingPlan {
     long long items;
     size_t wsk_bytes, partial_bytes, col_bytes = 0; // the forward scratch, the row-side slabs, the column-side slabs
     size_t len_bytes = 0; // SIGSVGD_FLAG_NAN_TAILS: the paths' lengths, ahead of the forward scratch
+    bool log_k = false;   // SIGSVGD_FLAG_LOG_K: ring_log_plan's block exponents in LDS and scratch
     size_t total() const { return ring_ws_total(len_bytes + wsk_bytes + partial_bytes + col_bytes); }
 };
 
@@ -83,7 +84,8 @@ void long_set_grid(LongPlan &pl)
 
 int long_make_plan(int A, int B, int M, int N, int d, int n, int want_grad, LongPlan &pl, const char *who = "gram_long")
 {
-    const int rc = ring_make_plan(M, N, n, want_grad, d, who, pl); // (+ the band's nrow + 1 points of X_i in LDS)
+    int rc = ring_make_plan(M, N, n, want_grad, d, who, pl); // (+ the band's nrow + 1 points of X_i in LDS)
+    if (!rc && pl.log_k) rc = ring_log_plan(who, pl);
     if (rc) return rc;
     // work items (i, chunk of JC columns): enough to give every resident wave one, few enough gradient slabs
     int JC = 32;
@@ -120,7 +122,8 @@ int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, boo
                     bool want_bw = false)
 {
     const int want_grad = want_row || want_col;
-    const int rc = ring_make_plan(M, N, n, want_grad || want_bw, d, "gram_long", pl);
+    int rc = ring_make_plan(M, N, n, want_grad || want_bw, d, "gram_long", pl);
+    if (!rc && pl.log_k) rc = ring_log_plan("gram_long", pl);
     if (rc) return rc;
     auto tiles = [](int rows, int chunk) { return (rows + chunk - 1) / chunk; };
     int IC = 32, JC = 32;
@@ -306,9 +309,13 @@ bool long_exact(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_EXACT_ADJ
 // SIGSVGD_FLAG_NAN_TAILS: the bytes of the launch's length arrays (nY: Y's paths, 0 where Y is X), and
 // the length pass into them, ahead of the launch on its stream (a: the launch's arguments, whose scratch follows the arrays)
 bool long_nan_tails(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAN_TAILS) != 0; }
+// SIGSVGD_FLAG_LOG_K (the entry points refuse it with NAIVE_SOLVER, EXACT_ADJOINT and NAN_TAILS)
+bool long_log_k(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_LOG_K) != 0; }
+// what the plan of a launch takes from its flags, before it is made
 void long_set_lengths(const LongProblem &p, int nY, LongPlan &pl)
 {
     pl.len_bytes = long_nan_tails(p) ? nan_tail_bytes(p.A, nY) : 0;
+    pl.log_k = long_log_k(p);
 }
 int long_find_lengths(const LongProblem &p, int nY, const LongPlan &pl, const LongArgs &a)
 {
@@ -359,11 +366,19 @@ int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t strea
 }
 // the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations; `exact`
 // (long_exact below: a gradient launch with the default stencil): gram_long_exact.hip's, for every kind; `nan_tails`
-// (SIGSVGD_FLAG_NAN_TAILS, the paired and the two-sided family): gram_long_nantail.hip's, for every kind and both stencils
+// (SIGSVGD_FLAG_NAN_TAILS, the paired and the two-sided family): gram_long_nantail.hip's, for every kind and both stencils;
+// `log_k` (SIGSVGD_FLAG_LOG_K, the same two families): gram_long_logk.hip's, for every kind
 template <typename F, typename Plan>
 int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a,
-                  bool exact = false, bool nan_tails = false)
+                  bool exact = false, bool nan_tails = false, bool log_k = false)
 {
+    if (log_k) { // (the entry points refuse it with the other two and with the first-order stencil)
+        hipError_t e = long_log_k_launch(F::id, dtype, kind, grad, pl.grid, pl.lds, stream, &a);
+        if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+        return SIGSVGD_OK;
+    }
     if (nan_tails) { // (the entry points refuse it with the exact adjoint and on the families that have no such kernels)
         hipError_t e = long_nan_tail_launch(F::id, dtype, kind, naive, grad, pl.grid, pl.lds, stream, &a);
         if (e != hipSuccess) return hip_fail(e, F::attr_failed);
@@ -481,13 +496,14 @@ bool pair_use_bands(int A, const LongPlan &pl, const PairBandsPlan &bp)
 int pair_schedule(const LongProblem &p, int want_grad, int *waves_per_pair, int *grid, size_t *lds_bytes)
 {
     LongPlan pl;
+    pl.log_k = long_log_k(p);
     const int rc = pair_make_plan(p.A, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (rc) return rc;
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
     // (the exact adjoint has the one-wavefront kernel only: pair_bands.hip has its own sweep)
-    // (and so have launches with NaN-marked tails, whose pairs differ in their bands)
-    const bool bands = !(want_grad && long_exact(p)) && !long_nan_tails(p) && pair_use_bands(p.A, pl, bp);
+    // (and so have launches with NaN-marked tails, whose pairs differ in their bands, and log-domain launches)
+    const bool bands = !(want_grad && long_exact(p)) && !long_nan_tails(p) && !long_log_k(p) && pair_use_bands(p.A, pl, bp);
     *waves_per_pair = bands ? bp.NB : 1;
     *grid = bands ? bp.grid : pl.grid;
     *lds_bytes = bands ? bp.lds : pl.lds;
@@ -507,12 +523,13 @@ int pair_launch(const LongProblem &p)
     PairBandsPlan bp;
     pair_bands_plan(p.A, p.TX, p.TY, p.d, p.n, pair_geom(pl), bp);
     const bool exact = want_grad && long_exact(p); // (the one-wavefront schedule, as the bandwidth launch)
-    if (!exact && !long_nan_tails(p) && pair_use_bands(p.A, pl, bp))
+    if (!exact && !long_nan_tails(p) && !long_log_k(p) && pair_use_bands(p.A, pl, bp))
         return pair_bands_launch(p, pair_geom(pl), bp, a.wsk); // the same scratch slots, fewer used
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
     rc = long_find_lengths(p, p.A, pl, a);
     if (rc) return rc;
-    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact, long_nan_tails(p));
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact, long_nan_tails(p),
+                                           long_log_k(p));
 }
 
 // The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
@@ -553,7 +570,7 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
         rc = long_find_lengths(p, yx ? 0 : p.B, pl, a);
         if (!rc)
             rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_exact(p),
-                                            long_nan_tails(p));
+                                            long_nan_tails(p), long_log_k(p));
     }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,

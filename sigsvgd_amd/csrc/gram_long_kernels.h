@@ -1,8 +1,9 @@
 // The long-path kernels (gram_long_kernel, gram_long2_kernel, gram_long_part_kernel), their argument structs and their
 // families for ring_launch (ring_sweep.h).  Included by gram_long.hip (plans, reduce kernels, launchers; every kind but Matern),
 // by gram_long_matern.hip (the Matern kinds' instantiations), by gram_long_exact.hip and gram_long_exact_matern.hip (the
-// exact adjoint's instantiations) and by gram_long_nantail.hip and gram_long_nantail_matern.hip (the
-// instantiations for batches of paths of different lengths).
+// exact adjoint's instantiations), by gram_long_nantail.hip and gram_long_nantail_matern.hip (the
+// instantiations for batches of paths of different lengths) and by gram_long_logk.hip and
+// gram_long_logk_matern.hip (the log-domain instantiations).
 //
 // Signature-kernel Gram matrix and gradient for the built-in static kernels on long paths.
 //
@@ -145,8 +146,10 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
     using IO = typename RingIO<IOX>::type;
     constexpr bool EXACT = RingIO<IOX>::exact;
     constexpr bool NT = RingIO<IOX>::nan_tails; // (the paired mode only, no bandwidth pass)
+    constexpr bool LOGK = RingIO<IOX>::log_k;   // (the same; K_out gets ln K, the gradients those of ln K)
     static_assert(!BW || (PAIRED && GRAD), "the bandwidth pass needs the paired mode's reverse sweep");
     static_assert(!NT || (PAIRED && !BW), "NaN-marked tails: the paired mode without the bandwidth pass");
+    static_assert(!LOGK || (PAIRED && !BW), "the log-domain solve: the paired mode without the bandwidth pass");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -159,6 +162,8 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
         lenX = nan_tail_lengths(a.wsk, a.A, a.A);
         lenY = lenX + a.A;
     }
+    [[maybe_unused]] RingLog lg;
+    if constexpr (LOGK) lg = ring_log<GRAD>(a, rw, xs + (nrow + 1) * d); // (its block exponents: behind the band's points)
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
         const int i = PAIRED ? (int)item : (int)(item / a.nchunks);
@@ -219,7 +224,8 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
                 __syncthreads();
             };
 
-            const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rp, fill, stage_x);
+            double Kval = ring_forward<NAIVE, GRAD, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
+            if constexpr (LOGK) Kval = ring_log_finish(rp, Kval, lg); // ln K
             if (((rp.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
@@ -227,7 +233,7 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
             __syncthreads();
-            ring_reverse<NAIVE, EXACT>(rp, fill, stage_x);
+            ring_reverse<NAIVE, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
             __syncthreads();
 
@@ -274,8 +280,10 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
     using IO = typename RingIO<IOX>::type;
     constexpr bool EXACT = RingIO<IOX>::exact;
     constexpr bool NT = RingIO<IOX>::nan_tails; // (no bandwidth pass)
+    constexpr bool LOGK = RingIO<IOX>::log_k;   // (the same; K_out gets ln K, the gradients those of ln K)
     static_assert(!BW || GRAD, "the bandwidth pass needs the reverse sweep");
     static_assert(!NT || !BW, "NaN-marked tails: no bandwidth pass");
+    static_assert(!LOGK || !BW, "the log-domain solve: no bandwidth pass");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -288,6 +296,8 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
         lenX = nan_tail_lengths(a.wsk, a.A, a.yx ? 0 : a.B);
         lenY = a.yx ? lenX : lenX + a.A;
     }
+    [[maybe_unused]] RingLog lg;
+    if constexpr (LOGK) lg = ring_log<GRAD>(a, rw, xs + (nrow + 1) * d); // (its block exponents: behind the band's points)
 
     for (long long item = blockIdx.x; item < a.items; item += gridDim.x) {
         // the item's tile (ti, tj): rows i0 .. i1 - 1 x columns j0 .. j1 - 1, walked row by row
@@ -364,7 +374,8 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                     __syncthreads();
                 };
 
-                const double Kval = ring_forward<NAIVE, GRAD, EXACT>(rp, fill, stage_x);
+                double Kval = ring_forward<NAIVE, GRAD, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
+                if constexpr (LOGK) Kval = ring_log_finish(rp, Kval, lg); // ln K
                 if (((rp.P - 1) & (kWave - 1)) == lane) {
                     static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)Kval;
                     if (a.yx) static_cast<IO *>(a.K_out)[(size_t)j * a.B + i] = (IO)Kval; // the mirror: same bits
@@ -375,7 +386,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the forward solution is in L2 before it is read back
                 __syncthreads();
-                ring_reverse<NAIVE, EXACT>(rp, fill, stage_x);
+                ring_reverse<NAIVE, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // S is in L2 before it is read back
                 __syncthreads();
 
@@ -695,6 +706,46 @@ hipError_t nan_tail_launch_any(int family, int dtype, int kind, bool naive, bool
     }
     return hipErrorInvalidValue;
 }
+// the families of launches with SIGSVGD_FLAG_LOG_K: their base's arguments, ids and texts, the LogIO
+// kernels (forward-only and gradient, default stencil); the Gram mode of gram_long_kernel has none
+struct PairLogFamily : LongFamily<true> {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<LogIO<IO>, false, GRAD, KIND, true>; }
+};
+struct Long2LogFamily : Long2Family {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<LogIO<IO>, false, GRAD, KIND>; }
+};
+// the launch of family `family` (the paired or the two-sided one) with the LogIO kernel of `kind`, for the two units that build
+// them: the unit names its kinds, K0 .. (a kind of another unit: hipErrorInvalidValue)
+template <typename F, typename IO, int K0, int... KS>
+hipError_t log_k_launch_kind(int kind, bool grad, const ExactPlan &pl, hipStream_t stream, const typename F::Args &a)
+{
+    if (kind == K0)
+        return grad ? ring_launch_one<F, IO, false, true, K0>(pl, stream, a) : ring_launch_one<F, IO, false, false, K0>(pl, stream, a);
+    if constexpr (sizeof...(KS) > 0)
+        return log_k_launch_kind<F, IO, KS...>(kind, grad, pl, stream, a);
+    else
+        return hipErrorInvalidValue;
+}
+template <typename F, int... KS>
+hipError_t log_k_launch_family(int dtype, int kind, bool grad, const ExactPlan &pl, hipStream_t stream, const void *args)
+{
+    const typename F::Args &a = *static_cast<const typename F::Args *>(args);
+    return dtype == SIGSVGD_F64 ? log_k_launch_kind<F, double, KS...>(kind, grad, pl, stream, a)
+                                : log_k_launch_kind<F, float, KS...>(kind, grad, pl, stream, a);
+}
+template <int... KS>
+hipError_t log_k_launch_any(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                            const void *args)
+{
+    const ExactPlan pl{grid, lds};
+    switch (family) {
+    case LongFamily<true>::id: return log_k_launch_family<PairLogFamily, KS...>(dtype, kind, grad, pl, stream, args);
+    case Long2Family::id: return log_k_launch_family<Long2LogFamily, KS...>(dtype, kind, grad, pl, stream, args);
+    }
+    return hipErrorInvalidValue;
+}
 struct PartFamily { // (always with the gradient)
     using Args = PartArgs;
     static constexpr bool has_kind = true, has_fwd_only = false, bandwidth = false;
@@ -729,5 +780,11 @@ hipError_t long_nan_tail_matern_launch(int family, int dtype, int kind, bool nai
                                        hipStream_t stream, const void *args);
 hipError_t long_nan_tail_lengths(int dtype, const void *X, int nX, int TX, const void *Y, int nY, int TY, int d, int *lens,
                                  hipStream_t stream);
+// gram_long_logk.hip: the launch of the paired or the two-sided family's LogIO instantiation for `kind`
+// (the Matern kinds from gram_long_logk_matern.hip), default stencil.  gram_long.hip's family_launch calls it.
+hipError_t long_log_k_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                             const void *args);
+hipError_t long_log_k_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                                    const void *args);
 
 } // namespace sigsvgd

@@ -19,24 +19,33 @@ namespace sigsvgd {
 // rename every instantiation the kernels already have; this way those keep their names and, statement for statement, their code.
 // NaN-marked tails are named the same way: NanTailIO<float> / NanTailIO<double>.  Their kernels read each
 // path's length (nan_tail_lengths below) and solve each pair on its own grid; the sweeps are the unflagged ones.
+// The log-domain solve again: LogIO<float> / LogIO<double>.  Its sweeps carry a running power-of-two
+// scale (ring_forward / ring_reverse with LOG), the kernels store ln K and file the S partials already divided by K.
 template <typename T>
 struct ExactIO {};
 template <typename T>
 struct NanTailIO {};
 template <typename T>
+struct LogIO {};
+template <typename T>
 struct RingIO {
     using type = T;
-    static constexpr bool exact = false, nan_tails = false;
+    static constexpr bool exact = false, nan_tails = false, log_k = false;
 };
 template <typename T>
 struct RingIO<ExactIO<T>> {
     using type = T;
-    static constexpr bool exact = true, nan_tails = false;
+    static constexpr bool exact = true, nan_tails = false, log_k = false;
 };
 template <typename T>
 struct RingIO<NanTailIO<T>> {
     using type = T;
-    static constexpr bool exact = false, nan_tails = true;
+    static constexpr bool exact = false, nan_tails = true, log_k = false;
+};
+template <typename T>
+struct RingIO<LogIO<T>> {
+    using type = T;
+    static constexpr bool exact = false, nan_tails = false, log_k = true;
 };
 
 // The lengths of a launch with SIGSVGD_FLAG_NAN_TAILS: int lenX[nX], then int lenY[nY] (nY = 0 where Y is X: one array serves
@@ -90,6 +99,25 @@ int ring_make_plan(int M, int N, int n, int want_grad, int row_doubles, const ch
     pl.lds = ((size_t)pl.nrow * pl.W + pl.Q + 2 + kWave + (size_t)(pl.nrow + 1) * row_doubles) * sizeof(double);
     if (pl.lds > kRingMaxLds) {
         set_error("%s: per-wave state needs %zu B of LDS (> 160 KiB)", who, pl.lds);
+        return SIGSVGD_E_UNSUPPORTED;
+    }
+    const int per_cu = (int)(kRingMaxLds / pl.lds);
+    pl.resident = (long long)device_cu_count() * (per_cu > 8 ? 8 : per_cu);
+    return SIGSVGD_OK;
+}
+
+// A launch with SIGSVGD_FLAG_LOG_K on plan pl: one int per block of 64 sweep steps beside the boundary
+// row in LDS (behind the caller's rows), and the forward sweep's [band][block] exponents in the wave's scratch, behind its spare
+// row (a forward-only launch keeps them too, alone: one forward sweep for both).  The resident waves follow the larger LDS;
+// refuses as ring_make_plan does.
+__host__ __device__ inline int ring_log_blocks(int nsteps) { return (nsteps + kWave - 1) / kWave; }
+int ring_log_plan(const char *who, RingPlan &pl)
+{
+    const size_t nblk = (size_t)ring_log_blocks(pl.nsteps);
+    pl.lds += ((nblk + 1) * sizeof(int) + 7) & ~(size_t)7;
+    pl.per_wave += (size_t)pl.nbands * nblk * sizeof(int);
+    if (pl.lds > kRingMaxLds) {
+        set_error("%s: per-wave state needs %zu B of LDS (> 160 KiB) with SIGSVGD_FLAG_LOG_K", who, pl.lds);
         return SIGSVGD_E_UNSUPPORTED;
     }
     const int per_cu = (int)(kRingMaxLds / pl.lds);
@@ -208,6 +236,55 @@ __device__ __forceinline__ RingWave ring_wave(const Args &a, unsigned char *smem
     return w;
 }
 
+// ---- the log-domain solve (SIGSVGD_FLAG_LOG_K) -------------------------------------------------------
+// Both sweeps are linear in the solution, so a band may carry it times 2^-E: between blocks of 64 sweep steps the wave takes the
+// largest exponent of its lanes' live values and, once that has drifted past kLogDrift, multiplies them by its power of two and
+// adds it to the running exponent E (F in the reverse sweep).  Powers of two only: every rounding of the sweep commutes with
+// them, so the mantissas are the unscaled solve's.  Every band starts at E = 0 (its first cells sit on the grid's edge, where
+// the solution is 1).  What a band leaves for the next one in the boundary row is under the exponent of the block that wrote it:
+// etab keeps one int per block beside the row, and each block brings the 64 entries it is about to read to its own exponent
+// first (one entry per lane) before it puts its own exponent in the table, in place.  The stored forward solution is the scaled
+// one, with the [band][block] exponents in ews; the reverse sweep multiplies each value it reads back by 2^(E_fwd + F - E) / m
+// (m 2^E the pair's K), so what it files in wss is the relative sensitivity GG / K, O(1), and everything behind S is unchanged.
+struct RingLog {
+    int *etab;    // LDS [blocks + 1]
+    int *ews;     // the wave's scratch [nbands][blocks]: the forward sweep's exponents
+    int nblk;
+    int E;        // the exponent of the value ring_forward returned
+    double inv_m; // 1 / that value (NaN where it is <= 0: the pair's gradient is NaN, as its ln K)
+};
+constexpr int kLogDrift = 8;
+template <bool GRAD, typename Args>
+__device__ __forceinline__ RingLog ring_log(const Args &a, const RingWave &w, void *lds_behind_rows)
+{
+    RingLog lg;
+    lg.etab = static_cast<int *>(lds_behind_rows);
+    lg.ews = reinterpret_cast<int *>(GRAD ? w.spare - threadIdx.x + kWave : a.wsk + (size_t)blockIdx.x * a.wsk_per_block);
+    lg.nblk = ring_log_blocks(w.nsteps);
+    lg.E = 0;
+    lg.inv_m = 1.0;
+    return lg;
+}
+// the largest binary exponent of a and b over the lanes with `valid` (the same in every lane, from a scalar register)
+__device__ __forceinline__ int wave_max_exp(bool valid, double a, double b)
+{
+    int e = valid ? max(__builtin_amdgcn_frexp_exp(a), __builtin_amdgcn_frexp_exp(b)) : -4096;
+#pragma unroll
+    for (int o = kWave / 2; o; o >>= 1) e = max(e, __shfl_xor(e, o));
+    return __builtin_amdgcn_readfirstlane(e);
+}
+// ln K of the pair from the forward sweep's value (in the lane that holds row P - 1) and exponent, in every lane; sets inv_m.
+// As much of the exponent as fp64 holds goes back into the value before the logarithm (a K of order 1 under a large wave-wide
+// exponent would otherwise be the difference of two large terms): where K fits fp64 the result is log(K) itself.
+__device__ __forceinline__ double ring_log_finish(const RingWave &w, double Kval, RingLog &lg)
+{
+    const double m = __shfl(Kval, (w.P - 1) & (kWave - 1));
+    const bool pos = m > 0.0;
+    lg.inv_m = pos ? 1.0 / m : __builtin_nan("");
+    const int e0 = min(max(lg.E, -900), 900); // (m is within 2^-120 .. 2^120 of the wave's largest value, which is near 1)
+    return pos ? __builtin_fma((double)(lg.E - e0), 6.93147180559945309417e-01, log(ldexp(m, e0))) : __builtin_nan("");
+}
+
 // ---- forward sweep of one pair over all bands: returns the final value of the lane that holds row P - 1 ----------------------
 // fill(a0, b_lo, b_hi): coarse columns b_lo .. b_hi of the increment rows a0 .. a0 + nrow - 1 into the ring, between barriers;
 // band(a0): called as each band starts, before its first fill.  (The step of gram_generic_kernel: branch-free, results of
@@ -215,18 +292,26 @@ __device__ __forceinline__ RingWave ring_wave(const Args &a, unsigned char *smem
 // EXACT (default stencil with GRAD only): what the sweep keeps for the reverse sweep is not K00 =
 // K_fwd[p][q] but the cell's derivative of the step in its increment, c = (K10 + K01) (1/2 + g/6) + K00 g/6, in the same slot;
 // the arithmetic that produces K is the same.
-template <bool NAIVE, bool GRAD, bool EXACT = false, typename Fill, typename Band>
-__device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, Band &&band)
+// LOG (see RingLog above): the value returned is times 2^-lg->E.
+template <bool NAIVE, bool GRAD, bool EXACT = false, bool LOG = false, typename Fill, typename Band>
+__device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, Band &&band, [[maybe_unused]] RingLog *lg = nullptr)
 {
     static_assert(!EXACT || (GRAD && !NAIVE), "the exact adjoint is the default stencil's, and a gradient launch's");
+    static_assert(!LOG || (!EXACT && !NAIVE), "the log-domain solve is the default stencil's GG solve");
     const int lane = threadIdx.x;
     const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
     double *rowbuf = w.rowbuf;
     double Kval = 1.0;
+    [[maybe_unused]] int E = 0;        // LOG: the band's values are times 2^-E
+    [[maybe_unused]] double one = 1.0; // LOG: 2^-E, the grid's upper edge
     for (int kb = 0; kb < w.nbands; ++kb) {
         const int p = kb * kWave + lane;
         const bool rowvalid = p < P;
         const bool first = kb == 0;
+        if constexpr (LOG) {
+            E = 0;
+            one = 1.0;
+        }
         const int a0 = (kb * kWave) >> n;
         band(a0);
         const double *Drow = w.ring + (size_t)((min(p, P - 1) >> n) - a0) * W;
@@ -241,6 +326,24 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
                 fill(a0, have + 1, to);
                 have = to;
             }
+            if constexpr (LOG) {
+                if (s0 > 0) {
+                    const int e = wave_max_exp(rowvalid, cur, upprev);
+                    if (e > kLogDrift || e < -kLogDrift) {
+                        cur = ldexp(cur, -e);
+                        upprev = ldexp(upprev, -e);
+                        rb = ldexp(rb, -e);
+                        E += e;
+                        one = ldexp(1.0, -E);
+                    }
+                }
+                // the entries of the boundary row this block reads, s0 + 2 .. s0 + 65 (lane 63 of the band above stored entry
+                // k on its step k + 62), to this block's exponent; then the block's own exponent for the band below
+                const int idx = s0 + 2 + lane;
+                if (!first && idx <= Q) rowbuf[idx] = ldexp(rowbuf[idx], lg->etab[(idx + kWave - 2) >> 6] - E);
+                if (lane == 0) lg->etab[s0 >> 6] = lg->ews[kb * lg->nblk + (s0 >> 6)] = E;
+                __syncthreads();
+            }
             double gf = Drow[(min(max(s0 - lane, 0), Q - 1) >> n) & (W - 1)];
             const int s1 = min(s0 + kWave, nsteps);
             for (int s = s0; s < s1; ++s) {
@@ -248,7 +351,7 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
                 const bool active = rowvalid && q >= 0 && q < Q;
                 const double gfn = Drow[(min(max(q + 1, 0), Q - 1) >> n) & (W - 1)];
                 const double rbr = rowbuf[min(s + 2, Q)];
-                const double rbn = first ? 1.0 : rbr;
+                const double rbn = first ? (LOG ? one : 1.0) : rbr;
                 double up_in = shfl_up_f64(cur);
                 up_in = (lane == 0) ? rb : up_in;
                 const double nw = stencil(cur, up_in, upprev, gf * w.inv_r2, NAIVE);
@@ -269,6 +372,7 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
         }
         if (p == P - 1) Kval = cur;
     }
+    if constexpr (LOG) lg->E = E;
     return Kval;
 }
 
@@ -280,10 +384,13 @@ __device__ __forceinline__ double ring_forward(const RingWave &w, Fill &&fill, B
 // alpha = beta = 0 outside the grid.  Lane p + 1 is one column ahead, so h is the one number it formed on the step before
 // (its newest alpha less the beta of the step before that): the one shfl_down_f64 of the step moves it, and the band below
 // hands its row of h over in rowbuf.  The sum filed in w.wss is lambda c, c from ring_forward<.., EXACT>.
-template <bool NAIVE, bool EXACT = false, typename Fill, typename Band>
-__device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Band &&band)
+// LOG (see RingLog above): the same scheme under a running exponent F of its own; the sum filed in
+// w.wss is GG / K, from lg->E and lg->inv_m of the forward sweep.
+template <bool NAIVE, bool EXACT = false, bool LOG = false, typename Fill, typename Band>
+__device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Band &&band, [[maybe_unused]] RingLog *lg = nullptr)
 {
     static_assert(!EXACT || !NAIVE, "the exact adjoint is the default stencil's");
+    static_assert(!LOG || (!EXACT && !NAIVE), "the log-domain solve is the default stencil's GG solve");
     const int lane = threadIdx.x;
     const int N = w.N, n = w.n, P = w.P, Q = w.Q, W = w.W, nsteps = w.nsteps;
     double *rowbuf = w.rowbuf;
@@ -301,6 +408,8 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
         double cur = 1.0, dprev = 1.0, sb = 0.0;
         [[maybe_unused]] double bprev = 0.0; // EXACT: cur = h, dprev = the lane's newest alpha, bprev = its newest beta
         if constexpr (EXACT) cur = dprev = 0.0;
+        [[maybe_unused]] int F = 0, Rsplit = 0;                   // LOG: the band's values are times 2^-F
+        [[maybe_unused]] double one = 1.0, fsA = 1.0, fsB = 1.0; // LOG: 2^-F; what a stored row >= / < Rsplit is multiplied by
         const int nsp = Q + L - 1;
         int q = Q - 1 + (L - 1 - lane);
         int R = Q - 1 + L - 1; // row of the stored forward solution on reverse step 0
@@ -318,9 +427,35 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
                 fill(a0, from, low - 1);
                 low = from;
             }
+            if constexpr (LOG) {
+                if (sp0 > 0) {
+                    const int e = wave_max_exp(rowvalid, cur, dprev);
+                    if (e > kLogDrift || e < -kLogDrift) {
+                        cur = ldexp(cur, -e);
+                        dprev = ldexp(dprev, -e);
+                        F += e;
+                        one = ldexp(1.0, -F);
+                    }
+                }
+                // the entries of the boundary row this block reads, Q - 1 - sp0 down to Q - 64 - sp0 (lane 0 of the band below,
+                // of Lb rows, stored entry k on its step Q + Lb - 2 - k), to this block's exponent; the table entries are read
+                // before the block's own exponent goes in
+                const int idx = Q - 1 - sp0 - lane, Lb = min(kWave, P - (kb + 1) * kWave);
+                const bool mine = !lastband && idx >= 0;
+                const int fb = mine ? lg->etab[(Q + Lb - 2 - idx) >> 6] : 0;
+                __syncthreads();
+                if (mine) rowbuf[idx] = ldexp(rowbuf[idx], fb - F);
+                if (lane == 0) lg->etab[sp0 >> 6] = F;
+                __syncthreads();
+                // the stored forward rows of this block are R down to R - 63: at most two blocks of the forward sweep
+                const int *ef = lg->ews + kb * lg->nblk, hb = max(R, 0) >> 6;
+                Rsplit = hb << 6;
+                fsA = ldexp(lg->inv_m, ef[hb] + F - lg->E);
+                fsB = ldexp(lg->inv_m, ef[max(hb - 1, 0)] + F - lg->E);
+            }
             double gf = Drow[(min(max(q, 0), Q - 1) >> n) & (W - 1)];
             double rbk = rowbuf[max(Q - 1 - sp0, 0)];
-            rb = lastband ? 1.0 : rbk;
+            rb = lastband ? (LOG ? one : 1.0) : rbk;
             if constexpr (EXACT) rb = lastband ? (sp0 == 0 ? 1.0 : 0.0) : rbk; // (below the grid 0; the 1 is lambda(P-1, Q-1))
             // (the groups past nsp have no lane inside the grid and change nothing; their S stores go to the spare row)
             for (int sp1 = sp0; sp1 < sp0 + kWave; sp1 += KPF) {
@@ -330,9 +465,10 @@ __device__ __forceinline__ void ring_reverse(const RingWave &w, Fill &&fill, Ban
                     const bool active = rowvalid && q >= 0 && q < Q;
                     const double gfn = Drow[(min(max(q - 1, 0), Q - 1) >> n) & (W - 1)];
                     const double rbr = rowbuf[max(Q - 2 - sp, 0)];
-                    double rbn = lastband ? 1.0 : rbr;
+                    double rbn = lastband ? (LOG ? one : 1.0) : rbr;
                     if constexpr (EXACT) rbn = lastband ? 0.0 : rbr;
-                    const double kf = (double)kfr[u];
+                    double kf = (double)kfr[u];
+                    if constexpr (LOG) kf *= R >= Rsplit ? fsA : fsB;
                     kfr[u] = wrow[(size_t)max(R - KPF, 0) * kWave];
                     double down_in = shfl_down_f64(cur);
                     down_in = (lane == L - 1) ? rb : down_in;

@@ -133,8 +133,10 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
 
 
 def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
-           fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False) -> int:
+           fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False) -> int:
     f = 0
+    if log_k:
+        f |= _lib.FLAG_LOG_K
     if nan_tails:
         f |= _lib.FLAG_NAN_TAILS
     if naive:
@@ -278,22 +280,22 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
 
 def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                      want_gradX: bool = True, want_gradY: bool = True, y_is_x: bool = False,
-                     exact_adjoint: bool = False, nan_tails: bool = False) -> bool:
+                     exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False) -> bool:
     """Whether `gram_long_fwd_bwd2` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
-    state beyond the LDS; nan_tails together with exact_adjoint); any other error raises."""
+    state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either); any other error raises."""
     return _query("gram_long2_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                                  1 if want_gradX else 0, 1 if want_gradY else 0,
                                                  _flags(False, False, y_is_x, False, exact_adjoint=exact_adjoint,
-                                                        nan_tails=nan_tails)),
+                                                        nan_tails=nan_tails, log_k=log_k)),
                   (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                        grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
                        y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True,
-                       exact_adjoint: bool = False,
-                       nan_tails: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       exact_adjoint: bool = False, nan_tails: bool = False,
+                       log_k: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(K[A,B], gX[A,TX,d] or None, gY[B,TY,d] or None) on the long route from one solve per pair
     (`sigsvgd_gram_long_fwd_bwd2`): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each its own slot (grad_out
     None = ones), K bit-identical to `gram_long_fwd`.  y_is_x (Y holds X's values; A == B, TX == TY): each unordered pair is
@@ -301,7 +303,10 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
     sym: weights grad_out + grad_out^T.  Both give no gY (it is returned as None).  Neither gradient wanted: forward only.
     Computed and returned in X's dtype; bit-reproducible.  nan_tails (SIGSVGD_FLAG_NAN_TAILS; here
     and on the paired launches below): a path ends before its first point whose channel 0 is NaN, pair (i, j) is solved on
-    its own grid, and the gradient rows from a path's end on are exact zeros."""
+    its own grid, and the gradient rows from a path's end on are exact zeros.  log_k (SIGSVGD_FLAG_LOG_K, DESIGN.md section
+    5.21; here and on the paired launches below): the first result is ln K and the gradients are those of sum(grad_out * ln K),
+    from sweeps that carry a running power-of-two scale, so nothing overflows while ln K itself is representable; a pair
+    whose discrete K is <= 0 gives NaN.  Default stencil only, not with exact_adjoint or nan_tails."""
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
@@ -309,7 +314,7 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
         raise ValueError("sym and y_is_x need X and Y of one shape")
     want_gradY = bool(want_gradY) and not (sym or y_is_x)
     go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails)
+    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
     gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
@@ -322,25 +327,26 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
 
 
 def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-               want_grad: bool = True, exact_adjoint: bool = False, nan_tails: bool = False) -> bool:
+               want_grad: bool = True, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False) -> bool:
     """Whether `pair_fwd` (want_grad False) / `pair_fwd_bwd` take pairs X [A, TX, d], Y [A, TY, d]: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
-    state beyond the LDS; nan_tails together with exact_adjoint); any other error raises."""
+    state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either); any other error raises."""
     return _query("pair_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                            1 if want_grad else 0, _flags(False, False, False, False, exact_adjoint=exact_adjoint,
-                                                                         nan_tails=nan_tails)),
+                                                                         nan_tails=nan_tails, log_k=log_k)),
                   (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def pair_schedule(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-                  want_grad: bool = True, exact_adjoint: bool = False, nan_tails: bool = False) -> Tuple[int, int, int]:
+                  want_grad: bool = True, exact_adjoint: bool = False, nan_tails: bool = False,
+                  log_k: bool = False) -> Tuple[int, int, int]:
     """(waves_per_pair, grid, lds_bytes) of the paired launch these arguments would run now (`sigsvgd_pair_schedule`, host
     only, SIGSVGD_PAIR_MODE included): 1 wave per pair is the serial kernel of csrc/gram_long.hip, more the band-parallel one
     of csrc/pair_bands.hip.  The results do not depend on it, bit for bit.  exact_adjoint: gradient launches with it always
-    run 1 wave per pair, and so does every launch with nan_tails."""
+    run 1 wave per pair, and so does every launch with nan_tails or log_k."""
     waves, grid, lds = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
     _query("pair_schedule", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind), 1 if want_grad else 0,
-                             _flags(False, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails)),
+                             _flags(False, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)),
            (waves, grid, lds))
     return waves.value, grid.value, lds.value
 
@@ -352,14 +358,14 @@ def _prep_pair(X, Y):
 
 
 def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
-             naive: bool = False, nan_tails: bool = False) -> torch.Tensor:
+             naive: bool = False, nan_tails: bool = False, log_k: bool = False) -> torch.Tensor:
     """K[A] = k_sig(X_i, Y_i) of the built-in static kernels (`sigsvgd_pair_fwd`, the paired mode of csrc/gram_long.hip): one
     solve per pair.  X [A,TX,d] and Y [A,TY,d] at their own lengths; fp64 increments and sweeps, K in X's dtype, bit-identical
-    to the diagonal of `gram_long_fwd(X, Y)`."""
+    to the diagonal of `gram_long_fwd(X, Y)`.  log_k: ln K, bit-identical to the diagonal of the two-sided launch with log_k."""
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
-    flags = _flags(naive, False, False, False, nan_tails=nan_tails)
+    flags = _flags(naive, False, False, False, nan_tails=nan_tails, log_k=log_k)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
     _launch(dev, "pair_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
                               int(static_kind), flags, K.data_ptr()),
@@ -369,8 +375,8 @@ def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
 
 def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                  grad_out: Optional[torch.Tensor] = None, naive: bool = False, want_x: bool = True, want_y: bool = True,
-                 exact_adjoint: bool = False,
-                 nan_tails: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+                 exact_adjoint: bool = False, nan_tails: bool = False,
+                 log_k: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(K[A], gX[A,TX,d] or None, gY[A,TY,d] or None): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each path's
     own slot (grad_out None = ones), from one forward and one reverse sweep per pair (`sigsvgd_pair_fwd_bwd`).  Computed
     and returned in X's dtype; bit-reproducible."""
@@ -380,7 +386,7 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     Xc, Yc = _prep_pair(X, Y)
     (A, TX, d), TY = Xc.shape, Yc.shape[1]
     go = _weights(grad_out, (A,), Xc.dtype)
-    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails)
+    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
     K = torch.empty((A,), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
     gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None

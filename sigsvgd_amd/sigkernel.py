@@ -328,6 +328,12 @@ def _nan_kw(nan_tails) -> dict:
     return {"nan_tails": True} if nan_tails else {}
 
 
+def _log_kw(log_k) -> dict:
+    """the `log_k` keyword of the long route's launches and queries, handed over only where it is set,
+    as `_exact_kw`"""
+    return {"log_k": True} if log_k else {}
+
+
 # ------------------------------------------------------------------------------------------------
 # batches of paths of different lengths (DESIGN.md section 5.20)
 # ------------------------------------------------------------------------------------------------
@@ -566,15 +572,16 @@ class _SigKernelPair(torch.autograd.Function):
     there is one launch per call.  The launch computes in X's dtype; each gradient returns in its own input's dtype."""
 
     @staticmethod
-    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, exact_grad=False, nan_tails=False):
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, naive, exact_grad=False, nan_tails=False, log_k=False):
         want_x, want_y = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ctx.dtypes = (X.dtype, Y.dtype)
         if want_x or want_y:
             K, gX, gY = ops.pair_fwd_bwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, None, naive, want_x,
-                                         want_y, **_exact_kw(exact_grad), **_nan_kw(nan_tails))
+                                         want_y, **_exact_kw(exact_grad), **_nan_kw(nan_tails), **_log_kw(log_k))
             ctx.save_for_backward(gX, gY)
         else:
-            K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive, **_nan_kw(nan_tails))
+            K = ops.pair_fwd(X.detach(), Y.detach(), inv_h, dyadic_order, static_kind, naive, **_nan_kw(nan_tails),
+                             **_log_kw(log_k))
         return K
 
     @staticmethod
@@ -585,6 +592,90 @@ class _SigKernelPair(torch.autograd.Function):
             gX = (gX1 * grad_output.to(gX1.dtype)[:, None, None]).to(ctx.dtypes[0])
         if gY1 is not None:
             gY = (gY1 * grad_output.to(gY1.dtype)[:, None, None]).to(ctx.dtypes[1])
+        return gX, gY, None, None, None, None, None, None, None
+
+
+# ------------------------------------------------------------------------------------------------
+# log-domain and normalised kernels
+# ------------------------------------------------------------------------------------------------
+def _log_forward(X, Y, cfg, y_is_x):
+    """ln K [A, B]: the flagged two-sided launch, forward only"""
+    static_kind, inv_h, dyadic_order = cfg
+    return ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, None, False, False, y_is_x, False, False,
+                                  log_k=True)[0]
+
+
+class _SigKernelLogGram(torch.autograd.Function):
+    """forward: ln K = log Gram(X, Y), one flagged two-sided launch (`ops.gram_long_fwd_bwd2(..., log_k=True)`), forward only.
+    backward: one flagged launch with grad_out = grad_output, which returns d sum(grad_output ln K) / dX and, with grad_Y, / dY."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, sym, y_is_x, grad_Y):
+        ctx.cfg = (static_kind, inv_h, dyadic_order)
+        ctx.sym, ctx.y_is_x, ctx.y_dtype = sym, y_is_x, Y.dtype
+        ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
+        Xd, Yd = X.detach(), Y.detach()
+        ctx.save_for_backward(Xd, Yd)
+        return _log_forward(Xd, Yd, ctx.cfg, y_is_x)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y = ctx.saved_tensors
+        static_kind, inv_h, dyadic_order = ctx.cfg
+        want_x, want_y = ctx.want
+        gX = gY = None
+        if want_x or want_y:
+            _, gX, gY = ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, grad_output, False, ctx.sym,
+                                               ctx.y_is_x and not want_y, want_x, want_y, log_k=True)
+        if gY is not None:
+            gY = gY.to(ctx.y_dtype)
+        return gX, gY, None, None, None, None, None, None
+
+
+class _SigKernelNormGram(torch.autograd.Function):
+    """The normalised Gram matrix Khat_ij = K(X_i, Y_j) / sqrt(K(X_i, X_i) K(Y_j, Y_j)) = exp(l_ij - a_i / 2 - b_j / 2) from the
+    logarithms alone, so that it exists where K itself overflows.
+
+    forward: l from one flagged two-sided launch, a and b from flagged paired launches on (X, X) and (Y, Y) (one where one
+    tensor is in both slots); all forward only.  The paired and the two-sided launch give ln K the same bits, so the diagonal of
+    Khat(X, X) is exactly 1.
+    backward, for upstream G with W = G * Khat: one flagged two-sided launch with grad_out = W, and per batch that is
+    differentiated one flagged `ops.pair_fwd_bwd` with grad_out = -rowsum(W) / 2 (X) or -colsum(W) / 2 (Y), whose gX + gY is
+    added.  sym (one batch in both slots, gradient folded into the first): the two-sided launch weights W + W^T and the paired
+    launch on X carries both sums.  No host sync anywhere."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, sym, y_is_x, grad_Y):
+        ctx.cfg = (static_kind, inv_h, dyadic_order)
+        ctx.sym, ctx.y_is_x, ctx.y_dtype = sym, y_is_x, Y.dtype
+        ctx.want = (ctx.needs_input_grad[0], bool(grad_Y) and ctx.needs_input_grad[1])
+        Xd, Yd = X.detach(), Y.detach()
+        l = _log_forward(Xd, Yd, ctx.cfg, y_is_x)
+        a = ops.pair_fwd(Xd, Xd, inv_h, dyadic_order, static_kind, log_k=True)
+        b = a if y_is_x else ops.pair_fwd(Yd, Yd, inv_h, dyadic_order, static_kind, log_k=True).to(a.dtype)
+        Khat = torch.exp(l - (0.5 * a[:, None] + 0.5 * b[None, :]))  # (symmetric where l is; a - (a / 2 + a / 2) = 0 exactly)
+        ctx.save_for_backward(Xd, Yd, Khat)
+        return Khat
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y, Khat = ctx.saved_tensors
+        static_kind, inv_h, dyadic_order = ctx.cfg
+        want_x, want_y = ctx.want
+        if not (want_x or want_y):
+            return (None,) * 8
+        W = grad_output * Khat
+        _, gX, gY = ops.gram_long_fwd_bwd2(X, Y, inv_h, dyadic_order, static_kind, W, False, ctx.sym,
+                                           ctx.y_is_x and not want_y, want_x, want_y, log_k=True)
+
+        def diagonal_term(P, weights):  # d sum(weights ln K(P_i, P_i)) / dP: both slots
+            _, pX, pY = ops.pair_fwd_bwd(P, P, inv_h, dyadic_order, static_kind, weights, log_k=True)
+            return pX + pY
+
+        if want_x:
+            gX = gX + diagonal_term(X, -0.5 * (W.sum(1) + W.sum(0) if ctx.sym else W.sum(1)))
+        if want_y:
+            gY = (gY + diagonal_term(Y, -0.5 * W.sum(0))).to(ctx.y_dtype)
         return gX, gY, None, None, None, None, None, None
 
 
@@ -699,10 +790,27 @@ class SigKernel:
     gradient-bearing launch of `compute_Gram`, `compute_kernel`, `compute_distance`, `compute_mmd` and `gram_and_grad` then
     takes the long route with SIGSVGD_FLAG_EXACT_ADJOINT whatever the shape (fp64 sweeps; K keeps the long route's bits);
     shapes the long route refuses raise NotImplementedError.  Forward-only calls are untouched, and so is `_naive_solver=True`,
-    whose GG is exact already.  Not together with fp32_sweeps (ValueError)."""
+    whose GG is exact already.  Not together with fp32_sweeps (ValueError).
+
+    normalize=True: `compute_Gram`, `compute_kernel`, `compute_distance` and `compute_mmd` return the
+    normalised kernel K(x, y) / sqrt(K(x, x) K(y, y)), built from the log-domain launches of the long route
+    (SIGSVGD_FLAG_LOG_K), so it exists and is differentiable where K itself overflows (K(x, x) of rough paths passes fp32 from
+    about 300 points and fp64 from about 1600).  Whatever the shape, these calls run on the long route at its fp64 cost, as
+    exact_grad=True does; shapes it refuses, `lengths_*`, exact_grad=True, `_naive_solver=True`, a sigma that requires grad and
+    user static kernels raise NotImplementedError, fp32_sweeps=True ValueError.  `compute_log_Gram` and `compute_log_kernel`
+    return ln K itself (with any value of normalize); `gram_and_grad` is not normalised."""
 
     def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False,
-                 exact_grad: bool = False):
+                 exact_grad: bool = False, normalize: bool = False):
+        if normalize and fp32_sweeps:
+            raise ValueError("SigKernel: normalize=True runs on the long route's fp64 log-domain sweeps; fp32_sweeps=True "
+                             "selects an fp32-sweep kernel.  Use one of them")
+        if normalize and exact_grad:
+            raise NotImplementedError("SigKernel: normalize=True with exact_grad=True: SIGSVGD_FLAG_LOG_K together with "
+                                      "SIGSVGD_FLAG_EXACT_ADJOINT is not built")
+        if normalize and _naive_solver:
+            raise NotImplementedError("SigKernel: normalize=True with _naive_solver=True: the log-domain kernels have the "
+                                      "default stencil only")
         if exact_grad and fp32_sweeps:
             raise ValueError("SigKernel: exact_grad=True runs every gradient launch on the long route's fp64 sweeps; "
                              "fp32_sweeps=True selects an fp32-sweep kernel.  Use one of them")
@@ -711,6 +819,7 @@ class SigKernel:
         self._naive_solver = bool(_naive_solver)
         self.fp32_sweeps = bool(fp32_sweeps)
         self.exact_grad = bool(exact_grad)
+        self.normalize = bool(normalize)
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
@@ -728,6 +837,8 @@ class SigKernel:
         if grad_Y and sym:
             raise ValueError("compute_Gram: grad_Y=True differentiates the second slot itself; sym=True folds it into the "
                              "first.  Use one of them")
+        if self.normalize:
+            return self._log_gram(_SigKernelNormGram, "compute_Gram", X, Y, sym, grad_Y, lengths_X, lengths_Y)
         if lengths_X is not None or lengths_Y is not None:
             return self._lengths_gram(X, Y, bool(sym), bool(grad_Y), lengths_X, lengths_Y)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
@@ -792,6 +903,60 @@ class SigKernel:
             raise _refused("compute_kernel", X, Y, self.dyadic_order, "a batch with lengths")
         return _SigKernelPair.apply(Xn, Yn, static_kind, inv_h, self.dyadic_order, self._naive_solver, False, True)
 
+    # -- log-domain and normalised kernels -----------------------------------------------------------
+    def _log_static(self, what, X, Y, lengths_X=None, lengths_Y=None):
+        """-> (static_kind, inv_h) of a call that runs the log-domain launches, and its refusals"""
+        if lengths_X is not None or lengths_Y is not None:
+            raise NotImplementedError(f"{what}: lengths_X / lengths_Y with the log-domain launches: SIGSVGD_FLAG_LOG_K together "
+                                      "with SIGSVGD_FLAG_NAN_TAILS is not built")
+        if self.exact_grad or self._naive_solver:
+            raise NotImplementedError(f"{what}: the log-domain launches have the default stencil's GG gradient only "
+                                      "(not with exact_grad=True or _naive_solver=True)")
+        if _learned_sigma(self.static_kernel) is not None:
+            raise NotImplementedError(f"{what}: a static-kernel sigma that requires grad: the bandwidth launches do not take "
+                                      "SIGSVGD_FLAG_LOG_K")
+        static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
+        if static_kind is None:
+            raise NotImplementedError(f"{what}: the user static kernel {type(self.static_kernel).__name__} runs on "
+                                      "ops.PDESolve, which has no log-domain form; the built-in static kernels have one")
+        return static_kind, inv_h
+
+    def _log_gram(self, node, what, X, Y, sym, grad_Y, lengths_X=None, lengths_Y=None):
+        """the two-sided log-domain node (`_SigKernelLogGram` or `_SigKernelNormGram`) of a call, whatever the shape"""
+        static_kind, inv_h = self._log_static(what, X, Y, lengths_X, lengths_Y)
+        y_is_x = _same_storage(X, Y)
+        if not ops.gram_long2_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind,
+                                    True, True, False, log_k=True):
+            raise _refused(what, X, Y, self.dyadic_order, "the log-domain solve")
+        return node.apply(X, Y, static_kind, inv_h, self.dyadic_order, bool(sym), y_is_x, bool(grad_Y))
+
+    def compute_log_Gram(self, X: torch.Tensor, Y: torch.Tensor, sym: bool = False, grad_Y: bool = False) -> torch.Tensor:
+        """ln K[i,j] = ln k_sig(X_i, Y_j) from the log-domain launch of the long route (SIGSVGD_FLAG_LOG_K), differentiable as
+        `compute_Gram` is (sym, grad_Y as there): finite where K itself overflows.  NaN where the discrete K is <= 0."""
+        if grad_Y and sym:
+            raise ValueError("compute_log_Gram: grad_Y=True differentiates the second slot itself; sym=True folds it into the "
+                             "first.  Use one of them")
+        return self._log_gram(_SigKernelLogGram, "compute_log_Gram", X, Y, sym, grad_Y)
+
+    def compute_log_kernel(self, X: torch.Tensor, Y: torch.Tensor) -> torch.Tensor:
+        """ln k_sig(X_i, Y_i) -> [batch] from the paired log-domain launch, differentiable in X and in Y (each its own slot)."""
+        assert X.shape[0] == Y.shape[0], "compute_log_kernel pairs X_i with Y_i"
+        static_kind, inv_h = self._log_static("compute_log_kernel", X, Y)
+        want_grad = torch.is_grad_enabled() and (X.requires_grad or Y.requires_grad)
+        if not ops.pair_takes(X.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind, want_grad,
+                              log_k=True):
+            raise _refused("compute_log_kernel", X, Y, self.dyadic_order, "the log-domain solve")
+        return _SigKernelPair.apply(X, Y, static_kind, inv_h, self.dyadic_order, False, False, False, True)
+
+    def _normalized_kernel(self, X, Y, lengths_X, lengths_Y):
+        """compute_kernel with normalize=True: exp(ln k(X_i, Y_i) - ln k(X_i, X_i) / 2 - ln k(Y_i, Y_i) / 2) of three paired
+        log-domain launches (two where one tensor is in both slots of the call: then the result is exactly 1)"""
+        self._log_static("compute_kernel", X, Y, lengths_X, lengths_Y)
+        a = self.compute_log_kernel(X, X)
+        if _same_storage(X, Y):
+            return torch.exp(a - 0.5 * a - 0.5 * a)
+        return torch.exp(self.compute_log_kernel(X, Y) - 0.5 * a - 0.5 * self.compute_log_kernel(Y, Y).to(a.dtype))
+
     def compute_kernel(self, X: torch.Tensor, Y: torch.Tensor, lengths_X=None, lengths_Y=None) -> torch.Tensor:
         """Paired kernel k_sig(X_i, Y_i) -> [batch], one solve per pair, differentiable in X and in Y (each its own slot:
         compute_kernel(X, X) differentiates to the sum of both).  Built-in static kernels run on the paired route
@@ -800,6 +965,8 @@ class SigKernel:
         torch autograd; one without it takes the diagonal of its Gram launch.  lengths_X / lengths_Y: as `compute_Gram`'s; the
         pairs then run on the paired route whatever the shape."""
         assert X.shape[0] == Y.shape[0], "compute_kernel pairs X_i with Y_i"
+        if self.normalize:
+            return self._normalized_kernel(X, Y, lengths_X, lengths_Y)
         if lengths_X is not None or lengths_Y is not None:
             return self._lengths_kernel(X, Y, lengths_X, lengths_Y)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
@@ -827,6 +994,8 @@ class SigKernel:
 
     def compute_distance(self, X: torch.Tensor, Y: torch.Tensor, lengths_X=None, lengths_Y=None) -> torch.Tensor:
         """mean_i k(X_i, X_i) + mean_i k(Y_i, Y_i) - 2 mean_i k(X_i, Y_i).  lengths_X / lengths_Y: as `compute_Gram`'s."""
+        if self.normalize:
+            self._log_static("compute_distance", X, Y, lengths_X, lengths_Y)
         if lengths_X is None and lengths_Y is None:
             return (self.compute_kernel(X, X).mean() + self.compute_kernel(Y, Y).mean()
                     - 2.0 * self.compute_kernel(X, Y).mean())
@@ -838,6 +1007,8 @@ class SigKernel:
         """Biased squared MMD: mean K_XX + mean K_YY - 2 mean K_XY.  grad_Y=True differentiates Y through the cross term
         too (`compute_Gram(X, Y, grad_Y=True)`); the default gives Y the gradient of mean K_YY alone.  lengths_X /
         lengths_Y: as `compute_Gram`'s."""
+        if self.normalize:
+            self._log_static("compute_mmd", X, Y, lengths_X, lengths_Y)
         if lengths_X is None and lengths_Y is None:
             K_XX = self.compute_Gram(X, X, sym=True)
             K_YY = self.compute_Gram(Y, Y, sym=True)
