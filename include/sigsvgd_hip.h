@@ -202,6 +202,32 @@ extern "C" {
                                       /* SIGSVGD_FLAG_NAIVE_SOLVER, SIGSVGD_FLAG_EXACT_ADJOINT or SIGSVGD_FLAG_NAN_TAILS is set too.  Every   */
                                       /* other entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol,   */
                                       /* no changed signature; an earlier library answers SIGSVGD_E_BADARG                                    */
+#define SIGSVGD_FLAG_NORMALIZED 2048u /* normalised signature kernel and its gradient from one call on the long route (DESIGN.md section      */
+                                      /* 5.22).  With l_ij = ln K(X_i, Y_j), a_i = ln K(X_i, X_i), b_j = ln K(Y_j, Y_j), all from the          */
+                                      /* log-domain solve of SIGSVGD_FLAG_LOG_K (which the bit implies and is not combined with), K_out holds   */
+                                      /* K^_ij = exp(l_ij - (a_i / 2 + b_j / 2)), kept in fp64 until the one rounding to the I/O type (same     */
+                                      /* layout, same mirror store with SIGSVGD_FLAG_Y_IS_X, whose diagonal is exactly 1).  With w = grad_out   */
+                                      /* (NULL: ones; SIGSVGD_FLAG_SYM: w + w^T) and U = w * K^ entry by entry, in the GG convention            */
+                                      /*   gradX_out[i] = sum_j U_ij d1 l_ij - 1/2 (sum_j U_ij) grad a_i,                                      */
+                                      /*   gradY_out[j] = sum_i U_ij d2 l_ij - 1/2 (sum_i U_ij) grad b_j,                                      */
+                                      /* grad a_i the derivative of ln K(X_i, X_i) in both slots; each row summed in fp64 and rounded once.     */
+                                      /* SIGSVGD_FLAG_Y_IS_X, SIGSVGD_FLAG_SYM, NULL outputs and forward-only launches mean what they mean      */
+                                      /* without the bit: with Y_IS_X and no SYM gradX_out[i] is the derivative of sum_j w_ij K^(X_i, Y_j) in   */
+                                      /* X_i at fixed Y = X, the first-slot gradient SVGD uses; the diagonal pairs of a Y_IS_X launch, whose    */
+                                      /* K^ is the constant 1, are left out of both terms.  Every pair is solved once; the diagonals are        */
+                                      /* a paired pass ahead of the launch on the same stream, no host synchronisation, no allocation.  A pair  */
+                                      /* whose discrete K is <= 0 gives NaN in its K^ and the gradient rows it touches, a diagonal K <= 0 in    */
+                                      /* its whole row or column.  All six static kinds, both dtypes, any dyadic order, default stencil.        */
+                                      /* Taken by sigsvgd_gram_long_fwd_bwd2 and sigsvgd_gram_long2_workspace_bytes only.  The workspace is     */
+                                      /* the SIGSVGD_FLAG_LOG_K launch's plus the diagonals' logarithms (8 (A + B) bytes, 8 A with Y_IS_X,   */
+                                      /* padded to 256 B) and, with a gradient output, the pairs' fp64 weights w K^ (8 A B bytes), per side  */
+                                      /* whose gradient is wanted that side's fp64 diagonal gradients ([A][TX][d] or [B][TY][d]) and sums       */
+                                      /* ([A] or [B]); never less than the LOG_K launch's.  The weights stay fp64: with fp32 I/O a K^ below     */
+                                      /* fp32's range is stored as 0 and still counts in the gradient under a large grad_out.                   */
+                                      /* SIGSVGD_E_UNSUPPORTED before any device work when SIGSVGD_FLAG_NAIVE_SOLVER,                           */
+                                      /* SIGSVGD_FLAG_EXACT_ADJOINT, SIGSVGD_FLAG_NAN_TAILS or SIGSVGD_FLAG_LOG_K is set too.  Every other      */
+                                      /* entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol, no        */
+                                      /* changed signature; an earlier library answers SIGSVGD_E_BADARG                                         */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */

@@ -160,6 +160,23 @@ static int check_log_k(const char *who, unsigned flags)
     return SIGSVGD_E_UNSUPPORTED;
 }
 
+// SIGSVGD_FLAG_NORMALIZED on the two entry points that take it (sigsvgd_gram_long_fwd_bwd2 and its
+// workspace query; every other one keeps its answer for an unknown bit): refused before any device work together with a flag
+// whose kernels have no normalised form, and with SIGSVGD_FLAG_LOG_K, which it implies and whose output it replaces
+static int check_normalized(const char *who, unsigned flags)
+{
+    if (!(flags & SIGSVGD_FLAG_NORMALIZED)) return SIGSVGD_OK;
+    const char *other = (flags & SIGSVGD_FLAG_NAIVE_SOLVER)    ? "SIGSVGD_FLAG_NAIVE_SOLVER"
+                        : (flags & SIGSVGD_FLAG_EXACT_ADJOINT) ? "SIGSVGD_FLAG_EXACT_ADJOINT"
+                        : (flags & SIGSVGD_FLAG_NAN_TAILS)     ? "SIGSVGD_FLAG_NAN_TAILS"
+                        : (flags & SIGSVGD_FLAG_LOG_K)         ? "SIGSVGD_FLAG_LOG_K"
+                                                               : nullptr;
+    if (!other) return SIGSVGD_OK;
+    set_error("%s: SIGSVGD_FLAG_NORMALIZED together with %s is not built (the normalised kernels are the log-domain solve of the "
+              "default stencil on the launch's grid, and store K^ where that flag stores ln K)", who, other);
+    return SIGSVGD_E_UNSUPPORTED;
+}
+
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
                         int n, int kind, unsigned flags, const void *K_out)
 {
@@ -195,11 +212,13 @@ static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags,
 // (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, and for a launch with the reverse
 // sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; `nan_tails`: the entry point takes SIGSVGD_FLAG_NAN_TAILS
 // (the others answer UNSUPPORTED before anything else: check_nan_tails) and with it SIGSVGD_FLAG_LOG_K (check_log_k: the others
-// refuse that bit as an unknown one); every other bit is refused.
-static int check_long(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
+// refuse that bit as an unknown one); `normalized`: the entry point takes SIGSVGD_FLAG_NORMALIZED (check_normalized; the
+// two-sided launch and its query only); every other bit is refused.
+static int check_long(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false, bool normalized = false)
 {
     if (check_nan_tails("gram_long", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
     if (nan_tails && check_log_k("gram_long", p.flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (normalized && check_normalized("gram_long", p.flags)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
@@ -208,7 +227,7 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false, bool
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
     const unsigned known =
         SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
-        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u);
+        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u) | (normalized ? SIGSVGD_FLAG_NORMALIZED : 0u);
     if (p.flags & ~known)
         return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
@@ -227,9 +246,10 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false, bool
 
 // the two-sided entry points: check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says: one batch in both slots
 // (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
-static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false, bool nan_tails = false)
+static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false, bool nan_tails = false,
+                       bool normalized = false)
 {
-    const int rc = check_long(p, launch, grad, nan_tails);
+    const int rc = check_long(p, launch, grad, nan_tails, normalized);
     if (rc) return rc;
     if ((p.flags & SIGSVGD_FLAG_Y_IS_X) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
@@ -787,7 +807,7 @@ int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int 
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY, true);
+    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY, true, true);
     if (rc) return rc;
     return long2_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
@@ -798,7 +818,7 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out, true); // (neither: forward only)
+    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out, true, true); // (neither: forward only)
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
     return long2_launch(p);

@@ -2,6 +2,7 @@
 // the workspace queries and the launchers.  The kernels and their families are in gram_long_kernels.h; this unit builds every
 // kind but the Matern ones, which family_launch sends to gram_long_matern.hip, and launches with SIGSVGD_FLAG_EXACT_ADJOINT
 //  go to gram_long_exact.hip: the plans, the workspace and everything behind the kernel are the same.
+// Launches with SIGSVGD_FLAG_NORMALIZED are a short pipeline of their own, long2_norm_launch below.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -66,7 +67,10 @@ struct LongPlan : RingPlan {
     size_t wsk_bytes, partial_bytes, col_bytes = 0; // the forward scratch, the row-side slabs, the column-side slabs
     size_t len_bytes = 0; // SIGSVGD_FLAG_NAN_TAILS: the paths' lengths, ahead of the forward scratch
     bool log_k = false;   // SIGSVGD_FLAG_LOG_K: ring_log_plan's block exponents in LDS and scratch
-    size_t total() const { return ring_ws_total(len_bytes + wsk_bytes + partial_bytes + col_bytes); }
+    // SIGSVGD_FLAG_NORMALIZED: log_k, len_bytes holds the diagonals' logarithms, and behind the slabs
+    // come the diagonals' gradients and the weighted sums (long2_norm_plan)
+    size_t norm_bytes = 0;
+    size_t total() const { return ring_ws_total(len_bytes + wsk_bytes + partial_bytes + col_bytes + norm_bytes); }
 };
 
 // The grid of a launch of pl.items work items and its forward scratch: one wavefront per item up to what the device holds,
@@ -149,6 +153,38 @@ int long2_make_plan(int A, int B, int M, int N, int d, int n, bool want_row, boo
     const size_t rowslabs = yx ? (want_grad ? pl.nti + 1 : 0) : (want_row ? pl.nchunks : 0);
     pl.partial_bytes = (size_t)A * rowslabs * M * d * sizeof(double);
     pl.col_bytes = !yx && want_col ? (size_t)B * pl.nti * N * d * sizeof(double) : 0;
+    return SIGSVGD_OK;
+}
+
+// What a launch with SIGSVGD_FLAG_NORMALIZED adds to its two-sided plan `pl`.  dx, dy: the paired
+// log-domain plans of the diagonal passes (X_i, X_i) and, unless yx, (Y_j, Y_j), with the reverse sweep where that side's
+// gradient is wanted; their scratch aliases the launch's, which grows to the largest of the three.  Behind the slabs: the fp64
+// unit-weight gradients of the diagonal pairs, [A][TX][d] and [B][TY][d], then the weighted sums [A] and [B], each padded to
+// 256 B and only where its side's gradient is wanted; and at the head, before the logarithms, the pairs' weights U [A][B]
+// (norm_weights) of a gradient launch.  A forward-only launch adds neither.
+struct NormPlan {
+    LongPlan dx, dy;
+    size_t diagX_bytes = 0, diagY_bytes = 0, sumX_bytes = 0, sumY_bytes = 0;
+};
+int long2_norm_plan(const LongProblem &p, bool want_row, bool want_gradY, bool yx, Long2Plan &pl, NormPlan &np)
+{
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    np.dx.log_k = true;
+    int rc = pair_make_plan(p.A, p.TX, p.TX, p.d, p.n, want_row, np.dx);
+    if (rc) return rc;
+    pl.wsk_bytes = std::max(pl.wsk_bytes, np.dx.wsk_bytes);
+    if (!yx) {
+        np.dy.log_k = true;
+        rc = pair_make_plan(p.B, p.TY, p.TY, p.d, p.n, want_gradY, np.dy);
+        if (rc) return rc;
+        pl.wsk_bytes = std::max(pl.wsk_bytes, np.dy.wsk_bytes);
+    }
+    np.diagX_bytes = want_row ? pad((size_t)p.A * p.TX * p.d * sizeof(double)) : 0;
+    np.diagY_bytes = want_gradY ? pad((size_t)p.B * p.TY * p.d * sizeof(double)) : 0;
+    np.sumX_bytes = want_row ? pad((size_t)p.A * sizeof(double)) : 0;
+    np.sumY_bytes = want_gradY ? pad((size_t)p.B * sizeof(double)) : 0;
+    pl.norm_bytes = np.diagX_bytes + np.diagY_bytes + np.sumX_bytes + np.sumY_bytes;
+    if (want_row || want_gradY) pl.len_bytes += norm_weight_bytes(p.A, p.B); // (ahead of the logarithms: long_set_lengths)
     return SIGSVGD_OK;
 }
 
@@ -311,11 +347,24 @@ bool long_exact(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_EXACT_ADJ
 bool long_nan_tails(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NAN_TAILS) != 0; }
 // SIGSVGD_FLAG_LOG_K (the entry points refuse it with NAIVE_SOLVER, EXACT_ADJOINT and NAN_TAILS)
 bool long_log_k(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_LOG_K) != 0; }
+// SIGSVGD_FLAG_NORMALIZED (the two-sided entry points only, which refuse it with the four flags above)
+bool long_normalized(const LongProblem &p) { return (p.flags & SIGSVGD_FLAG_NORMALIZED) != 0; }
+// Which instantiations a launch runs (family_launch).  The flags behind the modes exclude each other: the entry points refuse
+// every pair of them, and an entry point that has no kernels of a mode refuses its flag, so any family may ask.
+enum class LongMode { Plain, Exact, NanTails, LogK, Normalized };
+LongMode long_mode(const LongProblem &p)
+{
+    return long_normalized(p) ? LongMode::Normalized
+           : long_log_k(p)    ? LongMode::LogK
+           : long_nan_tails(p) ? LongMode::NanTails
+           : long_exact(p)     ? LongMode::Exact
+                               : LongMode::Plain;
+}
 // what the plan of a launch takes from its flags, before it is made
 void long_set_lengths(const LongProblem &p, int nY, LongPlan &pl)
 {
-    pl.len_bytes = long_nan_tails(p) ? nan_tail_bytes(p.A, nY) : 0;
-    pl.log_k = long_log_k(p);
+    pl.len_bytes = long_nan_tails(p) ? nan_tail_bytes(p.A, nY) : long_normalized(p) ? norm_log_bytes(p.A, nY) : 0;
+    pl.log_k = long_log_k(p) || long_normalized(p);
 }
 int long_find_lengths(const LongProblem &p, int nY, const LongPlan &pl, const LongArgs &a)
 {
@@ -364,29 +413,37 @@ int bw_launch(int dtype, int kind, bool naive, const Plan &pl, hipStream_t strea
     if (e != hipSuccess) return hip_fail(e, F::launch_failed);
     return SIGSVGD_OK;
 }
-// the launch of family F: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's instantiations; `exact`
-// (long_exact below: a gradient launch with the default stencil): gram_long_exact.hip's, for every kind; `nan_tails`
-// (SIGSVGD_FLAG_NAN_TAILS, the paired and the two-sided family): gram_long_nantail.hip's, for every kind and both stencils;
-// `log_k` (SIGSVGD_FLAG_LOG_K, the same two families): gram_long_logk.hip's, for every kind
+// the launch of family F in mode `mode`.  Plain: ring_launch or bw_launch, and for the Matern kinds gram_long_matern.hip's
+// instantiations; Exact (long_exact above; it changes a gradient launch with the default stencil only):
+// gram_long_exact.hip's, for every kind; NanTails (SIGSVGD_FLAG_NAN_TAILS, the paired and the two-sided family):
+// gram_long_nantail.hip's, for every kind and both stencils; LogK (SIGSVGD_FLAG_LOG_K, the same two families):
+// gram_long_logk.hip's, for every kind; Normalized (SIGSVGD_FLAG_NORMALIZED, the same two): gram_long_norm.hip's, for every kind
 template <typename F, typename Plan>
 int family_launch(int dtype, int kind, bool naive, bool grad, const Plan &pl, hipStream_t stream, const typename F::Args &a,
-                  bool exact = false, bool nan_tails = false, bool log_k = false)
+                  LongMode mode = LongMode::Plain)
 {
-    if (log_k) { // (the entry points refuse it with the other two and with the first-order stencil)
+    if (mode == LongMode::Normalized) { // (the entry points refuse it with the other three and with the first-order stencil)
+        hipError_t e = long_norm_launch(F::id, dtype, kind, grad, pl.grid, pl.lds, stream, &a);
+        if (e != hipSuccess) return hip_fail(e, F::attr_failed);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, F::launch_failed);
+        return SIGSVGD_OK;
+    }
+    if (mode == LongMode::LogK) { // (the entry points refuse it with the other two and with the first-order stencil)
         hipError_t e = long_log_k_launch(F::id, dtype, kind, grad, pl.grid, pl.lds, stream, &a);
         if (e != hipSuccess) return hip_fail(e, F::attr_failed);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, F::launch_failed);
         return SIGSVGD_OK;
     }
-    if (nan_tails) { // (the entry points refuse it with the exact adjoint and on the families that have no such kernels)
+    if (mode == LongMode::NanTails) { // (the entry points refuse it with the exact adjoint and on families without such kernels)
         hipError_t e = long_nan_tail_launch(F::id, dtype, kind, naive, grad, pl.grid, pl.lds, stream, &a);
         if (e != hipSuccess) return hip_fail(e, F::attr_failed);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(e, F::launch_failed);
         return SIGSVGD_OK;
     }
-    if (exact && grad && !naive) {
+    if (mode == LongMode::Exact && grad && !naive) {
         hipError_t e = long_exact_launch(F::id, dtype, kind, pl.grid, pl.lds, stream, &a);
         if (e != hipSuccess) return hip_fail(e, F::attr_failed);
         e = hipGetLastError();
@@ -427,7 +484,10 @@ int long2_workspace(const LongProblem &p, int want_gradX, int want_gradY, size_t
 {
     return ring_plan_total<Long2Plan>(bytes, [&](Long2Plan &pl) {
         long_set_lengths(p, long_yx(p) ? 0 : p.B, pl);
-        return long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl);
+        int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_gradX != 0, want_gradY != 0, long_yx(p), pl);
+        NormPlan np;
+        if (!rc && long_normalized(p)) rc = long2_norm_plan(p, want_gradX != 0, want_gradY != 0, long_yx(p), pl, np);
+        return rc;
     });
 }
 // the two-sided bandwidth launch: the scratch also where neither coordinate gradient is wanted (the paired one's workspace is
@@ -462,7 +522,7 @@ int long_launch(const LongProblem &p)
     LongArgs a;
     int rc = long_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_grad, pl);
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
-    if (!rc) rc = family_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, long_exact(p));
+    if (!rc) rc = family_launch<LongFamily<false>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, long_mode(p));
     if (!rc && want_grad) // a row's slabs in chunk order
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, pl.nchunks, p.TX * p.d, 0, "launch long2_reduce_kernel (rows)");
     return rc;
@@ -528,8 +588,7 @@ int pair_launch(const LongProblem &p)
     a.gradX = p.gradX_out; a.gradY = p.gradY_out;
     rc = long_find_lengths(p, p.A, pl, a);
     if (rc) return rc;
-    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, exact, long_nan_tails(p),
-                                           long_log_k(p));
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, long_naive(p), want_grad, pl, p.stream, a, long_mode(p));
 }
 
 // The paired launch with the bandwidth derivative: dk_out[A] = dK_i / d inv_h.  Always the one-wavefront
@@ -542,7 +601,7 @@ int pair_h_launch(const LongProblem &p, void *dk_out)
     if (!rc) rc = long_args("pair", pl, p, 1, a);
     if (rc) return rc;
     a.gradX = p.gradX_out; a.gradY = p.gradY_out; a.dK_dinvh = dk_out;
-    return family_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_exact(p));
+    return family_launch<PairHFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_mode(p));
 }
 
 // The two-sided launch, with the bandwidth derivative where dk_out is given (dk_out[A][B] =
@@ -551,6 +610,51 @@ int pair_h_launch(const LongProblem &p, void *dk_out)
 // gradX_out and gradY_out both NULL: forward only.  Y_IS_X: A == B, TX == TY, no gradY_out; gradX_out then gets both sides of
 // every unordered pair.
 namespace {
+// The launch with SIGSVGD_FLAG_NORMALIZED on plan pl + np with the two-sided arguments a, all on the
+// caller's stream: the diagonal passes (the paired NormIO kernel on (X, X) and, unless yx, on (Y, Y): ln K unrounded to the head
+// of the workspace, the pairs' unit-weight gradients where wanted), the two-sided NormIO kernel (each pair solved once; K^ stored,
+// the slabs weighted by U = w K^, which it files too; yx: the diagonal pairs by 0), the row and column sums of U, and the slab
+// reductions that add -1/2 sum times the diagonal's gradient.
+int long2_norm_launch(const LongProblem &p, const Long2Plan &pl, const NormPlan &np, const Long2Args &a)
+{
+    const bool yx = long_yx(p), want_row = p.gradX_out != nullptr, want_gradY = p.gradY_out != nullptr;
+    unsigned char *scratch = reinterpret_cast<unsigned char *>(a.wsk);
+    double *lnA = reinterpret_cast<double *>(scratch - norm_log_bytes(p.A, yx ? 0 : p.B)), *lnB = lnA + p.A;
+    const double *U = reinterpret_cast<const double *>(scratch - pl.len_bytes); // (gradient launches: norm_weights)
+    unsigned char *tail = scratch + pl.wsk_bytes + pl.partial_bytes + pl.col_bytes;
+    double *diagX = reinterpret_cast<double *>(tail), *diagY = reinterpret_cast<double *>(tail + np.diagX_bytes);
+    double *sumX = reinterpret_cast<double *>(tail + np.diagX_bytes + np.diagY_bytes);
+    double *sumY = reinterpret_cast<double *>(tail + np.diagX_bytes + np.diagY_bytes + np.sumX_bytes);
+    // a diagonal pass: `rows` paths of T points in both slots, on the launch's scratch
+    auto diagonal = [&](const LongPlan &dp, const void *paths, int rows, int T, double *ln_out, double *grad) {
+        LongProblem q = p;
+        q.X = q.Y = paths; q.A = rows; q.TX = q.TY = T; q.grad_out = nullptr; q.K_out = ln_out;
+        PairArgs da;
+        const int rc = long_args("gram_long", dp, q, 1, da);
+        if (rc) return rc;
+        da.wsk = a.wsk; // (not the head of the workspace, where the logarithms are)
+        da.gradX = grad; da.gradY = nullptr;
+        return family_launch<LongFamily<true>>(p.dtype, p.kind, false, grad != nullptr, dp, p.stream, da, LongMode::Normalized);
+    };
+    int rc = diagonal(np.dx, p.X, p.A, p.TX, lnA, want_row ? diagX : nullptr);
+    if (!rc && !yx) rc = diagonal(np.dy, p.Y, p.B, p.TY, lnB, want_gradY ? diagY : nullptr);
+    if (!rc)
+        rc = family_launch<Long2Family>(p.dtype, p.kind, false, a.want_row || a.want_col, pl, p.stream, a, LongMode::Normalized);
+    if (rc || (!want_row && !want_gradY)) return rc;
+    hipError_t e = long_norm_sums(U, p.A, p.B, want_row ? sumX : nullptr, want_gradY ? sumY : nullptr, p.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch long_norm_sums_kernel");
+    if (want_row) { // yx: a row's nti + 1 slabs, column side first
+        e = long_norm_reduce(p.dtype, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0, sumX,
+                             diagX, p.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch long_norm_reduce_kernel (rows)");
+    }
+    if (want_gradY) {
+        e = long_norm_reduce(p.dtype, a.colpart, p.gradY_out, p.B, pl.nti, p.TY * p.d, 0, sumY, diagY, p.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch long_norm_reduce_kernel (columns)");
+    }
+    return SIGSVGD_OK;
+}
+
 template <bool BW>
 int long2_launch_any(const LongProblem &p, void *dk_out)
 {
@@ -559,18 +663,24 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
     std::conditional_t<BW, Long2HArgs, Long2Args> a;
     long_set_lengths(p, yx ? 0 : p.B, pl); // (BW: the entry points refuse the flag)
     int rc = long2_make_plan(p.A, p.B, p.TX, p.TY, p.d, p.n, want_row, p.gradY_out != nullptr, yx, pl, BW);
+    [[maybe_unused]] NormPlan np;
+    if constexpr (!BW) {
+        if (!rc && long_normalized(p)) rc = long2_norm_plan(p, want_row, p.gradY_out != nullptr, yx, pl, np);
+    }
     if (!rc) rc = long_args("gram_long", pl, p, p.B, a);
     if (rc) return rc;
     a.colpart = long_colpart(pl, a);
     a.IC = pl.IC; a.nti = pl.nti; a.yx = yx ? 1 : 0; a.want_row = want_row ? 1 : 0; a.want_col = want_col ? 1 : 0;
+    if constexpr (!BW) {
+        if (long_normalized(p)) return long2_norm_launch(p, pl, np, a);
+    }
     if constexpr (BW) {
         a.dK_dinvh = dk_out;
-        rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_exact(p));
+        rc = family_launch<Long2HFamily>(p.dtype, p.kind, long_naive(p), true, pl, p.stream, a, long_mode(p));
     } else {
         rc = long_find_lengths(p, yx ? 0 : p.B, pl, a);
         if (!rc)
-            rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_exact(p),
-                                            long_nan_tails(p), long_log_k(p));
+            rc = family_launch<Long2Family>(p.dtype, p.kind, long_naive(p), want_row || want_col, pl, p.stream, a, long_mode(p));
     }
     if (!rc && want_row) // yx: a row's nti + 1 slabs, column side first
         rc = long2_reduce(p, a.partials, p.gradX_out, p.A, yx ? pl.nti + 1 : pl.nchunks, p.TX * p.d, yx ? pl.IC : 0,

@@ -3,7 +3,8 @@
 // by gram_long_matern.hip (the Matern kinds' instantiations), by gram_long_exact.hip and gram_long_exact_matern.hip (the
 // exact adjoint's instantiations), by gram_long_nantail.hip and gram_long_nantail_matern.hip (the
 // instantiations for batches of paths of different lengths) and by gram_long_logk.hip and
-// gram_long_logk_matern.hip (the log-domain instantiations).
+// gram_long_logk_matern.hip (the log-domain instantiations), and by gram_long_norm.hip and
+// gram_long_norm_matern.hip (the normalised kernel's instantiations).
 //
 // Signature-kernel Gram matrix and gradient for the built-in static kernels on long paths.
 //
@@ -149,6 +150,9 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
     constexpr bool LOGK = RingIO<IOX>::log_k;   // (the same; K_out gets ln K, the gradients those of ln K)
     static_assert(!BW || (PAIRED && GRAD), "the bandwidth pass needs the paired mode's reverse sweep");
     static_assert(!NT || (PAIRED && !BW), "NaN-marked tails: the paired mode without the bandwidth pass");
+    // (the diagonal pass of a normalised launch, Y = X pair by pair; K_out is double[A] and gets ln K
+    // unrounded, gradX double[A][TX][d] and gets the pair's unit-weight gradient in both slots, gX + gY)
+    constexpr bool NORM = RingIO<IOX>::normalized;
     static_assert(!LOGK || (PAIRED && !BW), "the log-domain solve: the paired mode without the bandwidth pass");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
@@ -226,7 +230,11 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
 
             double Kval = ring_forward<NAIVE, GRAD, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
             if constexpr (LOGK) Kval = ring_log_finish(rp, Kval, lg); // ln K
-            if (((rp.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
+            if constexpr (NORM) {
+                if (((rp.P - 1) & (kWave - 1)) == lane) static_cast<double *>(a.K_out)[i] = Kval;
+            } else {
+                if (((rp.P - 1) & (kWave - 1)) == lane) static_cast<IO *>(a.K_out)[PAIRED ? (size_t)i : (size_t)i * a.B + j] = (IO)Kval;
+            }
             if (!GRAD) {
                 __syncthreads(); // (the next pair's first fill overwrites the ring, its sweep the boundary row)
                 continue;
@@ -240,7 +248,16 @@ __global__ __launch_bounds__(64) void gram_long_kernel(
             // ---- gradient: S -> dG (4-corner scatter) -> static-kernel derivative -> gX_i (and gY_i, paired) ---------------
             double w = GO ? (double)GO[PAIRED ? (size_t)i : (size_t)i * a.B + j] : 1.0;
             if (!PAIRED && a.sym) w += GO ? (double)GO[(size_t)j * a.B + i] : 1.0;
-            if constexpr (PAIRED) { // (either output skipped when NULL)
+            if constexpr (NORM) { // (M == N: a point's entry has the same lane in both passes, which adds to its own store)
+                double *gD = static_cast<double *>(a.gradX);
+                static_grad_pass<KIND, true>(rp, xi, Mp, yj, Np, d, a.inv_h, [&](int m, int c, double g) {
+                    gD[((size_t)i * M + m) * d + c] = g;
+                });
+                static_grad_pass<KIND, false>(rp, yj, Np, xi, Mp, d, a.inv_h, [&](int nn, int c, double g) {
+                    double *o = gD + ((size_t)i * N + nn) * d + c;
+                    *o += g;
+                });
+            } else if constexpr (PAIRED) { // (either output skipped when NULL)
                 IO *gX = static_cast<IO *>(a.gradX), *gY = static_cast<IO *>(a.gradY);
                 if (gX)
                     static_grad_pass<KIND, true>(rp, xi, Mp, yj, Np, d, a.inv_h, [&](int m, int c, double g) {
@@ -284,6 +301,8 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
     static_assert(!BW || GRAD, "the bandwidth pass needs the reverse sweep");
     static_assert(!NT || !BW, "NaN-marked tails: no bandwidth pass");
     static_assert(!LOGK || !BW, "the log-domain solve: no bandwidth pass");
+    // (the log-domain solve, then K_out gets K^ = exp(ln K - (a_i + b_j) / 2) and the pair's weight K^ too)
+    constexpr bool NORM = RingIO<IOX>::normalized;
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int lane = threadIdx.x;
     const int M = a.M, N = a.N, W = a.W, nrow = a.nrow, d = a.d;
@@ -291,6 +310,11 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
     double *ring = rw.ring;
     double *xs = rw.dump + kWave; // [nrow + 1][d]: points a0 .. a0 + nrow of X_i (clamped to M - 1)
     const IO *GO = static_cast<const IO *>(a.grad_out);
+    [[maybe_unused]] const double *lnA = nullptr, *lnB = nullptr;
+    if constexpr (NORM) { // (yx: one array serves both slots)
+        lnA = norm_logs(a.wsk, a.A, a.yx ? 0 : a.B);
+        lnB = a.yx ? lnA : lnA + a.A;
+    }
     [[maybe_unused]] const int *lenX = nullptr, *lenY = nullptr;
     if constexpr (NT) { // (yx: one array serves both slots)
         lenX = nan_tail_lengths(a.wsk, a.A, a.yx ? 0 : a.B);
@@ -376,6 +400,7 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
 
                 double Kval = ring_forward<NAIVE, GRAD, EXACT, LOGK>(rp, fill, stage_x, LOGK ? &lg : nullptr);
                 if constexpr (LOGK) Kval = ring_log_finish(rp, Kval, lg); // ln K
+                if constexpr (NORM) Kval = exp64(Kval - (0.5 * lnA[i] + 0.5 * lnB[j])); // K^, fp64 until the store rounds it
                 if (((rp.P - 1) & (kWave - 1)) == lane) {
                     static_cast<IO *>(a.K_out)[(size_t)i * a.B + j] = (IO)Kval;
                     if (a.yx) static_cast<IO *>(a.K_out)[(size_t)j * a.B + i] = (IO)Kval; // the mirror: same bits
@@ -398,6 +423,18 @@ __global__ __launch_bounds__(64) void gram_long2_kernel(std::conditional_t<BW, L
                         w = wc = w + wt;
                     else
                         wc = wt; // yx: the column side is d k(X_j, X_i) / d X_j
+                }
+                if constexpr (NORM) { // the gradients behind S are those of ln K: times K^ they are K^'s at fixed diagonals
+                    // (yx: a diagonal pair's K^ is the constant 1.  Its two terms would cancel only to the fp32 rounding of the
+                    // stored S, so it is left out of both: weight 0 here and in long_norm_sums' row)
+                    const double u = a.yx && i == j ? 0.0 : Kval;
+                    w *= u;
+                    wc *= u;
+                    if (lane == 0) { // U for the sums of the diagonals' terms (yx: the column side's is row j's entry)
+                        double *U = norm_weights(a.wsk, a.A, a.yx ? 0 : a.B, a.A, a.B);
+                        U[(size_t)i * a.B + j] = w;
+                        if (a.yx) U[(size_t)j * a.B + i] = wc;
+                    }
                 }
                 // yx: row k's slabs are [nti + 1]: the column side's of tile rows 0 .. k / IC, then the row side's
                 const int TDx = M * d, TDy = N * d;
@@ -746,6 +783,27 @@ hipError_t log_k_launch_any(int family, int dtype, int kind, bool grad, int grid
     }
     return hipErrorInvalidValue;
 }
+// the families of launches with SIGSVGD_FLAG_NORMALIZED: the NormIO kernels (forward-only and gradient,
+// default stencil), the paired one for the diagonal pass and the two-sided one for the launch itself; launched as the LogIO ones
+struct PairNormFamily : LongFamily<true> {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long_kernel<NormIO<IO>, false, GRAD, KIND, true>; }
+};
+struct Long2NormFamily : Long2Family {
+    template <typename IO, bool NAIVE, bool GRAD, int KIND>
+    static constexpr auto kernel() { return &gram_long2_kernel<NormIO<IO>, false, GRAD, KIND>; }
+};
+template <int... KS>
+hipError_t norm_launch_any(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                           const void *args)
+{
+    const ExactPlan pl{grid, lds};
+    switch (family) {
+    case LongFamily<true>::id: return log_k_launch_family<PairNormFamily, KS...>(dtype, kind, grad, pl, stream, args);
+    case Long2Family::id: return log_k_launch_family<Long2NormFamily, KS...>(dtype, kind, grad, pl, stream, args);
+    }
+    return hipErrorInvalidValue;
+}
 struct PartFamily { // (always with the gradient)
     using Args = PartArgs;
     static constexpr bool has_kind = true, has_fwd_only = false, bandwidth = false;
@@ -786,5 +844,17 @@ hipError_t long_log_k_launch(int family, int dtype, int kind, bool grad, int gri
                              const void *args);
 hipError_t long_log_k_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
                                     const void *args);
+// gram_long_norm.hip: the launch of the paired or the two-sided family's NormIO instantiation for `kind`
+// (the Matern kinds from gram_long_norm_matern.hip), default stencil, and the two small kernels behind a normalised launch:
+// long_norm_sums: rowsum[i] = sum_j U_ij (where given) and colsum[j] = sum_i U_ij (where given) of the weights U [A][B] the
+// two-sided kernel stored (norm_weights); long_norm_reduce: out[k][e] = the sum of row k's slabs as long2_reduce_kernel
+// adds them, minus sums[k] / 2 times diag[k][e], rounded once.  gram_long.hip calls them.
+hipError_t long_norm_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                            const void *args);
+hipError_t long_norm_matern_launch(int family, int dtype, int kind, bool grad, int grid, size_t lds, hipStream_t stream,
+                                   const void *args);
+hipError_t long_norm_sums(const double *U, int A, int B, double *rowsum, double *colsum, hipStream_t stream);
+hipError_t long_norm_reduce(int dtype, const double *partials, void *out, int rows, int nslabs, int TD, int skip,
+                            const double *sums, const double *diag, hipStream_t stream);
 
 } // namespace sigsvgd

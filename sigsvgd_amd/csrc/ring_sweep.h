@@ -21,6 +21,9 @@ namespace sigsvgd {
 // path's length (nan_tail_lengths below) and solve each pair on its own grid; the sweeps are the unflagged ones.
 // The log-domain solve again: LogIO<float> / LogIO<double>.  Its sweeps carry a running power-of-two
 // scale (ring_forward / ring_reverse with LOG), the kernels store ln K and file the S partials already divided by K.
+// The normalised kernel once more: NormIO<float> / NormIO<double>, log_k as well, so the sweeps are LogIO's.
+// Behind ring_log_finish the two-sided kernel forms K^ = exp(ln K - (a_i + b_j) / 2) from the diagonals' logarithms (norm_logs
+// below), stores it and weights the pair's gradient by it; the paired kernel is the diagonal pass that writes those logarithms.
 template <typename T>
 struct ExactIO {};
 template <typename T>
@@ -28,24 +31,31 @@ struct NanTailIO {};
 template <typename T>
 struct LogIO {};
 template <typename T>
+struct NormIO {};
+template <typename T>
 struct RingIO {
     using type = T;
-    static constexpr bool exact = false, nan_tails = false, log_k = false;
+    static constexpr bool exact = false, nan_tails = false, log_k = false, normalized = false;
 };
 template <typename T>
 struct RingIO<ExactIO<T>> {
     using type = T;
-    static constexpr bool exact = true, nan_tails = false, log_k = false;
+    static constexpr bool exact = true, nan_tails = false, log_k = false, normalized = false;
 };
 template <typename T>
 struct RingIO<NanTailIO<T>> {
     using type = T;
-    static constexpr bool exact = false, nan_tails = true, log_k = false;
+    static constexpr bool exact = false, nan_tails = true, log_k = false, normalized = false;
 };
 template <typename T>
 struct RingIO<LogIO<T>> {
     using type = T;
-    static constexpr bool exact = false, nan_tails = false, log_k = true;
+    static constexpr bool exact = false, nan_tails = false, log_k = true, normalized = false;
+};
+template <typename T>
+struct RingIO<NormIO<T>> {
+    using type = T;
+    static constexpr bool exact = false, nan_tails = false, log_k = true, normalized = true;
 };
 
 // The lengths of a launch with SIGSVGD_FLAG_NAN_TAILS: int lenX[nX], then int lenY[nY] (nY = 0 where Y is X: one array serves
@@ -58,6 +68,31 @@ __host__ __device__ inline size_t nan_tail_bytes(int nX, int nY)
 __device__ __forceinline__ const int *nan_tail_lengths(const float *wsk, int nX, int nY)
 {
     return reinterpret_cast<const int *>(reinterpret_cast<const unsigned char *>(wsk) - nan_tail_bytes(nX, nY));
+}
+
+
+// The diagonals' logarithms of a launch with SIGSVGD_FLAG_NORMALIZED: double a[nX] = ln K(X_i, X_i),
+// then double b[nY] = ln K(Y_j, Y_j) (nY = 0 where Y is X: one array serves both slots), padded to 256 B, at the head of the
+// workspace right before the forward scratch, where the lengths of a launch with NaN-marked tails are (the two flags exclude
+// each other).  The kernels find them from the scratch pointer they already have, so no argument struct changes.
+__host__ __device__ inline size_t norm_log_bytes(int nX, int nY)
+{
+    return (((size_t)nX + (size_t)nY) * sizeof(double) + 255) & ~(size_t)255;
+}
+__device__ __forceinline__ const double *norm_logs(const float *wsk, int nX, int nY)
+{
+    return reinterpret_cast<const double *>(reinterpret_cast<const unsigned char *>(wsk) - norm_log_bytes(nX, nY));
+}
+// A gradient launch keeps the pairs' weights U_ij = w_ij K^_ij too, double U[A][B] padded to 256 B right before the logarithms:
+// the two-sided kernel stores each as it forms it, in fp64 (a K^ below the I/O type's range still counts under a large w), and
+// long_norm_sums adds the rows and columns.
+__host__ __device__ inline size_t norm_weight_bytes(int A, int B)
+{
+    return ((size_t)A * (size_t)B * sizeof(double) + 255) & ~(size_t)255;
+}
+__device__ __forceinline__ double *norm_weights(float *wsk, int nX, int nY, int A, int B)
+{
+    return reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(wsk) - norm_log_bytes(nX, nY) - norm_weight_bytes(A, B));
 }
 
 namespace {

@@ -153,17 +153,21 @@ class SignatureKernel:
     (not a truncation level).  static_kernel: None or "rbf" (the reference's RBF), "imq", "rq", "matern32", "matern52" (each built on
     `bandwidth_fn`), or a static-kernel instance, used as it is.  fp32_sweeps: `SigKernel`'s (the IMQ and rational-quadratic kernels
     on the register-resident fp32-sweep kernel at order 0, T <= 64).  exact_grad: `SigKernel`'s (every gradient the exact derivative of
-    the discrete kernel, on the long route).  Unknown keyword arguments are accepted and ignored, as in
+    the discrete kernel, on the long route).  normalize: `SigKernel`'s (the normalised kernel
+    K(x, y) / sqrt(K(x, x) K(y, y)) from the long route's log-domain launches: `__call__` through `compute_Gram`, `gram_and_grad` --
+    and with it `SVGD` and `ScoreEstimator` -- from one launch with SIGSVGD_FLAG_NORMALIZED).  Unknown
+    keyword arguments are accepted and ignored, as in
     the reference (examples/script_planning_robot.py:391 passes `bandwidth=`)."""
 
     def __init__(self, bandwidth_fn: scalar_function = None, depth: int = 3, static_kernel=None, fp32_sweeps: bool = False,
-                 exact_grad: bool = False, **kwargs):
+                 exact_grad: bool = False, normalize: bool = False, **kwargs):
         if static_kernel is None or isinstance(static_kernel, str):
             name = "rbf" if static_kernel is None else static_kernel.lower()
             if name not in _STATIC_BY_NAME:
                 raise ValueError(f'static_kernel must be one of {sorted(_STATIC_BY_NAME)} or an instance, got {static_kernel!r}')
             static_kernel = _STATIC_BY_NAME[name](bandwidth_fn=bandwidth_fn)
-        self.kernel = SigKernel(static_kernel, dyadic_order=depth, fp32_sweeps=fp32_sweeps, exact_grad=exact_grad)
+        self.kernel = SigKernel(static_kernel, dyadic_order=depth, fp32_sweeps=fp32_sweeps, exact_grad=exact_grad,
+                                normalize=normalize)
 
     def __call__(self, X, Y, **kwargs):
         # The reference upcasts to fp64 around compute_Gram and casts K back; the HIP kernels read fp32/fp64 paths

@@ -133,8 +133,11 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
 
 
 def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
-           fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False) -> int:
+           fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False,
+           normalized: bool = False) -> int:
     f = 0
+    if normalized:
+        f |= _lib.FLAG_NORMALIZED
     if log_k:
         f |= _lib.FLAG_LOG_K
     if nan_tails:
@@ -280,22 +283,24 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
 
 def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                      want_gradX: bool = True, want_gradY: bool = True, y_is_x: bool = False,
-                     exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False) -> bool:
+                     exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False,
+                     normalized: bool = False) -> bool:
     """Whether `gram_long_fwd_bwd2` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
-    state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either); any other error raises."""
+    state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either; normalized together with any of
+    the three); any other error raises."""
     return _query("gram_long2_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
                                                  1 if want_gradX else 0, 1 if want_gradY else 0,
                                                  _flags(False, False, y_is_x, False, exact_adjoint=exact_adjoint,
-                                                        nan_tails=nan_tails, log_k=log_k)),
+                                                        nan_tails=nan_tails, log_k=log_k, normalized=normalized)),
                   (ctypes.c_size_t(0),), may_refuse=True)
 
 
 def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                        grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
                        y_is_x: bool = False, want_gradX: bool = True, want_gradY: bool = True,
-                       exact_adjoint: bool = False, nan_tails: bool = False,
-                       log_k: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
+                       exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False,
+                       normalized: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]:
     """(K[A,B], gX[A,TX,d] or None, gY[B,TY,d] or None) on the long route from one solve per pair
     (`sigsvgd_gram_long_fwd_bwd2`): gX = d sum(grad_out*K)/dX and gY = d sum(grad_out*K)/dY, each its own slot (grad_out
     None = ones), K bit-identical to `gram_long_fwd`.  y_is_x (Y holds X's values; A == B, TX == TY): each unordered pair is
@@ -306,7 +311,12 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
     its own grid, and the gradient rows from a path's end on are exact zeros.  log_k (SIGSVGD_FLAG_LOG_K, DESIGN.md section
     5.21; here and on the paired launches below): the first result is ln K and the gradients are those of sum(grad_out * ln K),
     from sweeps that carry a running power-of-two scale, so nothing overflows while ln K itself is representable; a pair
-    whose discrete K is <= 0 gives NaN.  Default stencil only, not with exact_adjoint or nan_tails."""
+    whose discrete K is <= 0 gives NaN.  Default stencil only, not with exact_adjoint or nan_tails.  normalized
+    (SIGSVGD_FLAG_NORMALIZED; this launch only): the first result is the normalised kernel
+    K^_ij = K(X_i, Y_j) / sqrt(K(X_i, X_i) K(Y_j, Y_j)), formed in the log domain, and the gradients are those of
+    sum(grad_out * K^), the diagonals' dependence included, each slot its own; with y_is_x gX is the gradient in X_i of
+    sum_j grad_out_ij K^(X_i, Y_j) at fixed Y = X (SVGD's), and K^'s diagonal is exactly 1.  Every pair is solved once.  Not
+    with naive, exact_adjoint, nan_tails or log_k."""
     dev = _require_gpu(X, Y, grad_out)
     Xc, Yc = _prep_long(X, Y)
     (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
@@ -314,7 +324,8 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
         raise ValueError("sym and y_is_x need X and Y of one shape")
     want_gradY = bool(want_gradY) and not (sym or y_is_x)
     go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
+    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k,
+                   normalized=normalized)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
     gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None

@@ -798,7 +798,10 @@ class SigKernel:
     about 300 points and fp64 from about 1600).  Whatever the shape, these calls run on the long route at its fp64 cost, as
     exact_grad=True does; shapes it refuses, `lengths_*`, exact_grad=True, `_naive_solver=True`, a sigma that requires grad and
     user static kernels raise NotImplementedError, fp32_sweeps=True ValueError.  `compute_log_Gram` and `compute_log_kernel`
-    return ln K itself (with any value of normalize); `gram_and_grad` is not normalised."""
+    return ln K itself (with any value of normalize).  `gram_and_grad` with normalize=True returns the
+    normalised Gram matrix and the gradient of sum(grad_out * K^) in X from exactly one launch of the long route
+    (`ops.gram_long_fwd_bwd2(..., normalized=True)`, SIGSVGD_FLAG_NORMALIZED: each pair solved once), whatever the shape; with
+    Y None that is the gradient at fixed second slot, which SVGD uses.  The same refusals."""
 
     def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False,
                  exact_grad: bool = False, normalize: bool = False):
@@ -1023,11 +1026,24 @@ class SigKernel:
         """One fused launch: (K, d sum(grad_out*K)/dX) with detached tensors.  Equivalent to
         `K = compute_Gram(X, Y); g = autograd.grad((grad_out*K).sum(), X)` (score.py:68-69)."""
         Yv = X if Y is None else Y
+        if self.normalize:
+            return self._normalized_gram_and_grad(X, Yv, grad_out, sym, Y is None)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
         if static_kind is None:
             return self._user_gram_and_grad(X, Yv, grad_out, sym)
         cfg = (static_kind, inv_h, self.dyadic_order, self._naive_solver, sym, Y is None, self.fp32_sweeps, self.exact_grad)
         return _solve_gram(X, Yv, cfg, grad_out, True, False, True)[:2]
+
+    def _normalized_gram_and_grad(self, X, Y, grad_out, sym, y_is_x):
+        """gram_and_grad with normalize=True: (K^, d sum(grad_out * K^) / dX, first slot) from one
+        launch with SIGSVGD_FLAG_NORMALIZED on the long route, whatever the shape; `_log_static`'s refusals"""
+        static_kind, inv_h = self._log_static("gram_and_grad", X, Y)
+        if not ops.gram_long2_takes(X.shape[0], Y.shape[0], X.shape[1], Y.shape[1], X.shape[2], self.dyadic_order, static_kind,
+                                    True, False, y_is_x, normalized=True):
+            raise _refused("gram_and_grad", X, Y, self.dyadic_order, "the normalised kernel")
+        go = None if grad_out is None else grad_out.detach()
+        return ops.gram_long_fwd_bwd2(X, Y, inv_h, self.dyadic_order, static_kind, go, False, bool(sym), y_is_x, True, False,
+                                      normalized=True)[:2]
 
     def _user_gram_and_grad(self, X, Y, grad_out, sym):
         """gram_and_grad for a user static kernel: its grid (with the graph to X), K and dG from one PDE launch, and dG
