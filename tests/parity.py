@@ -18,6 +18,12 @@ def sized_walks(rng, B, T, d, scale=1.0):
     return np.cumsum(scale / np.sqrt(T) * rng.standard_normal((B, T, d)), axis=1).astype(np.float32)
 
 
+def bounded_points(seed, A, T, d, sd):
+    """[A, T, d] fp32 paths of independent points `sd` * N(0, 1) from `seed`: bounded, so a static kernel of bandwidth 1 never
+    decays along the path, and rough, so the signature kernel still grows (tests/long_reference.py)"""
+    return (sd * np.random.default_rng(seed).standard_normal((A, T, d))).astype(np.float32)
+
+
 def signed_weights(A, B, seed):
     """grad_out with every entry of the same order and random sign: w = s u, s = +-1, u uniform in [0.5, 1.5] -- no pair
     is hidden behind a weight near zero"""

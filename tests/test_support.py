@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from parity import rel_entry, rel_max, sized_walks, walks
+from parity import bounded_points, rel_entry, rel_max, sized_walks, walks
 
 
 def test_rel_entry_floors():
@@ -67,6 +67,20 @@ def test_sized_walks_are_the_values_the_tolerances_were_validated_on():
     assert Y[0, 0, 0] == np.float32(0.0006150766857899725) and Y[1, 3, 1] == np.float32(-0.24937637150287628)
     # `scale` multiplies the steps before the sum: a power of two commutes with every rounding
     assert sized_walks(np.random.default_rng(7), 2, 4, 2, 2.0).tobytes() == (2 * Y).tobytes()
+
+
+# printed by `bounded_points(7, 2, 4, 2, 0.5)` on the commit that added it (tests/long_reference.py chose its seeds on these values)
+BOUNDED_POINTS_SEED7_2_4_2 = ("193d213a2df5183ecc5b0cbed4fde3be9cca68be8cdcfdbe2359f63c2c8c2b3f"
+                              "7e027cbe71d79ebe94cc7a3ee5b9363e6de3573d2733eebe85a16fbc64ffb13e")
+
+
+def test_bounded_points_are_the_values_the_tolerances_were_validated_on():
+    Z = bounded_points(7, 2, 4, 2, 0.5)
+    assert Z.dtype == np.float32 and Z.shape == (2, 4, 2)
+    assert Z.tobytes().hex() == BOUNDED_POINTS_SEED7_2_4_2
+    assert Z[1, 3, 1] == np.float32(0.5 * np.random.default_rng(7).standard_normal((2, 4, 2))[1, 3, 1])
+    # independent points, not a walk: `sd` multiplies each point, and a power of two commutes with the rounding
+    assert bounded_points(7, 2, 4, 2, 1.0).tobytes() == (2 * Z).tobytes()
 
 
 # ---- tests/guarded_workspace.py on CPU tensors: a detector that cannot fail proves nothing ---------------------------------
