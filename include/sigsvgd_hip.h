@@ -228,6 +228,40 @@ extern "C" {
                                       /* SIGSVGD_FLAG_EXACT_ADJOINT, SIGSVGD_FLAG_NAN_TAILS or SIGSVGD_FLAG_LOG_K is set too.  Every other      */
                                       /* entry point treats it as the unknown bit it was.  A later revision of ABI 10: no new symbol, no        */
                                       /* changed signature; an earlier library answers SIGSVGD_E_BADARG                                         */
+#define SIGSVGD_FLAG_NORMALIZED_FUSED 4096u /* normalised signature kernel and its first-slot gradient on the fused Gram route (DESIGN.md */
+                                      /* section 5.23): sigsvgd_gram_fwd, sigsvgd_gram_fwd_bwd and sigsvgd_gram_workspace_bytes (bit 2048  */
+                                      /* stays the ignored bit it always was there).  SIGSVGD_FLAG_NORMALIZED's semantics restricted to    */
+                                      /* what this route has, one T for both batches and the first-slot gradient: a_i = ln K(X_i, X_i) and */
+                                      /* b_j = ln K(Y_j, Y_j) from the paired log-domain solve (fp64, unrounded), s_ij = exp(-(a_i + b_j)  */
+                                      /* / 2) in fp64, K_out[i][j] = K_ij s_ij with K_ij what the unflagged launch of the same route       */
+                                      /* returns, the product formed in fp64 and rounded once to the I/O type; with SIGSVGD_FLAG_Y_IS_X     */
+                                      /* the diagonal is stored as exactly 1 and K_out stays bit-symmetric.  With w = grad_out (NULL:      */
+                                      /* ones; SIGSVGD_FLAG_SYM: w + w^T) and U = w * K^ entry by entry, in the GG convention               */
+                                      /*   gradX_out[i] = sum_j w_ij s_ij d1 K_ij - 1/2 (sum_j U_ij) grad a_i,                             */
+                                      /* grad a_i the derivative of ln K(X_i, X_i) in both slots; with Y_IS_X the diagonal pair is left    */
+                                      /* out of both terms (weight 0, U 0): its two terms would come from an fp32-sweep and an fp64 solve  */
+                                      /* and cancel to 1e-5 of |grad a_i| only.  Pipeline, all on the caller's stream without host         */
+                                      /* synchronisation or allocation (capturable): the diagonal pass of SIGSVGD_FLAG_NORMALIZED, a       */
+                                      /* kernel that writes W' = (I/O type)(w s) (always, also for grad_out == NULL; SYM applied there),   */
+                                      /* the unflagged launch with grad_out = W' on whatever route it takes -- no pair kernel differs, and */
+                                      /* SIGSVGD_FLAG_FORCE_GENERIC and SIGSVGD_FLAG_FP32_SWEEPS mean what they mean without the bit --,   */
+                                      /* and one wavefront per row that scales K_out in place, adds U_i in fp64 in a fixed order (no       */
+                                      /* atomics: two runs give the same bits) and adds the diagonal term to gradX_out in one fma per      */
+                                      /* entry.  The accuracy is the unflagged route's: K^ per entry as K, the gradient within that        */
+                                      /* route's bound of max|first term| + max|second term|.  Defined where K(X_i, X_i) and K(Y_j, Y_j)   */
+                                      /* fit the I/O type, as the unflagged launch's K_out is (a 64-point walk's is 1e7 .. 1e12); past     */
+                                      /* that use SIGSVGD_FLAG_NORMALIZED on the long route.  A diagonal K <= 0 gives NaN in its row or    */
+                                      /* column.  All six static kinds, both dtypes, every dyadic order and route of these entry points.  */
+                                      /* Workspace: the unflagged query's bytes plus the logarithms (8 (A + B) bytes, 8 A with Y_IS_X),    */
+                                      /* the diagonal pass's scratch (sigsvgd_pair_workspace_bytes with SIGSVGD_FLAG_LOG_K) and, for a     */
+                                      /* gradient launch, W' [A][B] (sized for fp64 I/O: the query has no dtype), the fp64 diagonal        */
+                                      /* gradients [A][T][d] and the sums [A]; each padded to 256 B; never less than the unflagged         */
+                                      /* query's.  A shape whose diagonal pass the paired plan refuses is refused as a whole, with that    */
+                                      /* plan's message, and every refusal comes before any device work.  SIGSVGD_E_UNSUPPORTED with       */
+                                      /* SIGSVGD_FLAG_NAIVE_SOLVER (the diagonal pass has the default stencil only) and from               */
+                                      /* sigsvgd_gram_sym_partial; SIGSVGD_FLAG_EXACT_ADJOINT keeps its answer.  Every other entry point   */
+                                      /* treats it as the unknown bit it is.  A later revision of ABI 10: no new symbol, no changed        */
+                                      /* signature; an earlier library ignores the bit here and returns the unnormalised K                 */
 #define SIGSVGD_FLAG_FORCE_GENERIC 8u /* use the coverage kernel: fp64 end to end (every entry of K is the fp64 reference's up to */
                                       /* the store in `dtype`, in any regime): whole-grid fp64 tables where they fit LDS, per-band */
                                       /* fp64 increments beyond that (dyadic order 0, T <= ~200); one wavefront per pair; tests,   */

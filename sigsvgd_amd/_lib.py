@@ -19,7 +19,7 @@ SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hi
            "gram_band.hip", "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
            "pair_bands_matern.hip", "sqdist_select.hip", "sig_pde_exact.hip", "gram_long_exact.hip",
            "gram_long_exact_matern.hip", "gram_long_nantail.hip", "gram_long_nantail_matern.hip", "gram_long_logk.hip",
-           "gram_long_logk_matern.hip", "gram_long_norm.hip", "gram_long_norm_matern.hip"]
+           "gram_long_logk_matern.hip", "gram_long_norm.hip", "gram_long_norm_matern.hip", "gram_norm_fused.hip"]
 # every header of csrc/ (a source includes headers only), then the public header, which stays the last element
 HEADERS = [os.path.join(_CSRC, h) for h in ("sig_common.h", "quad_sweeps.h", "ring_sweep.h", "long_static.h", "pair_bands.h",
                                             "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h",
@@ -37,6 +37,7 @@ FLAG_EXACT_ADJOINT = 256
 FLAG_NAN_TAILS = 512
 FLAG_LOG_K = 1024
 FLAG_NORMALIZED = 2048
+FLAG_NORMALIZED_FUSED = 4096
 VEC_GAUSSIAN, VEC_IMQ, VEC_UNIT = 0, 1, 2
 E_BADARG, E_UNSUPPORTED, E_WORKSPACE, E_HIP = -1, -2, -3, -4
 ABI_VERSION = 10

@@ -77,6 +77,14 @@ int long2_h_launch(const LongProblem &p, void *dk_out);
 int long_part_tiles(const LongProblem &p, int stride, int *R, int *JC);
 int long_part_workspace(const LongProblem &p, int off, int stride, size_t *bytes);
 int long_part_launch(const LongProblem &p, int off, int stride);
+// the fused route's normalised launch: the diagonal pass (gram_long.hip) and the two kernels around
+// the pair solve (gram_norm_fused.hip)
+int norm_diag_workspace(int rows, int T, int d, int n, int want_grad, size_t *bytes);
+int norm_diag_launch(const LongProblem &p, double *ln_out, double *grad);
+hipError_t norm_fused_weights(int dtype, const void *go, const double *lnA, const double *lnB, void *W, int A, int B, bool sym,
+                              bool yx, hipStream_t stream);
+hipError_t norm_fused_finish(int dtype, void *K, const void *go, const double *lnA, const double *lnB, int A, int B, bool sym,
+                             bool yx, void *gradX, const double *diag, double *sums, int TD, hipStream_t stream);
 // the distance select (sqdist_select.hip)
 size_t select_workspace_bytes();
 int select_launch(const void *X, const void *Y, int A, int B, int TX, int TY, int d, int dtype, unsigned flags,
@@ -453,6 +461,118 @@ static int dispatch(const GramProblem &p)
     return SIGSVGD_E_BADARG;
 }
 
+// The bytes sigsvgd_gram_workspace_bytes reports for launches without SIGSVGD_FLAG_NORMALIZED_FUSED: the largest plan of the
+// launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B the symmetric launch and --
+// gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch and, when A == B, the symmetric one.
+static int gram_workspace(int A, int B, int T, int d, int n, int kind, int want_grad, unsigned flags, size_t *bytes)
+{
+    size_t most = 0;
+    auto cover = [&](bool sym, bool partial) {
+        const unsigned f = sym ? flags | SIGSVGD_FLAG_Y_IS_X : flags & ~SIGSVGD_FLAG_Y_IS_X;
+        const GramRoute r = gram_route(A, B, T, d, n, kind, f, want_grad, partial);
+        if (partial && r != GramRoute::Fast && r != GramRoute::Quad) return (int)SIGSVGD_OK; // (not a partial-solve shape)
+        WsPlan w;
+        const int rc = route_plan(r, A, B, T, d, n, kind, want_grad, sym, w);
+        if (w.total() > most) most = w.total();
+        return rc;
+    };
+    const bool yx = (flags & SIGSVGD_FLAG_Y_IS_X) && A == B;
+    int rc = cover(yx, false);
+    if (!rc && !yx && A == B) rc = cover(true, false);
+    if (!rc && yx && want_grad) rc = cover(true, true);
+    if (rc) return rc;
+    *bytes = most;
+    return SIGSVGD_OK;
+}
+
+// ---- SIGSVGD_FLAG_NORMALIZED_FUSED: the normalised kernel around an unchanged fused launch ---------
+// The bit with SIGSVGD_FLAG_NAIVE_SOLVER: refused before any device work (the diagonal pass is the log-domain solve of the
+// default stencil only, and K^'s diagonal would not be 1 under two stencils)
+static int check_norm_fused(const char *who, unsigned flags)
+{
+    if (!(flags & SIGSVGD_FLAG_NORMALIZED_FUSED) || !(flags & SIGSVGD_FLAG_NAIVE_SOLVER)) return SIGSVGD_OK;
+    set_error("%s: SIGSVGD_FLAG_NORMALIZED_FUSED together with SIGSVGD_FLAG_NAIVE_SOLVER is not built (the diagonal pass is the "
+              "log-domain solve of the default stencil)", who);
+    return SIGSVGD_E_UNSUPPORTED;
+}
+
+// The workspace of such a launch, from its 256-B aligned base: the unflagged launch's whole workspace (what gram_workspace
+// reports for the flags without the bit), the diagonals' logarithms double[A] and, unless yx, double[B], the diagonal pass's
+// scratch (the larger of the two passes'), and for a gradient launch the weights W' [A][B] (sized for fp64 I/O: the query has
+// no dtype), the fp64 diagonal gradients [A][T][d] and the sums [A]; each padded to 256 B, then the slack of aligning.
+struct NormFusedPlan {
+    size_t inner = 0, logs = 0, scratch = 0, weights = 0, diag = 0, sums = 0;
+    size_t total() const { return inner + logs + scratch + weights + diag + sums + 256; }
+};
+static int norm_fused_plan(int A, int B, int T, int d, int n, int kind, int want_grad, unsigned flags, NormFusedPlan &np)
+{
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const bool yx = (flags & SIGSVGD_FLAG_Y_IS_X) && A == B;
+    size_t inner = 0, sx = 0, sy = 0;
+    int rc = gram_workspace(A, B, T, d, n, kind, want_grad, flags & ~SIGSVGD_FLAG_NORMALIZED_FUSED, &inner);
+    if (!rc) rc = norm_diag_workspace(A, T, d, n, want_grad, &sx);
+    if (!rc && !yx) rc = norm_diag_workspace(B, T, d, n, 0, &sy);
+    if (rc) return rc;
+    np.inner = pad(inner);
+    np.logs = pad(((size_t)A + (yx ? 0 : (size_t)B)) * sizeof(double));
+    np.scratch = pad(sx > sy ? sx : sy);
+    if (want_grad) {
+        np.weights = pad((size_t)A * B * sizeof(double));
+        np.diag = pad((size_t)A * T * d * sizeof(double));
+        np.sums = pad((size_t)A * sizeof(double));
+    }
+    return SIGSVGD_OK;
+}
+
+// The launch, all on p's stream, no host synchronisation, no allocation: the diagonal pass on (X, X) -- with the gradient of
+// ln K(X_i, X_i) for a gradient launch -- and, unless yx, forward only on (Y, Y); W' = w s (SYM applied there: the inner
+// launch runs without the bit, s_ij is not s_ji between two batches); the unflagged launch dispatch(p) on whatever route
+// gram_route picks, with grad_out = W'; the finish kernel over K_out and gradX_out in place.  Every refusal -- the shape's, the
+// diagonal plan's, the workspace's -- comes from the plan, before any device work.
+static int gram_norm_fused(const GramProblem &p)
+{
+    const bool yx = (p.flags & SIGSVGD_FLAG_Y_IS_X) != 0, sym = (p.flags & SIGSVGD_FLAG_SYM) != 0;
+    const bool grad = p.gradX_out != nullptr;
+    if (yx && p.A != p.B) return bad_arg("gram_norm_fused: Y_IS_X needs A == B");
+    NormFusedPlan np;
+    int rc = norm_fused_plan(p.A, p.B, p.T, p.d, p.n, p.kind, grad, p.flags, np);
+    if (rc) return rc;
+    if (p.ws_bytes < np.total() || !p.ws) {
+        set_error("gram_norm_fused: workspace %zu B too small, required %zu B", p.ws_bytes, np.total());
+        return SIGSVGD_E_WORKSPACE;
+    }
+    unsigned char *base = reinterpret_cast<unsigned char *>((reinterpret_cast<uintptr_t>(p.ws) + 255) & ~(uintptr_t)255);
+    double *lnA = reinterpret_cast<double *>(base + np.inner), *lnB = yx ? lnA : lnA + p.A;
+    unsigned char *scratch = base + np.inner + np.logs;
+    void *W = scratch + np.scratch;
+    double *diag = reinterpret_cast<double *>(scratch + np.scratch + np.weights);
+    double *sums = reinterpret_cast<double *>(scratch + np.scratch + np.weights + np.diag);
+
+    LongProblem q{p.X, p.X, p.A, 1, p.T, p.T, p.d, p.dtype, p.inv_h, p.n, p.kind, 0u, nullptr, nullptr, nullptr, nullptr,
+                  scratch, np.scratch, p.stream};
+    rc = norm_diag_launch(q, lnA, grad ? diag : nullptr);
+    if (!rc && !yx) {
+        q.X = q.Y = p.Y;
+        q.A = p.B;
+        rc = norm_diag_launch(q, lnB, nullptr);
+    }
+    if (rc) return rc;
+    GramProblem in = p;
+    in.flags &= ~(unsigned)(SIGSVGD_FLAG_NORMALIZED_FUSED | SIGSVGD_FLAG_SYM);
+    in.ws = base;
+    in.ws_bytes = np.inner;
+    if (grad) {
+        const hipError_t e = norm_fused_weights(p.dtype, p.grad_out, lnA, lnB, W, p.A, p.B, sym, yx, p.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch norm_fused_weights_kernel");
+        in.grad_out = W;
+    }
+    rc = dispatch(in);
+    if (rc) return rc;
+    const hipError_t e = norm_fused_finish(p.dtype, p.K_out, p.grad_out, lnA, lnB, p.A, p.B, sym, yx, p.gradX_out, diag, sums,
+                                           p.T * p.d, p.stream);
+    return e != hipSuccess ? hip_fail(e, "launch norm_fused_finish_kernel") : SIGSVGD_OK;
+}
+
 } // namespace sigsvgd
 
 using namespace sigsvgd;
@@ -469,25 +589,16 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     if (!static_kind_known(static_kind)) return bad_arg("bad static kernel kind %d", static_kind);
     if (no_exact_adjoint("gram_workspace_bytes", flags)) return SIGSVGD_E_UNSUPPORTED;
-    // The largest plan of the launches these arguments can reach (the rule of include/sigsvgd_hip.h): with Y_IS_X and A == B
-    // the symmetric launch and -- gradient queries -- the symmetric partial solve of the shape; otherwise the ordered launch
-    // and, when A == B, the symmetric one.
-    size_t most = 0;
-    auto cover = [&](bool sym, bool partial) {
-        const unsigned f = sym ? flags | SIGSVGD_FLAG_Y_IS_X : flags & ~SIGSVGD_FLAG_Y_IS_X;
-        const GramRoute r = gram_route(A, B, T, d, dyadic_order, static_kind, f, want_grad, partial);
-        if (partial && r != GramRoute::Fast && r != GramRoute::Quad) return (int)SIGSVGD_OK; // (not a partial-solve shape)
-        WsPlan w;
-        const int rc = route_plan(r, A, B, T, d, dyadic_order, static_kind, want_grad, sym, w);
-        if (w.total() > most) most = w.total();
-        return rc;
-    };
-    const bool yx = (flags & SIGSVGD_FLAG_Y_IS_X) && A == B;
-    int rc = cover(yx, false);
-    if (!rc && !yx && A == B) rc = cover(true, false);
-    if (!rc && yx && want_grad) rc = cover(true, true);
+    if (!(flags & SIGSVGD_FLAG_NORMALIZED_FUSED))
+        return gram_workspace(A, B, T, d, dyadic_order, static_kind, want_grad, flags, bytes);
+    if (check_norm_fused("gram_workspace_bytes", flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (A < 1 || B < 1 || T < 2 || d < 1 || dyadic_order < 0 || dyadic_order > 10)
+        return bad_arg("bad shape A=%d B=%d T=%d d=%d order %d (need A,B,d >= 1, T >= 2 and 0 <= order <= 10)", A, B, T, d,
+                       dyadic_order);
+    NormFusedPlan np;
+    const int rc = norm_fused_plan(A, B, T, d, dyadic_order, static_kind, want_grad ? 1 : 0, flags, np);
     if (rc) return rc;
-    *bytes = most;
+    *bytes = np.total();
     return SIGSVGD_OK;
 }
 
@@ -499,7 +610,9 @@ int sigsvgd_gram_fwd(const void *X, const void *Y, int A, int B, int T, int d, i
     if (rc) return rc;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr,
                   K_out, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    if (check_norm_fused("gram_fwd", flags)) return SIGSVGD_E_UNSUPPORTED;
     Range range("sigsvgd_gram_fwd");
+    if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) return gram_norm_fused(p);
     return dispatch(p);
 }
 
@@ -514,7 +627,9 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
     if (no_exact_adjoint("gram_fwd_bwd", flags)) return SIGSVGD_E_UNSUPPORTED;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out,
                   K_out, gradX_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    if (check_norm_fused("gram_fwd_bwd", flags)) return SIGSVGD_E_UNSUPPORTED;
     Range range("sigsvgd_gram_fwd_bwd");
+    if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) return gram_norm_fused(p);
     return dispatch(p);
 }
 
@@ -527,6 +642,11 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
     if (rc) return rc;
     if (!grad_partial) return bad_arg("grad_partial == NULL");
     if (no_exact_adjoint("sym_partial", flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) {
+        set_error("sym_partial: SIGSVGD_FLAG_NORMALIZED_FUSED is not built for the partial solve (sigsvgd_gram_fwd, "
+                  "sigsvgd_gram_fwd_bwd and sigsvgd_gram_workspace_bytes take it)");
+        return SIGSVGD_E_UNSUPPORTED;
+    }
     GramProblem p{X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags | SIGSVGD_FLAG_Y_IS_X, grad_out,
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     const GramRoute r = gram_route(p, true);

@@ -2,7 +2,8 @@
 // the workspace queries and the launchers.  The kernels and their families are in gram_long_kernels.h; this unit builds every
 // kind but the Matern ones, which family_launch sends to gram_long_matern.hip, and launches with SIGSVGD_FLAG_EXACT_ADJOINT
 //  go to gram_long_exact.hip: the plans, the workspace and everything behind the kernel are the same.
-// Launches with SIGSVGD_FLAG_NORMALIZED are a short pipeline of their own, long2_norm_launch below.
+// Launches with SIGSVGD_FLAG_NORMALIZED are a short pipeline of their own, long2_norm_launch below; its
+// diagonal pass, norm_diagonal_pass, also serves the fused Gram route's SIGSVGD_FLAG_NORMALIZED_FUSED (section 5.23; norm_diag_launch).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -610,6 +611,23 @@ int pair_h_launch(const LongProblem &p, void *dk_out)
 // gradX_out and gradY_out both NULL: forward only.  Y_IS_X: A == B, TX == TY, no gradY_out; gradX_out then gets both sides of
 // every unordered pair.
 namespace {
+// A diagonal pass of a normalised launch (DESIGN.md sections 5.22, 5.23): `rows` paths of T points in both slots on the paired
+// log-domain plan dp, the paired NormIO kernel on problem p's stream with its dtype, kind, order and bandwidth.  ln_out[rows] gets
+// ln K(x, x) unrounded, grad[rows][T][d] (where given) the pair's unit-weight gradient in both slots, both fp64; wsk: the
+// launch's scratch (not the head of p's workspace, where the long route keeps the logarithms), dp.wsk_bytes of it at least.
+int norm_diagonal_pass(const LongProblem &p, const LongPlan &dp, const void *paths, int rows, int T, float *wsk, double *ln_out,
+                       double *grad)
+{
+    LongProblem q = p;
+    q.X = q.Y = paths; q.A = rows; q.TX = q.TY = T; q.grad_out = nullptr; q.K_out = ln_out;
+    PairArgs da;
+    const int rc = long_args("gram_long", dp, q, 1, da);
+    if (rc) return rc;
+    da.wsk = wsk;
+    da.gradX = grad; da.gradY = nullptr;
+    return family_launch<LongFamily<true>>(p.dtype, p.kind, false, grad != nullptr, dp, p.stream, da, LongMode::Normalized);
+}
+
 // The launch with SIGSVGD_FLAG_NORMALIZED on plan pl + np with the two-sided arguments a, all on the
 // caller's stream: the diagonal passes (the paired NormIO kernel on (X, X) and, unless yx, on (Y, Y): ln K unrounded to the head
 // of the workspace, the pairs' unit-weight gradients where wanted), the two-sided NormIO kernel (each pair solved once; K^ stored,
@@ -625,19 +643,8 @@ int long2_norm_launch(const LongProblem &p, const Long2Plan &pl, const NormPlan 
     double *diagX = reinterpret_cast<double *>(tail), *diagY = reinterpret_cast<double *>(tail + np.diagX_bytes);
     double *sumX = reinterpret_cast<double *>(tail + np.diagX_bytes + np.diagY_bytes);
     double *sumY = reinterpret_cast<double *>(tail + np.diagX_bytes + np.diagY_bytes + np.sumX_bytes);
-    // a diagonal pass: `rows` paths of T points in both slots, on the launch's scratch
-    auto diagonal = [&](const LongPlan &dp, const void *paths, int rows, int T, double *ln_out, double *grad) {
-        LongProblem q = p;
-        q.X = q.Y = paths; q.A = rows; q.TX = q.TY = T; q.grad_out = nullptr; q.K_out = ln_out;
-        PairArgs da;
-        const int rc = long_args("gram_long", dp, q, 1, da);
-        if (rc) return rc;
-        da.wsk = a.wsk; // (not the head of the workspace, where the logarithms are)
-        da.gradX = grad; da.gradY = nullptr;
-        return family_launch<LongFamily<true>>(p.dtype, p.kind, false, grad != nullptr, dp, p.stream, da, LongMode::Normalized);
-    };
-    int rc = diagonal(np.dx, p.X, p.A, p.TX, lnA, want_row ? diagX : nullptr);
-    if (!rc && !yx) rc = diagonal(np.dy, p.Y, p.B, p.TY, lnB, want_gradY ? diagY : nullptr);
+    int rc = norm_diagonal_pass(p, np.dx, p.X, p.A, p.TX, a.wsk, lnA, want_row ? diagX : nullptr);
+    if (!rc && !yx) rc = norm_diagonal_pass(p, np.dy, p.Y, p.B, p.TY, a.wsk, lnB, want_gradY ? diagY : nullptr);
     if (!rc)
         rc = family_launch<Long2Family>(p.dtype, p.kind, false, a.want_row || a.want_col, pl, p.stream, a, LongMode::Normalized);
     if (rc || (!want_row && !want_gradY)) return rc;
@@ -692,6 +699,28 @@ int long2_launch_any(const LongProblem &p, void *dk_out)
 } // namespace
 int long2_launch(const LongProblem &p) { return long2_launch_any<false>(p, nullptr); }
 int long2_h_launch(const LongProblem &p, void *dk_out) { return long2_launch_any<true>(p, dk_out); }
+
+// The diagonal pass for the fused Gram route (SIGSVGD_FLAG_NORMALIZED_FUSED; capi.hip).
+// norm_diag_workspace: the bytes of its scratch (alignment slack included; the plan's refusals and messages) for `rows` paths of
+// T points.  norm_diag_launch: p.X = the paths, p.A = the rows, p.TX = the points, p.ws / p.ws_bytes = that scratch; ln_out and
+// grad (NULL: forward only) as norm_diagonal_pass takes them.
+int norm_diag_workspace(int rows, int T, int d, int n, int want_grad, size_t *bytes)
+{
+    return ring_plan_total<LongPlan>(bytes, [&](LongPlan &pl) {
+        pl.log_k = true;
+        return pair_make_plan(rows, T, T, d, n, want_grad, pl);
+    });
+}
+int norm_diag_launch(const LongProblem &p, double *ln_out, double *grad)
+{
+    LongPlan dp;
+    dp.log_k = true;
+    int rc = pair_make_plan(p.A, p.TX, p.TX, p.d, p.n, grad != nullptr, dp);
+    unsigned char *base = nullptr;
+    if (!rc) rc = ring_ws_base("gram_norm_fused (diagonal pass)", p.ws, p.ws_bytes, dp.total(), base);
+    if (rc) return rc;
+    return norm_diagonal_pass(p, dp, p.X, p.A, p.TX, reinterpret_cast<float *>(base), ln_out, grad);
+}
 
 // The share of rank `off` of `stride` (Y = X: B = A, TY = TX).  K_out gets the owned pairs and their mirror images, gradX_out
 // (fp64 whatever the dtype) is overwritten whole; a rank that owns no tile launches the reduction alone, which writes zeros.

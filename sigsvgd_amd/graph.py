@@ -13,6 +13,9 @@ the library launches on the capturing stream, all buffers are static) and replay
 static_kind / fp32_sweeps: the built-in static kernel of the Gram launch and `ops.gram_fwd_bwd`'s opt-in to the fp32-sweep
 kernels for the IMQ and rational-quadratic kernels (`static_kind=_lib.STATIC_IMQ, fp32_sweeps=True`: the captured launch
 sequence is then the RBF one's; without the flag those kinds capture the coverage kernel's launches).
+normalize=True: the iteration runs on the normalised kernel K(x, y) / sqrt(K(x, x) K(y, y)) and its first-slot gradient
+(`ops.gram_fwd_bwd(..., normalized=True)`, SIGSVGD_FLAG_NORMALIZED_FUSED): the unflagged launch
+between a diagonal pass and two small kernels, all captured; the replayed step equals the eager iteration bit for bit.
 
 Semantics per update mode are those of `SVGD.step` (reference src/inference/svgd.py:93-116) with
 optimizer=None (manual), adaptive_gradient=True (the reference's simple Adagrad) or torch.optim.Adam.
@@ -27,13 +30,14 @@ from . import _lib, ops
 class GraphedSigSVGD:
     def __init__(self, X0: torch.Tensor, inv_h: float, dyadic_order: int = 0, lr: float = 1e-3, update: str = "manual",
                  betas=(0.9, 0.999), eps: float = 1e-8, warmup: int = 2, static_kind: int = _lib.STATIC_RBF,
-                 fp32_sweeps: bool = False):
+                 fp32_sweeps: bool = False, normalize: bool = False):
         if X0.device.type != "cuda" or X0.dtype != torch.float32 or X0.dim() != 3:
             raise ValueError("GraphedSigSVGD needs float32 particles [N, T, d] on the HIP device")
         if update not in ("manual", "adagrad", "adam"):
             raise ValueError(f"unknown update mode {update!r}")
         self.inv_h, self.dyadic_order, self.lr, self.update = float(inv_h), int(dyadic_order), float(lr), update
         self.static_kind, self.fp32_sweeps = int(static_kind), bool(fp32_sweeps)
+        self.normalize = bool(normalize)
         self.X = X0.detach().clone().contiguous()
         self.score = torch.zeros_like(self.X)
         self._adagrad = torch.zeros_like(self.X) if update == "adagrad" else None
@@ -75,7 +79,8 @@ class GraphedSigSVGD:
 
     def _iteration(self):
         K, gk = ops.gram_fwd_bwd(self.X, self.X, self.inv_h, self.dyadic_order, self.static_kind, y_is_x=True,
-                                 check_regime=False, fp32_sweeps=self.fp32_sweeps)
+                                 check_regime=False, fp32_sweeps=self.fp32_sweeps,
+                                 **({"normalized": True} if self.normalize else {}))
         if self.update == "adam":
             v, _ = ops.svgd_adam(K, self.score, gk, self.X, self.lr, self._adam, inplace=True)
         else:

@@ -155,19 +155,21 @@ class SignatureKernel:
     on the register-resident fp32-sweep kernel at order 0, T <= 64).  exact_grad: `SigKernel`'s (every gradient the exact derivative of
     the discrete kernel, on the long route).  normalize: `SigKernel`'s (the normalised kernel
     K(x, y) / sqrt(K(x, x) K(y, y)) from the long route's log-domain launches: `__call__` through `compute_Gram`, `gram_and_grad` --
-    and with it `SVGD` and `ScoreEstimator` -- from one launch with SIGSVGD_FLAG_NORMALIZED).  Unknown
+    and with it `SVGD` and `ScoreEstimator` -- from one launch with SIGSVGD_FLAG_NORMALIZED).
+    normalize_route: `SigKernel`'s ("fused": the normalised kernel around the fused Gram launch, one
+    `ops.gram_fwd_bwd(..., normalized=True)` per `gram_and_grad`).  Unknown
     keyword arguments are accepted and ignored, as in
     the reference (examples/script_planning_robot.py:391 passes `bandwidth=`)."""
 
     def __init__(self, bandwidth_fn: scalar_function = None, depth: int = 3, static_kernel=None, fp32_sweeps: bool = False,
-                 exact_grad: bool = False, normalize: bool = False, **kwargs):
+                 exact_grad: bool = False, normalize: bool = False, normalize_route: str = "long", **kwargs):
         if static_kernel is None or isinstance(static_kernel, str):
             name = "rbf" if static_kernel is None else static_kernel.lower()
             if name not in _STATIC_BY_NAME:
                 raise ValueError(f'static_kernel must be one of {sorted(_STATIC_BY_NAME)} or an instance, got {static_kernel!r}')
             static_kernel = _STATIC_BY_NAME[name](bandwidth_fn=bandwidth_fn)
         self.kernel = SigKernel(static_kernel, dyadic_order=depth, fp32_sweeps=fp32_sweeps, exact_grad=exact_grad,
-                                normalize=normalize)
+                                normalize=normalize, normalize_route=normalize_route)
 
     def __call__(self, X, Y, **kwargs):
         # The reference upcasts to fp64 around compute_Gram and casts K back; the HIP kernels read fp32/fp64 paths

@@ -134,10 +134,12 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
 
 def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
            fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False,
-           normalized: bool = False) -> int:
+           normalized: bool = False, normalized_fused: bool = False) -> int:
     f = 0
     if normalized:
         f |= _lib.FLAG_NORMALIZED
+    if normalized_fused:
+        f |= _lib.FLAG_NORMALIZED_FUSED
     if log_k:
         f |= _lib.FLAG_LOG_K
     if nan_tails:
@@ -161,16 +163,17 @@ def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_for
 
 def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
              naive: bool = False, force_generic: bool = False, y_is_x: bool = False,
-             stored_forward: bool = False, fp32_sweeps: bool = False) -> torch.Tensor:
+             stored_forward: bool = False, fp32_sweeps: bool = False, normalized: bool = False) -> torch.Tensor:
     """K[A,B] = signature-kernel Gram matrix (forward only).  y_is_x: the caller states that Y holds the
-    same values as X, so each unordered pair is solved once and K is mirrored.  fp32_sweeps: see `gram_fwd_bwd`."""
+    same values as X, so each unordered pair is solved once and K is mirrored.  fp32_sweeps, normalized: see `gram_fwd_bwd`."""
     dev = _require_gpu(X, Y)
     Xc, Yc = _prep_paths(X, Y)
     A, T, d = Xc.shape
     B = Yc.shape[0]
     if y_is_x and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x needs X and Y of one shape")
-    flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward, fp32_sweeps)
+    flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward, fp32_sweeps,
+                   normalized_fused=normalized)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
                               int(static_kind), flags, K.data_ptr()),
@@ -182,8 +185,15 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
                  grad_out: Optional[torch.Tensor] = None, naive: bool = False, sym: bool = False,
                  y_is_x: bool = False, force_generic: bool = False,
                  check_regime: bool = True, stored_forward: bool = False,
-                 fp32_sweeps: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                 fp32_sweeps: bool = False, normalized: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """(K[A,B], gradX[A,T,d]) with gradX = d sum(grad_out*K)/dX (first slot); grad_out None = ones.
+
+    `normalized=True` (SIGSVGD_FLAG_NORMALIZED_FUSED; here, on `gram_fwd` and `gram_takes`): K is the
+    normalised kernel K^_ij = K(X_i, Y_j) / sqrt(K(X_i, X_i) K(Y_j, Y_j)) and gradX the first-slot gradient of
+    sum(grad_out * K^), the diagonals' dependence included -- the unflagged launch of the same route between a diagonal pass
+    and two small kernels, one capturable call.  With y_is_x K^'s diagonal is exactly 1 and the diagonal pairs carry no
+    gradient.  Defined where K(x, x) fits the dtype (T <= 128 does); `gram_long_fwd_bwd2(normalized=True)` past that.  Not
+    with naive.
 
     Bit-reproducible: every reduction over pairs runs in an order fixed by the launch geometry (no floating-point
     atomics), so two calls on the same input -- eager or replayed from a captured graph -- return the same bits.
@@ -206,7 +216,7 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     go = _weights(grad_out, (A, B), Xc.dtype)
     if (y_is_x or sym) and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x / sym need X and Y of one shape")
-    flags = _flags(naive, sym, y_is_x, force_generic, stored_forward, fp32_sweeps)
+    flags = _flags(naive, sym, y_is_x, force_generic, stored_forward, fp32_sweeps, normalized_fused=normalized)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, T, d), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
@@ -217,11 +227,13 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
 
 def gram_takes(A: int, B: int, T: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                want_grad: bool = True, naive: bool = False, sym: bool = False, y_is_x: bool = False,
-               fp32_sweeps: bool = False) -> bool:
+               fp32_sweeps: bool = False, normalized: bool = False) -> bool:
     """Whether `gram_fwd` (want_grad False) / `gram_fwd_bwd` take paths [A, T, d] x [B, T, d] with these settings: the
     library's workspace query for the call's flags, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (the
-    per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those); any other error raises."""
-    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False, False, fp32_sweeps)
+    per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those; normalized together with naive, or a
+    shape whose diagonal pass the paired plan refuses); any other error raises."""
+    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False, False, fp32_sweeps,
+                   normalized_fused=normalized)
     return _query("gram_workspace_bytes", (int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
                                            1 if want_grad else 0, flags), (ctypes.c_size_t(0),), may_refuse=True)
 

@@ -679,6 +679,30 @@ class _SigKernelNormGram(torch.autograd.Function):
         return gX, gY, None, None, None, None, None, None
 
 
+class _SigKernelNormFusedGram(torch.autograd.Function):
+    """The normalised Gram matrix on the fused route (`SigKernel(normalize=True, normalize_route="fused")`, DESIGN.md section
+    5.23).  forward: one `ops.gram_fwd(..., normalized=True)`.  backward: one `ops.gram_fwd_bwd(..., normalized=True)` with
+    grad_out = grad_output, which returns d sum(grad_output * Khat) / dX, the diagonals' dependence included (first slot; sym:
+    weights grad_output + grad_output^T).  Y gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, X, Y, static_kind, inv_h, dyadic_order, sym, y_is_x, fp32_sweeps):
+        ctx.cfg = (static_kind, inv_h, dyadic_order, sym, y_is_x, fp32_sweeps)
+        Xd, Yd = X.detach(), Y.detach()
+        ctx.save_for_backward(Xd, Yd)
+        return ops.gram_fwd(Xd, Yd, inv_h, dyadic_order, static_kind, y_is_x=y_is_x, normalized=True, **_fp32_kw(fp32_sweeps))
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        X, Y = ctx.saved_tensors
+        static_kind, inv_h, dyadic_order, sym, y_is_x, fp32_sweeps = ctx.cfg
+        gX = None
+        if ctx.needs_input_grad[0]:
+            gX = ops.gram_fwd_bwd(X, Y, inv_h, dyadic_order, static_kind, grad_output, sym=sym, y_is_x=y_is_x, normalized=True,
+                                  **_fp32_kw(fp32_sweeps))[1]
+        return gX, None, None, None, None, None, None, None
+
+
 # ------------------------------------------------------------------------------------------------
 # a static-kernel sigma that requires grad (DESIGN.md section 5.16)
 # ------------------------------------------------------------------------------------------------
@@ -801,11 +825,25 @@ class SigKernel:
     return ln K itself (with any value of normalize).  `gram_and_grad` with normalize=True returns the
     normalised Gram matrix and the gradient of sum(grad_out * K^) in X from exactly one launch of the long route
     (`ops.gram_long_fwd_bwd2(..., normalized=True)`, SIGSVGD_FLAG_NORMALIZED: each pair solved once), whatever the shape; with
-    Y None that is the gradient at fixed second slot, which SVGD uses.  The same refusals."""
+    Y None that is the gradient at fixed second slot, which SVGD uses.  The same refusals.
+
+    normalize=True, normalize_route="fused" (the default "long" is everything above, unchanged):
+    `gram_and_grad` is exactly one `ops.gram_fwd_bwd(..., normalized=True)` (SIGSVGD_FLAG_NORMALIZED_FUSED: the normalisation
+    around the unflagged fused launch, at that launch's cost and accuracy), `compute_Gram` a node of `ops.gram_fwd` /
+    `ops.gram_fwd_bwd` with the flag, `compute_mmd` follows through it; fp32_sweeps=True means there what it means without
+    normalize.  For shapes whose K(x, x) fits the dtype (T <= 128 does).  grad_Y=True, `lengths_*`, a sigma that requires grad,
+    user static kernels and shapes `ops.gram_takes` refuses raise NotImplementedError (exact_grad=True and _naive_solver=True
+    do at construction).  `compute_kernel`, `compute_distance` and the `compute_log_*` methods keep the long route.
+    normalize_route="fused" without normalize=True raises ValueError."""
 
     def __init__(self, static_kernel, dyadic_order: int, _naive_solver: bool = False, fp32_sweeps: bool = False,
-                 exact_grad: bool = False, normalize: bool = False):
-        if normalize and fp32_sweeps:
+                 exact_grad: bool = False, normalize: bool = False, normalize_route: str = "long"):
+        if normalize_route not in ("long", "fused"):
+            raise ValueError(f"SigKernel: normalize_route must be 'long' or 'fused', got {normalize_route!r}")
+        if normalize_route == "fused" and not normalize:
+            raise ValueError("SigKernel: normalize_route='fused' selects the route of the normalised kernel; it needs "
+                             "normalize=True")
+        if normalize and fp32_sweeps and normalize_route != "fused":
             raise ValueError("SigKernel: normalize=True runs on the long route's fp64 log-domain sweeps; fp32_sweeps=True "
                              "selects an fp32-sweep kernel.  Use one of them")
         if normalize and exact_grad:
@@ -823,6 +861,7 @@ class SigKernel:
         self.fp32_sweeps = bool(fp32_sweeps)
         self.exact_grad = bool(exact_grad)
         self.normalize = bool(normalize)
+        self.normalize_route = normalize_route
         self.speculate_ones = True
         self.value_check_min_batch = 32  # below this a launch is latency-bound and the compare would not pay
 
@@ -840,6 +879,11 @@ class SigKernel:
         if grad_Y and sym:
             raise ValueError("compute_Gram: grad_Y=True differentiates the second slot itself; sym=True folds it into the "
                              "first.  Use one of them")
+        if self.normalize and self.normalize_route == "fused":
+            static_kind, inv_h = self._fused_norm_static("compute_Gram", X, Y, sym, _same_storage(X, Y), grad_Y, lengths_X,
+                                                         lengths_Y)
+            return _SigKernelNormFusedGram.apply(X, Y, static_kind, inv_h, self.dyadic_order, bool(sym), _same_storage(X, Y),
+                                                 self.fp32_sweeps)
         if self.normalize:
             return self._log_gram(_SigKernelNormGram, "compute_Gram", X, Y, sym, grad_Y, lengths_X, lengths_Y)
         if lengths_X is not None or lengths_Y is not None:
@@ -1010,7 +1054,9 @@ class SigKernel:
         """Biased squared MMD: mean K_XX + mean K_YY - 2 mean K_XY.  grad_Y=True differentiates Y through the cross term
         too (`compute_Gram(X, Y, grad_Y=True)`); the default gives Y the gradient of mean K_YY alone.  lengths_X /
         lengths_Y: as `compute_Gram`'s."""
-        if self.normalize:
+        if self.normalize and self.normalize_route == "fused":  # (its refusals before the first of the three launches)
+            self._fused_norm_static("compute_mmd", X, Y, False, False, grad_Y, lengths_X, lengths_Y)
+        elif self.normalize:
             self._log_static("compute_mmd", X, Y, lengths_X, lengths_Y)
         if lengths_X is None and lengths_Y is None:
             K_XX = self.compute_Gram(X, X, sym=True)
@@ -1026,6 +1072,11 @@ class SigKernel:
         """One fused launch: (K, d sum(grad_out*K)/dX) with detached tensors.  Equivalent to
         `K = compute_Gram(X, Y); g = autograd.grad((grad_out*K).sum(), X)` (score.py:68-69)."""
         Yv = X if Y is None else Y
+        if self.normalize and self.normalize_route == "fused":
+            static_kind, inv_h = self._fused_norm_static("gram_and_grad", X, Yv, sym, Y is None)
+            go = None if grad_out is None else grad_out.detach()
+            return ops.gram_fwd_bwd(X, Yv, inv_h, self.dyadic_order, static_kind, go, sym=bool(sym), y_is_x=Y is None,
+                                    normalized=True, **_fp32_kw(self.fp32_sweeps))
         if self.normalize:
             return self._normalized_gram_and_grad(X, Yv, grad_out, sym, Y is None)
         static_kind, inv_h = _resolve_static(self.static_kernel, X, Yv)
@@ -1044,6 +1095,27 @@ class SigKernel:
         go = None if grad_out is None else grad_out.detach()
         return ops.gram_long_fwd_bwd2(X, Y, inv_h, self.dyadic_order, static_kind, go, False, bool(sym), y_is_x, True, False,
                                       normalized=True)[:2]
+
+    def _fused_norm_static(self, what, X, Y, sym, y_is_x, grad_Y=False, lengths_X=None, lengths_Y=None):
+        """-> (static_kind, inv_h) of a call on the fused route's normalised launch (normalize_route="fused", DESIGN.md section
+        5.23), and its refusals, each before any device work"""
+        if grad_Y:
+            raise NotImplementedError(f"{what}: grad_Y=True with normalize_route='fused': the fused route has the first-slot "
+                                      "gradient only; normalize_route='long' returns both")
+        if lengths_X is not None or lengths_Y is not None:
+            raise NotImplementedError(f"{what}: lengths_X / lengths_Y with normalize_route='fused': the fused route takes one "
+                                      "length for every path")
+        if _learned_sigma(self.static_kernel) is not None:
+            raise NotImplementedError(f"{what}: a static-kernel sigma that requires grad: the bandwidth launches do not take "
+                                      "SIGSVGD_FLAG_NORMALIZED_FUSED")
+        static_kind, inv_h = _resolve_static(self.static_kernel, X, Y)
+        if static_kind is None:
+            raise NotImplementedError(f"{what}: the user static kernel {type(self.static_kernel).__name__} runs on "
+                                      "ops.PDESolve, which has no normalised form; the built-in static kernels have one")
+        if not ops.gram_takes(X.shape[0], Y.shape[0], max(X.shape[1], Y.shape[1]), X.shape[2], self.dyadic_order, static_kind,
+                              True, False, bool(sym), bool(y_is_x), normalized=True, **_fp32_kw(self.fp32_sweeps)):
+            raise NotImplementedError(f"{what}: {_lib.last_error()}")
+        return static_kind, inv_h
 
     def _user_gram_and_grad(self, X, Y, grad_out, sym):
         """gram_and_grad for a user static kernel: its grid (with the graph to X), K and dG from one PDE launch, and dG
