@@ -129,7 +129,40 @@ extern "C" {
 #define SIGSVGD_VEC_UNIT 2     /* k = sq, w = 1: dK = grad_scale * sum_j grad_out_ij (XM_i - YM_j),
                                   the adjoint of sigsvgd_vec_sqdist (autograd through the distance) */
 
-/* flags */
+/* flags
+ *
+ * Which entry point takes which flag (one row per family; a family's workspace, plan and schedule queries answer as its
+ * launches do).  Columns, in the order of the bits: NV NAIVE_SOLVER, SYM, YX Y_IS_X, FG FORCE_GENERIC, WC WS_CLEAN,
+ * SF STORED_FORWARD, FOLD FOLD_TILES, FP32 FP32_SWEEPS, EX EXACT_ADJOINT, NT NAN_TAILS, LK LOG_K, NM NORMALIZED,
+ * NF NORMALIZED_FUSED.  Cells:
+ *   T  taken: the flag means what its paragraph below says        i  taken and ignored: the bit changes nothing
+ *   G  taken by the gradient forms (a launch with a gradient output, a query with want_grad / want_gradX / want_gradY),
+ *      B otherwise
+ *   U  SIGSVGD_E_UNSUPPORTED ahead of every other check of the flags: the entry point has no kernels for the bit
+ *   R  SIGSVGD_E_UNSUPPORTED from the choice of kernel: the partial solve has the fp32-sweep kernels only
+ *   B  an unknown bit: SIGSVGD_E_BADARG, the message states the refused bits in hex and lists the ones taken
+ *                        NV  SYM YX  FG  WC  SF  FOLD FP32 EX  NT  LK  NM  NF
+ * gram_workspace_bytes   T   i   T   T   i   i   i    T    U   i   i   i   T
+ * gram_fwd               T   T   T   T   i   i   i    T    i   i   i   i   T
+ * gram_fwd_bwd           T   T   T   T   i   i   i    T    U   i   i   i   T
+ * gram_sym_partial       R   T   i   R   i   i   T    T    U   i   i   i   U
+ * pde                    T   B   B   B   B   B   B    B    G   B   B   B   B
+ * gram_long              T   T   i   B   B   B   B    B    G   U   B   B   B
+ * pair                   T   B   B   B   B   B   B    B    G   T   T   B   B
+ * gram_long2             T   T   T   B   B   B   B    B    G   T   T   T   B
+ * gram_long_h            T   T   T   B   B   B   B    B    T   U   B   B   B
+ * pair_h                 T   B   B   B   B   B   B    B    T   U   B   B   B
+ * gram_long_partial      T   T   i   B   B   B   T    B    U   U   B   B   B
+ * sqdist_select          B   B   T   B   B   B   B    B    B   B   B   B   B
+ * Rows: pde = sigsvgd_pde_fwd, _fwd_bwd; gram_long = sigsvgd_gram_long_fwd, _fwd_bwd; pair = sigsvgd_pair_fwd, _fwd_bwd,
+ * _schedule; gram_long2 = sigsvgd_gram_long_fwd_bwd2; gram_long_h = sigsvgd_gram_long_fwd_bwd_h; pair_h =
+ * sigsvgd_pair_fwd_bwd_h; gram_long_partial = sigsvgd_gram_long_sym_partial and its plan; the others are named in full.
+ * Pairs that are not built -- SIGSVGD_E_UNSUPPORTED wherever the first flag is taken, checked after the U cells and before
+ * the unknown bits, the message names both flags: NT with EX; LK with NV, EX or NT; NM with NV, EX, NT or LK; NF with NV.
+ * On the long route (the six rows from gram_long to gram_long_partial) NV with IMQ, RQ or a Matern kind is
+ * SIGSVGD_E_UNSUPPORTED.  SYM needs A == B (and TX == TY) where it is T; YX needs them in sigsvgd_gram_fwd_bwd, in
+ * sigsvgd_gram_fwd with NF, in gram_long2, gram_long_h and sqdist_select; with either, gram_long2 and gram_long_h take no
+ * gradY_out.  (tests/test_flag_contract_cpu.py runs every flag word against this table.) */
 #define SIGSVGD_FLAG_NAIVE_SOLVER 1u /* first-order stencil (sigkernel _naive_solver=True)      */
 #define SIGSVGD_FLAG_SYM 2u          /* sigkernel sym=True backward weighting: go + go^T (A==B) */
 #define SIGSVGD_FLAG_Y_IS_X 4u       /* caller guarantees Y aliases X (same values): lets the   */

@@ -2,6 +2,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <dlfcn.h>
 
 #include "sig_common.h"
@@ -125,64 +126,94 @@ static const char *static_kind_name(int kind)
     }
 }
 
-// SIGSVGD_FLAG_EXACT_ADJOINT on a route that has the GG kernels only: refused before any device work
-static int no_exact_adjoint(const char *who, unsigned flags)
+// ---- which entry point takes which flag: the table of include/sigsvgd_hip.h, stated by tests/test_flag_contract_cpu.py ----
+// A new flag is a row of kFlags, a bit in the rules of the families that take it and, where it excludes others, a row of
+// kNotBuiltWith.  Every refusal here comes before any device work.
+enum : unsigned {
+    NV = SIGSVGD_FLAG_NAIVE_SOLVER, SYM = SIGSVGD_FLAG_SYM, YX = SIGSVGD_FLAG_Y_IS_X, FG = SIGSVGD_FLAG_FORCE_GENERIC,
+    WC = SIGSVGD_FLAG_WS_CLEAN, SF = SIGSVGD_FLAG_STORED_FORWARD, FOLD = SIGSVGD_FLAG_FOLD_TILES, FP32 = SIGSVGD_FLAG_FP32_SWEEPS,
+    EX = SIGSVGD_FLAG_EXACT_ADJOINT, NT = SIGSVGD_FLAG_NAN_TAILS, LK = SIGSVGD_FLAG_LOG_K, NM = SIGSVGD_FLAG_NORMALIZED,
+    NF = SIGSVGD_FLAG_NORMALIZED_FUSED
+};
+// the flags in the order of their bits; not_built_for: what an entry point without kernels for the bit says of itself and of
+// those that have them (the flags no rule lists under `not_built` have none)
+struct FlagName { unsigned bit; const char *name, *not_built_for; };
+static const FlagName kFlags[] = {
+    {NV, "NAIVE_SOLVER"}, {SYM, "SYM"}, {YX, "Y_IS_X"}, {FG, "FORCE_GENERIC"}, {WC, "WS_CLEAN"}, {SF, "STORED_FORWARD"},
+    {FOLD, "FOLD_TILES"}, {FP32, "FP32_SWEEPS"},
+    {EX, "EXACT_ADJOINT", "this route (the gradient launches of sigsvgd_pde_fwd_bwd, sigsvgd_gram_long_fwd_bwd / _fwd_bwd2 / "
+                          "_fwd_bwd_h and sigsvgd_pair_fwd_bwd / _fwd_bwd_h take it)"},
+    {NT, "NAN_TAILS", "this entry point (sigsvgd_gram_long_fwd_bwd2, sigsvgd_pair_fwd, sigsvgd_pair_fwd_bwd, "
+                      "sigsvgd_pair_schedule and their workspace queries take it)"},
+    {LK, "LOG_K"}, {NM, "NORMALIZED"},
+    {NF, "NORMALIZED_FUSED", "the partial solve (sigsvgd_gram_fwd, sigsvgd_gram_fwd_bwd and sigsvgd_gram_workspace_bytes take it)"},
+};
+// the pairs that are not built (DESIGN.md sections 5.20 to 5.23), each once: wherever `flag` is taken, none of `others` may
+// be set beside it; the refusal names the first of them that is
+struct NotBuiltWith { unsigned flag, others[4]; const char *why; };
+static const NotBuiltWith kNotBuiltWith[] = {
+    {NT, {EX}, "the exact adjoint's kernels solve every pair on the launch's grid"},
+    {LK, {NV, EX, NT}, "the log-domain kernels are the default stencil's GG solve on the launch's grid"},
+    {NM, {NV, EX, NT, LK}, "the normalised kernels are the log-domain solve of the default stencil on the launch's grid, and "
+                           "store K^ where that flag stores ln K"},
+    {NF, {NV}, "the diagonal pass is the log-domain solve of the default stencil"},
+};
+// One family of entry points: the name its refusals carry, the bits it takes (acts on, or accepts without effect), those only
+// its forms with the reverse sweep take, and those it answers SIGSVGD_E_UNSUPPORTED ahead of every other check.  The fused
+// route's entry points never refused the bits they do not know (`refuses_unknown` false): there those bits change nothing.
+struct FlagRule { const char *who; unsigned taken, grad_taken, not_built; bool refuses_unknown = true; };
+static const unsigned kFusedBits = NV | SYM | YX | FG | WC | SF | FOLD | FP32 | NF;
+// (who, taken, grad_taken, not_built, refuses_unknown)
+static const FlagRule kGramQuery{"gram_workspace_bytes", kFusedBits, 0, EX, false};
+static const FlagRule kGramFwd{"gram_fwd", kFusedBits, 0, 0, false}; // (EX: ignored here, as it always was)
+static const FlagRule kGramFwdBwd{"gram_fwd_bwd", kFusedBits, 0, EX, false};
+static const FlagRule kSymPartial{"sym_partial", kFusedBits & ~NF, 0, EX | NF, false};
+static const FlagRule kPde{"pde", NV, EX, 0};
+static const FlagRule kLong{"gram_long", NV | SYM | YX, EX, NT};
+static const FlagRule kLong2{"gram_long", NV | SYM | YX | NT | LK | NM, EX, 0};
+static const FlagRule kLongH{"gram_long", NV | SYM | YX | EX, 0, NT};
+static const FlagRule kLongPartial{"gram_long", NV | SYM | YX | FOLD, 0, EX | NT};
+static const FlagRule kPair{"pair", NV | NT | LK, EX, 0};
+static const FlagRule kPairH{"pair", NV | EX, 0, NT};
+static const FlagRule kSelect{"sqdist_select", YX, 0, 0};
+
+enum Form { QUERY, LAUNCH };      // what a check can know: a query's shape, order, kind and flags; a launch's pointers, dtype, inv_h too
+enum Sweeps { FORWARD, REVERSE }; // REVERSE: the form runs the reverse sweep (a gradient launch, or its query)
+static Sweeps reverse_if(bool grad) { return grad ? REVERSE : FORWARD; }
+enum FlagChecks { NOT_BUILT = 1, UNKNOWN = 2, EVERY_CHECK = 3 };
+
+static const char *flag_name(unsigned bit)
 {
-    if (!(flags & SIGSVGD_FLAG_EXACT_ADJOINT)) return SIGSVGD_OK;
-    set_error("%s: SIGSVGD_FLAG_EXACT_ADJOINT is not built for this route (the gradient launches of sigsvgd_pde_fwd_bwd, "
-              "sigsvgd_gram_long_fwd_bwd / _fwd_bwd2 / _fwd_bwd_h and sigsvgd_pair_fwd_bwd / _fwd_bwd_h take it)", who);
-    return SIGSVGD_E_UNSUPPORTED;
+    for (const FlagName &f : kFlags)
+        if (f.bit == bit) return f.name;
+    return "?";
 }
 
-// SIGSVGD_FLAG_NAN_TAILS on the long route: refused before any device work by the entry points that
-// have no such kernels (`takes` false), and together with SIGSVGD_FLAG_EXACT_ADJOINT by all of them
-static int check_nan_tails(const char *who, unsigned flags, bool takes)
+// The flags of one call against its family's rule, in this order: the bits the family has no kernels for, the pairs that are
+// not built (both UNSUPPORTED), then the bits it does not know (BADARG; the message lists the ones it takes).  `which`: the
+// long-path families check their pointers and shape between the second and the third.
+static int check_flags(const FlagRule &r, unsigned flags, Sweeps sweeps = FORWARD, int which = EVERY_CHECK)
 {
-    if (!(flags & SIGSVGD_FLAG_NAN_TAILS)) return SIGSVGD_OK;
-    if (!takes) {
-        set_error("%s: SIGSVGD_FLAG_NAN_TAILS is not built for this entry point (sigsvgd_gram_long_fwd_bwd2, sigsvgd_pair_fwd, "
-                  "sigsvgd_pair_fwd_bwd, sigsvgd_pair_schedule and their workspace queries take it)", who);
+    for (const FlagName &f : kFlags) {
+        if (!(which & NOT_BUILT) || !(flags & r.not_built & f.bit)) continue;
+        set_error("%s: SIGSVGD_FLAG_%s is not built for %s", r.who, f.name, f.not_built_for);
         return SIGSVGD_E_UNSUPPORTED;
     }
-    if (flags & SIGSVGD_FLAG_EXACT_ADJOINT) {
-        set_error("%s: SIGSVGD_FLAG_NAN_TAILS together with SIGSVGD_FLAG_EXACT_ADJOINT is not built (the exact adjoint's kernels "
-                  "solve every pair on the launch's grid)", who);
-        return SIGSVGD_E_UNSUPPORTED;
+    for (const NotBuiltWith &pair : kNotBuiltWith) {
+        if (!(which & NOT_BUILT) || !(flags & r.taken & pair.flag)) continue;
+        for (unsigned other : pair.others) {
+            if (!(flags & other)) continue;
+            set_error("%s: SIGSVGD_FLAG_%s together with SIGSVGD_FLAG_%s is not built (%s)", r.who, flag_name(pair.flag),
+                      flag_name(other), pair.why);
+            return SIGSVGD_E_UNSUPPORTED;
+        }
     }
-    return SIGSVGD_OK;
-}
-
-// SIGSVGD_FLAG_LOG_K on the entry points that take it (those that take SIGSVGD_FLAG_NAN_TAILS; the
-// others keep their answer for an unknown bit): refused before any device work together with a flag whose kernels have no
-// log-domain form
-static int check_log_k(const char *who, unsigned flags)
-{
-    if (!(flags & SIGSVGD_FLAG_LOG_K)) return SIGSVGD_OK;
-    const char *other = (flags & SIGSVGD_FLAG_NAIVE_SOLVER)    ? "SIGSVGD_FLAG_NAIVE_SOLVER"
-                        : (flags & SIGSVGD_FLAG_EXACT_ADJOINT) ? "SIGSVGD_FLAG_EXACT_ADJOINT"
-                        : (flags & SIGSVGD_FLAG_NAN_TAILS)     ? "SIGSVGD_FLAG_NAN_TAILS"
-                                                               : nullptr;
-    if (!other) return SIGSVGD_OK;
-    set_error("%s: SIGSVGD_FLAG_LOG_K together with %s is not built (the log-domain kernels are the default stencil's GG solve "
-              "on the launch's grid)", who, other);
-    return SIGSVGD_E_UNSUPPORTED;
-}
-
-// SIGSVGD_FLAG_NORMALIZED on the two entry points that take it (sigsvgd_gram_long_fwd_bwd2 and its
-// workspace query; every other one keeps its answer for an unknown bit): refused before any device work together with a flag
-// whose kernels have no normalised form, and with SIGSVGD_FLAG_LOG_K, which it implies and whose output it replaces
-static int check_normalized(const char *who, unsigned flags)
-{
-    if (!(flags & SIGSVGD_FLAG_NORMALIZED)) return SIGSVGD_OK;
-    const char *other = (flags & SIGSVGD_FLAG_NAIVE_SOLVER)    ? "SIGSVGD_FLAG_NAIVE_SOLVER"
-                        : (flags & SIGSVGD_FLAG_EXACT_ADJOINT) ? "SIGSVGD_FLAG_EXACT_ADJOINT"
-                        : (flags & SIGSVGD_FLAG_NAN_TAILS)     ? "SIGSVGD_FLAG_NAN_TAILS"
-                        : (flags & SIGSVGD_FLAG_LOG_K)         ? "SIGSVGD_FLAG_LOG_K"
-                                                               : nullptr;
-    if (!other) return SIGSVGD_OK;
-    set_error("%s: SIGSVGD_FLAG_NORMALIZED together with %s is not built (the normalised kernels are the log-domain solve of the "
-              "default stencil on the launch's grid, and store K^ where that flag stores ln K)", who, other);
-    return SIGSVGD_E_UNSUPPORTED;
+    const unsigned taken = r.taken | (sweeps == REVERSE ? r.grad_taken : 0u), unknown = flags & ~taken;
+    if (!(which & UNKNOWN) || !r.refuses_unknown || !unknown) return SIGSVGD_OK;
+    char list[128] = "";
+    for (const FlagName &f : kFlags)
+        if (taken & f.bit) snprintf(list + strlen(list), sizeof(list) - strlen(list), "%s%s", list[0] ? ", " : "", f.name);
+    return bad_arg("%s: unknown flag bits 0x%x (%s only)", r.who, unknown, list);
 }
 
 static int check_common(const void *X, const void *Y, int A, int B, int T, int d, int dtype, double inv_h,
@@ -200,44 +231,31 @@ static int check_common(const void *X, const void *Y, int A, int B, int T, int d
     return SIGSVGD_OK;
 }
 
-// the shape, dtype, order and flag checks of the PDE entry points (sig_pde.hip): only SIGSVGD_FLAG_NAIVE_SOLVER means
-// anything there, and for a gradient launch (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; every other bit is refused
-static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags, bool grad = false)
+// the shape, dtype, order and flag checks of the PDE entry points (sig_pde.hip)
+static int check_pde(int npairs, int M, int N, int dtype, int n, unsigned flags, const FlagRule &rule, Sweeps sweeps)
 {
-    if (grad) flags &= ~SIGSVGD_FLAG_EXACT_ADJOINT;
     if (npairs < 1 || M < 2 || N < 2)
         return bad_arg("pde: bad shape npairs=%d M=%d N=%d (need npairs >= 1, M, N >= 2)", npairs, M, N);
     if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("pde: bad dtype %d", dtype);
     if (n < 0 || n > 10) return bad_arg("pde: bad dyadic order %d", n);
-    if (flags & ~SIGSVGD_FLAG_NAIVE_SOLVER)
-        return bad_arg("pde: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", flags & ~SIGSVGD_FLAG_NAIVE_SOLVER);
-    return SIGSVGD_OK;
+    return check_flags(rule, flags, sweeps);
 }
 
 // The checks of the long-path entry points (gram_long.hip), each condition in one place.  check_long: the Gram mode's, which
-// every mode shares -- with `launch` the pointers, dtype and inv_h of a launch too, without it what a workspace query can
-// know.  SIGSVGD_FLAG_NAIVE_SOLVER (RBF and linear only: UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_SYM
-// (A == B and TX == TY) and SIGSVGD_FLAG_Y_IS_X (no effect in the Gram mode) are taken, and for a launch with the reverse
-// sweep (`grad`) SIGSVGD_FLAG_EXACT_ADJOINT; `nan_tails`: the entry point takes SIGSVGD_FLAG_NAN_TAILS
-// (the others answer UNSUPPORTED before anything else: check_nan_tails) and with it SIGSVGD_FLAG_LOG_K (check_log_k: the others
-// refuse that bit as an unknown one); `normalized`: the entry point takes SIGSVGD_FLAG_NORMALIZED (check_normalized; the
-// two-sided launch and its query only); every other bit is refused.
-static int check_long(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false, bool normalized = false)
+// every mode shares -- for a LAUNCH the pointers, dtype and inv_h too, for a QUERY what a workspace query can know -- around
+// the flags `rule` lets through: SIGSVGD_FLAG_SYM needs A == B and TX == TY, SIGSVGD_FLAG_NAIVE_SOLVER is built for RBF and
+// linear only (UNSUPPORTED with IMQ, rational quadratic and Matern), SIGSVGD_FLAG_Y_IS_X has no effect in the Gram mode.
+static int check_long(const LongProblem &p, Form form, const FlagRule &rule, Sweeps sweeps)
 {
-    if (check_nan_tails("gram_long", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
-    if (nan_tails && check_log_k("gram_long", p.flags)) return SIGSVGD_E_UNSUPPORTED;
-    if (normalized && check_normalized("gram_long", p.flags)) return SIGSVGD_E_UNSUPPORTED;
+    const bool launch = form == LAUNCH;
+    if (check_flags(rule, p.flags, sweeps, NOT_BUILT)) return SIGSVGD_E_UNSUPPORTED;
     if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("gram_long: null pointer argument");
     if (p.A < 1 || p.B < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("gram_long: bad shape A=%d B=%d TX=%d TY=%d d=%d (need A, B, d >= 1 and TX, TY >= 2)", p.A, p.B, p.TX,
                        p.TY, p.d);
     if (!static_kind_known(p.kind)) return bad_arg("gram_long: bad static kernel kind %d", p.kind);
     if (p.n < 0 || p.n > 10) return bad_arg("gram_long: bad dyadic order %d", p.n);
-    const unsigned known =
-        SIGSVGD_FLAG_NAIVE_SOLVER | SIGSVGD_FLAG_SYM | SIGSVGD_FLAG_Y_IS_X | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
-        (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u) | (normalized ? SIGSVGD_FLAG_NORMALIZED : 0u);
-    if (p.flags & ~known)
-        return bad_arg("gram_long: unknown flag bits 0x%x (NAIVE_SOLVER, SYM and Y_IS_X only)", p.flags & ~known);
+    if (check_flags(rule, p.flags, sweeps, UNKNOWN)) return SIGSVGD_E_BADARG;
     if ((p.flags & SIGSVGD_FLAG_SYM) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long: sym backward needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
     if (launch && p.dtype != SIGSVGD_F32 && p.dtype != SIGSVGD_F64) return bad_arg("gram_long: bad dtype %d", p.dtype);
@@ -254,10 +272,9 @@ static int check_long(const LongProblem &p, bool launch, bool grad = false, bool
 
 // the two-sided entry points: check_long's, and there SIGSVGD_FLAG_Y_IS_X means what it says: one batch in both slots
 // (A == B, TX == TY), whose gradient has one slot; SYM too weights one slot only
-static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool grad = false, bool nan_tails = false,
-                       bool normalized = false)
+static int check_long2(const LongProblem &p, Form form, const FlagRule &rule, Sweeps sweeps, bool want_gradY)
 {
-    const int rc = check_long(p, launch, grad, nan_tails, normalized);
+    const int rc = check_long(p, form, rule, sweeps);
     if (rc) return rc;
     if ((p.flags & SIGSVGD_FLAG_Y_IS_X) && (p.A != p.B || p.TX != p.TY))
         return bad_arg("gram_long2: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", p.A, p.B, p.TX, p.TY);
@@ -266,55 +283,48 @@ static int check_long2(const LongProblem &p, bool launch, bool want_gradY, bool 
     return SIGSVGD_OK;
 }
 
-// the partial entry points: check_long's for one batch in both slots with SIGSVGD_FLAG_FOLD_TILES taken too, and the rank's
-// tiles: tile_offset in [0, tile_stride).  SIGSVGD_FLAG_EXACT_ADJOINT: UNSUPPORTED (gram_long_part_kernel has the GG sweep only)
-static int check_long_partial(const LongProblem &p, bool launch, int tile_offset, int tile_stride)
+// the partial entry points: check_long's for one batch in both slots, and the rank's tiles: tile_offset in [0, tile_stride).
+// SIGSVGD_FLAG_EXACT_ADJOINT (gram_long_part_kernel has the GG sweep only) is refused first, under the launch's own name
+static int check_long_partial(const LongProblem &p, Form form, const FlagRule &rule, int tile_offset, int tile_stride)
 {
-    if (no_exact_adjoint("gram_long_sym_partial", p.flags)) return SIGSVGD_E_UNSUPPORTED;
-    LongProblem q = p;
-    q.flags &= ~(unsigned)SIGSVGD_FLAG_FOLD_TILES;
-    const int rc = check_long(q, launch);
+    const FlagRule own{"gram_long_sym_partial", 0, 0, rule.not_built & EX, false};
+    int rc = check_flags(own, p.flags);
+    if (!rc) rc = check_long(p, form, rule, FORWARD);
     if (rc) return rc;
     if (tile_stride < 1 || tile_offset < 0 || tile_offset >= tile_stride)
         return bad_arg("gram_long_sym_partial: bad tile_offset/stride %d/%d", tile_offset, tile_stride);
     return SIGSVGD_OK;
 }
 
-// the paired entry points (B = 1: one column of pairs): the pointers, flags (SIGSVGD_FLAG_NAIVE_SOLVER only) and shape under
-// the mode's own name, then check_long's remaining conditions; `grad`: a launch with the reverse sweep, which takes
-// SIGSVGD_FLAG_EXACT_ADJOINT too; `nan_tails`: as in check_long
-static int check_pair(const LongProblem &p, bool launch, bool grad = false, bool nan_tails = false)
+// the paired entry points (B = 1: one column of pairs): the pointers, flags and shape under the mode's own name, then
+// check_long's remaining conditions
+static int check_pair(const LongProblem &p, Form form, const FlagRule &rule, Sweeps sweeps)
 {
-    if (check_nan_tails("pair", p.flags, nan_tails)) return SIGSVGD_E_UNSUPPORTED;
-    if (nan_tails && check_log_k("pair", p.flags)) return SIGSVGD_E_UNSUPPORTED;
-    if (launch && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
-    const unsigned known = SIGSVGD_FLAG_NAIVE_SOLVER | (grad ? SIGSVGD_FLAG_EXACT_ADJOINT : 0u) |
-                           (nan_tails ? SIGSVGD_FLAG_NAN_TAILS | SIGSVGD_FLAG_LOG_K : 0u);
-    if (p.flags & ~known)
-        return bad_arg("pair: unknown flag bits 0x%x (only SIGSVGD_FLAG_NAIVE_SOLVER)", p.flags & ~known);
+    if (check_flags(rule, p.flags, sweeps, NOT_BUILT)) return SIGSVGD_E_UNSUPPORTED;
+    if (form == LAUNCH && (!p.X || !p.Y || !p.K_out)) return bad_arg("pair: null pointer argument");
+    if (check_flags(rule, p.flags, sweeps, UNKNOWN)) return SIGSVGD_E_BADARG;
     if (p.A < 1 || p.TX < 2 || p.TY < 2 || p.d < 1)
         return bad_arg("pair: bad shape A=%d TX=%d TY=%d d=%d (need A, d >= 1 and TX, TY >= 2)", p.A, p.TX, p.TY, p.d);
-    return check_long(p, launch, grad, nan_tails);
+    return check_long(p, form, rule, sweeps);
 }
 
 // the bandwidth entry points, after their mode's own checks: a static kernel that has a bandwidth,
-// and with `launch` a place for the derivative
-static int check_bandwidth(const char *who, const LongProblem &p, bool launch, const void *dK_dinvh_out)
+// and for a LAUNCH a place for the derivative
+static int check_bandwidth(const char *who, const LongProblem &p, Form form, const void *dK_dinvh_out)
 {
     if (!static_kind_radial(p.kind))
         return bad_arg("%s: the linear static kernel has no bandwidth (SIGSVGD_STATIC_RBF, _IMQ, _RQ, _MATERN32 or _MATERN52)", who);
-    if (launch && !dK_dinvh_out) return bad_arg("%s: dK_dinvh_out == NULL", who);
+    if (form == LAUNCH && !dK_dinvh_out) return bad_arg("%s: dK_dinvh_out == NULL", who);
     return SIGSVGD_OK;
 }
 
-// the distance select's (sqdist_select.hip): the shape, the one flag it takes (SIGSVGD_FLAG_Y_IS_X: one batch in both slots)
+// the distance select's (sqdist_select.hip): the shape, its flags (SIGSVGD_FLAG_Y_IS_X: one batch in both slots)
 // and the element count n = A B TX TY, which must stay below 2^63
-static int check_select(int A, int B, int TX, int TY, int d, unsigned flags, unsigned long long *n)
+static int check_select(int A, int B, int TX, int TY, int d, unsigned flags, const FlagRule &rule, unsigned long long *n)
 {
     if (A < 1 || B < 1 || TX < 1 || TY < 1 || d < 1)
         return bad_arg("sqdist_select: bad shape A=%d B=%d TX=%d TY=%d d=%d (need all >= 1)", A, B, TX, TY, d);
-    if (flags & ~SIGSVGD_FLAG_Y_IS_X)
-        return bad_arg("sqdist_select: unknown flag bits 0x%x (only SIGSVGD_FLAG_Y_IS_X)", flags & ~SIGSVGD_FLAG_Y_IS_X);
+    if (check_flags(rule, flags)) return SIGSVGD_E_BADARG;
     if ((flags & SIGSVGD_FLAG_Y_IS_X) && (A != B || TX != TY))
         return bad_arg("sqdist_select: Y_IS_X needs A == B and TX == TY (got A=%d B=%d TX=%d TY=%d)", A, B, TX, TY);
     const unsigned __int128 count = (unsigned __int128)((unsigned long long)A * (unsigned long long)B) *
@@ -486,16 +496,6 @@ static int gram_workspace(int A, int B, int T, int d, int n, int kind, int want_
 }
 
 // ---- SIGSVGD_FLAG_NORMALIZED_FUSED: the normalised kernel around an unchanged fused launch ---------
-// The bit with SIGSVGD_FLAG_NAIVE_SOLVER: refused before any device work (the diagonal pass is the log-domain solve of the
-// default stencil only, and K^'s diagonal would not be 1 under two stencils)
-static int check_norm_fused(const char *who, unsigned flags)
-{
-    if (!(flags & SIGSVGD_FLAG_NORMALIZED_FUSED) || !(flags & SIGSVGD_FLAG_NAIVE_SOLVER)) return SIGSVGD_OK;
-    set_error("%s: SIGSVGD_FLAG_NORMALIZED_FUSED together with SIGSVGD_FLAG_NAIVE_SOLVER is not built (the diagonal pass is the "
-              "log-domain solve of the default stencil)", who);
-    return SIGSVGD_E_UNSUPPORTED;
-}
-
 // The workspace of such a launch, from its 256-B aligned base: the unflagged launch's whole workspace (what gram_workspace
 // reports for the flags without the bit), the diagonals' logarithms double[A] and, unless yx, double[B], the diagonal pass's
 // scratch (the larger of the two passes'), and for a gradient launch the weights W' [A][B] (sized for fp64 I/O: the query has
@@ -588,10 +588,9 @@ int sigsvgd_gram_workspace_bytes(int A, int B, int T, int d, int dyadic_order, i
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     if (!static_kind_known(static_kind)) return bad_arg("bad static kernel kind %d", static_kind);
-    if (no_exact_adjoint("gram_workspace_bytes", flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (check_flags(kGramQuery, flags)) return SIGSVGD_E_UNSUPPORTED;
     if (!(flags & SIGSVGD_FLAG_NORMALIZED_FUSED))
         return gram_workspace(A, B, T, d, dyadic_order, static_kind, want_grad, flags, bytes);
-    if (check_norm_fused("gram_workspace_bytes", flags)) return SIGSVGD_E_UNSUPPORTED;
     if (A < 1 || B < 1 || T < 2 || d < 1 || dyadic_order < 0 || dyadic_order > 10)
         return bad_arg("bad shape A=%d B=%d T=%d d=%d order %d (need A,B,d >= 1, T >= 2 and 0 <= order <= 10)", A, B, T, d,
                        dyadic_order);
@@ -610,7 +609,7 @@ int sigsvgd_gram_fwd(const void *X, const void *Y, int A, int B, int T, int d, i
     if (rc) return rc;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr,
                   K_out, nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    if (check_norm_fused("gram_fwd", flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (check_flags(kGramFwd, flags)) return SIGSVGD_E_UNSUPPORTED;
     Range range("sigsvgd_gram_fwd");
     if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) return gram_norm_fused(p);
     return dispatch(p);
@@ -624,10 +623,9 @@ int sigsvgd_gram_fwd_bwd(const void *X, const void *Y, int A, int B, int T, int 
     if (rc) return rc;
     if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_fwd for forward only)");
     if ((flags & SIGSVGD_FLAG_Y_IS_X) && A != B) return bad_arg("Y_IS_X needs A == B");
-    if (no_exact_adjoint("gram_fwd_bwd", flags)) return SIGSVGD_E_UNSUPPORTED;
+    if (check_flags(kGramFwdBwd, flags)) return SIGSVGD_E_UNSUPPORTED;
     GramProblem p{X, Y, A, B, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out,
                   K_out, gradX_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    if (check_norm_fused("gram_fwd_bwd", flags)) return SIGSVGD_E_UNSUPPORTED;
     Range range("sigsvgd_gram_fwd_bwd");
     if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) return gram_norm_fused(p);
     return dispatch(p);
@@ -641,12 +639,7 @@ int sigsvgd_gram_sym_partial(const void *X, int N, int T, int d, int dtype, doub
     int rc = check_common(X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags, K_partial);
     if (rc) return rc;
     if (!grad_partial) return bad_arg("grad_partial == NULL");
-    if (no_exact_adjoint("sym_partial", flags)) return SIGSVGD_E_UNSUPPORTED;
-    if (flags & SIGSVGD_FLAG_NORMALIZED_FUSED) {
-        set_error("sym_partial: SIGSVGD_FLAG_NORMALIZED_FUSED is not built for the partial solve (sigsvgd_gram_fwd, "
-                  "sigsvgd_gram_fwd_bwd and sigsvgd_gram_workspace_bytes take it)");
-        return SIGSVGD_E_UNSUPPORTED;
-    }
+    if (check_flags(kSymPartial, flags)) return SIGSVGD_E_UNSUPPORTED;
     GramProblem p{X, X, N, N, T, d, dtype, inv_h, 0, static_kind, flags | SIGSVGD_FLAG_Y_IS_X, grad_out,
                   K_partial, grad_partial, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
     const GramRoute r = gram_route(p, true);
@@ -811,7 +804,7 @@ int sigsvgd_signature_backward(const void *X, const void *grad_sig, int N, int L
 int sigsvgd_pde_workspace_bytes(int npairs, int M, int N, int dyadic_order, int want_grad, unsigned flags, size_t *bytes)
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
-    const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags, want_grad != 0);
+    const int rc = check_pde(npairs, M, N, SIGSVGD_F64, dyadic_order, flags, kPde, reverse_if(want_grad));
     if (rc) return rc;
     return pde_workspace(npairs, M, N, dyadic_order, want_grad ? 1 : 0, bytes);
 }
@@ -820,7 +813,7 @@ int sigsvgd_pde_fwd(const void *G, int npairs, int M, int N, int dtype, int dyad
                     void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!G || !K_out) return bad_arg("pde_fwd: null pointer argument");
-    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags);
+    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags, kPde, FORWARD);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd");
     return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0, false, nullptr, K_out,
@@ -831,7 +824,7 @@ int sigsvgd_pde_fwd_bwd(const void *G, int npairs, int M, int N, int dtype, int 
                         const void *grad_out, void *K_out, void *dG_out, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!G || !K_out || !dG_out) return bad_arg("pde_fwd_bwd: null pointer argument");
-    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags, true);
+    const int rc = check_pde(npairs, M, N, dtype, dyadic_order, flags, kPde, REVERSE);
     if (rc) return rc;
     Range range("sigsvgd_pde_fwd_bwd");
     return pde_launch(G, npairs, M, N, dtype, dyadic_order, (flags & SIGSVGD_FLAG_NAIVE_SOLVER) != 0,
@@ -846,7 +839,7 @@ int sigsvgd_gram_long_workspace_bytes(int A, int B, int TX, int TY, int d, int d
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long(p, false, want_grad != 0);
+    const int rc = check_long(p, QUERY, kLong, reverse_if(want_grad));
     if (rc) return rc;
     return long_workspace(p, want_grad ? 1 : 0, bytes);
 }
@@ -857,7 +850,7 @@ int sigsvgd_gram_long_fwd(const void *X, const void *Y, int A, int B, int TX, in
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr, K_out, nullptr, nullptr,
                         workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long(p, true);
+    const int rc = check_long(p, LAUNCH, kLong, FORWARD);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd");
     return long_launch(p);
@@ -869,7 +862,7 @@ int sigsvgd_gram_long_fwd_bwd(const void *X, const void *Y, int A, int B, int TX
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long(p, true, true);
+    const int rc = check_long(p, LAUNCH, kLong, REVERSE);
     if (rc) return rc;
     if (!gradX_out) return bad_arg("gradX_out == NULL (use sigsvgd_gram_long_fwd for forward only)");
     Range range("sigsvgd_gram_long_fwd_bwd");
@@ -881,7 +874,7 @@ int sigsvgd_pair_workspace_bytes(int A, int TX, int TY, int d, int dyadic_order,
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false, want_grad != 0, true);
+    const int rc = check_pair(p, QUERY, kPair, reverse_if(want_grad));
     if (rc) return rc;
     return pair_workspace(p, want_grad ? 1 : 0, bytes);
 }
@@ -891,7 +884,7 @@ int sigsvgd_pair_schedule(int A, int TX, int TY, int d, int dyadic_order, int st
 {
     if (!waves_per_pair || !grid || !lds_bytes) return bad_arg("pair: schedule query without a place for its answer");
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_pair(p, false, want_grad != 0, true);
+    const int rc = check_pair(p, QUERY, kPair, reverse_if(want_grad));
     if (rc) return rc;
     return pair_schedule(p, want_grad ? 1 : 0, waves_per_pair, grid, lds_bytes);
 }
@@ -902,7 +895,7 @@ int sigsvgd_pair_fwd(const void *X, const void *Y, int A, int TX, int TY, int d,
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, nullptr, K_out, nullptr, nullptr,
                         workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_pair(p, true, false, true);
+    const int rc = check_pair(p, LAUNCH, kPair, FORWARD);
     if (rc) return rc;
     Range range("sigsvgd_pair_fwd");
     return pair_launch(p);
@@ -914,7 +907,7 @@ int sigsvgd_pair_fwd_bwd(const void *X, const void *Y, int A, int TX, int TY, in
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_pair(p, true, true, true);
+    const int rc = check_pair(p, LAUNCH, kPair, REVERSE);
     if (rc) return rc;
     if (!gradX_out && !gradY_out)
         return bad_arg("pair: gradX_out and gradY_out both NULL (use sigsvgd_pair_fwd for forward only)");
@@ -927,7 +920,7 @@ int sigsvgd_gram_long2_workspace_bytes(int A, int B, int TX, int TY, int d, int 
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long2(p, false, want_gradY != 0, want_gradX || want_gradY, true, true);
+    const int rc = check_long2(p, QUERY, kLong2, reverse_if(want_gradX || want_gradY), want_gradY != 0);
     if (rc) return rc;
     return long2_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
@@ -938,7 +931,7 @@ int sigsvgd_gram_long_fwd_bwd2(const void *X, const void *Y, int A, int B, int T
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long2(p, true, gradY_out != nullptr, gradX_out || gradY_out, true, true); // (neither: forward only)
+    const int rc = check_long2(p, LAUNCH, kLong2, reverse_if(gradX_out || gradY_out), gradY_out != nullptr);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd2");
     return long2_launch(p);
@@ -949,8 +942,8 @@ int sigsvgd_gram_long_h_workspace_bytes(int A, int B, int TX, int TY, int d, int
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, B, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    int rc = check_long2(p, false, want_gradY != 0, true); // (the launch always runs the reverse sweep)
-    if (!rc) rc = check_bandwidth("gram_long_h", p, false, nullptr);
+    int rc = check_long2(p, QUERY, kLongH, REVERSE, want_gradY != 0); // (the launch always runs the reverse sweep)
+    if (!rc) rc = check_bandwidth("gram_long_h", p, QUERY, nullptr);
     if (rc) return rc;
     return long2_h_workspace(p, want_gradX ? 1 : 0, want_gradY ? 1 : 0, bytes);
 }
@@ -962,8 +955,8 @@ int sigsvgd_gram_long_fwd_bwd_h(const void *X, const void *Y, int A, int B, int 
 {
     const LongProblem p{X, Y, A, B, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    int rc = check_long2(p, true, gradY_out != nullptr, true);
-    if (!rc) rc = check_bandwidth("gram_long_h", p, true, dK_dinvh_out);
+    int rc = check_long2(p, LAUNCH, kLongH, REVERSE, gradY_out != nullptr);
+    if (!rc) rc = check_bandwidth("gram_long_h", p, LAUNCH, dK_dinvh_out);
     if (rc) return rc;
     Range range("sigsvgd_gram_long_fwd_bwd_h");
     return long2_h_launch(p, dK_dinvh_out);
@@ -974,8 +967,8 @@ int sigsvgd_pair_h_workspace_bytes(int A, int TX, int TY, int d, int dyadic_orde
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, A, 1, TX, TY, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    int rc = check_pair(p, false, true);
-    if (!rc) rc = check_bandwidth("pair_h", p, false, nullptr);
+    int rc = check_pair(p, QUERY, kPairH, REVERSE);
+    if (!rc) rc = check_bandwidth("pair_h", p, QUERY, nullptr);
     if (rc) return rc;
     return pair_workspace(p, 1, bytes); // (the launch always runs the reverse sweep)
 }
@@ -987,8 +980,8 @@ int sigsvgd_pair_fwd_bwd_h(const void *X, const void *Y, int A, int TX, int TY, 
 {
     const LongProblem p{X, Y, A, 1, TX, TY, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_out, gradX_out,
                         gradY_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    int rc = check_pair(p, true, true);
-    if (!rc) rc = check_bandwidth("pair_h", p, true, dK_dinvh_out);
+    int rc = check_pair(p, LAUNCH, kPairH, REVERSE);
+    if (!rc) rc = check_bandwidth("pair_h", p, LAUNCH, dK_dinvh_out);
     if (rc) return rc;
     Range range("sigsvgd_pair_fwd_bwd_h");
     return pair_h_launch(p, dK_dinvh_out);
@@ -999,7 +992,7 @@ int sigsvgd_gram_long_partial_plan(int N, int T, int d, int dyadic_order, int st
 {
     if (!tile_rows || !tile_cols) return bad_arg("gram_long_partial_plan: tile_rows / tile_cols == NULL");
     const LongProblem p{nullptr, nullptr, N, N, T, T, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long_partial(p, false, 0, tile_stride);
+    const int rc = check_long_partial(p, QUERY, kLongPartial, 0, tile_stride);
     if (rc) return rc;
     return long_part_tiles(p, tile_stride, tile_rows, tile_cols);
 }
@@ -1009,7 +1002,7 @@ int sigsvgd_gram_long_partial_workspace_bytes(int N, int T, int d, int dyadic_or
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     const LongProblem p{nullptr, nullptr, N, N, T, T, d, SIGSVGD_F32, 0.0, dyadic_order, static_kind, flags};
-    const int rc = check_long_partial(p, false, tile_offset, tile_stride);
+    const int rc = check_long_partial(p, QUERY, kLongPartial, tile_offset, tile_stride);
     if (rc) return rc;
     return long_part_workspace(p, tile_offset, tile_stride, bytes);
 }
@@ -1020,7 +1013,7 @@ int sigsvgd_gram_long_sym_partial(const void *X, int N, int T, int d, int dtype,
 {
     const LongProblem p{X, X, N, N, T, T, d, dtype, inv_h, dyadic_order, static_kind, flags, grad_out, K_partial, grad_partial,
                         nullptr, workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
-    const int rc = check_long_partial(p, true, tile_offset, tile_stride);
+    const int rc = check_long_partial(p, LAUNCH, kLongPartial, tile_offset, tile_stride);
     if (rc) return rc;
     if (!grad_partial) return bad_arg("gram_long_sym_partial: grad_partial == NULL");
     Range range("sigsvgd_gram_long_sym_partial");
@@ -1032,7 +1025,7 @@ int sigsvgd_sqdist_select_workspace_bytes(int A, int B, int TX, int TY, int d, u
 {
     if (no_bytes(bytes)) return SIGSVGD_E_BADARG;
     unsigned long long n = 0;
-    const int rc = check_select(A, B, TX, TY, d, flags, &n);
+    const int rc = check_select(A, B, TX, TY, d, flags, kSelect, &n);
     if (rc) return rc;
     *bytes = select_workspace_bytes();
     return SIGSVGD_OK;
@@ -1043,7 +1036,7 @@ int sigsvgd_sqdist_select(const void *X, const void *Y, int A, int B, int TX, in
 {
     if (!X || !Y || !out_device) return bad_arg("sqdist_select: null pointer argument");
     unsigned long long n = 0;
-    const int rc = check_select(A, B, TX, TY, d, flags, &n);
+    const int rc = check_select(A, B, TX, TY, d, flags, kSelect, &n);
     if (rc) return rc;
     if (dtype != SIGSVGD_F32 && dtype != SIGSVGD_F64) return bad_arg("sqdist_select: bad dtype %d", dtype);
     if (rank >= n) return bad_arg("sqdist_select: rank %llu outside the %llu elements", rank, n);

@@ -132,33 +132,22 @@ def _prep_paths(X: torch.Tensor, Y: torch.Tensor):
     return pad_to_length(X.detach(), T).contiguous(), pad_to_length(Y.detach(), T).contiguous()
 
 
-def _flags(naive: bool, sym: bool, y_is_x: bool, force_generic: bool, stored_forward: bool = False,
-           fp32_sweeps: bool = False, exact_adjoint: bool = False, nan_tails: bool = False, log_k: bool = False,
-           normalized: bool = False, normalized_fused: bool = False) -> int:
-    f = 0
-    if normalized:
-        f |= _lib.FLAG_NORMALIZED
-    if normalized_fused:
-        f |= _lib.FLAG_NORMALIZED_FUSED
-    if log_k:
-        f |= _lib.FLAG_LOG_K
-    if nan_tails:
-        f |= _lib.FLAG_NAN_TAILS
-    if naive:
-        f |= _lib.FLAG_NAIVE_SOLVER
-    if sym:
-        f |= _lib.FLAG_SYM
-    if y_is_x:
-        f |= _lib.FLAG_Y_IS_X
-    if force_generic:
-        f |= _lib.FLAG_FORCE_GENERIC
-    if stored_forward:
-        f |= _lib.FLAG_STORED_FORWARD
-    if fp32_sweeps:
-        f |= _lib.FLAG_FP32_SWEEPS
-    if exact_adjoint:
-        f |= _lib.FLAG_EXACT_ADJOINT
-    return f
+# the settings of a launch, by the names the wrappers give them, as the bits of include/sigsvgd_hip.h
+_FLAG_BITS = {"naive": _lib.FLAG_NAIVE_SOLVER, "sym": _lib.FLAG_SYM, "y_is_x": _lib.FLAG_Y_IS_X,
+              "force_generic": _lib.FLAG_FORCE_GENERIC, "stored_forward": _lib.FLAG_STORED_FORWARD,
+              "fp32_sweeps": _lib.FLAG_FP32_SWEEPS, "exact_adjoint": _lib.FLAG_EXACT_ADJOINT, "nan_tails": _lib.FLAG_NAN_TAILS,
+              "log_k": _lib.FLAG_LOG_K, "normalized": _lib.FLAG_NORMALIZED, "normalized_fused": _lib.FLAG_NORMALIZED_FUSED,
+              "fold": _lib.FLAG_FOLD_TILES}
+
+
+def _flags(*in_table_order, **named) -> int:
+    """The flag word of the settings that are true, by their names in `_FLAG_BITS`; a name it does not hold is a TypeError.
+    This package passes names only; values without one are read in the table's order, as the per-flag tests of tests/ state
+    the bits of earlier versions."""
+    if len(in_table_order) > len(_FLAG_BITS) or not named.keys() <= _FLAG_BITS.keys() - list(_FLAG_BITS)[:len(in_table_order)]:
+        raise TypeError(f"_flags takes {', '.join(_FLAG_BITS)}, each once; got {len(in_table_order)} values and {sorted(named)}")
+    named.update(zip(_FLAG_BITS, in_table_order))
+    return sum(_FLAG_BITS[name] for name, on in named.items() if on)
 
 
 def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -172,8 +161,8 @@ def gram_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
     B = Yc.shape[0]
     if y_is_x and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x needs X and Y of one shape")
-    flags = _flags(naive, False, bool(y_is_x) and A == B, force_generic, stored_forward, fp32_sweeps,
-                   normalized_fused=normalized)
+    flags = _flags(naive=naive, y_is_x=bool(y_is_x) and A == B, force_generic=force_generic, stored_forward=stored_forward,
+                   fp32_sweeps=fp32_sweeps, normalized_fused=normalized)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
                               int(static_kind), flags, K.data_ptr()),
@@ -198,7 +187,7 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     Bit-reproducible: every reduction over pairs runs in an order fixed by the launch geometry (no floating-point
     atomics), so two calls on the same input -- eager or replayed from a captured graph -- return the same bits.
 
-    Accuracy (include/sigsvgd_hip.h): every entry of K within 1e-5 of the fp64 reference's, relative to max(|K|, 0.1) --
+    Accuracy (include/sigsvgd_hip.h): every entry of K within 1e-5 of the fp64 reference's, plain |K - K_ref| / |K_ref| --
     the fp32-sweep kernels check every pair for cancellation and for its conditioning in the increments and hand the pairs
     that fail to an exact fp64 pass inside the same call; the gradient of such a pair keeps the fp32 solution (its error is
     relative to the largest gradient entry of the launch).  `force_generic=True`: fp64 sweeps for K and the gradient alike.
@@ -216,7 +205,8 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     go = _weights(grad_out, (A, B), Xc.dtype)
     if (y_is_x or sym) and X.shape[1] != Y.shape[1]:
         raise ValueError("y_is_x / sym need X and Y of one shape")
-    flags = _flags(naive, sym, y_is_x, force_generic, stored_forward, fp32_sweeps, normalized_fused=normalized)
+    flags = _flags(naive=naive, sym=sym, y_is_x=y_is_x, force_generic=force_generic, stored_forward=stored_forward,
+                   fp32_sweeps=fp32_sweeps, normalized_fused=normalized)
     K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
     gX = torch.empty((A, T, d), dtype=Xc.dtype, device=dev)
     _launch(dev, "gram_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
@@ -232,7 +222,7 @@ def gram_takes(A: int, B: int, T: int, d: int, dyadic_order: int = 0, static_kin
     library's workspace query for the call's flags, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (the
     per-pair state outgrows the LDS: the long route, `gram_long_fwd*`, takes those; normalized together with naive, or a
     shape whose diagonal pass the paired plan refuses); any other error raises."""
-    flags = _flags(naive, sym and want_grad, bool(y_is_x) and (want_grad or A == B), False, False, fp32_sweeps,
+    flags = _flags(naive=naive, sym=sym and want_grad, y_is_x=bool(y_is_x) and (want_grad or A == B), fp32_sweeps=fp32_sweeps,
                    normalized_fused=normalized)
     return _query("gram_workspace_bytes", (int(A), int(B), int(T), int(d), int(dyadic_order), int(static_kind),
                                            1 if want_grad else 0, flags), (ctypes.c_size_t(0),), may_refuse=True)
@@ -252,20 +242,59 @@ def _prep_long(X, Y):
     return X.detach().contiguous(), Y.detach().to(X.dtype).contiguous()
 
 
+def _prep_pair(X, Y):
+    if X.dim() != 3 or Y.dim() != 3 or X.shape[0] != Y.shape[0]:
+        raise ValueError(f"pairs need X [A, TX, d] and Y [A, TY, d]; got {tuple(X.shape)} and {tuple(Y.shape)}")
+    return _prep_long(X, Y)
+
+
+# ---- the long route: what its seven launches and their queries share -------------------------------------------------------------
+def _long_geometry(pair: bool, A, B, TX, TY, d, dyadic_order, static_kind, wants, flags: int):
+    """-> (shape, query arguments) of a long-route call, the one place that knows their order (`_lib.ARGTYPES`): the shape is
+    A, B, TX, TY, d in the Gram mode and A, TX, TY, d in the paired one; a launch states X, Y, shape, dtype, inv_h, order,
+    kind, flags, its query shape, order, kind, `wants` as 0 / 1, flags."""
+    shape = (int(A), int(TX), int(TY), int(d)) if pair else (int(A), int(B), int(TX), int(TY), int(d))
+    return shape, (*shape, int(dyadic_order), int(static_kind), *(1 if w else 0 for w in wants), flags)
+
+
+def _long_query(query: str, pair: bool, A, B, TX, TY, d, dyadic_order, static_kind, wants, outs=None, **settings) -> bool:
+    """A host-only query of the long route: `_query` with the arguments of `_long_geometry`; without `outs` the `*_takes`
+    question (False exactly where the library reports SIGSVGD_E_UNSUPPORTED)."""
+    _, qargs = _long_geometry(pair, A, B, TX, TY, d, dyadic_order, static_kind, wants, _flags(**settings))
+    return _query(query, qargs, outs or (ctypes.c_size_t(0),), may_refuse=outs is None)
+
+
+def _long_launch(name: str, query: str, X, Y, inv_h, dyadic_order, static_kind, wants, pair: bool = False, weights=(),
+                 grads=(), with_dK: bool = False, **settings):
+    """A launch of the long route, -> (K, the gradient of each slot in `grads` or None, dK_dinvh if `with_dK`): the paths
+    prepared, K [A, B] (`pair`: [A]) and the outputs allocated in X's dtype, `sigsvgd_<name>` launched with the workspace of
+    `sigsvgd_<query>(..., *wants, flags)`.  weights: (grad_out,) where the entry point has the argument; grads: one want per
+    gradient output the entry point has (X's, then Y's); settings: the keywords of `_flags`."""
+    dev = _require_gpu(X, Y, *weights)
+    Xc, Yc = (_prep_pair if pair else _prep_long)(X, Y)
+    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
+    if (settings.get("sym") or settings.get("y_is_x")) and (A != B or TX != TY):
+        raise ValueError("sym and y_is_x need X and Y of one shape")
+    flags = _flags(**settings)
+    shape, qargs = _long_geometry(pair, A, B, TX, TY, d, dyadic_order, static_kind, wants, flags)
+    new = lambda *size: torch.empty(size, dtype=Xc.dtype, device=dev)
+    outs = [new(*shape[:1 if pair else 2])]
+    go = [_weights(w, outs[0].shape, Xc.dtype) for w in weights]
+    outs += [new(*size) if want else None for want, size in zip(grads, ((A, TX, d), (B, TY, d)))]
+    if with_dK:
+        outs.append(new(*outs[0].shape))
+    _launch(dev, name, (Xc.data_ptr(), Yc.data_ptr(), *shape, _io_dtype(Xc), float(inv_h), int(dyadic_order), int(static_kind),
+                        flags, *map(_ptr, go + outs)), query, qargs)
+    return tuple(outs)
+
+
 def gram_long_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                   naive: bool = False) -> torch.Tensor:
     """K[A,B] of the built-in static kernels on long paths (`sigsvgd_gram_long_fwd`, csrc/gram_long.hip): the launches
     `gram_fwd` refuses for LDS.  X [A,TX,d] and Y [B,TY,d] at their own lengths; fp64 increments and sweeps, K in X's
     dtype."""
-    dev = _require_gpu(X, Y)
-    Xc, Yc = _prep_long(X, Y)
-    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
-    flags = _flags(naive, False, False, False)
-    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    _launch(dev, "gram_long_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                   int(dyadic_order), int(static_kind), flags, K.data_ptr()),
-            "gram_long_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags))
-    return K
+    return _long_launch("gram_long_fwd", "gram_long_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, (0,),
+                        naive=naive)[0]
 
 
 def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -278,19 +307,8 @@ def gram_long_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: in
     gradient launch of the long route below): gX is the exact derivative of the discrete K returned -- the adjoint of the
     default stencil itself -- instead of the reference's GG convention, which differs from it by per cents; K has the
     same bits, the workspace the same bytes.  With naive=True (where GG is exact) it changes nothing."""
-    dev = _require_gpu(X, Y, grad_out)
-    Xc, Yc = _prep_long(X, Y)
-    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
-    go = _weights(grad_out, (A, B), Xc.dtype)
-    if sym and (A != B or TX != TY):
-        raise ValueError("sym needs X and Y of one shape")
-    flags = _flags(naive, sym, False, False, exact_adjoint=exact_adjoint)
-    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev)
-    _launch(dev, "gram_long_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                       int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), gX.data_ptr()),
-            "gram_long_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags))
-    return K, gX
+    return _long_launch("gram_long_fwd_bwd", "gram_long_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, (1,),
+                        weights=(grad_out,), grads=(True,), naive=naive, sym=sym, exact_adjoint=exact_adjoint)
 
 
 def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -301,11 +319,9 @@ def gram_long2_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either; normalized together with any of
     the three); any other error raises."""
-    return _query("gram_long2_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                                 1 if want_gradX else 0, 1 if want_gradY else 0,
-                                                 _flags(False, False, y_is_x, False, exact_adjoint=exact_adjoint,
-                                                        nan_tails=nan_tails, log_k=log_k, normalized=normalized)),
-                  (ctypes.c_size_t(0),), may_refuse=True)
+    return _long_query("gram_long2_workspace_bytes", False, A, B, TX, TY, d, dyadic_order, static_kind,
+                       (want_gradX, want_gradY), y_is_x=y_is_x, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k,
+                       normalized=normalized)
 
 
 def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -329,24 +345,10 @@ def gram_long_fwd_bwd2(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: i
     sum(grad_out * K^), the diagonals' dependence included, each slot its own; with y_is_x gX is the gradient in X_i of
     sum_j grad_out_ij K^(X_i, Y_j) at fixed Y = X (SVGD's), and K^'s diagonal is exactly 1.  Every pair is solved once.  Not
     with naive, exact_adjoint, nan_tails or log_k."""
-    dev = _require_gpu(X, Y, grad_out)
-    Xc, Yc = _prep_long(X, Y)
-    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
-    if (sym or y_is_x) and (A != B or TX != TY):
-        raise ValueError("sym and y_is_x need X and Y of one shape")
-    want_gradY = bool(want_gradY) and not (sym or y_is_x)
-    go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k,
-                   normalized=normalized)
-    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
-    gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
-    _launch(dev, "gram_long_fwd_bwd2", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                        int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX),
-                                        _ptr(gY)),
-            "gram_long2_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1 if want_gradX else 0,
-                                           1 if want_gradY else 0, flags))
-    return K, gX, gY
+    wants = (want_gradX, bool(want_gradY) and not (sym or y_is_x))
+    return _long_launch("gram_long_fwd_bwd2", "gram_long2_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, wants,
+                        weights=(grad_out,), grads=wants, naive=naive, sym=sym, y_is_x=y_is_x, exact_adjoint=exact_adjoint,
+                        nan_tails=nan_tails, log_k=log_k, normalized=normalized)
 
 
 def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -354,10 +356,8 @@ def pair_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_k
     """Whether `pair_fwd` (want_grad False) / `pair_fwd_bwd` take pairs X [A, TX, d], Y [A, TY, d]: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, or per-wave
     state beyond the LDS; nan_tails together with exact_adjoint; log_k together with either); any other error raises."""
-    return _query("pair_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                           1 if want_grad else 0, _flags(False, False, False, False, exact_adjoint=exact_adjoint,
-                                                                         nan_tails=nan_tails, log_k=log_k)),
-                  (ctypes.c_size_t(0),), may_refuse=True)
+    return _long_query("pair_workspace_bytes", True, A, A, TX, TY, d, dyadic_order, static_kind, (want_grad,),
+                       exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
 
 
 def pair_schedule(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -368,16 +368,9 @@ def pair_schedule(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, stati
     of csrc/pair_bands.hip.  The results do not depend on it, bit for bit.  exact_adjoint: gradient launches with it always
     run 1 wave per pair, and so does every launch with nan_tails or log_k."""
     waves, grid, lds = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_size_t(0)
-    _query("pair_schedule", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind), 1 if want_grad else 0,
-                             _flags(False, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)),
-           (waves, grid, lds))
+    _long_query("pair_schedule", True, A, A, TX, TY, d, dyadic_order, static_kind, (want_grad,), (waves, grid, lds),
+                exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
     return waves.value, grid.value, lds.value
-
-
-def _prep_pair(X, Y):
-    if X.dim() != 3 or Y.dim() != 3 or X.shape[0] != Y.shape[0]:
-        raise ValueError(f"pairs need X [A, TX, d] and Y [A, TY, d]; got {tuple(X.shape)} and {tuple(Y.shape)}")
-    return _prep_long(X, Y)
 
 
 def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -385,15 +378,8 @@ def pair_fwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.
     """K[A] = k_sig(X_i, Y_i) of the built-in static kernels (`sigsvgd_pair_fwd`, the paired mode of csrc/gram_long.hip): one
     solve per pair.  X [A,TX,d] and Y [A,TY,d] at their own lengths; fp64 increments and sweeps, K in X's dtype, bit-identical
     to the diagonal of `gram_long_fwd(X, Y)`.  log_k: ln K, bit-identical to the diagonal of the two-sided launch with log_k."""
-    dev = _require_gpu(X, Y)
-    Xc, Yc = _prep_pair(X, Y)
-    (A, TX, d), TY = Xc.shape, Yc.shape[1]
-    flags = _flags(naive, False, False, False, nan_tails=nan_tails, log_k=log_k)
-    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
-    _launch(dev, "pair_fwd", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
-                              int(static_kind), flags, K.data_ptr()),
-            "pair_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), 0, flags))
-    return K
+    return _long_launch("pair_fwd", "pair_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, (0,), pair=True,
+                        naive=naive, nan_tails=nan_tails, log_k=log_k)[0]
 
 
 def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -405,18 +391,9 @@ def pair_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     and returned in X's dtype; bit-reproducible."""
     if not (want_x or want_y):
         raise ValueError("pair_fwd_bwd needs want_x or want_y (pair_fwd for the forward only)")
-    dev = _require_gpu(X, Y, grad_out)
-    Xc, Yc = _prep_pair(X, Y)
-    (A, TX, d), TY = Xc.shape, Yc.shape[1]
-    go = _weights(grad_out, (A,), Xc.dtype)
-    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint, nan_tails=nan_tails, log_k=log_k)
-    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
-    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
-    gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
-    _launch(dev, "pair_fwd_bwd", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                  int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX), _ptr(gY)),
-            "pair_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), 1, flags))
-    return K, gX, gY
+    return _long_launch("pair_fwd_bwd", "pair_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, (1,), pair=True,
+                        weights=(grad_out,), grads=(want_x, want_y), naive=naive, exact_adjoint=exact_adjoint,
+                        nan_tails=nan_tails, log_k=log_k)
 
 
 def gram_long_h_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -425,10 +402,8 @@ def gram_long_h_takes(A: int, B: int, TX: int, TY: int, d: int, dyadic_order: in
     """Whether `gram_long_fwd_bwd_h` takes paths X [A, TX, d] x Y [B, TY, d] with these outputs: the library's workspace
     query, host only.  False exactly where it reports SIGSVGD_E_UNSUPPORTED (past 8192 refined cells on a side, per-wave
     state beyond the LDS, or the first-order stencil with IMQ / rational quadratic / Matern); any other error raises."""
-    return _query("gram_long_h_workspace_bytes", (int(A), int(B), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                                  1 if want_gradX else 0, 1 if want_gradY else 0,
-                                                  _flags(naive, False, y_is_x, False, exact_adjoint=exact_adjoint)),
-                  (ctypes.c_size_t(0),), may_refuse=True)
+    return _long_query("gram_long_h_workspace_bytes", False, A, B, TX, TY, d, dyadic_order, static_kind,
+                       (want_gradX, want_gradY), naive=naive, y_is_x=y_is_x, exact_adjoint=exact_adjoint)
 
 
 def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -439,33 +414,18 @@ def gram_long_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: 
     RBF, IMQ, rational quadratic and Matern).  dK_dinvh is unweighted -- grad_out and sym weight gX and gY only -- and with y_is_x
     exactly symmetric; dK/dsigma = -inv_h^2 dK_dinvh.  K, gX and gY have the bits `gram_long_fwd_bwd2` returns.  Neither
     gradient wanted: the reverse sweep still runs.  Bit-reproducible."""
-    dev = _require_gpu(X, Y, grad_out)
-    Xc, Yc = _prep_long(X, Y)
-    (A, TX, d), (B, TY) = Xc.shape, Yc.shape[:2]
-    if (sym or y_is_x) and (A != B or TX != TY):
-        raise ValueError("sym and y_is_x need X and Y of one shape")
-    want_gradY = bool(want_gradY) and not (sym or y_is_x)
-    go = _weights(grad_out, (A, B), Xc.dtype)
-    flags = _flags(naive, sym, y_is_x, False, exact_adjoint=exact_adjoint)
-    K = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    dK = torch.empty((A, B), dtype=Xc.dtype, device=dev)
-    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_gradX else None
-    gY = torch.empty((B, TY, d), dtype=Xc.dtype, device=dev) if want_gradY else None
-    _launch(dev, "gram_long_fwd_bwd_h", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                         int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX),
-                                         _ptr(gY), dK.data_ptr()),
-            "gram_long_h_workspace_bytes", (A, B, TX, TY, d, int(dyadic_order), int(static_kind), 1 if want_gradX else 0,
-                                            1 if want_gradY else 0, flags))
-    return K, gX, gY, dK
+    wants = (want_gradX, bool(want_gradY) and not (sym or y_is_x))
+    return _long_launch("gram_long_fwd_bwd_h", "gram_long_h_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, wants,
+                        weights=(grad_out,), grads=wants, with_dK=True, naive=naive, sym=sym, y_is_x=y_is_x,
+                        exact_adjoint=exact_adjoint)
 
 
 def pair_h_takes(A: int, TX: int, TY: int, d: int, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
                  naive: bool = False, exact_adjoint: bool = False) -> bool:
     """Whether `pair_fwd_bwd_h` takes pairs X [A, TX, d], Y [A, TY, d]: the library's workspace query, host only.  False
     exactly where it reports SIGSVGD_E_UNSUPPORTED (as `gram_long_h_takes`); any other error raises."""
-    return _query("pair_h_workspace_bytes", (int(A), int(TX), int(TY), int(d), int(dyadic_order), int(static_kind),
-                                             _flags(naive, False, False, False, exact_adjoint=exact_adjoint)),
-                  (ctypes.c_size_t(0),), may_refuse=True)
+    return _long_query("pair_h_workspace_bytes", True, A, A, TX, TY, d, dyadic_order, static_kind, (), naive=naive,
+                       exact_adjoint=exact_adjoint)
 
 
 def pair_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _lib.STATIC_RBF,
@@ -475,20 +435,8 @@ def pair_fwd_bwd_h(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int =
     inverse bandwidth (`sigsvgd_pair_fwd_bwd_h`), unweighted; equal, bit for bit, to the diagonal of
     `gram_long_fwd_bwd_h`'s.  K, gX and gY have the bits `pair_fwd_bwd` returns; neither gradient wanted is allowed.  Always
     the one-wavefront schedule."""
-    dev = _require_gpu(X, Y, grad_out)
-    Xc, Yc = _prep_pair(X, Y)
-    (A, TX, d), TY = Xc.shape, Yc.shape[1]
-    go = _weights(grad_out, (A,), Xc.dtype)
-    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint)
-    K = torch.empty((A,), dtype=Xc.dtype, device=dev)
-    dK = torch.empty((A,), dtype=Xc.dtype, device=dev)
-    gX = torch.empty((A, TX, d), dtype=Xc.dtype, device=dev) if want_x else None
-    gY = torch.empty((A, TY, d), dtype=Xc.dtype, device=dev) if want_y else None
-    _launch(dev, "pair_fwd_bwd_h", (Xc.data_ptr(), Yc.data_ptr(), A, TX, TY, d, _io_dtype(Xc), float(inv_h),
-                                    int(dyadic_order), int(static_kind), flags, _ptr(go), K.data_ptr(), _ptr(gX), _ptr(gY),
-                                    dK.data_ptr()),
-            "pair_h_workspace_bytes", (A, TX, TY, d, int(dyadic_order), int(static_kind), flags))
-    return K, gX, gY, dK
+    return _long_launch("pair_fwd_bwd_h", "pair_h_workspace_bytes", X, Y, inv_h, dyadic_order, static_kind, (), pair=True,
+                        weights=(grad_out,), grads=(want_x, want_y), with_dK=True, naive=naive, exact_adjoint=exact_adjoint)
 
 
 def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] = None) -> torch.Tensor:
@@ -512,7 +460,7 @@ def path_sqdist_select(X, Y: Optional[torch.Tensor] = None, rank: Optional[int] 
     rank = (n - 1) // 2 if rank is None else int(rank)
     if not 0 <= rank < n:
         raise ValueError(f"rank {rank} outside the {n} elements")
-    flags = _lib.FLAG_Y_IS_X if Y is None else 0
+    flags = _flags(y_is_x=Y is None)
     out = torch.empty((), dtype=torch.float64, device=dev)
     _launch(dev, "sqdist_select", (Xc.data_ptr(), Yc.data_ptr(), A, B, TX, TY, d, _io_dtype(Xc), flags, rank, out.data_ptr()),
             "sqdist_select_workspace_bytes", (A, B, TX, TY, d, flags))
@@ -690,7 +638,7 @@ def gram_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, static
     N, T, d = Xc.shape
     go = _weights(grad_out, (N, N), Xc.dtype)
     Kp, gp = _partial_out(out, Xc, dev)
-    flags = _flags(False, sym, True, False, False, fp32_sweeps) | (_lib.FLAG_FOLD_TILES if fold else 0)
+    flags = _flags(sym=sym, y_is_x=True, fp32_sweeps=fp32_sweeps, fold=fold)
     _launch(dev, "gram_sym_partial", (Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(static_kind), flags,
                                       int(tile_offset), int(tile_stride), _ptr(go), Kp.data_ptr(), gp.data_ptr()),
             "gram_workspace_bytes", (N, N, T, d, 0, int(static_kind), 1, flags))
@@ -737,7 +685,7 @@ def gram_long_sym_partial(X, inv_h: float, tile_offset: int, tile_stride: int, d
     N, T, d = Xc.shape
     go = _weights(grad_out, (N, N), Xc.dtype)
     Kp, gp = _partial_out(out, Xc, dev)
-    flags = _flags(naive, sym, True, False) | (_lib.FLAG_FOLD_TILES if fold else 0)
+    flags = _flags(naive=naive, sym=sym, y_is_x=True, fold=fold)
     _launch(dev, "gram_long_sym_partial", (Xc.data_ptr(), N, T, d, _io_dtype(Xc), float(inv_h), int(dyadic_order),
                                            int(static_kind), flags, int(tile_offset), int(tile_stride), _ptr(go),
                                            Kp.data_ptr(), gp.data_ptr()),
@@ -982,7 +930,7 @@ def pde_fwd(G, dyadic_order: int = 0, naive: bool = False) -> torch.Tensor:
     dev = _require_gpu(G)
     Gc = _prep_grid(G)
     npairs, M, N = Gc.shape
-    flags = _lib.FLAG_NAIVE_SOLVER if naive else 0
+    flags = _flags(naive=naive)
     K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
     _launch(dev, "pde_fwd", (Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, K.data_ptr()),
             "pde_workspace_bytes", (npairs, M, N, int(dyadic_order), 0, flags))
@@ -1003,7 +951,7 @@ def pde_fwd_bwd(G, dyadic_order: int = 0, grad_out: Optional[torch.Tensor] = Non
         if grad_out.numel() != npairs:
             raise ValueError(f"grad_out must have {npairs} entries, got {tuple(grad_out.shape)}")
         go = grad_out.detach().reshape(npairs).to(Gc.dtype).contiguous()
-    flags = _flags(naive, False, False, False, exact_adjoint=exact_adjoint)
+    flags = _flags(naive=naive, exact_adjoint=exact_adjoint)
     K = torch.empty(npairs, dtype=Gc.dtype, device=dev)
     dG = torch.empty_like(Gc)
     _launch(dev, "pde_fwd_bwd", (Gc.data_ptr(), npairs, M, N, _io_dtype(Gc), int(dyadic_order), flags, _ptr(go),
