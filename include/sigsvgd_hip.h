@@ -54,7 +54,9 @@
  *     64 .. 256 cells per side: the reference's own call shapes): fp64 static kernel + 4-corner
  *     increments, fp32 PDE sweeps in difference form, fp32 storage of per-pair intermediates, fp32
  *     gradient contraction, fp64 reduction over pairs; the coverage kernel (other refinements, longer
- *     paths, linear kernel, naive solver, SIGSVGD_FLAG_FORCE_GENERIC) is fp64 end to end (DESIGN.md
+ *     paths, more than 16 channels -- except RBF paths of 17 to 32 channels at dyadic order 0, 3 <= T <= 64 with
+ *     SIGSVGD_FLAG_FP32_SWEEPS, which take the register-resident kernel: see the flag --, linear kernel, naive solver,
+ *     SIGSVGD_FLAG_FORCE_GENERIC) is fp64 end to end (DESIGN.md
  *     "precision plan").  The fp32 route is checked PER PAIR and a pair that fails a check has its K solved
  *     again by the coverage kernel in fp64 (static kernel, increments, sweeps) inside the same call:
  *       (1) cancellation -- the largest |K| on the pair's PDE grid exceeds 2x .. 8x max(|K|, 0.1)
@@ -185,7 +187,13 @@ extern "C" {
                                       /* sigsvgd_gram_sym_partial take it.  One-channel Gram + gradient launches stay on the coverage      */
                                       /* kernel as for RBF; with any other kind, shape, order, SIGSVGD_FLAG_NAIVE_SOLVER or                */
                                       /* SIGSVGD_FLAG_FORCE_GENERIC the bit is accepted and ignored (as it was before this revision of     */
-                                      /* ABI 10, which adds no symbol and changes no signature)                                             */
+                                      /* ABI 10, which adds no symbol and changes no signature).                                            */
+                                      /* RBF: at dyadic order 0, 3 <= T <= 64, default stencil, 17 <= d <= 32 the   */
+                                      /* bit sends sigsvgd_gram_fwd / _fwd_bwd (and their _workspace_bytes query) to the same kernel's      */
+                                      /* 32-channel layout, at the same contract, instead of the coverage kernel; opt-in because K and the  */
+                                      /* gradient then are fp32-sweep results where the default route's are fp64 ones.  RBF at d <= 16 runs  */
+                                      /* that kernel by default and the bit changes nothing there; sigsvgd_gram_sym_partial and              */
+                                      /* sigsvgd_gram_sym_tile_rows (which has no flags argument) keep refusing d > 16 with or without it   */
 #define SIGSVGD_FLAG_EXACT_ADJOINT 256u /* gradient launches of the long route (sigsvgd_pde_fwd_bwd, sigsvgd_gram_long_fwd_bwd, _fwd_bwd2,     */
                                       /* _fwd_bwd_h, sigsvgd_pair_fwd_bwd, _fwd_bwd_h): every gradient -- dG_out,      */
                                       /* gradX_out, gradY_out, dK_dinvh_out -- is the exact derivative of the discrete K the launch returns, */

@@ -14,8 +14,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_PKG, "csrc")
 # SIGSVGD_LIB_PATH: A/B benchmarking of two builds on the same GPU box (scripts/ab.py); never set in tests
 LIB_PATH = os.environ.get("SIGSVGD_LIB_PATH") or os.path.join(_PKG, "libsigsvgd_hip.so")
-SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "sweep_host.hip", "gram_quad.hip",
-           "svgd_phi.hip", "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip",
+SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hip", "gram_fast_wide.hip", "sweep_host.hip",
+           "gram_quad.hip", "svgd_phi.hip", "vec_kernels.hip", "vec_fused.hip", "cost_kernels.hip", "sig_backward.hip", "gram_dyad.hip",
            "gram_band.hip", "sig_pde.hip", "gram_long.hip", "gram_long_matern.hip", "pair_bands.hip", "pair_bands_f32.hip",
            "pair_bands_matern.hip", "sqdist_select.hip", "sig_pde_exact.hip", "gram_long_exact.hip",
            "gram_long_exact_matern.hip", "gram_long_nantail.hip", "gram_long_nantail_matern.hip", "gram_long_logk.hip",

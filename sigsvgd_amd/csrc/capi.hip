@@ -411,6 +411,9 @@ static bool band_parallel(int A, int B, int T, int d, int n, bool sym)
 // not take the launch) and keeps them for one-channel paths.
 // SIGSVGD_FLAG_FP32_SWEEPS is the caller's opt-in to the register-resident kernel for the IMQ and
 // rational-quadratic kernels with the default stencil at that kernel's shapes -- the one-channel gradient rule first, as for RBF.
+// For RBF with the default stencil it is the opt-in to the same kernel's 32-channel layout for paths of 17 to 32 channels
+// (fast_wide_supported) -- ordered and Y_IS_X launches only: the partial solve, whose ownership unit
+// sigsvgd_gram_sym_tile_rows answers without a flags argument, keeps refusing d > 16.
 // In every other case the bit changes nothing: without it every route is what it was.
 static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigned flags, int want_grad, bool partial = false)
 {
@@ -419,6 +422,7 @@ static GramRoute gram_route(int A, int B, int T, int d, int n, int kind, unsigne
     if ((flags & SIGSVGD_FLAG_FP32_SWEEPS) && (kind == SIGSVGD_STATIC_IMQ || kind == SIGSVGD_STATIC_RQ) &&
         !(flags & SIGSVGD_FLAG_NAIVE_SOLVER) && fast_supported(T, d, n) && (partial || !(want_grad && d == 1)))
         return GramRoute::Fast;
+    if ((flags & SIGSVGD_FLAG_FP32_SWEEPS) && fp32 && !partial && fast_wide_supported(T, d, n)) return GramRoute::Fast;
     // IMQ, the rational quadratic and the Matern kernels have fp64 kernels only and are held to fp64 results: the plan that keeps
     // the increments in fp64 wherever their table (or the per-band layout) fits, what FORCE_GENERIC selects (DESIGN.md sections
     // 5.15, 5.17)

@@ -1,6 +1,7 @@
 // Host side of the register-resident fast path (n == 0, T <= 64): which shapes it takes, its workspace plan and its two entry
 // points.  The kernel and the launchers of its instantiations are in gram_fast_kernel.h; this unit builds the RBF ones and
-// sends the IMQ / rational-quadratic launches to gram_fast_radial.hip.  The shared launch tail is sweep_host.hip's.
+// sends the IMQ / rational-quadratic launches to gram_fast_radial.hip and the RBF launches of 17 to 32 channels to
+// gram_fast_wide.hip.  The shared launch tail is sweep_host.hip's.
 #include <cstdlib>
 
 #include "gram_fast_kernel.h"
@@ -8,6 +9,8 @@
 namespace sigsvgd {
 
 bool fast_supported(int T, int d, int n) { return n == 0 && T >= 3 && T <= 64 && d <= 16; }
+// the shapes of the 32-channel layout (gram_fast_wide.hip; RBF with SIGSVGD_FLAG_FP32_SWEEPS only: gram_route)
+bool fast_wide_supported(int T, int d, int n) { return n == 0 && T >= 3 && T <= 64 && d >= 17 && d <= 32; }
 
 namespace {
 // geometry of a GRADIENT launch (the forward-only launches keep no partial sums): rows per tile, workgroups a CU holds
@@ -54,7 +57,7 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
 {
     WsPlan w;
     const bool rbf = kind == SIGSVGD_STATIC_RBF;
-    w.fixed_windows = rbf && fixed_windows(T, want_grad) ? 1 : 0;
+    w.fixed_windows = rbf && d <= 16 && fixed_windows(T, want_grad) ? 1 : 0; // (the 32-channel kernels: general windows only)
     w.wave_balance = rbf && wave_balance(T, d, want_grad, sym) ? 1 : 0;
     w.half_offset = rbf && half_offset(T, d, want_grad, sym) ? 1 : 0;
     if (d <= 4) w.kflag = w.take(flag_area_bytes(A, B));
@@ -78,8 +81,9 @@ int run(const GramProblem &p, const WsPlan &w, bool sym, const TileMap &own, voi
     fill_sweep_args(a, p, w, base);
     a.tm = own;
     int tile_rows = 0;
-    rc = p.kind == SIGSVGD_STATIC_RBF ? dispatch_variant<0>(p, a, w, out != nullptr, sym, tile_rows)
-                                      : fast_radial_dispatch(p, a, w, out != nullptr, sym, tile_rows);
+    rc = p.kind != SIGSVGD_STATIC_RBF ? fast_radial_dispatch(p, a, w, out != nullptr, sym, tile_rows)
+         : p.d > 16                   ? fast_wide_dispatch(p, a, w, out != nullptr, sym, tile_rows)
+                                      : dispatch_variant<0>(p, a, w, out != nullptr, sym, tile_rows);
     if (rc) return rc;
     return finish_launch(p, w, base, sym, a.tm, tile_rows, out, out64);
 }

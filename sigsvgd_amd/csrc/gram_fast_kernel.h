@@ -1,6 +1,7 @@
 // gram_fast_kernel and what launches an instantiation of it: the argument structs, the sweep statements, the kernel template,
-// launch_grad / launch_variant / dispatch_variant.  Included by gram_fast.hip (RBF, RADIAL = 0: plans and entry points) and by
-// gram_fast_radial.hip (IMQ / rational quadratic, RADIAL = 1); no host state and no environment reads in here.
+// launch_grad / launch_variant / dispatch_variant.  Included by gram_fast.hip (RBF, RADIAL = 0: plans and entry points), by
+// gram_fast_radial.hip (IMQ / rational quadratic, RADIAL = 1) and by gram_fast_wide.hip (RBF, the 32-channel layout DPAD = 32 for
+// paths of 17 to 32 channels); no host state and no environment reads in here.
 //
 // Register-resident signature-kernel Gram forward/backward for the headline shapes:
 // dyadic order 0, path length T <= 64, RBF static kernel, second-order stencil.
@@ -530,7 +531,9 @@ using f32x2 = __attribute__((ext_vector_type(2))) float;
 
 __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_STRIDE + lane; }
 
-// LP: the last of the DPAD channels is padding (d == DPAD - 1, e.g. the 7-DoF arm at DPAD = 8): its FMA in the
+// DPAD: channels of the layout, 4, 8, 16 or 32 (d is zero-padded to it).  32 (gram_fast_wide.hip): 4-wave
+// workgroups at one wave per SIMD, phase 1 in two blocks of 16 channels, general windows only.
+// LP: the last of the DPAD channels is padding (d == DPAD - 1, e.g. the 7-DoF arm at DPAD = 8; DPAD = 4, 8 and 32): its FMA in the
 // static kernel and its travelling column sum are dropped.
 // RING: slots per lane = length of the column ring.  64 in general; 32 for paths of <= 32 points (T <= 32), where the
 // skewed phases 1 and 4 take 34 iterations instead of 66 and a wavefront solves TWO pairs at once: lanes 0..31 own the
@@ -552,8 +555,8 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // General windows only (no PFIX, no BAL); instantiated in gram_fast_radial.hip.
 template <int DPAD, int NW, bool GRAD, bool SYM, bool LP, int RING = 64, int PFIX = 0, int BAL = 0, int RADIAL = 0, int HALF = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
-    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : 2),
-    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 2) : ((DPAD <= 8) ? 3 : 2)))) void gram_fast_kernel(FastArgsOf<RADIAL> a)
+    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : ((DPAD <= 8) ? 3 : (DPAD <= 16) ? 2 : 1),
+    GRAD ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : (DPAD <= 16) ? 2 : 1) : ((DPAD <= 8) ? 3 : (DPAD <= 16) ? 2 : 1)))) void gram_fast_kernel(FastArgsOf<RADIAL> a)
 {
     constexpr int DC = LP ? DPAD - 1 : DPAD; // channels that can be non-zero
     constexpr int NT = NW * 64;
@@ -858,18 +861,49 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 const double *nbase = ynd + (RING - lrow);
                 // the y~ row of column t+1 is fetched while column t is computed (one s_waitcnt per
                 // column instead of one per ds_read, and the LDS latency is off the exp chain)
-                double ynx[DPAD], nnx;
+                // (32 channels: the row in two blocks of 16, see below -- a half row ahead)
+                constexpr int YPF = (DPAD > 16) ? DPAD / 2 : DPAD; // doubles of y~ fetched ahead
+                double ynx[YPF], nnx;
 #pragma unroll
-                for (int c = 0; c < DPAD; ++c) ynx[c] = ybase[c];
+                for (int c = 0; c < YPF; ++c) ynx[c] = ybase[c];
                 nnx = LP ? 0.0 : nbase[0];
 #pragma unroll
                 for (int t = 0; t < RING + 2; ++t) {
                     double g;
                     if (t < RING) {
+                        double e2;
+                        if constexpr (DPAD > 16) {
+                            // The 32-channel layout walks the dot product in two blocks of 16 channels: block 1 of column t is
+                            // fetched while block 0 is multiplied, block 0 of column t + 1 while block 1 is, so that 16 + 16
+                            // doubles of y~ are live beside the row's 32 of x~ -- the 16-channel kernel's figure -- instead of 32 + 32.
+                            constexpr int HB = DPAD / 2;
+                            double ycu[HB];
+#pragma unroll
+                            for (int c = 0; c < HB; ++c) ycu[c] = ynx[c];
+                            e2 = LP ? xn : xn + nnx;
+                            {
+                                const double *yr = ybase + t * YDS + HB;
+#pragma unroll
+                                for (int c = 0; c < HB; ++c) ynx[c] = yr[c];
+                                if (!LP && t < RING - 1) nnx = nbase[t + 1];
+                            }
+#pragma unroll
+                            for (int c = 0; c < HB; ++c) e2 = __builtin_fma(xs[c], ycu[c], e2);
+#pragma unroll
+                            for (int c = 0; c < HB; ++c) ycu[c] = ynx[c];
+                            if (t < RING - 1) {
+                                const double *yr = ybase + (t + 1) * YDS;
+#pragma unroll
+                                for (int c = 0; c < HB; ++c) ynx[c] = yr[c];
+                            }
+                            if (LP) e2 += ycu[HB - 1]; // LP: the row's last slot is the norm
+#pragma unroll
+                            for (int c = HB; c < DC; ++c) e2 = __builtin_fma(xs[c], ycu[c - HB], e2);
+                        } else {
                         double ycu[DPAD];
 #pragma unroll
                         for (int c = 0; c < DPAD; ++c) ycu[c] = ynx[c];
-                        double e2 = LP ? xn + ycu[DPAD - 1] : xn + nnx; // LP: the row's last slot is the norm
+                        e2 = LP ? xn + ycu[DPAD - 1] : xn + nnx; // LP: the row's last slot is the norm
                         if (t < RING - 1) {
                             const double *yr = ybase + (t + 1) * YDS;
 #pragma unroll
@@ -878,6 +912,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                         }
 #pragma unroll
                         for (int c = 0; c < DC; ++c) e2 = __builtin_fma(xs[c], ycu[c], e2);
+                        }
                         if constexpr (RADIAL) {
                             // e2 is s (rounding leaves it a few ulp below 0 for coincident points; a NaN stays one).  k_imq =
                             // (1 + s)^-1/2 and k_rq = k_imq^2; -phi' = k_imq^3 / 2 and k_imq^4; both carry the 1 / sqrt(12)
@@ -1171,6 +1206,31 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 f32x2 ynx[DPAD / 2];
 #pragma unroll
                 for (int c = 0; c < DPAD / 2; ++c) ynx[c] = f32x2{0.f, 0.f};
+                if constexpr (DPAD > 16) {
+                // The 32-channel layout: the same loop, stated a second time for its pragma alone.  66 iterations of 32 channels pass
+                // the size up to which `#pragma unroll` unrolls completely; left rolled, the slot index is a run-time value and the
+                // K slots live in scratch memory.  (Sharing the body through a lambda, or giving the loop below this pragma, changes
+                // the code of existing instantiations -- scripts/compare_device_code.py --, which stay as they are.)
+#pragma clang loop unroll(full)
+                for (int it = 0; it < RING + 2; ++it) {
+                    const float Sv = Svn, gcu = gnx;
+                    f32x2 ycu[DPAD / 2];
+#pragma unroll
+                    for (int c = 0; c < DPAD / 2; ++c) ycu[c] = ynx[c];
+                    if (it + 1 < RING + 2) { // next iteration's operands: slot (RING-2 - it) & RM, column slot (RING - it) & RM
+                        Svn = Ksl[(RING - 2 - it) & RM];
+                        if (it + 1 >= 2) {
+                            const int k2n = (RING - it) & RM;
+                            gnx = Gs_all[gsoff + k2n * GSS];
+                            const f32x2 *yr = reinterpret_cast<const f32x2 *>(yf + (yfrow + k2n) * YFS);
+#pragma unroll
+                            for (int c = 0; c < DPAD / 2; ++c) ynx[c] = yr[c];
+                        }
+                    }
+                    grad_part(Sv, it >= 2, gcu, ycu);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                } else {
 #pragma unroll
                 for (int it = 0; it < RING + 2; ++it) {
                     const float Sv = Svn, gcu = gnx;
@@ -1189,6 +1249,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                     }
                     grad_part(Sv, it >= 2, gcu, ycu);
                     __builtin_amdgcn_sched_barrier(0);
+                }
                 }
 
                 SIG_STAMP(4)
@@ -1293,6 +1354,8 @@ constexpr bool fast_has_half() { return SYM && LP && DPAD == 8; }
 
 // gram_fast_radial.hip: dispatch_variant<1> below (RADIAL = 1: IMQ and rational quadratic, a.kind), called from gram_fast.hip's `run`
 int fast_radial_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows);
+// gram_fast_wide.hip: the 32-channel layout (RBF, 17 <= d <= 32), called from gram_fast.hip's `run`
+int fast_wide_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad, bool sym, int &tile_rows);
 
 namespace {
 // a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths, or
@@ -1301,7 +1364,7 @@ namespace {
 template <int DPAD, int NW, bool SYM, bool LP, int RING, int RADIAL>
 void launch_grad(bool fix, bool bal, bool half, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
 {
-    if constexpr (RADIAL == 0 && RING == 64 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches)
+    if constexpr (RADIAL == 0 && RING == 64 && DPAD <= 16 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches; the 32-channel kernels: general windows only)
         if constexpr (fast_has_half<DPAD, SYM, LP>()) {
             if (fix && half) {
                 hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, 0, 0, 1>), grid, block, 0, stream, a);
@@ -1338,7 +1401,7 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
 #ifdef SIGSVGD_PHASE_STAMPS
     a.stamps = phase_stamps_begin(p.stream);
 #endif
-    const long long resident = (long long)ncu * (grad ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : (NW == 4 ? ((DPAD <= 8) ? 3 : 2) : 1)); // workgroups the chip holds at once (LDS / VGPR bound)
+    const long long resident = (long long)ncu * (grad ? ((RING == 32 && NW == 4 && DPAD <= 8) ? 3 : 1) : (NW == 4 ? ((DPAD <= 8) ? 3 : (DPAD <= 16) ? 2 : 1) : 1)); // workgroups the chip holds at once (LDS / VGPR bound)
     dim3 grid((unsigned)(total < resident ? total : resident), 1);
     dim3 block(NW * 64);
     if (grad) { // the reduction kernel re-derives the segments from this geometry: it must be the one the workspace was cut for
@@ -1349,7 +1412,7 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
             return SIGSVGD_E_BADARG;
         }
     }
-    constexpr bool HAS_LP = DPAD <= 8; // the d == DPAD - 1 instantiations exist for the 4- and 8-channel layouts
+    constexpr bool HAS_LP = DPAD <= 8 || DPAD == 32; // the d == DPAD - 1 instantiations exist for the 4-, 8- and 32-channel layouts
     const bool lp = HAS_LP && grad && p.d == DPAD - 1;
     FastArgsOf<RADIAL> ka{}; // the kernel's arguments: `a`, and for the radial kinds the kind
     static_cast<FastArgs &>(ka) = a;

@@ -432,6 +432,7 @@ int generic_repair_launch(const GramProblem &p, const unsigned char *flags, bool
 
 // register-resident fast path (n == 0, T <= 64) -- gram_fast.hip (kernel: gram_fast_kernel.h); off / stride / fold: the row tiles a partial solve owns
 bool fast_supported(int T, int d, int n);
+bool fast_wide_supported(int T, int d, int n); // 17 .. 32 channels: gram_fast_wide.hip, RBF with SIGSVGD_FLAG_FP32_SWEEPS only
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off = 0, int stride = 1, bool fold = false,
                  int kind = SIGSVGD_STATIC_RBF); // (IMQ / rational quadratic with SIGSVGD_FLAG_FP32_SWEEPS: general windows only)
 int fast_launch(const GramProblem &p);

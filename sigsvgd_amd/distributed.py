@@ -140,8 +140,9 @@ class ShardedSigSVGD:
     `last_route` names the last step's route ("partial", "rowwise" or "long_partial"); `route(X_shard)` answers it without a step.
     fp32_sweeps=True with static_kind 2 or 3 at order 0: the fused partial solve takes the step at
     3 <= T <= 64, d <= 16 (`ops.gram_sym_partial(..., static_kind=, fp32_sweeps=True)`: the register-resident kernel, each
-    unordered pair once, K within 1e-5 per entry instead of fp64 results), and the row-wise solve passes the flag too; with
-    any other kind it changes nothing.
+    unordered pair once, K within 1e-5 per entry instead of fp64 results), and the row-wise solve passes the flag too.  With RBF
+    at order 0 it sends the row-wise step of 17 <= d <= 32 channels, 3 <= T <= 64, to the register-resident kernel (section 5.25;
+    the partial solve stops at 16 channels); with any other kind it changes nothing.
 
     update: "manual" (X - lr * v, the reference's optimizer=None), "adagrad" (its adaptive_gradient=True) or "adam"
     (torch.optim.Adam with `betas`, `eps`; lr is its learning rate); mask: multiplies the velocity, broadcastable to the
@@ -209,7 +210,8 @@ class ShardedSigSVGD:
             rows_fn = self._rows_fused_or_long
         elif rows_fn is None and (self.dyadic_order != 0 or self.static_kind != _lib.STATIC_RBF):
             rows_fn = lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, self.dyadic_order, self.static_kind, **self._fp32_kw)
-        self.rows_fn = rows_fn or (lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h))
+        # (RBF at order 0: the flag changes a row-wise launch of 17 to 32 channels only)
+        self.rows_fn = rows_fn or (lambda Xs, Xf, inv_h: ops.gram_fwd_bwd(Xs, Xf, inv_h, **self._fp32_kw))
         self.rowwise = bool(rowwise)
         self.last_K_partial = None  # ALIASES the step's preallocated buffer: the next step() overwrites it (clone to keep it)
         self.last_K_rows = None

@@ -12,7 +12,8 @@ the library launches on the capturing stream, all buffers are static) and replay
 
 static_kind / fp32_sweeps: the built-in static kernel of the Gram launch and `ops.gram_fwd_bwd`'s opt-in to the fp32-sweep
 kernels for the IMQ and rational-quadratic kernels (`static_kind=_lib.STATIC_IMQ, fp32_sweeps=True`: the captured launch
-sequence is then the RBF one's; without the flag those kinds capture the coverage kernel's launches).
+sequence is then the RBF one's; without the flag those kinds capture the coverage kernel's launches) and for RBF particles of
+17 to 32 channels (order 0, T <= 64).
 normalize=True: the iteration runs on the normalised kernel K(x, y) / sqrt(K(x, x) K(y, y)) and its first-slot gradient
 (`ops.gram_fwd_bwd(..., normalized=True)`, SIGSVGD_FLAG_NORMALIZED_FUSED): the unflagged launch
 between a diagonal pass and two small kernels, all captured; the replayed step equals the eager iteration bit for bit.

@@ -151,8 +151,8 @@ _STATIC_BY_NAME = {"rbf": BatchGaussianKernel, "imq": BatchIMQKernel, "rq": Batc
 class SignatureKernel:
     """Signature kernel with a static kernel on path points; `depth` is the DYADIC ORDER of the PDE solver
     (not a truncation level).  static_kernel: None or "rbf" (the reference's RBF), "imq", "rq", "matern32", "matern52" (each built on
-    `bandwidth_fn`), or a static-kernel instance, used as it is.  fp32_sweeps: `SigKernel`'s (the IMQ and rational-quadratic kernels
-    on the register-resident fp32-sweep kernel at order 0, T <= 64).  exact_grad: `SigKernel`'s (every gradient the exact derivative of
+    `bandwidth_fn`), or a static-kernel instance, used as it is.  fp32_sweeps: `SigKernel`'s (the IMQ and rational-quadratic kernels,
+    and RBF paths of 17 to 32 channels, on the register-resident fp32-sweep kernel at order 0, T <= 64).  exact_grad: `SigKernel`'s (every gradient the exact derivative of
     the discrete kernel, on the long route).  normalize: `SigKernel`'s (the normalised kernel
     K(x, y) / sqrt(K(x, x) K(y, y)) from the long route's log-domain launches: `__call__` through `compute_Gram`, `gram_and_grad` --
     and with it `SVGD` and `ScoreEstimator` -- from one launch with SIGSVGD_FLAG_NORMALIZED).

@@ -195,7 +195,9 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     (`static_kind` 2, 3), which by default run on the fp64 coverage kernel and are held to fp64 results, take the
     register-resident fp32-sweep kernel RBF runs at dyadic order 0, 3 <= T <= 64, d <= 16 -- and with it the accuracy above
     (K per entry within 1e-5, the gradient within 1e-5 of its largest entry).  One-channel gradient launches stay on the
-    coverage kernel as for RBF; for every other kind, shape, order or solver the argument changes nothing.
+    coverage kernel as for RBF.  RBF paths of 17 <= d <= 32 channels at order 0, 3 <= T <= 64, which by
+    default run on the coverage kernel, take the same kernel's 32-channel layout at the same accuracy.  For every other kind,
+    shape, order or solver the argument changes nothing.
     `check_regime` and `stored_forward` are accepted for callers written against earlier versions (when long paths
     could run on a kernel that regenerated the forward solution and declined rough pairs) and have no effect."""
     dev = _require_gpu(X, Y, grad_out)

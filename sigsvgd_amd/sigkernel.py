@@ -803,7 +803,8 @@ class SigKernel:
 
     fp32_sweeps=True: `IMQStaticKernel` and `RationalQuadraticKernel` Gram launches at dyadic order 0,
     3 <= T <= 64, d <= 16 run on the register-resident fp32-sweep kernel RBF runs there (K per entry within 1e-5, the gradient
-    within 1e-5 of its largest entry) instead of the fp64 coverage kernel; everything else is unchanged.  It reaches the fused
+    within 1e-5 of its largest entry) instead of the fp64 coverage kernel, and so do `RBFKernel` launches of 17 <= d <= 32
+    channels at order 0, 3 <= T <= 64 (section 5.25; RBF at d <= 16 runs there by default); everything else is unchanged.  It reaches the fused
     Gram launches only: the long route, the paired route of `compute_kernel` and a learned sigma (a `sigma` tensor that requires
     grad takes the long route's bandwidth launch, section 5.16) ignore it.
 
