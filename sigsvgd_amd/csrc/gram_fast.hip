@@ -51,7 +51,55 @@ static bool half_offset(int T, int d, int want_grad, bool sym)
     return !(e && e[0] == 'o' && e[1] == 'f');
 }
 
-// [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab]
+// ... and there the twin that stages every column from its image (the kernel's HALF = 2), unless SIGSVGD_COLUMN_IMAGES=off (read
+// per launch, like the three above); the plan records the choice, so the workspace query and the launch agree
+static bool column_images()
+{
+    const char *e = getenv("SIGSVGD_COLUMN_IMAGES");
+    return !(e && e[0] == 'o' && e[1] == 'f');
+}
+
+// ---- column images of the HALF = 2 twin (gram_fast_kernel.h, IMG) -----------------------------------------------------------
+constexpr int COLIMG_DOUBLES = 64 * 8 + 8; // [64][8] as the kernel's yd holds a column, then the 8 doubles of its yref
+inline size_t colimg_bytes(int B) { return ((size_t)B * COLIMG_DOUBLES * sizeof(double) + 255) & ~(size_t)255; }
+
+// The scaled norm of a point, nscale * |y~_t|^2, as stage_store of gram_fast_kernel forms it in lane c == 0 of the point's eight
+// lanes -- the number phase 1 adds to every exponent of the column, so its bits are the result's bits.  There the source reads
+// `s = v * v * nscale; s += shfl_xor(s, 1); s += shfl_xor(s, 2); s += shfl_xor(s, 4)` and hipcc contracts the first level: the
+// lane's own product enters as a fused multiply-add, the neighbour's arrives rounded.  Stated here operation by operation.
+__device__ __forceinline__ double column_norm(double v, double nscale)
+{
+#pragma clang fp contract(off)
+    const double vv = v * v;
+    const double s = vv * nscale;
+    double r = __builtin_fma(nscale, vv, __shfl_xor(s, 1, 64));
+    r = r + __shfl_xor(r, 2, 64);
+    r = r + __shfl_xor(r, 4, 64);
+    return r;
+}
+
+// One workgroup per column j, thread e = element (t = e / 8, c = e % 8) as in stage_store: channels 0..6 the point centred on the
+// column's first point (fp64 of the fp32 or fp64 input), channel 7 the scaled norm; then the first point itself (channel 7: 0).
+// Every double of the image is written: the workspace comes as it is.
+__global__ __launch_bounds__(512) void fast_column_image_kernel(const void *Y, double *img, int io64, double inv_h)
+{
+    constexpr int T = 64, d = 7, DPAD = 8;
+    const int j = blockIdx.x, e = threadIdx.x, t = e / DPAD, c = e % DPAD;
+    const double nscale = -inv_h * 1.4426950408889634074; // (the kernel's, RBF)
+    double sv = 0.0, sr = 0.0;
+    if (c < d) {
+        sv = load_any(Y, ((size_t)j * T + t) * d + c, io64);
+        sr = load_any(Y, (size_t)j * T * d + c, io64);
+    }
+    const double v = sv - sr;
+    const double s = column_norm(v, nscale);
+    double *o = img + (size_t)j * COLIMG_DOUBLES;
+    if (c < d) o[e] = v;
+    if (c == 0) o[e + DPAD - 1] = s;
+    if (t == 0) o[T * DPAD + c] = sr;
+}
+
+// [flags (the 4-channel instantiations, i.e. paths in one to four channels: see the kernel)][row segments][column slab][column images]
 // (kind: the IMQ and rational-quadratic launches have the general-window kernels only; the areas are kind-independent)
 WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, int stride, bool fold, int kind)
 {
@@ -66,6 +114,10 @@ WsPlan fast_plan(int A, int B, int T, int d, int want_grad, bool sym, int off, i
         w.rseg = w.take(w.g.rseg_bytes);
         w.cslab = w.take(w.g.cslab_bytes);
     }
+    w.column_images = w.half_offset && column_images() ? 1 : 0;
+    // (after the areas every fast launch has: their offsets stay.  The areas are kind-independent -- an IMQ / rational-quadratic
+    //  launch is sized like the RBF launch of its shape, tests/test_fp32_static_cabi.py -- so those take the area and leave it unused)
+    if (half_offset(T, d, want_grad, sym) && column_images()) w.colimg = w.take(colimg_bytes(B));
     return w;
 }
 
@@ -80,6 +132,13 @@ int run(const GramProblem &p, const WsPlan &w, bool sym, const TileMap &own, voi
     FastArgs a{};
     fill_sweep_args(a, p, w, base);
     a.tm = own;
+    if (w.column_images) { // the HALF = 2 twin reads the columns from their images: formed here, in front of it on the same stream
+        double *img = ws_at<double>(base, w.colimg);
+        hipLaunchKernelGGL(fast_column_image_kernel, dim3((unsigned)p.B), dim3(512), 0, p.stream, p.Y, img, a.io64, p.inv_h);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "launch fast_column_image_kernel");
+        a.Y = img;
+    }
     int tile_rows = 0;
     rc = p.kind != SIGSVGD_STATIC_RBF ? fast_radial_dispatch(p, a, w, out != nullptr, sym, tile_rows)
          : p.d > 16                   ? fast_wide_dispatch(p, a, w, out != nullptr, sym, tile_rows)

@@ -91,7 +91,7 @@ __device__ __forceinline__ void bal_end(bool first)
 constexpr int SIG_FAST_PHASES = 9; // stamp slots of the diagnostic build (launch_variant names them), per half of the workgroup
 
 struct FastArgs {
-    const void *X, *Y, *go;
+    const void *X, *Y, *go; // (HALF = 2: Y is the launch's column images, [B][64 * 8 + 8] doubles, not the paths)
     void *K;
     // Gradient partial sums leave the kernel through plain stores into slabs that the reduction kernel below adds up in
     // a FIXED order (no atomics: the result is bit-reproducible run to run, and nothing needs zeroing):
@@ -549,6 +549,8 @@ __device__ __forceinline__ int gs_index(int slot, int lane) { return slot * GS_S
 // BAL: 0, or the wave-balance schedule of the pair (see bal_top above); it adds the s_setprio and their branches, nothing else.
 // HALF: 0, or 1: the younger half of the workgroup runs half a pair behind the older one (see half_younger in the kernel; DESIGN.md
 // 5.1.2).  The symmetric 7-of-8-channel gradient kernel with fixed windows only; it has its own priority schedule (BAL = 0).
+// 2: the same, and the columns are staged from images that fast_column_image_kernel formed once per launch (see IMG in the kernel;
+// a value of HALF and not a parameter of its own, so that every other instantiation keeps its name).
 // RADIAL: 0 the RBF static kernel; 1 the inverse multiquadric or the rational quadratic, told apart by the wave-uniform a.kind
 // (DESIGN.md 5.18).  Phase 1 then evaluates k = phi(s), s = |x~ - y~|^2 inv_h clamped at 0, in place of the exponential, and the
 // G image holds -phi'(s) where RBF's holds k (for RBF the two are the same number); nothing after `rd = g - gprev` depends on it.
@@ -643,6 +645,22 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     struct RawElem { unsigned lo, hi; }; // the element's bits: an fp32 value in `lo`, an fp64 value in both words
     RawElem raw_v[EPT], raw_r[EPT];      // (RAW_STAGE)
     double stage_v[EPT], stage_r[EPT];
+    // Column images (HALF = 2; DESIGN.md 5.1, "Column images"): a launch stages 66,048 items at C4 and has 1,024 distinct columns,
+    // and what stage_store forms of a column -- the centred fp64 values, the scaled norm of every point (an xor tree of three
+    // dependent LDS round trips) and the first point -- is the same for every item of the column.  fast_column_image_kernel
+    // (gram_fast.hip) forms it once per launch, [64][8] doubles as yd holds them (channel 7: the norm) and the 8 doubles of yref;
+    // a.Y points at these images, stage_load is one 8-byte load per thread (eight threads: one more for yref) and stage_store
+    // converts for yf and stores.  Same operands, same operations, same bits as HALF = 1.
+    constexpr bool IMG = HALF == 2;
+    constexpr int IMG_DOUBLES = 64 * 8 + 8; // doubles of one column's image (4,160 B)
+    // -DSIG_EXPERIMENT_STAGE_COPY, timing experiment only (results are garbage; profiles/column_images_bound.txt): the bound that
+    // was taken before the images were built.  The HALF = 1 twin (SIGSVGD_COLUMN_IMAGES=off) stages a column as if its image lay
+    // ready in memory -- one 8-byte load per thread at the loop top, plain stores in the window, no subtraction, no norm tree.
+#ifdef SIG_EXPERIMENT_STAGE_COPY
+    constexpr bool STAGE_COPY = HALF == 1;
+#else
+    constexpr bool STAGE_COPY = false;
+#endif
     // (word by word, the high word under its own condition: one register per word on both paths, nothing to move or widen
     //  -- which would be a use -- after the load)
     auto load_raw = [&](const void *b, size_t idx) -> RawElem {
@@ -657,6 +675,32 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
         return io64 ? __hiloint2double((int)r.hi, (int)r.lo) : (double)__uint_as_float(r.lo);
     };
     auto stage_load = [&](int j) {
+        if constexpr (IMG) {
+            static_assert(EPT == 1 && NT == 64 * DPAD, "column images: thread e holds element e");
+            raw_v[0] = raw_r[0] = RawElem{0u, 0u};
+            if (j < a.B) {
+                const uint2 *img = reinterpret_cast<const uint2 *>(static_cast<const double *>(a.Y) + (size_t)j * IMG_DOUBLES);
+                const uint2 w = img[tid];
+                raw_v[0] = RawElem{w.x, w.y};
+                if (tid < DPAD) { // (the threads that store yref)
+                    const uint2 r = img[64 * DPAD + tid];
+                    raw_r[0] = RawElem{r.x, r.y};
+                }
+            }
+            return;
+        }
+        if constexpr (STAGE_COPY) {
+            // one 8-byte word of the column's own [T][d] fp32 block (224 of them; thread tid takes word (tid & 127) + 96 * bit 7 of
+            // tid < 224, so every address is inside the column whatever the launch's B)
+            static_assert(EPT == 1, "stage copy: one element per thread");
+            raw_v[0] = raw_r[0] = RawElem{0u, 0u};
+            if (j < a.B) {
+                const uint2 w = *reinterpret_cast<const uint2 *>(static_cast<const char *>(a.Y) + (size_t)j * (64 * 7 * 4) +
+                                                                 (size_t)(((tid & 127) + ((tid >> 7) & 1) * 96) * 8));
+                raw_v[0] = RawElem{w.x, w.y};
+            }
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const int e = tid + k * NT;
@@ -677,6 +721,31 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     // (RADIAL: the plain scale of s = |x~ - y~|^2 inv_h -- no log2 e, positive)
     const double nscale = RADIAL ? inv_h : -inv_h * 1.4426950408889634074; // exponent scale: exp(-d/h) = 2^(nscale*d)
     auto stage_store = [&](int buf) { // (buf: HALF only, the yf / yref buffer of the column; 0 otherwise)
+        if constexpr (IMG) {
+            const int t = tid / DPAD, c = tid % DPAD;
+            const double v = __hiloint2double((int)raw_v[0].hi, (int)raw_v[0].lo); // (c == DPAD - 1: the norm)
+            yd[t * YDS + c] = v;
+            yd[(t + RING) * YDS + c] = v;
+            const float vf = (c == DPAD - 1) ? 0.f : (float)v; // (the padded channel of yf holds 0, as stage_store leaves it)
+            float *yfb = yf + buf * YFB;
+            yfb[t * YFS + c] = vf;
+            yfb[(t + RING) * YFS + c] = vf;
+            if (t == 0) yref[buf * DPAD + c] = __hiloint2double((int)raw_r[0].hi, (int)raw_r[0].lo);
+            return;
+        }
+        if constexpr (STAGE_COPY) {
+            // the loaded bits, with the fp64 exponent forced to 2^-10 (one v_and_or_b32): every exponent of the static kernel then
+            // stays tame, K comes out near 1 and the fp64 re-sweep, which a grid of garbage would trigger, never fires
+            const int t = tid / DPAD, c = tid % DPAD;
+            const double v = __hiloint2double((int)((raw_v[0].hi & 0x800FFFFFu) | 0x3F500000u), (int)raw_v[0].lo);
+            yd[t * YDS + c] = v;
+            yd[(t + RING) * YDS + c] = v;
+            float *yfb = yf + buf * YFB;
+            yfb[t * YFS + c] = __uint_as_float(raw_v[0].lo);
+            yfb[(t + RING) * YFS + c] = __uint_as_float(raw_v[0].lo);
+            if (t == 0) yref[buf * DPAD + c] = v;
+            return;
+        }
 #pragma unroll
         for (int k = 0; k < EPT; ++k) {
             const int e = tid + k * NT;
@@ -1360,12 +1429,17 @@ int fast_wide_dispatch(const GramProblem &p, FastArgs &a, const WsPlan &w, bool 
 namespace {
 // a gradient instantiation, or (64-slot ring, `fix`: the plan's fixed_windows) its fixed-window twin for 64-point paths, or
 // (`bal`: the plan's wave_balance) that twin's twin with the wave-balance schedule, or (`half`: the plan's half_offset) its twin with
-// the halves of the workgroup half a pair apart; RADIAL has none of them
+// the halves of the workgroup half a pair apart, or (`img`: the plan's column_images) that twin's twin which stages the columns from
+// their images; RADIAL has none of them
 template <int DPAD, int NW, bool SYM, bool LP, int RING, int RADIAL>
-void launch_grad(bool fix, bool bal, bool half, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
+void launch_grad(bool fix, bool bal, bool half, bool img, dim3 grid, dim3 block, hipStream_t stream, const FastArgsOf<RADIAL> &a)
 {
     if constexpr (RADIAL == 0 && RING == 64 && DPAD <= 16 && NW == (DPAD <= 8 ? 8 : 4)) { // (the workgroup shapes dispatch_variant gives gradient launches; the 32-channel kernels: general windows only)
         if constexpr (fast_has_half<DPAD, SYM, LP>()) {
+            if (fix && half && img) { // (a.Y: the column images, see gram_fast.hip's `run`)
+                hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, 0, 0, 2>), grid, block, 0, stream, a);
+                return;
+            }
             if (fix && half) {
                 hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, true, SYM, LP, RING, 63, 0, 0, 1>), grid, block, 0, stream, a);
                 return;
@@ -1420,18 +1494,19 @@ int launch_variant(const GramProblem &p, FastArgs &a, const WsPlan &w, bool grad
     const bool fix = grad && w.fixed_windows && p.T == 64; // (the kernel's PFIX must be the launch's T - 1)
     const bool bal = fix && w.wave_balance;
     const bool half = fix && w.half_offset;
+    const bool img = half && w.column_images; // (gram_fast.hip's `run` has formed the images and pointed a.Y at them)
     if (!grad && sym)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, true, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (!grad)
         hipLaunchKernelGGL((gram_fast_kernel<DPAD, NW, false, false, false, RING, 0, 0, RADIAL>), grid, block, 0, p.stream, ka);
     else if (sym && lp)
-        launch_grad<DPAD, NW, true, HAS_LP, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, true, HAS_LP, RING, RADIAL>(fix, bal, half, img, grid, block, p.stream, ka);
     else if (sym)
-        launch_grad<DPAD, NW, true, false, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, true, false, RING, RADIAL>(fix, bal, half, img, grid, block, p.stream, ka);
     else if (lp)
-        launch_grad<DPAD, NW, false, HAS_LP, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, false, HAS_LP, RING, RADIAL>(fix, bal, half, img, grid, block, p.stream, ka);
     else
-        launch_grad<DPAD, NW, false, false, RING, RADIAL>(fix, bal, half, grid, block, p.stream, ka);
+        launch_grad<DPAD, NW, false, false, RING, RADIAL>(fix, bal, half, img, grid, block, p.stream, ka);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "launch gram_fast_kernel");
 #ifdef SIGSVGD_PHASE_STAMPS

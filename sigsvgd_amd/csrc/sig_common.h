@@ -359,12 +359,14 @@ struct WsPlan {
     GradGeom g{}; // geometry of the fp32-sweep kernels' launch (grad_reduce_launch re-derives its segments from it)
     WsArea kflag;        // [A][B] cancellation flags the fp64 pass reads
     WsArea rseg, cslab;  // row segments, column slab of the gradient
+    WsArea colimg;       // gram_fast.hip: [B] column images of the half-offset twin that stages from them (column_images below)
     WsArea crec, rowg, dcache; // gram_quad.hip: column records, row accumulators, increment scratch
     WsArea wsk;          // forward-solution scratch (gram_band.hip, gram_generic.hip)
     WsArea counter, partials, colslab; // gram_generic.hip: work counter, gradient partials, column-side slab
     int fixed_windows = 0; // gram_fast.hip: the launch runs the kernel whose sweeps have their EXEC windows as immediates
     int wave_balance = 0;  // gram_fast.hip: ... and, where that kernel has a wave-balance twin, the twin
     int half_offset = 0;   // gram_fast.hip: ... or, where it has one, the twin that runs the halves of a workgroup half a pair apart
+    int column_images = 0; // gram_fast.hip: ... and stages every column from its LDS image, formed once per launch into `colimg`
     size_t end = 0; // bytes of the areas
     WsArea take(size_t bytes) // the next area, behind the ones taken so far
     {
