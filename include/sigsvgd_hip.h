@@ -65,6 +65,11 @@
  *           in the increments, sum |K_fwd U D| / max(|K|, 0.1), exceeds 150 (forward-only launches: the bound
  *           sum |K_fwd D| max(grid maximum, 1) / max(|K|, 0.1) exceeds 300): there the fp32 STORAGE of the
  *           increments limits K whatever the precision of the sweeps.
+ *     The rule is defined once, in sigsvgd_amd/csrc/sweep_scaffold.h.  The exact pass ENFORCES the bound below for paths
+ *     in d <= 4 channels on the register-resident kernel (T <= 64) and d <= 3 on the quadrant, refined-grid and band
+ *     kernels; for d >= 5 the bound is measured, not enforced.  sigsvgd_gram_fwd and sigsvgd_gram_fwd_bwd apply (2) in
+ *     its two forms (the bound 300 forward-only, the condition number 150 with the gradient), so for a flagged pair the
+ *     two may return different bits, both within the bound.
  *     Measured bound (DESIGN.md sections 2, 3): every entry of K_out within 1e-5 RELATIVE of the fp64
  *     reference's (plain |K - K_ref| / |K_ref|, no floor) over the committed rough-path cases and 18,000
  *     random soak cases; unflagged pairs of the calibration study are within 2.5e-6.  (The 8- / 16-channel

@@ -21,8 +21,8 @@ SOURCES = ["capi.hip", "gram_generic.hip", "gram_fast.hip", "gram_fast_radial.hi
            "gram_long_exact_matern.hip", "gram_long_nantail.hip", "gram_long_nantail_matern.hip", "gram_long_logk.hip",
            "gram_long_logk_matern.hip", "gram_long_norm.hip", "gram_long_norm_matern.hip", "gram_norm_fused.hip"]
 # every header of csrc/ (a source includes headers only), then the public header, which stays the last element
-HEADERS = [os.path.join(_CSRC, h) for h in ("sig_common.h", "quad_sweeps.h", "ring_sweep.h", "long_static.h", "pair_bands.h",
-                                            "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h",
+HEADERS = [os.path.join(_CSRC, h) for h in ("sig_common.h", "sweep_scaffold.h", "quad_sweeps.h", "ring_sweep.h", "long_static.h",
+                                            "pair_bands.h", "gram_fast_kernel.h", "gram_long_kernels.h", "pair_bands_kernel.h",
                                             "sig_pde_kernel.h")] + \
           [os.path.join(_PKG, "..", "include", "sigsvgd_hip.h")]
 

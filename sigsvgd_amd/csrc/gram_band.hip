@@ -19,6 +19,7 @@
 // Reference semantics: sigkernel _SigKernelGram.forward/backward [RECALLED, SURVEY.md App. A]; static kernel
 // src/kernels/_traj_kernels.py:176-195; callers src/inference/score.py:68-69.
 #include "sig_common.h"
+#include "sweep_scaffold.h"
 
 namespace sigsvgd {
 
@@ -55,7 +56,8 @@ constexpr int BPAD = 64;   // boundary rows: entry e lives at [BPAD + e]; lanes 
 // range just waits).  A sweep takes ceil((P + 63) / BGS) + BLAG (nb - 1) phases instead of nb (P + 63) steps: 368 against 621
 // step times at the notebook's shape, 544 against 1,180 at the maze script's.  A workgroup is one pair: nb wavefronts.
 // Serial schedule (template parameter SER): see the kernel.  The arithmetic of every cell and the order of every sum (a coarse
-// cell's fine rows lie inside one band, since r divides 64) do not depend on the schedule: K is the same bit for bit.
+// cell's fine rows lie inside one band where r <= 64; at r = 128 -- T = 3, order 7 -- they span two bands, which both add into
+// the cell's block sum of the gradient pass) do not depend on the schedule: K is the same bit for bit.
 constexpr int BGS = 16; // steps per phase
 constexpr int BLAG = 5; // phases a band runs behind its neighbour: BLAG * BGS > 62 + BGS + 1 steps (see the refills in the kernel)
 constexpr int BPP = 1;  // pairs per workgroup of the band-parallel schedule (2: measured, slower -- twice the rounds at the reference's sizes)
@@ -269,18 +271,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
     const long long it0 = a.nitems * blockIdx.x / gridDim.x, it1 = a.nitems * (blockIdx.x + 1) / gridDim.x;
     int remaining = (int)(it1 - it0);
     long long item = it0;
-    int kq = 0, cstart = 0;
-    {
-        long long rem = it0;
-        for (;; ++kq) {
-            const int cn = a.B - (SYM ? a.tm.tile_of(kq) * nslots : 0);
-            if (rem < cn) break;
-            rem -= cn;
-        }
-        cstart = (int)rem;
-    }
+    const ItemSeek seek = item_seek<SYM>(a.tm, a.B, nslots, it0);
+    int kq = seek.kq, cstart = seek.cstart;
 #pragma unroll 1
     while (remaining > 0) {
+    // (tile_range of sweep_scaffold.h, kept as a copy: through the helper the four ordered gradient kernels of the serial schedule
+    //  differ and the notebook's shape loses, N = 100, T = 10, order 4, ordered Gram + gradient: 0.628-0.630 -> 0.674 ms)
     const int itile = a.tm.tile_of(kq);
     const int cfirst = SYM ? itile * nslots : 0;
     const int ncolr = min(a.B - cfirst - cstart, remaining);
@@ -295,6 +291,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
         int lanep = lane;
         asm volatile("" : "+v"(lanep));
         // ---- stage y_j (coarse points, centred on its first point) ------------------------------------------------
+        // (the same loop as in gram_dyad.hip, kept as a copy: through a stage_coarse_column helper three kernels here change their
+        //  VGPR count -- gram_bandp_kernel<8, true, false, false, false> 120 -> 121)
         __syncthreads();
         for (int e = tid; e < T * DPAD; e += NT) {
             const int t = e / DPAD, c = e % DPAD;
@@ -317,6 +315,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_s_waitcnt(0xc07f);
             // ---- coarse static kernel: lane m = point row m; G[m][b] in fp64, row differences, 4-corner increments --------
+            // (gram_dyad.hip's up to stride and offset, kept as a copy: the shared helper costs a dyad kernel a VGPR spill, see there)
             const int m = min(lanep, T - 1);
             double xs[DPAD], xn = 0.0;
 #pragma unroll
@@ -416,7 +415,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
             float km = misc[4];
             for (int b = 1; b < (SER ? 1 : nb); ++b) km = fmaxf(km, misc[4 + b]);
             const float kfv = (float)kfin;
-            const bool cancelled = kfv == kfv && km > (d == 1 ? 2.f : (d == 2 || !COMP) ? 4.f : 8.f) * fmaxf(fabsf(kfv), 0.1f);
+            // (kernels without the two-float add -- !COMP, band_comp -- flag from 4 where the rule has 8: open question in the header)
+            const bool cancelled = kfv == kfv && km > repair_ratio(d, COMP ? 8.f : 4.f) * repair_den(kfv);
             if (lanep == 0) {
                 store_any(a.K, (size_t)i * a.B + j, kfin, io64);
                 if (SYM && j != i) store_any(a.K, (size_t)j * a.B + i, kfin, io64);
@@ -546,22 +546,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
                     }
 #pragma unroll
                     for (int off = 1; off < 64; off <<= 1) cs += __shfl_xor(cs, off, 64);
-                    ill = kfin_keep == kfin_keep && cs * 3.46410161513775459f > 150.f * fmaxf(fabsf(kfin_keep), 0.1f);
+                    ill = kfin_keep == kfin_keep && repair_ill(cs, repair_den(kfin_keep));
                 }
                 if (lanep == 0) a.kflag[(size_t)i * a.B + j] = (canc_keep || ill) ? 1 : 0;
             }
             __syncthreads(); // the tables are staged; the increments (verdict) are not needed any more
             const int colwave = nb > 1 ? 1 : 0; // the wavefront of the column side (a one-band pair has one wavefront for both)
             if (valid && (SER || band0 == 0 || (SYM && band0 == colwave))) {
-                float w_ij = 1.f, w_ji = 1.f;
-                if (a.go) {
-                    w_ij = (float)load_any(a.go, (size_t)i * a.B + j, io64);
-                    if (SYM || a.symw) w_ji = (float)load_any(a.go, (size_t)j * a.B + i, io64);
-                    if (a.symw) { w_ij += w_ji; w_ji = w_ij; }
-                } else if (a.symw) {
-                    w_ij = 2.f; w_ji = 2.f;
-                }
-                if (SYM && j == i) w_ji = 0.f; // diagonal pair: first-slot derivative only
+                const PairWeights pw = pair_weights<true, SYM>(a.go, a.symw, a.B, i, j, io64);
+                const float w_ij = pw.ij, w_ji = pw.ji;
                 const float ns32 = (float)(-inv_h * 1.4426950408889634074);
                 const int me = min(lanep, T - 1);
                 float acc[DPAD];
@@ -633,7 +626,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(GRAD && SER
     }
     if (GRAD && row_ok && lead) { // the segment's row-side sums
         const int tot = T * d;
-        double *dstr = a.rseg + (((size_t)(kq + (int)blockIdx.x)) * nslots + slot) * (size_t)tot;
+        double *dstr = rseg_slot(a.rseg, kq, nslots, slot, tot);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_waitcnt(0xc07f);
         for (int e = lane; e < tot; e += 64) {

@@ -21,6 +21,7 @@
 // Reference semantics: sigkernel _SigKernelGram.forward/backward [RECALLED, SURVEY.md App. A]; static kernel
 // src/kernels/_traj_kernels.py:176-195; callers src/inference/score.py:68-69.
 #include "sig_common.h"
+#include "sweep_scaffold.h"
 
 namespace sigsvgd {
 
@@ -33,8 +34,8 @@ struct DyadArgs {
     TileMap tm;
     long long nitems;
     double inv_h;
-    unsigned char *kflag; // [A][B]: 1 where the fp32 solution of the pair cancelled (max |K_grid| > max(2, r max(|K|, 0.1)) with r = 4 (d <= 2) or 8, as in
-                          // gram_quad.hip): the launcher lets the coverage kernel solve those pairs' K again in fp64
+    unsigned char *kflag; // [A][B]: 1 where the repair rule of sweep_scaffold.h flags the pair: the launcher lets the coverage kernel
+                          // solve those pairs' K again in fp64
 };
 
 namespace {
@@ -47,7 +48,7 @@ constexpr int DHN = 136;  // hand-over rows: entries 0 .. 129 are read
 } // namespace
 
 // FEW (forward-only launches of paths in <= 3 channels, 8-channel layout): the forward steps also accumulate sum |K_fwd * D|,
-// the bound on the condition number of gram_fast.hip ("conditioning"); gradient launches take the condition number itself
+// the bound on the condition number of sweep_scaffold.h ("the repair rule"); gradient launches take the condition number itself
 // from the coarse tables (sum |S_coarse D_coarse|, one pass over (T-1)^2 entries per pair)
 template <int DPAD, bool GRAD, bool SYM, int DNW, bool FEW = false>
 __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW == 8 ? 2 : 1, 2))) void gram_dyad_kernel(DyadArgs a)
@@ -83,23 +84,13 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
     const long long it0 = a.nitems * blockIdx.x / gridDim.x, it1 = a.nitems * (blockIdx.x + 1) / gridDim.x;
     int remaining = (int)(it1 - it0);
     long long item = it0;
-    int kq = 0, cstart = 0;
-    {
-        long long rem = it0;
-        for (;; ++kq) {
-            const int cn = a.B - (SYM ? a.tm.tile_of(kq) * DNW : 0);
-            if (rem < cn) break;
-            rem -= cn;
-        }
-        cstart = (int)rem;
-    }
+    const ItemSeek seek = item_seek<SYM>(a.tm, a.B, DNW, it0);
+    int kq = seek.kq, cstart = seek.cstart;
 #pragma unroll 1
     while (remaining > 0) {
-    const int itile = a.tm.tile_of(kq);
-    const int cfirst = SYM ? itile * DNW : 0;
-    const int ncolr = min(a.B - cfirst - cstart, remaining);
-    const int i0 = itile * DNW, i = i0 + wave;
-    const int j0 = cfirst + cstart, j1 = j0 + ncolr;
+    const TileRange tr = tile_range<SYM>(a.tm, a.B, DNW, kq, cstart, remaining);
+    const int i = tr.i0 + wave;
+    const int j0 = tr.cfirst + cstart, j1 = j0 + tr.ncol;
     const bool row_ok = i < a.A;
     if (GRAD)
         for (int e = lane; e < DTMAX * DPAD; e += 64) wl.rowacc[e] = 0.f;
@@ -109,6 +100,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
         int lanep = lane;
         asm volatile("" : "+v"(lanep));
         // ---- stage y_j (coarse points, centred on its first point) ------------------------------------------------
+        // (the same loop as in gram_band.hip, kept as a copy: through a stage_coarse_column helper three band kernels change
+        //  their VGPR count -- gram_bandp_kernel<8, true, false, false, false> 120 -> 121)
         __syncthreads();
         for (int e = tid; e < T * DPAD; e += NT) {
             const int t = e / DPAD, c = e % DPAD;
@@ -125,6 +118,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
         __syncthreads();
 
         if (row_ok && (!SYM || j >= i)) {
+            // (pair_weights of sweep_scaffold.h, kept as a copy: through the helper the 8-wave 16-channel symmetric gradient kernel
+            //  spills 67 VGPRs instead of 68 -- resources must be equal -- profiles/sweep_scaffold_resources.txt)
             float w_ij = 1.f, w_ji = 1.f;
             if (GRAD) {
                 if (a.go) {
@@ -137,6 +132,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                 if (SYM && j == i) w_ji = 0.f; // diagonal pair: first-slot derivative only
             }
             // ---- coarse static kernel: lane m = point row m; G[m][b] in fp64, row differences, 4-corner increments --------
+            // (gram_band.hip's up to stride and offset of the table, kept as a copy: through a coarse_static_kernel helper
+            //  gram_dyad_kernel<8, true, false, 8> spills 35 VGPRs for 36, scratch 136 B for 140)
             float xf[DPAD]; // x~_m in fp32 for the coarse contraction
             {
                 const int m = min(lanep, T - 1);
@@ -168,6 +165,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
             __builtin_amdgcn_s_waitcnt(0xc07f);
 
             float Dsl[64], Ssl[64];
+            // (The chain state and the set-up of both sweeps are gram_quad.hip's, kept as a copy: as a QuadChain struct with
+            //  quad_visit_forward / quad_visit_reverse helpers -- six forms -- gram_dyad_kernel<16, true, true, 8> spills 67 VGPRs for 68.)
             float fc = 1.f, fuA = 1.f, fuB = 1.f, fV = 0.f;
             float svc = 1.f, svA = 1.f, svB = 1.f, svV = 0.f;
             int fwd_prev = -1;
@@ -178,30 +177,12 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
             float cnd = 0.f;  // FEW: this lane's share of sum |K_fwd * gamma|
             float kfin_keep = 0.f;
             bool canc_keep = false;
-            // visit list, 8 bits per visit: band | half << 1 | reverse << 2 | leave K[64][.] << 3
-            unsigned long long vis = 0;
-            int nv = 0;
-            auto add = [&](int b, int h, int r, int hk) {
-                if ((b ? nrows1 : 64) > 0 && (h ? nrows1 : 64) > 0) {
-                    vis |= (unsigned long long)(b | (h << 1) | (r << 2) | (hk << 3)) << (8 * nv);
-                    ++nv;
-                }
-            };
-            if (GRAD) {
-                if (nrows1 > 0) { // band 0 forward (leaves K[64][.]), band 1, then band 0 again (re-swept: see gram_quad.hip)
-                    add(0, 0, 0, 1); add(0, 1, 0, 1); add(1, 0, 0, 0); add(1, 1, 1, 0);
-                    add(1, 0, 1, 0); add(0, 1, 1, 0); add(0, 0, 1, 0);
-                } else {
-                    add(0, 0, 1, 0);
-                }
-            } else {
-                add(0, 0, 0, 1); add(0, 1, 0, 1); add(1, 0, 0, 0); add(1, 1, 0, 0);
-            }
+            const QuadVisits qv = quad_visit_list(GRAD, nrows1, 0, 0); // (quad_sweeps.h; none of gram_quad.hip's scratch bits)
             const int b_last = nrows1 > 0 ? 1 : 0, h_last = nrows1 > 0 ? 1 : 0;
 
 #pragma unroll 1
-            for (int v = 0; v < nv; ++v) {
-                const int code = (int)((vis >> (8 * v)) & 255);
+            for (int v = 0; v < qv.nv; ++v) {
+                const int code = (int)((qv.vis >> (8 * v)) & 255);
                 const int b = code & 1, h = (code >> 1) & 1;
                 const bool rev = (code & 4) != 0, leave_k = (code & 8) != 0;
                 const int nrows = b ? nrows1 : 64, ncols = h ? nrows1 : 64;
@@ -270,11 +251,11 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                     // value 1 to K = 0.18 therefore came out 1.7e-5 off (soak of round 4, case 504: T = 3, order 6, d = 2): at order
                     // >= 5 every pair whose grid maximum exceeds 1.5 max(|K|, 0.1) goes to the fp64 pass, and below that order the
                     // round-3 ratios apply WITHOUT the floor "grid maximum > 2" (the boundary value alone is a maximum of 1).
-                    const float kden = fmaxf(fabsf(kfin), 0.1f);
-                    bool fl = kmax > (n >= 5 ? 1.5f : (d == 1 ? 2.f : d == 2 ? 4.f : 8.f)) * kden;
-                    if constexpr (FEW) { // conditioning bound of a forward-only launch (gram_fast.hip); sqrt(12) gamma = the fine increment
+                    const float kden = repair_den(kfin);
+                    bool fl = kmax > (n >= 5 ? 1.5f : repair_ratio(d)) * kden; // (order >= 5: 1.5, rounding per row of shared increments, above)
+                    if constexpr (FEW) { // conditioning bound of a forward-only launch; sqrt(12) gamma = the fine increment
                         const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
-                        fl = fl || sds * 3.46410161513775459f * fmaxf(kmax, 1.f) > 300.f * kden;
+                        fl = fl || repair_fwd_bound(sds, kmax, kden);
                     }
                     const bool cancelled = __builtin_amdgcn_ballot_w64(kfin == kfin && fl) != 0;
                     if (lanep == nrows - 1) {
@@ -348,14 +329,14 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
                 __builtin_amdgcn_s_waitcnt(0xc07f);
                 // the pair's verdict for the exact fp64 pass: the grid maximum (above) or, in <= 3 channels, the condition number
                 // of K in the STORED increments -- one fp32 value per coarse cell, shared by its r^2 fine cells, so
-                // dK/dD_coarse = the block sum of S: c1 = sqrt(12) sum |Sc * Dc| / max(|K|, 0.1) > 150 (gram_fast.hip, "conditioning")
+                // dK/dD_coarse = the block sum of S: c1 = sqrt(12) sum |Sc * Dc| / max(|K|, 0.1) > 150 (sweep_scaffold.h, "the repair rule")
                 {
                     bool ill = false;
                     if (d <= 3) {
                         float cs = 0.f;
                         for (int e = lanep; e < Tm * Tm; e += 64) cs = __builtin_fmaf(fabsf((float)wl.Sc[e]), fabsf(wl.Dc[e]), cs);
                         const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cs)), 63));
-                        ill = kfin_keep == kfin_keep && c1 * 3.46410161513775459f > 150.f * fmaxf(fabsf(kfin_keep), 0.1f);
+                        ill = kfin_keep == kfin_keep && repair_ill(c1, repair_den(kfin_keep));
                     }
                     // (`lane`, not the per-pair opaque copy `lanep`: with `lanep == 0` hipcc reuses the mask it formed for the sweeps'
                     //  boundary lanes at the top of the pair, keeps it live across every sweep statement, and the 16-channel
@@ -445,6 +426,8 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
     }
     if (GRAD && row_ok) { // the segment's row-side sums
         const int tot = T * d;
+        // (rseg_slot of sweep_scaffold.h, kept as a copy: it renumbers the registers of all 8 gradient kernels, and with the
+        //  weights' copy above the unit is the parent's instruction for instruction)
         double *dstr = a.rseg + (((size_t)(kq + (int)blockIdx.x)) * DNW + wave) * (size_t)tot;
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -453,7 +436,7 @@ __global__ __launch_bounds__(DNW * 64) __attribute__((amdgpu_waves_per_eu(DNW ==
             dstr[e] = (double)wl.rowacc[m * DPAD + c];
         }
     }
-    remaining -= ncolr;
+    remaining -= tr.ncol;
     ++kq;
     cstart = 0;
     } // row tiles of the range

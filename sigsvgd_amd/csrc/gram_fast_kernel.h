@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "sig_common.h"
+#include "sweep_scaffold.h"
 
 namespace sigsvgd {
 
@@ -262,7 +263,7 @@ __constant__ const SweepMasks32 SWEEP_MASK32 = SweepMasks32();
 #define SIG_FWD_KSL(DIAG, K) "v_mov_b32 %[" K "], %[" DIAG "]\n\t"
 #define SIG_FWD_NOKSL "v_max_f32 %[km], |%[cur]|, %[km]\n\t" // (forward-only launches: the largest |K| of the grid, in the hazard slot)
 // few-channel forward-only launches also sum |K[l][q] * gamma[l][q]| over the cells: the forward half of the condition
-// estimate sum |S * D| / |K| that decides whether the pair goes to the exact fp64 pass (see the kernel, "conditioning")
+// estimate sum |S * D| / |K| that decides whether the pair goes to the exact fp64 pass (sweep_scaffold.h, "the repair rule")
 #define SIG_FWD_NOKSL_SD(DIAG, G) "v_max_f32 %[km], |%[cur]|, %[km]\n\tv_fma_f32 %[sd], |%[" DIAG "]|, |%[" G "]|, %[sd]\n\t"
 #define SIG_REV_STEP_X(DN, DDIAG, G, K, EXECW)                                                \
     "s_mov_b64 exec, -1\n\t"                                                                  \
@@ -787,24 +788,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
     const long long it0 = a.nitems * blockIdx.x / gridDim.x, it1 = a.nitems * (blockIdx.x + 1) / gridDim.x;
     int remaining = (int)(it1 - it0);
     long long item = it0; // index of the (row tile, column) item in work
-    int kq = 0, cstart = 0;
-    {
-        long long rem = it0;
-        for (;; ++kq) {
-            const int cn = a.B - (SYM ? a.tm.tile_of(kq) * NWR : 0);
-            if (rem < cn) break;
-            rem -= cn;
-        }
-        cstart = (int)rem;
-    }
+    const ItemSeek seek = item_seek<SYM>(a.tm, a.B, NWR, it0);
+    int kq = seek.kq, cstart = seek.cstart;
     bool staged = false;
     while (remaining > 0) {
-    const int itile = a.tm.tile_of(kq);
-    const int cfirst = SYM ? itile * NWR : 0; // first column that touches or crosses the diagonal
-    const int ncol = min(a.B - cfirst - cstart, remaining);
+    const TileRange tr = tile_range<SYM>(a.tm, a.B, NWR, kq, cstart, remaining);
+    const int cfirst = tr.cfirst, ncol = tr.ncol;
     const int jnext_tile = SYM ? a.tm.tile_of(kq + 1) * NWR : 0; // where the range goes on, on the next owned tile
     const bool more_tiles = remaining > ncol;
-    const int i0 = itile * NWR + wave * RPW;                // first (or only) row of this wavefront: scalar
+    const int i0 = tr.i0 + wave * RPW;                      // first (or only) row of this wavefront: scalar
     const int i = (RING == 32) ? i0 + (lane >> 5) : i0;     // the row this LANE works for
     const bool row_ok = i < a.A;
 #pragma unroll
@@ -1068,28 +1060,18 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 // d = 4 since a soak case with T = 33, d = 4 showed an entry of |K| ~ 0.005 off by 1.7e-5 RELATIVE after the fp64
                 // re-sweep on fp32 increments: tiny entries need the exact pass whatever their conditioning):
                 // the fp64 re-sweep below runs on fp32 increments, which is not enough where the discrete solution is
-                // ill-conditioned, so such pairs are flagged for the EXACT fp64 pass of the coverage kernel that follows the
-                // launch (fp64 static kernel, increments and sweeps: 6e-8).  Two rules, either one flags the pair:
-                //   * cancellation of magnitudes (round 3): the grid maximum above 4 max(|K|, 0.1) (2 in one channel) -- the fp32
-                //     sweeps resolve ~1e-6 of the largest value on the grid, the boundary value 1 included;
-                //   * CONDITIONING (round 4): K[P][P] as a function of the increments has the first-order condition number
-                //     c1 = sum |S * D| / |K| (S = K_fwd * U is dK/dD up to the stencil's second-order terms), and the fp32
-                //     STORAGE of the increments (6e-8 each) costs K up to 2.7e-8 c1 whatever the precision of the sweeps
-                //     (measured over 5,000 pairs of 25 roughness regimes, scripts/dev/cond_study.py: error <= 2.7e-8 c1, every
-                //     pair beyond 3e-6 has c1 > 230; smooth paths -- the bench inputs at d <= 3 -- stay below 100 at T <= 128).
-                //     Gradient launches have S in the slots after the reverse sweep and flag c1 > 150 there (below, "conditioning");
-                //     forward-only launches have no U and use the bound  sum |K_fwd * D| * max(grid maximum, 1) / |K| > 300
-                //     (>= c1 up to 15 % in every pair of the study, within a factor 7 of it for three channels; no pair beyond
-                //     2.5e-6 stays below it).
-                // A pair that came out NaN (a NaN in its inputs) is not marked: the coverage kernel's clamped exponential would
-                // turn it into a number.  Compiled into the 4-channel kernels only: in the 8-channel ones the ballot and the byte
+                // ill-conditioned, so such pairs are flagged for the exact fp64 pass by the repair rule of sweep_scaffold.h
+                // (gradient launches: the condition number, after the reverse sweep -- below, "conditioning").
+                // Compiled into the 4-channel kernels only: in the 8-channel ones the ballot and the byte
                 // store cost the headline launch 1.7 % (same-box A/B), and no pair of >= 4 channels needs it (worst entry 9e-7 in
                 // the roughest regimes of the study).
                 bool x0 = false, x1 = false;
                 if constexpr (DPAD == 4) {
                     if (a.kflag) {
-                        const float kden = fmaxf(fabsf(kf), 0.1f);
-                        bool fl = km > (d == 1 ? 2.f : 4.f) * kden;
+                        const float kden = repair_den(kf);
+                        // (the grid maximum above 4 max(|K|, 0.1), 2 in one channel, in this kernel's three and four channels too: its
+                        //  fp32 sweeps resolve ~1e-6 of the largest value on the grid, the boundary value 1 included)
+                        bool fl = km > repair_ratio(d, 4.f) * kden;
                         if constexpr (!GRAD) { // sum over the pair's lanes of sum_q |K[l][q] gamma[l][q]|, times sqrt(12): in units of D
                             const float wsum = wave_sum_dpp<RING == 64>(sd);
                             float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wsum), 63));
@@ -1097,7 +1079,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                                 const float s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wsum), 31));
                                 sds = (lane >> 5) ? sds : s0;
                             }
-                            fl = fl || sds * 3.46410161513775459f * fmaxf(km, 1.f) > 300.f * kden;
+                            fl = fl || repair_fwd_bound(sds, km, kden);
                         }
                         const unsigned long long xbal = __builtin_amdgcn_ballot_w64(mine && kf == kf && fl);
                         x0 = (RING == 64) ? xbal != 0 : (unsigned)xbal != 0u;
@@ -1114,7 +1096,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 kf_keep = kf;
                 x0_keep = x0;
                 x1_keep = x1;
-                if (__builtin_expect(__builtin_amdgcn_ballot_w64(mine && km > 4.f * fmaxf(fabsf(kf), 0.1f)) != 0, 0)) {
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(mine && km > kResweepRatio * repair_den(kf)) != 0, 0)) {
                     const double k64 = resweep_fwd_fp64<RING>(Dsl, P, lrow);
                     if (lrow == P - 1 && mine) { // (same lane, same addresses as the first store: the later one stands)
                         store_any(a.K, (size_t)i * a.B + j, k64, io64);
@@ -1134,6 +1116,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                 __builtin_amdgcn_s_setprio(1);
             }
             if (GRAD) {
+                // (pair_weights of sweep_scaffold.h is not used here: this kernel's weights are per LANE -- `mine`, `wcol`, two rows
+                //  per wavefront -- and the diagonal rule lives in `wcol`; the same holds for rseg_slot and the slot `rslot` below)
                 // weights of this lane's pair: row side w_ij, column side w_ji (per lane with two rows per wavefront,
                 // uniform otherwise; fetched here so that the loads are long back when the gradient pass needs them)
                 float w_ij = 1.f, w_ji = 1.f; // (per lane with two rows per wavefront; uniform otherwise)
@@ -1257,7 +1241,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(
                             const float c10 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wsum), 31));
                             c1 = (lane >> 5) ? c1 : c10;
                         }
-                        const bool ill = kf_keep == kf_keep && c1 * 3.46410161513775459f > 150.f * fmaxf(fabsf(kf_keep), 0.1f);
+                        const bool ill = kf_keep == kf_keep && repair_ill(c1, repair_den(kf_keep));
                         if (lrow == P - 1 && mine)
                             a.kflag[(size_t)i * a.B + j] = (((RING == 32 && (lane >> 5)) ? x1_keep : x0_keep) || ill) ? 1 : 0;
                     }

@@ -36,6 +36,7 @@
 // Reference semantics: sigkernel _SigKernelGram.forward/backward [RECALLED, SURVEY.md App. A];
 // static kernel src/kernels/_traj_kernels.py:176-195.
 #include "sig_common.h"
+#include "sweep_scaffold.h"
 
 namespace sigsvgd {
 
@@ -67,15 +68,12 @@ namespace {
 #define SIGQ_NW 8
 #endif
 constexpr int QNW = SIGQ_NW; // wavefronts (rows i) per workgroup
+// Which pairs are solved again in fp64: the repair rule of sweep_scaffold.h, as it stands there.  Paths in <= 3 channels are
+// also checked for their CONDITIONING in the increments: that, not the grid maximum, is what the 9 soak cases of round 3
+// beyond 1e-5 had in common.  (-DSIGQ_CANCEL_RATIO=x: a study's ratio for d >= 3 in place of the rule's.)
 #ifndef SIGQ_CANCEL_RATIO
 #define SIGQ_CANCEL_RATIO 8.f
 #endif
-// A pair is solved again in fp64 when max |K_grid| > ratio * max(|K[P][P]|, 0.1): the fp32 sweeps lose about 5e-7 (T = 64) ..
-// 2e-6 (T = 128) of the LARGEST value on the grid (the boundary value 1 included: round 3 also asked for a grid maximum above
-// 2, which left pairs that decay to K < 0.125 unchecked).  ratio = 8; 4 for paths in two channels and 2 in one.  Paths in <= 3
-// channels are also checked for their CONDITIONING in the increments (sum |S D| / |K|, gram_fast.hip): that, not the grid
-// maximum, is what the 9 soak cases of round 3 beyond 1e-5 had in common.
-constexpr float QUAD_CANCEL_RATIO = SIGQ_CANCEL_RATIO;
 // floats of a wavefront's column-side records of one pair: 4 quadrant passes + 2 halves of point row 64, each
 // [DPAD + 1 values][64 lanes], + 4 seam-column records of DPAD + 1 values (sized for DPAD = 16)
 constexpr int QREC = 6656;
@@ -140,7 +138,7 @@ __device__ __forceinline__ float q_add_ror1(float acc, float v)
 // EARLY: paths of <= 112 points (second band / half of <= 47 cells): the sweeps skip the steps beyond a quadrant's last
 // anti-diagonal (T=100, d=7: 2.51 -> 2.40 ms symmetric); longer paths keep the unconditional 128-step statements
 // FEW (forward-only launches of paths in <= 3 channels): the forward steps also accumulate sum |K_fwd * D|, the bound on the
-// condition number that sends ill-conditioned pairs to the exact fp64 pass (gram_fast.hip, "conditioning"; gradient launches
+// condition number that sends ill-conditioned pairs to the exact fp64 pass (sweep_scaffold.h, "the repair rule"; gradient launches
 // take the condition number itself from the S slots after each reverse sweep, a uniform branch on d)
 template <int DPAD, bool GRAD, bool SYM, bool ROWG = false, bool EARLY = false, bool FEW = false>
 __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))) void gram_quad_kernel(QuadArgs a)
@@ -208,28 +206,18 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
     const long long it0 = a.nitems * blockIdx.x / gridDim.x, it1 = a.nitems * (blockIdx.x + 1) / gridDim.x;
     int remaining = (int)(it1 - it0);
     long long item = it0; // index of the (row tile, column) item in work
-    int kq = 0, cstart = 0;
-    {
-        long long rem = it0;
-        for (;; ++kq) {
-            const int cn = a.B - (SYM ? a.tm.tile_of(kq) * QNW : 0);
-            if (rem < cn) break;
-            rem -= cn;
-        }
-        cstart = (int)rem;
-    }
+    const ItemSeek seek = item_seek<SYM>(a.tm, a.B, QNW, it0);
+    int kq = seek.kq, cstart = seek.cstart;
     // this wavefront's column-side records / global row accumulator (re-derived from scalars where they are used: as
     // values living across the pair they are spilled)
 #define SIGQ_CRW (a.crec + ((size_t)blockIdx.x * QNW + wave) * QREC)
 #define SIGQ_RGW (a.rowg + ((size_t)blockIdx.x * QNW + wave) * (128 * 16))
 #pragma unroll 1
     while (remaining > 0) {
-    const int itile = a.tm.tile_of(kq);
-    const int cfirst = SYM ? itile * QNW : 0; // first column that touches or crosses the diagonal
-    const int ncol = min(a.B - cfirst - cstart, remaining);
-    const int i0 = itile * QNW;
+    const TileRange tr = tile_range<SYM>(a.tm, a.B, QNW, kq, cstart, remaining);
+    const int i0 = tr.i0, ncol = tr.ncol;
     const int i = i0 + wave;
-    const int j0 = cfirst + cstart, j1 = j0 + ncol;
+    const int j0 = tr.cfirst + cstart, j1 = j0 + ncol;
     const bool row_ok = i < a.A;
     if (rowlds) {
         for (int e = lane; e < 128 * RS; e += 64) rowacc[e] = 0.f;
@@ -300,17 +288,8 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 
         SIG_STAMP(7)
         if (row_ok && (!SYM || j >= i)) {
-            float w_ij = 1.f, w_ji = 1.f; // row-side / column-side weights
-            if (GRAD) {
-                if (a.go) {
-                    w_ij = (float)load_any(a.go, (size_t)i * a.B + j, io64);
-                    if (SYM || a.symw) w_ji = (float)load_any(a.go, (size_t)j * a.B + i, io64);
-                    if (a.symw) { w_ij += w_ji; w_ji = w_ij; }
-                } else if (a.symw) {
-                    w_ij = 2.f; w_ji = 2.f;
-                }
-                if (SYM && j == i) w_ji = 0.f; // diagonal pair: first-slot derivative only
-            }
+            const PairWeights pw = pair_weights<GRAD, SYM>(a.go, a.symw, a.B, i, j, io64);
+            const float w_ij = pw.ij, w_ji = pw.ji; // row-side / column-side weights
 
             // ---- G row 64 (the row beyond band 0): differences along the row for lane 63 of band 0 ------------
             {
@@ -350,6 +329,8 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
 
             float Dsl[64]; // increments / sqrt(12) of the quadrant in work
             float Ssl[64]; // K_fwd, then S = K_fwd * U, of the quadrant in work
+            // (The chain state and the set-up of both sweeps below are also gram_dyad.hip's, kept as copies: as a QuadChain struct with
+            //  quad_visit_forward / quad_visit_reverse helpers gram_quad_kernel<16, true, true, false, true> spills 54 VGPRs for 55.)
             float fc = 1.f, fuA = 1.f, fuB = 1.f, fV = 0.f; // forward chain of the band in work (K, neighbours, V)
             float svc = 1.f, svA = 1.f, svB = 1.f, svV = 0.f; // the same at the end of quadrant (0,0)
             int fwd_prev = -1;                               // quadrant (b + 2 h) of the previous forward sweep
@@ -367,36 +348,18 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
             float kfin_keep = 0.f;
             bool canc_keep = false;
 
-            // visit list, 8 bits per visit: band | half << 1 | reverse << 2 | leave K[64][.] << 3 | increments << 4 (0 compute,
-            // 1 compute and keep in the launch's scratch, 2 take from there) | scratch slot << 6
-            unsigned long long vis = 0;
-            int nv = 0;
+            // visit list (quad_sweeps.h); the caller's bits: increments << 4 (0 compute, 1 compute and keep in the launch's scratch,
+            // 2 take from there) | scratch slot << 6.  The increments of the three quadrants that are visited twice make a round
+            // trip through L2 instead of being recomputed.
             const int keep = a.dcache ? 1 : 0, take = a.dcache ? 2 : 0; // (from the uniform kernel argument: the visit codes
                                                                         //  must stay scalar, the EXEC windows are fetched by them)
-            auto add = [&](int b, int h, int r, int hk, int dm, int ds) {
-                if ((b ? nrows1 : 64) > 0 && (h ? nrows1 : 64) > 0) {
-                    vis |= (unsigned long long)(b | (h << 1) | (r << 2) | (hk << 3) | (dm << 4) | (ds << 6)) << (8 * nv);
-                    ++nv;
-                }
-            };
-            if (GRAD) {
-                if (nrows1 > 0) {
-                    // band 0 forward (leaves K[64][.]; the lanes' state at the end of (0,0) is kept: sv*), band 1, then band 0
-                    // again, where (0,1) restarts from the kept state instead of a third pass over (0,0).  The increments of
-                    // the three quadrants that are visited twice make a round trip through L2 instead of being recomputed.
-                    add(0, 0, 0, 1, keep, 0); add(0, 1, 0, 1, keep, 1); add(1, 0, 0, 0, keep, 2); add(1, 1, 1, 0, 0, 0);
-                    add(1, 0, 1, 0, take, 2); add(0, 1, 1, 0, take, 1); add(0, 0, 1, 0, take, 0);
-                } else {
-                    add(0, 0, 1, 0, 0, 0);
-                }
-            } else {
-                add(0, 0, 0, 1, 0, 0); add(0, 1, 0, 1, 0, 0); add(1, 0, 0, 0, 0, 0); add(1, 1, 0, 0, 0, 0);
-            }
+            const QuadVisits qv = quad_visit_list(GRAD, nrows1, keep, take);
+            const int nv = qv.nv;
             const int b_last = nrows1 > 0 ? 1 : 0, h_last = nrows1 > 0 ? 1 : 0;
 
 #pragma unroll 1
             for (int v = 0; v < nv; ++v) {
-                const int code = (int)((vis >> (8 * v)) & 255);
+                const int code = (int)((qv.vis >> (8 * v)) & 255);
                 // a wave's priority falls as it advances through its visits: the wave that is behind on a SIMD gets the issue
                 // slots, the two stay closer and wait less at the pair's closing barrier (5.31 -> 5.15 ms symmetric,
                 // 6.67 -> 6.38 ordered at N=256, T=128, d=14)
@@ -554,15 +517,15 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
                 SIG_STAMP(2)
                 if (!kdone && b == b_last && h == h_last) { // K[P][P]: last value of the last row with cells
                     kdone = true;
-                    // a pair whose solution cancelled (see gram_fast.hip, resweep_fwd_fp64) is marked for the fp64 pass
+                    // a pair whose solution cancelled (sweep_scaffold.h, "the repair rule") is marked for the fp64 pass
                     const float kfin = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(fc), nrows - 1));
-                    const float kden = fmaxf(fabsf(kfin), 0.1f);
+                    const float kden = repair_den(kfin);
                     // (round 4: without the floor "grid maximum > 2" -- a pair that decays from the boundary value 1 to K < 1 / ratio
                     //  loses the same ~2e-6 of the LARGEST value on its grid as one that oscillates)
-                    bool fl = kmax > (d == 1 ? 2.f : d == 2 ? 4.f : QUAD_CANCEL_RATIO) * kden;
-                    if constexpr (FEW) { // conditioning bound of a forward-only launch: sum |K_fwd D| max(grid maximum, 1) > 300 max(|K|, 0.1)
+                    bool fl = kmax > repair_ratio(d, SIGQ_CANCEL_RATIO) * kden;
+                    if constexpr (FEW) { // conditioning bound of a forward-only launch
                         const float sds = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
-                        fl = fl || sds * 3.46410161513775459f * fmaxf(kmax, 1.f) > 300.f * kden;
+                        fl = fl || repair_fwd_bound(sds, kmax, kden);
                     }
                     const bool cancelled = __builtin_amdgcn_ballot_w64(kfin == kfin && fl) != 0;
                     if (lanep == nrows - 1) {
@@ -752,11 +715,11 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
             SIG_STAMP(0)
             if (GRAD && a.kflag) {
                 // the pair's verdict for the exact fp64 pass: cancellation of magnitudes (forward sweep) or, in <= 3 channels,
-                // the condition number c1 = sum |S D| / max(|K|, 0.1) > 150 (gram_fast.hip, "conditioning")
+                // the condition number c1 = sum |S D| / max(|K|, 0.1) (sweep_scaffold.h, "the repair rule")
                 bool ill = false;
                 if (DPAD == 8 && d <= 3) {
                     const float c1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wave_sum_dpp<true>(cnd)), 63));
-                    ill = kfin_keep == kfin_keep && c1 * 3.46410161513775459f > 150.f * fmaxf(fabsf(kfin_keep), 0.1f);
+                    ill = kfin_keep == kfin_keep && repair_ill(c1, repair_den(kfin_keep));
                 }
                 if (lanep == 0) a.kflag[(size_t)i * a.B + j] = (canc_keep || ill) ? 1 : 0;
             }
@@ -853,7 +816,7 @@ __global__ __launch_bounds__(QNW * 64) __attribute__((amdgpu_waves_per_eu(2, 2))
         int lf = lane;
         asm volatile("" : "+v"(lf));
         const int tot = T * d;
-        double *dstr = a.rseg + (((size_t)(kq + (int)blockIdx.x)) * QNW + wave) * (size_t)tot;
+        double *dstr = rseg_slot(a.rseg, kq, QNW, wave, tot);
         if (!rowlds) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wavefront's read-modify-writes have landed
         for (int e = lf; e < tot; e += 64) {
             const int m = e / d, c = e - m * d;

@@ -31,7 +31,7 @@
     "ds_write_b32 %[ha], %[cur]\n\t"                                                          \
     "v_add_u32 %[ha], %[hinc], %[ha]\n\t"
 #define SIG_Q_FWD(SH, KI, W, UP, DIAG, G, K, BNA, BNB) SIG_Q_FWD_X(SH, KI, W, UP, DIAG, G, K, BNA, "", BNB)
-// sum over the cells of |K[l][q] * gamma[l][q]|: the forward half of the condition estimate (gram_fast.hip, "conditioning")
+// sum over the cells of |K[l][q] * gamma[l][q]|: the forward half of the condition estimate (sweep_scaffold.h, "the repair rule")
 #define SIG_Q_SD(DIAG, G) "v_fma_f32 %[sd], |%[" DIAG "]|, |%[" G "]|, %[sd]\n\t"
 #define SIG_Q_REV(SH, KI, W, DN, DDIAG, G, K, BNA, BNB)                                       \
     SH " %[tm], %[" W "], %[" KI "]\n\t"                                                      \
@@ -201,4 +201,37 @@ __device__ __forceinline__ void quad_rev_all(float &cur, float &dnA, float &dnB,
 {
     if (!EARLY || (S0 & ~15) <= slast) quad_rev4<S0>(cur, dnA, dnB, V, D + (S0 & 63), S + (S0 & 63), wr, rows, hb, bm, ha, hinc, r3);
     if constexpr (S0 >= 4) quad_rev_all<S0 - 4, EARLY>(cur, dnA, dnB, V, D, S, wr, rows, hb, bm, ha, hinc, r3, slast);
+}
+
+// ---- a pair's walk over its quadrants, around the sweeps ---------------------------------------------------------------------
+// The grid of a pair is 2 x 2 quadrants: band b (cell rows 64 b ..), half h (cell columns 64 h ..); band 1 / half 1 have
+// nrows1 = P - 64 rows / columns (0: a single quadrant).  Visit list, 8 bits per visit: band | half << 1 | reverse << 2 |
+// leave K[64][.] << 3 | the caller's bits << 4 (gram_quad.hip: where the increments come from and their scratch slot; 0 in
+// gram_dyad.hip).  Gradient launches: band 0 forward (leaves K[64][.]; the lanes' state at the end of (0,0) is kept), band 1,
+// then band 0 again, where (0,1) restarts from the kept state instead of a third pass over (0,0).
+struct QuadVisits {
+    unsigned long long vis;
+    int nv;
+};
+__device__ __forceinline__ QuadVisits quad_visit_list(bool grad, int nrows1, int keep, int take)
+{
+    unsigned long long vis = 0;
+    int nv = 0;
+    auto add = [&](int b, int h, int r, int hk, int dm, int ds) {
+        if ((b ? nrows1 : 64) > 0 && (h ? nrows1 : 64) > 0) {
+            vis |= (unsigned long long)(b | (h << 1) | (r << 2) | (hk << 3) | (dm << 4) | (ds << 6)) << (8 * nv);
+            ++nv;
+        }
+    };
+    if (grad) {
+        if (nrows1 > 0) {
+            add(0, 0, 0, 1, keep, 0); add(0, 1, 0, 1, keep, 1); add(1, 0, 0, 0, keep, 2); add(1, 1, 1, 0, 0, 0);
+            add(1, 0, 1, 0, take, 2); add(0, 1, 1, 0, take, 1); add(0, 0, 1, 0, take, 0);
+        } else {
+            add(0, 0, 1, 0, 0, 0);
+        }
+    } else {
+        add(0, 0, 0, 1, 0, 0); add(0, 1, 0, 1, 0, 0); add(1, 0, 0, 0, 0, 0); add(1, 1, 0, 0, 0, 0);
+    }
+    return {vis, nv};
 }

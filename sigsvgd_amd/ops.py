@@ -190,7 +190,11 @@ def gram_fwd_bwd(X, Y, inv_h: float, dyadic_order: int = 0, static_kind: int = _
     Accuracy (include/sigsvgd_hip.h): every entry of K within 1e-5 of the fp64 reference's, plain |K - K_ref| / |K_ref| --
     the fp32-sweep kernels check every pair for cancellation and for its conditioning in the increments and hand the pairs
     that fail to an exact fp64 pass inside the same call; the gradient of such a pair keeps the fp32 solution (its error is
-    relative to the largest gradient entry of the launch).  `force_generic=True`: fp64 sweeps for K and the gradient alike.
+    relative to the largest gradient entry of the launch).  The exact pass enforces the bound for paths in d <= 4 channels on
+    the register-resident kernel (T <= 64) and d <= 3 on the quadrant, refined-grid and band kernels; for d >= 5 it is
+    measured, not enforced.  `gram_fwd` and `gram_fwd_bwd` test the conditioning differently (a bound of 300 forward-only,
+    the condition number against 150 with the gradient: csrc/sweep_scaffold.h), so the two may return different bits,
+    both inside the bound, for a flagged pair.  `force_generic=True`: fp64 sweeps for K and the gradient alike.
     `fp32_sweeps=True` (SIGSVGD_FLAG_FP32_SWEEPS): the IMQ and rational-quadratic static kernels
     (`static_kind` 2, 3), which by default run on the fp64 coverage kernel and are held to fp64 results, take the
     register-resident fp32-sweep kernel RBF runs at dyadic order 0, 3 <= T <= 64, d <= 16 -- and with it the accuracy above

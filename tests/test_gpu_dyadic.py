@@ -150,9 +150,21 @@ def test_band_kernels_agree(gpu, monkeypatch, T, n, d, sym):
     Same arithmetic per cell and the same order in every block sum: K and the flags of the exact pass are equal bit for bit;
     the gradients differ by the order of the fixed-order reduction only (tiles of up to 8 rows against tiles of one).
     SIGSVGD_BAND_MODE picks the schedule."""
+    _band_kernels_agree(gpu, monkeypatch, T, n, d, sym, 11)
+
+
+@pytest.mark.parametrize("T,n", [(3, 7), (5, 6)])
+@pytest.mark.parametrize("sym", [True, False])
+def test_band_kernels_agree_wide_blocks(gpu, monkeypatch, T, n, sym):
+    """the same at 64 and 128 fine cells per coarse cell, where a coarse cell's block sum spans a whole band or two (two
+    wavefronts of the band-parallel schedule add into one cell), in a launch of three rows and two channels"""
+    _band_kernels_agree(gpu, monkeypatch, T, n, 2, sym, 3)
+
+
+def _band_kernels_agree(gpu, monkeypatch, T, n, d, sym, A):
     from sigsvgd_amd import ops
 
-    A, B = 11, 11 if sym else 7
+    B = A if sym else 7
     X = walks(A, T, d, 21, 0.2)
     Y = X if sym else walks(B, T, d, 22, 0.2)
     go = np.random.default_rng(3).uniform(0.5, 1.5, (A, B)).astype(np.float32)
